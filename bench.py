@@ -3,27 +3,32 @@
 
 One "step" = one full shot of BASELINE.json configs[3] (256^3 constant velocity, 1000 time steps, O(8),
 fp32) through fwi_forward() on one MI355X.  With N > 1 (launched by torch.distributed.run, one process
-per GPU) every rank runs its own shot per step -- shots are independent -- and the K steps of the timed
-region form one gradient evaluation over N*K shots, closed by the path's one real exchange: ONE RCCL
-all-reduce of the model-sized gradient accumulator ("an RCCL all-reduce ... only for the final gradient
-sum", north_star), inside the timed region.  The reported value is the aggregate over ranks.
+per GPU) every rank runs its own shot per step -- shots are independent.  With `--mode gradient` the K steps of the
+timed region form one gradient evaluation over N*K shots, closed by the path's one real exchange: ONE RCCL all-reduce
+of the model-sized gradient accumulator ("an RCCL all-reduce ... only for the final gradient sum", north_star), inside
+the timed region.  The reported value is the aggregate over ranks.
 
 No torch in this process: the launcher only provides RANK / WORLD_SIZE / MASTER_*; the control plane
 (unique-id hand-off, barriers) is the package's stdlib TCP rendezvous, the data path is HIP + RCCL behind
 the C-ABI, and the max-over-ranks of the elapsed time goes through RCCL too (fwi_allreduce_f64_max).
 With N > 1 any RCCL failure is fatal (non-zero exit): there is no host-side fallback for the sum.
 
-At N = 1 the same invocation also runs short extra legs and reports them in the same JSON line (`legs`, and
-`roofline.hbm_regime`): the 512^3 forward run (working set past the 256 MiB Infinity Cache: the honest HBM
-number), the 256^3 gradient shot (forward + store, adjoint + imaging) in the standard and in the increment update
-form (the fp32 mode that meets north_star's 1e-5 end to end), configs[1] (2-D 1024^2 x 2000 steps) with the sponge
-and with the convolutional PML, and the 256^3 / npml 16 run with the convolutional PML.  `--leg NAME` runs one leg
-alone (what the rocprofv3 passes use).
+A plain run times the headline leg only.  With `--full`, at N = 1 the same invocation also runs short extra legs and
+reports them in the same JSON line (`legs`, `roofline.hbm_regime` and `cpu_baseline`): the 512^3 forward run
+(working set past the 256 MiB Infinity Cache: the honest HBM number), the 256^3 gradient shot (forward + store,
+adjoint + imaging) in the standard and in the increment update form (the fp32 mode that meets north_star's 1e-5 end
+to end), configs[1] (2-D 1024^2 x 2000 steps) with the sponge and with the convolutional PML, the 256^3 / npml 16 run
+with the convolutional PML, and the CPU baseline.  `--leg NAME` runs one leg alone (what the rocprofv3 passes use).
 
-For every N (also N = 1 under FWI_BENCH_FORCE_EXCHANGE=1) `legs.gradient` is the path's real multi-GPU pattern
-(configs[2] / configs[4]): per shot forward + store and adjoint + imaging into the device accumulator, then the ONE
-RCCL all-reduce of that accumulator, with a check in the line: g.g after the sum = N^2 x g.g before it (every rank
-runs the same shot, so the sum is N g).
+With `--full`, for every N (also N = 1 under FWI_BENCH_FORCE_EXCHANGE=1) `legs.gradient` is the path's real multi-GPU
+pattern (configs[2] / configs[4]): per shot forward + store and adjoint + imaging into the device accumulator, then
+the ONE RCCL all-reduce of that accumulator, with a check in the line: g.g after the sum = N^2 x g.g before it (every
+rank runs the same shot, so the sum is N g); N > 1 runs add the 2-D configuration beside the headline.
+
+`--dump-outputs DIR` writes what the headline's last timed step returned to its caller as DIR/<name>.npy: the
+seismograms (nt, nrec), and in gradient mode also the adjoint's source-side series and a fixed, seeded sample of the
+gradient accumulator (the sum over the --steps timed shots, as a caller reading the gradient after them gets it).
+The inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import faulthandler
@@ -92,8 +97,9 @@ def measured_traffic(leg):
 
 
 def run_leg(make_workload, device, steps, warmup, grad=False, engine_kw=None, exchange=None, barrier=None,
-            max_over_ranks=None, dtype=None):
-    """Time `steps` shots of a workload; returns (workload, per-shot wall s, kernel us/launch, info)."""
+            max_over_ranks=None, dtype=None, keep_outputs=False):
+    """Time `steps` shots of a workload; returns (workload, per-shot wall s, kernel us/launch, info).
+    `keep_outputs`: info["outputs"] holds what the last timed shot returned (see --dump-outputs)."""
     from full_waveform_inversion_amd import Engine
     w = make_workload()
     ft = np.float64 if dtype == "float64" else np.float32
@@ -107,12 +113,14 @@ def run_leg(make_workload, device, steps, warmup, grad=False, engine_kw=None, ex
         e.set_model(model)
         set_model_ms = 1e3 * (time.perf_counter() - t_sm)
         ex = exchange(e) if exchange else None
+        last = {}
 
         def step():
             d = e.forward(None, (w.src_idx[:1], wav), w.rec_idx, save=grad)
+            last["seismogram"] = d
             ms = e.last_loop_ms()
             if grad:
-                e.adjoint(d)  # residual = the data themselves: same work as any residual
+                last["adjoint"] = e.adjoint(d)  # residual = the data themselves: same work as any residual
                 ms += e.last_loop_ms()
             return ms
 
@@ -174,6 +182,12 @@ def run_leg(make_workload, device, steps, warmup, grad=False, engine_kw=None, ex
         if pl[0]:  # the context placed some of its arrays by measurement (3-D CPML / increment form; fwi_placement_info)
             info["placement"] = {"us_before": round(pl[0], 2), "us_after": round(pl[1], 2),
                                  "offsets_MiB": [s >> 20 for s in pl[2][:5]]}
+        if keep_outputs:  # untimed: the accumulated gradient is model-sized, so a fixed, seeded sample of it
+            if grad:
+                g = e.gradient().ravel()
+                n = min(g.size, 1 << 20)
+                last["gradient_sample"] = g[np.sort(np.random.default_rng(0).choice(g.size, n, replace=False))]
+            info["outputs"] = last
         return w, el, 1e3 * float(np.mean(loop_ms)) / (w.nt * sweeps), info
     finally:
         e.close()
@@ -208,11 +222,20 @@ def main():
                     help="headline leg: forward = the stencil run; gradient = forward(save) + adjoint(imaging) per step")
     ap.add_argument("--leg", default="all", choices=["all", "headline", "hbm", "gradient", "gradient_increment", "cfg2",
                                                      "cfg2_cpml", "cpml3d", "cpml3d_adjoint", "cpml512", "fp64", "point", "bf16"],
-                    help="all: headline + (at N = 1) the three extra legs; or one leg alone (profiling passes)")
+                    help="all: headline + (with --full) the extra legs; or one leg alone (profiling passes)")
     ap.add_argument("--leg-nt", type=int, default=0, help="time steps of a --leg run (0 = the leg's own)")
     ap.add_argument("--cpu-steps", type=int, default=200,
-                    help="time steps of the CPU baseline sample (200 of the 1000 steps, ~3 s on 16 cores); 0 = skip")
+                    help="time steps of the CPU baseline sample of --full (200 of the 1000 steps, ~3 s on 16 cores); "
+                         "0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the extra legs, the HBM-regime roofline and the CPU baseline (N = 1), "
+                         "the gradient all-reduce leg and the 2-D leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (in gradient mode "
+                         "the gradient sample is of the accumulator, i.e. summed over the --steps timed shots)")
     args = ap.parse_args()
+    if args.dump_outputs and args.leg not in ("all", "headline"):
+        ap.error("--dump-outputs writes the headline's outputs: use it with --leg all or headline")
 
     # one node, one process per GPU: the driver only supports dmabuf IPC, and the RCCL bootstrap of a
     # single-node job belongs on loopback (the container's hostname may not resolve)
@@ -278,7 +301,11 @@ def main():
             headline_workload, local, args.steps, args.warmup, grad=grad,
             engine_kw=dict(kernel=args.kernel, zchunk=args.zchunk, image_stride=S),
             exchange=exchange if multi else None, barrier=rdzv.barrier if rdzv else None,
-            max_over_ranks=max_over_ranks if multi else None)
+            max_over_ranks=max_over_ranks if multi else None, keep_outputs=bool(args.dump_outputs))
+        if rank == 0 and args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in info["outputs"].items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a))
         if rank == 0:
             npts = int(np.prod(w.shape))
             sweeps = 2 if grad else 1            # forward + adjoint sweep per shot
@@ -304,7 +331,9 @@ def main():
                                        "one rccl allreduce of the gradient accumulator after the K shots (timed)" if grad
                                        else "none in this forward-only leg (shots are independent; the slowest rank's "
                                             "time is taken with a 1-double rccl allreduce); the gradient all-reduce of "
-                                            "configs[2] / configs[4] is timed in legs.gradient"),
+                                            "configs[2] / configs[4] is timed in legs.gradient" +
+                                            ("" if args.full and args.leg == "all" and args.grid == 256
+                                             else " of a --full run, or by --mode gradient")),
                            "rccl_ranks": info["rccl_ranks"], "control_plane": "stdlib tcp rendezvous (no torch)"},
                 "roofline": roofline_entry(
                     "headline" if (args.grid == 256 and not grad) else "other", w, kern_us, bpu,
@@ -313,10 +342,10 @@ def main():
                     "wavefield working set 3 x %d MiB%s" % (
                         bpu, npts, w.nt * sweeps, npts * 4 >> 20,
                         " fits the 256 MiB Infinity Cache: the fraction of the 8 TB/s HBM peak is kept for "
-                        "continuity, the HBM-regime number is roofline.hbm_regime" if resident else "")),
+                        "continuity, the HBM-regime number is roofline.hbm_regime of a --full run at N = 1" if resident else "")),
             }
 
-    extra = world == 1 and rank == 0 and not grad and args.grid == 256
+    extra = args.full and world == 1 and rank == 0 and not grad and args.grid == 256
     legs = {}
     want = (lambda name: args.leg == name or (args.leg == "all" and extra))
 
@@ -363,7 +392,7 @@ def main():
         legs[name] = r
 
     # the gradient leg runs on every rank when there is an exchange to time (N > 1, or the forced rehearsal)
-    if args.leg == "gradient" or (args.leg == "all" and not grad and args.grid == 256 and (extra or multi)):
+    if args.leg == "gradient" or (args.leg == "all" and args.full and not grad and args.grid == 256 and (extra or multi)):
         gradient_leg("gradient", None, 22.0,
                      "256^3 gradient shot, STANDARD update form: forward + store (20 B/update), adjoint + paired "
                      "imaging (24 B/update); the forward-term store (%.1f GiB) streams through HBM",
@@ -495,7 +524,7 @@ def main():
     # Optional -- a failure here is recorded in the line, never allowed to cost the headline measurement.
     desync = False
     if multi and not grad and not os.environ.get("FWI_BENCH_NO_2D_SCALING") and (
-            (args.leg == "all" and args.grid == 256) or os.environ.get("FWI_BENCH_FORCE_2D_SCALING")):
+            (args.leg == "all" and args.full and args.grid == 256) or os.environ.get("FWI_BENCH_FORCE_2D_SCALING")):
         try:
             rdzv.set_timeout(30.0)
             def wl2():

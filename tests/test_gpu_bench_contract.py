@@ -1,5 +1,5 @@
-"""The bench line's contract (driver: one JSON line with metric / value / roofline / cpu_baseline ...), checked on a
-small grid so that it runs in seconds: `bench.py --leg headline` and one extra leg."""
+"""The bench line's contract (driver: one JSON line with metric / value / roofline ...; cpu_baseline and the extra legs
+with --full), checked on a small grid so that it runs in seconds: `bench.py --leg headline` and one extra leg."""
 import json
 import os
 import subprocess
@@ -33,6 +33,44 @@ def test_headline_line_has_the_contract_fields(gpu):
     assert r["bound"] == "infinity-cache-resident"  # a 64^3 working set certainly is
     # value = updates / wall time, consistent with ms_per_step
     assert abs(d["value"] - 64 ** 3 * 40 / (d["ms_per_step"] * 1e-3) / 1e9) < 0.02 * d["value"]
+
+
+def test_a_plain_run_times_the_headline_only_and_dumps_what_it_computed(gpu, tmp_path):
+    """Without --full the line carries the headline alone (no extra legs, no CPU baseline), and --dump-outputs writes
+    the last step's seismograms; the same arguments give the same outputs."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / ("run%d" % i)
+        d = _run("--steps", "3", "--warmup", "1", "--nt", "500", "--dump-outputs", str(out))
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and "legs" not in d and "cpu_baseline" not in d
+        assert "hbm_regime" not in d["roofline"]
+        assert abs(d["value"] - 256 ** 3 * 500 / (d["ms_per_step"] * 1e-3) / 1e9) < 0.02 * d["value"]
+        assert sorted(os.listdir(out)) == ["seismogram.npy"]
+        dumps.append(np.load(out / "seismogram.npy"))
+    s = dumps[0]
+    assert s.dtype == np.float32 and s.shape == (500, 256) and np.isfinite(s).all() and np.abs(s).max() > 0
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_a_gradient_run_dumps_seismograms_adjoint_and_a_gradient_sample(gpu, tmp_path):
+    """The gradient accumulator is reset before the timed loop and sums the timed shots only: with --steps 3 it holds
+    three times what --steps 1 leaves there, so --steps really is the number of timed steps."""
+    import numpy as np
+    got = {}
+    for k in (1, 3):
+        out = tmp_path / ("steps%d" % k)
+        d = _run("--mode", "gradient", "--grid", "64", "--nt", "200", "--steps", str(k), "--warmup", "1",
+                 "--dump-outputs", str(out))
+        assert d["steps"] == k
+        assert sorted(os.listdir(out)) == ["adjoint.npy", "gradient_sample.npy", "seismogram.npy"]
+        got[k] = [np.load(out / n) for n in ("seismogram.npy", "adjoint.npy", "gradient_sample.npy")]
+    s, a, g = got[1]
+    assert s.shape == (200, 256) and a.shape == (200, 1) and g.shape == (64 ** 3,)
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() and np.abs(x).max() > 0 for x in (s, a, g))
+    assert np.array_equal(got[3][0], s) and np.array_equal(got[3][1], a)   # the last step's seismograms / adjoint
+    g3 = got[3][2].astype(np.float64)
+    assert np.linalg.norm(g3 - 3 * g) <= 1e-5 * np.linalg.norm(3 * g)
 
 
 def test_an_extra_leg_alone_reports_its_roofline(gpu):
@@ -70,7 +108,8 @@ def test_the_multi_rank_path_as_the_driver_launches_it_with_one_rank(gpu):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["config"]["rccl_ranks"] == 1 and "rccl allreduce" in d["config"]["exchange"]
     assert d["value"] > 0
-    # the 2-D configuration rides along in N > 1 runs (control-plane barriers only); optional, so errors are recorded
+    # the 2-D configuration rides along in N > 1 --full runs, forced here (control-plane barriers only); optional, so
+    # errors are recorded
     leg = d["legs"]["cfg2"]
     assert "error" not in leg, leg
     assert leg["n_gpus"] == 1 and leg["kernel"] == "step2d_fused" and leg["Gpts_per_s"] > 50

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r02
 rm -rf $O; mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 cut -c1-400 $O/bench.json
 cd /tmp && export TMPDIR=/tmp
 prof() {  # name, rocprof args..., -- bench args

@@ -33,7 +33,7 @@ pmc_args_of() {  # shorter runs for the counter passes (every dispatch is serial
   esac
 }
 if [ $PART = all ] || [ $PART = 1 ]; then
-  (cd $R && python bench.py > $O/bench.json 2> $O/bench.err) || { tail -5 $O/bench.err; exit 1; }
+  (cd $R && python bench.py --full > $O/bench.json 2> $O/bench.err) || { tail -5 $O/bench.err; exit 1; }
   cut -c1-300 $O/bench.json
   for leg in $LEGS; do
     prof kt_$leg --kernel-trace --stats --output-format csv -d $O/kt_$leg -- python3 $R/bench.py $(args_of $leg) || exit 1
