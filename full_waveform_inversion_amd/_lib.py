@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FWI_HIP_LIB") or os.path.join(_HERE, "libfwi_hip.so")
 CSRC_DIR = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 F32, F64 = 0, 1
 KERNEL_AUTO, KERNEL_POINT, KERNEL_STREAM = 0, 1, 2
 WRT_VELOCITY, WRT_SLOWNESS2 = 0, 1
@@ -86,6 +86,12 @@ SIGNATURES = {
     "fwi_vec_clip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_set_model_vec": (C.c_int, [_P, _I32]),
     "fwi_gradient_vec": (C.c_int, [_P, _I32, _I32]),
+    "fwi_set_illumination": (C.c_int, [_P, _I32]),
+    "fwi_illumination": (C.c_int, [_P, _I32, _P]),
+    "fwi_illumination_vec": (C.c_int, [_P, _I32, _I32]),
+    "fwi_allreduce_illumination": (C.c_int, [_P]),
+    "fwi_vec_mul": (C.c_int, [_P, _I32, _I32]),
+    "fwi_vec_recip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_mc_score": (C.c_int, [_I32, _I32, _I32, _I32, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P,
                                C.POINTER(_D)]),
     "fwi_mc_forward": (C.c_int, [_I32, _I32, _I32, _I32, _I64, _P, _P, _P]),

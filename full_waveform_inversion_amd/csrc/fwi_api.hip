@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/fwi.h"
+#include "fwi_illum.h"
 #include "fwi_kernels.h"
 
 using namespace fwi;
@@ -117,7 +118,10 @@ struct fwi_ctx {
     int istride = 1;          // imaging stride: the forward term is stored / correlated every istride-th step
     void *logical = nullptr;  // nz x ny x nx staging array for host <-> compact copies when cx != nx
     void *g_acc = nullptr;    // compact gradient accumulator
-    void *g_out = nullptr;    // compact scratch for fwi_gradient
+    void *g_out = nullptr;    // compact scratch for fwi_gradient (and fwi_illumination)
+    // source-side illumination (fwi_set_illumination): compact accumulator of sum q^2 over the imaging steps of every
+    // fwi_adjoint(image) since the last fwi_gradient_reset; nullptr = disabled (the default: no launch, no memory)
+    void *h_acc = nullptr;
     double *red = nullptr;    // reduction scalars
 
     // host copies
@@ -1389,6 +1393,7 @@ struct Impl {
                 if ((rc = run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr,
                                     T(0), 1, qb)))
                     return rc;
+                if ((rc = illum_accumulate(ctx, q_store, cnt))) return rc;  // this segment's slots, before they are reused
                 if ((rc = run_fused(ctx, sw, spare, n0 + cnt - 1, -1, cnt, ctx->rec, amp, &ctx->src, series, rs, 2,
                                     qb)))
                     return rc;
@@ -1427,6 +1432,7 @@ struct Impl {
                 if ((rc = run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), qo,
                                     noq)))
                     return rc;
+                if ((rc = illum_accumulate(ctx, q_store, cnt))) return rc;  // slots 0 .. cnt - 1 (not the carry)
                 const int hi = n0 + cnt - 1;
                 plan(hi, n0, [&](int n) -> const T * {
                     if (n + 1 >= nt) return nullptr;
@@ -1480,9 +1486,40 @@ struct Impl {
             HIPCHK(ctx, launch_source_image<T>((const T *)ctx->series, (const T *)ctx->wav, (const int64_t *)ctx->src.cidx,
                                                (const T *)ctx->src.cq, (T *)ctx->g_acc, nt, ctx->nsrc, ctx->istride,
                                                (T)(1.0 / (double)rs), s));
+        if (image && K == 0) {  // the whole store: the ceil(nt / S) slots of this shot, once
+            if ((rc = illum_accumulate(ctx, q_store, (nt + ctx->istride - 1) / ctx->istride))) return rc;
+            if (ctx->h_acc && ctx->qbf16 && ctx->nsrc > 0)  // the source's exact share at its nodes (closed form)
+                HIPCHK(ctx, launch_illum_source_bf16((float *)ctx->h_acc, ctx->q_store, g.npts, (const float *)ctx->wav,
+                                                     (const int64_t *)ctx->src.cidx, (const float *)ctx->src.cq, nt,
+                                                     ctx->nsrc, ctx->istride, s));
+        }
         if ((rc = loop.end())) return rc;
         return download_samples(ctx, (adj_src_out && ctx->nsrc) ? adj_src_out : nullptr, ctx->series, nt, ctx->nsrc,
                                 ctx->src_sp, nullptr, nullptr);
+    }
+
+    // illumination accumulator += sum of the squares of `nslots` store slots (no-op while illumination is disabled)
+    static int illum_accumulate(fwi_ctx *ctx, const void *store, int nslots) {
+        if (!ctx->h_acc) return FWI_OK;
+        HIPCHK(ctx, launch_illum_accumulate<T>((T *)ctx->h_acc, store, ctx->gd.npts, nslots, ctx->qbf16 ? 1 : 0,
+                                               ctx->stream));
+        return FWI_OK;
+    }
+
+    // H_m = (S / dt^4) acc (the per-step factor of the gradient, S / dt^2, times the 1 / dt^2 of q ~ dt^2 d2u/dt2),
+    // H_c = H_m (2 / c^3)^2, into the compact device array `dev`
+    static int illumination_vec(fwi_ctx *ctx, int32_t wrt, void *dev) {
+        const double dt2 = ctx->cfg.dt * ctx->cfg.dt;
+        HIPCHK(ctx, launch_illum_finalize<T>(ctx->gd, (const T *)ctx->h_acc, (const T *)ctx->c_dev, (T *)dev,
+                                             (double)ctx->istride / (dt2 * dt2), wrt == FWI_WRT_VELOCITY, ctx->stream));
+        return FWI_OK;
+    }
+
+    static int illumination(fwi_ctx *ctx, int32_t wrt, T *out) {
+        int rc = illumination_vec(ctx, wrt, ctx->g_out);
+        if (rc || (rc = download_compact(ctx, out, ctx->g_out))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return FWI_OK;
     }
 
     static int gradient_vec(fwi_ctx *ctx, int32_t wrt, void *dev) {
@@ -1888,7 +1925,7 @@ void fwi_destroy(fwi_ctx *ctx) {
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
     void *ptrs[] = {ctx->u[0], ctx->u[1], ctx->C, ctx->c_dev, ctx->dz, ctx->dy, ctx->dx, ctx->q_store,
-                    ctx->g_acc, ctx->g_out, ctx->red, ctx->amp, ctx->series, ctx->wav, ctx->snap, ctx->fwd[0],
+                    ctx->g_acc, ctx->h_acc, ctx->g_out, ctx->red, ctx->amp, ctx->series, ctx->wav, ctx->snap, ctx->fwd[0],
                     ctx->fwd[1], ctx->fx[0], ctx->fx[1], ctx->fwx[0], ctx->fwx[1], ctx->logical, ctx->vf, ctx->fwv};
     for (fwi_ctx::PointSet *ps : {&ctx->src, &ctx->rec})
         for (void *p : {ps->pidx, ps->cidx, ps->cu, ps->cq, ps->s_start, ps->s_pidx, ps->s_cidx, ps->s_cu,
@@ -2051,6 +2088,7 @@ int fwi_gradient_reset(fwi_ctx *ctx) {
     if (!ctx) return FWI_EINVAL;
     (void)hipSetDevice(ctx->cfg.device);
     HIPCHK(ctx, hipMemsetAsync(ctx->g_acc, 0, (size_t)ctx->gd.npts * ctx->esize, ctx->stream));
+    if (ctx->h_acc) HIPCHK(ctx, hipMemsetAsync(ctx->h_acc, 0, (size_t)ctx->gd.npts * ctx->esize, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return FWI_OK;
 }
@@ -2061,11 +2099,16 @@ int fwi_gradient_add(fwi_ctx *dst, fwi_ctx *src) {
     if (dst->cfg.device != src->cfg.device || dst->cfg.dtype != src->cfg.dtype || dst->gd.npts != src->gd.npts ||
         dst->gd.nx != src->gd.nx || dst->gd.nz != src->gd.nz)
         return dst->fail(FWI_EINVAL, "fwi_gradient_add: contexts differ in device, dtype or shape");
+    if (!dst->h_acc != !src->h_acc)
+        return dst->fail(FWI_EINVAL, "fwi_gradient_add: illumination is enabled in one context only");
     (void)hipSetDevice(dst->cfg.device);
     HIPCHK(dst, hipStreamSynchronize(src->stream));  // src's adjoint sweeps are complete
     int rc = DISPATCH(dst, Impl<float>::vec_axpby(dst, dst->g_acc, 1.0, src->g_acc, 1.0),
                       Impl<double>::vec_axpby(dst, dst->g_acc, 1.0, src->g_acc, 1.0));
     if (rc) return rc;
+    if (dst->h_acc && (rc = DISPATCH(dst, Impl<float>::vec_axpby(dst, dst->h_acc, 1.0, src->h_acc, 1.0),
+                                     Impl<double>::vec_axpby(dst, dst->h_acc, 1.0, src->h_acc, 1.0))))
+        return rc;
     HIPCHK(dst, hipStreamSynchronize(dst->stream));
     return FWI_OK;
 }
@@ -2248,6 +2291,85 @@ int fwi_allreduce_gradient(fwi_ctx *ctx) {
                                ctx->cfg.dtype == FWI_F32 ? ncclFloat32 : ncclFloat64, ncclSum, ctx->comm,
                                ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return FWI_OK;
+}
+
+int fwi_set_illumination(fwi_ctx *ctx, int32_t on) {
+    if (!ctx) return FWI_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    const size_t bytes = (size_t)ctx->gd.npts * ctx->esize;
+    if (on && !ctx->h_acc) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        HIPCHK(ctx, hipMalloc(&ctx->h_acc, bytes));
+        hipError_t e = hipMemsetAsync(ctx->h_acc, 0, bytes, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(ctx->h_acc);
+            ctx->h_acc = nullptr;
+            return ctx->fail(FWI_EHIP, "fwi_set_illumination: %s", hipGetErrorString(e));
+        }
+    } else if (!on && ctx->h_acc) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // no sweep in flight still adds into it
+        void *p = ctx->h_acc;
+        ctx->h_acc = nullptr;
+        HIPCHK(ctx, hipFree(p));
+    }
+    return FWI_OK;
+}
+
+#define ILLUM_READABLE(ctx, who, wrt)                                                                              \
+    do {                                                                                                           \
+        if ((wrt) != FWI_WRT_VELOCITY && (wrt) != FWI_WRT_SLOWNESS2)                                               \
+            return (ctx)->fail(FWI_EINVAL, "%s: unknown parametrisation %d", who, (int)(wrt));                     \
+        if (!(ctx)->h_acc) return (ctx)->fail(FWI_ESTATE, "%s: illumination is disabled (fwi_set_illumination)", who); \
+        if (!(ctx)->have_model) return (ctx)->fail(FWI_ESTATE, "%s: no model set", who);                          \
+    } while (0)
+
+int fwi_illumination(fwi_ctx *ctx, int32_t wrt, void *out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!out) return ctx->fail(FWI_EINVAL, "fwi_illumination: null output");
+    ILLUM_READABLE(ctx, "fwi_illumination", wrt);
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, Impl<float>::illumination(ctx, wrt, (float *)out),
+                    Impl<double>::illumination(ctx, wrt, (double *)out));
+}
+
+int fwi_illumination_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, v, slot);
+    ILLUM_READABLE(ctx, "fwi_illumination_vec", wrt);
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, Impl<float>::illumination_vec(ctx, wrt, v), Impl<double>::illumination_vec(ctx, wrt, v));
+}
+
+int fwi_allreduce_illumination(fwi_ctx *ctx) {
+    if (!ctx) return FWI_EINVAL;
+    if (!ctx->comm) return ctx->fail(FWI_ESTATE, "fwi_allreduce_illumination: call fwi_comm_init first");
+    if (!ctx->h_acc) return ctx->fail(FWI_ESTATE, "fwi_allreduce_illumination: illumination is disabled");
+    (void)hipSetDevice(ctx->cfg.device);
+    NCCLCHK(ctx, ncclAllReduce(ctx->h_acc, ctx->h_acc, (size_t)ctx->gd.npts,
+                               ctx->cfg.dtype == FWI_F32 ? ncclFloat32 : ncclFloat64, ncclSum, ctx->comm,
+                               ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return FWI_OK;
+}
+
+int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vy, y);
+    VEC_OR_FAIL(ctx, vx, x);
+    (void)hipSetDevice(ctx->cfg.device);
+    HIPCHK(ctx, DISPATCH(ctx, launch_vec_mul<float>(ctx->gd, (float *)vy, (const float *)vx, ctx->stream),
+                         launch_vec_mul<double>(ctx->gd, (double *)vy, (const double *)vx, ctx->stream)));
+    return FWI_OK;
+}
+
+int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vy, y);
+    (void)hipSetDevice(ctx->cfg.device);
+    HIPCHK(ctx, DISPATCH(ctx, launch_vec_recip<float>(ctx->gd, (float *)vy, a, b, ctx->stream),
+                         launch_vec_recip<double>(ctx->gd, (double *)vy, a, b, ctx->stream)));
     return FWI_OK;
 }
 

@@ -46,11 +46,14 @@ class Engine:
     ``update_form="increment"`` carries the recursion as (u, v = u - u_prev): same mathematics, ~4x less fp32
     round-off growth, 25 % more traffic.  ``abc="cpml"`` replaces the sponge by a convolutional PML.
     ``store_dtype="bf16"`` halves the forward-term store of an fp32 engine.
+    ``illumination=True`` accumulates the source-side illumination (the pseudo-Hessian diagonal) beside the gradient:
+    :meth:`illumination`; off by default, when it costs nothing.
     """
 
     def __init__(self, shape, h, dt, nt_max, order=8, npml=0, sigma_max=None, dtype="float32",
                  device=0, kernel="auto", zchunk=0, ckpt_interval=0, image_stride=1, update_form="standard",
-                 abc="sponge", pml_alpha_max=0.0, store_dtype="native", launch_mode="auto"):
+                 abc="sponge", pml_alpha_max=0.0, store_dtype="native", launch_mode="auto",
+                 illumination=False):
         shape = tuple(int(s) for s in shape)
         if len(shape) not in (2, 3):
             raise ValueError("shape must be (nz, nx) or (nz, ny, nx)")
@@ -74,6 +77,7 @@ class Engine:
         # "graph": each sweep's time loop as one hipGraph; "auto": where that was measured to pay (fwi_config.launch_mode)
         self._launch_mode = _lib.LAUNCH_MODES[launch_mode]
         self.pml_alpha_max = float(pml_alpha_max)
+        self._illum = bool(illumination)
         self._lib = _lib.load()
         self._ctx = None
         self._nsrc = self._nrec = self._nt = 0
@@ -95,6 +99,8 @@ class Engine:
         ctx = C.c_void_p()
         _lib.check(None, self._lib.fwi_create(C.byref(cfg), C.byref(ctx)))
         self._ctx = ctx
+        if self._illum:
+            self._chk(self._lib.fwi_set_illumination(ctx, 1))
 
     def close(self):
         if self._ctx is not None:
@@ -236,6 +242,34 @@ class Engine:
         """This engine's gradient accumulator += ``other``'s (same shape, same GPU)."""
         self._chk(self._lib.fwi_gradient_add(self._ctx, other._ctx))
 
+    # -- source-side illumination (include/fwi.h fwi_set_illumination) ------------
+    @property
+    def illumination_enabled(self):
+        return self._illum
+
+    def set_illumination(self, on):
+        """Switch the illumination accumulator on (allocated and zeroed) or off (freed); takes effect with the next
+        adjoint sweep.  A context that does not exist yet gets it when it is created."""
+        self._illum = bool(on)
+        if self._ctx is not None:
+            self._chk(self._lib.fwi_set_illumination(self._ctx, int(self._illum)))
+
+    def illumination(self, wrt="velocity"):
+        """H summed over the adjoint sweeps since ``reset_gradient``: ``(S / dt^4) sum_n q^n(x)^2`` for
+        ``wrt="slowness2"``, times ``(2 / c^3)^2`` for ``wrt="velocity"``.  Raises while illumination is off."""
+        h = np.zeros(self.shape, self.dtype)
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        self._chk(self._lib.fwi_illumination(self._c, w, h.ctypes.data_as(C.c_void_p)))
+        return h
+
+    def illumination_vec(self, slot, wrt="velocity"):
+        """Vector ``slot`` := :meth:`illumination` on the device."""
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        self._chk(self._lib.fwi_illumination_vec(self._c, w, slot))
+
+    def allreduce_illumination(self):
+        self._chk(self._lib.fwi_allreduce_illumination(self._c))
+
     # -- reductions, exchange, measurement --------------------------------------
     def dot(self, a, b):
         a, b = self._host(a).ravel(), self._host(b).ravel()
@@ -305,6 +339,14 @@ class Engine:
         out = C.c_double(0.0)
         self._chk(self._lib.fwi_vec_absmax(self._c, x, C.byref(out)))
         return out.value
+
+    def vec_mul(self, y, x):
+        """y = x * y, elementwise, on the device."""
+        self._chk(self._lib.fwi_vec_mul(self._c, y, x))
+
+    def vec_recip(self, y, a=1.0, b=0.0):
+        """y = a / (y + b), elementwise, on the device."""
+        self._chk(self._lib.fwi_vec_recip(self._c, y, float(a), float(b)))
 
     def vec_clip(self, x, lo, hi):
         self._chk(self._lib.fwi_vec_clip(self._c, x, float(lo), float(hi)))

@@ -12,16 +12,18 @@ import os
 import numpy as np
 
 
-def save_state(path, it, x, f, g, S, Y, log, evals, history=None, bounds=None):
+def save_state(path, it, x, f, g, S, Y, log, evals, history=None, bounds=None, precond=None):
     """Optimiser state after iteration ``it`` (SURVEY.md s.5 "checkpoint / resume": "optimiser state save per L-BFGS
     iteration"): model, misfit, gradient, the curvature pairs oldest first, the log, and the settings a continuation
-    must share (``history``, ``bounds``).  Written to a temporary file and renamed, so an interrupted run never leaves
+    must share (``history``, ``bounds``, the diagonal preconditioner ``precond``).  Written to a temporary file and renamed, so an interrupted run never leaves
     a torn file behind.  In a multi-rank job only ONE rank should pass a path (every rank holds the same state)."""
     tmp = "%s.tmp.%d.npz" % (path, os.getpid())
     arrays = {"x": np.asarray(x), "g": np.asarray(g)}
     for i, (s, y) in enumerate(zip(S, Y)):
         arrays["s%d" % i] = np.asarray(s)
         arrays["y%d" % i] = np.asarray(y)
+    if precond is not None:
+        arrays["precond"] = np.asarray(precond)
     meta = {"history": None if history is None else int(history),
             "bounds": None if bounds is None else [float(bounds[0]), float(bounds[1])]}
     np.savez(tmp, it=np.int64(it), f=np.float64(f), evals=np.int64(evals), npairs=np.int64(len(S)),
@@ -31,19 +33,20 @@ def save_state(path, it, x, f, g, S, Y, log, evals, history=None, bounds=None):
 
 
 def load_state(path):
-    """The dict :func:`save_state` wrote: ``it, f, evals, x, g, S, Y, log`` (+ ``history``, ``bounds`` when the file
-    holds them)."""
+    """The dict :func:`save_state` wrote: ``it, f, evals, x, g, S, Y, log, precond`` (+ ``history``, ``bounds`` when
+    the file holds them; ``precond`` is None when the run had none)."""
     with np.load(path) as z:
         n = int(z["npairs"])
         st = {"it": int(z["it"]), "f": float(z["f"]), "evals": int(z["evals"]), "x": z["x"].copy(), "g": z["g"].copy(),
               "S": [z["s%d" % i].copy() for i in range(n)], "Y": [z["y%d" % i].copy() for i in range(n)],
-              "log": json.loads(bytes(z["log"]).decode())}
+              "log": json.loads(bytes(z["log"]).decode()),
+              "precond": z["precond"].copy() if "precond" in z.files else None}
         if "meta" in z.files:
             st.update(json.loads(bytes(z["meta"]).decode()))
         return st
 
 
-def _checked_resume(resume, history, bounds, shape=None):
+def _checked_resume(resume, history, bounds, shape=None, precond=None, check_precond=True):
     """Load and validate a state for continuation: the bit-for-bit promise holds only if the continuation runs with
     the settings of the run that wrote the file, so differing ``history`` / ``bounds`` (when the file records them)
     and arrays of the wrong shape are errors, not silent changes; more pairs than ``history`` are trimmed (oldest
@@ -56,11 +59,18 @@ def _checked_resume(resume, history, bounds, shape=None):
         b = None if bounds is None else [float(bounds[0]), float(bounds[1])]
         if st["bounds"] != b:
             raise ValueError("resume: the state was written with bounds=%r, this run has bounds=%r" % (st["bounds"], b))
+    sp = st.get("precond")
+    if check_precond:  # (precond: an array, or None for none)
+        if (sp is None) != (precond is None) or (sp is not None and not np.array_equal(np.asarray(sp), np.asarray(precond))):
+            raise ValueError("resume: the state was written with preconditioner %s, this run has %s"
+                             % ("None" if sp is None else "p", "None" if precond is None else "another p"))
+    elif sp is None:
+        raise ValueError("resume: this run wants a preconditioner, the state was written without one")
     x = np.asarray(st["x"])
     if shape is not None and tuple(x.shape) != tuple(shape):
         raise ValueError("resume: the state holds a model of shape %r, the engine's grid is %r" % (x.shape, tuple(shape)))
     for name, a in [("g", st["g"])] + [("s%d" % i, s) for i, s in enumerate(st["S"])] + \
-                   [("y%d" % i, y) for i, y in enumerate(st["Y"])]:
+                   [("y%d" % i, y) for i, y in enumerate(st["Y"])] + ([("precond", sp)] if sp is not None else []):
         if np.asarray(a).shape != x.shape:
             raise ValueError("resume: %s has shape %r, the model %r" % (name, np.asarray(a).shape, x.shape))
     if len(st["S"]) != len(st["Y"]):
@@ -74,7 +84,7 @@ def _search_failed(log):
 
 
 def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, c1=1e-4, max_ls=8,
-          gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None):
+          gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None, precond=None):
     """Minimise ``f`` given ``fg(x) -> (f, g)``.
 
     Line search: backtracking (safeguarded quadratic interpolation) until the Armijo condition holds; while no backtracking was needed and the slope
@@ -91,6 +101,13 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
     ``resume``: such a path (or the dict of :func:`load_state`): the run continues after the iteration it holds --
     ``x0`` is ignored and no misfit is re-evaluated -- and, ``fg`` being deterministic, reproduces the
     uninterrupted run bit for bit (``maxiter`` counts iterations of the whole run, not of this call).
+
+    ``precond``: a fixed diagonal preconditioner p > 0 (an array shaped like ``x``, or a callable ``precond(x, f, g)``
+    called once after the first evaluation, so that p can be built from that evaluation's illumination at no extra
+    cost; see ``shots.illumination_preconditioner``).  The initial inverse Hessian of every iteration becomes
+    ``gamma * diag(p)`` with ``gamma = s.y / (y.(p y))``; the first step (and a restart) is ``p g`` scaled so that
+    ``first_step`` bounds the largest change.  p is part of the checkpoint; resuming with another p is an error.
+    ``None`` leaves the iteration exactly as without this argument.
     """
     dot = dot or (lambda a, b: float(np.sum(np.multiply(a, b, dtype=np.float64))))  # no BLAS threads
     if int(history) < 1:
@@ -100,8 +117,12 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
     def project(x):
         return np.clip(x, lo, hi) if bounds is not None else x
 
+    pc = None if precond is None or callable(precond) else np.asarray(precond)
     if resume is not None:
-        st = _checked_resume(resume, history, bounds, None if x0 is None else np.shape(x0))
+        st = _checked_resume(resume, history, bounds, None if x0 is None else np.shape(x0), pc,
+                             check_precond=not callable(precond))
+        if callable(precond):
+            pc = np.asarray(st["precond"])
         x, f, g, S, Y = st["x"], st["f"], st["g"], list(st["S"]), list(st["Y"])
         log, evals, it0 = list(st["log"]), st["evals"], st["it"]
         if _search_failed(log):
@@ -112,8 +133,12 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
         _require_finite(f, float(np.abs(g).max()), dot(g, g), 0)
         S, Y, log = [], [], [{"iter": 0, "f": f, "evals": 1}]
         evals, it0 = 1, 0
+        if callable(precond):
+            pc = np.asarray(precond(x, f, g))
+        if pc is not None and not (pc.shape == np.shape(g) and np.all(pc > 0) and np.all(np.isfinite(pc))):
+            raise ValueError("precond must be finite, > 0 and shaped like the model")
         if checkpoint:
-            save_state(checkpoint, 0, x, f, g, S, Y, log, evals, history, bounds)
+            save_state(checkpoint, 0, x, f, g, S, Y, log, evals, history, bounds, pc)
     for it in range(it0 + 1, maxiter + 1):
         if not float(np.abs(g).max()) > gtol:
             break  # stationary (or projected onto a bound everywhere)
@@ -124,7 +149,13 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
             a = rho * dot(s, q)
             q -= a * y
             al.append((a, rho))
-        if S:
+        if pc is not None:  # initial inverse Hessian gamma diag(p)
+            q *= pc
+            if S:
+                q *= dot(S[-1], Y[-1]) / dot(Y[-1], pc * Y[-1])
+            else:
+                q *= (first_step if first_step is not None else 1.0) / float(np.abs(q).max())
+        elif S:
             q *= dot(S[-1], Y[-1]) / dot(Y[-1], Y[-1])
         else:
             gmax = float(np.abs(g).max())
@@ -136,7 +167,8 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
         gp = dot(g, p)
         if not gp < 0.0:  # not a descent direction: restart from steepest descent
             S, Y = [], []
-            p = -g * ((first_step if first_step is not None else 1.0) / float(np.abs(g).max()))
+            p = -g if pc is None else -(pc * g)
+            p = p * ((first_step if first_step is not None else 1.0) / float(np.abs(p).max()))
             gp = dot(g, p)
         t, best, shrunk = 1.0, None, False
         for _ in range(max_ls):
@@ -156,7 +188,7 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
         if best is None:
             log.append({"iter": it, "f": f, "evals": evals, "note": "line search failed"})
             if checkpoint:  # the terminal entry too: a resumed run must not repeat the failed search
-                save_state(checkpoint, it - 1, x, f, g, S, Y, log, evals, history, bounds)
+                save_state(checkpoint, it - 1, x, f, g, S, Y, log, evals, history, bounds, pc)
             break
         t, fn, xn, gn = best
         s, y = xn - x, gn - g
@@ -170,7 +202,7 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
         _require_finite(f, float(np.abs(g).max()), dot(g, g), it)
         log.append({"iter": it, "f": f, "evals": evals, "step": t})
         if checkpoint:
-            save_state(checkpoint, it, x, f, g, S, Y, log, evals, history, bounds)
+            save_state(checkpoint, it, x, f, g, S, Y, log, evals, history, bounds, pc)
         if callback:
             callback(it, x, f, g)
     return x, f, log
@@ -193,8 +225,13 @@ def _require_finite(f, gmax, gg, it):
                                  "check the time step against the CFL limit of the current model" % (it, f, gmax, gg))
 
 
+def lbfgs_device_slots(history=5):
+    """Vector slots :func:`lbfgs_device` uses for itself: a ``precond_slot`` must be this or higher."""
+    return 7 + 2 * (int(history) + 1)
+
+
 def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=None, c1=1e-4, max_ls=8,
-                 gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None):
+                 gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None, precond_slot=None):
     """The same iteration as :func:`lbfgs` with every model-sized vector resident on the GPU
     (``Engine.vec_*`` slots): per iteration only scalars cross PCIe.
 
@@ -205,6 +242,11 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
     ``checkpoint`` / ``resume``: as in :func:`lbfgs` (the state file is the same: a run may be saved by one and
     resumed by the other); saving downloads the model, the gradient and the curvature pairs once per iteration
     (2 + 2 x history model-sized arrays over PCIe: ~0.1 s at 256^3 against ~7 s of shots per evaluation).
+
+    ``precond_slot``: the vector slot (``>= lbfgs_device_slots(history)``; created here, zeroed) of the diagonal
+    preconditioner p of :func:`lbfgs`.  ``fg`` fills it during the first evaluation
+    (``shots.preconditioned_fg_device``); it stays fixed afterwards, is saved with the state and, on resume, is
+    restored from it before any evaluation.
     """
     m = int(history)
     if m < 1:
@@ -213,19 +255,28 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
     # m + 1 pair slots: the candidate pair is formed in a spare slot, so the oldest pair is evicted only
     # once the candidate has passed the curvature test
     S0, Y0 = 7, 7 + (m + 1)
-    engine.vec_create(7 + 2 * (m + 1))
+    nslots = lbfgs_device_slots(m)
+    PC = precond_slot
+    if PC is not None:
+        if int(PC) < nslots:
+            raise ValueError("precond_slot must be >= %d (the optimiser's own slots come first)" % nslots)
+        PC = int(PC)
+        nslots = PC + 1
+    engine.vec_create(nslots)
     pairs = []  # ring of (s_slot, y_slot), oldest first
     free = list(range(m + 1))
 
     def save(it, f, log, evals):
         save_state(checkpoint, it, engine.vec_download(X), f, engine.vec_download(G),
                    [engine.vec_download(s) for s, _ in pairs], [engine.vec_download(y) for _, y in pairs], log, evals,
-                   m, bounds)
+                   m, bounds, None if PC is None else engine.vec_download(PC))
 
     if resume is not None:
-        st = _checked_resume(resume, m, bounds, getattr(engine, "shape", None))
+        st = _checked_resume(resume, m, bounds, getattr(engine, "shape", None), check_precond=PC is None)
         if _search_failed(st["log"]):
             return np.asarray(st["x"]), st["f"], list(st["log"])
+        if PC is not None:
+            engine.vec_upload(PC, st["precond"])
         engine.vec_upload(X, st["x"])
         engine.vec_upload(G, st["g"])
         for s_h, y_h in list(zip(st["S"], st["Y"]))[-m:]:
@@ -240,6 +291,9 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
             engine.vec_clip(X, *bounds)
         f = fg(X, G)
         _require_finite(f, engine.vec_absmax(G), engine.vec_dot(G, G), 0)
+        if PC is not None and not engine.vec_absmax(PC) > 0.0:
+            raise ValueError("precond_slot %d is empty after the first evaluation: fg must fill it "
+                             "(shots.preconditioned_fg_device)" % PC)
         log = [{"iter": 0, "f": f, "evals": 1}]
         evals, it0 = 1, 0
         if checkpoint:
@@ -255,7 +309,16 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
             a = rho * engine.vec_dot(s, P)
             engine.vec_axpby(P, -a, y, 1.0)
             al.append((a, rho))
-        if pairs:
+        if PC is not None:  # initial inverse Hessian gamma diag(p); GN is free until the line search
+            engine.vec_mul(P, PC)
+            if pairs:
+                s, y = pairs[-1]
+                engine.vec_copy(GN, y)
+                engine.vec_mul(GN, PC)
+                engine.vec_axpby(P, 0.0, P, engine.vec_dot(s, y) / engine.vec_dot(y, GN))
+            else:
+                engine.vec_axpby(P, 0.0, P, (first_step if first_step is not None else 1.0) / engine.vec_absmax(P))
+        elif pairs:
             s, y = pairs[-1]
             engine.vec_axpby(P, 0.0, P, engine.vec_dot(s, y) / engine.vec_dot(y, y))
         else:
@@ -268,7 +331,10 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
             free += [s - S0 for s, _ in pairs]
             pairs = []
             engine.vec_copy(P, G)
-            engine.vec_axpby(P, 0.0, P, (first_step if first_step is not None else 1.0) / gmax)
+            if PC is not None:
+                engine.vec_mul(P, PC)
+            engine.vec_axpby(P, 0.0, P, (first_step if first_step is not None else 1.0)
+                             / (gmax if PC is None else engine.vec_absmax(P)))
             gp = -engine.vec_dot(G, P)
         t, best, shrunk = 1.0, None, False
         for _ in range(max_ls):  # the same search as lbfgs(): Armijo backtracking, Wolfe-curvature expansion

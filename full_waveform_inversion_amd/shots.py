@@ -93,6 +93,12 @@ class NoExchange:
     def reduce_device(self, engine, misfit):
         return misfit
 
+    def reduce_illumination(self, engine, wrt="velocity", slot=None):
+        """The illumination H (host array), or into the device vector ``slot`` (returns None)."""
+        if slot is not None:
+            return engine.illumination_vec(slot, wrt)
+        return engine.illumination(wrt)
+
 
 class RcclExchange:
     """Production exchange: RCCL all-reduce (over xGMI) of the device-side accumulators.
@@ -133,6 +139,11 @@ class RcclExchange:
         engine.allreduce_gradient()
         return engine.allreduce_f64([misfit])[0]
 
+    def reduce_illumination(self, engine, wrt="velocity", slot=None):
+        """Sum the device-side illumination accumulators over the ranks, then read H as NoExchange does."""
+        engine.allreduce_illumination()
+        return NoExchange.reduce_illumination(self, engine, wrt, slot)
+
 
 class HostExchange:
     """Sum on host arrays over the control plane (:class:`rendezvous.Rendezvous`): the path the CPU-only
@@ -147,6 +158,12 @@ class HostExchange:
         g = self.rdzv.allreduce_array(engine.gradient(wrt))
         return g, self.rdzv.allreduce([misfit])[0]
 
+    def reduce_illumination(self, engine, wrt="velocity", slot=None):
+        H = self.rdzv.allreduce_array(engine.illumination(wrt))
+        if slot is None:
+            return H
+        engine.vec_upload(slot, H)
+
 
 class EnginePool:
     """Several engines (contexts + streams) on ONE GPU working through a rank's shots concurrently.
@@ -159,7 +176,7 @@ class EnginePool:
     (``abc="cpml"``) a 1024^2 launch ends on its four corner tiles, and the overlap is what fills the idle CUs: 1.01 s
     one after the other, 0.65 s with two contexts, **0.55 s with three**, 1.24 s with four (round 3).  3-D shots are
     bandwidth-bound: use a pool of one.  Engines after the first only add into the first one's gradient
-    accumulator, which also owns the RCCL communicator.
+    accumulator (and illumination accumulator), which also owns the RCCL communicator.
     """
 
     MAX_USEFUL = 6
@@ -236,7 +253,26 @@ def model_data(engine, model, shots, exchange=None):
     return shots
 
 
-def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", objective=None, device_l2=True):
+class _Illuminated:
+    """Turns illumination on in every engine for one evaluation, and back off afterwards if it was off."""
+
+    def __init__(self, engine, on):
+        self.engs = _engines(engine) if on else []
+        self.was = [e.illumination_enabled for e in self.engs]
+
+    def __enter__(self):
+        for e in self.engs:
+            e.set_illumination(True)
+        return self
+
+    def __exit__(self, *exc):
+        for e, was in zip(self.engs, self.was):
+            if not was:
+                e.set_illumination(False)
+
+
+def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", objective=None, device_l2=True,
+                        illumination=False):
     """J = sum_shots objective(F_s(model), d_obs,s) and dJ/dmodel, summed over all ranks.
 
     ``objective(d_syn, d_obs) -> (J, dJ/dd_syn)``; default least squares 1/2 ||d_syn - d_obs||^2
@@ -246,15 +282,22 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     engine's dtype, i.e. with an fp32 engine ``d_obs`` is rounded to fp32 before the subtraction, which puts
     ~6e-8 |d| / |r| of relative noise on J and on the residual (visible to a line search only once |r| / |d|
     approaches 1e-6).  ``device_l2=False`` keeps the residual in fp64 on the host, ``d_obs`` exact.
+
+    ``illumination=True``: returns ``(J, g, H)`` with H the source-side illumination of the same sweeps, in the same
+    parametrisation as g, summed over all ranks (``Engine.illumination``): no extra propagation.
     """
     from .objectives import l2
     objective = objective or l2
     ex = exchange or NoExchange()
-    for e in _engines(engine):
-        e.set_model(model)
-        e.reset_gradient()
-    misfit = _sweep_shots(engine, shots, ex, objective, device_l2)
-    return ex.reduce(_engines(engine)[0], misfit, wrt)[::-1]
+    with _Illuminated(engine, illumination):
+        for e in _engines(engine):
+            e.set_model(model)
+            e.reset_gradient()
+        misfit = _sweep_shots(engine, shots, ex, objective, device_l2)
+        out = ex.reduce(_engines(engine)[0], misfit, wrt)[::-1]
+        if illumination:
+            out = out + (ex.reduce_illumination(_engines(engine)[0], wrt),)
+    return out
 
 
 def _sweep_shots(engine, shots, ex, objective, device_l2=True):
@@ -286,21 +329,73 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True):
 
 
 def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=None, wrt="velocity",
-                               objective=None, device_l2=True):
+                               objective=None, device_l2=True, illum_slot=None):
     """Like :func:`misfit_and_gradient`, with the model read from and the gradient written to
-    device-resident vectors (``Engine.vec_*``): no model-sized array crosses PCIe."""
+    device-resident vectors (``Engine.vec_*``): no model-sized array crosses PCIe.  ``illum_slot``: the vector
+    that receives the illumination H of the same sweeps (see :func:`misfit_and_gradient`)."""
     from .objectives import l2
     objective = objective or l2
     ex = exchange or NoExchange()
     engs = _engines(engine)
-    engs[0].set_model_vec(model_slot)
-    if len(engs) > 1:  # the optimiser's vectors live in the primary engine: hand the model over
-        model = engs[0].vec_download(model_slot)
-        for e in engs[1:]:
-            e.set_model(model)
-    for e in engs:
-        e.reset_gradient()
-    misfit = _sweep_shots(engine, shots, ex, objective, device_l2)
-    misfit = ex.reduce_device(engs[0], misfit)
-    engs[0].gradient_vec(grad_slot, wrt)
+    with _Illuminated(engine, illum_slot is not None):
+        engs[0].set_model_vec(model_slot)
+        if len(engs) > 1:  # the optimiser's vectors live in the primary engine: hand the model over
+            model = engs[0].vec_download(model_slot)
+            for e in engs[1:]:
+                e.set_model(model)
+        for e in engs:
+            e.reset_gradient()
+        misfit = _sweep_shots(engine, shots, ex, objective, device_l2)
+        misfit = ex.reduce_device(engs[0], misfit)
+        engs[0].gradient_vec(grad_slot, wrt)
+        if illum_slot is not None:
+            ex.reduce_illumination(engs[0], wrt, illum_slot)
     return misfit
+
+
+# Relative floor of the illumination preconditioner p = 1 / (H / max(H) + eps).  max(H) sits on the source cells, so
+# eps is a fraction of the illumination right at a source: cells lit by less than eps of that get a gain of about
+# 1 / eps, the best-lit ones a gain of about 1.  Chosen by measurement (DESIGN.md, "Illumination preconditioning").
+ILLUMINATION_EPS = 1e-3
+
+
+def illumination_preconditioner(H, eps=ILLUMINATION_EPS):
+    """p = 1 / (H / max(H) + eps), elementwise (host arrays)."""
+    H = np.asarray(H, np.float64)
+    m = float(np.abs(H).max())
+    if not m > 0.0 or not np.isfinite(m):
+        raise ValueError("illumination is zero or not finite: nothing to precondition with")
+    return 1.0 / (H / m + float(eps))
+
+
+def illumination_preconditioner_vec(engine, slot, eps=ILLUMINATION_EPS):
+    """Vector ``slot`` holding H := 1 / (H / max(H) + eps), on the device."""
+    m = engine.vec_absmax(slot)
+    if not m > 0.0 or not np.isfinite(m):
+        raise ValueError("illumination is zero or not finite: nothing to precondition with")
+    engine.vec_recip(slot, m, float(eps) * m)
+
+
+def preconditioned_fg_device(engine, shots, precond_slot, eps=ILLUMINATION_EPS, exchange=None, wrt="velocity",
+                             **kw):
+    """``fg(x_slot, g_slot) -> f`` for :func:`lbfgs.lbfgs_device` with ``precond_slot``: the first evaluation that
+    finds the slot empty (all zeros, as ``lbfgs_device`` creates it) also accumulates the illumination and turns it
+    into the preconditioner there; every other evaluation is a plain one.  A resumed run finds the slot filled from
+    its state and never rebuilds it."""
+    built = [False]
+
+    def fg(x_slot, g_slot):
+        if not built[0] and engine_of(engine).vec_absmax(precond_slot) == 0.0:
+            f = misfit_and_gradient_device(engine, x_slot, g_slot, shots, exchange, wrt, illum_slot=precond_slot, **kw)
+            illumination_preconditioner_vec(engine_of(engine), precond_slot, eps)
+            built[0] = True
+            return f
+        built[0] = True
+        return misfit_and_gradient_device(engine, x_slot, g_slot, shots, exchange, wrt, **kw)
+
+    return fg
+
+
+def engine_of(engine):
+    """The engine that holds the optimiser's vectors (the primary one of a pool)."""
+    return _engines(engine)[0]

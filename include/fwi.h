@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define FWI_ABI_VERSION 13
+#define FWI_ABI_VERSION 14
 
 enum { FWI_F32 = 0, FWI_F64 = 1 };
 
@@ -192,6 +192,24 @@ int fwi_vec_clip(fwi_ctx *ctx, int32_t x, double lo, double hi);
 int fwi_set_model_vec(fwi_ctx *ctx, int32_t slot);
 /* slot := accumulated gradient (after fwi_allreduce_gradient, if any), as fwi_gradient() */
 int fwi_gradient_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot);
+
+/* Source-side illumination: the diagonal of the pseudo-Hessian (Shin et al., 2001), the usual preconditioner of an FWI
+ * gradient with surface acquisition.  Off by default; while off no kernel of it runs and no memory is held.
+ * With S the image stride and q^n the stored forward term (q^n = C (L u^n + src^n) ~ dt^2 d2u/dt2, what the imaging
+ * condition correlates with; in bf16-store mode bf16(C L u^n) + C src^n):
+ *     H_m(x) = (S / dt^4) sum_{n % S == 0} q^n(x)^2      illumination w.r.t. m = 1/c^2 (FWI_WRT_SLOWNESS2)
+ *     H_c(x) = H_m(x) (2 / c(x)^3)^2                     w.r.t. velocity (FWI_WRT_VELOCITY, the Gauss-Newton diagonal)
+ * It accumulates like the gradient: over every fwi_adjoint(..., image != 0) since the last fwi_gradient_reset (which
+ * zeroes it), by one streaming pass over the store per shot (per checkpoint segment with ckpt_interval) -- no extra
+ * wave propagation.  fwi_gradient_add sums it too when both contexts have it on (FWI_EINVAL when only one has).
+ * Reading it while it is off or before a model is set is FWI_ESTATE.  No reference counterpart. */
+int fwi_set_illumination(fwi_ctx *ctx, int32_t on);  /* on != 0: allocate and zero the accumulator; 0: free it */
+int fwi_illumination(fwi_ctx *ctx, int32_t wrt, void *out);        /* model-shaped host buffer, context dtype */
+int fwi_illumination_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot); /* slot := H, as fwi_illumination() */
+int fwi_allreduce_illumination(fwi_ctx *ctx);  /* in-place sum over the ranks of fwi_comm_init */
+/* Elementwise vector operations for a diagonal preconditioner (pad columns of the compact layout stay 0). */
+int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x);               /* y := x * y */
+int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b);    /* y := a / (y + b) */
 
 /* Shot-parallel exchange: one RCCL communicator per context, sum of the
  * gradient accumulators over ranks (in place, on device).  The reference's

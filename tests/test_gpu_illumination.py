@@ -1,0 +1,201 @@
+"""Source-side illumination on the GPU (include/fwi.h fwi_set_illumination) against H built from the NumPy oracle's
+stored forward term: H_m = (S / dt^4) sum_{n % S == 0} q^n(x)^2, H_c = H_m (2 / c^3)^2, over every path that fills
+the store (2-D fused / tile, 3-D stream / point, image stride, checkpoint recomputation, bf16 store, off-grid
+sources), summed over shots and over the contexts of a pool; and the preconditioned L-BFGS built on it."""
+import numpy as np
+import pytest
+
+from full_waveform_inversion_amd import Engine, FwiError, shots as sh, workloads
+from full_waveform_inversion_amd.lbfgs import lbfgs_device, lbfgs_device_slots
+from full_waveform_inversion_amd.points import Spread
+from oracle import fwi_oracle as fo
+
+pytestmark = pytest.mark.gpu
+
+TOL32, TOL64, TOLBF16 = 1e-5, 1e-12, 1e-4  # (bf16: the tolerance of the bf16 store's gradient check)
+
+
+def rel(a, b):
+    return float(np.linalg.norm(np.asarray(a, np.float64) - np.asarray(b, np.float64)) / np.linalg.norm(b))
+
+
+def oracle_H(p, S):
+    qs = np.asarray(p.q_store, np.float64)
+    Hm = (S / p.dt ** 4) * np.sum(qs[::S] ** 2, axis=0)
+    return Hm, Hm * (2.0 / p.c ** 3) ** 2
+
+
+CASES = [  # id, shape, order, npml, nt, dtype, kernel name, engine / oracle options, tolerance
+    ("2d_fused_sponge", (192, 256), 8, 8, 80, "float32", "step2d_fused", {}, TOL32),
+    ("2d_fused_mixed_steps", (192, 256), 8, 8, 82, "float32", "step2d_fused", {}, TOL32),
+    ("2d_fused_cpml", (192, 256), 8, 8, 80, "float32", "step2d_fused", {"abc": "cpml", "pml_alpha_max": 40.0}, TOL32),
+    ("2d_fused_stride4", (192, 256), 8, 8, 80, "float32", "step2d_fused", {"image_stride": 4}, TOL32),
+    ("2d_fused_ckpt", (192, 256), 8, 8, 80, "float32", "step2d_fused", {"ckpt_interval": 8}, TOL32),
+    ("2d_tile_cpml", (72, 96), 8, 12, 60, "float32", "step2d_tile", {"abc": "cpml", "pml_alpha_max": 40.0}, TOL32),
+    ("3d_stream", (40, 36, 44), 8, 6, 60, "float32", "step3d_stream", {}, TOL32),
+    ("3d_stream_increment", (40, 36, 44), 8, 6, 60, "float32", "step3d_stream", {"update_form": "increment"}, TOL32),
+    ("3d_stream_cpml", (40, 36, 44), 8, 6, 60, "float32", "step3d_stream", {"abc": "cpml", "pml_alpha_max": 30.0},
+     TOL32),
+    ("3d_point", (40, 36, 44), 8, 6, 60, "float32", "step_point", {"kernel": "point"}, TOL32),
+    ("3d_stride4", (40, 36, 44), 8, 6, 60, "float32", "step3d_stream", {"image_stride": 4}, TOL32),
+    ("3d_ckpt", (40, 36, 44), 8, 6, 60, "float32", "step3d_stream", {"ckpt_interval": 16}, TOL32),
+    ("3d_fp64", (33, 29, 50), 4, 5, 50, "float64", "step3d_stream", {}, TOL64),
+    ("3d_fp64_ckpt", (33, 29, 50), 4, 5, 50, "float64", "step3d_stream", {"ckpt_interval": 7}, TOL64),
+    ("3d_bf16", (40, 36, 44), 8, 6, 60, "float32", "step3d_stream", {"store_dtype": "bf16"}, TOLBF16),
+    ("3d_bf16_stride3", (33, 29, 50), 8, 0, 60, "float32", "step3d_stream", {"store_dtype": "bf16", "image_stride": 3},
+     TOLBF16),
+]
+ORACLE_KEYS = ("abc", "pml_alpha_max", "image_stride", "store_dtype")
+
+
+def _problem(shape, order, nt, seed=0):
+    rng = np.random.default_rng(seed)
+    c = 2000.0 + 600.0 * rng.random(shape)
+    h = 10.0
+    dt = 0.6 * fo.cfl_dt(c.max(), h, len(shape), order)
+    src = np.array([[s // 2 for s in shape], [s // 3 for s in shape], [s // 2 for s in shape]])  # a duplicate node
+    rec = np.stack([rng.integers(0, s, 8) for s in shape], 1)
+    wav = np.stack([fo.ricker(nt, dt, 0.12 / dt / 8) * a for a in (1.0, 0.7, -0.4)], 1)
+    return c, h, dt, src, rec, wav
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_illumination_matches_the_oracle_store(gpu, case):
+    _, shape, order, npml, nt, dtype, kname, opts, tol = case
+    c, h, dt, src, rec, wav = _problem(shape, order, nt)
+    S = opts.get("image_stride", 1)
+    p = fo.Propagator(c, h, dt, order, npml, **{k: v for k, v in opts.items() if k in ORACLE_KEYS})
+    d = p.forward(src, wav, rec)
+    Hm, Hc = oracle_H(p, S)
+    with Engine(shape, h, dt, nt, order=order, npml=npml, sigma_max=p.sigma_max, dtype=dtype, illumination=True,
+                **opts) as e:
+        e.forward(c, (src, wav), rec, save=True)
+        assert e.kernel_name == kname
+        e.adjoint(d * 0.5)
+        hm, hc = e.illumination("slowness2"), e.illumination("velocity")
+        e.vec_create(1)
+        e.illumination_vec(0, "velocity")
+        hv = e.vec_download(0)
+    assert rel(hm, Hm) < tol and rel(hc, Hc) < tol, (rel(hm, Hm), rel(hc, Hc))
+    assert np.array_equal(hv, hc)
+
+
+def test_off_grid_sources_share_nodes(gpu):
+    shape, order, nt = (40, 36, 44), 8, 60
+    c, h, dt, _, rec, wav = _problem(shape, order, nt)
+    xyz = np.array([[20.3, 17.6, 21.2], [20.7, 17.6, 21.9], [11.0, 12.5, 14.0]])  # the first two share nodes
+    S = Spread(xyz, shape)
+    for opts, tol in (({}, TOL32), ({"store_dtype": "bf16"}, TOLBF16)):
+        p = fo.Propagator(c, h, dt, order, 6, **opts)
+        p.forward(S.idx, S.scatter(wav), rec)
+        Hm, _ = oracle_H(p, 1)
+        with Engine(shape, h, dt, nt, order=order, npml=6, sigma_max=p.sigma_max, illumination=True, **opts) as e:
+            d = e.forward_at(c, (xyz, wav), rec.astype(np.float64), save=True)
+            e.adjoint(d)
+            assert rel(e.illumination("slowness2"), Hm) < tol, opts
+
+
+def test_shots_and_pool_contexts_sum_and_reset_zeroes(gpu):
+    shape, order, npml, nt = (192, 256), 8, 8, 80
+    c, h, dt, _, rec, wav = _problem(shape, order, nt)
+    srcs = [np.array([[10, x]]) for x in (40, 100, 160, 220)]
+    p = fo.Propagator(c, h, dt, order, npml)
+    Hc = 0.0
+    for s in srcs:
+        p.forward(s, wav[:, :1], rec)
+        Hc = Hc + oracle_H(p, 1)[1]
+    shots = [sh.Shot(s, wav[:, 0], rec) for s in srcs]
+    mk = lambda: Engine(shape, h, dt, nt, order=order, npml=npml, sigma_max=p.sigma_max)  # noqa: E731
+    with sh.EnginePool(mk, 1) as one, sh.EnginePool(mk, 2) as two:
+        sh.model_data(one, c * 1.02, shots)
+        f1, g1, H1 = sh.misfit_and_gradient(one, c, shots, illumination=True)
+        f2, g2, H2 = sh.misfit_and_gradient(two, c, shots, illumination=True)
+        assert not any(e.illumination_enabled for e in two.engines)  # switched back off after the evaluation
+        f0, g0 = sh.misfit_and_gradient(one, c, shots)
+        # the gradient does not see the illumination (the misfit: up to the order of its fp64 atomic block sums)
+        assert np.array_equal(g0, g1) and abs(f0 - f1) <= 1e-12 * f0
+        assert rel(H1, Hc) < TOL32 and rel(H2, Hc) < TOL32
+        e = one.primary
+        e.set_illumination(True)
+        shots[0].forward(e, True)
+        e.adjoint(np.ones((nt, len(rec)), np.float32))
+        assert np.abs(e.illumination()).max() > 0
+        e.reset_gradient()
+        assert not np.any(e.illumination())
+        with pytest.raises(FwiError):  # one context with, one without
+            e.gradient_add_from(two.engines[1])
+        e.set_illumination(False)
+        with pytest.raises(FwiError):
+            e.illumination()
+
+
+def test_gradient_is_bit_identical_with_illumination_on_and_off(gpu):
+    for shape, opts in (((40, 36, 44), {"update_form": "increment"}), ((192, 256), {"ckpt_interval": 8}),
+                        ((40, 36, 44), {"store_dtype": "bf16"})):
+        order, nt = 8, 60 if len(shape) == 3 else 80
+        c, h, dt, src, rec, wav = _problem(shape, order, nt)
+        src = src[1:]  # distinct nodes: the bf16 store's source pairing adds entries of a shared node atomically
+        wav = wav[:, 1:]
+        out = []
+        for on in (False, True):
+            with Engine(shape, h, dt, nt, order=order, npml=6, sigma_max=50.0, illumination=on, **opts) as e:
+                d = e.forward(c, (src, wav), rec, save=True)
+                a = e.adjoint(d * 0.3)
+                out.append((d, a, e.gradient()))
+        for x, y in zip(*out):
+            assert np.array_equal(x, y), opts
+
+
+def test_reading_while_disabled_or_without_a_model_raises(gpu):
+    with Engine((32, 40), 10.0, 1e-3, 8) as e:
+        with pytest.raises(FwiError) as ei:
+            e.illumination()
+        assert ei.value.code == 3
+        e.set_illumination(True)
+        with pytest.raises(FwiError) as ei:
+            e.illumination()  # no model yet
+        assert ei.value.code == 3
+        with pytest.raises(FwiError) as ei:
+            e._chk(e._lib.fwi_illumination(e._ctx, 5, np.zeros((32, 40), np.float32).ctypes.data))
+        assert ei.value.code == 1
+
+
+def test_vec_mul_and_recip(gpu):
+    rng = np.random.default_rng(1)
+    x, y = rng.random((30, 37)).astype(np.float32), rng.random((30, 37)).astype(np.float32)
+    with Engine((30, 37), 10.0, 1e-3, 8) as e:
+        e.vec_create(2)
+        e.vec_upload(0, y)
+        e.vec_upload(1, x)
+        e.vec_mul(0, 1)
+        assert np.allclose(e.vec_download(0), x * y, rtol=1e-6)
+        e.vec_recip(1, 2.0, 0.5)
+        assert np.allclose(e.vec_download(1), 2.0 / (x + 0.5), rtol=1e-6)
+
+
+def _inversion(pre):
+    w = workloads.cfg3(0.25, nshots=8)
+    wav = w.wavelet()
+    shots = [sh.Shot(w.src_idx[i:i + 1], wav, w.rec_idx) for i in range(len(w.src_idx))]
+    sigma = fo.default_sigma_max(float(w.c.max()), w.h, w.npml)
+    with sh.EnginePool(lambda: sh.inversion_engine(w.shape, w.h, w.dt, w.nt, order=w.order, npml=w.npml,
+                                                   sigma_max=sigma), 2) as pool:
+        sh.model_data(pool, w.c.astype(np.float32), shots)
+        m0 = w.c_init.astype(np.float32)
+        bounds = (0.5 * float(w.c.min()), 1.5 * float(w.c.max()))
+        slot = lbfgs_device_slots(5) if pre else None
+        fg = (sh.preconditioned_fg_device(pool, shots, slot, eps=1e-2) if pre else
+              (lambda xs, gs: sh.misfit_and_gradient_device(pool, xs, gs, shots)))
+        _, f, log = lbfgs_device(pool.primary, fg, m0, maxiter=5, history=5, first_step=0.02 * float(m0.max()),
+                                 bounds=bounds, precond_slot=slot)
+    return f, log
+
+
+def test_preconditioned_lbfgs_beats_the_plain_one_on_cfg3(gpu):
+    f_plain, log_plain = _inversion(False)
+    f_pre, log_pre = _inversion(True)
+    print("plain", [e["f"] for e in log_plain], "preconditioned", [e["f"] for e in log_pre])
+    # the same starting model: the same misfit, up to the order in which the device's misfit reduction adds its block
+    # sums (fp64 atomics: the last bit or two differ from run to run, with or without illumination)
+    assert abs(log_pre[0]["f"] - log_plain[0]["f"]) <= 1e-12 * log_plain[0]["f"]
+    assert f_pre < f_plain

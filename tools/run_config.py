@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 from full_waveform_inversion_amd import Engine, shots as sh, workloads  # noqa: E402
-from full_waveform_inversion_amd.lbfgs import lbfgs, lbfgs_device  # noqa: E402
+from full_waveform_inversion_amd.lbfgs import lbfgs, lbfgs_device, lbfgs_device_slots  # noqa: E402
 
 
 def main():
@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--launch-mode", default="auto", choices=["auto", "stream", "graph"])
     ap.add_argument("--checkpoint", default="", help="optimiser state file, rewritten after every iteration (rank 0 only)")
     ap.add_argument("--resume", default="", help="continue from such a state file (every rank reads it)")
+    ap.add_argument("--precondition", nargs="?", type=float, const=sh.ILLUMINATION_EPS, default=None, metavar="EPS",
+                    help="L-BFGS with the source-illumination preconditioner p = 1 / (H / max H + EPS), built from the "
+                         "first evaluation (default EPS %g); off when absent" % sh.ILLUMINATION_EPS)
     a = ap.parse_args()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -77,18 +80,35 @@ def main():
         evals[0] += 1
         return sh.misfit_and_gradient(pool, m, shots, ex)
 
+    eps = a.precondition
+    first_H = []
+
+    def fg_host(m):  # with --precondition: the first evaluation also returns the illumination
+        if eps is None or first_H:
+            return fg(m)
+        evals[0] += 1
+        J, g, H = sh.misfit_and_gradient(pool, m, shots, ex, illumination=True)
+        first_H.append(H)
+        return J, g
+
     m0 = w.c_init.astype(np.float32)
     ckpt = a.checkpoint if (a.checkpoint and rank == 0) else None  # every rank holds the same state: one writer
     bounds = (0.5 * float(w.c.min()), 1.5 * float(w.c.max()))
     if a.iters > 0 and not a.host_lbfgs:
+        pslot = lbfgs_device_slots(5) if eps is not None else None
+        fg_p = sh.preconditioned_fg_device(pool, shots, pslot, eps, ex) if eps is not None else None
+
         def fg_dev(xs, gs):
             evals[0] += 1
+            if fg_p is not None:
+                return fg_p(xs, gs)
             return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex)
         _, _, log = lbfgs_device(e, fg_dev, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
-                                 bounds=bounds, checkpoint=ckpt, resume=a.resume or None)
+                                 bounds=bounds, checkpoint=ckpt, resume=a.resume or None, precond_slot=pslot)
     elif a.iters > 0:
-        _, _, log = lbfgs(fg, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
-                          bounds=bounds, dot=e.dot, checkpoint=ckpt, resume=a.resume or None)
+        pc = (lambda x, f, g: sh.illumination_preconditioner(first_H[0], eps)) if eps is not None else None
+        _, _, log = lbfgs(fg_host, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
+                          bounds=bounds, dot=e.dot, checkpoint=ckpt, resume=a.resume or None, precond=pc)
     else:
         J, g = fg(m0)
         log = [{"iter": 0, "f": J, "gnorm": float(np.sqrt(e.dot(g, g)))}]
@@ -99,7 +119,7 @@ def main():
                           "n_gpus": world, "rccl_ranks": getattr(ex, "rccl_ranks", None), "engines_per_gpu": psize, "evaluations": evals[0], "seconds": round(el, 3),
                           "Gpts_per_s_fwd_plus_adj": round(upd / el / 1e9, 2), "kernel": e.kernel_name,
                           "update_form": e.update_form, "abc": a.abc, "launch_mode": a.launch_mode,
-                          "log": log}))
+                          "precondition_eps": eps, "log": log}))
     pool.close()
     if rdzv is not None:
         rdzv.barrier()
