@@ -1084,9 +1084,7 @@ struct Impl {
             HIPCHK(ctx, hipMemsetAsync(*ctx->mov_slot[i], 0, ctx->mov_bytes[i] + ctx->place_pad, ctx->stream));
         int rc = pml_zero(ctx);
         if (rc) return rc;
-        hipEvent_t e0, e1;
-        HIPCHK(ctx, hipEventCreate(&e0));
-        HIPCHK(ctx, hipEventCreate(&e1));
+        hipEvent_t e0 = nullptr, e1 = nullptr;  // (every failure from here on leaves through `done`, which destroys them)
         const fwi_ctx::PointSet nobody;
         auto none = [](int) -> T * { return nullptr; };
         auto noq = [](int, const T *&p, const T *&p2) { p = p2 = nullptr; };
@@ -1110,6 +1108,11 @@ struct Impl {
         };
         float best = 0.f, t = 0.f, t2 = 0.f;
         int n = 8;
+        auto event = [&](hipEvent_t *e) -> int {
+            HIPCHK(ctx, hipEventCreate(e));
+            return FWI_OK;
+        };
+        if ((rc = event(&e0)) || (rc = event(&e1))) goto done;
         // warm up (code objects' first use, clocks), then the position the context was created with -- twice, the better
         if ((rc = timed(24, &t)) || (rc = timed(8, &t))) goto done;
         n = std::max(4, std::min(12, (int)(1500.f / std::max(t, 1.f))));  // ~1.5 ms per trial
@@ -1144,8 +1147,8 @@ struct Impl {
         }
         if (!rc) ctx->place_us[1] = best;
     done:
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
         return rc;
     }
 
@@ -1724,6 +1727,24 @@ int create_impl(fwi_ctx *ctx) {
     return FWI_OK;
 }
 
+// FWI_PLACEMENT_TUNE=fixed:<k0>,<k1>,... (fwi_create): one to eight offsets in units of 2 MiB, each within the
+// 14 MiB of slack (0 ... 7); the last one repeats for the arrays that are not listed
+bool parse_fixed_placement(const char *s, int k[8]) {
+    int n = 0;
+    for (;;) {
+        char *end = nullptr;
+        if (*s < '0' || *s > '9') return false;  // (no sign, no blank: strtol would take them)
+        const long v = strtol(s, &end, 10);
+        if (v > 7 || n == 8) return false;
+        k[n++] = (int)v;
+        if (*end == '\0') break;
+        if (*end != ',') return false;
+        s = end + 1;
+    }
+    for (; n < 8; ++n) k[n] = k[n - 1];
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1884,14 +1905,23 @@ int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
                 (int)ctx->fused2d, (int)ctx->xpml, ctx->pml_lines, ctx->tune.ty, ctx->tune.zchunk);
     // 3-D CPML contexts past the cache-resident sizes place their small arrays by measurement (Impl::tune_placement).
     // FWI_PLACEMENT_TUNE: "0" = off, "pad" = padded allocations without the search (A/B hooks), "force" = also on grids
-    // below the size threshold (tests: the oracle comparisons run small grids)
+    // below the size threshold (tests: the oracle comparisons run small grids), "fixed:<k0>,<k1>,..." = on any grid, NO
+    // search: movable array i (in the search order) sits k_i * 2 MiB into its allocation, the last value repeats (tests:
+    // a layout that is asked for instead of timed; 0 <= k <= 7, anything else is FWI_EINVAL).  A context that places
+    // nothing ignores "fixed:" as it ignores "force".
     const char *pt = getenv("FWI_PLACEMENT_TUNE");
+    const bool place_fixed = pt && !strncmp(pt, "fixed:", 6);
     const bool place_on = cfg->dtype == FWI_F32 && cfg->ndim == 3 && ctx->kernel == K_STREAM && !(pt && !strcmp(pt, "0")) &&
-                          ((double)ctx->gd.ptot * ctx->esize >= 48e6 || (pt && !strcmp(pt, "force")));
+                          ((double)ctx->gd.ptot * ctx->esize >= 48e6 || (pt && !strcmp(pt, "force")) || place_fixed);
     if (place_on && ctx->xpml) ctx->place_kind = 1;
     else if (place_on && ctx->inc && !ctx->cpml) ctx->place_kind = 2;
     const bool place = ctx->place_kind != 0;
     if (place) ctx->place_pad = (size_t)14 << 20;
+    int fixed_k[8] = {};
+    if (place && place_fixed && !parse_fixed_placement(pt + 6, fixed_k)) {
+        delete ctx;  // (nothing on the device yet)
+        return bad("FWI_PLACEMENT_TUNE=fixed:<k0>,<k1>,...: one to eight offsets, each 0 ... 7 (units of 2 MiB)");
+    }
     int rc = create_impl(ctx);
     const size_t vslack = ctx->place_kind ? ctx->place_pad : 0;
     if (rc == FWI_OK && ctx->inc &&
@@ -1907,12 +1937,23 @@ int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
                 rc = ctx->fail(FWI_ENOMEM, "allocating the fused 2-D buffer pair failed");
         }
     }
-    if (rc == FWI_OK && place && !(pt && !strcmp(pt, "pad"))) rc = Impl<float>::tune_placement(ctx);
+    if (rc == FWI_OK && place && place_fixed) {
+        // every allocation was zeroed over its whole padded length where its content matters before the first write
+        // (tz, ty, v, C; the x border's psi / zeta are zeroed where they lie at the start of every sweep)
+        for (int i = 0; i < ctx->nmov; ++i) {
+            ctx->mov_shift[i] = (size_t)fixed_k[i] * ((size_t)2 << 20);
+            *ctx->mov_slot[i] = (char *)*ctx->mov_slot[i] + ctx->mov_shift[i];
+        }
+    } else if (rc == FWI_OK && place && !(pt && !strcmp(pt, "pad"))) {
+        rc = Impl<float>::tune_placement(ctx);
+    }
     if (rc) {
-        g_create_error = "fwi_create: " + ctx->err;
+        const std::string msg = "fwi_create: " + ctx->err;
         fwi_destroy(ctx);
+        g_create_error = msg;  // (the reason the creation failed, not what fwi_destroy may have had to say after it)
         return rc;
     }
+    g_create_error.clear();
     *out = ctx;
     return FWI_OK;
 }
@@ -1924,35 +1965,63 @@ void fwi_destroy(fwi_ctx *ctx) {
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
-    void *ptrs[] = {ctx->u[0], ctx->u[1], ctx->C, ctx->c_dev, ctx->dz, ctx->dy, ctx->dx, ctx->q_store,
-                    ctx->g_acc, ctx->h_acc, ctx->g_out, ctx->red, ctx->amp, ctx->series, ctx->wav, ctx->snap, ctx->fwd[0],
-                    ctx->fwd[1], ctx->fx[0], ctx->fx[1], ctx->fwx[0], ctx->fwx[1], ctx->logical, ctx->vf, ctx->fwv};
-    for (fwi_ctx::PointSet *ps : {&ctx->src, &ctx->rec})
+    // the movable arrays (fwi_create, Impl::tune_placement) go back to the start of their allocations BEFORE any pointer
+    // is read for freeing: hipFree takes what hipMalloc returned, not an address inside it
+    for (int i = 0; i < ctx->nmov; ++i)
+        if (*ctx->mov_slot[i]) *ctx->mov_slot[i] = (char *)*ctx->mov_slot[i] - ctx->mov_shift[i];
+    // The function returns nothing, so the FIRST free the runtime refuses is reported through the thread's creation
+    // error (fwi_last_error(NULL)): "fwi_destroy: hipFree(<member>[<index>]): <HIP error>".  The rest is still freed.
+    bool failed = false;
+    auto release = [&](const char *member, int idx, void *p) {
+        if (!p) return;
+        const hipError_t e = hipFree(p);
+        if (e == hipSuccess || failed) return;
+        failed = true;
+        char msg[256];
+        snprintf(msg, sizeof msg, "fwi_destroy: hipFree(%s[%d]): %s", member, idx, hipGetErrorString(e));
+        g_create_error = msg;
+    };
+    int k = 0;
+    for (fwi_ctx::PointSet *ps : {&ctx->src, &ctx->rec}) {
+        int j = 0;
         for (void *p : {ps->pidx, ps->cidx, ps->cu, ps->cq, ps->s_start, ps->s_pidx, ps->s_cidx, ps->s_cu,
                         ps->s_cq, ps->s_col, ps->s_run, ps->fi_run, ps->fi_start, ps->fi_lz, ps->fi_lx, ps->fi_col, ps->fi_int,
                         ps->fi_cidx, ps->fi_cu, ps->fi_cq, ps->fr_start, ps->fr_lz, ps->fr_lx, ps->fr_col, ps->pr_start,
                         ps->pr_ent})
-            if (p) (void)hipFree(p);
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (void *v : ctx->vecs)
-        if (v) (void)hipFree(v);
-    // (the four movable arrays: back to the start of their allocations)
-    for (int i = 0; i < ctx->nmov; ++i)
-        if (*ctx->mov_slot[i]) *ctx->mov_slot[i] = (char *)*ctx->mov_slot[i] - ctx->mov_shift[i];
-    for (int d = 0; d < 3; ++d)
-        for (void *q : {ctx->pml_psi[d], ctx->pml_zeta[d], ctx->pml_a[d], ctx->pml_b[d], ctx->pml_psi_fw[d],
-                        ctx->pml_zeta_fw[d], ctx->pml_spare_psi[d], ctx->pml_spare_zeta[d]})
-            if (q) (void)hipFree(q);
-    if (ctx->pml_snap) (void)hipFree(ctx->pml_snap);
-    for (void *q : {ctx->pml_tz, ctx->pml_ty})
-        if (q) (void)hipFree(q);
-    if (ctx->fused_order) (void)hipFree(ctx->fused_order);
-    for (fwi_ctx::SpreadSet *sp : {&ctx->src_sp, &ctx->rec_sp})
-        for (void *q : {sp->pt_start, sp->owner, sp->weight})
-            if (q) (void)hipFree(q);
-    for (void *q : {ctx->pts_a, ctx->pts_d})
-        if (q) (void)hipFree(q);
+            release(ps == &ctx->src ? "src" : "rec", j++, p);
+    }
+    const struct {
+        const char *member;
+        void *p;
+    } fields[] = {{"u", ctx->u[0]}, {"u", ctx->u[1]}, {"C", ctx->C}, {"c_dev", ctx->c_dev}, {"dz", ctx->dz}, {"dy", ctx->dy},
+                  {"dx", ctx->dx}, {"q_store", ctx->q_store}, {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc},
+                  {"g_out", ctx->g_out}, {"red", ctx->red}, {"amp", ctx->amp}, {"series", ctx->series}, {"wav", ctx->wav},
+                  {"snap", ctx->snap}, {"fwd", ctx->fwd[0]}, {"fwd", ctx->fwd[1]}, {"fx", ctx->fx[0]}, {"fx", ctx->fx[1]},
+                  {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
+                  {"pml_snap", ctx->pml_snap}, {"pml_tz", ctx->pml_tz}, {"pml_ty", ctx->pml_ty},
+                  {"fused_order", ctx->fused_order}, {"pts_a", ctx->pts_a}, {"pts_d", ctx->pts_d}};
+    const char *prev = "";
+    for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
+        k = strcmp(prev, f.member) ? 0 : k + 1;
+        prev = f.member;
+        release(f.member, k, f.p);
+    }
+    k = 0;
+    for (void *v : ctx->vecs) release("vecs", k++, v);
+    for (int d = 0; d < 3; ++d) {
+        release("pml_psi", d, ctx->pml_psi[d]);
+        release("pml_zeta", d, ctx->pml_zeta[d]);
+        release("pml_a", d, ctx->pml_a[d]);
+        release("pml_b", d, ctx->pml_b[d]);
+        release("pml_psi_fw", d, ctx->pml_psi_fw[d]);
+        release("pml_zeta_fw", d, ctx->pml_zeta_fw[d]);
+        release("pml_spare_psi", d, ctx->pml_spare_psi[d]);
+        release("pml_spare_zeta", d, ctx->pml_spare_zeta[d]);
+    }
+    for (fwi_ctx::SpreadSet *sp : {&ctx->src_sp, &ctx->rec_sp}) {
+        k = 0;
+        for (void *q : {sp->pt_start, sp->owner, sp->weight}) release(sp == &ctx->src_sp ? "src_sp" : "rec_sp", k++, q);
+    }
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

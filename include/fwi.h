@@ -114,9 +114,21 @@ typedef struct fwi_config {
 } fwi_config;
 
 /* Context life cycle.  [north_star: "thin ctypes C-ABI shim"; SURVEY s.8b] */
+/* fwi_create reads FWI_PLACEMENT_TUNE from the environment (the placement of fwi_placement_info below): unset = the
+ * search runs where the context is large enough; "0" = no padded allocations, no search; "pad" = padded allocations, no
+ * search; "force" = the search also on grids below its size threshold; "fixed:<k0>,<k1>,..." = on any grid size and
+ * WITHOUT a search, movable array i (search order of fwi_placement_info) sits k_i * 2 MiB into its padded allocation,
+ * the last value repeating for the arrays not listed (tests: a layout that is asked for, not timed).  One to eight
+ * values, each 0 ... 7; anything else makes fwi_create fail with FWI_EINVAL.  A context that places nothing (2-D, fp64,
+ * the point kernel, the plain sponge in standard form) ignores "force" and "fixed:" alike. */
 int fwi_create(const fwi_config *cfg, fwi_ctx **out);
+/* Frees everything the context owns; every device array through the pointer its allocation returned, wherever the
+ * placement left the array.  The function returns nothing: if the runtime refuses a free, the FIRST such failure is
+ * written to the calling thread's creation-error text, the one fwi_last_error(NULL) returns, as
+ * "fwi_destroy: hipFree(<member>[<index>]): <HIP error>", and the remaining arrays are still freed. */
 void fwi_destroy(fwi_ctx *ctx);
-/* Last error text of ctx (or of the failed fwi_create when ctx == NULL). */
+/* Last error text of ctx.  With ctx == NULL: the calling thread's creation-error text -- the reason of the last failed
+ * fwi_create, or a "fwi_destroy: ..." message (above).  A successful fwi_create on that thread clears it. */
 const char *fwi_last_error(const fwi_ctx *ctx);
 int fwi_abi_version(void);
 
@@ -241,7 +253,8 @@ int fwi_last_host_ms(fwi_ctx *ctx, double *submit_ms_out, double *graph_build_ms
  * allocations and keeps the fastest; results never depend on it.  Time per step before and after the search in
  * microseconds (0 = no search ran for this context) and, into shift_bytes_out[8], the chosen offsets in bytes of the
  * movable arrays in search order (CPML: ty, zeta_x, tz, psi_x, then v in increment form; increment form without CPML:
- * v, C; unused entries 0).  Any out pointer may be NULL.  No reference counterpart. */
+ * v, C; unused entries 0).  Under FWI_PLACEMENT_TUNE=fixed:... (fwi_create) the offsets are the requested ones and both
+ * times are 0: no search ran.  Any out pointer may be NULL.  No reference counterpart. */
 int fwi_placement_info(fwi_ctx *ctx, double *us_before_out, double *us_after_out, int64_t *shift_bytes_out);
 /* Change fwi_config.launch_mode of a live context (takes effect with the next sweep): the A/B of stream launches against
  * hipGraph launches on ONE context, the same buffers and the same cache state (tools/graph_probe.py). */

@@ -1,6 +1,7 @@
 """Lifecycle stress (a script, not collected by pytest): thousands of create / use / destroy cycles of the wave
 engine context and of the Monte Carlo plan on one GPU.  Leaked streams, events or device buffers show up as a HIP
-error or as free device memory shrinking between the first and the last hundred cycles."""
+error, as a "fwi_destroy:" message in fwi_last_error(NULL), or as free device memory shrinking between the first and the
+last hundred cycles."""
 import ctypes as C
 import os
 import sys
@@ -9,7 +10,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
-from full_waveform_inversion_amd import Engine, source_inversion as si  # noqa: E402
+from full_waveform_inversion_amd import Engine, _lib, source_inversion as si  # noqa: E402
 
 hip = C.CDLL("libamdhip64.so")
 
@@ -34,6 +35,11 @@ def main(n=1500):
     # points spread on the device, the two-step 3-D kernel
     options = [dict(), dict(abc="cpml", pml_alpha_max=20.0), dict(update_form="increment"), dict(store_dtype="bf16"),
                dict(abc="cpml", update_form="increment")]
+    shape_p = (80, 72, 96)  # 2.7 MB per padded field
+    cp = (2000.0 + 300.0 * rng.random(shape_p)).astype(np.float32)
+    placed = [dict(update_form="increment"), dict(abc="cpml", pml_alpha_max=20.0),
+              dict(abc="cpml", pml_alpha_max=20.0, update_form="increment")]
+    lib = _lib.load()
     for i in range(n):
         kw = options[i % len(options)]
         plain = not kw
@@ -54,6 +60,19 @@ def main(n=1500):
                 dd = e.forward(c2, ([[20, 22]], w), [[5, 6], [30, 40]], save=True)
                 e.adjoint(dd)
                 e.gradient()
+        if i % 7 == 0:
+            # a placed context (tests/test_gpu_placement.py): every movable array at its own non-zero offset inside a
+            # padded allocation, the increment form and the CPML (standard / increment form) in turn
+            os.environ["FWI_PLACEMENT_TUNE"] = "fixed:1,3,5,7,2"
+            kwp = placed[(i // 7) % len(placed)]
+            with Engine(shape_p, 10.0, 1e-3, 12, npml=8, sigma_max=200.0, **kwp) as e:
+                assert any(e.placement_info()[2])
+                dd = e.forward(cp, ([[40, 36, 48]], w), [[3, 4, 5], [60, 50, 70]], save=True)
+                e.adjoint(dd)
+                e.gradient()
+            del os.environ["FWI_PLACEMENT_TUNE"]
+        msg = lib.fwi_last_error(None) or b""
+        assert not msg.startswith(b"fwi_destroy:"), msg.decode()  # (a device free the runtime refused)
         with si.MonteCarloPlan(d, G, 512) as plan:
             plan.invert("full_mt", 300, seed=i)
         si.invert_on_device(d, G, 100, "DC", seed=i)
