@@ -4,7 +4,8 @@ Drop-in entry points named by BASELINE.json's north_star -- ``forward(model,
 src, rec)``, ``adjoint(residual)``, ``gradient()`` -- over hand-written gfx950
 HIP kernels behind a ctypes C-ABI (include/fwi.h).  The reference repository
 has no such path; see DESIGN.md for the provenance of the
-scheme and of the oracle it is checked against.
+scheme and of the oracle it is checked against.  Beyond the gradient: ``Engine.born`` (the linearised forward
+operator J), ``shots.gauss_newton_hvp`` (J^T J v) and ``newton`` (conjugate gradients on it).
 """
 from __future__ import annotations
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/fwi.h"
+#include "fwi_born.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
 
@@ -122,6 +123,9 @@ struct fwi_ctx {
     // source-side illumination (fwi_set_illumination): compact accumulator of sum q^2 over the imaging steps of every
     // fwi_adjoint(image) since the last fwi_gradient_reset; nullptr = disabled (the default: no launch, no memory)
     void *h_acc = nullptr;
+    // Born modelling (fwi_born): w = dC / C of the last perturbation, compact; allocated by the first fwi_born call
+    void *born_w = nullptr;
+    const char *born_path = "none";  // path of the last Born sweep (fwi_born_path)
     double *red = nullptr;    // reduction scalars
 
     // host copies
@@ -355,6 +359,7 @@ struct Impl {
         int prev_n = -1;
         void *v = nullptr;  // increment form: the v field of this sweep
         bool pml_fw = false;  // CPML: this sweep is the checkpointed forward recomputation (its own memory variables)
+        const void *born_w = nullptr;  // fused Born sweep: w (compact); the step kernel adds w q_in(n) inside q
     };
 
     static StepArgs<T> base_args(fwi_ctx *ctx, int cur) {
@@ -1052,6 +1057,13 @@ struct Impl {
                 }
                 HIPCHK(ctx, launch_step<T>(ctx->kernel, g, a, ctx->tune, ctx->stream));
                 if (axes) HIPCHK(ctx, launch_pml<T>(g, p, 3, dn < 0, ctx->stream, axes));  // their term joins u' (and q)
+            } else if (sw.born_w) {  // (born_fused_supported: 3-D fp32 O(8) stream contexts without the CPML)
+                if constexpr (std::is_same<T, float>::value) {
+                    a.g = (T *)sw.born_w;  // read only
+                    HIPCHK(ctx, (launch_stream_born<T, 4>(g, a, ctx->tune, ctx->stream)));
+                } else {
+                    return ctx->fail(FWI_ESTATE, "the fused Born path is fp32 only");
+                }
             } else {
                 HIPCHK(ctx, launch_step<T>(ctx->kernel, g, a, ctx->tune, ctx->stream));
             }
@@ -1499,6 +1511,74 @@ struct Impl {
         if ((rc = loop.end())) return rc;
         return download_samples(ctx, (adj_src_out && ctx->nsrc) ? adj_src_out : nullptr, ctx->series, nt, ctx->nsrc,
                                 ctx->src_sp, nullptr, nullptr);
+    }
+
+    // Born modelling dd = J dm (include/fwi.h, fwi_born).  dm comes from the host (`dm_host`) or from a compact device
+    // vector (`dm_dev`).  The Born field du obeys the wavefield's recursion with the distributed source w q^n, w = dC / C,
+    // in the place of the point source: the sweep runs the ordinary one-step launches of run_steps on zeroed fields (no
+    // injection, nothing stored) and adds A w q^n to du^{n+1} after step n (fwi_born.hip); the receiver sampling that
+    // rides on the next step launch then sees the completed field.  `fused` (born_fused_supported contexts): the step
+    // kernel itself adds w q^n inside q (fwi_born3d.hip) and there is no second pass.  The store is read, never written.
+    static int born(fwi_ctx *ctx, int32_t wrt, const T *dm_host, const void *dm_dev, bool fused, T *seis_out) {
+        const GridDesc &g = ctx->gd;
+        const int nt = ctx->nt, nrec = ctx->nrec;
+        hipStream_t s = ctx->stream;
+        int rc;
+        if (!ctx->born_w) HIPCHK(ctx, hipMalloc(&ctx->born_w, (size_t)g.npts * sizeof(T)));
+        if (dm_host && (rc = upload_compact(ctx, ctx->born_w, dm_host))) return rc;
+        HIPCHK(ctx, launch_born_weight<T>(g, (const T *)(dm_host ? ctx->born_w : dm_dev), (const T *)ctx->c_dev,
+                                          (T *)ctx->born_w, wrt == FWI_WRT_VELOCITY, s));
+        ctx->have_syn = false;           // ctx->series is about to hold dd instead of the forward's synthetics
+        ctx->have_dev_residual = false;  // ... and ctx->amp a copy of it, once the sweep has ended
+        if ((rc = zero_fields(ctx, ctx->u[0], ctx->u[1]))) return rc;
+        Sweep sw;
+        sw.f[0] = ctx->u[0];
+        sw.f[1] = ctx->u[1];
+        sw.v = ctx->vf;
+        if (ctx->inc) HIPCHK(ctx, hipMemsetAsync(ctx->vf, 0, (size_t)g.ptot * sizeof(T), s));
+        if (ctx->cpml && (rc = pml_zero(ctx))) return rc;
+        T *series = (T *)ctx->series;
+        const fwi_ctx::PointSet nobody;
+        auto none = [](int) -> T * { return nullptr; };
+        auto noq = [](int, const T *&p, const T *&p2) { p = p2 = nullptr; };
+        const int damp = base_args(ctx, 0).damp;
+        TimeLoop loop(ctx);
+        if ((rc = loop.begin())) return rc;
+        const T *const qs = (const T *)ctx->q_store;
+        auto qn = [&](int n, const T *&p, const T *&p2) { p = qs + (size_t)n * g.npts; p2 = nullptr; };
+        if (fused) {
+            sw.born_w = ctx->born_w;
+            if ((rc = run_steps(ctx, sw, 0, 1, nt, nobody, (const T *)nullptr, &ctx->rec, series, T(1), none, qn))) return rc;
+        }
+        for (int n = 0; n < nt && !fused; ++n) {
+            if ((rc = run_steps(ctx, sw, n, 1, 1, nobody, (const T *)nullptr, &ctx->rec, series, T(1), none, noq)))
+                return rc;
+            HIPCHK(ctx, launch_born_scatter<T>(g, (T *)sw.f[sw.cur], (T *)sw.v, qs + (size_t)n * g.npts,
+                                               (const T *)ctx->born_w, (const T *)ctx->dz, (const T *)ctx->dy,
+                                               (const T *)ctx->dx, damp, s));
+        }
+        if ((rc = flush_record(ctx, sw, ctx->rec, series, T(1)))) return rc;
+        if ((rc = loop.end())) return rc;
+        ctx->born_path = fused ? "fused" : "scatter";
+        // dd stays on the device as the residual of the next fwi_adjoint(ctx, NULL, ...): per node in ctx->amp (off-grid
+        // receivers: gathered per point for the caller, then spread back onto the nodes, as fwi_misfit_l2 does)
+        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
+        const void *out = ctx->series;
+        size_t out_bytes = (size_t)nt * nrec * sizeof(T);
+        if (nrec && sp.npts) {
+            if ((rc = ensure(ctx, &ctx->pts_d, &ctx->cap_pts_d, (size_t)nt * sp.npts * sizeof(T)))) return rc;
+            HIPCHK(ctx, launch_gather_series<T>((const T *)ctx->series, (T *)ctx->pts_d, (const int *)sp.pt_start,
+                                                (const T *)sp.weight, nt, sp.npts, nrec, s));
+            HIPCHK(ctx, launch_scatter_series<T>((const T *)ctx->pts_d, (T *)ctx->amp, (const int *)sp.owner,
+                                                 (const T *)sp.weight, nt, sp.npts, nrec, s));
+            out = ctx->pts_d;
+            out_bytes = (size_t)nt * sp.npts * sizeof(T);
+        } else if (nrec) {
+            HIPCHK(ctx, hipMemcpyAsync(ctx->amp, ctx->series, out_bytes, hipMemcpyDeviceToDevice, s));
+        }
+        if ((rc = download_series(ctx, seis_out, out, (nrec && seis_out) ? out_bytes : 0))) return rc;
+        ctx->have_dev_residual = true;
+        return FWI_OK;
     }
 
     // illumination accumulator += sum of the squares of `nslots` store slots (no-op while illumination is disabled)
@@ -1994,7 +2074,7 @@ void fwi_destroy(fwi_ctx *ctx) {
         const char *member;
         void *p;
     } fields[] = {{"u", ctx->u[0]}, {"u", ctx->u[1]}, {"C", ctx->C}, {"c_dev", ctx->c_dev}, {"dz", ctx->dz}, {"dy", ctx->dy},
-                  {"dx", ctx->dx}, {"q_store", ctx->q_store}, {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc},
+                  {"dx", ctx->dx}, {"q_store", ctx->q_store}, {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc}, {"born_w", ctx->born_w},
                   {"g_out", ctx->g_out}, {"red", ctx->red}, {"amp", ctx->amp}, {"series", ctx->series}, {"wav", ctx->wav},
                   {"snap", ctx->snap}, {"fwd", ctx->fwd[0]}, {"fwd", ctx->fwd[1]}, {"fx", ctx->fx[0]}, {"fx", ctx->fx[1]},
                   {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
@@ -2299,6 +2379,60 @@ int fwi_gradient_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot) {
     (void)hipSetDevice(ctx->cfg.device);
     return DISPATCH(ctx, Impl<float>::gradient_vec(ctx, wrt, v), Impl<double>::gradient_vec(ctx, wrt, v));
 }
+
+// FWI_BORN_AUTO on a context that has both paths: decided by measurement (tools/born_probe.py)
+constexpr bool BORN_AUTO_IS_FUSED = true;
+
+// contexts whose step kernel has the Born variants of fwi_born3d.hip
+static bool born_fused_supported(const fwi_ctx *ctx) {
+    return ctx->gd.ndim == 3 && ctx->cfg.dtype == FWI_F32 && ctx->cfg.order == 8 && ctx->kernel == K_STREAM && !ctx->cpml;
+}
+
+// the argument and state checks fwi_born and fwi_born_vec share; *fused: the path the sweep takes
+static int born_callable(fwi_ctx *ctx, const char *who, int32_t wrt, int32_t mode, bool *fused) {
+    if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
+        return ctx->fail(FWI_EINVAL, "%s: unknown parametrisation %d", who, (int)wrt);
+    if (mode != FWI_BORN_AUTO && mode != FWI_BORN_SCATTER && mode != FWI_BORN_FUSED)
+        return ctx->fail(FWI_EINVAL, "%s: unknown mode %d", who, (int)mode);
+    // the sweep needs every q^n, in the field's type, resident at once
+    if (ctx->istride > 1)
+        return ctx->fail(FWI_EINVAL, "%s: not available with image_stride > 1 (the store holds every %d-th step only)", who,
+                         ctx->istride);
+    if (ctx->qbf16) return ctx->fail(FWI_EINVAL, "%s: not available with store_dtype = bf16", who);
+    if (ctx->ckpt > 0)
+        return ctx->fail(FWI_EINVAL, "%s: not available with ckpt_interval > 0 (the store holds one segment at a time)", who);
+    if (mode == FWI_BORN_FUSED && !born_fused_supported(ctx))
+        return ctx->fail(FWI_EINVAL, "%s: FWI_BORN_FUSED: this context has no fused Born path (3-D fp32 O(8) stream "
+                                     "kernel without the CPML only)", who);
+    *fused = mode == FWI_BORN_FUSED || (mode == FWI_BORN_AUTO && BORN_AUTO_IS_FUSED && born_fused_supported(ctx));
+    if (!ctx->have_forward || !ctx->have_q)
+        return ctx->fail(FWI_ESTATE, "%s: needs fwi_forward(save=1) on this context first", who);
+    return FWI_OK;
+}
+
+int fwi_born(fwi_ctx *ctx, int32_t wrt, const void *dm_host, int32_t mode, void *seis_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!dm_host) return ctx->fail(FWI_EINVAL, "fwi_born: null model perturbation");
+    bool fused = false;
+    int rc = born_callable(ctx, "fwi_born", wrt, mode, &fused);
+    if (rc) return rc;
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, Impl<float>::born(ctx, wrt, (const float *)dm_host, nullptr, fused, (float *)seis_out),
+                    Impl<double>::born(ctx, wrt, (const double *)dm_host, nullptr, fused, (double *)seis_out));
+}
+
+int fwi_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, void *seis_out) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, v, slot);
+    bool fused = false;
+    int rc = born_callable(ctx, "fwi_born_vec", wrt, mode, &fused);
+    if (rc) return rc;
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, Impl<float>::born(ctx, wrt, nullptr, v, fused, (float *)seis_out),
+                    Impl<double>::born(ctx, wrt, nullptr, v, fused, (double *)seis_out));
+}
+
+const char *fwi_born_path(const fwi_ctx *ctx) { return ctx ? ctx->born_path : ""; }
 
 int fwi_comm_unique_id(void *id_out) {
     static_assert(sizeof(ncclUniqueId) == FWI_UNIQUE_ID_BYTES, "ncclUniqueId size");

@@ -128,6 +128,19 @@ __device__ __forceinline__ void st_qf(double *base, int64_t elem, const vec<doub
 template <bool QB>
 __device__ __forceinline__ vec<double> ld_qf(const double *base, int64_t elem) { return ldv_stream<double>(base + elem); }
 
+// w of a fused Born sweep (step3d_stream, IMAGE 3): a model-sized array re-read every step.  A streaming load, like
+// the imaging variants' g: at 256^3 the three fields then stay in the Infinity Cache (58.1 against 60.7 us/step with a
+// plain load, 70.3 against 72.6 in increment form; 512^3 within +-1.3 %: profiles/r05_born_loads_ab.json).
+// FWI_BORN_W_PLAIN builds the plain-load form for the A/B (make variant EXTRA=-DFWI_BORN_W_PLAIN).
+template <typename T>
+__device__ __forceinline__ vec<T> ld_born_w(const T *p) {
+#ifdef FWI_BORN_W_PLAIN
+    return ldv<T>(p);
+#else
+    return ldv_stream<T>(p);
+#endif
+}
+
 __device__ __forceinline__ f4 ld4(const float *p) { return ldv<float>(p); }
 __device__ __forceinline__ void st4(float *p, const f4 &v) { stv<float>(p, v); }
 __device__ __forceinline__ f4 ld4_stream(const float *p) { return ldv_stream<float>(p); }

@@ -127,6 +127,11 @@ hipError_t launch_step(int kernel, const GridDesc &g, const StepArgs<T> &a, cons
 template <typename T, int R>
 hipError_t launch_stream_r(const GridDesc &g, const StepArgs<T> &a, const StreamTuning &t, hipStream_t s);
 
+// The 3-D stream kernel's Born variants (fwi_stream3d.h, IMAGE 3; instantiated in fwi_born3d.hip for fp32 O(8) only):
+// the step of `a` with the scattering source w q^n inside q -- a.q_in = q^n, a.g = w (read only).  Sponge or no border.
+template <typename T, int R>
+hipError_t launch_stream_born(const GridDesc &g, const StepArgs<T> &a, const StreamTuning &t, hipStream_t s);
+
 // out[i] = u[pidx[i]] * scale
 template <typename T>
 hipError_t launch_record(const T *u, const int64_t *pidx, T *out, T scale, int n, hipStream_t s);

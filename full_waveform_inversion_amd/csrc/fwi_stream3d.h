@@ -26,6 +26,8 @@ namespace fwi {
 // Infinity Cache traffic.  Blocks are renumbered so each XCD (private 4 MiB
 // L2) owns a contiguous slab of tiles and shares those halo rows on chip.
 // ---------------------------------------------------------------------------
+// IMAGE 3 (Born sweeps, fwi_born3d.hip): nothing is imaged or stored back; the scattering source w q_in joins q,
+// q = C (L u + ...) + w q_in, with w read through the pointer `g` -- two more 16-byte loads per lane and plane.
 // IMAGE: 0 = off, 1 = g += u_cur * q_in, 2 = additionally g += u_prev * q_in2 (increment form, round 4: u_prev = u_cur - v) (two time levels per
 // read-modify-write of g: the adjoint sweep is HBM-bound, this takes it from 28 to 24 B/update).
 // XP: the convolutional PML of the x border carried in the lanes (1 = forward recursion, 2 = its transpose): the
@@ -303,7 +305,8 @@ __global__ __launch_bounds__(64 * TY) void step3d_stream(StepArgs<T> a, GridDesc
                 if (IMAGE == 2) qi2 = ld_qf<QB>(a.q_in2, (int64_t)z * cplane + co);
                 // g is touched once per (other) step: streaming hints keep it from evicting the three
                 // wavefield arrays from the Infinity Cache (adjoint 68 -> 59 us/step at 256^3)
-                gi = ldv_stream<T>(a.g + (int64_t)z * cplane + co);
+                // (IMAGE 3: w, re-read every step of the sweep)
+                gi = IMAGE == 3 ? ld_born_w<T>(a.g + (int64_t)z * cplane + co) : ldv_stream<T>(a.g + (int64_t)z * cplane + co);
             }
             __syncthreads();
 
@@ -444,6 +447,7 @@ __global__ __launch_bounds__(64 * TY) void step3d_stream(StepArgs<T> a, GridDesc
                 if (XP) br += xterm.v[j];
                 if (TP) br += (zin ? tzr[ct].v[j] : T(0)) + (yin ? tyr[ct].v[j] : T(0));
                 q.v[j] = Cc[cp].v[j] * br;
+                if (IMAGE == 3) q.v[j] = fma(gi.v[j], qi.v[j], q.v[j]);  // Born: the scattering source w q^n
                 if (INC) {  // v' = A (B v + q), u' = u + v'
                     vn.v[j] = DAMP ? fma(B.v[j], up[cp].v[j], q.v[j]) * A.v[j] : up[cp].v[j] + q.v[j];
                     un.v[j] = X[HALO + j] + vn.v[j];
@@ -465,7 +469,7 @@ __global__ __launch_bounds__(64 * TY) void step3d_stream(StepArgs<T> a, GridDesc
                     stv<T>(a.xp_zeta + (int64_t)z * xplane + xld, xn1);
                 }
             }
-            if (IMAGE) {
+            if (IMAGE == 1 || IMAGE == 2) {
 #pragma unroll
                 for (int j = 0; j < VL; ++j) {
                     gi.v[j] = fma(X[HALO + j], qi.v[j], gi.v[j]);
@@ -479,7 +483,7 @@ __global__ __launch_bounds__(64 * TY) void step3d_stream(StepArgs<T> a, GridDesc
                 if (INC) stv<T>(a.v + (int64_t)z * sz + poff, vn);
                 stv<T>(a.u_prev + (int64_t)z * sz + poff, un);
                 if (SAVE_Q) st_qf<QB>(a.q_out, (int64_t)z * cplane + coff, q);
-                if (IMAGE) stv_stream<T>(a.g + (int64_t)z * cplane + coff, gi);
+                if (IMAGE == 1 || IMAGE == 2) stv_stream<T>(a.g + (int64_t)z * cplane + coff, gi);
             }
         }
     }
@@ -597,6 +601,38 @@ static hipError_t launch_stream_mode(const GridDesc &g, const StepArgs<T> &a, in
             return launch_stream_full<T, R, TY, DAMP, true, 1>(g, a, zchunk, tw, s);
     }
     return launch_stream_full<T, R, TY, DAMP, false, 1>(g, a, zchunk, tw, s);
+}
+
+// Born sweeps of the headline family (3-D, O(8), sponge or no border, standard / increment form): the IMAGE = 3 variants,
+// with their own dispatch so that only fwi_born3d.hip instantiates them.  a.q_in = q^n, a.g = w (never written).
+template <typename T, int R, int TY, bool DAMP>
+static hipError_t launch_stream_born_mode(const GridDesc &g, const StepArgs<T> &a, int zchunk, int tw, hipStream_t s) {
+    const int nxt = stream_nxt(g, tw);
+    const int nyt = (g.ny + TY - 1) / TY;
+    const int nzc = (g.nz + zchunk - 1) / zchunk;
+    const int nblk = nxt * nyt * nzc;
+    const int nrb = (a.rec_out && a.nrec > 0) ? (a.nrec + 64 * TY * 4 - 1) / (64 * TY * 4) : 0;
+    const dim3 grid(nblk + nrb), block(64, TY);
+    const bool full = g.nx % (64 * VecOf<T>::VL) == 0 && g.ny % TY == 0 && tw == 64 * VecOf<T>::VL;
+#define FWI_BORN_GO(FULL, INC)                                                                                     \
+    hipLaunchKernelGGL((step3d_stream<T, R, TY, DAMP, false, 3, FULL, 1, INC>), grid, block, 0, s, a, g, zchunk, nxt, nyt, \
+                       nblk, tw)
+    if (full && a.v) FWI_BORN_GO(true, true);
+    else if (full) FWI_BORN_GO(true, false);
+    else if (a.v) FWI_BORN_GO(false, true);
+    else FWI_BORN_GO(false, false);
+#undef FWI_BORN_GO
+    return hipGetLastError();
+}
+
+template <typename T, int R>
+hipError_t launch_stream_born(const GridDesc &g, const StepArgs<T> &a, const StreamTuning &t, hipStream_t s) {
+    if (!a.q_in || !a.g || a.q_out || a.q_in2 || a.q_bf16 || a.pml_tz || a.pml_ty || a.xp_mode) return hipErrorInvalidValue;
+    const int zc = t.zchunk > 0 ? t.zchunk : g.nz;
+    if (a.damp) return t.ty == 4 ? launch_stream_born_mode<T, R, 4, true>(g, a, zc, t.tile_x, s)
+                                 : launch_stream_born_mode<T, R, 8, true>(g, a, zc, t.tile_x, s);
+    return t.ty == 4 ? launch_stream_born_mode<T, R, 4, false>(g, a, zc, t.tile_x, s)
+                     : launch_stream_born_mode<T, R, 8, false>(g, a, zc, t.tile_x, s);
 }
 
 template <typename T, int R>

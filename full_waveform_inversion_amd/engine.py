@@ -270,6 +270,37 @@ class Engine:
     def allreduce_illumination(self):
         self._chk(self._lib.fwi_allreduce_illumination(self._c))
 
+    # -- Born modelling (include/fwi.h fwi_born) -----------------------------------
+    born_leaves_residual = True  # ``born`` keeps J dm on the device as the residual of ``adjoint(None)``
+
+    def _born(self, call, wrt, mode, download):
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        out = np.zeros((self._nt, self._nrec), self.dtype) if download else None
+        self._chk(call(w, _lib.BORN_MODES[mode], out.ctypes.data_as(C.c_void_p) if download else None))
+        return out
+
+    def born(self, dm, wrt="velocity", mode="auto", download=True):
+        """Linearised (Born) data ``J dm`` as ``(nt, nrec)`` at the receivers of the last ``forward(save=True)``, whose
+        store it reads: the derivative of ``forward`` along the model perturbation ``dm`` (a velocity perturbation, or
+        one of ``1 / c^2`` with ``wrt="slowness2"``).  The data also stay on the device as the residual of the next
+        ``adjoint(None)``, so ``forward(save=True)``, ``born``, ``adjoint(None)``, ``gradient`` is the Gauss-Newton
+        product ``J^T J dm``; ``download=False`` skips the copy to the host and returns None.  ``mode``: "scatter"
+        (every engine), "fused" (3-D fp32 O(8) stream-kernel engines without the CPML: the scattering source inside the
+        step kernel, about 0.6 - 0.75 of the time) or "auto" (fused where it exists); :attr:`born_path` names the path
+        taken.  Not available with ``image_stride > 1``, ``store_dtype="bf16"`` or ``ckpt_interval > 0``."""
+        dm = self._host(dm, self.shape)
+        return self._born(lambda w, m, o: self._lib.fwi_born(self._c, w, dm.ctypes.data_as(C.c_void_p), m, o),
+                          wrt, mode, download)
+
+    def born_vec(self, slot, wrt="velocity", mode="auto", download=True):
+        """:meth:`born` with ``dm`` read from the device vector ``slot``."""
+        return self._born(lambda w, m, o: self._lib.fwi_born_vec(self._c, w, int(slot), m, o), wrt, mode, download)
+
+    @property
+    def born_path(self):
+        """Name of the path the last Born sweep took ("scatter" or "fused"; "none" before the first)."""
+        return self._lib.fwi_born_path(self._ctx).decode() if self._ctx is not None else "none"
+
     # -- reductions, exchange, measurement --------------------------------------
     def dot(self, a, b):
         a, b = self._host(a).ravel(), self._host(b).ravel()

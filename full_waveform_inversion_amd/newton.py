@@ -1,0 +1,80 @@
+"""Gauss-Newton steps: conjugate gradients on the Hessian-vector products of :mod:`shots`.
+
+``H_GN = sum_s J_s^T J_s`` is applied matrix-free (``shots.gauss_newton_hvp``: three sweeps per shot and product), so an
+inner iteration costs about one and a half gradient evaluations.  Host arrays are enough at this size of problem; the
+products themselves run on the device.  No reference counterpart.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+def cg(hvp, b, x0=None, precond=None, maxiter=20, rtol=1e-6, callback=None):
+    """Preconditioned conjugate gradients for ``H x = b`` with ``H`` symmetric positive (semi-)definite, given as
+    ``hvp(p) -> H p`` on arrays of ``b``'s shape.  ``precond``: None, an array applied elementwise (an approximate
+    inverse diagonal, e.g. ``shots.illumination_preconditioner``) or a callable ``r -> M^-1 r``.
+
+    Stops when ``||r|| <= rtol ||r_0||``, after ``maxiter`` products, or on a direction of non-positive curvature
+    ``p^T H p <= 0`` (the iterate reached so far is returned; a Gauss-Newton Hessian has none up to round-off).
+    Returns ``(x, log)``: one entry per iterate k = 0, 1, ... with ``iter``, ``rnorm`` = ||b - H x_k|| and, from k = 1
+    on, ``curvature`` = p^T H p and ``alpha`` of the step that led there; the last entry carries ``stop`` =
+    "converged" | "maxiter" | "negative_curvature".  ``callback(k, x_k)`` is called for every iterate.
+    """
+    b = np.asarray(b, np.float64)
+    apply_m = (lambda r: r) if precond is None else precond if callable(precond) else \
+        (lambda r, m=np.asarray(precond, np.float64): m * r)
+    x = np.zeros_like(b) if x0 is None else np.array(x0, np.float64)
+    r = b - np.asarray(hvp(x), np.float64) if x0 is not None else b.copy()
+    z = np.asarray(apply_m(r), np.float64)
+    p = z.copy()
+    rz = float(np.vdot(r, z))
+    r0 = float(np.linalg.norm(r))
+    log = [{"iter": 0, "rnorm": r0}]
+    if callback:
+        callback(0, x)
+    if r0 == 0.0:
+        log[-1]["stop"] = "converged"
+        return x, log
+    for k in range(1, int(maxiter) + 1):
+        Hp = np.asarray(hvp(p), np.float64)
+        curv = float(np.vdot(p, Hp))
+        if not curv > 0.0:
+            log[-1]["stop"] = "negative_curvature"
+            log[-1]["curvature"] = curv
+            return x, log
+        alpha = rz / curv
+        x = x + alpha * p
+        r = r - alpha * Hp
+        rn = float(np.linalg.norm(r))
+        log.append({"iter": k, "rnorm": rn, "curvature": curv, "alpha": alpha})
+        if callback:
+            callback(k, x)
+        if rn <= rtol * r0:
+            log[-1]["stop"] = "converged"
+            return x, log
+        z = np.asarray(apply_m(r), np.float64)
+        rz_new = float(np.vdot(r, z))
+        p = z + (rz_new / rz) * p
+        rz = rz_new
+    log[-1]["stop"] = "maxiter"
+    return x, log
+
+
+def gauss_newton_step(engine, model, shots, g, exchange=None, wrt="velocity", precond=None, maxiter=10, rtol=1e-2,
+                      damping=0.0, callback=None):
+    """The (truncated) Gauss-Newton step ``p``: ``(H_GN + damping I) p = -g`` at ``model`` by :func:`cg`, with ``g``
+    the gradient ``shots.misfit_and_gradient`` returned there (same ``wrt``).  ``precond`` as in :func:`cg`; the
+    illumination preconditioner of ``shots.illumination_preconditioner`` fits (the illumination is the diagonal of the
+    pseudo-Hessian).  Every inner iteration is one ``shots.gauss_newton_hvp``: three sweeps per shot, and the engine's
+    gradient accumulator is overwritten.  Returns ``(p, log)`` (``log`` as :func:`cg`)."""
+    from .shots import _engines, gauss_newton_hvp
+    for e in _engines(engine):
+        e.set_model(model)
+    g = np.asarray(g, np.float64)
+
+    def hvp(v):
+        dtype = getattr(_engines(engine)[0], "dtype", np.float64)
+        Hv = np.asarray(gauss_newton_hvp(engine, None, shots, np.asarray(v, dtype), exchange, wrt), np.float64)
+        return Hv + damping * v if damping else Hv
+
+    return cg(hvp, -g, precond=precond, maxiter=maxiter, rtol=rtol, callback=callback)

@@ -52,6 +52,17 @@ class Shot:
         r = self.rec_spread.scatter(residual) if self.rec_spread is not None else residual
         engine.adjoint(np.ascontiguousarray(r))
 
+    def born(self, engine, dm, wrt="velocity", download=True):
+        """Born data ``J dm`` at this shot's receivers, ``(nt, nrec)``, after ``forward(engine, save=True)``."""
+        d = engine.born(dm, wrt) if download else engine.born(dm, wrt, download=False)
+        if d is None or self._on_device(engine) or self.rec_spread is None:
+            return d
+        return self.rec_spread.gather(d)
+
+    def _residual_stays(self, engine):
+        """``engine.born`` leaves exactly this shot's ``J dm`` on the device as the residual of ``adjoint(None)``"""
+        return getattr(engine, "born_leaves_residual", False) and (self.rec_spread is None or self._on_device(engine))
+
 
 def inversion_engine(shape, h, dt, nt_max, **kw):
     """The :class:`Engine` an INVERSION should run on: ``update_form="increment"`` unless the caller says otherwise.
@@ -351,6 +362,73 @@ def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=No
         if illum_slot is not None:
             ex.reduce_illumination(engs[0], wrt, illum_slot)
     return misfit
+
+
+def _hvp_sweep(engine, shots, ex, born_one):
+    """forward(save) + Born + adjoint(imaging) of this rank's shots; ``born_one(e, s, download)`` applies J_s."""
+
+    def one(e, i):
+        s = shots[i]
+        s.forward(e, save=True)
+        if s._residual_stays(e):
+            born_one(e, s, False)
+            e.adjoint(None)
+        else:
+            s.adjoint(e, born_one(e, s, True))
+
+    mine = partition_shots(len(shots), ex.rank, ex.world)
+    if isinstance(engine, EnginePool):
+        engine.map_shots(mine, one)
+        for other in engine.engines[1:]:
+            engine.primary.gradient_add_from(other)
+    else:
+        for i in mine:
+            one(engine, i)
+
+
+def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity"):
+    """Gauss-Newton Hessian-vector product ``H v = sum_s J_s^T J_s v`` at ``model``, summed over all ranks: ``v`` and
+    the result are model-shaped and in the parametrisation ``wrt``.  Per shot ``forward(save=True)``, ``born``,
+    ``adjoint`` -- THREE sweeps per shot and product, because the forward-term store holds one shot at a time.
+    OVERWRITES the gradient accumulator of the engine(s) (``reset_gradient`` first, like :func:`misfit_and_gradient`).
+    ``model=None`` keeps the model the engines already hold.  The shots need no observed data."""
+    ex = exchange or NoExchange()
+    engs = _engines(engine)
+    for e in engs:
+        if model is not None:
+            e.set_model(model)
+        e.reset_gradient()
+    _hvp_sweep(engine, shots, ex, lambda e, s, download: s.born(e, v, wrt, download=download))
+    return ex.reduce(engs[0], 0.0, wrt)[0]
+
+
+def gauss_newton_hvp_device(engine, model_slot, v_slot, out_slot, shots, exchange=None, wrt="velocity"):
+    """:func:`gauss_newton_hvp` on device vectors (``Engine.vec_*``): the model is read from ``model_slot`` (None: the
+    model the engines hold), v from ``v_slot`` and ``H v`` is written to ``out_slot``; the Born data stay on the device
+    as the adjoint's residual, so no model- or data-sized array crosses PCIe (the further engines of a pool receive the
+    model and v from the primary one through the host).  OVERWRITES the gradient accumulator; three sweeps per shot."""
+    ex = exchange or NoExchange()
+    engs = _engines(engine)
+    if model_slot is not None:
+        engs[0].set_model_vec(model_slot)
+    if len(engs) > 1:  # the vectors live in the primary engine: hand model and v over
+        v = engs[0].vec_download(v_slot)
+        if model_slot is not None:
+            model = engs[0].vec_download(model_slot)
+            for e in engs[1:]:
+                e.set_model(model)
+    for e in engs:
+        e.reset_gradient()
+
+    def born_one(e, s, download):
+        if e is not engs[0]:
+            return s.born(e, v, wrt, download=download)
+        d = e.born_vec(v_slot, wrt, download=download)
+        return d if d is None or s._on_device(e) or s.rec_spread is None else s.rec_spread.gather(d)
+
+    _hvp_sweep(engine, shots, ex, born_one)
+    ex.reduce_device(engs[0], 0.0)
+    engs[0].gradient_vec(out_slot, wrt)
 
 
 # Relative floor of the illumination preconditioner p = 1 / (H / max(H) + eps).  max(H) sits on the source cells, so

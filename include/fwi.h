@@ -36,6 +36,8 @@
 extern "C" {
 #endif
 
+/* Stays 14 with the Born calls (fwi_born, fwi_born_vec, fwi_born_path): they are purely additive -- three new symbols,
+ * fwi_config and every existing call unchanged -- so a client built against the earlier 14 keeps working. */
 #define FWI_ABI_VERSION 14
 
 enum { FWI_F32 = 0, FWI_F64 = 1 };
@@ -222,6 +224,41 @@ int fwi_allreduce_illumination(fwi_ctx *ctx);  /* in-place sum over the ranks of
 /* Elementwise vector operations for a diagonal preconditioner (pad columns of the compact layout stay 0). */
 int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x);               /* y := x * y */
 int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b);    /* y := a / (y + b) */
+
+/* Born (linearised) modelling dd = J dm: the exact derivative of the discrete fwi_forward along a model perturbation,
+ * whose exact transpose is fwi_adjoint(image) + fwi_gradient.  With C = dt^2 c^2 and q^n the forward term the store of
+ * fwi_forward(save != 0) holds for every step (q^n = C (L u^n + PML terms + src^n)):
+ *     w        = dC / C = 2 dc / c  (FWI_WRT_VELOCITY: dm is dc)   or   -c^2 dm  (FWI_WRT_SLOWNESS2: dm perturbs 1 / c^2)
+ *     dq^n     = C (L du^n + the CPML terms of du^n) + w q^n        (no point source)
+ *     du^{n+1} = A (2 du^n - B du^{n-1} + dq^n),   du^0 = du^{-1} = 0;   dd^n = R du^{n+1},  n = 0 .. nt - 1
+ * (increment form: dv' = A (B dv + dq), du' = du + dv'; the CPML memory variables of du start at zero and follow the
+ * forward recursion).  The Born field obeys the wavefield's own recursion with the distributed source w q^n, so J costs
+ * one more sweep over data already on the device: the ordinary one-step launches, each followed by du^{n+1} += A w q^n.
+ *  - Needs a preceding fwi_forward / fwi_forward_spread with save != 0 on this context (else FWI_ESTATE); uses that
+ *    call's nt and receivers and returns (nt, nrec) -- per point after fwi_forward_spread, as that call does.
+ *  - Reads the store, never writes it: it may be called any number of times after one forward, and a following
+ *    fwi_adjoint(..., image = 1) accumulates bit for bit what it would have without the Born call in between.
+ *  - Runs in the context's wavefield buffers (free once the forward sweep has ended) plus one model-shaped compact array for w, allocated by the first call and
+ *    freed by fwi_destroy.
+ *  - Leaves dd on the device as the residual of the next fwi_adjoint(ctx, NULL, ...): the Gauss-Newton product
+ *    H v = J^T J v is fwi_forward(save), fwi_born_vec, fwi_adjoint(NULL, image = 1), fwi_gradient_vec with no model- or
+ *    data-sized PCIe transfer (seis_out == NULL skips the download).  The forward's synthetics are gone for
+ *    fwi_misfit_l2 afterwards (FWI_ESTATE, the rule that holds after an adjoint).
+ *  - Contexts whose store does not hold every q^n in the field's type cannot serve it: image_stride > 1,
+ *    store_dtype = bf16 and ckpt_interval > 0 return FWI_EINVAL.  (Checkpointed Born -- recompute a segment, then sweep
+ *    it -- is a follow-up.)
+ *  - mode: FWI_BORN_SCATTER is the path above, available on every context.  FWI_BORN_FUSED carries w q^n inside the step
+ *    kernel (no second pass: 24 instead of 32 B per point and step, 28 instead of 44 in increment form); it exists for
+ *    3-D fp32 O(8) contexts on the stream kernel without the CPML and returns FWI_EINVAL on any other.  FWI_BORN_AUTO takes
+ *    FUSED where it exists (measured at 0.58 - 0.74 of SCATTER's time per step), SCATTER elsewhere.  The
+ *    selector is an argument, not an environment switch.  The two paths agree to round-off, not bit for bit.
+ *  - The time loop is timed like the others (fwi_last_loop_ms, fwi_last_host_ms) and honours launch_mode.
+ * No reference counterpart. */
+enum { FWI_BORN_AUTO = 0, FWI_BORN_SCATTER = 1, FWI_BORN_FUSED = 2 };
+int fwi_born(fwi_ctx *ctx, int32_t wrt, const void *dm_host, int32_t mode, void *seis_out /* (nt, nrec) or NULL */);
+int fwi_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, void *seis_out); /* dm from a device vector */
+const char *fwi_born_path(const fwi_ctx *ctx);  /* static name of the path the last Born sweep took: "scatter", "fused";
+                                                   "none" before the first */
 
 /* Shot-parallel exchange: one RCCL communicator per context, sum of the
  * gradient accumulators over ranks (in place, on device).  The reference's
