@@ -95,6 +95,8 @@ SIGNATURES = {
     "fwi_vec_recip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_born": (C.c_int, [_P, _I32, _P, _I32, _P]),
     "fwi_born_vec": (C.c_int, [_P, _I32, _I32, _I32, _P]),
+    "fwi_born_imaging": (C.c_int, [_P, _I32, _P, _I32, _P]),
+    "fwi_born_imaging_vec": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "fwi_born_path": (C.c_char_p, [_P]),
     "fwi_mc_score": (C.c_int, [_I32, _I32, _I32, _I32, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P,
                                C.POINTER(_D)]),

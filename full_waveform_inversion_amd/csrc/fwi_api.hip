@@ -125,6 +125,9 @@ struct fwi_ctx {
     void *h_acc = nullptr;
     // Born modelling (fwi_born): w = dC / C of the last perturbation, compact; allocated by the first fwi_born call
     void *born_w = nullptr;
+    // ... on a bf16 store: (nt, nsrc) amplitudes w(x_s) wav^n_s of the source's exact share (launch_born_source_share)
+    void *born_src = nullptr;
+    size_t cap_born_src = 0;
     const char *born_path = "none";  // path of the last Born sweep (fwi_born_path)
     double *red = nullptr;    // reduction scalars
 
@@ -1060,7 +1063,10 @@ struct Impl {
             } else if (sw.born_w) {  // (born_fused_supported: 3-D fp32 O(8) stream contexts without the CPML)
                 if constexpr (std::is_same<T, float>::value) {
                     a.g = (T *)sw.born_w;  // read only
-                    HIPCHK(ctx, (launch_stream_born<T, 4>(g, a, ctx->tune, ctx->stream)));
+                    if (a.q_bf16)
+                        HIPCHK(ctx, (launch_stream_born_bf16<4>(g, a, ctx->tune, ctx->stream)));
+                    else
+                        HIPCHK(ctx, (launch_stream_born<T, 4>(g, a, ctx->tune, ctx->stream)));
                 } else {
                     return ctx->fail(FWI_ESTATE, "the fused Born path is fp32 only");
                 }
@@ -1513,21 +1519,50 @@ struct Impl {
                                 ctx->src_sp, nullptr, nullptr);
     }
 
-    // Born modelling dd = J dm (include/fwi.h, fwi_born).  dm comes from the host (`dm_host`) or from a compact device
-    // vector (`dm_dev`).  The Born field du obeys the wavefield's recursion with the distributed source w q^n, w = dC / C,
-    // in the place of the point source: the sweep runs the ordinary one-step launches of run_steps on zeroed fields (no
-    // injection, nothing stored) and adds A w q^n to du^{n+1} after step n (fwi_born.hip); the receiver sampling that
-    // rides on the next step launch then sees the completed field.  `fused` (born_fused_supported contexts): the step
-    // kernel itself adds w q^n inside q (fwi_born3d.hip) and there is no second pass.  The store is read, never written.
+    // Born modelling dd = J dm (include/fwi.h, fwi_born / fwi_born_imaging).  dm comes from the host (`dm_host`) or from a
+    // compact device vector (`dm_dev`).  The Born field du obeys the wavefield's recursion with the distributed source
+    // w q^n, w = dC / C, in the place of the point source: the sweep runs the ordinary one-step launches of run_steps on
+    // zeroed fields (no injection, nothing stored) and adds A w q^n to du^{n+1} after step n (fwi_born.hip); the receiver
+    // sampling that rides on the next step launch then sees the completed field.  `fused` (born_fused_supported
+    // contexts): the step kernel itself adds w q^n inside q (fwi_born3d.hip) and there is no second pass.  The store and
+    // the snapshots are read, never written.
+    //
+    // The imaging operator J_img (the transpose of what adjoint(image) + gradient compute on THIS context's store) is the
+    // same sweep on whatever the store holds:
+    //  - image_stride S > 1: the scattering source acts on the stored steps n % S == 0 only, from slot n / S, with the
+    //    quadrature weight S folded into w; the steps in between are plain launches, batched into one run_steps call.
+    //  - bf16 store: the slot holds bf16(C L u^n); the source's exact share w(x_s) C src^n(x_s) joins du^{n+1} through the
+    //    step launch's fused injection at the source nodes (amplitudes ctx->born_src; entries of one node summed first).
+    //  - ckpt_interval K > 0: segment by segment in ascending order, the forward state is restored from its snapshot and
+    //    the segment's q^n are recomputed into the slot buffer by the recomputation fields of the adjoint (fwd, fwv, fwx,
+    //    the forward set of memory variables); the Born field then sweeps those slots in u[], vf and the main set.
     static int born(fwi_ctx *ctx, int32_t wrt, const T *dm_host, const void *dm_dev, bool fused, T *seis_out) {
         const GridDesc &g = ctx->gd;
-        const int nt = ctx->nt, nrec = ctx->nrec;
+        const int nt = ctx->nt, nrec = ctx->nrec, S = ctx->istride, K = ctx->ckpt;
         hipStream_t s = ctx->stream;
         int rc;
         if (!ctx->born_w) HIPCHK(ctx, hipMalloc(&ctx->born_w, (size_t)g.npts * sizeof(T)));
         if (dm_host && (rc = upload_compact(ctx, ctx->born_w, dm_host))) return rc;
-        HIPCHK(ctx, launch_born_weight<T>(g, (const T *)(dm_host ? ctx->born_w : dm_dev), (const T *)ctx->c_dev,
-                                          (T *)ctx->born_w, wrt == FWI_WRT_VELOCITY, s));
+        if (S > 1)
+            HIPCHK(ctx, launch_born_weight_strided<T>(g, (const T *)(dm_host ? ctx->born_w : dm_dev), (const T *)ctx->c_dev,
+                                                      (T *)ctx->born_w, wrt == FWI_WRT_VELOCITY, S, s));
+        else
+            HIPCHK(ctx, launch_born_weight<T>(g, (const T *)(dm_host ? ctx->born_w : dm_dev), (const T *)ctx->c_dev,
+                                              (T *)ctx->born_w, wrt == FWI_WRT_VELOCITY, s));
+        const fwi_ctx::PointSet nobody;
+        const fwi_ctx::PointSet *share = &nobody;  // bf16 store: the sources, injected with the share's amplitudes
+        const T *share_amp = nullptr;
+        if (ctx->qbf16 && ctx->nsrc > 0) {
+            if constexpr (std::is_same<T, float>::value) {
+                if ((rc = ensure(ctx, &ctx->born_src, &ctx->cap_born_src, (size_t)nt * ctx->nsrc * sizeof(T)))) return rc;
+                HIPCHK(ctx, launch_born_source_share((const float *)ctx->born_w, (const int64_t *)ctx->src.cidx,
+                                                     (const float *)ctx->wav, (float *)ctx->born_src, nt, ctx->nsrc, s));
+                share = &ctx->src;
+                share_amp = (const T *)ctx->born_src;
+            } else {
+                return ctx->fail(FWI_ESTATE, "the bf16 store is fp32 only");
+            }
+        }
         ctx->have_syn = false;           // ctx->series is about to hold dd instead of the forward's synthetics
         ctx->have_dev_residual = false;  // ... and ctx->amp a copy of it, once the sweep has ended
         if ((rc = zero_fields(ctx, ctx->u[0], ctx->u[1]))) return rc;
@@ -1538,24 +1573,86 @@ struct Impl {
         if (ctx->inc) HIPCHK(ctx, hipMemsetAsync(ctx->vf, 0, (size_t)g.ptot * sizeof(T), s));
         if (ctx->cpml && (rc = pml_zero(ctx))) return rc;
         T *series = (T *)ctx->series;
-        const fwi_ctx::PointSet nobody;
         auto none = [](int) -> T * { return nullptr; };
         auto noq = [](int, const T *&p, const T *&p2) { p = p2 = nullptr; };
         const int damp = base_args(ctx, 0).damp;
+        // steps first .. first + cnt - 1 of the Born sweep; slot(n): what the store holds of step n (n % S == 0)
+        auto born_steps = [&](int first, int cnt, auto slot) -> int {
+            const int end = first + cnt;
+            for (int n = first; n < end;) {
+                if (n % S != 0) {  // up to the next stored step: the plain launches, one call
+                    const int m = std::min(end, (n / S + 1) * S) - n;
+                    sw.born_w = nullptr;
+                    if ((rc = run_steps(ctx, sw, n, 1, m, nobody, (const T *)nullptr, &ctx->rec, series, T(1), none, noq)))
+                        return rc;
+                    n += m;
+                    continue;
+                }
+                if (fused) {
+                    const int m = S == 1 ? end - n : 1;
+                    sw.born_w = ctx->born_w;
+                    auto qn = [&](int k, const T *&p, const T *&p2) { p = (const T *)slot(k); p2 = nullptr; };
+                    if ((rc = run_steps(ctx, sw, n, 1, m, *share, share_amp, &ctx->rec, series, T(1), none, qn))) return rc;
+                    n += m;
+                    continue;
+                }
+                if ((rc = run_steps(ctx, sw, n, 1, 1, *share, share_amp, &ctx->rec, series, T(1), none, noq))) return rc;
+                if (ctx->qbf16) {
+                    if constexpr (std::is_same<T, float>::value)
+                        HIPCHK(ctx, launch_born_scatter_bf16(g, (float *)sw.f[sw.cur], slot(n), (const float *)ctx->born_w,
+                                                             (const float *)ctx->dz, (const float *)ctx->dy,
+                                                             (const float *)ctx->dx, damp, s));
+                } else {
+                    HIPCHK(ctx, launch_born_scatter<T>(g, (T *)sw.f[sw.cur], (T *)sw.v, (const T *)slot(n),
+                                                       (const T *)ctx->born_w, (const T *)ctx->dz, (const T *)ctx->dy,
+                                                       (const T *)ctx->dx, damp, s));
+                }
+                ++n;
+            }
+            return FWI_OK;
+        };
+        const bool fused2d = K > 0 && use_fused(ctx, nt);  // the recomputation takes FUSED2D_STEPS steps per launch
+        void *fspare[2] = {ctx->fwx[0], ctx->fwx[1]};
         TimeLoop loop(ctx);
         if ((rc = loop.begin())) return rc;
-        const T *const qs = (const T *)ctx->q_store;
-        auto qn = [&](int n, const T *&p, const T *&p2) { p = qs + (size_t)n * g.npts; p2 = nullptr; };
-        if (fused) {
-            sw.born_w = ctx->born_w;
-            if ((rc = run_steps(ctx, sw, 0, 1, nt, nobody, (const T *)nullptr, &ctx->rec, series, T(1), none, qn))) return rc;
-        }
-        for (int n = 0; n < nt && !fused; ++n) {
-            if ((rc = run_steps(ctx, sw, n, 1, 1, nobody, (const T *)nullptr, &ctx->rec, series, T(1), none, noq)))
-                return rc;
-            HIPCHK(ctx, launch_born_scatter<T>(g, (T *)sw.f[sw.cur], (T *)sw.v, qs + (size_t)n * g.npts,
-                                               (const T *)ctx->born_w, (const T *)ctx->dz, (const T *)ctx->dy,
-                                               (const T *)ctx->dx, damp, s));
+        if (K > 0) {
+            Sweep fw;
+            fw.f[0] = ctx->fwd[0];
+            fw.f[1] = ctx->fwd[1];
+            fw.v = ctx->fwv;
+            fw.pml_fw = true;
+            T *const qs = (T *)ctx->q_store;
+            for (int n0 = 0, seg = 0; n0 < nt; n0 += K, ++seg) {
+                const int cnt = std::min(K, nt - n0);
+                const T *sn = (const T *)ctx->snap + (size_t)seg * 2 * g.ptot;
+                fw.cur = 0;
+                fw.prev_n = -1;
+                HIPCHK(ctx, hipMemcpyAsync(fw.f[0], sn, (size_t)g.ptot * sizeof(T), hipMemcpyDeviceToDevice, s));
+                HIPCHK(ctx, hipMemcpyAsync(ctx->inc ? fw.v : fw.f[1], sn + g.ptot, (size_t)g.ptot * sizeof(T),
+                                           hipMemcpyDeviceToDevice, s));
+                if (ctx->cpml && (rc = pml_snapshot(ctx, seg, true, true))) return rc;
+                if (fused2d) {
+                    rc = run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), 1,
+                                   qs - (size_t)n0 * g.npts);  // slot (n - n0)
+                } else {
+                    auto qo = [&](int n) -> T * { return qs + (size_t)(n - n0) * g.npts; };
+                    rc = run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), qo, noq);
+                }
+                if (rc) return rc;
+                if ((rc = born_steps(n0, cnt, [&](int n) -> const void * { return qs + (size_t)(n - n0) * g.npts; })))
+                    return rc;
+            }
+            if (fused2d) {  // the recomputation's buffer pairs may have changed roles: keep ownership consistent
+                ctx->fwd[0] = fw.f[0];
+                ctx->fwd[1] = fw.f[1];
+                ctx->fwx[0] = fspare[0];
+                ctx->fwx[1] = fspare[1];
+                if (ctx->inc) ctx->fwv = fw.v;
+            }
+        } else {
+            const char *const qs = (const char *)ctx->q_store;  // (slot addresses in bytes: the store may hold bf16)
+            const size_t slot_bytes = (size_t)g.npts * ctx->qes;
+            if ((rc = born_steps(0, nt, [&](int n) -> const void * { return qs + (size_t)(n / S) * slot_bytes; }))) return rc;
         }
         if ((rc = flush_record(ctx, sw, ctx->rec, series, T(1)))) return rc;
         if ((rc = loop.end())) return rc;
@@ -2079,7 +2176,8 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"snap", ctx->snap}, {"fwd", ctx->fwd[0]}, {"fwd", ctx->fwd[1]}, {"fx", ctx->fx[0]}, {"fx", ctx->fx[1]},
                   {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
                   {"pml_snap", ctx->pml_snap}, {"pml_tz", ctx->pml_tz}, {"pml_ty", ctx->pml_ty},
-                  {"fused_order", ctx->fused_order}, {"pts_a", ctx->pts_a}, {"pts_d", ctx->pts_d}};
+                  {"fused_order", ctx->fused_order}, {"pts_a", ctx->pts_a}, {"pts_d", ctx->pts_d},
+                  {"born_src", ctx->born_src}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2380,27 +2478,32 @@ int fwi_gradient_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot) {
     return DISPATCH(ctx, Impl<float>::gradient_vec(ctx, wrt, v), Impl<double>::gradient_vec(ctx, wrt, v));
 }
 
-// FWI_BORN_AUTO on a context that has both paths: decided by measurement (tools/born_probe.py)
+// FWI_BORN_AUTO on a context that has both paths: decided by measurement (tools/born_probe.py; on the
+// bf16, strided and checkpointed stores too: profiles/r06_born_modes.json)
 constexpr bool BORN_AUTO_IS_FUSED = true;
 
-// contexts whose step kernel has the Born variants of fwi_born3d.hip
+// contexts whose step kernel has the Born variants of fwi_born3d.hip (bf16 store: fwi_born3d_bf16.hip)
 static bool born_fused_supported(const fwi_ctx *ctx) {
     return ctx->gd.ndim == 3 && ctx->cfg.dtype == FWI_F32 && ctx->cfg.order == 8 && ctx->kernel == K_STREAM && !ctx->cpml;
 }
 
-// the argument and state checks fwi_born and fwi_born_vec share; *fused: the path the sweep takes
-static int born_callable(fwi_ctx *ctx, const char *who, int32_t wrt, int32_t mode, bool *fused) {
+// the argument and state checks the Born calls share; *fused: the path the sweep takes.  `imaging`: fwi_born_imaging[_vec],
+// defined on every store; the exact operator needs every q^n, in the field's type, resident at once.
+static int born_callable(fwi_ctx *ctx, const char *who, bool imaging, int32_t wrt, int32_t mode, bool *fused) {
     if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
         return ctx->fail(FWI_EINVAL, "%s: unknown parametrisation %d", who, (int)wrt);
     if (mode != FWI_BORN_AUTO && mode != FWI_BORN_SCATTER && mode != FWI_BORN_FUSED)
         return ctx->fail(FWI_EINVAL, "%s: unknown mode %d", who, (int)mode);
-    // the sweep needs every q^n, in the field's type, resident at once
-    if (ctx->istride > 1)
-        return ctx->fail(FWI_EINVAL, "%s: not available with image_stride > 1 (the store holds every %d-th step only)", who,
-                         ctx->istride);
-    if (ctx->qbf16) return ctx->fail(FWI_EINVAL, "%s: not available with store_dtype = bf16", who);
-    if (ctx->ckpt > 0)
-        return ctx->fail(FWI_EINVAL, "%s: not available with ckpt_interval > 0 (the store holds one segment at a time)", who);
+    if (!imaging) {
+        if (ctx->istride > 1)
+            return ctx->fail(FWI_EINVAL, "%s: not available with image_stride > 1 (the store holds every %d-th step only; "
+                                         "fwi_born_imaging serves this context)", who, ctx->istride);
+        if (ctx->qbf16)
+            return ctx->fail(FWI_EINVAL, "%s: not available with store_dtype = bf16 (fwi_born_imaging serves this context)", who);
+        if (ctx->ckpt > 0)
+            return ctx->fail(FWI_EINVAL, "%s: not available with ckpt_interval > 0 (the store holds one segment at a time; "
+                                         "fwi_born_imaging serves this context)", who);
+    }
     if (mode == FWI_BORN_FUSED && !born_fused_supported(ctx))
         return ctx->fail(FWI_EINVAL, "%s: FWI_BORN_FUSED: this context has no fused Born path (3-D fp32 O(8) stream "
                                      "kernel without the CPML only)", who);
@@ -2410,26 +2513,44 @@ static int born_callable(fwi_ctx *ctx, const char *who, int32_t wrt, int32_t mod
     return FWI_OK;
 }
 
-int fwi_born(fwi_ctx *ctx, int32_t wrt, const void *dm_host, int32_t mode, void *seis_out) {
+static int born_host(fwi_ctx *ctx, const char *who, bool imaging, int32_t wrt, const void *dm_host, int32_t mode,
+                     void *seis_out) {
     if (!ctx) return FWI_EINVAL;
-    if (!dm_host) return ctx->fail(FWI_EINVAL, "fwi_born: null model perturbation");
+    if (!dm_host) return ctx->fail(FWI_EINVAL, "%s: null model perturbation", who);
     bool fused = false;
-    int rc = born_callable(ctx, "fwi_born", wrt, mode, &fused);
+    int rc = born_callable(ctx, who, imaging, wrt, mode, &fused);
     if (rc) return rc;
     (void)hipSetDevice(ctx->cfg.device);
     return DISPATCH(ctx, Impl<float>::born(ctx, wrt, (const float *)dm_host, nullptr, fused, (float *)seis_out),
                     Impl<double>::born(ctx, wrt, (const double *)dm_host, nullptr, fused, (double *)seis_out));
 }
 
-int fwi_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, void *seis_out) {
+static int born_vec(fwi_ctx *ctx, const char *who, bool imaging, int32_t wrt, int32_t slot, int32_t mode, void *seis_out) {
     if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
+    void *v = vec_slot(ctx, slot);
+    if (!v) return ctx->fail(FWI_EINVAL, "%s: vector slot %d does not exist", who, (int)slot);
     bool fused = false;
-    int rc = born_callable(ctx, "fwi_born_vec", wrt, mode, &fused);
+    int rc = born_callable(ctx, who, imaging, wrt, mode, &fused);
     if (rc) return rc;
     (void)hipSetDevice(ctx->cfg.device);
     return DISPATCH(ctx, Impl<float>::born(ctx, wrt, nullptr, v, fused, (float *)seis_out),
                     Impl<double>::born(ctx, wrt, nullptr, v, fused, (double *)seis_out));
+}
+
+int fwi_born(fwi_ctx *ctx, int32_t wrt, const void *dm_host, int32_t mode, void *seis_out) {
+    return born_host(ctx, "fwi_born", false, wrt, dm_host, mode, seis_out);
+}
+
+int fwi_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, void *seis_out) {
+    return born_vec(ctx, "fwi_born_vec", false, wrt, slot, mode, seis_out);
+}
+
+int fwi_born_imaging(fwi_ctx *ctx, int32_t wrt, const void *dm_host, int32_t mode, void *seis_out) {
+    return born_host(ctx, "fwi_born_imaging", true, wrt, dm_host, mode, seis_out);
+}
+
+int fwi_born_imaging_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, void *seis_out) {
+    return born_vec(ctx, "fwi_born_imaging_vec", true, wrt, slot, mode, seis_out);
 }
 
 const char *fwi_born_path(const fwi_ctx *ctx) { return ctx ? ctx->born_path : ""; }

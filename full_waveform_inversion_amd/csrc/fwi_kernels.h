@@ -132,6 +132,10 @@ hipError_t launch_stream_r(const GridDesc &g, const StepArgs<T> &a, const Stream
 template <typename T, int R>
 hipError_t launch_stream_born(const GridDesc &g, const StepArgs<T> &a, const StreamTuning &t, hipStream_t s);
 
+// ... with q^n read from a bf16 store (a.q_bf16 set; standard form; instantiated in fwi_born3d_bf16.hip for O(8))
+template <int R>
+hipError_t launch_stream_born_bf16(const GridDesc &g, const StepArgs<float> &a, const StreamTuning &t, hipStream_t s);
+
 // out[i] = u[pidx[i]] * scale
 template <typename T>
 hipError_t launch_record(const T *u, const int64_t *pidx, T *out, T scale, int n, hipStream_t s);

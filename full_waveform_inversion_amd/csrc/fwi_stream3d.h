@@ -605,7 +605,8 @@ static hipError_t launch_stream_mode(const GridDesc &g, const StepArgs<T> &a, in
 
 // Born sweeps of the headline family (3-D, O(8), sponge or no border, standard / increment form): the IMAGE = 3 variants,
 // with their own dispatch so that only fwi_born3d.hip instantiates them.  a.q_in = q^n, a.g = w (never written).
-template <typename T, int R, int TY, bool DAMP>
+// (QB: q^n from a bf16 store -- standard form only, as that store is; instantiated by fwi_born3d_bf16.hip alone)
+template <typename T, int R, int TY, bool DAMP, bool QB = false>
 static hipError_t launch_stream_born_mode(const GridDesc &g, const StepArgs<T> &a, int zchunk, int tw, hipStream_t s) {
     const int nxt = stream_nxt(g, tw);
     const int nyt = (g.ny + TY - 1) / TY;
@@ -615,12 +616,18 @@ static hipError_t launch_stream_born_mode(const GridDesc &g, const StepArgs<T> &
     const dim3 grid(nblk + nrb), block(64, TY);
     const bool full = g.nx % (64 * VecOf<T>::VL) == 0 && g.ny % TY == 0 && tw == 64 * VecOf<T>::VL;
 #define FWI_BORN_GO(FULL, INC)                                                                                     \
-    hipLaunchKernelGGL((step3d_stream<T, R, TY, DAMP, false, 3, FULL, 1, INC>), grid, block, 0, s, a, g, zchunk, nxt, nyt, \
-                       nblk, tw)
-    if (full && a.v) FWI_BORN_GO(true, true);
-    else if (full) FWI_BORN_GO(true, false);
-    else if (a.v) FWI_BORN_GO(false, true);
-    else FWI_BORN_GO(false, false);
+    hipLaunchKernelGGL((step3d_stream<T, R, TY, DAMP, false, 3, FULL, 1, INC, QB>), grid, block, 0, s, a, g, zchunk, nxt, \
+                       nyt, nblk, tw)
+    if constexpr (QB) {
+        if (a.v) return hipErrorInvalidValue;
+        if (full) FWI_BORN_GO(true, false);
+        else FWI_BORN_GO(false, false);
+    } else {
+        if (full && a.v) FWI_BORN_GO(true, true);
+        else if (full) FWI_BORN_GO(true, false);
+        else if (a.v) FWI_BORN_GO(false, true);
+        else FWI_BORN_GO(false, false);
+    }
 #undef FWI_BORN_GO
     return hipGetLastError();
 }
@@ -633,6 +640,18 @@ hipError_t launch_stream_born(const GridDesc &g, const StepArgs<T> &a, const Str
                                  : launch_stream_born_mode<T, R, 8, true>(g, a, zc, t.tile_x, s);
     return t.ty == 4 ? launch_stream_born_mode<T, R, 4, false>(g, a, zc, t.tile_x, s)
                      : launch_stream_born_mode<T, R, 8, false>(g, a, zc, t.tile_x, s);
+}
+
+// ... with q^n read from a bf16 store (a.q_bf16; fp32, standard form): 22 B per point and step instead of 24
+template <int R>
+hipError_t launch_stream_born_bf16(const GridDesc &g, const StepArgs<float> &a, const StreamTuning &t, hipStream_t s) {
+    if (!a.q_in || !a.g || a.q_out || a.q_in2 || !a.q_bf16 || a.v || a.pml_tz || a.pml_ty || a.xp_mode)
+        return hipErrorInvalidValue;
+    const int zc = t.zchunk > 0 ? t.zchunk : g.nz;
+    if (a.damp) return t.ty == 4 ? launch_stream_born_mode<float, R, 4, true, true>(g, a, zc, t.tile_x, s)
+                                 : launch_stream_born_mode<float, R, 8, true, true>(g, a, zc, t.tile_x, s);
+    return t.ty == 4 ? launch_stream_born_mode<float, R, 4, false, true>(g, a, zc, t.tile_x, s)
+                     : launch_stream_born_mode<float, R, 8, false, true>(g, a, zc, t.tile_x, s);
 }
 
 template <typename T, int R>

@@ -270,7 +270,7 @@ class Engine:
     def allreduce_illumination(self):
         self._chk(self._lib.fwi_allreduce_illumination(self._c))
 
-    # -- Born modelling (include/fwi.h fwi_born) -----------------------------------
+    # -- Born modelling (include/fwi.h fwi_born, fwi_born_imaging) -----------------------------------
     born_leaves_residual = True  # ``born`` keeps J dm on the device as the residual of ``adjoint(None)``
 
     def _born(self, call, wrt, mode, download):
@@ -279,7 +279,14 @@ class Engine:
         self._chk(call(w, _lib.BORN_MODES[mode], out.ctypes.data_as(C.c_void_p) if download else None))
         return out
 
-    def born(self, dm, wrt="velocity", mode="auto", download=True):
+    born_operators = ("exact", "imaging")  # what ``born(..., operator=)`` accepts (shots.Shot.born asks)
+
+    def _born_call(self, operator, vec):
+        if operator not in self.born_operators:
+            raise ValueError("operator must be 'exact' or 'imaging'")
+        return getattr(self._lib, "fwi_born" + ("_imaging" if operator == "imaging" else "") + ("_vec" if vec else ""))
+
+    def born(self, dm, wrt="velocity", mode="auto", download=True, operator="exact"):
         """Linearised (Born) data ``J dm`` as ``(nt, nrec)`` at the receivers of the last ``forward(save=True)``, whose
         store it reads: the derivative of ``forward`` along the model perturbation ``dm`` (a velocity perturbation, or
         one of ``1 / c^2`` with ``wrt="slowness2"``).  The data also stay on the device as the residual of the next
@@ -287,14 +294,22 @@ class Engine:
         product ``J^T J dm``; ``download=False`` skips the copy to the host and returns None.  ``mode``: "scatter"
         (every engine), "fused" (3-D fp32 O(8) stream-kernel engines without the CPML: the scattering source inside the
         step kernel, about 0.6 - 0.75 of the time) or "auto" (fused where it exists); :attr:`born_path` names the path
-        taken.  Not available with ``image_stride > 1``, ``store_dtype="bf16"`` or ``ckpt_interval > 0``."""
-        dm = self._host(dm, self.shape)
-        return self._born(lambda w, m, o: self._lib.fwi_born(self._c, w, dm.ctypes.data_as(C.c_void_p), m, o),
-                          wrt, mode, download)
+        taken.
 
-    def born_vec(self, slot, wrt="velocity", mode="auto", download=True):
+        ``operator="exact"`` is the derivative of ``forward`` and needs a store that holds every step in the field's
+        type: it is refused with ``image_stride > 1``, ``store_dtype="bf16"`` or ``ckpt_interval > 0``.
+        ``operator="imaging"`` is the operator whose exact transpose THIS engine's ``adjoint(image)`` + ``gradient``
+        are (``fwi_born_imaging``): the same thing, bit for bit, on a plain engine and with checkpointing; with
+        ``image_stride = S`` the scattering source acts on every S-th step with weight S, with the bf16 store it is
+        formed from the rounded store.  It runs on every engine and keeps ``J^T J`` symmetric on each."""
+        dm = self._host(dm, self.shape)
+        call = self._born_call(operator, False)
+        return self._born(lambda w, m, o: call(self._c, w, dm.ctypes.data_as(C.c_void_p), m, o), wrt, mode, download)
+
+    def born_vec(self, slot, wrt="velocity", mode="auto", download=True, operator="exact"):
         """:meth:`born` with ``dm`` read from the device vector ``slot``."""
-        return self._born(lambda w, m, o: self._lib.fwi_born_vec(self._c, w, int(slot), m, o), wrt, mode, download)
+        call = self._born_call(operator, True)
+        return self._born(lambda w, m, o: call(self._c, w, int(slot), m, o), wrt, mode, download)
 
     @property
     def born_path(self):

@@ -52,9 +52,14 @@ class Shot:
         r = self.rec_spread.scatter(residual) if self.rec_spread is not None else residual
         engine.adjoint(np.ascontiguousarray(r))
 
-    def born(self, engine, dm, wrt="velocity", download=True):
-        """Born data ``J dm`` at this shot's receivers, ``(nt, nrec)``, after ``forward(engine, save=True)``."""
-        d = engine.born(dm, wrt) if download else engine.born(dm, wrt, download=False)
+    def born(self, engine, dm, wrt="velocity", download=True, operator="exact"):
+        """Born data ``J dm`` at this shot's receivers, ``(nt, nrec)``, after ``forward(engine, save=True)``.
+        ``operator`` as in :meth:`Engine.born`; an engine that names no ``born_operators`` has the one Born operator
+        its ``born(dm, wrt)`` computes, and gets no keyword."""
+        kw = {} if download else {"download": False}
+        if operator != "exact" and operator in getattr(engine, "born_operators", ()):
+            kw["operator"] = operator
+        d = engine.born(dm, wrt, **kw)
         if d is None or self._on_device(engine) or self.rec_spread is None:
             return d
         return self.rec_spread.gather(d)
@@ -390,6 +395,9 @@ def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity"):
     """Gauss-Newton Hessian-vector product ``H v = sum_s J_s^T J_s v`` at ``model``, summed over all ranks: ``v`` and
     the result are model-shaped and in the parametrisation ``wrt``.  Per shot ``forward(save=True)``, ``born``,
     ``adjoint`` -- THREE sweeps per shot and product, because the forward-term store holds one shot at a time.
+    J is the engine's imaging Born operator (``Engine.born(operator="imaging")``), the exact transpose of its
+    ``adjoint`` + ``gradient``: H is symmetric positive semi-definite on every engine -- ``image_stride``, the bf16
+    store and checkpointing included -- and is today's product, bit for bit, on a plain one.
     OVERWRITES the gradient accumulator of the engine(s) (``reset_gradient`` first, like :func:`misfit_and_gradient`).
     ``model=None`` keeps the model the engines already hold.  The shots need no observed data."""
     ex = exchange or NoExchange()
@@ -398,7 +406,7 @@ def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity"):
         if model is not None:
             e.set_model(model)
         e.reset_gradient()
-    _hvp_sweep(engine, shots, ex, lambda e, s, download: s.born(e, v, wrt, download=download))
+    _hvp_sweep(engine, shots, ex, lambda e, s, download: s.born(e, v, wrt, download=download, operator="imaging"))
     return ex.reduce(engs[0], 0.0, wrt)[0]
 
 
@@ -422,8 +430,8 @@ def gauss_newton_hvp_device(engine, model_slot, v_slot, out_slot, shots, exchang
 
     def born_one(e, s, download):
         if e is not engs[0]:
-            return s.born(e, v, wrt, download=download)
-        d = e.born_vec(v_slot, wrt, download=download)
+            return s.born(e, v, wrt, download=download, operator="imaging")
+        d = e.born_vec(v_slot, wrt, download=download, operator="imaging")
         return d if d is None or s._on_device(e) or s.rec_spread is None else s.rec_spread.gather(d)
 
     _hvp_sweep(engine, shots, ex, born_one)

@@ -36,8 +36,9 @@
 extern "C" {
 #endif
 
-/* Stays 14 with the Born calls (fwi_born, fwi_born_vec, fwi_born_path): they are purely additive -- three new symbols,
- * fwi_config and every existing call unchanged -- so a client built against the earlier 14 keeps working. */
+/* Stays 14 with the Born calls (fwi_born, fwi_born_vec, fwi_born_path; fwi_born_imaging, fwi_born_imaging_vec): they
+ * are purely additive -- new symbols, fwi_config and every existing call unchanged -- so a client built against the
+ * earlier 14 keeps working. */
 #define FWI_ABI_VERSION 14
 
 enum { FWI_F32 = 0, FWI_F64 = 1 };
@@ -244,9 +245,9 @@ int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b);    /* y := a / (
  *    H v = J^T J v is fwi_forward(save), fwi_born_vec, fwi_adjoint(NULL, image = 1), fwi_gradient_vec with no model- or
  *    data-sized PCIe transfer (seis_out == NULL skips the download).  The forward's synthetics are gone for
  *    fwi_misfit_l2 afterwards (FWI_ESTATE, the rule that holds after an adjoint).
- *  - Contexts whose store does not hold every q^n in the field's type cannot serve it: image_stride > 1,
- *    store_dtype = bf16 and ckpt_interval > 0 return FWI_EINVAL.  (Checkpointed Born -- recompute a segment, then sweep
- *    it -- is a follow-up.)
+ *  - Contexts whose store does not hold every q^n in the field's type cannot serve the EXACT derivative: on
+ *    image_stride > 1, store_dtype = bf16 and ckpt_interval > 0 fwi_born / fwi_born_vec return FWI_EINVAL.
+ *    fwi_born_imaging (below) runs on every context.
  *  - mode: FWI_BORN_SCATTER is the path above, available on every context.  FWI_BORN_FUSED carries w q^n inside the step
  *    kernel (no second pass: 24 instead of 32 B per point and step, 28 instead of 44 in increment form); it exists for
  *    3-D fp32 O(8) contexts on the stream kernel without the CPML and returns FWI_EINVAL on any other.  FWI_BORN_AUTO takes
@@ -257,6 +258,25 @@ int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b);    /* y := a / (
 enum { FWI_BORN_AUTO = 0, FWI_BORN_SCATTER = 1, FWI_BORN_FUSED = 2 };
 int fwi_born(fwi_ctx *ctx, int32_t wrt, const void *dm_host, int32_t mode, void *seis_out /* (nt, nrec) or NULL */);
 int fwi_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, void *seis_out); /* dm from a device vector */
+/* The IMAGING Born operator J_img: the operator whose exact transpose fwi_adjoint(image) + fwi_gradient are ON THIS
+ * CONTEXT'S STORE, so that H = J_img^T J_img is symmetric positive semi-definite under every store mode (conjugate
+ * gradients needs that; the exact J paired with a decimated J^T is not symmetric).  The recursion of fwi_born with the
+ * scattering source taken from what the store holds, q~:
+ *     dq^n = C (L du^n + the CPML terms of du^n) + [n % S == 0] S w q~^n,    S = image_stride
+ *  - plain store (S = 1, native type): q~^n = q^n, J_img = J; the call takes fwi_born's code path, bit for bit.
+ *  - image_stride S > 1: q~^n is slot n / S; the source acts on the stored steps only, with the quadrature weight S
+ *    (folded into w once per call).  The steps in between are plain step launches: no scatter pass, no Born variant.
+ *  - store_dtype = bf16: q~^n = bf16(C L u^n) + C src^n, the split the imaging side uses: the store's part is read as
+ *    bf16 (FUSED: 22 instead of 24 B per point and step; SCATTER: 14 instead of 16 B in its second pass), the source's
+ *    exact share w(x_s) C src^n(x_s) joins du^{n+1} at the source nodes (entries that share a node are summed first).
+ *  - ckpt_interval K > 0: J_img = J (a recomputed q^n is the stored q^n).  Segment by segment in ascending order the
+ *    forward state is restored from its snapshot, the segment's q^n are recomputed into the slot buffer and the Born
+ *    field sweeps them: one forward sweep's work more than a store-all Born sweep.  The snapshots are read, never
+ *    written.
+ * State rules, mode, the residual left for fwi_adjoint(ctx, NULL, ...), timing, launch_mode and fwi_born_path are those
+ * of fwi_born; FWI_BORN_FUSED exists on the same contexts (the bf16 store included).  No reference counterpart. */
+int fwi_born_imaging(fwi_ctx *ctx, int32_t wrt, const void *dm_host, int32_t mode, void *seis_out /* (nt, nrec) or NULL */);
+int fwi_born_imaging_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, void *seis_out);
 const char *fwi_born_path(const fwi_ctx *ctx);  /* static name of the path the last Born sweep took: "scatter", "fused";
                                                    "none" before the first */
 
