@@ -2078,8 +2078,8 @@ int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
     // two modes on two contexts side by side had shown the graph 6 - 13 % ahead on the 3-D CPML: an artefact of that set-up
     // (the stream-mode context ran 6 % slower than it does alone), which is why the A/B is done on one context now.
     if (getenv("FWI_DEBUG_PML"))
-        fprintf(stderr, "fwi: cpml=%d fused2d=%d x-in-kernel=%d line-axes=%d (ty %d zchunk %d)\n", (int)ctx->cpml,
-                (int)ctx->fused2d, (int)ctx->xpml, ctx->pml_lines, ctx->tune.ty, ctx->tune.zchunk);
+        fprintf(stderr, "fwi: cpml=%d fused2d=%d pair3d=%d x-in-kernel=%d line-axes=%d (ty %d zchunk %d)\n", (int)ctx->cpml,
+                (int)ctx->fused2d, (int)ctx->pair3d, (int)ctx->xpml, ctx->pml_lines, ctx->tune.ty, ctx->tune.zchunk);
     // 3-D CPML contexts past the cache-resident sizes place their small arrays by measurement (Impl::tune_placement).
     // FWI_PLACEMENT_TUNE: "0" = off, "pad" = padded allocations without the search (A/B hooks), "force" = also on grids
     // below the size threshold (tests: the oracle comparisons run small grids), "fixed:<k0>,<k1>,..." = on any grid, NO
