@@ -24,6 +24,7 @@
 #include "fwi_born.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
+#include "fwi_smooth.h"
 
 using namespace fwi;
 
@@ -175,6 +176,7 @@ struct fwi_ctx {
     void *series = nullptr;  // (nt, n) sampled series of the running sweep
     size_t cap_wav = 0, cap_amp = 0, cap_series = 0;
     std::vector<void *> vecs;  // optimiser vectors (compact, model-sized)
+    void *smooth_tmp = nullptr;  // compact ping-pong vector of fwi_vec_smooth; allocated by its first call
     void *pin = nullptr;     // pinned host staging for the time series
     size_t cap_pin = 0;
     // checkpointing (SURVEY s.8f-3): snapshot of (u^n, u^{n-1}) every `ckpt` steps instead of the
@@ -1924,6 +1926,23 @@ bool parse_fixed_placement(const char *s, int k[8]) {
 
 }  // namespace
 
+template <typename T>
+static int vec_smooth_passes(fwi_ctx *ctx, void *vy, const int *axis, const int *R, const double (*w)[SMOOTH_RMAX + 1],
+                             int npass) {
+    // ping-pong between the vector and the context's spare one; an odd number of passes ends in the spare: copied back
+    T *cur = (T *)vy, *other = (T *)ctx->smooth_tmp;
+    for (int p = 0; p < npass; ++p) {
+        T wt[SMOOTH_RMAX + 1];
+        for (int k = 0; k <= R[p]; ++k) wt[k] = (T)w[p][k];
+        HIPCHK(ctx, launch_smooth_axis<T>(ctx->gd, other, cur, axis[p], R[p], wt, ctx->stream));
+        std::swap(cur, other);
+    }
+    if (cur != (T *)vy)
+        HIPCHK(ctx, hipMemcpyAsync(vy, cur, (size_t)ctx->gd.npts * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+    return FWI_OK;
+}
+
+
 extern "C" {
 
 int fwi_abi_version(void) { return FWI_ABI_VERSION; }
@@ -2177,7 +2196,7 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
                   {"pml_snap", ctx->pml_snap}, {"pml_tz", ctx->pml_tz}, {"pml_ty", ctx->pml_ty},
                   {"fused_order", ctx->fused_order}, {"pts_a", ctx->pts_a}, {"pts_d", ctx->pts_d},
-                  {"born_src", ctx->born_src}};
+                  {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2695,6 +2714,41 @@ int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b) {
     HIPCHK(ctx, DISPATCH(ctx, launch_vec_recip<float>(ctx->gd, (float *)vy, a, b, ctx->stream),
                          launch_vec_recip<double>(ctx->gd, (double *)vy, a, b, ctx->stream)));
     return FWI_OK;
+}
+
+int fwi_vec_smooth(fwi_ctx *ctx, int32_t y, const double *sigma) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vy, y);
+    if (!sigma) return ctx->fail(FWI_EINVAL, "fwi_vec_smooth: null sigma");
+    const GridDesc &g = ctx->gd;
+    const int nd = g.ndim;
+    int axis[3], R[3], npass = 0;
+    double w[3][SMOOTH_RMAX + 1];
+    // applied in the order x, y, z; sigma is in grid order (z, [y,] x)
+    for (int d = nd - 1; d >= 0; --d) {
+        const double sg = sigma[d];
+        const int ax = (nd == 2 && d == 1) ? 2 : d;  // internal axis: 0 = z, 1 = y, 2 = x
+        const int n = ax == 0 ? g.nz : ax == 1 ? g.ny : g.nx;
+        if (!std::isfinite(sg) || sg < 0.0)
+            return ctx->fail(FWI_EINVAL, "fwi_vec_smooth: sigma[%d] = %g must be finite and >= 0", d, sg);
+        if (3.0 * sg + 0.5 >= (double)(SMOOTH_RMAX + 1))
+            return ctx->fail(FWI_EINVAL, "fwi_vec_smooth: sigma[%d] = %g gives a radius above %d (apply the operator twice)",
+                             d, sg, SMOOTH_RMAX);
+        const int r = smooth_radius(sg);
+        if (r > n)
+            return ctx->fail(FWI_EINVAL, "fwi_vec_smooth: sigma[%d] = %g gives radius %d, the axis has %d cells "
+                             "(one reflection only)", d, sg, r, n);
+        if (r == 0) continue;  // the identity on this axis: no launch
+        axis[npass] = ax;
+        R[npass] = r;
+        smooth_weights(sg, r, w[npass]);
+        ++npass;
+    }
+    if (npass == 0) return FWI_OK;
+    (void)hipSetDevice(ctx->cfg.device);
+    if (!ctx->smooth_tmp) HIPCHK(ctx, hipMalloc(&ctx->smooth_tmp, (size_t)g.npts * ctx->esize));
+    return DISPATCH(ctx, vec_smooth_passes<float>(ctx, vy, axis, R, w, npass),
+                    vec_smooth_passes<double>(ctx, vy, axis, R, w, npass));
 }
 
 static int allreduce_scalars(fwi_ctx *ctx, double *vals, int32_t n, ncclRedOp_t op, const char *who) {

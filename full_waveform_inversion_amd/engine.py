@@ -394,6 +394,17 @@ class Engine:
         """y = a / (y + b), elementwise, on the device."""
         self._chk(self._lib.fwi_vec_recip(self._c, y, float(a), float(b)))
 
+    def vec_smooth(self, slot, sigma):
+        """Vector ``slot`` := S slot, the separable Gaussian of width ``sigma`` cells (a scalar: the same on every axis;
+        else one width per axis in the order of ``shape``) with mirrored edges: scipy's
+        ``gaussian_filter(mode="reflect", truncate=3.0)`` on the device, in place."""
+        sg = np.atleast_1d(np.asarray(sigma, np.float64))
+        if sg.ndim != 1 or sg.size not in (1, len(self.shape)):
+            raise _lib.FwiError(_lib.EINVAL, "vec_smooth: sigma must be a scalar or %d widths, got shape %r"
+                                % (len(self.shape), tuple(np.shape(sigma))))
+        sg = np.ascontiguousarray(np.broadcast_to(sg, (len(self.shape),)))
+        self._chk(self._lib.fwi_vec_smooth(self._c, int(slot), sg.ctypes.data_as(C.POINTER(C.c_double))))
+
     def vec_clip(self, x, lo, hi):
         self._chk(self._lib.fwi_vec_clip(self._c, x, float(lo), float(hi)))
 

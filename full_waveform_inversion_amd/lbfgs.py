@@ -12,11 +12,12 @@ import os
 import numpy as np
 
 
-def save_state(path, it, x, f, g, S, Y, log, evals, history=None, bounds=None, precond=None):
+def save_state(path, it, x, f, g, S, Y, log, evals, history=None, bounds=None, precond=None, h0=None):
     """Optimiser state after iteration ``it`` (SURVEY.md s.5 "checkpoint / resume": "optimiser state save per L-BFGS
     iteration"): model, misfit, gradient, the curvature pairs oldest first, the log, and the settings a continuation
     must share (``history``, ``bounds``, the diagonal preconditioner ``precond``).  Written to a temporary file and renamed, so an interrupted run never leaves
-    a torn file behind.  In a multi-rank job only ONE rank should pass a path (every rank holds the same state)."""
+    a torn file behind.  In a multi-rank job only ONE rank should pass a path (every rank holds the same state).
+    ``h0``: the tag of the run's initial-inverse-Hessian operator (:func:`lbfgs`), recorded when there is one."""
     tmp = "%s.tmp.%d.npz" % (path, os.getpid())
     arrays = {"x": np.asarray(x), "g": np.asarray(g)}
     for i, (s, y) in enumerate(zip(S, Y)):
@@ -26,6 +27,8 @@ def save_state(path, it, x, f, g, S, Y, log, evals, history=None, bounds=None, p
         arrays["precond"] = np.asarray(precond)
     meta = {"history": None if history is None else int(history),
             "bounds": None if bounds is None else [float(bounds[0]), float(bounds[1])]}
+    if h0 is not None:
+        meta["h0"] = str(h0)
     np.savez(tmp, it=np.int64(it), f=np.float64(f), evals=np.int64(evals), npairs=np.int64(len(S)),
              log=np.frombuffer(json.dumps(log).encode(), np.uint8),
              meta=np.frombuffer(json.dumps(meta).encode(), np.uint8), **arrays)
@@ -46,7 +49,7 @@ def load_state(path):
         return st
 
 
-def _checked_resume(resume, history, bounds, shape=None, precond=None, check_precond=True):
+def _checked_resume(resume, history, bounds, shape=None, precond=None, check_precond=True, h0=None):
     """Load and validate a state for continuation: the bit-for-bit promise holds only if the continuation runs with
     the settings of the run that wrote the file, so differing ``history`` / ``bounds`` (when the file records them)
     and arrays of the wrong shape are errors, not silent changes; more pairs than ``history`` are trimmed (oldest
@@ -59,6 +62,8 @@ def _checked_resume(resume, history, bounds, shape=None, precond=None, check_pre
         b = None if bounds is None else [float(bounds[0]), float(bounds[1])]
         if st["bounds"] != b:
             raise ValueError("resume: the state was written with bounds=%r, this run has bounds=%r" % (st["bounds"], b))
+    if st.get("h0") != (None if h0 is None else str(h0)):
+        raise ValueError("resume: the state was written with h0=%r, this run has h0=%r" % (st.get("h0"), h0))
     sp = st.get("precond")
     if check_precond:  # (precond: an array, or None for none)
         if (sp is None) != (precond is None) or (sp is not None and not np.array_equal(np.asarray(sp), np.asarray(precond))):
@@ -84,7 +89,7 @@ def _search_failed(log):
 
 
 def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, c1=1e-4, max_ls=8,
-          gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None, precond=None):
+          gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None, precond=None, h0=None):
     """Minimise ``f`` given ``fg(x) -> (f, g)``.
 
     Line search: backtracking (safeguarded quadratic interpolation) until the Armijo condition holds; while no backtracking was needed and the slope
@@ -108,7 +113,16 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
     ``gamma * diag(p)`` with ``gamma = s.y / (y.(p y))``; the first step (and a restart) is ``p g`` scaled so that
     ``first_step`` bounds the largest change.  p is part of the checkpoint; resuming with another p is an error.
     ``None`` leaves the iteration exactly as without this argument.
+
+    ``h0``: a callable ``h0(q) -> B q`` applying a symmetric positive semi-definite operator B (one with a spatial
+    extent, e.g. ``shots.smoothing_h0``).  Wherever the iteration multiplies by p it applies B instead: the initial
+    inverse Hessian is ``gamma B`` with ``gamma = s.y / (y.(B y))``, the first step and a restart are ``B g`` scaled by
+    ``first_step / max |B g|``.  With ``precond`` as well, p keeps its bookkeeping (built once, saved, checked on
+    resume) and ``h0`` is responsible for using it.  A ``tag`` attribute of ``h0`` (a string naming the operator) is
+    recorded in the state file; resuming with another tag is an error.  ``None`` leaves the iteration bit for bit as
+    it is without this argument.
     """
+    h0_tag = getattr(h0, "tag", None)
     dot = dot or (lambda a, b: float(np.sum(np.multiply(a, b, dtype=np.float64))))  # no BLAS threads
     if int(history) < 1:
         raise ValueError("history must be >= 1")
@@ -120,7 +134,7 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
     pc = None if precond is None or callable(precond) else np.asarray(precond)
     if resume is not None:
         st = _checked_resume(resume, history, bounds, None if x0 is None else np.shape(x0), pc,
-                             check_precond=not callable(precond))
+                             check_precond=not callable(precond), h0=h0_tag)
         if callable(precond):
             pc = np.asarray(st["precond"])
         x, f, g, S, Y = st["x"], st["f"], st["g"], list(st["S"]), list(st["Y"])
@@ -138,7 +152,7 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
         if pc is not None and not (pc.shape == np.shape(g) and np.all(pc > 0) and np.all(np.isfinite(pc))):
             raise ValueError("precond must be finite, > 0 and shaped like the model")
         if checkpoint:
-            save_state(checkpoint, 0, x, f, g, S, Y, log, evals, history, bounds, pc)
+            save_state(checkpoint, 0, x, f, g, S, Y, log, evals, history, bounds, pc, h0_tag)
     for it in range(it0 + 1, maxiter + 1):
         if not float(np.abs(g).max()) > gtol:
             break  # stationary (or projected onto a bound everywhere)
@@ -149,7 +163,13 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
             a = rho * dot(s, q)
             q -= a * y
             al.append((a, rho))
-        if pc is not None:  # initial inverse Hessian gamma diag(p)
+        if h0 is not None:  # initial inverse Hessian gamma B
+            q = np.array(h0(q), copy=True)
+            if S:
+                q *= dot(S[-1], Y[-1]) / dot(Y[-1], h0(Y[-1]))
+            else:
+                q *= (first_step if first_step is not None else 1.0) / float(np.abs(q).max())
+        elif pc is not None:  # initial inverse Hessian gamma diag(p)
             q *= pc
             if S:
                 q *= dot(S[-1], Y[-1]) / dot(Y[-1], pc * Y[-1])
@@ -167,7 +187,7 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
         gp = dot(g, p)
         if not gp < 0.0:  # not a descent direction: restart from steepest descent
             S, Y = [], []
-            p = -g if pc is None else -(pc * g)
+            p = -h0(g) if h0 is not None else -g if pc is None else -(pc * g)
             p = p * ((first_step if first_step is not None else 1.0) / float(np.abs(p).max()))
             gp = dot(g, p)
         t, best, shrunk = 1.0, None, False
@@ -188,7 +208,7 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
         if best is None:
             log.append({"iter": it, "f": f, "evals": evals, "note": "line search failed"})
             if checkpoint:  # the terminal entry too: a resumed run must not repeat the failed search
-                save_state(checkpoint, it - 1, x, f, g, S, Y, log, evals, history, bounds, pc)
+                save_state(checkpoint, it - 1, x, f, g, S, Y, log, evals, history, bounds, pc, h0_tag)
             break
         t, fn, xn, gn = best
         s, y = xn - x, gn - g
@@ -202,7 +222,7 @@ def lbfgs(fg, x0, maxiter=5, history=5, first_step=None, bounds=None, dot=None, 
         _require_finite(f, float(np.abs(g).max()), dot(g, g), it)
         log.append({"iter": it, "f": f, "evals": evals, "step": t})
         if checkpoint:
-            save_state(checkpoint, it, x, f, g, S, Y, log, evals, history, bounds, pc)
+            save_state(checkpoint, it, x, f, g, S, Y, log, evals, history, bounds, pc, h0_tag)
         if callback:
             callback(it, x, f, g)
     return x, f, log
@@ -231,7 +251,7 @@ def lbfgs_device_slots(history=5):
 
 
 def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=None, c1=1e-4, max_ls=8,
-                 gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None, precond_slot=None):
+                 gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None, precond_slot=None, h0=None):
     """The same iteration as :func:`lbfgs` with every model-sized vector resident on the GPU
     (``Engine.vec_*`` slots): per iteration only scalars cross PCIe.
 
@@ -247,6 +267,13 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
     preconditioner p of :func:`lbfgs`.  ``fg`` fills it during the first evaluation
     (``shots.preconditioned_fg_device``); it stays fixed afterwards, is saved with the state and, on resume, is
     restored from it before any evaluation.
+
+    ``h0``: the operator B of :func:`lbfgs` as a callable ``h0(slot)`` that applies it to a vector slot in place
+    (``shots.smoothing_h0_device``); it takes the place of the multiplication by p in the same three spots, and with
+    ``precond_slot`` as well the slot keeps its bookkeeping while ``h0`` is responsible for reading it.  An ``h0`` that
+    needs vector slots of its own says how many in an ``nslots`` attribute: they are created behind the optimiser's
+    (and the preconditioner's), and ``h0.setup(first_slot)`` is called once after ``vec_create`` -- on resume too --
+    to fill them.  ``h0.tag`` is recorded and checked as in :func:`lbfgs`.
     """
     m = int(history)
     if m < 1:
@@ -262,17 +289,27 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
             raise ValueError("precond_slot must be >= %d (the optimiser's own slots come first)" % nslots)
         PC = int(PC)
         nslots = PC + 1
-    engine.vec_create(nslots)
+    h0_tag = getattr(h0, "tag", None)
+    engine.vec_create(nslots + int(getattr(h0, "nslots", 0)))
+    if hasattr(h0, "setup"):
+        h0.setup(nslots)
+    if h0 is not None:
+        B = h0
+    elif PC is not None:
+        def B(slot):
+            engine.vec_mul(slot, PC)
+    else:
+        B = None
     pairs = []  # ring of (s_slot, y_slot), oldest first
     free = list(range(m + 1))
 
     def save(it, f, log, evals):
         save_state(checkpoint, it, engine.vec_download(X), f, engine.vec_download(G),
                    [engine.vec_download(s) for s, _ in pairs], [engine.vec_download(y) for _, y in pairs], log, evals,
-                   m, bounds, None if PC is None else engine.vec_download(PC))
+                   m, bounds, None if PC is None else engine.vec_download(PC), h0_tag)
 
     if resume is not None:
-        st = _checked_resume(resume, m, bounds, getattr(engine, "shape", None), check_precond=PC is None)
+        st = _checked_resume(resume, m, bounds, getattr(engine, "shape", None), check_precond=PC is None, h0=h0_tag)
         if _search_failed(st["log"]):
             return np.asarray(st["x"]), st["f"], list(st["log"])
         if PC is not None:
@@ -309,12 +346,12 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
             a = rho * engine.vec_dot(s, P)
             engine.vec_axpby(P, -a, y, 1.0)
             al.append((a, rho))
-        if PC is not None:  # initial inverse Hessian gamma diag(p); GN is free until the line search
-            engine.vec_mul(P, PC)
+        if B is not None:  # initial inverse Hessian gamma diag(p) or gamma B; GN is free until the line search
+            B(P)
             if pairs:
                 s, y = pairs[-1]
                 engine.vec_copy(GN, y)
-                engine.vec_mul(GN, PC)
+                B(GN)
                 engine.vec_axpby(P, 0.0, P, engine.vec_dot(s, y) / engine.vec_dot(y, GN))
             else:
                 engine.vec_axpby(P, 0.0, P, (first_step if first_step is not None else 1.0) / engine.vec_absmax(P))
@@ -331,10 +368,10 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
             free += [s - S0 for s, _ in pairs]
             pairs = []
             engine.vec_copy(P, G)
-            if PC is not None:
-                engine.vec_mul(P, PC)
+            if B is not None:
+                B(P)
             engine.vec_axpby(P, 0.0, P, (first_step if first_step is not None else 1.0)
-                             / (gmax if PC is None else engine.vec_absmax(P)))
+                             / (gmax if B is None else engine.vec_absmax(P)))
             gp = -engine.vec_dot(G, P)
         t, best, shrunk = 1.0, None, False
         for _ in range(max_ls):  # the same search as lbfgs(): Armijo backtracking, Wolfe-curvature expansion

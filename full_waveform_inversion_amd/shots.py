@@ -485,3 +485,138 @@ def preconditioned_fg_device(engine, shots, precond_slot, eps=ILLUMINATION_EPS, 
 def engine_of(engine):
     """The engine that holds the optimiser's vectors (the primary one of a pool)."""
     return _engines(engine)[0]
+
+
+# -- Gaussian model-space smoothing as the initial inverse Hessian of the L-BFGS (DESIGN.md s.4f) -----------------------
+
+def _axis_widths(sigma, ndim):
+    s = np.atleast_1d(np.asarray(sigma, np.float64))
+    if s.ndim != 1 or s.size not in (1, ndim) or not np.all(np.isfinite(s)) or np.any(s < 0.0):
+        raise ValueError("sigma must be a finite width >= 0, or one per axis (%d), got %r" % (ndim, sigma))
+    return tuple(float(v) for v in np.broadcast_to(s, (ndim,)))
+
+
+def gaussian_smooth(x, sigma):
+    """The operator of ``Engine.vec_smooth`` in NumPy: per axis ``R = int(3 sigma + 0.5)``, normalised weights
+    ``exp(-k^2 / 2 sigma^2)``, half-sample mirror at both ends (one reflection: ``R <= n``).  Equals
+    ``scipy.ndimage.gaussian_filter(x, sigma, mode="reflect", truncate=3.0)``; used when scipy is not installed."""
+    x = np.asarray(x)
+    out = x
+    for ax, sg in reversed(list(enumerate(_axis_widths(sigma, x.ndim)))):  # x first, z last
+        R = int(3.0 * sg + 0.5)
+        if R == 0:
+            continue
+        n = x.shape[ax]
+        if R > n:
+            raise ValueError("sigma=%g gives radius %d on an axis of %d cells (one reflection only)" % (sg, R, n))
+        k = np.arange(-R, R + 1)
+        w = np.exp(-0.5 * (k / sg) ** 2)
+        w /= w.sum()
+        a = np.moveaxis(out, ax, 0)
+        pad = np.concatenate([a[:R][::-1], a, a[n - R:][::-1]], 0)
+        acc = np.zeros(a.shape, np.result_type(x.dtype, np.float64))
+        for j in range(2 * R + 1):
+            acc += w[j] * pad[j:j + n]
+        out = np.moveaxis(acc.astype(x.dtype, copy=False), 0, ax)
+    return out
+
+
+def _default_smooth():
+    try:
+        from scipy.ndimage import gaussian_filter
+    except ImportError:
+        return gaussian_smooth
+    return lambda x, sigma: gaussian_filter(x, sigma, mode="reflect", truncate=3.0)
+
+
+def _h0_tag(sigma, mask, with_precond):
+    import zlib
+    crc = None if mask is None else zlib.crc32(np.ascontiguousarray(mask, np.float64).tobytes())
+    return "gauss(sigma=%r,mask=%r,precond=%d)" % (list(sigma), crc, int(bool(with_precond)))
+
+
+def _checked_mask(mask):
+    m = np.asarray(mask, np.float64)
+    if not (np.all(m >= 0.0) and np.all(m <= 1.0)):
+        raise ValueError("mask must lie in [0, 1]")
+    return m
+
+
+def smoothing_h0(sigma, mask=None, precond=None, smooth=None):
+    """``h0`` for :func:`lbfgs.lbfgs`: ``B = M S' D S' M`` with ``S'`` the Gaussian of width ``sigma / sqrt(2)`` (so
+    that with D = M = I the composite has width ``sigma``), ``D = diag(precond)`` (an array, or a callable returning
+    it when B is first applied; None: I) and ``M = diag(mask)`` (model-shaped, in [0, 1]; None: I).  B = A A^T with
+    A = M S' D^(1/2): symmetric positive semi-definite whatever the spectrum of S', so ``-B g`` descends; cells with
+    ``mask == 0`` never move.  ``smooth(x, sigma_per_axis)``: the filter (default scipy's
+    ``gaussian_filter(mode="reflect", truncate=3.0)`` when scipy imports, else :func:`gaussian_smooth`)."""
+    smooth = smooth or _default_smooth()
+    M = None if mask is None else _checked_mask(mask)
+    cache = {}
+
+    def h0(q):
+        q = np.asarray(q)
+        s1 = cache.get("s1")
+        if s1 is None:
+            s1 = cache["s1"] = tuple(v / np.sqrt(2.0) for v in _axis_widths(sigma, q.ndim))
+            cache["M"] = None if M is None else M.astype(q.dtype)
+            cache["D"] = None if precond is None else np.asarray(precond() if callable(precond) else precond, q.dtype)
+        v = q if cache["M"] is None else q * cache["M"]
+        v = smooth(v, s1)
+        if cache["D"] is not None:
+            v = v * cache["D"]
+        v = smooth(v, s1)
+        return np.asarray(v if cache["M"] is None else v * cache["M"])
+
+    h0.tag = _h0_tag(np.atleast_1d(np.asarray(sigma, np.float64)).tolist(), M, precond is not None)
+    return h0
+
+
+def smoothing_h0_device(engine, sigma, mask=None, precond_slot=None):
+    """:func:`smoothing_h0` on device vectors, for :func:`lbfgs.lbfgs_device`: ``h0(slot)`` applies
+    ``B = M S' D S' M`` in place with ``Engine.vec_mul`` and ``Engine.vec_smooth`` -- nothing model-sized crosses PCIe.
+    D is read from ``precond_slot`` when B is applied; the mask is uploaded once into the one slot ``lbfgs_device``
+    creates for it (``h0.nslots`` / ``h0.setup``).  Same tag as the host twin: a state file moves between the two."""
+    e = engine_of(engine)
+    s1 = tuple(v / np.sqrt(2.0) for v in _axis_widths(sigma, len(e.shape)))
+    M = None if mask is None else _checked_mask(mask)
+    if M is not None and M.shape != tuple(e.shape):
+        raise ValueError("mask has shape %r, the grid %r" % (M.shape, tuple(e.shape)))
+    where = {}
+
+    def h0(slot):
+        if M is not None:
+            e.vec_mul(slot, where["mask"])
+        e.vec_smooth(slot, s1)
+        if precond_slot is not None:
+            e.vec_mul(slot, precond_slot)
+        e.vec_smooth(slot, s1)
+        if M is not None:
+            e.vec_mul(slot, where["mask"])
+
+    def setup(first_slot):
+        if M is not None:
+            where["mask"] = int(first_slot)
+            e.vec_upload(where["mask"], M)
+
+    h0.nslots = 0 if M is None else 1
+    h0.setup = setup
+    h0.tag = _h0_tag(np.atleast_1d(np.asarray(sigma, np.float64)).tolist(), M, precond_slot is not None)
+    return h0
+
+
+def source_mute(shape, shots, radius):
+    """Mask ``1 - exp(-(d / radius)^2)``, d the distance in cells to the nearest source node of ``shots``: 0 on the
+    sources, ~1 a few radii away.  Damps the source imprint of the gradient (host NumPy, built once)."""
+    if not float(radius) > 0.0:
+        raise ValueError("radius must be > 0")
+    src = np.unique(np.concatenate([np.asarray(s.src_idx).reshape(-1, len(shape)) for s in shots], 0), axis=0)
+    axes = [np.arange(n, dtype=np.float64) for n in shape]
+    d2 = np.full(shape, np.inf)
+    for node in src:
+        t = np.zeros(shape)
+        for ax, (a, c) in enumerate(zip(axes, node)):
+            sh_ = [1] * len(shape)
+            sh_[ax] = -1
+            t = t + ((a - float(c)) ** 2).reshape(sh_)
+        np.minimum(d2, t, out=d2)
+    return 1.0 - np.exp(-d2 / float(radius) ** 2)

@@ -226,6 +226,17 @@ int fwi_allreduce_illumination(fwi_ctx *ctx);  /* in-place sum over the ranks of
 int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x);               /* y := x * y */
 int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b);    /* y := a / (y + b) */
 
+/* Gaussian smoothing of a vector slot, in place and stream-ordered like fwi_vec_axpby: y := S y, S = S_z S_y S_x applied
+ * in the order x, y, z.  `sigma`: ndim widths in cells, in grid order (z, [y,] x).  Per axis of n cells and width s:
+ *   R = int(3 s + 0.5),  w_k = exp(-k^2 / 2 s^2) / sum_{j=-R..R} exp(-j^2 / 2 s^2),  (S_s x)_i = sum_k w_k x_rho(i+k),
+ * rho the half-sample mirror (rho(j) = -1 - j for j < 0, 2 n - 1 - j for j >= n): scipy.ndimage.gaussian_filter with
+ * mode="reflect", truncate=3.0.  S is symmetric and preserves constants (it is not positive semi-definite on its own).
+ * s = 0 is the identity on that axis (no launch).  FWI_EINVAL: a negative or non-finite width, R > 32, R > n (one
+ * reflection only), a slot that does not exist.  The weights are formed in fp64 and rounded to the context's dtype; the
+ * summation order is fixed, so equal inputs give equal bits on every call and rank.  Pad columns stay zero.  The
+ * ping-pong vector is the context's own (allocated by the first call, freed by fwi_destroy).  No reference counterpart. */
+int fwi_vec_smooth(fwi_ctx *ctx, int32_t y, const double *sigma);
+
 /* Born (linearised) modelling dd = J dm: the exact derivative of the discrete fwi_forward along a model perturbation,
  * whose exact transpose is fwi_adjoint(image) + fwi_gradient.  With C = dt^2 c^2 and q^n the forward term the store of
  * fwi_forward(save != 0) holds for every step (q^n = C (L u^n + PML terms + src^n)):

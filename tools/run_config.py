@@ -39,6 +39,12 @@ def main():
     ap.add_argument("--precondition", nargs="?", type=float, const=sh.ILLUMINATION_EPS, default=None, metavar="EPS",
                     help="L-BFGS with the source-illumination preconditioner p = 1 / (H / max H + EPS), built from the "
                          "first evaluation (default EPS %g); off when absent" % sh.ILLUMINATION_EPS)
+    ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
+                    help="L-BFGS initial inverse Hessian B = M S' D S' M: Gaussian smoothing of width SIGMA cells "
+                         "(shots.smoothing_h0_device), D the --precondition diagonal when given; off when absent")
+    ap.add_argument("--mute-sources", type=float, default=None, metavar="RADIUS",
+                    help="mask M = 1 - exp(-(d / RADIUS)^2) around the source nodes (shots.source_mute), applied inside "
+                         "the --smooth operator (SIGMA 0 when --smooth is absent)")
     a = ap.parse_args()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -94,8 +100,12 @@ def main():
     m0 = w.c_init.astype(np.float32)
     ckpt = a.checkpoint if (a.checkpoint and rank == 0) else None  # every rank holds the same state: one writer
     bounds = (0.5 * float(w.c.min()), 1.5 * float(w.c.max()))
+    use_h0 = a.smooth is not None or a.mute_sources is not None
+    h0_sigma = a.smooth if a.smooth is not None else 0.0
+    mute = sh.source_mute(w.shape, shots, a.mute_sources) if a.mute_sources is not None else None
     if a.iters > 0 and not a.host_lbfgs:
         pslot = lbfgs_device_slots(5) if eps is not None else None
+        h0 = sh.smoothing_h0_device(pool, h0_sigma, mask=mute, precond_slot=pslot) if use_h0 else None
         fg_p = sh.preconditioned_fg_device(pool, shots, pslot, eps, ex) if eps is not None else None
 
         def fg_dev(xs, gs):
@@ -104,11 +114,24 @@ def main():
                 return fg_p(xs, gs)
             return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex)
         _, _, log = lbfgs_device(e, fg_dev, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
-                                 bounds=bounds, checkpoint=ckpt, resume=a.resume or None, precond_slot=pslot)
+                                 bounds=bounds, checkpoint=ckpt, resume=a.resume or None, precond_slot=pslot, h0=h0)
     elif a.iters > 0:
         pc = (lambda x, f, g: sh.illumination_preconditioner(first_H[0], eps)) if eps is not None else None
+        held = {}
+
+        def pc_keep(x, f, g):  # the optimiser builds p once (or restores it on resume); the h0 below reads it
+            held["p"] = pc(x, f, g)
+            return held["p"]
+
+        def p_of_run():
+            if "p" not in held:  # resumed: the optimiser took p from the state file
+                from full_waveform_inversion_amd.lbfgs import load_state
+                held["p"] = load_state(a.resume)["precond"]
+            return held["p"]
+        h0 = sh.smoothing_h0(h0_sigma, mask=mute, precond=p_of_run if eps is not None else None) if use_h0 else None
         _, _, log = lbfgs(fg_host, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
-                          bounds=bounds, dot=e.dot, checkpoint=ckpt, resume=a.resume or None, precond=pc)
+                          bounds=bounds, dot=e.dot, checkpoint=ckpt, resume=a.resume or None,
+                          precond=pc_keep if pc is not None else None, h0=h0)
     else:
         J, g = fg(m0)
         log = [{"iter": 0, "f": J, "gnorm": float(np.sqrt(e.dot(g, g)))}]
@@ -119,7 +142,8 @@ def main():
                           "n_gpus": world, "rccl_ranks": getattr(ex, "rccl_ranks", None), "engines_per_gpu": psize, "evaluations": evals[0], "seconds": round(el, 3),
                           "Gpts_per_s_fwd_plus_adj": round(upd / el / 1e9, 2), "kernel": e.kernel_name,
                           "update_form": e.update_form, "abc": a.abc, "launch_mode": a.launch_mode,
-                          "precondition_eps": eps, "log": log}))
+                          "precondition_eps": eps, "smooth_sigma": a.smooth,
+                          "mute_sources_radius": a.mute_sources, "log": log}))
     pool.close()
     if rdzv is not None:
         rdzv.barrier()
