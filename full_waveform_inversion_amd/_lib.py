@@ -24,6 +24,7 @@ ABCS = {"sponge": 0, "cpml": 1}
 STORE_DTYPES = {"native": 0, "bf16": 1}
 LAUNCH_MODES = {"auto": 0, "stream": 1, "graph": 2}
 BORN_MODES = {"auto": 0, "scatter": 1, "fused": 2}
+REG_KINDS = {"tikhonov": 0, "tv": 1}
 UNIQUE_ID_BYTES = 128
 EINVAL = 1
 ERROR_NAMES = {1: "FWI_EINVAL", 2: "FWI_EHIP", 3: "FWI_ESTATE", 4: "FWI_ENOMEM", 5: "FWI_ECOMM"}
@@ -95,6 +96,7 @@ SIGNATURES = {
     "fwi_vec_mul": (C.c_int, [_P, _I32, _I32]),
     "fwi_vec_recip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_vec_smooth": (C.c_int, [_P, _I32, C.POINTER(_D)]),
+    "fwi_vec_regularizer": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _D, _D, C.POINTER(_D), _D, C.POINTER(_D)]),
     "fwi_born": (C.c_int, [_P, _I32, _P, _I32, _P]),
     "fwi_born_vec": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "fwi_born_imaging": (C.c_int, [_P, _I32, _P, _I32, _P]),

@@ -24,6 +24,7 @@
 #include "fwi_born.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
+#include "fwi_reg.h"
 #include "fwi_smooth.h"
 
 using namespace fwi;
@@ -177,6 +178,7 @@ struct fwi_ctx {
     size_t cap_wav = 0, cap_amp = 0, cap_series = 0;
     std::vector<void *> vecs;  // optimiser vectors (compact, model-sized)
     void *smooth_tmp = nullptr;  // compact ping-pong vector of fwi_vec_smooth; allocated by its first call
+    void *reg_part = nullptr;    // block partial sums (and their total) of fwi_vec_regularizer; allocated by its first call
     void *pin = nullptr;     // pinned host staging for the time series
     size_t cap_pin = 0;
     // checkpointing (SURVEY s.8f-3): snapshot of (u^n, u^{n-1}) every `ckpt` steps instead of the
@@ -1942,6 +1944,21 @@ static int vec_smooth_passes(fwi_ctx *ctx, void *vy, const int *axis, const int 
     return FWI_OK;
 }
 
+template <typename T>
+static int vec_regularizer(fwi_ctx *ctx, int32_t kind, const void *x, const void *x0, const void *v, void *out,
+                           double alpha, double beta, const double w[3], double eps, double *value_out) {
+    const int64_t nb = reg_blocks<T>(ctx->gd);
+    if (!ctx->reg_part) HIPCHK(ctx, hipMalloc(&ctx->reg_part, (size_t)(nb + 1) * sizeof(double)));
+    double *part = (double *)ctx->reg_part;
+    HIPCHK(ctx, launch_regularizer<T>(ctx->gd, kind, (T *)out, (const T *)x, (const T *)x0, (const T *)v, alpha, beta, w,
+                                      eps, part, ctx->stream));
+    if (value_out) {
+        HIPCHK(ctx, hipMemcpyAsync(value_out, part + nb, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return FWI_OK;
+}
+
 
 extern "C" {
 
@@ -2196,7 +2213,7 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
                   {"pml_snap", ctx->pml_snap}, {"pml_tz", ctx->pml_tz}, {"pml_ty", ctx->pml_ty},
                   {"fused_order", ctx->fused_order}, {"pts_a", ctx->pts_a}, {"pts_d", ctx->pts_d},
-                  {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}};
+                  {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}, {"reg_part", ctx->reg_part}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2749,6 +2766,40 @@ int fwi_vec_smooth(fwi_ctx *ctx, int32_t y, const double *sigma) {
     if (!ctx->smooth_tmp) HIPCHK(ctx, hipMalloc(&ctx->smooth_tmp, (size_t)g.npts * ctx->esize));
     return DISPATCH(ctx, vec_smooth_passes<float>(ctx, vy, axis, R, w, npass),
                     vec_smooth_passes<double>(ctx, vy, axis, R, w, npass));
+}
+
+int fwi_vec_regularizer(fwi_ctx *ctx, int32_t kind, int32_t x, int32_t x0, int32_t v, int32_t out, double alpha,
+                        double beta, const double *weight, double eps, double *value_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (kind != FWI_REG_TIKHONOV && kind != FWI_REG_TV)
+        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: unknown kind %d", (int)kind);
+    void *vx = vec_slot(ctx, x), *vx0 = nullptr, *vv = nullptr, *vout = nullptr;
+    if (!vx) return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: x: vector slot %d does not exist", (int)x);
+    if (x0 != -1 && !(vx0 = vec_slot(ctx, x0)))
+        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: x0: vector slot %d does not exist", (int)x0);
+    if (v != -1 && !(vv = vec_slot(ctx, v)))
+        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: v: vector slot %d does not exist", (int)v);
+    if (out != -1 && !(vout = vec_slot(ctx, out)))
+        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: out: vector slot %d does not exist", (int)out);
+    if (vout && (vout == vx || vout == vx0 || vout == vv))
+        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: out (slot %d) must not alias %s", (int)out,
+                         vout == vx ? "x" : vout == vx0 ? "x0" : "v");
+    if (!vout && !value_out)
+        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: out == -1 and value_out == NULL: nothing to do");
+    if (!weight) return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: null weight");
+    const int nd = ctx->gd.ndim;
+    for (int d = 0; d < nd; ++d)
+        if (!std::isfinite(weight[d]) || weight[d] < 0.0)
+            return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: weight[%d] = %g must be finite and >= 0", d, weight[d]);
+    if (kind == FWI_REG_TV && (!std::isfinite(eps) || eps <= 0.0))
+        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: eps = %g must be finite and > 0 for total variation", eps);
+    if (!std::isfinite(alpha)) return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: alpha = %g must be finite", alpha);
+    if (!std::isfinite(beta)) return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: beta = %g must be finite", beta);
+    const double w[3] = {weight[0], nd == 3 ? weight[1] : 0.0, weight[nd - 1]};  // z, y, x
+    if (kind != FWI_REG_TV) eps = 0.0;
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, vec_regularizer<float>(ctx, kind, vx, vx0, vv, vout, alpha, beta, w, eps, value_out),
+                    vec_regularizer<double>(ctx, kind, vx, vx0, vv, vout, alpha, beta, w, eps, value_out));
 }
 
 static int allreduce_scalars(fwi_ctx *ctx, double *vals, int32_t n, ncclRedOp_t op, const char *who) {

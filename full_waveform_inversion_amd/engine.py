@@ -405,6 +405,32 @@ class Engine:
         sg = np.ascontiguousarray(np.broadcast_to(sg, (len(self.shape),)))
         self._chk(self._lib.fwi_vec_smooth(self._c, int(slot), sg.ctypes.data_as(C.POINTER(C.c_double))))
 
+    def vec_regularizer(self, x, out=None, kind="tv", x0=None, v=None, alpha=1.0, beta=0.0, weight=1.0, eps=None):
+        """First-order Tikhonov (``kind="tikhonov"``) or smoothed isotropic total variation (``"tv"``, with ``eps`` > 0)
+        of d = slot ``x`` - slot ``x0`` (``x0=None``: d = x): returns R(d) and, with a slot ``out``, sets
+        ``out := alpha L(d; v) + beta out`` on the device (``v=None``: v = d, L(d; d) is the gradient of R; for fixed d, L
+        is the symmetric positive semi-definite operator sum_a w_a D_a' diag(k(d)) D_a; ``include/fwi.h``).  ``weight``: a
+        scalar for every axis, else one weight per axis in the order of ``shape``.  The host twin is
+        :mod:`full_waveform_inversion_amd.regularizers`."""
+        w = np.atleast_1d(np.asarray(weight, np.float64))
+        if w.ndim != 1 or w.size not in (1, len(self.shape)):
+            raise _lib.FwiError(_lib.EINVAL, "vec_regularizer: weight must be a scalar or %d weights, got shape %r"
+                                % (len(self.shape), tuple(np.shape(weight))))
+        w = np.ascontiguousarray(np.broadcast_to(w, (len(self.shape),)))
+        k = _lib.REG_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+        if isinstance(k, str):
+            raise _lib.FwiError(_lib.EINVAL, "vec_regularizer: unknown kind %r (one of %s)" % (kind, sorted(_lib.REG_KINDS)))
+        if eps is None:
+            if k == _lib.REG_KINDS["tv"]:
+                raise _lib.FwiError(_lib.EINVAL, "vec_regularizer: total variation needs eps > 0")
+            eps = 0.0
+        slot = lambda s: -1 if s is None else int(s)  # noqa: E731
+        val = C.c_double(0.0)
+        self._chk(self._lib.fwi_vec_regularizer(self._c, int(k), int(x), slot(x0), slot(v), slot(out), float(alpha),
+                                                float(beta), w.ctypes.data_as(C.POINTER(C.c_double)), float(eps),
+                                                C.byref(val)))
+        return val.value
+
     def vec_clip(self, x, lo, hi):
         self._chk(self._lib.fwi_vec_clip(self._c, x, float(lo), float(hi)))
 

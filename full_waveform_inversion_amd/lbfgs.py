@@ -251,7 +251,8 @@ def lbfgs_device_slots(history=5):
 
 
 def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=None, c1=1e-4, max_ls=8,
-                 gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None, precond_slot=None, h0=None):
+                 gtol=0.0, callback=None, c2=0.9, checkpoint=None, resume=None, precond_slot=None, h0=None,
+                 extra_slots=0):
     """The same iteration as :func:`lbfgs` with every model-sized vector resident on the GPU
     (``Engine.vec_*`` slots): per iteration only scalars cross PCIe.
 
@@ -274,6 +275,9 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
     needs vector slots of its own says how many in an ``nslots`` attribute: they are created behind the optimiser's
     (and the preconditioner's), and ``h0.setup(first_slot)`` is called once after ``vec_create`` -- on resume too --
     to fill them.  ``h0.tag`` is recorded and checked as in :func:`lbfgs`.
+
+    ``extra_slots``: that many more slots, zeroed, are created behind all of these for ``fg``'s own use (the prior model
+    of ``regularizers.regularized_fg_device``: ``regularizers.prior_slot`` says which).
     """
     m = int(history)
     if m < 1:
@@ -290,7 +294,7 @@ def lbfgs_device(engine, fg, x0, maxiter=5, history=5, first_step=None, bounds=N
         PC = int(PC)
         nslots = PC + 1
     h0_tag = getattr(h0, "tag", None)
-    engine.vec_create(nslots + int(getattr(h0, "nslots", 0)))
+    engine.vec_create(nslots + int(getattr(h0, "nslots", 0)) + int(extra_slots))
     if hasattr(h0, "setup"):
         h0.setup(nslots)
     if h0 is not None:

@@ -61,12 +61,16 @@ def cg(hvp, b, x0=None, precond=None, maxiter=20, rtol=1e-6, callback=None):
 
 
 def gauss_newton_step(engine, model, shots, g, exchange=None, wrt="velocity", precond=None, maxiter=10, rtol=1e-2,
-                      damping=0.0, callback=None):
+                      damping=0.0, callback=None, regularizer=None):
     """The (truncated) Gauss-Newton step ``p``: ``(H_GN + damping I) p = -g`` at ``model`` by :func:`cg`, with ``g``
     the gradient ``shots.misfit_and_gradient`` returned there (same ``wrt``).  ``precond`` as in :func:`cg`; the
     illumination preconditioner of ``shots.illumination_preconditioner`` fits (the illumination is the diagonal of the
     pseudo-Hessian).  Every inner iteration is one ``shots.gauss_newton_hvp``: three sweeps per shot, and the engine's
-    gradient accumulator is overwritten.  Returns ``(p, log)`` (``log`` as :func:`cg`)."""
+    gradient accumulator is overwritten.  Returns ``(p, log)`` (``log`` as :func:`cg`).
+
+    ``regularizer``: a ``regularizers.Regularizer``; its symmetric positive semi-definite term ``lam L(model - x0; v)``
+    is added to every product (host fp64), for a ``g`` that already holds its gradient
+    (``regularizers.regularized_fg``).  None: no such term."""
     from .shots import _engines, gauss_newton_hvp
     for e in _engines(engine):
         e.set_model(model)
@@ -75,6 +79,7 @@ def gauss_newton_step(engine, model, shots, g, exchange=None, wrt="velocity", pr
     def hvp(v):
         dtype = getattr(_engines(engine)[0], "dtype", np.float64)
         Hv = np.asarray(gauss_newton_hvp(engine, None, shots, np.asarray(v, dtype), exchange, wrt), np.float64)
-        return Hv + damping * v if damping else Hv
+        Hv = Hv + damping * v if damping else Hv
+        return Hv if regularizer is None else Hv + regularizer.hvp(model, v)
 
     return cg(hvp, -g, precond=precond, maxiter=maxiter, rtol=rtol, callback=callback)

@@ -237,6 +237,28 @@ int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b);    /* y := a / (
  * ping-pong vector is the context's own (allocated by the first call, freed by fwi_destroy).  No reference counterpart. */
 int fwi_vec_smooth(fwi_ctx *ctx, int32_t y, const double *sigma);
 
+/* First-order Tikhonov and smoothed isotropic total-variation regularisation of a vector slot, stream-ordered like
+ * fwi_vec_axpby.  d = x - x0 (x0 = -1: d = x); per axis a of the grid order (z, [y,] x), with weight[a] >= 0 in cell units:
+ *   (D_a d)_i = d_{i+e_a} - d_i for i_a < n_a - 1, 0 on the last cell of the axis (against nx, not the padded row),
+ *   s_i = sum_a weight[a] (D_a d)_i^2,
+ *   FWI_REG_TIKHONOV  R = 1/2 sum_i s_i,                    k_i = 1,
+ *   FWI_REG_TV        R = sum_i (sqrt(s_i + eps^2) - eps),  k_i = 1 / sqrt(s_i + eps^2),   eps > 0,
+ *   L(d; v)_j = sum_a weight[a] [k_{j-e_a}(d) (D_a v)_{j-e_a} - k_j(d) (D_a v)_j]  =  (sum_a weight[a] D_a^T diag(k) D_a v)_j.
+ * The call computes out := alpha L(d; v) + beta out (v = -1: v = d, L(d; d) is the gradient of R; out = -1: the value
+ * only) and, with value_out != NULL, *value_out = R(d) (this synchronises the stream).  For fixed d, L is symmetric
+ * positive semi-definite in v (the exact Hessian of Tikhonov, the lagged-diffusivity one of TV) with the constants in its
+ * null space.  With beta == 0 the old contents of out are not read.  All arithmetic between the loads and the final
+ * rounding to the context's dtype is fp64; R is summed in fp64 in a fixed order (block partial sums in a buffer the
+ * context owns, allocated by the first call and freed by fwi_destroy; no atomics): equal inputs give equal bits on
+ * every call and rank.  Pad columns of out are written as zeros.  FWI_EINVAL, naming the argument and touching nothing:
+ * an unknown kind; a slot that does not exist; out aliasing x, x0 or v; out == -1 with value_out == NULL; a null weight;
+ * a negative or non-finite weight[a]; TV with eps not finite or <= 0; a non-finite alpha or beta.  eps is ignored by
+ * Tikhonov.  No reference counterpart. */
+enum { FWI_REG_TIKHONOV = 0, FWI_REG_TV = 1 };
+int fwi_vec_regularizer(fwi_ctx *ctx, int32_t kind, int32_t x, int32_t x0 /* -1: none */, int32_t v /* -1: v = d */,
+                        int32_t out /* -1: value only */, double alpha, double beta, const double *weight /* ndim */,
+                        double eps, double *value_out /* R(d), or NULL */);
+
 /* Born (linearised) modelling dd = J dm: the exact derivative of the discrete fwi_forward along a model perturbation,
  * whose exact transpose is fwi_adjoint(image) + fwi_gradient.  With C = dt^2 c^2 and q^n the forward term the store of
  * fwi_forward(save != 0) holds for every step (q^n = C (L u^n + PML terms + src^n)):

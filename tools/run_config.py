@@ -15,7 +15,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
-from full_waveform_inversion_amd import Engine, shots as sh, workloads  # noqa: E402
+from full_waveform_inversion_amd import Engine, regularizers as rg, shots as sh, workloads  # noqa: E402
 from full_waveform_inversion_amd.lbfgs import lbfgs, lbfgs_device, lbfgs_device_slots  # noqa: E402
 
 
@@ -45,7 +45,19 @@ def main():
     ap.add_argument("--mute-sources", type=float, default=None, metavar="RADIUS",
                     help="mask M = 1 - exp(-(d / RADIUS)^2) around the source nodes (shots.source_mute), applied inside "
                          "the --smooth operator (SIGMA 0 when --smooth is absent)")
+    ap.add_argument("--regularize", default=None, choices=["tikhonov", "tv"],
+                    help="add LAMBDA R(m - prior) to the misfit (regularizers.py): first-order Tikhonov or smoothed "
+                         "isotropic total variation; off when absent")
+    ap.add_argument("--reg-weight", type=float, default=None, metavar="LAMBDA", help="the weight of --regularize")
+    ap.add_argument("--reg-eps", type=float, default=None, metavar="EPS",
+                    help="smoothing of the total variation, in the model's units per cell (default: 1e-3 max m0)")
+    ap.add_argument("--reg-prior", default=None, choices=["start"],
+                    help="penalise m - m_start (the starting model, kept in one more vector slot) instead of m")
     a = ap.parse_args()
+    if (a.regularize is None) != (a.reg_weight is None):
+        ap.error("--regularize and --reg-weight go together")
+    if a.regularize is None and (a.reg_eps is not None or a.reg_prior is not None):
+        ap.error("--reg-eps / --reg-prior need --regularize")
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
     from full_waveform_inversion_amd import _lib as _fl
@@ -100,6 +112,11 @@ def main():
     m0 = w.c_init.astype(np.float32)
     ckpt = a.checkpoint if (a.checkpoint and rank == 0) else None  # every rank holds the same state: one writer
     bounds = (0.5 * float(w.c.min()), 1.5 * float(w.c.max()))
+    reg_eps = None
+    if a.regularize == "tv":
+        reg_eps = a.reg_eps if a.reg_eps is not None else 1e-3 * float(m0.max())
+    # the prior is the starting model of the RUN: a resumed run builds the same m0 again
+    reg_prior = m0 if a.reg_prior == "start" else None
     use_h0 = a.smooth is not None or a.mute_sources is not None
     h0_sigma = a.smooth if a.smooth is not None else 0.0
     mute = sh.source_mute(w.shape, shots, a.mute_sources) if a.mute_sources is not None else None
@@ -113,8 +130,14 @@ def main():
             if fg_p is not None:
                 return fg_p(xs, gs)
             return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex)
+        extra = 0
+        if a.regularize is not None:
+            xs0 = rg.prior_slot(5, pslot, h0) if reg_prior is not None else None
+            extra = 0 if xs0 is None else 1
+            fg_dev = rg.regularized_fg_device(pool, fg_dev, a.reg_weight, a.regularize, 1.0, reg_eps, xs0, reg_prior)
         _, _, log = lbfgs_device(e, fg_dev, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
-                                 bounds=bounds, checkpoint=ckpt, resume=a.resume or None, precond_slot=pslot, h0=h0)
+                                 bounds=bounds, checkpoint=ckpt, resume=a.resume or None, precond_slot=pslot, h0=h0,
+                                 extra_slots=extra)
     elif a.iters > 0:
         pc = (lambda x, f, g: sh.illumination_preconditioner(first_H[0], eps)) if eps is not None else None
         held = {}
@@ -129,11 +152,14 @@ def main():
                 held["p"] = load_state(a.resume)["precond"]
             return held["p"]
         h0 = sh.smoothing_h0(h0_sigma, mask=mute, precond=p_of_run if eps is not None else None) if use_h0 else None
+        if a.regularize is not None:
+            fg_host = rg.regularized_fg(fg_host, a.reg_weight, a.regularize, 1.0, reg_eps, reg_prior)
         _, _, log = lbfgs(fg_host, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
                           bounds=bounds, dot=e.dot, checkpoint=ckpt, resume=a.resume or None,
                           precond=pc_keep if pc is not None else None, h0=h0)
     else:
-        J, g = fg(m0)
+        fg1 = fg if a.regularize is None else rg.regularized_fg(fg, a.reg_weight, a.regularize, 1.0, reg_eps, reg_prior)
+        J, g = fg1(m0)
         log = [{"iter": 0, "f": J, "gnorm": float(np.sqrt(e.dot(g, g)))}]
     el = time.perf_counter() - t0
     if rank == 0:
@@ -143,7 +169,8 @@ def main():
                           "Gpts_per_s_fwd_plus_adj": round(upd / el / 1e9, 2), "kernel": e.kernel_name,
                           "update_form": e.update_form, "abc": a.abc, "launch_mode": a.launch_mode,
                           "precondition_eps": eps, "smooth_sigma": a.smooth,
-                          "mute_sources_radius": a.mute_sources, "log": log}))
+                          "mute_sources_radius": a.mute_sources, "regularize": a.regularize,
+                          "reg_weight": a.reg_weight, "reg_eps": reg_eps, "reg_prior": a.reg_prior, "log": log}))
     pool.close()
     if rdzv is not None:
         rdzv.barrier()
