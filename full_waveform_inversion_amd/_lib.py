@@ -60,6 +60,8 @@ SIGNATURES = {
     "fwi_forward_spread": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _I32, _P]),
     "fwi_adjoint": (C.c_int, [_P, _P, _I32, _P]),
     "fwi_misfit_l2": (C.c_int, [_P, _P, C.POINTER(_D)]),
+    "fwi_misfit_weighted": (C.c_int, [_P, _P, _P, _P, _I32, C.POINTER(_D)]),
+    "fwi_residual_weight": (C.c_int, [_P, _P, _P, _I32]),
     "fwi_gradient": (C.c_int, [_P, _I32, _P]),
     "fwi_gradient_reset": (C.c_int, [_P]),
     "fwi_gradient_add": (C.c_int, [_P, _P]),

@@ -22,6 +22,7 @@
 
 #include "../../include/fwi.h"
 #include "fwi_born.h"
+#include "fwi_data.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
 #include "fwi_reg.h"
@@ -179,6 +180,13 @@ struct fwi_ctx {
     std::vector<void *> vecs;  // optimiser vectors (compact, model-sized)
     void *smooth_tmp = nullptr;  // compact ping-pong vector of fwi_vec_smooth; allocated by its first call
     void *reg_part = nullptr;    // block partial sums (and their total) of fwi_vec_regularizer; allocated by its first call
+    // fwi_misfit_weighted / fwi_residual_weight (fwi_data.hip), allocated by their first call: the series between the two
+    // filter passes, the weights, the taps, the block partial sums of J (and their total)
+    void *data_tmp = nullptr, *data_w = nullptr, *data_taps = nullptr, *data_part = nullptr;
+    size_t cap_data_tmp = 0, cap_data_w = 0, cap_data_taps = 0, cap_data_part = 0;
+    // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
+    enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
+    int resid_pts_in = RESID_PTS_NONE;
     void *pin = nullptr;     // pinned host staging for the time series
     size_t cap_pin = 0;
     // checkpointing (SURVEY s.8f-3): snapshot of (u^n, u^{n-1}) every `ckpt` steps instead of the
@@ -1679,6 +1687,7 @@ struct Impl {
         }
         if ((rc = download_series(ctx, seis_out, out, (nrec && seis_out) ? out_bytes : 0))) return rc;
         ctx->have_dev_residual = true;
+        ctx->resid_pts_in = (nrec && sp.npts) ? fwi_ctx::RESID_PTS_D : fwi_ctx::RESID_PTS_NONE;
         return FWI_OK;
     }
 
@@ -1739,6 +1748,103 @@ struct Impl {
         }
         *J_out = 0.5 * ss;
         ctx->have_dev_residual = true;
+        ctx->resid_pts_in = (n && ctx->nrec && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
+        return FWI_OK;
+    }
+
+    // weights (nt, ntr) and taps b_0 .. b_R of the caller -> the device; the buffers of the two filter passes.  R_out:
+    // the half-width that meets samples (taps beyond nt - 1 are not uploaded)
+    static int data_prepare(fwi_ctx *ctx, const T *weights, const double *taps, int R, int nt, int ntr, const T **w_dev,
+                            const double **taps_dev, int *R_out) {
+        const size_t n = (size_t)nt * ntr;
+        int rc;
+        if ((rc = ensure(ctx, &ctx->data_tmp, &ctx->cap_data_tmp, n * sizeof(T)))) return rc;
+        if ((rc = ensure(ctx, &ctx->data_part, &ctx->cap_data_part, (size_t)(fir_blocks(nt, ntr) + 1) * sizeof(double))))
+            return rc;
+        *w_dev = nullptr;
+        if (weights) {
+            if ((rc = ensure(ctx, &ctx->data_w, &ctx->cap_data_w, n * sizeof(T)))) return rc;
+            if ((rc = upload_series(ctx, ctx->data_w, weights, n * sizeof(T)))) return rc;
+            *w_dev = (const T *)ctx->data_w;
+        }
+        *taps_dev = nullptr;
+        *R_out = 0;
+        if (taps) {
+            *R_out = std::min(R, nt - 1);
+            const size_t bytes = (size_t)(*R_out + 1) * sizeof(double);
+            if ((rc = ensure(ctx, &ctx->data_taps, &ctx->cap_data_taps, bytes))) return rc;
+            // the taps are the caller's pageable memory: the copy is complete before anything that can fail and return
+            // follows it (at most 32 KB, in the stream's order behind the uploads above)
+            HIPCHK(ctx, hipMemcpyAsync(ctx->data_taps, taps, bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            *taps_dev = (const double *)ctx->data_taps;
+        }
+        return FWI_OK;
+    }
+
+    // e = M . B (d_syn - d_obs), J = 1/2 sum e^2, r = B (M . e) where the adjoint sweep reads its amplitudes
+    static int misfit_weighted(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, double *J_out) {
+        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
+        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
+        const size_t n = (size_t)nt * ntr;
+        double ss = 0.0;
+        if (n && ctx->nrec) {
+            // off-grid receivers: filtered and weighted per POINT (against the gathered synthetics kept by the forward),
+            // then scattered onto the nodes, as misfit_l2 does
+            void *resid = ctx->amp;
+            int rc, Re;
+            if (sp.npts) {
+                if ((rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T)))) return rc;
+                resid = ctx->pts_a;
+            }
+            if ((rc = upload_series(ctx, resid, d_obs, n * sizeof(T)))) return rc;
+            const T *w;
+            const double *b;
+            if ((rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
+            double *part = (double *)ctx->data_part;
+            // neither taps nor weights: e is the plain residual and the call is fwi_misfit_l2 with a fixed-order sum, so
+            // J is summed as there, from the residual as stored; otherwise from the unrounded e
+            const bool plain = !w && !b;
+            HIPCHK(ctx, launch_fir_time<T>((T *)ctx->data_tmp, (const T *)(sp.npts ? ctx->pts_d : ctx->series),
+                                           (const T *)resid, nullptr, w, b, Re, nt, ntr, part, plain, ctx->stream));
+            HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)ctx->data_tmp, nullptr, w, nullptr, b, Re, nt, ntr, nullptr,
+                                           false, ctx->stream));
+            if (sp.npts)
+                HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
+                                                     (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(&ss, part + fir_blocks(nt, ntr), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        *J_out = 0.5 * ss;
+        ctx->have_dev_residual = true;
+        ctx->resid_pts_in = (n && ctx->nrec && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
+        return FWI_OK;
+    }
+
+    // device residual := B M^2 B residual: per node, or per off-grid point and scattered onto the nodes again
+    static int residual_weight(fwi_ctx *ctx, const T *weights, const double *taps, int R) {
+        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
+        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
+        if (!ctx->nrec || !nt || !ntr) return FWI_OK;
+        void *resid = ctx->amp;
+        if (sp.npts) {
+            if (ctx->resid_pts_in == fwi_ctx::RESID_PTS_NONE)
+                return ctx->fail(FWI_ESTATE, "fwi_residual_weight: the residual's per-point series were not kept "
+                                             "(off-grid receivers): weight it on the host");
+            resid = ctx->resid_pts_in == fwi_ctx::RESID_PTS_A ? ctx->pts_a : ctx->pts_d;
+        }
+        int rc, Re;
+        const T *w;
+        const double *b;
+        if ((rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
+        HIPCHK(ctx, launch_fir_time<T>((T *)ctx->data_tmp, (const T *)resid, nullptr, nullptr, w, b, Re, nt, ntr, nullptr,
+                                       false, ctx->stream));
+        HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)ctx->data_tmp, nullptr, w, nullptr, b, Re, nt, ntr, nullptr,
+                                       false, ctx->stream));
+        if (sp.npts)
+            HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
+                                                 (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return FWI_OK;
     }
 
@@ -2213,7 +2319,9 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
                   {"pml_snap", ctx->pml_snap}, {"pml_tz", ctx->pml_tz}, {"pml_ty", ctx->pml_ty},
                   {"fused_order", ctx->fused_order}, {"pts_a", ctx->pts_a}, {"pts_d", ctx->pts_d},
-                  {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}, {"reg_part", ctx->reg_part}};
+                  {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}, {"reg_part", ctx->reg_part},
+                  {"data_tmp", ctx->data_tmp}, {"data_w", ctx->data_w}, {"data_taps", ctx->data_taps},
+                  {"data_part", ctx->data_part}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2354,6 +2462,38 @@ int fwi_misfit_l2(fwi_ctx *ctx, const void *d_obs, double *J_out) {
     (void)hipSetDevice(ctx->cfg.device);
     return DISPATCH(ctx, Impl<float>::misfit_l2(ctx, (const float *)d_obs, J_out),
                     Impl<double>::misfit_l2(ctx, (const double *)d_obs, J_out));
+}
+
+static int data_args(fwi_ctx *ctx, const char *who, const double *taps, int32_t R) {
+    if (R < 0 || R > FIR_RMAX) return ctx->fail(FWI_EINVAL, "%s: R=%d outside [0, %d]", who, (int)R, FIR_RMAX);
+    if (R > 0 && !taps) return ctx->fail(FWI_EINVAL, "%s: null taps with R=%d", who, (int)R);
+    return FWI_OK;
+}
+
+int fwi_misfit_weighted(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
+                        double *J_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "fwi_misfit_weighted: no forward run whose data to compare");
+    if (!J_out || (ctx->nrec && !d_obs)) return ctx->fail(FWI_EINVAL, "fwi_misfit_weighted: null argument");
+    if (int rc = data_args(ctx, "fwi_misfit_weighted", taps, R)) return rc;
+    if (!ctx->have_syn)
+        return ctx->fail(FWI_ESTATE, "fwi_misfit_weighted: the synthetics of the last forward are gone (an fwi_adjoint "
+                                     "or fwi_born has run since): call it between fwi_forward and fwi_adjoint");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx,
+                    Impl<float>::misfit_weighted(ctx, (const float *)d_obs, (const float *)weights, taps, R, J_out),
+                    Impl<double>::misfit_weighted(ctx, (const double *)d_obs, (const double *)weights, taps, R, J_out));
+}
+
+int fwi_residual_weight(fwi_ctx *ctx, const void *weights, const double *taps, int32_t R) {
+    if (!ctx) return FWI_EINVAL;
+    if (int rc = data_args(ctx, "fwi_residual_weight", taps, R)) return rc;
+    if (!ctx->have_dev_residual)
+        return ctx->fail(FWI_ESTATE, "fwi_residual_weight: no residual on the device (fwi_born, fwi_misfit_l2 or "
+                                     "fwi_misfit_weighted leave one; fwi_adjoint uses it up)");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, Impl<float>::residual_weight(ctx, (const float *)weights, taps, R),
+                    Impl<double>::residual_weight(ctx, (const double *)weights, taps, R));
 }
 
 int fwi_gradient(fwi_ctx *ctx, int32_t wrt, void *g_out) {

@@ -226,6 +226,39 @@ class Engine:
         self._chk(self._lib.fwi_misfit_l2(self._c, d_obs.ctypes.data_as(C.c_void_p), C.byref(J)))
         return J.value
 
+    def _data_args(self, weights, taps):
+        """(weights pointer, taps pointer, R) of ``fwi_misfit_weighted`` / ``fwi_residual_weight``, and the arrays they
+        point into"""
+        wp = tp = None
+        R = 0
+        if weights is not None:
+            weights = self._host(weights, (self._nt, self._nrec))
+            wp = weights.ctypes.data_as(C.c_void_p)
+        if taps is not None:
+            taps = np.ascontiguousarray(taps, dtype=np.float64)
+            if taps.ndim != 1 or taps.size < 1:
+                raise ValueError("taps must be the 1-D array b_0 .. b_R")
+            tp, R = taps.ctypes.data_as(C.c_void_p), taps.size - 1
+        return wp, tp, R, (weights, taps)
+
+    def misfit_weighted(self, d_obs, weights=None, taps=None):
+        """``J = 1/2 ||M . B (d_syn - d_obs)||^2`` for the last forward's seismograms: ``B`` the symmetric FIR filter along
+        time with the one-sided ``taps`` ``b_0 .. b_R`` (None: the identity), ``M`` the ``weights >= 0`` of the data's
+        shape (None: 1; a negative weight is NOT refused on the device and acts as its absolute value).  The adjoint
+        source ``B (M^2 . B (d_syn - d_obs))`` is formed on the device and kept there for ``adjoint(None)``
+        (``fwi_misfit_weighted``; the NumPy twin is :class:`datafit.WeightedL2`)."""
+        d_obs = self._host(d_obs, (self._nt, self._nrec))
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        J = C.c_double(0.0)
+        self._chk(self._lib.fwi_misfit_weighted(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, C.byref(J)))
+        return J.value
+
+    def residual_weight(self, weights=None, taps=None):
+        """The residual on the device (what ``born`` or a misfit call left for ``adjoint(None)``) := ``B M^2 B`` residual,
+        the Gauss-Newton weight of :meth:`misfit_weighted` (``fwi_residual_weight``)."""
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        self._chk(self._lib.fwi_residual_weight(self._c, wp, tp, R))
+
     def gradient(self, wrt="velocity"):
         if self._ctx is None:
             raise _lib.FwiError(3, "gradient: no model set")

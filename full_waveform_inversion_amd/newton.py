@@ -61,7 +61,7 @@ def cg(hvp, b, x0=None, precond=None, maxiter=20, rtol=1e-6, callback=None):
 
 
 def gauss_newton_step(engine, model, shots, g, exchange=None, wrt="velocity", precond=None, maxiter=10, rtol=1e-2,
-                      damping=0.0, callback=None, regularizer=None):
+                      damping=0.0, callback=None, regularizer=None, objective=None):
     """The (truncated) Gauss-Newton step ``p``: ``(H_GN + damping I) p = -g`` at ``model`` by :func:`cg`, with ``g``
     the gradient ``shots.misfit_and_gradient`` returned there (same ``wrt``).  ``precond`` as in :func:`cg`; the
     illumination preconditioner of ``shots.illumination_preconditioner`` fits (the illumination is the diagonal of the
@@ -70,7 +70,10 @@ def gauss_newton_step(engine, model, shots, g, exchange=None, wrt="velocity", pr
 
     ``regularizer``: a ``regularizers.Regularizer``; its symmetric positive semi-definite term ``lam L(model - x0; v)``
     is added to every product (host fp64), for a ``g`` that already holds its gradient
-    (``regularizers.regularized_fg``).  None: no such term."""
+    (``regularizers.regularized_fg``).  None: no such term.
+
+    ``objective``: the ``datafit.WeightedL2`` that ``g`` was computed with; every product then carries its weight,
+    ``H_GN = sum_s J_s^T B M_s^2 B J_s`` (``shots.gauss_newton_hvp``).  None: plain least squares."""
     from .shots import _engines, gauss_newton_hvp
     for e in _engines(engine):
         e.set_model(model)
@@ -78,7 +81,8 @@ def gauss_newton_step(engine, model, shots, g, exchange=None, wrt="velocity", pr
 
     def hvp(v):
         dtype = getattr(_engines(engine)[0], "dtype", np.float64)
-        Hv = np.asarray(gauss_newton_hvp(engine, None, shots, np.asarray(v, dtype), exchange, wrt), np.float64)
+        kw = {} if objective is None else {"objective": objective}
+        Hv = np.asarray(gauss_newton_hvp(engine, None, shots, np.asarray(v, dtype), exchange, wrt, **kw), np.float64)
         Hv = Hv + damping * v if damping else Hv
         return Hv if regularizer is None else Hv + regularizer.hvp(model, v)
 

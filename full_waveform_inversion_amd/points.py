@@ -48,6 +48,7 @@ class Spread:
             wts.append(w[ok])
             own.append(np.nonzero(ok)[0])
         self.n = coords.shape[0]
+        self.coords = np.array(coords)                                                 # (n, D) the points themselves (a copy)
         order = np.argsort(np.concatenate(own), kind="stable")  # entries grouped by point (the device gather's CSR)
         self.idx = np.ascontiguousarray(np.concatenate(idx)[order], dtype=np.int32)   # (m, D) nodes
         self.weights = np.concatenate(wts)[order]                                      # (m,)

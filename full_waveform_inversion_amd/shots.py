@@ -25,6 +25,7 @@ class Shot:
     src_spread: object = None
     rec_spread: object = None
     point_wavelet: np.ndarray | None = None  # (nt[, nsrc points]): the wavelets before spreading
+    weights: np.ndarray | None = None  # (nt, nrec) data weights >= 0 of a datafit.WeightedL2 objective (None: 1)
 
     @classmethod
     def at_coordinates(cls, src_xyz, wavelet, rec_xyz, shape, d_obs=None):
@@ -294,6 +295,9 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     ``objective(d_syn, d_obs) -> (J, dJ/dd_syn)``; default least squares 1/2 ||d_syn - d_obs||^2
     (see objectives.py for the reference's similarity measures as misfits).
 
+    A :class:`datafit.WeightedL2` objective (band-limited, weighted least squares) is handed each shot's
+    ``Shot.weights``; under ``device_l2`` an engine that has ``misfit_weighted`` forms its residual on the device too.
+
     ``device_l2`` (least squares only): form the residual and J on the device (``fwi_misfit_l2``) -- in the
     engine's dtype, i.e. with an fp32 engine ``d_obs`` is rounded to fp32 before the subtraction, which puts
     ~6e-8 |d| / |r| of relative noise on J and on the residual (visible to a line search only once |r| / |d|
@@ -319,7 +323,9 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
 def _sweep_shots(engine, shots, ex, objective, device_l2=True):
     """forward + adjoint of this rank's shots; returns the misfit, gradients summed into the
     (primary) engine's accumulator."""
+    from .datafit import WeightedL2
     from .objectives import l2
+    weighted = isinstance(objective, WeightedL2)
 
     def one(e, i):
         s = shots[i]
@@ -331,7 +337,11 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True):
             j = e.misfit_l2(s.d_obs)
             e.adjoint(None)
             return j
-        j, r = objective(d, s.d_obs)
+        if device_l2 and weighted and hasattr(e, "misfit_weighted") and (s.rec_spread is None or s._on_device(e)):
+            j = e.misfit_weighted(s.d_obs, s.weights, objective.taps)  # ... filtered and weighted there as well
+            e.adjoint(None)
+            return j
+        j, r = objective(d, s.d_obs, s.weights) if weighted else objective(d, s.d_obs)
         s.adjoint(e, r)
         return j
 
@@ -369,17 +379,25 @@ def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=No
     return misfit
 
 
-def _hvp_sweep(engine, shots, ex, born_one):
-    """forward(save) + Born + adjoint(imaging) of this rank's shots; ``born_one(e, s, download)`` applies J_s."""
+def _hvp_sweep(engine, shots, ex, born_one, objective=None):
+    """forward(save) + Born + adjoint(imaging) of this rank's shots; ``born_one(e, s, download)`` applies J_s.  With a
+    ``datafit.WeightedL2`` objective its weight ``W_s = B M_s^2 B`` acts on the Born data between the two: on the device
+    where the residual stays there and the engine has ``residual_weight``, else through the host twin."""
+    from .datafit import WeightedL2
+    if objective is not None and not isinstance(objective, WeightedL2):
+        raise ValueError("objective must be a datafit.WeightedL2 (or None: plain least squares)")
 
     def one(e, i):
         s = shots[i]
         s.forward(e, save=True)
-        if s._residual_stays(e):
+        if s._residual_stays(e) and (objective is None or hasattr(e, "residual_weight")):
             born_one(e, s, False)
+            if objective is not None:
+                e.residual_weight(s.weights, objective.taps)
             e.adjoint(None)
         else:
-            s.adjoint(e, born_one(e, s, True))
+            d = born_one(e, s, True)
+            s.adjoint(e, d if objective is None else objective.normal(d, s.weights))
 
     mine = partition_shots(len(shots), ex.rank, ex.world)
     if isinstance(engine, EnginePool):
@@ -391,8 +409,9 @@ def _hvp_sweep(engine, shots, ex, born_one):
             one(engine, i)
 
 
-def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity"):
-    """Gauss-Newton Hessian-vector product ``H v = sum_s J_s^T J_s v`` at ``model``, summed over all ranks: ``v`` and
+def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity", objective=None):
+    """Gauss-Newton Hessian-vector product ``H v = sum_s J_s^T J_s v`` at ``model`` (with ``objective`` a
+    ``datafit.WeightedL2``: ``sum_s J_s^T W_s J_s v``, ``W_s = B M_s^2 B``), summed over all ranks: ``v`` and
     the result are model-shaped and in the parametrisation ``wrt``.  Per shot ``forward(save=True)``, ``born``,
     ``adjoint`` -- THREE sweeps per shot and product, because the forward-term store holds one shot at a time.
     J is the engine's imaging Born operator (``Engine.born(operator="imaging")``), the exact transpose of its
@@ -406,15 +425,17 @@ def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity"):
         if model is not None:
             e.set_model(model)
         e.reset_gradient()
-    _hvp_sweep(engine, shots, ex, lambda e, s, download: s.born(e, v, wrt, download=download, operator="imaging"))
+    _hvp_sweep(engine, shots, ex, lambda e, s, download: s.born(e, v, wrt, download=download, operator="imaging"),
+               objective)
     return ex.reduce(engs[0], 0.0, wrt)[0]
 
 
-def gauss_newton_hvp_device(engine, model_slot, v_slot, out_slot, shots, exchange=None, wrt="velocity"):
+def gauss_newton_hvp_device(engine, model_slot, v_slot, out_slot, shots, exchange=None, wrt="velocity", objective=None):
     """:func:`gauss_newton_hvp` on device vectors (``Engine.vec_*``): the model is read from ``model_slot`` (None: the
     model the engines hold), v from ``v_slot`` and ``H v`` is written to ``out_slot``; the Born data stay on the device
     as the adjoint's residual, so no model- or data-sized array crosses PCIe (the further engines of a pool receive the
-    model and v from the primary one through the host).  OVERWRITES the gradient accumulator; three sweeps per shot."""
+    model and v from the primary one through the host).  OVERWRITES the gradient accumulator; three sweeps per shot.
+    ``objective`` as in :func:`gauss_newton_hvp`: its weight is applied by ``Engine.residual_weight`` on the device."""
     ex = exchange or NoExchange()
     engs = _engines(engine)
     if model_slot is not None:
@@ -434,7 +455,7 @@ def gauss_newton_hvp_device(engine, model_slot, v_slot, out_slot, shots, exchang
         d = e.born_vec(v_slot, wrt, download=download, operator="imaging")
         return d if d is None or s._on_device(e) or s.rec_spread is None else s.rec_spread.gather(d)
 
-    _hvp_sweep(engine, shots, ex, born_one)
+    _hvp_sweep(engine, shots, ex, born_one, objective)
     ex.reduce_device(engs[0], 0.0)
     engs[0].gradient_vec(out_slot, wrt)
 

@@ -177,6 +177,35 @@ int fwi_adjoint(fwi_ctx *ctx, const void *residual, int32_t image, void *adj_src
  * second copy of the data crosses PCIe.  [SURVEY s.8(a-1) row "gradient dot-products / J"] */
 int fwi_misfit_l2(fwi_ctx *ctx, const void *d_obs /* (nt, nrec) */, double *J_out);
 
+/* Band-limited, weighted least squares on the device.  With x = d_syn - d_obs of the last fwi_forward, shaped (nt, ntr)
+ * (ntr = nrec, or the receiver POINTS after fwi_forward_spread), B a symmetric FIR filter along time with the taps
+ * b_0 .. b_R (b_-k = b_k) on the zero-extended trace,
+ *     (B x)[n, j] = sum_{k = -R .. R} b_|k| x[n + k, j],   terms with n + k outside [0, nt) omitted   (so B^T = B),
+ * and M per-sample weights >= 0 of the shape of the data (context dtype):
+ *     e = M . (B x),     J = 1/2 sum e^2,     r = dJ/dd_syn = B (M . e).
+ * taps == NULL (with R = 0): B = I;  weights == NULL: M = 1.  *J_out = J, and r stays on the device as the residual of
+ * the next fwi_adjoint(ctx, NULL, ...): neither the synthetics nor the residual cross PCIe.  With off-grid receivers the
+ * filter and the weights act per point and r is then spread onto the nodes, as fwi_misfit_l2 does.  The difference
+ * d_syn - d_obs, the filter sums (over ascending k) and the weighting are fp64; e and r are each rounded to the
+ * context's dtype once.  J is summed from the unrounded e in fp64 in a fixed order (block partial sums, no atomics):
+ * equal inputs give equal bits.  With taps == NULL and weights == NULL the call is fwi_misfit_l2 with that fixed-order
+ * sum: r is its residual bit for bit and J is summed, as there, from the squares of the residual as stored (rounded to
+ * the context's dtype; in fp32 that J differs by some 1e-9 relative from the sum over the unrounded differences which
+ * taps = {1.0} gives).  R may exceed nt - 1: the taps beyond meet no sample.  State rules of fwi_misfit_l2:
+ * FWI_ESTATE without a forward or once an fwi_adjoint / fwi_born has run since.  FWI_EINVAL: a null J_out, a null d_obs
+ * with nrec > 0, R < 0, R > 4096, null taps with R > 0.  Negative or non-finite weights and taps are NOT checked (the
+ * weights would have to come back from the device): a negative weight acts as its absolute value, in J and in r.
+ * The work buffers are the context's own (allocated by the first call, freed by fwi_destroy).  No reference counterpart. */
+int fwi_misfit_weighted(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                        const double *taps /* R + 1, or NULL */, int32_t R, double *J_out);
+/* The Gauss-Newton counterpart: residual := B M^2 B residual, in place on the residual that fwi_born / fwi_born_imaging
+ * (or one of the misfit calls) left on the device, so that fwi_forward(save), fwi_born_imaging_vec, this call,
+ * fwi_adjoint(NULL, image = 1), fwi_gradient_vec is H v = J^T B M^2 B J v.  Per node, or per point after
+ * fwi_forward_spread (FWI_ESTATE when the per-point series of the residual were not kept).  Same arithmetic, arguments
+ * and FWI_EINVAL cases as above; FWI_ESTATE without a residual on the device.  Synchronises the stream. */
+int fwi_residual_weight(fwi_ctx *ctx, const void *weights /* (nt, ntr) or NULL */, const double *taps /* R + 1, or NULL */,
+                        int32_t R);
+
 /* gradient(): copy out the accumulated gradient, model-shaped, as dJ/dc
  * (FWI_WRT_VELOCITY) or dJ/d(1/c^2) (FWI_WRT_SLOWNESS2).
  * [SURVEY s.8(a-1) row gradient] */

@@ -15,7 +15,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
-from full_waveform_inversion_amd import Engine, regularizers as rg, shots as sh, workloads  # noqa: E402
+from full_waveform_inversion_amd import Engine, datafit, regularizers as rg, shots as sh, workloads  # noqa: E402
 from full_waveform_inversion_amd.lbfgs import lbfgs, lbfgs_device, lbfgs_device_slots  # noqa: E402
 
 
@@ -53,7 +53,22 @@ def main():
                     help="smoothing of the total variation, in the model's units per cell (default: 1e-3 max m0)")
     ap.add_argument("--reg-prior", default=None, choices=["start"],
                     help="penalise m - m_start (the starting model, kept in one more vector slot) instead of m")
+    ap.add_argument("--bands", default=None, metavar="F1,F2,...",
+                    help="frequency continuation (datafit.frequency_continuation): --iters L-BFGS iterations per band on the "
+                         "residual low-passed at F1, then F2, ... Hz (datafit.WeightedL2, formed on the device), each band "
+                         "from the model of the one before and with a fresh L-BFGS history")
+    ap.add_argument("--band-halfwidth", type=int, default=64, metavar="R", help="half-width of the --bands filters in samples")
+    ap.add_argument("--mute-direct", type=float, default=None, metavar="V_FAST",
+                    help="data weights that mute every trace up to offset / V_FAST + 2 / f0, with a taper of half a period "
+                         "(datafit.offset_time_mute)")
     a = ap.parse_args()
+    bands = [float(f) for f in a.bands.split(",")] if a.bands else None
+    if bands and (a.iters < 1 or a.checkpoint or a.resume):
+        ap.error("--bands needs --iters > 0 and runs without --checkpoint / --resume (one optimiser state per band)")
+    if bands and (a.precondition is not None or a.smooth is not None or a.mute_sources is not None
+                  or a.regularize is not None or a.host_lbfgs):
+        ap.error("--bands runs the plain device L-BFGS per band: it does not combine with --precondition, --smooth, "
+                 "--mute-sources, --regularize or --host-lbfgs")
     if (a.regularize is None) != (a.reg_weight is None):
         ap.error("--regularize and --reg-weight go together")
     if a.regularize is None and (a.reg_eps is not None or a.reg_prior is not None):
@@ -91,12 +106,18 @@ def main():
         e.set_model(w.c.astype(np.float32))
         ex = sh.RcclExchange(e, rdzv)  # raises on every rank if any rank's communicator fails
     sh.model_data(pool, w.c.astype(np.float32), shots, ex)
+    if a.mute_direct is not None:
+        for s in shots:
+            if s.d_obs is not None:
+                s.weights = datafit.offset_time_mute(s, w.h, w.dt, a.mute_direct, 2.0 / w.f0, int(0.5 / (w.f0 * w.dt)))
+    # the misfit of the stage that is running: least squares, or its band-limited / weighted form
+    obj = [datafit.WeightedL2() if a.mute_direct is not None else None]
     t0 = time.perf_counter()
     evals = [0]
 
     def fg(m):
         evals[0] += 1
-        return sh.misfit_and_gradient(pool, m, shots, ex)
+        return sh.misfit_and_gradient(pool, m, shots, ex, objective=obj[0])
 
     eps = a.precondition
     first_H = []
@@ -105,7 +126,7 @@ def main():
         if eps is None or first_H:
             return fg(m)
         evals[0] += 1
-        J, g, H = sh.misfit_and_gradient(pool, m, shots, ex, illumination=True)
+        J, g, H = sh.misfit_and_gradient(pool, m, shots, ex, objective=obj[0], illumination=True)
         first_H.append(H)
         return J, g
 
@@ -120,16 +141,29 @@ def main():
     use_h0 = a.smooth is not None or a.mute_sources is not None
     h0_sigma = a.smooth if a.smooth is not None else 0.0
     mute = sh.source_mute(w.shape, shots, a.mute_sources) if a.mute_sources is not None else None
-    if a.iters > 0 and not a.host_lbfgs:
+    if bands:
+        def run_band(x, taps):  # the device L-BFGS, started afresh: curvature pairs of another band are invalid
+            obj[0] = datafit.WeightedL2(taps)
+
+            def fg_band(xs, gs):
+                evals[0] += 1
+                return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex, objective=obj[0])
+            x, _, lg = lbfgs_device(e, fg_band, x, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
+                                    bounds=bounds)
+            return x, lg
+        _, logs = datafit.frequency_continuation(run_band, m0, bands,
+                                                 taps_of=lambda f: datafit.lowpass_taps(w.dt, f, a.band_halfwidth))
+        log = [{"band_hz": f, "log": lg} for f, lg in zip(bands, logs)]
+    elif a.iters > 0 and not a.host_lbfgs:
         pslot = lbfgs_device_slots(5) if eps is not None else None
         h0 = sh.smoothing_h0_device(pool, h0_sigma, mask=mute, precond_slot=pslot) if use_h0 else None
-        fg_p = sh.preconditioned_fg_device(pool, shots, pslot, eps, ex) if eps is not None else None
+        fg_p = sh.preconditioned_fg_device(pool, shots, pslot, eps, ex, objective=obj[0]) if eps is not None else None
 
         def fg_dev(xs, gs):
             evals[0] += 1
             if fg_p is not None:
                 return fg_p(xs, gs)
-            return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex)
+            return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex, objective=obj[0])
         extra = 0
         if a.regularize is not None:
             xs0 = rg.prior_slot(5, pslot, h0) if reg_prior is not None else None
@@ -170,7 +204,8 @@ def main():
                           "update_form": e.update_form, "abc": a.abc, "launch_mode": a.launch_mode,
                           "precondition_eps": eps, "smooth_sigma": a.smooth,
                           "mute_sources_radius": a.mute_sources, "regularize": a.regularize,
-                          "reg_weight": a.reg_weight, "reg_eps": reg_eps, "reg_prior": a.reg_prior, "log": log}))
+                          "reg_weight": a.reg_weight, "reg_eps": reg_eps, "reg_prior": a.reg_prior, "bands_hz": bands,
+                          "band_halfwidth": a.band_halfwidth if bands else None, "mute_direct": a.mute_direct, "log": log}))
     pool.close()
     if rdzv is not None:
         rdzv.barrier()
