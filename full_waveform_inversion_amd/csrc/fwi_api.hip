@@ -180,6 +180,8 @@ struct fwi_ctx {
     std::vector<void *> vecs;  // optimiser vectors (compact, model-sized)
     void *smooth_tmp = nullptr;  // compact ping-pong vector of fwi_vec_smooth; allocated by its first call
     void *reg_part = nullptr;    // block partial sums (and their total) of fwi_vec_regularizer; allocated by its first call
+    void *sum_part = nullptr;    // the same of fwi_vec_dot, fwi_dot and fwi_misfit_l2 (SUM_MAX_BLOCKS + 1 doubles); allocated
+                                 // by the first of those calls
     // fwi_misfit_weighted / fwi_residual_weight (fwi_data.hip), allocated by their first call: the series between the two
     // filter passes, the weights, the taps, the block partial sums of J (and their total)
     void *data_tmp = nullptr, *data_w = nullptr, *data_taps = nullptr, *data_part = nullptr;
@@ -290,6 +292,13 @@ int ensure(fwi_ctx *ctx, void **p, size_t *cap, size_t bytes) {
     *p = nullptr;
     HIPCHK(ctx, hipMalloc(p, bytes ? bytes : 16));
     *cap = bytes;
+    return FWI_OK;
+}
+
+// the block partials (and their total) of the fixed-order sums (launch_dot, launch_residual_l2): allocated on first use
+int sum_partials(fwi_ctx *ctx, double **part) {
+    if (!ctx->sum_part) HIPCHK(ctx, hipMalloc(&ctx->sum_part, (size_t)(SUM_MAX_BLOCKS + 1) * sizeof(double)));
+    *part = (double *)ctx->sum_part;
     return FWI_OK;
 }
 
@@ -1737,13 +1746,15 @@ struct Impl {
                 resid = ctx->pts_a;
             }
             if ((rc = upload_series(ctx, resid, d_obs, n * sizeof(T)))) return rc;
-            HIPCHK(ctx, hipMemsetAsync(ctx->red, 0, sizeof(double), ctx->stream));
+            double *part;
+            if ((rc = sum_partials(ctx, &part))) return rc;
             HIPCHK(ctx, launch_residual_l2<T>((const T *)(sp.npts ? ctx->pts_d : ctx->series), (T *)resid, (int64_t)n,
-                                              ctx->red, ctx->stream));
+                                              part, ctx->stream));
             if (sp.npts)
                 HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
                                                      (const T *)sp.weight, ctx->nt, sp.npts, ctx->nrec, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(&ss, ctx->red, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(&ss, part + sum_blocks((int64_t)n), sizeof(double), hipMemcpyDeviceToHost,
+                                       ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         }
         *J_out = 0.5 * ss;
@@ -1849,9 +1860,12 @@ struct Impl {
     }
 
     static int vec_dot(fwi_ctx *ctx, const void *x, const void *y, double *out) {
-        HIPCHK(ctx, hipMemsetAsync(ctx->red, 0, sizeof(double), ctx->stream));
-        HIPCHK(ctx, launch_dot<T>((const T *)x, (const T *)y, ctx->gd.npts, ctx->red, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out, ctx->red, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        double *part;
+        int rc = sum_partials(ctx, &part);
+        if (rc) return rc;
+        HIPCHK(ctx, launch_dot<T>((const T *)x, (const T *)y, ctx->gd.npts, part, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out, part + sum_blocks(ctx->gd.npts), sizeof(double), hipMemcpyDeviceToHost,
+                                   ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return FWI_OK;
     }
@@ -1886,6 +1900,9 @@ struct Impl {
     }
 
     static int dot(fwi_ctx *ctx, const T *a, const T *b, int64_t n, double *out) {
+        double *part;
+        int rc = sum_partials(ctx, &part);
+        if (rc) return rc;
         void *da = nullptr, *db = nullptr;
         HIPCHK(ctx, hipMalloc(&da, (size_t)n * sizeof(T)));
         hipError_t e = hipMalloc(&db, (size_t)n * sizeof(T));
@@ -1893,13 +1910,11 @@ struct Impl {
             (void)hipFree(da);
             return ctx->fail(FWI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e));
         }
-        int rc = FWI_OK;
         do {
             if ((e = hipMemcpyAsync(da, a, (size_t)n * sizeof(T), hipMemcpyHostToDevice, ctx->stream))) break;
             if ((e = hipMemcpyAsync(db, b, (size_t)n * sizeof(T), hipMemcpyHostToDevice, ctx->stream))) break;
-            if ((e = hipMemsetAsync(ctx->red, 0, sizeof(double), ctx->stream))) break;
-            if ((e = launch_dot<T>((const T *)da, (const T *)db, n, ctx->red, ctx->stream))) break;
-            if ((e = hipMemcpyAsync(out, ctx->red, sizeof(double), hipMemcpyDeviceToHost, ctx->stream))) break;
+            if ((e = launch_dot<T>((const T *)da, (const T *)db, n, part, ctx->stream))) break;
+            if ((e = hipMemcpyAsync(out, part + sum_blocks(n), sizeof(double), hipMemcpyDeviceToHost, ctx->stream))) break;
             e = hipStreamSynchronize(ctx->stream);
         } while (0);
         if (e != hipSuccess) rc = ctx->fail(FWI_EHIP, "fwi_dot: %s", hipGetErrorString(e));
@@ -2320,6 +2335,7 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"pml_snap", ctx->pml_snap}, {"pml_tz", ctx->pml_tz}, {"pml_ty", ctx->pml_ty},
                   {"fused_order", ctx->fused_order}, {"pts_a", ctx->pts_a}, {"pts_d", ctx->pts_d},
                   {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}, {"reg_part", ctx->reg_part},
+                  {"sum_part", ctx->sum_part},
                   {"data_tmp", ctx->data_tmp}, {"data_w", ctx->data_w}, {"data_taps", ctx->data_taps},
                   {"data_part", ctx->data_part}};
     const char *prev = "";

@@ -161,9 +161,14 @@ hipError_t launch_build_model(const GridDesc &g, const T *c, T *Cpad, double dt2
 // writing there (make_grid); tests/test_gpu_round4.py checks it after every kind of sweep.
 template <typename T>
 hipError_t launch_count_dirty_padding(const GridDesc &g, const T *f, unsigned long long *bad, hipStream_t s);
-// *out += sum a[i] * b[i]  (out must be zeroed by the caller)
+// part[sum_blocks(n)] = sum a[i] * b[i], added in a fixed order (no atomics: equal inputs give equal bits) through the
+// block partials part[0 .. sum_blocks(n)); part holds sum_blocks(n) + 1 <= SUM_MAX_BLOCKS + 1 doubles
+constexpr int SUM_MAX_BLOCKS = 1024;
+int sum_blocks(int64_t n);
 template <typename T>
-hipError_t launch_dot(const T *a, const T *b, int64_t n, double *out, hipStream_t s);
+hipError_t launch_dot(const T *a, const T *b, int64_t n, double *part, hipStream_t s);
+// partial[n] = sum of partial[0 .. n) in a fixed order, one block (fwi_reg.hip: the final kernel of the regulariser)
+hipError_t launch_sum_partials(double *partial, int64_t n, hipStream_t s);
 
 // off-grid points: per-point (nt, npts) <-> per-node (nt, nnodes) time series; a point's nodes are entries
 // pt_start[p] .. pt_start[p + 1] (at most 8), owner[m] is the point of entry m, w[m] its interpolation weight
@@ -173,9 +178,9 @@ hipError_t launch_scatter_series(const T *pt, T *node, const int *owner, const T
 template <typename T>
 hipError_t launch_gather_series(const T *node, T *pt, const int *pt_start, const T *w, int nt, int npts, int nnodes,
                                 hipStream_t s);
-// obs_inout := syn - obs_inout; *out += sum of its squares (out zeroed by the caller)
+// obs_inout := syn - obs_inout; part[sum_blocks(n)] = sum of its squares, as launch_dot
 template <typename T>
-hipError_t launch_residual_l2(const T *syn, T *obs_inout, int64_t n, double *out, hipStream_t s);
+hipError_t launch_residual_l2(const T *syn, T *obs_inout, int64_t n, double *part, hipStream_t s);
 
 // ---- convolutional PML (fwi_pml.hip): slab kernels around the undamped step kernels ------------------------
 // The SHELL of an axis of n cells: its two borders and the r cells inward that their term reaches (the rows whose
@@ -323,7 +328,8 @@ int pair3d_num_tiles(const GridDesc &g, int zchunk, int tw);
 int pair3d_tile_of(const GridDesc &g, int zchunk, int tw, int z, int y, int x);
 hipError_t launch_pair3d(const GridDesc &g, const Pair3dArgs &a, int zchunk, int tw, hipStream_t s);
 
-// optimiser vector algebra: y = a x + b y; clamp; *out = max(*out, max|x|) (out zeroed by the caller)
+// optimiser vector algebra: y = a x + b y; clamp (a NaN stays NaN); *out = max(*out, max|x|) (out zeroed by the caller;
+// NaN if any element is NaN, as np.abs(x).max())
 template <typename T>
 hipError_t launch_axpby(T *y, double a, const T *x, double b, int64_t n, hipStream_t s);
 // clamps the grid points only (pad columns of a compact array stay zero)

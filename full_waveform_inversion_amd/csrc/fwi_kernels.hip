@@ -643,33 +643,45 @@ hipError_t launch_count_dirty_padding(const GridDesc &g, const T *f, unsigned lo
     return hipGetLastError();
 }
 
-// wave64 shuffle reduction -> LDS across the 4 waves -> one fp64 atomic per block
+// The two sums of the optimiser and the misfit, in one fixed order: per thread over its ascending grid-stride indices
+// (fp64 accumulator, starting from +0), the wave's shuffle tree (offsets 32, 16, .., 1), the four waves as
+// (w0 + w1) + (w2 + w3) into part[block], and launch_sum_partials over the block partials (fwi_reg.hip: thread t adds
+// part[t], part[t + 256], .. in ascending order, then a halving tree over the 256 threads) into part[blocks].  No
+// floating-point atomics: equal inputs give equal bits on every call, context and rank.  tests/_vecops.py restates the
+// order in NumPy.
+__device__ inline void block_sum_to_partial(double acc, double *part) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    __shared__ double wsum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wsum[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
 template <typename T>
-__global__ __launch_bounds__(256) void dot_kernel(const T *a, const T *b, int64_t n, double *out) {
+__global__ __launch_bounds__(256) void dot_kernel(const T *a, const T *b, int64_t n, double *part) {
     double acc = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x)
         acc += (double)a[i] * (double)b[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    __shared__ double part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) part[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, (part[0] + part[1]) + (part[2] + part[3]));
+    block_sum_to_partial(acc, part);
 }
 
+int sum_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(SUM_MAX_BLOCKS, (n + 255) / 256)); }
+
 template <typename T>
-hipError_t launch_dot(const T *a, const T *b, int64_t n, double *out, hipStream_t s) {
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n + 255) / 256));
-    hipLaunchKernelGGL(dot_kernel<T>, dim3(blocks), dim3(256), 0, s, a, b, n, out);
-    return hipGetLastError();
+hipError_t launch_dot(const T *a, const T *b, int64_t n, double *part, hipStream_t s) {
+    const int blocks = sum_blocks(n);
+    hipLaunchKernelGGL(dot_kernel<T>, dim3(blocks), dim3(256), 0, s, a, b, n, part);
+    hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_sum_partials(part, blocks, s);
 }
 
 // Least-squares residual and misfit on the device: r = syn - obs (written over obs, where the adjoint
-// sweep reads its injection amplitudes), *out += sum r^2 -- same reduction shape as dot_kernel.
+// sweep reads its injection amplitudes), and the sum of r^2 in the order of dot_kernel.
 template <typename T>
-__global__ __launch_bounds__(256) void residual_l2_kernel(const T *syn, T *obs_inout, int64_t n, double *out) {
+__global__ __launch_bounds__(256) void residual_l2_kernel(const T *syn, T *obs_inout, int64_t n, double *part) {
     double acc = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
@@ -677,20 +689,15 @@ __global__ __launch_bounds__(256) void residual_l2_kernel(const T *syn, T *obs_i
         obs_inout[i] = r;
         acc += (double)r * (double)r;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    __shared__ double part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) part[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, (part[0] + part[1]) + (part[2] + part[3]));
+    block_sum_to_partial(acc, part);
 }
 
 template <typename T>
-hipError_t launch_residual_l2(const T *syn, T *obs_inout, int64_t n, double *out, hipStream_t s) {
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n + 255) / 256));
-    hipLaunchKernelGGL(residual_l2_kernel<T>, dim3(blocks), dim3(256), 0, s, syn, obs_inout, n, out);
-    return hipGetLastError();
+hipError_t launch_residual_l2(const T *syn, T *obs_inout, int64_t n, double *part, hipStream_t s) {
+    const int blocks = sum_blocks(n);
+    hipLaunchKernelGGL(residual_l2_kernel<T>, dim3(blocks), dim3(256), 0, s, syn, obs_inout, n, part);
+    hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_sum_partials(part, blocks, s);
 }
 
 // Off-grid points (multilinear interpolation): per-point time series <-> per-node time series on the device.
@@ -754,23 +761,35 @@ __global__ void axpby_kernel(T *y, double a, const T *x, double b, int64_t n) {
 template <typename T>
 __global__ void clip_kernel(T *x, double lo, double hi, int64_t n, int nx, int cx) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        if (cx == nx || (int)(i % cx) < nx) x[i] = (T)fmin(fmax((double)x[i], lo), hi);
+        if (cx == nx || (int)(i % cx) < nx) {
+            // NumPy's clip: only a value below lo or above hi is replaced, so a NaN stays and a zero that ties with a
+            // bound of the other sign keeps its own sign
+            const double v = (double)x[i];
+            if (v < lo)
+                x[i] = (T)lo;
+            else if (v > hi)
+                x[i] = (T)hi;
+        }
 }
 
-// *out = max(*out, max |x|): wave64 shuffle max, LDS across waves, one atomic per block.  The
-// bit pattern of a non-negative double orders like an unsigned integer.
+// *out = max(*out, max |x|) as NumPy's np.abs(x).max(): a NaN wins over everything, +inf over every number.  wave64
+// shuffle max, LDS across waves, one atomic per block.  The bit pattern of a non-negative double orders like an unsigned
+// integer, and that of a positive NaN (fabs clears the sign) lies above +inf's: the integer atomic propagates the NaN and
+// does not depend on the order of arrival.
+__device__ inline double nan_max(double a, double b) { return (a != a || a > b) ? a : b; }  // b if b is NaN, too
+
 template <typename T>
 __global__ __launch_bounds__(256) void absmax_kernel(const T *x, int64_t n, unsigned long long *out) {
     double m = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        m = fmax(m, fabs((double)x[i]));
+        m = nan_max(fabs((double)x[i]), m);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+    for (int off = 32; off > 0; off >>= 1) m = nan_max(m, __shfl_down(m, off, 64));
     __shared__ double part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
-        m = fmax(fmax(part[0], part[1]), fmax(part[2], part[3]));
+        m = nan_max(nan_max(part[0], part[1]), nan_max(part[2], part[3]));
         atomicMax(out, (unsigned long long)__double_as_longlong(m));
     }
 }

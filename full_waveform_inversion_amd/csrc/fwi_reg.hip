@@ -230,7 +230,11 @@ hipError_t launch_regularizer(const GridDesc &g, int kind, T *out, const T *x, c
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(reg_final, dim3(1), block, 0, s, partial, blocks);
+    return launch_sum_partials(partial, blocks, s);
+}
+
+hipError_t launch_sum_partials(double *partial, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(reg_final, dim3(1), dim3(RG_BLOCK), 0, s, partial, n);
     return hipGetLastError();
 }
 

@@ -238,8 +238,9 @@ def _backtrack(t, f0, gp, ft):
 
 
 def _require_finite(f, gmax, gg, it):
-    """A blown-up propagation must not pass for convergence: ``max |g|`` built on ``fmax`` ignores NaN
-    (an all-NaN gradient reads 0 = "stationary"), so the squared norm is checked as well."""
+    """A blown-up propagation must not pass for convergence.  ``max |g|`` is NaN when any entry is (``np.abs(g).max()``
+    on the host, ``fwi_vec_absmax`` on the device: the same semantics); the squared norm is checked as well, which also
+    catches finite entries whose squares overflow."""
     if not (np.isfinite(f) and np.isfinite(gmax) and np.isfinite(gg)):
         raise FloatingPointError("L-BFGS iteration %d: non-finite misfit or gradient (f=%r, max|g|=%r, g.g=%r); "
                                  "check the time step against the CFL limit of the current model" % (it, f, gmax, gg))

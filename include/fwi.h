@@ -173,7 +173,7 @@ int fwi_adjoint(fwi_ctx *ctx, const void *residual, int32_t image, void *adj_src
 
 /* Least-squares misfit on the device: with d_syn the seismograms of the last fwi_forward (still resident),
  * forms the residual r = d_syn - d_obs there, returns J = 1/2 sum r^2 (wave64 __shfl_down reduction, fp64
- * accumulate) and keeps r as the residual of the next fwi_adjoint(ctx, NULL, ...): neither the residual nor a
+ * accumulate, block sums added in a fixed order: equal inputs give equal bits on every call) and keeps r as the residual of the next fwi_adjoint(ctx, NULL, ...): neither the residual nor a
  * second copy of the data crosses PCIe.  [SURVEY s.8(a-1) row "gradient dot-products / J"] */
 int fwi_misfit_l2(fwi_ctx *ctx, const void *d_obs /* (nt, nrec) */, double *J_out);
 
@@ -218,7 +218,8 @@ int fwi_gradient_add(fwi_ctx *dst, fwi_ctx *src);
 
 /* Device-side reductions for the misfit and the optimiser's dot products:
  * sum_i a[i]*b[i] over n host elements of the context dtype, wave-shuffle
- * reduced on the GPU, fp64 accumulate.  [SURVEY s.8(a-1) row dot-products] */
+ * reduced on the GPU, fp64 accumulate, in a fixed order without floating-point atomics: equal inputs give equal
+ * bits on every call, context and rank (fwi_vec_dot and fwi_misfit_l2 alike).  [SURVEY s.8(a-1) row dot-products] */
 int fwi_dot(fwi_ctx *ctx, const void *a_host, const void *b_host, int64_t n, double *out);
 
 /* Device-resident, model-shaped vectors for the optimiser (L-BFGS history, search direction,
@@ -230,7 +231,9 @@ int fwi_vec_download(fwi_ctx *ctx, int32_t slot, void *host);
 int fwi_vec_copy(fwi_ctx *ctx, int32_t dst, int32_t src);
 int fwi_vec_axpby(fwi_ctx *ctx, int32_t y, double a, int32_t x, double b); /* y = a x + b y */
 int fwi_vec_dot(fwi_ctx *ctx, int32_t x, int32_t y, double *out);
+/* max |x| as NumPy's np.abs(x).max(): NaN if any element is NaN, +inf if any is infinite and none is NaN */
 int fwi_vec_absmax(fwi_ctx *ctx, int32_t x, double *out);
+/* x := min(max(x, lo), hi) as NumPy's np.clip: a NaN stays a NaN; lo > hi (or a NaN bound) is FWI_EINVAL */
 int fwi_vec_clip(fwi_ctx *ctx, int32_t x, double lo, double hi);
 /* model := slot (velocity), without leaving the device */
 int fwi_set_model_vec(fwi_ctx *ctx, int32_t slot);

@@ -112,7 +112,8 @@ def test_shots_and_pool_contexts_sum_and_reset_zeroes(gpu):
         f2, g2, H2 = sh.misfit_and_gradient(two, c, shots, illumination=True)
         assert not any(e.illumination_enabled for e in two.engines)  # switched back off after the evaluation
         f0, g0 = sh.misfit_and_gradient(one, c, shots)
-        # the gradient does not see the illumination (the misfit: up to the order of its fp64 atomic block sums)
+        # the gradient does not see the illumination (the misfit: the bar dates from fp64 atomic block sums; the device's
+        # sums now add in a fixed order, tests/test_gpu_vecops.py)
         assert np.array_equal(g0, g1) and abs(f0 - f1) <= 1e-12 * f0
         assert rel(H1, Hc) < TOL32 and rel(H2, Hc) < TOL32
         e = one.primary
@@ -196,6 +197,7 @@ def test_preconditioned_lbfgs_beats_the_plain_one_on_cfg3(gpu):
     f_pre, log_pre = _inversion(True)
     print("plain", [e["f"] for e in log_plain], "preconditioned", [e["f"] for e in log_pre])
     # the same starting model: the same misfit, up to the order in which the device's misfit reduction adds its block
-    # sums (fp64 atomics: the last bit or two differ from run to run, with or without illumination)
+    # sums (a bar from the time of fp64 atomics, when the last bit or two differed from run to run; the sums now add in a
+    # fixed order, tests/test_gpu_vecops.py)
     assert abs(log_pre[0]["f"] - log_plain[0]["f"]) <= 1e-12 * log_plain[0]["f"]
     assert f_pre < f_plain
