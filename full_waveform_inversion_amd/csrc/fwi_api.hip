@@ -25,6 +25,8 @@
 #include "fwi_data.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
+#include "fwi_match.h"
+#include "fwi_match_solve.h"
 #include "fwi_reg.h"
 #include "fwi_smooth.h"
 
@@ -186,6 +188,10 @@ struct fwi_ctx {
     // filter passes, the weights, the taps, the block partial sums of J (and their total)
     void *data_tmp = nullptr, *data_w = nullptr, *data_taps = nullptr, *data_part = nullptr;
     size_t cap_data_tmp = 0, cap_data_w = 0, cap_data_taps = 0, cap_data_part = 0;
+    // fwi_misfit_matched (fwi_match.hip), allocated by its first call: the filtered synthetics s' and data d' (with taps),
+    // the slices of the normal equations, G and b, the filter
+    void *match_s = nullptr, *match_d = nullptr, *match_part = nullptr, *match_norm = nullptr, *match_f = nullptr;
+    size_t cap_match_s = 0, cap_match_d = 0, cap_match_part = 0, cap_match_norm = 0, cap_match_f = 0;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
     enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
     int resid_pts_in = RESID_PTS_NONE;
@@ -1832,6 +1838,98 @@ struct Impl {
         return FWI_OK;
     }
 
+    // s' = B d_syn, d' = B d_obs, e = M . (C_f s' - d'), J = 1/2 sum e^2 + mu/2 |f|^2, r = B C_f^T (M . e) where the
+    // adjoint sweep reads its amplitudes; f given, or the minimiser (G + mu I)^-1 b of J
+    static int misfit_matched(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, int L, double mu,
+                              const double *f_in, double *f_out, double *normal_out, double *J_out) {
+        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
+        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec, K = 2 * L + 1;
+        const size_t n = (size_t)nt * ntr;
+        const bool data = n && ctx->nrec;
+        std::vector<double> f(K, 0.0), nrm((size_t)K * K + K, 0.0);
+        if (f_in) std::copy(f_in, f_in + K, f.begin());
+        // whatever residual the device held goes with the upload of d_obs: none is left until this call succeeds
+        ctx->have_dev_residual = false;
+        ctx->resid_pts_in = fwi_ctx::RESID_PTS_NONE;
+        void *resid = ctx->amp;
+        const T *w = nullptr, *s1 = nullptr, *d1 = nullptr;
+        const double *b = nullptr;
+        int rc, Re = 0;
+        if (data) {
+            // off-grid receivers: everything per POINT (against the gathered synthetics kept by the forward), r then
+            // scattered onto the nodes, as misfit_l2 does
+            if (sp.npts) {
+                if ((rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T)))) return rc;
+                resid = ctx->pts_a;
+            }
+            if ((rc = upload_series(ctx, resid, d_obs, n * sizeof(T)))) return rc;
+            if ((rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
+            if ((rc = ensure(ctx, &ctx->data_part, &ctx->cap_data_part,
+                             (size_t)(std::max(fir_blocks(nt, ntr), match_apply_blocks(nt, ntr)) + 1) * sizeof(double))))
+                return rc;
+            if ((rc = ensure(ctx, &ctx->match_f, &ctx->cap_match_f, (size_t)K * sizeof(double)))) return rc;
+            s1 = (const T *)(sp.npts ? ctx->pts_d : ctx->series);
+            d1 = (const T *)resid;
+            if (b) {  // each rounded to T once
+                if ((rc = ensure(ctx, &ctx->match_s, &ctx->cap_match_s, n * sizeof(T)))) return rc;
+                if ((rc = ensure(ctx, &ctx->match_d, &ctx->cap_match_d, n * sizeof(T)))) return rc;
+                HIPCHK(ctx, launch_fir_time<T>((T *)ctx->match_s, s1, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr,
+                                               false, ctx->stream));
+                HIPCHK(ctx, launch_fir_time<T>((T *)ctx->match_d, d1, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr,
+                                               false, ctx->stream));
+                s1 = (const T *)ctx->match_s;
+                d1 = (const T *)ctx->match_d;
+            }
+            if (!f_in || normal_out) {
+                if ((rc = ensure(ctx, &ctx->match_part, &ctx->cap_match_part,
+                                 (size_t)match_normal_partials(nt, ntr, L) * sizeof(double))))
+                    return rc;
+                if ((rc = ensure(ctx, &ctx->match_norm, &ctx->cap_match_norm, nrm.size() * sizeof(double)))) return rc;
+                HIPCHK(ctx, launch_match_normal<T>((double *)ctx->match_norm, (double *)ctx->match_part, s1, d1, w, L, nt,
+                                                   ntr, ctx->stream));
+                HIPCHK(ctx, hipMemcpyAsync(nrm.data(), ctx->match_norm, nrm.size() * sizeof(double),
+                                           hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            }
+        }
+        if (!f_in && match_solve(nrm.data(), nrm.data() + (size_t)K * K, K, mu, f.data()))
+            return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: the normal matrix G + mu I (L=%d, mu=%g) is not positive "
+                                         "definite: raise mu", L, mu);
+        double ss = 0.0;
+        if (data) {
+            double *part = (double *)ctx->data_part;
+            // (the filter is this call's pageable memory: the copy is complete before anything that can return follows)
+            HIPCHK(ctx, hipMemcpyAsync(ctx->match_f, f.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice,
+                                       ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            const double *fd = (const double *)ctx->match_f;
+            HIPCHK(ctx, launch_match_apply<T>((T *)ctx->data_tmp, s1, d1, nullptr, w, fd, L, false, nt, ntr, part,
+                                              ctx->stream));
+            // the synthetics s' and the data d' are used up: C_f^T (M . e) takes the place of s' (with taps), B then
+            // writes r over the uploaded d_obs
+            T *ct = b ? (T *)ctx->match_s : (T *)resid;
+            HIPCHK(ctx, launch_match_apply<T>(ct, (const T *)ctx->data_tmp, nullptr, w, nullptr, fd, L, true, nt, ntr,
+                                              nullptr, ctx->stream));
+            if (b)
+                HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)ct, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr,
+                                               false, ctx->stream));
+            if (sp.npts)
+                HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
+                                                     (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(&ss, part + match_apply_blocks(nt, ntr), sizeof(double), hipMemcpyDeviceToHost,
+                                       ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        double ff = 0.0;
+        for (int k = 0; k < K; ++k) ff += f[k] * f[k];
+        *J_out = 0.5 * ss + 0.5 * mu * ff;
+        if (f_out) std::copy(f.begin(), f.end(), f_out);
+        if (normal_out) std::copy(nrm.begin(), nrm.end(), normal_out);
+        ctx->have_dev_residual = true;
+        ctx->resid_pts_in = (data && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
+        return FWI_OK;
+    }
+
     // device residual := B M^2 B residual: per node, or per off-grid point and scattered onto the nodes again
     static int residual_weight(fwi_ctx *ctx, const T *weights, const double *taps, int R) {
         const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
@@ -2337,7 +2435,8 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}, {"reg_part", ctx->reg_part},
                   {"sum_part", ctx->sum_part},
                   {"data_tmp", ctx->data_tmp}, {"data_w", ctx->data_w}, {"data_taps", ctx->data_taps},
-                  {"data_part", ctx->data_part}};
+                  {"data_part", ctx->data_part}, {"match_s", ctx->match_s}, {"match_d", ctx->match_d},
+                  {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2499,6 +2598,33 @@ int fwi_misfit_weighted(fwi_ctx *ctx, const void *d_obs, const void *weights, co
     return DISPATCH(ctx,
                     Impl<float>::misfit_weighted(ctx, (const float *)d_obs, (const float *)weights, taps, R, J_out),
                     Impl<double>::misfit_weighted(ctx, (const double *)d_obs, (const double *)weights, taps, R, J_out));
+}
+
+int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R, int32_t L,
+                       double mu, const double *f_in, double *f_out, double *normal_out, double *J_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "fwi_misfit_matched: no forward run whose data to compare");
+    if (!J_out || (ctx->nrec && !d_obs)) return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: null argument");
+    if (int rc = data_args(ctx, "fwi_misfit_matched", taps, R)) return rc;
+    if (L < 0 || L > FWI_MATCH_LMAX)
+        return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: L=%d outside [0, %d]", (int)L, FWI_MATCH_LMAX);
+    if (!(mu >= 0.0) || !std::isfinite(mu)) return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: mu=%g must be finite and >= 0", mu);
+    if (f_in)
+        for (int k = 0; k < 2 * L + 1; ++k)
+            if (!std::isfinite(f_in[k])) return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: f_in[%d] is not finite", k);
+    if (!ctx->have_syn)
+        return ctx->fail(FWI_ESTATE, "fwi_misfit_matched: the synthetics of the last forward are gone (an fwi_adjoint "
+                                     "or fwi_born has run since): call it between fwi_forward and fwi_adjoint");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx,
+                    Impl<float>::misfit_matched(ctx, (const float *)d_obs, (const float *)weights, taps, R, L, mu, f_in,
+                                                f_out, normal_out, J_out),
+                    Impl<double>::misfit_matched(ctx, (const double *)d_obs, (const double *)weights, taps, R, L, mu, f_in,
+                                                 f_out, normal_out, J_out));
+}
+
+int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {
+    return match_solve(G, b, K, mu, f_out) ? FWI_EINVAL : FWI_OK;
 }
 
 int fwi_residual_weight(fwi_ctx *ctx, const void *weights, const double *taps, int32_t R) {

@@ -15,6 +15,23 @@ The engine forms ``e``, ``J`` and ``r`` on the device (``Engine.misfit_weighted`
 ``shots.misfit_and_gradient`` recognises.  Band-limiting the residual is how frequency continuation from low to high
 bands avoids cycle skipping (:func:`frequency_continuation`); the weights carry trace kills, direct-arrival mutes and
 offset / time windows (:func:`offset_time_mute`).  No reference counterpart.
+
+Matching-filter (source-independent) misfit, :class:`MatchedL2` (``Engine.misfit_matched``, ``fwi_misfit_matched``,
+``csrc/fwi_match.hip``): the source signature is never known exactly, and a wrong wavelet leaks into the model update.
+Per shot a short two-sided filter ``f = (f_-L .. f_L)``, ``K = 2 L + 1``, along time on the zero-extended trace takes
+it up and is eliminated by variable projection.  With ``s = d_syn``, ``d = d_obs``, ``B`` and ``M`` as above:
+
+    s' = B s,   d' = B d
+    (C_f x)[n, j]   = sum_{k=-L..L} f_k x[n - k, j]      terms with n - k outside [0, nt) omitted
+    (C_f^T y)[m, j] = sum_{k=-L..L} f_k y[m + k, j]      terms with m + k outside [0, nt) omitted
+    e = M . (C_f s' - d')
+    Phi(f; s) = 1/2 sum e^2 + mu/2 |f|^2                 mu >= 0 absolute, given by the caller
+    G[k, l] = sum_{n, j} M^2[n, j] s'[n - k, j] s'[n - l, j],    b[k] = sum_{n, j} M^2[n, j] s'[n - k, j] d'[n, j]
+    f* = (G + mu I)^-1 b,     J(s) = Phi(f*; s),     r = dJ/ds = B C_{f*}^T (M . e)       (dPhi/df = 0 at f*)
+
+``G`` is not Toeplitz (the weights, the truncation at both ends of the trace).  ``mu`` is independent of ``s`` on purpose:
+one that depended on ``s`` would add a term to the gradient (:func:`prewhitening` is a data-only choice).
+``L = 0, f = (1), mu = 0`` with a given filter is :class:`WeightedL2`'s ``e`` and ``r``.
 """
 from __future__ import annotations
 
@@ -23,6 +40,7 @@ import math
 import numpy as np
 
 R_MAX = 4096  # the largest half-width the device path accepts (fwi_misfit_weighted)
+L_MAX = 64    # the largest half-length of a matching filter the device path accepts (fwi_misfit_matched)
 
 
 def _lowpass_raw(dt, f, R):
@@ -134,6 +152,146 @@ class WeightedL2:
         M = self._weights(weights, x.shape)
         e = self.filter(x)
         return self.filter(e if M is None else M * M * e)
+
+
+def _conv_time(x, f, transpose=False):
+    """``C_f x`` (``C_f^T x`` with ``transpose``) along axis 0, ``f = (f_-L .. f_L)``, added over ascending k in fp64."""
+    x = np.asarray(x, np.float64)
+    f = np.asarray(f, np.float64)
+    L, nt = (len(f) - 1) // 2, x.shape[0]
+    out = np.zeros_like(x)
+    for k in range(-L, L + 1):
+        sh = -k if transpose else k  # out[n] += f_k x[n - sh]
+        if abs(sh) >= nt:
+            continue
+        if sh >= 0:
+            out[sh:] += f[k + L] * x[:nt - sh]
+        else:
+            out[:nt + sh] += f[k + L] * x[-sh:]
+    return out
+
+
+class MatchedL2:
+    """The matching-filter misfit of the module's definition in fp64 NumPy, and the ``objective=`` that
+    ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_matched`` replaces it by the device path).
+
+    ``L``: the half-length of the filter, ``K = 2 L + 1`` coefficients ``f[k + L] = f_k``.  ``mu``: the absolute damping
+    ``>= 0`` of the normal equations -- one number for every shot, or a sequence indexed like the list of shots (the shot
+    loop passes ``shot=`` and reads ``mu[shot]``): data-only numbers such as :func:`prewhitening` of each shot's
+    ``d_obs``, computed once and held through an inversion.  ``taps``: the one-sided ``b_0 .. b_R`` of ``B``, or None.
+    ``dtype``: round ``B s`` and ``B d`` to it once, as a device context of that dtype does (None: keep fp64).
+
+    ``filters`` maps a shot's index to the last ``f*`` the shot loop estimated for it (device or host branch alike).
+    Not a :class:`WeightedL2`: the Gauss-Newton operator of the reduced objective is not ``B M^2 B``."""
+
+    def __init__(self, L, mu, taps=None, dtype=None):
+        if int(L) != L or not 0 <= int(L) <= L_MAX:
+            raise ValueError("L must be an integer in [0, %d]" % L_MAX)
+        self.L, self.K = int(L), 2 * int(L) + 1
+        mu_all = np.atleast_1d(np.asarray(mu, np.float64))
+        if mu_all.ndim != 1 or not np.all(np.isfinite(mu_all)) or np.any(mu_all < 0.0):
+            raise ValueError("mu must be finite and >= 0 (a number, or one per shot)")
+        self.mu = float(mu) if np.ndim(mu) == 0 else mu_all
+        self.taps = _checked_taps(taps)
+        self.dtype = None if dtype is None else np.dtype(dtype)
+        self.filters = {}
+
+    def mu_of(self, shot=None):
+        """the damping of shot ``shot`` (the scalar ``mu`` for every shot, or ``mu[shot]``)"""
+        if np.ndim(self.mu) == 0:
+            return self.mu
+        if shot is None:
+            raise ValueError("mu is given per shot: the call needs shot=")
+        return float(self.mu[shot])
+
+    def filter(self, x):
+        """``B x`` (rounded to ``dtype`` once)"""
+        y = fir_time(x, self.taps)
+        return y if self.dtype is None else y.astype(self.dtype).astype(np.float64)
+
+    def _prepared(self, d_syn, d_obs, weights):
+        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
+        if s.ndim != 2 or s.shape != d.shape:
+            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
+        return self.filter(s), self.filter(d), WeightedL2._weights(weights, s.shape)
+
+    def normal(self, d_syn, d_obs, weights=None):
+        """``(G, b)`` of the definition: ``G`` is ``K x K``, symmetric, without ``mu``."""
+        s1, d1, M = self._prepared(d_syn, d_obs, weights)
+        nt, ntr = s1.shape
+        L, K = self.L, self.K
+        G, b = np.zeros((K, K)), np.zeros(K)
+        step = max(1, (1 << 22) // (K * nt))  # traces per block: the K shifted copies stay below 32 MB
+        for j0 in range(0, ntr, step):
+            sl = slice(j0, min(j0 + step, ntr))
+            Z = np.zeros((K, nt, sl.stop - sl.start))
+            for k in range(-L, L + 1):  # Z[k + L][n] = s'[n - k]
+                if k >= nt or -k >= nt:
+                    continue
+                if k >= 0:
+                    Z[k + L, k:] = s1[:nt - k, sl]
+                else:
+                    Z[k + L, :nt + k] = s1[-k:, sl]
+            Zw = Z if M is None else Z * (M[:, sl] * M[:, sl])
+            Z2, Zw2 = Z.reshape(K, -1), Zw.reshape(K, -1)
+            G += Zw2 @ Z2.T
+            b += Zw2 @ d1[:, sl].reshape(-1)
+        return 0.5 * (G + G.T), b
+
+    def solve(self, G, b, mu=None):
+        """``f* = (G + mu I)^-1 b``; ``mu``: this objective's scalar unless given.  Raises
+        ``ValueError`` when ``G + mu I`` is not positive definite (raise ``mu``)."""
+        mu = self.mu_of() if mu is None else float(mu)
+        A = np.asarray(G, np.float64) + mu * np.eye(len(b))
+        try:
+            np.linalg.cholesky(A)  # (the test of definiteness the device path makes)
+        except np.linalg.LinAlgError:
+            raise ValueError("the normal matrix G + mu I (mu = %g) is not positive definite: raise mu" % mu) from None
+        return np.linalg.solve(A, np.asarray(b, np.float64))
+
+    def apply(self, d_syn, d_obs, f, weights=None, mu=None):
+        """``(J, r)`` at the given filter: ``J = Phi(f; d_syn)``, ``r = B C_f^T (M . e)``, which is ``dJ/dd_syn`` of the
+        reduced objective when ``f`` is the minimiser :meth:`solve` returns."""
+        mu = self.mu_of() if mu is None else float(mu)
+        f = np.asarray(f, np.float64)
+        if f.shape != (self.K,):
+            raise ValueError("f must hold the 2 L + 1 = %d coefficients f_-L .. f_L" % self.K)
+        s1, d1, M = self._prepared(d_syn, d_obs, weights)
+        e = _conv_time(s1, f) - d1
+        if M is not None:
+            e *= M
+        J = 0.5 * float(np.sum(e * e)) + 0.5 * mu * float(np.sum(f * f))
+        return J, fir_time(_conv_time(e if M is None else M * e, f, transpose=True), self.taps)
+
+    def __call__(self, d_syn, d_obs, weights=None, shot=None):
+        """Estimate ``f*``, then :meth:`apply` it.  ``shot``: the index whose ``mu`` is read and under which ``f*`` is kept
+        in ``filters`` (the shot loop passes it)."""
+        mu = self.mu_of(shot)
+        f = self.solve(*self.normal(d_syn, d_obs, weights), mu=mu)
+        if shot is not None:
+            self.filters[shot] = f
+        return self.apply(d_syn, d_obs, f, weights, mu=mu)
+
+
+def matched_wavelet(wavelet, f):
+    """``C_f`` applied to a wavelet ``(nt,)`` or ``(nt, nsrc)``: the source signature a shot's matching filter
+    ``f = (f_-L .. f_L)`` implies, ``w'[n] = sum_k f_k w[n - k]``."""
+    f = np.asarray(f, np.float64)
+    if f.ndim != 1 or f.size % 2 != 1:
+        raise ValueError("f must hold 2 L + 1 coefficients f_-L .. f_L")
+    return _conv_time(wavelet, f)
+
+
+def prewhitening(d_obs, weights=None, percent=0.1):
+    """``percent / 100 * sum (M d_obs)^2``: a damping ``mu`` for :class:`MatchedL2` that depends on the data only --
+    compute it once per shot and hold it through an inversion (a ``mu`` that followed ``d_syn`` would break the
+    gradient)."""
+    d = np.asarray(d_obs, np.float64)
+    M = WeightedL2._weights(weights, d.shape)
+    if not (float(percent) >= 0.0 and np.isfinite(percent)):
+        raise ValueError("percent must be finite and >= 0")
+    md = d if M is None else M * d
+    return float(percent) / 100.0 * float(np.sum(md * md))
 
 
 def offset_time_mute(shot, h, dt, v_fast, t_pad=0.0, taper=0):

@@ -253,6 +253,37 @@ class Engine:
         self._chk(self._lib.fwi_misfit_weighted(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, C.byref(J)))
         return J.value
 
+    def misfit_matched(self, d_obs, L, mu, weights=None, taps=None, f=None, normal=False):
+        """Matching-filter (source-independent) misfit of the last forward's seismograms: with ``s' = B d_syn``,
+        ``d' = B d_obs``, ``e = M . (C_f s' - d')`` and ``C_f`` the convolution along time with the two-sided filter
+        ``f = (f_-L .. f_L)``, ``J = 1/2 sum e^2 + mu/2 |f|^2``.  ``f=None``: the filter is the minimiser
+        ``(G + mu I)^-1 b`` of J (normal equations on the device), so that J is the reduced objective and the adjoint
+        source ``B C_f^T (M . e)``, formed on the device and kept for ``adjoint(None)``, its gradient; otherwise the
+        given ``2 L + 1`` coefficients are used.  ``mu >= 0`` is absolute (``datafit.prewhitening``).  ``weights`` and
+        ``taps`` as in :meth:`misfit_weighted`.  Returns ``(J, f)``, with ``normal=True`` ``(J, f, G, b)``, ``G`` the
+        ``K x K`` normal matrix without ``mu`` (``fwi_misfit_matched``; the NumPy twin is :class:`datafit.MatchedL2`)."""
+        d_obs = self._host(d_obs, (self._nt, self._nrec))
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        if int(L) != L:
+            raise ValueError("L must be an integer")
+        L = int(L)
+        K = 2 * max(L, 0) + 1
+        fp = None
+        if f is not None:
+            f = np.ascontiguousarray(f, dtype=np.float64)
+            if f.shape != (K,):
+                raise ValueError("f must hold the 2 L + 1 = %d coefficients f_-L .. f_L" % K)
+            fp = f.ctypes.data_as(C.c_void_p)
+        f_out = np.zeros(K)
+        nrm = np.zeros(K * K + K) if normal else None
+        J = C.c_double(0.0)
+        self._chk(self._lib.fwi_misfit_matched(
+            self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, L, float(mu), fp, f_out.ctypes.data_as(C.c_void_p),
+            nrm.ctypes.data_as(C.c_void_p) if normal else None, C.byref(J)))
+        if normal:
+            return J.value, f_out, nrm[:K * K].reshape(K, K).copy(), nrm[K * K:].copy()
+        return J.value, f_out
+
     def residual_weight(self, weights=None, taps=None):
         """The residual on the device (what ``born`` or a misfit call left for ``adjoint(None)``) := ``B M^2 B`` residual,
         the Gauss-Newton weight of :meth:`misfit_weighted` (``fwi_residual_weight``)."""

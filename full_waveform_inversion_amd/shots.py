@@ -25,7 +25,7 @@ class Shot:
     src_spread: object = None
     rec_spread: object = None
     point_wavelet: np.ndarray | None = None  # (nt[, nsrc points]): the wavelets before spreading
-    weights: np.ndarray | None = None  # (nt, nrec) data weights >= 0 of a datafit.WeightedL2 objective (None: 1)
+    weights: np.ndarray | None = None  # (nt, nrec) data weights >= 0 of a datafit.WeightedL2 / MatchedL2 objective (None: 1)
 
     @classmethod
     def at_coordinates(cls, src_xyz, wavelet, rec_xyz, shape, d_obs=None):
@@ -298,6 +298,12 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     A :class:`datafit.WeightedL2` objective (band-limited, weighted least squares) is handed each shot's
     ``Shot.weights``; under ``device_l2`` an engine that has ``misfit_weighted`` forms its residual on the device too.
 
+    A :class:`datafit.MatchedL2` objective (matching-filter, source-independent misfit) is handed ``Shot.weights`` as
+    well; an engine that has ``misfit_matched`` estimates and applies each shot's filter on the device, otherwise the
+    NumPy twin does on the host.  Its damping is ``objective.mu``: one number for every shot, or a sequence indexed like
+    ``shots`` (``datafit.prewhitening`` of each shot's data).  Either branch leaves shot ``i``'s filter in
+    ``objective.filters[i]``.
+
     ``device_l2`` (least squares only): form the residual and J on the device (``fwi_misfit_l2``) -- in the
     engine's dtype, i.e. with an fp32 engine ``d_obs`` is rounded to fp32 before the subtraction, which puts
     ~6e-8 |d| / |r| of relative noise on J and on the residual (visible to a line search only once |r| / |d|
@@ -323,9 +329,10 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
 def _sweep_shots(engine, shots, ex, objective, device_l2=True):
     """forward + adjoint of this rank's shots; returns the misfit, gradients summed into the
     (primary) engine's accumulator."""
-    from .datafit import WeightedL2
+    from .datafit import MatchedL2, WeightedL2
     from .objectives import l2
     weighted = isinstance(objective, WeightedL2)
+    matched = isinstance(objective, MatchedL2)
 
     def one(e, i):
         s = shots[i]
@@ -340,6 +347,15 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True):
         if device_l2 and weighted and hasattr(e, "misfit_weighted") and (s.rec_spread is None or s._on_device(e)):
             j = e.misfit_weighted(s.d_obs, s.weights, objective.taps)  # ... filtered and weighted there as well
             e.adjoint(None)
+            return j
+        if device_l2 and matched and hasattr(e, "misfit_matched") and (s.rec_spread is None or s._on_device(e)):
+            # ... and so is the matching filter: estimated, applied and eliminated there; the shot's f* is kept
+            j, objective.filters[i] = e.misfit_matched(s.d_obs, objective.L, objective.mu_of(i), s.weights, objective.taps)
+            e.adjoint(None)
+            return j
+        if matched:
+            j, r = objective(d, s.d_obs, s.weights, shot=i)
+            s.adjoint(e, r)
             return j
         j, r = objective(d, s.d_obs, s.weights) if weighted else objective(d, s.d_obs)
         s.adjoint(e, r)

@@ -206,6 +206,38 @@ int fwi_misfit_weighted(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const v
 int fwi_residual_weight(fwi_ctx *ctx, const void *weights /* (nt, ntr) or NULL */, const double *taps /* R + 1, or NULL */,
                         int32_t R);
 
+/* Matching-filter (source-independent) misfit on the device: a short two-sided filter per shot takes up the unknown
+ * source signature and is eliminated by variable projection.  With s = d_syn of the last forward and d = d_obs, both
+ * (nt, ntr) as above, B and M as above, f = (f_-L .. f_L), K = 2 L + 1 coefficients stored f[k + L], acting along time
+ * on the zero-extended trace:
+ *     s' = B s,   d' = B d                                  (each rounded to the context's dtype once)
+ *     (C_f x)[n, j]   = sum_{k = -L .. L} f_k x[n - k, j]      terms with n - k outside [0, nt) omitted
+ *     (C_f^T y)[m, j] = sum_{k = -L .. L} f_k y[m + k, j]      terms with m + k outside [0, nt) omitted
+ *     e = M . (C_f s' - d'),     Phi(f; s) = 1/2 sum e^2 + mu/2 |f|^2          (mu >= 0 absolute, the caller's)
+ *     G[k, l] = sum_{n, j} M^2[n, j] s'[n - k, j] s'[n - l, j],     b[k] = sum_{n, j} M^2[n, j] s'[n - k, j] d'[n, j]
+ *     f* = (G + mu I)^-1 b,     J(s) = Phi(f*; s),     r = dJ/ds = B C_f*^T (M . e)     (dPhi/df = 0 at f*)
+ * G is not Toeplitz (the weights, the truncation at both ends of the trace) and is formed as defined.  mu does not
+ * depend on s: one that did would add a term to the gradient.  f_in == NULL: f = f* is estimated (normal equations on
+ * the device, fwi_match_solve on the host); otherwise f = f_in is used as given, and r is then dPhi/ds at that f.
+ * *J_out = Phi(f; s); f_out, if not NULL, receives the K coefficients used; normal_out, if not NULL, receives G (K K
+ * doubles, row-major, full, exactly symmetric, without mu) and then b (K doubles).  r stays on the device as the
+ * residual of the next fwi_adjoint(ctx, NULL, ...).  L = 0, f_in = {1}, mu = 0 is fwi_misfit_weighted's e and r (bit for
+ * bit without taps).  All sums are fp64 in a fixed order, without atomics: equal inputs give equal bits.  L may exceed
+ * nt - 1: the shifts beyond meet no sample, and mu > 0 carries them.  State rules, off-grid receivers and work buffers as
+ * fwi_misfit_weighted.  FWI_EINVAL: a null J_out, a null d_obs with nrec > 0, the tap errors of fwi_misfit_weighted,
+ * L < 0, L > FWI_MATCH_LMAX, mu < 0 or not finite, a non-finite f_in entry, and a G + mu I that is not positive definite
+ * (raise mu): then no residual is left on the device, the forward's synthetics remain and the call may be repeated.
+ * No reference counterpart. */
+#define FWI_MATCH_LMAX 64
+int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                       const double *taps /* R + 1, or NULL */, int32_t R, int32_t L, double mu,
+                       const double *f_in /* 2L+1, or NULL: estimate */, double *f_out /* 2L+1, or NULL */,
+                       double *normal_out /* K*K of G then K of b, or NULL */, double *J_out);
+/* f_out := (G + mu I)^-1 b for a symmetric K x K matrix G (row-major; the upper triangle is read): fp64 Cholesky, then
+ * forward and back substitution.  Pure host code: no context, no HIP call.  FWI_EINVAL: a null argument, K < 1,
+ * K > 2 FWI_MATCH_LMAX + 1, mu < 0 or not finite, a pivot that is not positive and finite. */
+int fwi_match_solve(const double *G /* K*K row-major */, const double *b, int32_t K, double mu, double *f_out);
+
 /* gradient(): copy out the accumulated gradient, model-shaped, as dJ/dc
  * (FWI_WRT_VELOCITY) or dJ/d(1/c^2) (FWI_WRT_SLOWNESS2).
  * [SURVEY s.8(a-1) row gradient] */

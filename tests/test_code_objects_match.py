@@ -1,0 +1,25 @@
+"""The code object of the matching-filter kernels (fwi_match.o): no scratch, no spilled registers, and the kernels that
+are built: the normal equations for fp32 and fp64 and the sum of their slices, the filter's convolution and correlation
+for fp32 and fp64 and the one fixed-order sum of squares."""
+import os
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import code_objects as co  # noqa: E402
+
+
+def test_match_kernels_use_no_scratch_and_spill_nothing():
+    path = os.path.join(co.CSRC, "fwi_match.o")
+    if not co.tools_present() or not os.path.exists(path):
+        pytest.skip("ROCm LLVM tools or the built objects are missing (run `make -C full_waveform_inversion_amd/csrc`)")
+    ks = co.kernels([path])
+    names = [k["name"] for k in ks]
+    count = lambda s: sum(s in n for n in names)  # noqa: E731
+    assert len(ks) == 8 and count("match_normal<") == 2 and count("match_apply<") == 4, names
+    assert count("match_reduce") == 1 and count("match_sum") == 1, names
+    bad = [k["name"] for k in ks if k.get("private_segment_fixed_size", 0) > 0 or k.get("vgpr_spill_count", 0) > 0
+           or k.get("sgpr_spill_count", 0) > 0]
+    assert not bad, bad

@@ -61,6 +61,13 @@ def main():
     ap.add_argument("--mute-direct", type=float, default=None, metavar="V_FAST",
                     help="data weights that mute every trace up to offset / V_FAST + 2 / f0, with a taper of half a period "
                          "(datafit.offset_time_mute)")
+    ap.add_argument("--match-source", type=int, default=None, metavar="L",
+                    help="matching-filter (source-independent) misfit: per shot a two-sided filter of 2 L + 1 coefficients "
+                         "between synthetics and data is estimated and eliminated (datafit.MatchedL2, on the device); "
+                         "composes with --bands and --mute-direct")
+    ap.add_argument("--match-mu-percent", type=float, default=0.1, metavar="P",
+                    help="damping of the filter's normal equations per shot: P / 100 of the energy of the shot's (weighted) "
+                         "observed data (datafit.prewhitening), computed once and held through the run")
     a = ap.parse_args()
     bands = [float(f) for f in a.bands.split(",")] if a.bands else None
     if bands and (a.iters < 1 or a.checkpoint or a.resume):
@@ -69,6 +76,10 @@ def main():
                   or a.regularize is not None or a.host_lbfgs):
         ap.error("--bands runs the plain device L-BFGS per band: it does not combine with --precondition, --smooth, "
                  "--mute-sources, --regularize or --host-lbfgs")
+    if a.match_source is not None and not 0 <= a.match_source <= datafit.L_MAX:
+        ap.error("--match-source L must lie in [0, %d]" % datafit.L_MAX)
+    if not (a.match_mu_percent >= 0.0 and np.isfinite(a.match_mu_percent)):
+        ap.error("--match-mu-percent P must be finite and >= 0")
     if (a.regularize is None) != (a.reg_weight is None):
         ap.error("--regularize and --reg-weight go together")
     if a.regularize is None and (a.reg_eps is not None or a.reg_prior is not None):
@@ -111,7 +122,25 @@ def main():
             if s.d_obs is not None:
                 s.weights = datafit.offset_time_mute(s, w.h, w.dt, a.mute_direct, 2.0 / w.f0, int(0.5 / (w.f0 * w.dt)))
     # the misfit of the stage that is running: least squares, or its band-limited / weighted form
-    obj = [datafit.WeightedL2() if a.mute_direct is not None else None]
+    match_mu = None
+    if a.match_source is not None:  # data-only numbers, fixed for the run (indexed like `shots`; 0 where a rank has no data)
+        match_mu = [datafit.prewhitening(s.d_obs, s.weights, a.match_mu_percent) if s.d_obs is not None else 0.0
+                    for s in shots]
+
+    def objective_of(taps):
+        """the misfit of one stage: a fresh object per band (a MatchedL2 keeps the shots' filters of ITS band)"""
+        if a.match_source is not None:
+            return datafit.MatchedL2(a.match_source, match_mu, taps)
+        return datafit.WeightedL2(taps) if (taps is not None or a.mute_direct is not None) else None
+
+    def filters_line(o, band=None):
+        """per shot of this rank, the share of the filter's energy outside lag 0: 0 = a pure scaling of the wavelet"""
+        if not isinstance(o, datafit.MatchedL2):
+            return
+        out = {i: float(1.0 - f[o.L] ** 2 / max(float(np.sum(f * f)), 1e-300)) for i, f in sorted(o.filters.items())}
+        print(json.dumps({"rank": rank, "band_hz": band, "match_filter_energy_outside_lag0": out}), flush=True)
+
+    obj = [objective_of(None)]
     t0 = time.perf_counter()
     evals = [0]
 
@@ -142,17 +171,17 @@ def main():
     h0_sigma = a.smooth if a.smooth is not None else 0.0
     mute = sh.source_mute(w.shape, shots, a.mute_sources) if a.mute_sources is not None else None
     if bands:
-        def run_band(x, taps):  # the device L-BFGS, started afresh: curvature pairs of another band are invalid
-            obj[0] = datafit.WeightedL2(taps)
+        def run_band(x, f_hz):  # the device L-BFGS, started afresh: curvature pairs of another band are invalid
+            obj[0] = objective_of(datafit.lowpass_taps(w.dt, f_hz, a.band_halfwidth))
 
             def fg_band(xs, gs):
                 evals[0] += 1
                 return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex, objective=obj[0])
             x, _, lg = lbfgs_device(e, fg_band, x, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
                                     bounds=bounds)
+            filters_line(obj[0], f_hz)
             return x, lg
-        _, logs = datafit.frequency_continuation(run_band, m0, bands,
-                                                 taps_of=lambda f: datafit.lowpass_taps(w.dt, f, a.band_halfwidth))
+        _, logs = datafit.frequency_continuation(run_band, m0, bands)  # (the band itself is handed on: no taps_of)
         log = [{"band_hz": f, "log": lg} for f, lg in zip(bands, logs)]
     elif a.iters > 0 and not a.host_lbfgs:
         pslot = lbfgs_device_slots(5) if eps is not None else None
@@ -196,6 +225,8 @@ def main():
         J, g = fg1(m0)
         log = [{"iter": 0, "f": J, "gnorm": float(np.sqrt(e.dot(g, g)))}]
     el = time.perf_counter() - t0
+    if not bands:
+        filters_line(obj[0])
     if rank == 0:
         upd = 2 * evals[0] * len(shots) * w.updates_per_shot  # forward + adjoint sweeps
         print(json.dumps({"config": w.name, "shape": list(w.shape), "nt": w.nt, "shots": len(shots),
@@ -205,7 +236,9 @@ def main():
                           "precondition_eps": eps, "smooth_sigma": a.smooth,
                           "mute_sources_radius": a.mute_sources, "regularize": a.regularize,
                           "reg_weight": a.reg_weight, "reg_eps": reg_eps, "reg_prior": a.reg_prior, "bands_hz": bands,
-                          "band_halfwidth": a.band_halfwidth if bands else None, "mute_direct": a.mute_direct, "log": log}))
+                          "band_halfwidth": a.band_halfwidth if bands else None, "mute_direct": a.mute_direct,
+                          "match_source": a.match_source,
+                          "match_mu_percent": a.match_mu_percent if a.match_source is not None else None, "log": log}))
     pool.close()
     if rdzv is not None:
         rdzv.barrier()
