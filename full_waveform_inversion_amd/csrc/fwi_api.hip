@@ -23,6 +23,7 @@
 #include "../../include/fwi.h"
 #include "fwi_born.h"
 #include "fwi_data.h"
+#include "fwi_envelope.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
 #include "fwi_match.h"
@@ -192,6 +193,10 @@ struct fwi_ctx {
     // the slices of the normal equations, G and b, the filter
     void *match_s = nullptr, *match_d = nullptr, *match_part = nullptr, *match_norm = nullptr, *match_f = nullptr;
     size_t cap_match_s = 0, cap_match_d = 0, cap_match_part = 0, cap_match_norm = 0, cap_match_f = 0;
+    // fwi_misfit_envelope (fwi_envelope.hip), allocated by its first call: the filtered synthetics s' and data d' (with
+    // taps; s' later holds q), g2 (g1 lies in data_tmp), the Hilbert taps
+    void *env_s = nullptr, *env_d = nullptr, *env_g2 = nullptr, *env_h = nullptr;
+    size_t cap_env_s = 0, cap_env_d = 0, cap_env_g2 = 0, cap_env_h = 0;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
     enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
     int resid_pts_in = RESID_PTS_NONE;
@@ -1930,6 +1935,73 @@ struct Impl {
         return FWI_OK;
     }
 
+    // s' = B d_syn, d' = B d_obs, e = M . (E(s')^p - E(d')^p), J = 1/2 sum e^2, r = B (g1 - H g2) where the adjoint sweep
+    // reads its amplitudes (fwi_envelope.h)
+    static int misfit_envelope(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
+                               const double *hilbert, int Q, int power, double eps, double *J_out) {
+        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
+        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
+        const size_t n = (size_t)nt * ntr;
+        double ss = 0.0;
+        if (n && ctx->nrec) {
+            // off-grid receivers: everything per POINT (against the gathered synthetics kept by the forward), r then
+            // scattered onto the nodes, as misfit_l2 does
+            void *resid = ctx->amp;
+            int rc, Re;
+            if (sp.npts) {
+                if ((rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T)))) return rc;
+                resid = ctx->pts_a;
+            }
+            if ((rc = upload_series(ctx, resid, d_obs, n * sizeof(T)))) return rc;
+            const T *w;
+            const double *b;
+            if ((rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
+            if ((rc = ensure(ctx, &ctx->data_part, &ctx->cap_data_part,
+                             (size_t)(std::max(fir_blocks(nt, ntr), env_blocks(nt, ntr)) + 1) * sizeof(double))))
+                return rc;
+            if ((rc = ensure(ctx, &ctx->env_g2, &ctx->cap_env_g2, n * sizeof(T)))) return rc;
+            // the taps that meet samples; are the even ones all zero (a Hilbert transformer's are)?
+            const int Qe = std::max(std::min(Q, nt - 1), 1);
+            bool odd_only = true;
+            for (int k = 2; k <= Qe; k += 2) odd_only = odd_only && hilbert[k - 1] == 0.0;
+            if ((rc = ensure(ctx, &ctx->env_h, &ctx->cap_env_h, (size_t)Qe * sizeof(double)))) return rc;
+            // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
+            HIPCHK(ctx, hipMemcpyAsync(ctx->env_h, hilbert, (size_t)Qe * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            const double *hd = (const double *)ctx->env_h;
+            const T *s1 = (const T *)(sp.npts ? ctx->pts_d : ctx->series), *d1 = (const T *)resid;
+            if (b) {  // each rounded to T once
+                if ((rc = ensure(ctx, &ctx->env_s, &ctx->cap_env_s, n * sizeof(T)))) return rc;
+                if ((rc = ensure(ctx, &ctx->env_d, &ctx->cap_env_d, n * sizeof(T)))) return rc;
+                HIPCHK(ctx, launch_fir_time<T>((T *)ctx->env_s, s1, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr, false,
+                                               ctx->stream));
+                HIPCHK(ctx, launch_fir_time<T>((T *)ctx->env_d, d1, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr, false,
+                                               ctx->stream));
+                s1 = (const T *)ctx->env_s;
+                d1 = (const T *)ctx->env_d;
+            }
+            double *part = (double *)ctx->data_part;
+            T *g1 = (T *)ctx->data_tmp, *g2 = (T *)ctx->env_g2;
+            HIPCHK(ctx, launch_env_forward<T>(g1, g2, s1, d1, w, hd, Qe, odd_only, power, eps, nt, ntr, part, ctx->stream));
+            // s' and d' are used up: without taps q is the residual, with taps it takes the place of s' and B writes r
+            // over the uploaded d_obs
+            T *q = b ? (T *)ctx->env_s : (T *)resid;
+            HIPCHK(ctx, launch_env_adjoint<T>(q, g1, g2, hd, Qe, odd_only, nt, ntr, ctx->stream));
+            if (b)
+                HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)q, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr,
+                                               false, ctx->stream));
+            if (sp.npts)
+                HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
+                                                     (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(&ss, part + env_blocks(nt, ntr), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        *J_out = 0.5 * ss;
+        ctx->have_dev_residual = true;
+        ctx->resid_pts_in = (n && ctx->nrec && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
+        return FWI_OK;
+    }
+
     // device residual := B M^2 B residual: per node, or per off-grid point and scattered onto the nodes again
     static int residual_weight(fwi_ctx *ctx, const T *weights, const double *taps, int R) {
         const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
@@ -2436,7 +2508,8 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"sum_part", ctx->sum_part},
                   {"data_tmp", ctx->data_tmp}, {"data_w", ctx->data_w}, {"data_taps", ctx->data_taps},
                   {"data_part", ctx->data_part}, {"match_s", ctx->match_s}, {"match_d", ctx->match_d},
-                  {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f}};
+                  {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f},
+                  {"env_s", ctx->env_s}, {"env_d", ctx->env_d}, {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2621,6 +2694,31 @@ int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs, const void *weights, con
                                                 f_out, normal_out, J_out),
                     Impl<double>::misfit_matched(ctx, (const double *)d_obs, (const double *)weights, taps, R, L, mu, f_in,
                                                  f_out, normal_out, J_out));
+}
+
+int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
+                        const double *hilbert, int32_t Q, int32_t power, double eps, double *J_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "fwi_misfit_envelope: no forward run whose data to compare");
+    if (!J_out || (ctx->nrec && !d_obs) || !hilbert) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: null argument");
+    if (int rc = data_args(ctx, "fwi_misfit_envelope", taps, R)) return rc;
+    if (Q < 1 || Q > FIR_RMAX) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: Q=%d outside [1, %d]", (int)Q, FIR_RMAX);
+    for (int k = 0; k < Q; ++k)
+        if (!std::isfinite(hilbert[k])) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: hilbert[%d] is not finite", k);
+    if (power != 1 && power != 2) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: power=%d is neither 1 nor 2", (int)power);
+    if (!(eps >= 0.0) || !std::isfinite(eps))
+        return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: eps=%g must be finite and >= 0", eps);
+    if (power == 1 && eps == 0.0)
+        return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: power 1 needs eps > 0 (the envelope is not differentiable at 0)");
+    if (!ctx->have_syn)
+        return ctx->fail(FWI_ESTATE, "fwi_misfit_envelope: the synthetics of the last forward are gone (an fwi_adjoint "
+                                     "or fwi_born has run since): call it between fwi_forward and fwi_adjoint");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx,
+                    Impl<float>::misfit_envelope(ctx, (const float *)d_obs, (const float *)weights, taps, R, hilbert, Q,
+                                                 power, eps, J_out),
+                    Impl<double>::misfit_envelope(ctx, (const double *)d_obs, (const double *)weights, taps, R, hilbert, Q,
+                                                  power, eps, J_out));
 }
 
 int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {

@@ -32,6 +32,25 @@ it up and is eliminated by variable projection.  With ``s = d_syn``, ``d = d_obs
 ``G`` is not Toeplitz (the weights, the truncation at both ends of the trace).  ``mu`` is independent of ``s`` on purpose:
 one that depended on ``s`` would add a term to the gradient (:func:`prewhitening` is a data-only choice).
 ``L = 0, f = (1), mu = 0`` with a given filter is :class:`WeightedL2`'s ``e`` and ``r``.
+
+Envelope misfit, :class:`EnvelopeL2` (``Engine.misfit_envelope``, ``fwi_misfit_envelope``, ``csrc/fwi_envelope.hip``):
+when the starting model puts an arrival more than half a period off, every least-squares misfit above pulls the wrong
+way (cycle skipping), and band-limiting only helps where the data have energy at low frequencies.  The envelope of a
+trace carries its low-frequency content even when its spectrum does not (Bozdag et al. 2011; Wu et al. 2014).  The
+Hilbert transformer ``H`` is an FIR filter with an antisymmetric impulse response, one-sided taps ``h_1 .. h_Q``
+(:func:`hilbert_taps`), on the zero-extended trace, so that ``H^T = -H`` exactly; the power ``p`` is 1 or 2.  With
+``s = d_syn``, ``d = d_obs``, ``B`` and ``M`` as above:
+
+    s' = B s,   d' = B d
+    (H x)[n, j] = sum_{k=1..Q} h_k (x[n - k, j] - x[n + k, j])      terms outside [0, nt) omitted
+    E(x) = sqrt(x^2 + (H x)^2 + eps^2)                               eps absolute, independent of s
+    e = M . (E(s')^p - E(d')^p)        J = 1/2 sum e^2
+    c = p . M . e . E(s')^(p-2)        g1 = c . s'      g2 = c . (H s')
+    r = dJ/ds = B (g1 - H g2)
+
+``eps > 0`` is required for ``p = 1`` (``E`` is not differentiable at 0), ``eps >= 0`` allowed for ``p = 2``.  Like
+``mu`` it must not follow ``s``: :func:`envelope_floor` is a data-only choice.  An envelope has no linear Gauss-Newton
+weight: :class:`EnvelopeL2` is not a :class:`WeightedL2`.
 """
 from __future__ import annotations
 
@@ -271,6 +290,138 @@ class MatchedL2:
         if shot is not None:
             self.filters[shot] = f
         return self.apply(d_syn, d_obs, f, weights, mu=mu)
+
+
+def hilbert_taps(Q):
+    """One-sided taps ``h_1 .. h_Q`` of a Hann-windowed FIR Hilbert transformer: ``2 / (pi k)`` for odd ``k``, 0 for even
+    ``k``, times ``(1 + cos(pi k / (Q + 1))) / 2``.  Its response ``2 sum h_k sin(w k)`` is within 2e-3 of 1 from
+    ``w = 4 pi / (Q + 1)`` to ``pi - 4 pi / (Q + 1)`` (:func:`hilbert_halfwidth`)."""
+    if int(Q) != Q or not 1 <= int(Q) <= R_MAX:
+        raise ValueError("Q must be an integer in [1, %d]" % R_MAX)
+    k = np.arange(1, int(Q) + 1, dtype=np.float64)
+    h = np.where(np.arange(1, int(Q) + 1) % 2 == 1, 2.0 / (np.pi * k), 0.0)
+    return h * 0.5 * (1.0 + np.cos(np.pi * k / (int(Q) + 1)))
+
+
+def hilbert_halfwidth(dt, f_lo):
+    """``Q = ceil(2 / (f_lo dt)) - 1``: the half-width at which :func:`hilbert_taps` is good from ``f_lo`` (Hz) to
+    Nyquist minus ``f_lo`` at the sampling interval ``dt``.  Raises above ``R_MAX``."""
+    if not (float(dt) > 0.0 and np.isfinite(dt)):
+        raise ValueError("dt must be > 0")
+    if not (0.0 < float(f_lo) < 0.5 / float(dt)):
+        raise ValueError("f_lo = %g outside (0, Nyquist = %g)" % (f_lo, 0.5 / float(dt)))
+    Q = max(int(math.ceil(round(2.0 / (float(f_lo) * float(dt)), 9))) - 1, 1)  # (2 / (5 * 1e-3) is not 400 in fp64)
+    if Q > R_MAX:
+        raise ValueError("f_lo = %g at dt = %g needs Q = %d taps, above %d: raise f_lo" % (f_lo, dt, Q, R_MAX))
+    return Q
+
+
+def _checked_hilbert(h):
+    h = np.ascontiguousarray(np.asarray(h, np.float64))
+    if h.ndim != 1 or not 1 <= h.size <= R_MAX or not np.all(np.isfinite(h)):
+        raise ValueError("hilbert must be a finite 1-D array h_1 .. h_Q, Q in [1, %d]" % R_MAX)
+    return h
+
+
+def hilbert_matrix(h, nt):
+    """``H`` as the dense antisymmetric ``nt x nt`` Toeplitz matrix of the zero-extended filter: ``H[n, n - k] = h_k``,
+    ``H[n, n + k] = -h_k``."""
+    col = np.zeros(nt)
+    m = min(len(h), nt - 1)
+    col[1:m + 1] = h[:m]
+    i = np.arange(nt)
+    d = i[:, None] - i[None, :]
+    return np.sign(d) * col[np.abs(d)]
+
+
+def hilbert_time(x, h):
+    """``H x`` along axis 0 in fp64."""
+    x = np.asarray(x, np.float64)
+    h = np.asarray(h, np.float64)
+    nt = x.shape[0]
+    if min(len(h), nt - 1) > _DENSE_MIN_R and nt <= _DENSE_MAX_NT and x.ndim == 2:
+        return hilbert_matrix(h, nt) @ x
+    out = np.zeros_like(x)
+    for k in range(1, min(len(h), nt - 1) + 1):
+        if h[k - 1] != 0.0:
+            out[k:] += h[k - 1] * x[:nt - k]
+            out[:nt - k] -= h[k - 1] * x[k:]
+    return out
+
+
+def envelope_floor(d_obs, percent=1.0):
+    """``percent / 100 * max |d_obs|``: a floor ``eps`` for :class:`EnvelopeL2` that depends on the data only -- like
+    :func:`prewhitening`, compute it once per shot and hold it through an inversion."""
+    if not (float(percent) >= 0.0 and np.isfinite(percent)):
+        raise ValueError("percent must be finite and >= 0")
+    d = np.asarray(d_obs, np.float64)
+    return float(percent) / 100.0 * (float(np.max(np.abs(d))) if d.size else 0.0)
+
+
+class EnvelopeL2:
+    """The envelope misfit of the module's definition in fp64 NumPy, ``objective(d_syn, d_obs, weights=None) -> (J, r)``,
+    and the ``objective=`` that ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_envelope`` replaces
+    it by the device path).
+
+    ``hilbert``: the one-sided taps ``h_1 .. h_Q`` (:func:`hilbert_taps`).  ``power``: 1 or 2.  ``eps``: the absolute
+    floor under the envelope, ``> 0`` for ``power=1``; None: :func:`envelope_floor` of each call's ``d_obs`` at
+    ``floor_percent``, a data-only number.  ``taps``: the one-sided ``b_0 .. b_R`` of ``B``, or None.  ``dtype``: round
+    ``B s``, ``B d``, ``g1``, ``g2`` and ``g1 - H g2`` to it once each, as a device context of that dtype does (None:
+    keep fp64).
+
+    Not a :class:`WeightedL2`: an envelope has no linear Gauss-Newton weight, and ``gauss_newton_hvp`` refuses it."""
+
+    def __init__(self, hilbert, power=1, eps=None, taps=None, dtype=None, floor_percent=1.0):
+        self.hilbert = _checked_hilbert(hilbert)
+        if power not in (1, 2):
+            raise ValueError("power must be 1 or 2")
+        self.power = int(power)
+        if eps is not None and not (float(eps) >= 0.0 and np.isfinite(eps) and (float(eps) > 0.0 or self.power == 2)):
+            raise ValueError("eps must be finite and >= 0, and > 0 for power 1")
+        self.eps = None if eps is None else float(eps)
+        self.floor_percent = float(floor_percent)
+        self.taps = _checked_taps(taps)
+        self.dtype = None if dtype is None else np.dtype(dtype)
+
+    def eps_of(self, d_obs):
+        """the floor of a shot: ``eps``, or :func:`envelope_floor` of its observed data"""
+        return self.eps if self.eps is not None else envelope_floor(d_obs, self.floor_percent)
+
+    def _round(self, x):
+        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+
+    def filter(self, x):
+        """``B x`` (rounded to ``dtype`` once)"""
+        return self._round(fir_time(x, self.taps))
+
+    def envelope2(self, x1, eps):
+        """``(E(x')^2, H x')`` of an already filtered gather"""
+        hx = hilbert_time(x1, self.hilbert)
+        return x1 * x1 + (hx * hx + eps * eps), hx
+
+    def __call__(self, d_syn, d_obs, weights=None):
+        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
+        if s.ndim != 2 or s.shape != d.shape:
+            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
+        M = WeightedL2._weights(weights, s.shape)
+        eps = self.eps_of(d)
+        if self.power == 1 and not eps > 0.0:
+            raise ValueError("power 1 needs eps > 0")
+        s1, d1 = self.filter(s), self.filter(d)
+        es2, hs = self.envelope2(s1, eps)
+        ed2, _ = self.envelope2(d1, eps)
+        if self.power == 1:
+            es = np.sqrt(es2)
+            e = es - np.sqrt(ed2)
+        else:
+            e = es2 - ed2
+        if M is not None:
+            e = M * e
+        c = e if M is None else M * e
+        c = c / es if self.power == 1 else 2.0 * c
+        g1, g2 = self._round(c * s1), self._round(c * hs)
+        q = self._round(g1 - hilbert_time(g2, self.hilbert))
+        return 0.5 * float(np.sum(e * e)), (q if self.taps is None else fir_time(q, self.taps))
 
 
 def matched_wavelet(wavelet, f):

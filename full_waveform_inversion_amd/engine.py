@@ -284,6 +284,29 @@ class Engine:
             return J.value, f_out, nrm[:K * K].reshape(K, K).copy(), nrm[K * K:].copy()
         return J.value, f_out
 
+    def misfit_envelope(self, d_obs, hilbert, power=1, eps=None, weights=None, taps=None):
+        """Envelope misfit of the last forward's seismograms: with ``s' = B d_syn``, ``d' = B d_obs``, ``H`` the
+        antisymmetric Hilbert FIR filter along time with the one-sided taps ``hilbert = h_1 .. h_Q``
+        (``datafit.hilbert_taps``) and ``E(x) = sqrt(x^2 + (H x)^2 + eps^2)``, ``J = 1/2 ||M . (E(s')^p - E(d')^p)||^2``,
+        ``p = power`` in {1, 2}.  ``eps >= 0`` is absolute and must not depend on the synthetics (``> 0`` for ``p = 1``);
+        None: ``datafit.envelope_floor(d_obs)``, 1 % of the largest observed amplitude.  ``weights`` and ``taps`` as in
+        :meth:`misfit_weighted`.  The adjoint source ``dJ/dd_syn`` is formed on the device and kept there for
+        ``adjoint(None)``.  Returns J (``fwi_misfit_envelope``; the NumPy twin is :class:`datafit.EnvelopeL2`)."""
+        if eps is None:
+            from .datafit import envelope_floor
+            eps = envelope_floor(d_obs)
+        d_obs = self._host(d_obs, (self._nt, self._nrec))
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        h = np.ascontiguousarray(hilbert, dtype=np.float64)
+        if h.ndim != 1 or h.size < 1:
+            raise ValueError("hilbert must be the 1-D array h_1 .. h_Q")
+        if int(power) != power:
+            raise ValueError("power must be 1 or 2")
+        J = C.c_double(0.0)
+        self._chk(self._lib.fwi_misfit_envelope(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R,
+                                                h.ctypes.data_as(C.c_void_p), h.size, int(power), float(eps), C.byref(J)))
+        return J.value
+
     def residual_weight(self, weights=None, taps=None):
         """The residual on the device (what ``born`` or a misfit call left for ``adjoint(None)``) := ``B M^2 B`` residual,
         the Gauss-Newton weight of :meth:`misfit_weighted` (``fwi_residual_weight``)."""

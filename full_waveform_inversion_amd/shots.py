@@ -25,7 +25,7 @@ class Shot:
     src_spread: object = None
     rec_spread: object = None
     point_wavelet: np.ndarray | None = None  # (nt[, nsrc points]): the wavelets before spreading
-    weights: np.ndarray | None = None  # (nt, nrec) data weights >= 0 of a datafit.WeightedL2 / MatchedL2 objective (None: 1)
+    weights: np.ndarray | None = None  # (nt, nrec) data weights >= 0 of a datafit.WeightedL2 / MatchedL2 / EnvelopeL2 objective (None: 1)
 
     @classmethod
     def at_coordinates(cls, src_xyz, wavelet, rec_xyz, shape, d_obs=None):
@@ -304,6 +304,10 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     ``shots`` (``datafit.prewhitening`` of each shot's data).  Either branch leaves shot ``i``'s filter in
     ``objective.filters[i]``.
 
+    A :class:`datafit.EnvelopeL2` objective (envelope misfit, against cycle skipping) is handed ``Shot.weights`` too; an
+    engine that has ``misfit_envelope`` forms envelopes, misfit and adjoint source on the device, otherwise the NumPy
+    twin does on the host.  Either branch uses ``objective.eps_of(d_obs)`` as the shot's floor.
+
     ``device_l2`` (least squares only): form the residual and J on the device (``fwi_misfit_l2``) -- in the
     engine's dtype, i.e. with an fp32 engine ``d_obs`` is rounded to fp32 before the subtraction, which puts
     ~6e-8 |d| / |r| of relative noise on J and on the residual (visible to a line search only once |r| / |d|
@@ -329,10 +333,11 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
 def _sweep_shots(engine, shots, ex, objective, device_l2=True):
     """forward + adjoint of this rank's shots; returns the misfit, gradients summed into the
     (primary) engine's accumulator."""
-    from .datafit import MatchedL2, WeightedL2
+    from .datafit import EnvelopeL2, MatchedL2, WeightedL2
     from .objectives import l2
     weighted = isinstance(objective, WeightedL2)
     matched = isinstance(objective, MatchedL2)
+    enveloped = isinstance(objective, EnvelopeL2)
 
     def one(e, i):
         s = shots[i]
@@ -357,7 +362,13 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True):
             j, r = objective(d, s.d_obs, s.weights, shot=i)
             s.adjoint(e, r)
             return j
-        j, r = objective(d, s.d_obs, s.weights) if weighted else objective(d, s.d_obs)
+        if device_l2 and enveloped and hasattr(e, "misfit_envelope") and (s.rec_spread is None or s._on_device(e)):
+            # ... and so are the envelopes, their misfit and its adjoint source
+            j = e.misfit_envelope(s.d_obs, objective.hilbert, objective.power, objective.eps_of(s.d_obs), s.weights,
+                                  objective.taps)
+            e.adjoint(None)
+            return j
+        j, r = objective(d, s.d_obs, s.weights) if (weighted or enveloped) else objective(d, s.d_obs)
         s.adjoint(e, r)
         return j
 

@@ -238,6 +238,26 @@ int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const vo
  * K > 2 FWI_MATCH_LMAX + 1, mu < 0 or not finite, a pivot that is not positive and finite. */
 int fwi_match_solve(const double *G /* K*K row-major */, const double *b, int32_t K, double mu, double *f_out);
 
+/* Envelope misfit on the device: the envelope of a trace carries its low-frequency content even where its spectrum does
+ * not, which widens the basin of attraction against cycle skipping.  With s = d_syn of the last forward and d = d_obs,
+ * both (nt, ntr) as above, B and M as above, H the antisymmetric Hilbert FIR filter with one-sided taps h_1 .. h_Q,
+ * stored hilbert[k - 1], acting along time on the zero-extended trace (H^T = -H exactly), power p in {1, 2}:
+ *     s' = B s,   d' = B d                                       (each rounded to the context's dtype once, with taps)
+ *     (H x)[n, j] = sum_{k = 1 .. Q} h_k (x[n - k, j] - x[n + k, j])     terms outside [0, nt) omitted
+ *     E(x) = sqrt(x^2 + (H x)^2 + eps^2)                         eps absolute: it must not depend on s
+ *     e = M . (E(s')^p - E(d')^p),     J = 1/2 sum e^2
+ *     c = p . M . e . E(s')^(p - 2),   g1 = c . s',   g2 = c . (H s')      (each rounded to the context's dtype once)
+ *     r = dJ/ds = B (g1 - H g2)                                  (g1 - H g2 rounded once; without taps it is r)
+ * *J_out = J; r stays on the device as the residual of the next fwi_adjoint(ctx, NULL, ...).  Q may exceed nt - 1:
+ * min(Q, nt - 1) taps are used.  Everything between the loads and the roundings named above is fp64; all sums run in a
+ * fixed order, without atomics: equal inputs give equal bits.  State rules, off-grid receivers and work buffers as
+ * fwi_misfit_weighted.  FWI_EINVAL: a null J_out, a null d_obs with nrec > 0, a null hilbert, the tap errors of
+ * fwi_misfit_weighted, Q < 1, Q > 4096, a non-finite hilbert entry, power other than 1 or 2, eps < 0 or not finite,
+ * eps == 0 with power 1 (E is not differentiable at 0).  No reference counterpart. */
+int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                        const double *taps /* R + 1, or NULL */, int32_t R, const double *hilbert /* Q: h_1 .. h_Q */,
+                        int32_t Q, int32_t power, double eps, double *J_out);
+
 /* gradient(): copy out the accumulated gradient, model-shaped, as dJ/dc
  * (FWI_WRT_VELOCITY) or dJ/d(1/c^2) (FWI_WRT_SLOWNESS2).
  * [SURVEY s.8(a-1) row gradient] */

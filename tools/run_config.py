@@ -68,6 +68,16 @@ def main():
     ap.add_argument("--match-mu-percent", type=float, default=0.1, metavar="P",
                     help="damping of the filter's normal equations per shot: P / 100 of the energy of the shot's (weighted) "
                          "observed data (datafit.prewhitening), computed once and held through the run")
+    ap.add_argument("--envelope", type=int, nargs="?", const=1, default=None, metavar="P", choices=(1, 2),
+                    help="envelope misfit against cycle skipping: 1/2 |M . (E(s)^P - E(d)^P)|^2 with E the envelope from an "
+                         "FIR Hilbert transformer (datafit.EnvelopeL2, on the device), P = 1 (default) or 2; needs "
+                         "--hilbert-fmin; composes with --bands and --mute-direct, not with --match-source")
+    ap.add_argument("--hilbert-fmin", type=float, default=None, metavar="F",
+                    help="lowest frequency (Hz) at which the Hilbert transformer of --envelope is accurate: sets its "
+                         "half-width Q = datafit.hilbert_halfwidth(dt, F)")
+    ap.add_argument("--envelope-floor-percent", type=float, default=1.0, metavar="X",
+                    help="floor under the envelopes per shot: X / 100 of the largest amplitude of the shot's observed data "
+                         "(datafit.envelope_floor), computed once and held through the run")
     a = ap.parse_args()
     bands = [float(f) for f in a.bands.split(",")] if a.bands else None
     if bands and (a.iters < 1 or a.checkpoint or a.resume):
@@ -80,6 +90,13 @@ def main():
         ap.error("--match-source L must lie in [0, %d]" % datafit.L_MAX)
     if not (a.match_mu_percent >= 0.0 and np.isfinite(a.match_mu_percent)):
         ap.error("--match-mu-percent P must be finite and >= 0")
+    if a.envelope is not None and a.match_source is not None:
+        ap.error("--envelope and --match-source are two misfits: choose one")
+    if (a.envelope is None) != (a.hilbert_fmin is None):
+        ap.error("--envelope and --hilbert-fmin go together")
+    if not (a.envelope_floor_percent >= 0.0 and np.isfinite(a.envelope_floor_percent)) or (
+            a.envelope == 1 and a.envelope_floor_percent == 0.0):
+        ap.error("--envelope-floor-percent X must be finite and >= 0, and > 0 with --envelope 1")
     if (a.regularize is None) != (a.reg_weight is None):
         ap.error("--regularize and --reg-weight go together")
     if a.regularize is None and (a.reg_eps is not None or a.reg_prior is not None):
@@ -92,6 +109,12 @@ def main():
         local %= ndev
     kw = {"nshots": a.shots} if a.shots else {}
     w = workloads.CONFIGS[a.config](a.scale, **kw)
+    hilbert = None
+    if a.envelope is not None:
+        try:
+            hilbert = datafit.hilbert_taps(datafit.hilbert_halfwidth(w.dt, a.hilbert_fmin))
+        except ValueError as err:
+            ap.error("--hilbert-fmin: %s" % err)
     wav = w.wavelet()
     shots = [sh.Shot(w.src_idx[i:i + 1], wav, w.rec_idx) for i in range(len(w.src_idx))]
     psize = a.pool or ((3 if a.abc == "cpml" else 2) if w.ndim == 2 else 1)  # (measured: shots.EnginePool)
@@ -131,6 +154,8 @@ def main():
         """the misfit of one stage: a fresh object per band (a MatchedL2 keeps the shots' filters of ITS band)"""
         if a.match_source is not None:
             return datafit.MatchedL2(a.match_source, match_mu, taps)
+        if a.envelope is not None:  # (the floor: a data-only number per shot, datafit.envelope_floor of its d_obs)
+            return datafit.EnvelopeL2(hilbert, a.envelope, None, taps, floor_percent=a.envelope_floor_percent)
         return datafit.WeightedL2(taps) if (taps is not None or a.mute_direct is not None) else None
 
     def filters_line(o, band=None):
@@ -237,7 +262,9 @@ def main():
                           "mute_sources_radius": a.mute_sources, "regularize": a.regularize,
                           "reg_weight": a.reg_weight, "reg_eps": reg_eps, "reg_prior": a.reg_prior, "bands_hz": bands,
                           "band_halfwidth": a.band_halfwidth if bands else None, "mute_direct": a.mute_direct,
-                          "match_source": a.match_source,
+                          "match_source": a.match_source, "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
+                          "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
+                          "envelope_floor_percent": a.envelope_floor_percent if a.envelope is not None else None,
                           "match_mu_percent": a.match_mu_percent if a.match_source is not None else None, "log": log}))
     pool.close()
     if rdzv is not None:
