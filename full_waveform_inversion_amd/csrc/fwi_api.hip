@@ -24,6 +24,7 @@
 #include "fwi_born.h"
 #include "fwi_data.h"
 #include "fwi_envelope.h"
+#include "fwi_gather_tile.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
 #include "fwi_match.h"
@@ -185,18 +186,19 @@ struct fwi_ctx {
     void *reg_part = nullptr;    // block partial sums (and their total) of fwi_vec_regularizer; allocated by its first call
     void *sum_part = nullptr;    // the same of fwi_vec_dot, fwi_dot and fwi_misfit_l2 (SUM_MAX_BLOCKS + 1 doubles); allocated
                                  // by the first of those calls
-    // fwi_misfit_weighted / fwi_residual_weight (fwi_data.hip), allocated by their first call: the series between the two
-    // filter passes, the weights, the taps, the block partial sums of J (and their total)
-    void *data_tmp = nullptr, *data_w = nullptr, *data_taps = nullptr, *data_part = nullptr;
-    size_t cap_data_tmp = 0, cap_data_w = 0, cap_data_taps = 0, cap_data_part = 0;
-    // fwi_misfit_matched (fwi_match.hip), allocated by its first call: the filtered synthetics s' and data d' (with taps),
-    // the slices of the normal equations, G and b, the filter
-    void *match_s = nullptr, *match_d = nullptr, *match_part = nullptr, *match_norm = nullptr, *match_f = nullptr;
-    size_t cap_match_s = 0, cap_match_d = 0, cap_match_part = 0, cap_match_norm = 0, cap_match_f = 0;
-    // fwi_misfit_envelope (fwi_envelope.hip), allocated by its first call: the filtered synthetics s' and data d' (with
-    // taps; s' later holds q), g2 (g1 lies in data_tmp), the Hilbert taps
-    void *env_s = nullptr, *env_d = nullptr, *env_g2 = nullptr, *env_h = nullptr;
-    size_t cap_env_s = 0, cap_env_d = 0, cap_env_g2 = 0, cap_env_h = 0;
+    // the data misfits and fwi_residual_weight (Impl<T>::Misfit), each allocated by the first call that needs it: the
+    // series between two passes (e; g1 of the envelope), the weights, the taps of B, the block partial sums of J (and
+    // their total), and the filtered synthetics s' and data d' of the misfits that filter first (with taps; s' later
+    // holds their adjoint source)
+    void *data_tmp = nullptr, *data_w = nullptr, *data_taps = nullptr, *data_part = nullptr, *data_s = nullptr,
+         *data_d = nullptr;
+    size_t cap_data_tmp = 0, cap_data_w = 0, cap_data_taps = 0, cap_data_part = 0, cap_data_s = 0, cap_data_d = 0;
+    // fwi_misfit_matched (fwi_match.hip): the slices of the normal equations, G and b, the filter
+    void *match_part = nullptr, *match_norm = nullptr, *match_f = nullptr;
+    size_t cap_match_part = 0, cap_match_norm = 0, cap_match_f = 0;
+    // fwi_misfit_envelope (fwi_envelope.hip): g2, the Hilbert taps
+    void *env_g2 = nullptr, *env_h = nullptr;
+    size_t cap_env_g2 = 0, cap_env_h = 0;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
     enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
     int resid_pts_in = RESID_PTS_NONE;
@@ -1742,38 +1744,6 @@ struct Impl {
         return FWI_OK;
     }
 
-    // d_obs -> ctx->amp, then amp := series - amp and J = 1/2 sum amp^2, all on the device
-    static int misfit_l2(fwi_ctx *ctx, const T *d_obs, double *J_out) {
-        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
-        const size_t n = (size_t)ctx->nt * (sp.npts ? sp.npts : ctx->nrec);
-        double ss = 0.0;
-        if (n && ctx->nrec) {
-            // off-grid receivers: the residual lives per POINT (against the gathered synthetics kept by the forward)
-            // and is then scattered onto the nodes, where the adjoint sweep injects it
-            void *resid = ctx->amp;
-            int rc;
-            if (sp.npts) {
-                if ((rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T)))) return rc;
-                resid = ctx->pts_a;
-            }
-            if ((rc = upload_series(ctx, resid, d_obs, n * sizeof(T)))) return rc;
-            double *part;
-            if ((rc = sum_partials(ctx, &part))) return rc;
-            HIPCHK(ctx, launch_residual_l2<T>((const T *)(sp.npts ? ctx->pts_d : ctx->series), (T *)resid, (int64_t)n,
-                                              part, ctx->stream));
-            if (sp.npts)
-                HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
-                                                     (const T *)sp.weight, ctx->nt, sp.npts, ctx->nrec, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(&ss, part + sum_blocks((int64_t)n), sizeof(double), hipMemcpyDeviceToHost,
-                                       ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        *J_out = 0.5 * ss;
-        ctx->have_dev_residual = true;
-        ctx->resid_pts_in = (n && ctx->nrec && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
-        return FWI_OK;
-    }
-
     // weights (nt, ntr) and taps b_0 .. b_R of the caller -> the device; the buffers of the two filter passes.  R_out:
     // the half-width that meets samples (taps beyond nt - 1 are not uploaded)
     static int data_prepare(fwi_ctx *ctx, const T *weights, const double *taps, int R, int nt, int ntr, const T **w_dev,
@@ -1781,7 +1751,7 @@ struct Impl {
         const size_t n = (size_t)nt * ntr;
         int rc;
         if ((rc = ensure(ctx, &ctx->data_tmp, &ctx->cap_data_tmp, n * sizeof(T)))) return rc;
-        if ((rc = ensure(ctx, &ctx->data_part, &ctx->cap_data_part, (size_t)(fir_blocks(nt, ntr) + 1) * sizeof(double))))
+        if ((rc = ensure(ctx, &ctx->data_part, &ctx->cap_data_part, (size_t)(gather_blocks(nt, ntr) + 1) * sizeof(double))))
             return rc;
         *w_dev = nullptr;
         if (weights) {
@@ -1804,42 +1774,125 @@ struct Impl {
         return FWI_OK;
     }
 
+    // What the data misfits share around their own launches: where the gathers lie, the upload of d_obs, the filter B
+    // before and after, the scatter onto the nodes, the read-back of the sum of squares and the state of the device
+    // residual.  Off-grid receivers: everything per POINT (against the gathered synthetics kept by the forward); the
+    // residual is then scattered onto the nodes, where the adjoint sweep injects it.
+    struct Misfit {
+        fwi_ctx *ctx;
+        int nt = 0, ntr = 0;
+        size_t n = 0;
+        bool data = false;          // there are receivers and samples: otherwise nothing is launched
+        T *resid = nullptr;         // d_obs after begin(), the residual after finish(): ctx->amp, or ctx->pts_a per point
+        const T *syn = nullptr;     // the synthetics of the last forward: ctx->series, or ctx->pts_d per point
+        const T *w = nullptr;       // data_prepare's: the weights, the taps of B, the half-width that meets samples
+        const double *b = nullptr;
+        int Re = 0;
+        double *part = nullptr;     // gather_blocks + 1 doubles: the block sums of a gather kernel and their total,
+        const double *sum = nullptr;  // ... which is what finish() reads back
+
+        explicit Misfit(fwi_ctx *c) : ctx(c) {}
+
+        // Whatever residual the device held goes with the upload of d_obs: none is left until finish() has succeeded.
+        int begin(const T *d_obs) {
+            const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
+            nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
+            n = (size_t)nt * ntr;
+            data = n && ctx->nrec;
+            ctx->have_dev_residual = false;
+            ctx->resid_pts_in = fwi_ctx::RESID_PTS_NONE;
+            if (!data) return FWI_OK;
+            resid = (T *)ctx->amp, syn = (const T *)ctx->series;
+            if (sp.npts) {
+                if (int rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T))) return rc;
+                resid = (T *)ctx->pts_a, syn = (const T *)ctx->pts_d;
+            }
+            return upload_series(ctx, resid, d_obs, n * sizeof(T));
+        }
+
+        // ... and the weights, the taps and the buffers of the filter passes
+        int begin(const T *d_obs, const T *weights, const double *taps, int R) {
+            int rc = begin(d_obs);
+            if (rc || !data || (rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
+            part = (double *)ctx->data_part;
+            sum = part + gather_blocks(nt, ntr);
+            return FWI_OK;
+        }
+
+        int filter(T *out, const T *in) {
+            HIPCHK(ctx, launch_fir_time<T>(out, in, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr, false, ctx->stream));
+            return FWI_OK;
+        }
+
+        // s1, d1: the synthetics and the data; with taps s' = B d_syn and d' = B d_obs, each rounded to T once
+        int prefilter(const T **s1, const T **d1) {
+            *s1 = syn, *d1 = resid;
+            if (!b) return FWI_OK;
+            int rc;
+            if ((rc = ensure(ctx, &ctx->data_s, &ctx->cap_data_s, n * sizeof(T))) ||
+                (rc = ensure(ctx, &ctx->data_d, &ctx->cap_data_d, n * sizeof(T))) ||
+                (rc = filter((T *)ctx->data_s, syn)) || (rc = filter((T *)ctx->data_d, resid)))
+                return rc;
+            *s1 = (const T *)ctx->data_s, *d1 = (const T *)ctx->data_d;
+            return FWI_OK;
+        }
+
+        // where a misfit that prefilters writes its adjoint source once s' and d' are used up: without taps it is the
+        // residual; with taps it takes the place of s', and finish() has B write r over the uploaded d_obs
+        T *adjoint_source() const { return b ? (T *)ctx->data_s : resid; }
+
+        // resid := B src (src == resid: it is there already), onto the nodes, *ss := the sum of squares
+        int finish(const T *src, double *ss) {
+            const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
+            if (data) {
+                if (src != resid)
+                    if (int rc = filter(resid, src)) return rc;
+                if (sp.npts)
+                    HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
+                                                         (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
+                HIPCHK(ctx, hipMemcpyAsync(ss, sum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            }
+            ctx->have_dev_residual = true;
+            ctx->resid_pts_in = (data && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
+            return FWI_OK;
+        }
+    };
+
+    // d_obs -> the residual buffer, then residual := d_syn - d_obs and J = 1/2 sum residual^2, all on the device
+    static int misfit_l2(fwi_ctx *ctx, const T *d_obs, double *J_out) {
+        Misfit m(ctx);
+        double ss = 0.0;
+        int rc = m.begin(d_obs);
+        if (rc) return rc;
+        if (m.data) {
+            if ((rc = sum_partials(ctx, &m.part))) return rc;
+            m.sum = m.part + sum_blocks((int64_t)m.n);
+            HIPCHK(ctx, launch_residual_l2<T>(m.syn, m.resid, (int64_t)m.n, m.part, ctx->stream));
+        }
+        if ((rc = m.finish(m.resid, &ss))) return rc;
+        *J_out = 0.5 * ss;
+        return FWI_OK;
+    }
+
     // e = M . B (d_syn - d_obs), J = 1/2 sum e^2, r = B (M . e) where the adjoint sweep reads its amplitudes
     static int misfit_weighted(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, double *J_out) {
-        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
-        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
-        const size_t n = (size_t)nt * ntr;
+        Misfit m(ctx);
         double ss = 0.0;
-        if (n && ctx->nrec) {
-            // off-grid receivers: filtered and weighted per POINT (against the gathered synthetics kept by the forward),
-            // then scattered onto the nodes, as misfit_l2 does
-            void *resid = ctx->amp;
-            int rc, Re;
-            if (sp.npts) {
-                if ((rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T)))) return rc;
-                resid = ctx->pts_a;
-            }
-            if ((rc = upload_series(ctx, resid, d_obs, n * sizeof(T)))) return rc;
-            const T *w;
-            const double *b;
-            if ((rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
-            double *part = (double *)ctx->data_part;
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        if (m.data) {
             // neither taps nor weights: e is the plain residual and the call is fwi_misfit_l2 with a fixed-order sum, so
             // J is summed as there, from the residual as stored; otherwise from the unrounded e
-            const bool plain = !w && !b;
-            HIPCHK(ctx, launch_fir_time<T>((T *)ctx->data_tmp, (const T *)(sp.npts ? ctx->pts_d : ctx->series),
-                                           (const T *)resid, nullptr, w, b, Re, nt, ntr, part, plain, ctx->stream));
-            HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)ctx->data_tmp, nullptr, w, nullptr, b, Re, nt, ntr, nullptr,
-                                           false, ctx->stream));
-            if (sp.npts)
-                HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
-                                                     (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(&ss, part + fir_blocks(nt, ntr), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            const bool plain = !m.w && !m.b;
+            T *e = (T *)ctx->data_tmp;
+            HIPCHK(ctx, launch_fir_time<T>(e, m.syn, m.resid, nullptr, m.w, m.b, m.Re, m.nt, m.ntr, m.part, plain,
+                                           ctx->stream));
+            HIPCHK(ctx, launch_fir_time<T>(m.resid, e, nullptr, m.w, nullptr, m.b, m.Re, m.nt, m.ntr, nullptr, false,
+                                           ctx->stream));
         }
+        if ((rc = m.finish(m.resid, &ss))) return rc;
         *J_out = 0.5 * ss;
-        ctx->have_dev_residual = true;
-        ctx->resid_pts_in = (n && ctx->nrec && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
         return FWI_OK;
     }
 
@@ -1847,51 +1900,23 @@ struct Impl {
     // adjoint sweep reads its amplitudes; f given, or the minimiser (G + mu I)^-1 b of J
     static int misfit_matched(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, int L, double mu,
                               const double *f_in, double *f_out, double *normal_out, double *J_out) {
-        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
-        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec, K = 2 * L + 1;
-        const size_t n = (size_t)nt * ntr;
-        const bool data = n && ctx->nrec;
+        const int K = 2 * L + 1;
         std::vector<double> f(K, 0.0), nrm((size_t)K * K + K, 0.0);
         if (f_in) std::copy(f_in, f_in + K, f.begin());
-        // whatever residual the device held goes with the upload of d_obs: none is left until this call succeeds
-        ctx->have_dev_residual = false;
-        ctx->resid_pts_in = fwi_ctx::RESID_PTS_NONE;
-        void *resid = ctx->amp;
-        const T *w = nullptr, *s1 = nullptr, *d1 = nullptr;
-        const double *b = nullptr;
-        int rc, Re = 0;
-        if (data) {
-            // off-grid receivers: everything per POINT (against the gathered synthetics kept by the forward), r then
-            // scattered onto the nodes, as misfit_l2 does
-            if (sp.npts) {
-                if ((rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T)))) return rc;
-                resid = ctx->pts_a;
-            }
-            if ((rc = upload_series(ctx, resid, d_obs, n * sizeof(T)))) return rc;
-            if ((rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
-            if ((rc = ensure(ctx, &ctx->data_part, &ctx->cap_data_part,
-                             (size_t)(std::max(fir_blocks(nt, ntr), match_apply_blocks(nt, ntr)) + 1) * sizeof(double))))
-                return rc;
+        Misfit m(ctx);
+        const T *s1 = nullptr, *d1 = nullptr;
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        if (m.data) {
             if ((rc = ensure(ctx, &ctx->match_f, &ctx->cap_match_f, (size_t)K * sizeof(double)))) return rc;
-            s1 = (const T *)(sp.npts ? ctx->pts_d : ctx->series);
-            d1 = (const T *)resid;
-            if (b) {  // each rounded to T once
-                if ((rc = ensure(ctx, &ctx->match_s, &ctx->cap_match_s, n * sizeof(T)))) return rc;
-                if ((rc = ensure(ctx, &ctx->match_d, &ctx->cap_match_d, n * sizeof(T)))) return rc;
-                HIPCHK(ctx, launch_fir_time<T>((T *)ctx->match_s, s1, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr,
-                                               false, ctx->stream));
-                HIPCHK(ctx, launch_fir_time<T>((T *)ctx->match_d, d1, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr,
-                                               false, ctx->stream));
-                s1 = (const T *)ctx->match_s;
-                d1 = (const T *)ctx->match_d;
-            }
+            if ((rc = m.prefilter(&s1, &d1))) return rc;
             if (!f_in || normal_out) {
                 if ((rc = ensure(ctx, &ctx->match_part, &ctx->cap_match_part,
-                                 (size_t)match_normal_partials(nt, ntr, L) * sizeof(double))))
+                                 (size_t)match_normal_partials(m.nt, m.ntr, L) * sizeof(double))))
                     return rc;
                 if ((rc = ensure(ctx, &ctx->match_norm, &ctx->cap_match_norm, nrm.size() * sizeof(double)))) return rc;
-                HIPCHK(ctx, launch_match_normal<T>((double *)ctx->match_norm, (double *)ctx->match_part, s1, d1, w, L, nt,
-                                                   ntr, ctx->stream));
+                HIPCHK(ctx, launch_match_normal<T>((double *)ctx->match_norm, (double *)ctx->match_part, s1, d1, m.w, L,
+                                                   m.nt, m.ntr, ctx->stream));
                 HIPCHK(ctx, hipMemcpyAsync(nrm.data(), ctx->match_norm, nrm.size() * sizeof(double),
                                            hipMemcpyDeviceToHost, ctx->stream));
                 HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1901,37 +1926,24 @@ struct Impl {
             return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: the normal matrix G + mu I (L=%d, mu=%g) is not positive "
                                          "definite: raise mu", L, mu);
         double ss = 0.0;
-        if (data) {
-            double *part = (double *)ctx->data_part;
+        T *ct = nullptr;
+        if (m.data) {
             // (the filter is this call's pageable memory: the copy is complete before anything that can return follows)
             HIPCHK(ctx, hipMemcpyAsync(ctx->match_f, f.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice,
                                        ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             const double *fd = (const double *)ctx->match_f;
-            HIPCHK(ctx, launch_match_apply<T>((T *)ctx->data_tmp, s1, d1, nullptr, w, fd, L, false, nt, ntr, part,
-                                              ctx->stream));
-            // the synthetics s' and the data d' are used up: C_f^T (M . e) takes the place of s' (with taps), B then
-            // writes r over the uploaded d_obs
-            T *ct = b ? (T *)ctx->match_s : (T *)resid;
-            HIPCHK(ctx, launch_match_apply<T>(ct, (const T *)ctx->data_tmp, nullptr, w, nullptr, fd, L, true, nt, ntr,
-                                              nullptr, ctx->stream));
-            if (b)
-                HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)ct, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr,
-                                               false, ctx->stream));
-            if (sp.npts)
-                HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
-                                                     (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(&ss, part + match_apply_blocks(nt, ntr), sizeof(double), hipMemcpyDeviceToHost,
-                                       ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            T *e = (T *)ctx->data_tmp;
+            HIPCHK(ctx, launch_match_apply<T>(e, s1, d1, nullptr, m.w, fd, L, false, m.nt, m.ntr, m.part, ctx->stream));
+            ct = m.adjoint_source();  // C_f^T (M . e)
+            HIPCHK(ctx, launch_match_apply<T>(ct, e, nullptr, m.w, nullptr, fd, L, true, m.nt, m.ntr, nullptr, ctx->stream));
         }
+        if ((rc = m.finish(ct, &ss))) return rc;
         double ff = 0.0;
         for (int k = 0; k < K; ++k) ff += f[k] * f[k];
         *J_out = 0.5 * ss + 0.5 * mu * ff;
         if (f_out) std::copy(f.begin(), f.end(), f_out);
         if (normal_out) std::copy(nrm.begin(), nrm.end(), normal_out);
-        ctx->have_dev_residual = true;
-        ctx->resid_pts_in = (data && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
         return FWI_OK;
     }
 
@@ -1939,29 +1951,15 @@ struct Impl {
     // reads its amplitudes (fwi_envelope.h)
     static int misfit_envelope(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
                                const double *hilbert, int Q, int power, double eps, double *J_out) {
-        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
-        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
-        const size_t n = (size_t)nt * ntr;
+        Misfit m(ctx);
         double ss = 0.0;
-        if (n && ctx->nrec) {
-            // off-grid receivers: everything per POINT (against the gathered synthetics kept by the forward), r then
-            // scattered onto the nodes, as misfit_l2 does
-            void *resid = ctx->amp;
-            int rc, Re;
-            if (sp.npts) {
-                if ((rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T)))) return rc;
-                resid = ctx->pts_a;
-            }
-            if ((rc = upload_series(ctx, resid, d_obs, n * sizeof(T)))) return rc;
-            const T *w;
-            const double *b;
-            if ((rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
-            if ((rc = ensure(ctx, &ctx->data_part, &ctx->cap_data_part,
-                             (size_t)(std::max(fir_blocks(nt, ntr), env_blocks(nt, ntr)) + 1) * sizeof(double))))
-                return rc;
-            if ((rc = ensure(ctx, &ctx->env_g2, &ctx->cap_env_g2, n * sizeof(T)))) return rc;
+        T *q = nullptr;
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        if (m.data) {
+            if ((rc = ensure(ctx, &ctx->env_g2, &ctx->cap_env_g2, m.n * sizeof(T)))) return rc;
             // the taps that meet samples; are the even ones all zero (a Hilbert transformer's are)?
-            const int Qe = std::max(std::min(Q, nt - 1), 1);
+            const int Qe = std::max(std::min(Q, m.nt - 1), 1);
             bool odd_only = true;
             for (int k = 2; k <= Qe; k += 2) odd_only = odd_only && hilbert[k - 1] == 0.0;
             if ((rc = ensure(ctx, &ctx->env_h, &ctx->cap_env_h, (size_t)Qe * sizeof(double)))) return rc;
@@ -1969,36 +1967,16 @@ struct Impl {
             HIPCHK(ctx, hipMemcpyAsync(ctx->env_h, hilbert, (size_t)Qe * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             const double *hd = (const double *)ctx->env_h;
-            const T *s1 = (const T *)(sp.npts ? ctx->pts_d : ctx->series), *d1 = (const T *)resid;
-            if (b) {  // each rounded to T once
-                if ((rc = ensure(ctx, &ctx->env_s, &ctx->cap_env_s, n * sizeof(T)))) return rc;
-                if ((rc = ensure(ctx, &ctx->env_d, &ctx->cap_env_d, n * sizeof(T)))) return rc;
-                HIPCHK(ctx, launch_fir_time<T>((T *)ctx->env_s, s1, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr, false,
-                                               ctx->stream));
-                HIPCHK(ctx, launch_fir_time<T>((T *)ctx->env_d, d1, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr, false,
-                                               ctx->stream));
-                s1 = (const T *)ctx->env_s;
-                d1 = (const T *)ctx->env_d;
-            }
-            double *part = (double *)ctx->data_part;
+            const T *s1, *d1;
+            if ((rc = m.prefilter(&s1, &d1))) return rc;
             T *g1 = (T *)ctx->data_tmp, *g2 = (T *)ctx->env_g2;
-            HIPCHK(ctx, launch_env_forward<T>(g1, g2, s1, d1, w, hd, Qe, odd_only, power, eps, nt, ntr, part, ctx->stream));
-            // s' and d' are used up: without taps q is the residual, with taps it takes the place of s' and B writes r
-            // over the uploaded d_obs
-            T *q = b ? (T *)ctx->env_s : (T *)resid;
-            HIPCHK(ctx, launch_env_adjoint<T>(q, g1, g2, hd, Qe, odd_only, nt, ntr, ctx->stream));
-            if (b)
-                HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)q, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr,
-                                               false, ctx->stream));
-            if (sp.npts)
-                HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
-                                                     (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(&ss, part + env_blocks(nt, ntr), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            HIPCHK(ctx, launch_env_forward<T>(g1, g2, s1, d1, m.w, hd, Qe, odd_only, power, eps, m.nt, m.ntr, m.part,
+                                              ctx->stream));
+            q = m.adjoint_source();  // g1 - H g2
+            HIPCHK(ctx, launch_env_adjoint<T>(q, g1, g2, hd, Qe, odd_only, m.nt, m.ntr, ctx->stream));
         }
+        if ((rc = m.finish(q, &ss))) return rc;
         *J_out = 0.5 * ss;
-        ctx->have_dev_residual = true;
-        ctx->resid_pts_in = (n && ctx->nrec && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
         return FWI_OK;
     }
 
@@ -2507,9 +2485,9 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}, {"reg_part", ctx->reg_part},
                   {"sum_part", ctx->sum_part},
                   {"data_tmp", ctx->data_tmp}, {"data_w", ctx->data_w}, {"data_taps", ctx->data_taps},
-                  {"data_part", ctx->data_part}, {"match_s", ctx->match_s}, {"match_d", ctx->match_d},
+                  {"data_part", ctx->data_part}, {"data_s", ctx->data_s}, {"data_d", ctx->data_d},
                   {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f},
-                  {"env_s", ctx->env_s}, {"env_d", ctx->env_d}, {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h}};
+                  {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2640,14 +2618,28 @@ int fwi_adjoint(fwi_ctx *ctx, const void *residual, int32_t image, void *adj_src
                     Impl<double>::adjoint(ctx, (const double *)residual, image, (double *)adj_src_out));
 }
 
-int fwi_misfit_l2(fwi_ctx *ctx, const void *d_obs, double *J_out) {
+// The checks every data misfit begins with: a forward run to compare, and the arguments all of them take (`out`: J_out,
+// or nullptr where another mandatory pointer is null).
+static int misfit_callable(fwi_ctx *ctx, const char *who, const void *d_obs, const void *out) {
     if (!ctx) return FWI_EINVAL;
-    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "fwi_misfit_l2: no forward run whose data to compare");
-    if (!J_out || (ctx->nrec && !d_obs)) return ctx->fail(FWI_EINVAL, "fwi_misfit_l2: null argument");
+    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "%s: no forward run whose data to compare", who);
+    if (!out || (ctx->nrec && !d_obs)) return ctx->fail(FWI_EINVAL, "%s: null argument", who);
+    return FWI_OK;
+}
+
+// ... and the one they end with, after their own parameters: the synthetics are still there (`also`: what else, besides
+// an fwi_adjoint, the entry point names as having overwritten them).  Selects the device.
+static int misfit_synthetics(fwi_ctx *ctx, const char *who, const char *also) {
     if (!ctx->have_syn)
-        return ctx->fail(FWI_ESTATE, "fwi_misfit_l2: the synthetics of the last forward are gone (an fwi_adjoint has "
-                                     "run since): call it between fwi_forward and fwi_adjoint");
+        return ctx->fail(FWI_ESTATE, "%s: the synthetics of the last forward are gone (an fwi_adjoint %shas run since): "
+                                     "call it between fwi_forward and fwi_adjoint", who, also);
     (void)hipSetDevice(ctx->cfg.device);
+    return FWI_OK;
+}
+
+int fwi_misfit_l2(fwi_ctx *ctx, const void *d_obs, double *J_out) {
+    if (int rc = misfit_callable(ctx, "fwi_misfit_l2", d_obs, J_out)) return rc;
+    if (int rc = misfit_synthetics(ctx, "fwi_misfit_l2", "")) return rc;
     return DISPATCH(ctx, Impl<float>::misfit_l2(ctx, (const float *)d_obs, J_out),
                     Impl<double>::misfit_l2(ctx, (const double *)d_obs, J_out));
 }
@@ -2660,14 +2652,9 @@ static int data_args(fwi_ctx *ctx, const char *who, const double *taps, int32_t 
 
 int fwi_misfit_weighted(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
                         double *J_out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "fwi_misfit_weighted: no forward run whose data to compare");
-    if (!J_out || (ctx->nrec && !d_obs)) return ctx->fail(FWI_EINVAL, "fwi_misfit_weighted: null argument");
+    if (int rc = misfit_callable(ctx, "fwi_misfit_weighted", d_obs, J_out)) return rc;
     if (int rc = data_args(ctx, "fwi_misfit_weighted", taps, R)) return rc;
-    if (!ctx->have_syn)
-        return ctx->fail(FWI_ESTATE, "fwi_misfit_weighted: the synthetics of the last forward are gone (an fwi_adjoint "
-                                     "or fwi_born has run since): call it between fwi_forward and fwi_adjoint");
-    (void)hipSetDevice(ctx->cfg.device);
+    if (int rc = misfit_synthetics(ctx, "fwi_misfit_weighted", "or fwi_born ")) return rc;
     return DISPATCH(ctx,
                     Impl<float>::misfit_weighted(ctx, (const float *)d_obs, (const float *)weights, taps, R, J_out),
                     Impl<double>::misfit_weighted(ctx, (const double *)d_obs, (const double *)weights, taps, R, J_out));
@@ -2675,9 +2662,7 @@ int fwi_misfit_weighted(fwi_ctx *ctx, const void *d_obs, const void *weights, co
 
 int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R, int32_t L,
                        double mu, const double *f_in, double *f_out, double *normal_out, double *J_out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "fwi_misfit_matched: no forward run whose data to compare");
-    if (!J_out || (ctx->nrec && !d_obs)) return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: null argument");
+    if (int rc = misfit_callable(ctx, "fwi_misfit_matched", d_obs, J_out)) return rc;
     if (int rc = data_args(ctx, "fwi_misfit_matched", taps, R)) return rc;
     if (L < 0 || L > FWI_MATCH_LMAX)
         return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: L=%d outside [0, %d]", (int)L, FWI_MATCH_LMAX);
@@ -2685,10 +2670,7 @@ int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs, const void *weights, con
     if (f_in)
         for (int k = 0; k < 2 * L + 1; ++k)
             if (!std::isfinite(f_in[k])) return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: f_in[%d] is not finite", k);
-    if (!ctx->have_syn)
-        return ctx->fail(FWI_ESTATE, "fwi_misfit_matched: the synthetics of the last forward are gone (an fwi_adjoint "
-                                     "or fwi_born has run since): call it between fwi_forward and fwi_adjoint");
-    (void)hipSetDevice(ctx->cfg.device);
+    if (int rc = misfit_synthetics(ctx, "fwi_misfit_matched", "or fwi_born ")) return rc;
     return DISPATCH(ctx,
                     Impl<float>::misfit_matched(ctx, (const float *)d_obs, (const float *)weights, taps, R, L, mu, f_in,
                                                 f_out, normal_out, J_out),
@@ -2698,9 +2680,7 @@ int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs, const void *weights, con
 
 int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
                         const double *hilbert, int32_t Q, int32_t power, double eps, double *J_out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "fwi_misfit_envelope: no forward run whose data to compare");
-    if (!J_out || (ctx->nrec && !d_obs) || !hilbert) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: null argument");
+    if (int rc = misfit_callable(ctx, "fwi_misfit_envelope", d_obs, hilbert ? J_out : nullptr)) return rc;
     if (int rc = data_args(ctx, "fwi_misfit_envelope", taps, R)) return rc;
     if (Q < 1 || Q > FIR_RMAX) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: Q=%d outside [1, %d]", (int)Q, FIR_RMAX);
     for (int k = 0; k < Q; ++k)
@@ -2710,10 +2690,7 @@ int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs, const void *weights, co
         return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: eps=%g must be finite and >= 0", eps);
     if (power == 1 && eps == 0.0)
         return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: power 1 needs eps > 0 (the envelope is not differentiable at 0)");
-    if (!ctx->have_syn)
-        return ctx->fail(FWI_ESTATE, "fwi_misfit_envelope: the synthetics of the last forward are gone (an fwi_adjoint "
-                                     "or fwi_born has run since): call it between fwi_forward and fwi_adjoint");
-    (void)hipSetDevice(ctx->cfg.device);
+    if (int rc = misfit_synthetics(ctx, "fwi_misfit_envelope", "or fwi_born ")) return rc;
     return DISPATCH(ctx,
                     Impl<float>::misfit_envelope(ctx, (const float *)d_obs, (const float *)weights, taps, R, hilbert, Q,
                                                  power, eps, J_out),

@@ -13,20 +13,15 @@
 namespace fwi {
 
 constexpr int FIR_RMAX = 4096;  // largest half-width the entry points accept
-// A block of 256 threads owns FIR_LANES traces by FIR_TT output times: lane = trace, one wave per FIR_TO consecutive
-// output times, which its threads keep in registers.
-constexpr int FIR_LANES = 64, FIR_TO = 8, FIR_TT = 4 * FIR_TO;
 
-// number of blocks of one launch = number of partial sums; a buffer handed over as `partial` holds one double more
-int64_t fir_blocks(int nt, int ntr);
-
-// out := [wpost .] B([wpre .] (in - sub)) over (nt, ntr); sub, wpre and wpost may each be nullptr (no subtraction, weight
+// out :=[wpost .] B([wpre .] (in - sub)) over (nt, ntr); sub, wpre and wpost may each be nullptr (no subtraction, weight
 // 1).  taps: R + 1 doubles b_0 .. b_R on the device, nullptr: B = I (R is then ignored).  R may exceed nt - 1: the taps
 // beyond are never read.  Everything between the loads and the one rounding to T is fp64, summed over ascending k.
-// partial != nullptr: partial[fir_blocks] := sum of the squares of the UNROUNDED output values -- sq_stored: of the values
-// as stored, rounded to T, which is what fwi_misfit_l2 sums -- added over the blocks' partial sums
-// partial[0 .. fir_blocks) in a fixed order: equal inputs give equal bits.  out must not alias in, sub or the weights
-// (tiles read their neighbours' rows).  Rows outside [0, nt) and traces >= ntr are never read.
+// partial != nullptr: partial[gather_blocks] := sum of the squares of the UNROUNDED output values -- sq_stored: of the
+// values as stored, rounded to T, which is what fwi_misfit_l2 sums -- added over the blocks' partial sums
+// partial[0 .. gather_blocks) in a fixed order (fwi_gather_tile.h has the tile and the sums): equal inputs give equal
+// bits.  out must not alias in, sub or the weights (tiles read their neighbours' rows).  Rows outside [0, nt) and
+// traces >= ntr are never read.
 template <typename T>
 hipError_t launch_fir_time(T *out, const T *in, const T *sub, const T *wpre, const T *wpost, const double *taps, int R,
                            int nt, int ntr, double *partial, bool sq_stored, hipStream_t s);

@@ -14,12 +14,9 @@
 
 namespace fwi {
 
-// number of blocks of one launch (the tiling is fir_time's: 64 traces by 32 output times) = number of partial sums; a
-// buffer handed over as `partial` holds one double more
-int64_t env_blocks(int nt, int ntr);
-
-// g1 := c . s, g2 := c . (H s), each rounded to T once; partial[env_blocks] := sum of the squares of the UNROUNDED e,
-// added over the blocks' partial sums partial[0 .. env_blocks) in a fixed order: equal inputs give equal bits.
+// g1 := c . s, g2 := c . (H s), each rounded to T once; partial[gather_blocks] := sum of the squares of the UNROUNDED e,
+// added over the blocks' partial sums partial[0 .. gather_blocks) in a fixed order (fwi_gather_tile.h has the tile and
+// the sums): equal inputs give equal bits.
 // s, d: (nt, ntr); w: the weights M (nullptr: 1); h: Q doubles h_1 .. h_Q on the device; power 1 or 2; eps >= 0
 // (> 0 with power 1).  Q may exceed nt - 1: the taps beyond are never read.  odd_only: the caller asserts that every
 // h_k with even k <= min(Q, nt - 1) is zero, and their products are then not formed (for finite s and d the bits are

@@ -31,14 +31,10 @@ template <typename T>
 hipError_t launch_match_normal(double *normal, double *partial, const T *s, const T *d, const T *w, int L, int nt,
                                int ntr, hipStream_t st);
 
-// number of blocks of one launch_match_apply = number of its partial sums; a buffer handed over as `partial` holds one
-// double more
-int64_t match_apply_blocks(int nt, int ntr);
-
 // out := [wpost .] (C ([wpre .] in) [- sub]) over (nt, ntr), C = C_f, or C_f^T with `corr`; f: K doubles on the device.
 // Per output the terms are added over ascending k in fp64; the result is rounded to T once, at the store.
-// partial != nullptr: partial[match_apply_blocks] := the sum of the squares of the unrounded outputs, added in a fixed
-// order.  out must not alias an input.
+// partial != nullptr: partial[gather_blocks] := the sum of the squares of the unrounded outputs, added in a fixed
+// order (fwi_gather_tile.h has the tile and the sums).  out must not alias an input.
 template <typename T>
 hipError_t launch_match_apply(T *out, const T *in, const T *sub, const T *wpre, const T *wpost, const double *f, int L,
                               bool corr, int nt, int ntr, double *partial, hipStream_t st);

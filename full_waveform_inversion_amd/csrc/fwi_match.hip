@@ -14,26 +14,27 @@
 // `partial`.  match_reduce adds the slices in ascending order and writes G (both triangles) and b.  The last tile row and
 // column also form the shifts a >= K up to the tile edge; those entries are never read again.
 //
-// match_apply.  The non-symmetric sibling of fir_time, without its chunking (K <= 129): lane = trace, a block of 256
-// owns 64 traces x 32 times, 8 consecutive outputs per thread, the coefficients in LDS (padded to a multiple of 8; the
-// padding is skipped, not multiplied), the 15 input rows that 8 outputs and 8 coefficients can pair in a register
-// window.  Sums over ascending k, in fp64; sum of squares as fir_time has it (per thread over ascending time, a fixed tree per block, match_sum).
+// match_apply.  The tile and the fixed-order sum of squares are the shared ones of fwi_gather_tile.h, not its march:
+// K <= 129, so nothing is chunked.  The coefficients sit in LDS (padded to a multiple of 8; the padding is skipped, not
+// multiplied), the 15 input rows that 8 outputs and 8 coefficients can pair in a register window that is read from
+// global memory.  Sums over ascending k, in fp64.
 //
 // No atomics anywhere.
 #include <hip/hip_runtime.h>
 
+#include "fwi_gather_tile.h"
+#include "fwi_kernels.h"
 #include "fwi_match.h"
 
 namespace fwi {
 
 namespace {
 
-constexpr int MT = 8;             // tile edge of match_normal, outputs per thread of match_apply
+constexpr int MT = GT_TO;         // tile edge of match_normal, outputs per thread of match_apply
 constexpr int MN_TT = 64;         // times per unit of match_normal
 constexpr int MN_SLICES = 256;    // most slices of the partials buffer
-constexpr int MA_BLOCK = 256, MA_TT = 4 * MT;
 constexpr int MATCH_KP = (2 * MATCH_LMAX + 1 + MT - 1) / MT * MT;  // 136
-static_assert(MN_TT % MT == 0 && MA_BLOCK == 64 * (MA_TT / MT), "whole steps of 8; one wave per 8 output times");
+static_assert(MN_TT % MT == 0, "whole steps of 8");
 
 struct NormalArgs {
     int nt, ntr, L, nT, P, xtiles, units, slices;
@@ -183,17 +184,16 @@ struct ApplyArgs {
 };
 
 template <typename T, bool CORR>
-__global__ __launch_bounds__(MA_BLOCK) void match_apply(T *__restrict__ out, const T *__restrict__ in,
+__global__ __launch_bounds__(GT_BLOCK) void match_apply(T *__restrict__ out, const T *__restrict__ in,
                                                         const T *__restrict__ sub, const T *__restrict__ wpre,
                                                         const T *__restrict__ wpost, const double *__restrict__ f,
                                                         ApplyArgs a, double *__restrict__ partial) {
     __shared__ double sF[MATCH_KP];
-    __shared__ double sRed[MA_BLOCK];
-    const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6;
-    const int gx = (int)(blockIdx.x % a.xtiles) * 64 + lane;
-    const int tn0 = (int)(blockIdx.x / a.xtiles) * MA_TT + grp * MT;  // this thread's first output time
+    __shared__ double sRed[GT_BLOCK];
+    const GatherTile c = gather_tile(a.xtiles);
+    const int tid = threadIdx.x, gx = c.gx, tn0 = c.tn0;
     const int nt = a.nt, ntr = a.ntr, K = 2 * a.L + 1, Kp = (K + MT - 1) / MT * MT;
-    for (int k = tid; k < Kp; k += MA_BLOCK) sF[k] = k < K ? f[k] : 0.0;
+    for (int k = tid; k < Kp; k += GT_BLOCK) sF[k] = k < K ? f[k] : 0.0;
     __syncthreads();
     const bool live = gx < ntr;
     auto X = [&](int row) -> double {
@@ -264,30 +264,7 @@ __global__ __launch_bounds__(MA_BLOCK) void match_apply(T *__restrict__ out, con
             }
         }
     }
-    if (partial) {
-        sRed[tid] = sq;
-        __syncthreads();
-        for (int st = MA_BLOCK / 2; st > 0; st >>= 1) {
-            if (tid < st) sRed[tid] += sRed[tid + st];
-            __syncthreads();
-        }
-        if (tid == 0) partial[blockIdx.x] = sRed[0];
-    }
-}
-
-// partial[n] = sum of partial[0 .. n): strided per thread, then a fixed tree
-__global__ __launch_bounds__(MA_BLOCK) void match_sum(double *partial, int64_t n) {
-    __shared__ double sRed[MA_BLOCK];
-    const int tid = threadIdx.x;
-    double acc = 0.0;
-    for (int64_t i = tid; i < n; i += MA_BLOCK) acc += partial[i];
-    sRed[tid] = acc;
-    __syncthreads();
-    for (int st = MA_BLOCK / 2; st > 0; st >>= 1) {
-        if (tid < st) sRed[tid] += sRed[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) partial[n] = sRed[0];
+    if (partial) block_tree_sum_to_partial(sq, sRed, partial);
 }
 
 }  // namespace
@@ -312,27 +289,24 @@ hipError_t launch_match_normal(double *normal, double *partial, const T *s, cons
     return hipGetLastError();
 }
 
-int64_t match_apply_blocks(int nt, int ntr) { return (int64_t)((ntr + 63) / 64) * ((nt + MA_TT - 1) / MA_TT); }
-
 template <typename T>
 hipError_t launch_match_apply(T *out, const T *in, const T *sub, const T *wpre, const T *wpost, const double *f, int L,
                               bool corr, int nt, int ntr, double *partial, hipStream_t st) {
-    const int64_t blocks = match_apply_blocks(nt, ntr);
+    const int64_t blocks = gather_blocks(nt, ntr);
     if (!out || !in || !f || nt < 1 || ntr < 1 || L < 0 || L > MATCH_LMAX || blocks > 0x7fffffff || out == in ||
         out == sub || out == wpre || out == wpost)
         return hipErrorInvalidValue;
     ApplyArgs a;
-    a.nt = nt, a.ntr = ntr, a.L = L, a.xtiles = (ntr + 63) / 64;
+    a.nt = nt, a.ntr = ntr, a.L = L, a.xtiles = gather_xtiles(ntr);
     if (corr)
-        hipLaunchKernelGGL((match_apply<T, true>), dim3((unsigned)blocks), dim3(MA_BLOCK), 0, st, out, in, sub, wpre,
+        hipLaunchKernelGGL((match_apply<T, true>), dim3((unsigned)blocks), dim3(GT_BLOCK), 0, st, out, in, sub, wpre,
                            wpost, f, a, partial);
     else
-        hipLaunchKernelGGL((match_apply<T, false>), dim3((unsigned)blocks), dim3(MA_BLOCK), 0, st, out, in, sub, wpre,
+        hipLaunchKernelGGL((match_apply<T, false>), dim3((unsigned)blocks), dim3(GT_BLOCK), 0, st, out, in, sub, wpre,
                            wpost, f, a, partial);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !partial) return e;
-    hipLaunchKernelGGL(match_sum, dim3(1), dim3(MA_BLOCK), 0, st, partial, blocks);
-    return hipGetLastError();
+    return launch_sum_partials(partial, blocks, st);
 }
 
 template hipError_t launch_match_normal<float>(double *, double *, const float *, const float *, const float *, int, int,

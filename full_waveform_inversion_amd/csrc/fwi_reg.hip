@@ -13,9 +13,11 @@
 //           and y fluxes from the neighbours' k in LDS, the low z flux carried over in registers from the plane before
 //           (a chunk that does not start at z = 0 forms it from the plane z0 - 1 first, without output).
 // Everything between the loads and the final rounding to T is fp64.  The value R is summed per thread over ascending z,
-// then over the block by a fixed tree into partial[block]; reg_final adds the partials in a fixed order.  No atomics.
+// then over the block by a fixed tree (fwi_gather_tile.h) into partial[block]; reg_final adds the partials in a fixed
+// order.  No atomics.
 #include <hip/hip_runtime.h>
 
+#include "fwi_gather_tile.h"
 #include "fwi_reg.h"
 
 namespace fwi {
@@ -23,7 +25,7 @@ namespace fwi {
 namespace {
 
 constexpr int RG_BLOCK = 256;
-static_assert(REG_TY * REG_XL == RG_BLOCK, "one thread per row and lane");
+static_assert(REG_TY * REG_XL == RG_BLOCK && RG_BLOCK == GT_BLOCK, "one thread per row and lane; the block sum's 256");
 
 template <typename T>
 struct alignas(16) Lane {
@@ -161,13 +163,7 @@ __global__ __launch_bounds__(RG_BLOCK) void reg_apply(T *out, const T *x, const 
         for (int e = 0; e < V; ++e) fzprev[e] = fz[e];
         __syncthreads();  // the next step stages the plane z + 2 where the plane z lies
     }
-    sRed[tid] = acc;
-    __syncthreads();
-    for (int s = RG_BLOCK / 2; s > 0; s >>= 1) {
-        if (tid < s) sRed[tid] += sRed[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) partial[blockIdx.x] = sRed[0];
+    block_tree_sum_to_partial(acc, sRed, partial);
 }
 
 // partial[n] = sum of partial[0 .. n): strided per thread, then a fixed tree
