@@ -66,6 +66,7 @@ SIGNATURES = {
     "fwi_misfit_matched": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _D, _P, _P, _P, C.POINTER(_D)]),
     "fwi_match_solve": (C.c_int, [_P, _P, _I32, _D, _P]),
     "fwi_misfit_envelope": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _I32, _D, C.POINTER(_D)]),
+    "fwi_misfit_correlation": (C.c_int, [_P, _P, _P, _P, _I32, _P, _D, C.POINTER(_D), _P]),
     "fwi_gradient": (C.c_int, [_P, _I32, _P]),
     "fwi_gradient_reset": (C.c_int, [_P]),
     "fwi_gradient_add": (C.c_int, [_P, _P]),

@@ -23,6 +23,7 @@
 #include "../../include/fwi.h"
 #include "fwi_born.h"
 #include "fwi_data.h"
+#include "fwi_corr.h"
 #include "fwi_envelope.h"
 #include "fwi_gather_tile.h"
 #include "fwi_illum.h"
@@ -199,6 +200,9 @@ struct fwi_ctx {
     // fwi_misfit_envelope (fwi_envelope.hip): g2, the Hilbert taps
     void *env_g2 = nullptr, *env_h = nullptr;
     size_t cap_env_g2 = 0, cap_env_h = 0;
+    // fwi_misfit_correlation (fwi_corr.hip): the per-tile sums and the terms of J, alpha / beta / rho, the trace weights
+    void *corr_part = nullptr, *corr_coef = nullptr, *corr_tw = nullptr;
+    size_t cap_corr_part = 0, cap_corr_coef = 0, cap_corr_tw = 0;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
     enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
     int resid_pts_in = RESID_PTS_NONE;
@@ -1980,6 +1984,48 @@ struct Impl {
         return FWI_OK;
     }
 
+    // s' = B d_syn, d' = B d_obs, rho_j the normalised zero-lag correlation of the weighted traces M s', M d' with the
+    // floor eps, J = sum_j w_j (1 - rho_j), r = B g where the adjoint sweep reads its amplitudes (fwi_corr.h)
+    static int misfit_correlation(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
+                                  const double *trace_weights, double eps, double *J_out, double *rho_out) {
+        Misfit m(ctx);
+        double J = 0.0;
+        T *g = nullptr;
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        if (m.data) {
+            const size_t np = corr_partials(m.nt, m.ntr);
+            if ((rc = ensure(ctx, &ctx->corr_part, &ctx->cap_corr_part, np * sizeof(double))) ||
+                (rc = ensure(ctx, &ctx->corr_coef, &ctx->cap_corr_coef, (size_t)3 * m.ntr * sizeof(double))))
+                return rc;
+            const double *tw = nullptr;
+            if (trace_weights) {
+                if ((rc = ensure(ctx, &ctx->corr_tw, &ctx->cap_corr_tw, (size_t)m.ntr * sizeof(double)))) return rc;
+                // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
+                HIPCHK(ctx, hipMemcpyAsync(ctx->corr_tw, trace_weights, (size_t)m.ntr * sizeof(double),
+                                           hipMemcpyHostToDevice, ctx->stream));
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                tw = (const double *)ctx->corr_tw;
+            }
+            double *part = (double *)ctx->corr_part, *coef = (double *)ctx->corr_coef;
+            m.sum = part + (np - 1);  // the total of the terms w_j (1 - rho_j): J itself
+            const T *s1, *d1;
+            if ((rc = m.prefilter(&s1, &d1))) return rc;
+            HIPCHK(ctx, launch_corr_sums<T>(part, s1, d1, m.w, m.nt, m.ntr, ctx->stream));
+            HIPCHK(ctx, launch_corr_coeffs(coef, part, tw, eps, m.nt, m.ntr, ctx->stream));
+            g = m.adjoint_source();  // in place of s' (with taps) or of d_obs (without): elementwise
+            HIPCHK(ctx, launch_corr_source<T>(g, s1, d1, m.w, coef, m.nt, m.ntr, ctx->stream));
+        }
+        if ((rc = m.finish(g, &J))) return rc;
+        if (m.data && rho_out) {
+            HIPCHK(ctx, hipMemcpyAsync(rho_out, (const double *)ctx->corr_coef + 2 * (size_t)m.ntr,
+                                       (size_t)m.ntr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        *J_out = J;
+        return FWI_OK;
+    }
+
     // device residual := B M^2 B residual: per node, or per off-grid point and scattered onto the nodes again
     static int residual_weight(fwi_ctx *ctx, const T *weights, const double *taps, int R) {
         const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
@@ -2487,7 +2533,8 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"data_tmp", ctx->data_tmp}, {"data_w", ctx->data_w}, {"data_taps", ctx->data_taps},
                   {"data_part", ctx->data_part}, {"data_s", ctx->data_s}, {"data_d", ctx->data_d},
                   {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f},
-                  {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h}};
+                  {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h},
+                  {"corr_part", ctx->corr_part}, {"corr_coef", ctx->corr_coef}, {"corr_tw", ctx->corr_tw}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2696,6 +2743,27 @@ int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs, const void *weights, co
                                                  power, eps, J_out),
                     Impl<double>::misfit_envelope(ctx, (const double *)d_obs, (const double *)weights, taps, R, hilbert, Q,
                                                   power, eps, J_out));
+}
+
+int fwi_misfit_correlation(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
+                           const double *trace_weights, double eps, double *J_out, double *rho_out) {
+    if (int rc = misfit_callable(ctx, "fwi_misfit_correlation", d_obs, J_out)) return rc;
+    if (int rc = data_args(ctx, "fwi_misfit_correlation", taps, R)) return rc;
+    if (!(eps >= 0.0) || !std::isfinite(eps))
+        return ctx->fail(FWI_EINVAL, "fwi_misfit_correlation: eps=%g must be finite and >= 0", eps);
+    if (trace_weights && ctx->nrec) {
+        const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
+        for (int j = 0; j < ntr; ++j)
+            if (!(trace_weights[j] >= 0.0) || !std::isfinite(trace_weights[j]))
+                return ctx->fail(FWI_EINVAL, "fwi_misfit_correlation: trace_weights[%d]=%g must be finite and >= 0", j,
+                                 trace_weights[j]);
+    }
+    if (int rc = misfit_synthetics(ctx, "fwi_misfit_correlation", "or fwi_born ")) return rc;
+    return DISPATCH(ctx,
+                    Impl<float>::misfit_correlation(ctx, (const float *)d_obs, (const float *)weights, taps, R,
+                                                    trace_weights, eps, J_out, rho_out),
+                    Impl<double>::misfit_correlation(ctx, (const double *)d_obs, (const double *)weights, taps, R,
+                                                     trace_weights, eps, J_out, rho_out));
 }
 
 int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {

@@ -51,6 +51,29 @@ Hilbert transformer ``H`` is an FIR filter with an antisymmetric impulse respons
 ``eps > 0`` is required for ``p = 1`` (``E`` is not differentiable at 0), ``eps >= 0`` allowed for ``p = 2``.  Like
 ``mu`` it must not follow ``s``: :func:`envelope_floor` is a data-only choice.  An envelope has no linear Gauss-Newton
 weight: :class:`EnvelopeL2` is not a :class:`WeightedL2`.
+
+Trace-normalised correlation misfit, :class:`NormalizedCorrelation` (``Engine.misfit_correlation``,
+``fwi_misfit_correlation``, ``csrc/fwi_corr.hip``): every misfit above is a difference of amplitudes, and a constant-
+density acoustic engine cannot model elastic amplitude-versus-offset, attenuation, receiver coupling or source strength.
+The zero-lag normalised ("global") correlation of Choi & Alkhalifah 2012 reads phase only and ignores the gain of every
+trace; it is the reference's ``CC`` measure (``objectives.correlation``) with weights, a band and a floor.  With
+``s = d_syn``, ``d = d_obs``, ``B`` and ``M`` as above, ``w_j >= 0`` optional weights per trace (default 1) and
+``eps >= 0`` an absolute floor:
+
+    s' = B s,  d' = B d            (rounded to the context dtype once, only when taps are given)
+    sh = M . s',  dh = M . d'
+    a_j = sum_n sh[n,j]^2    b_j = sum_n dh[n,j]^2    c_j = sum_n sh[n,j] dh[n,j]
+    ns_j = sqrt(a_j + eps^2)  nd_j = sqrt(b_j + eps^2)   rho_j = c_j / (ns_j nd_j)
+    trace j counts iff  b_j > 0 and a_j + eps^2 > 0;  otherwise J_j = 0, rho_j = 0 and its adjoint source is 0
+    J = sum_j w_j (1 - rho_j)
+    alpha_j = -w_j / (ns_j nd_j)     beta_j = c_j / ns_j^2
+    g = M . alpha_j (dh - beta_j sh)           (rounded to the dtype once)
+    r = dJ/ds = B g
+
+A scale per trace inside ``M`` cancels, so ``w`` is the only way to down-weight a trace.  Like ``mu`` and the envelope's
+floor, ``eps`` must not follow ``s``: :func:`correlation_floor` is a data-only choice.  With ``eps = 0``, no weights, no
+taps and mean-free traces, ``J / ntr`` and ``r / ntr`` are ``objectives.correlation(per_trace=True)``.  There is no
+Gauss-Newton weight of the form ``B M^2 B``: :class:`NormalizedCorrelation` is not a :class:`WeightedL2`.
 """
 from __future__ import annotations
 
@@ -422,6 +445,88 @@ class EnvelopeL2:
         g1, g2 = self._round(c * s1), self._round(c * hs)
         q = self._round(g1 - hilbert_time(g2, self.hilbert))
         return 0.5 * float(np.sum(e * e)), (q if self.taps is None else fir_time(q, self.taps))
+
+
+def correlation_floor(d_obs, percent=1.0):
+    """``percent / 100 * max_j ||d_obs[:, j]||_2``: a floor ``eps`` for :class:`NormalizedCorrelation` that depends on the
+    data only -- like :func:`envelope_floor`, compute it once per shot and hold it through an inversion."""
+    if not (float(percent) >= 0.0 and np.isfinite(percent)):
+        raise ValueError("percent must be finite and >= 0")
+    d = np.asarray(d_obs, np.float64)
+    if d.ndim != 2:
+        raise ValueError("d_obs must be (nt, ntr)")
+    return float(percent) / 100.0 * (float(np.sqrt(np.max(np.sum(d * d, axis=0)))) if d.size else 0.0)
+
+
+class NormalizedCorrelation:
+    """The trace-normalised correlation misfit of the module's definition in fp64 NumPy,
+    ``objective(d_syn, d_obs, weights=None, trace_weights=None) -> (J, r)``, and the ``objective=`` that
+    ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_correlation`` replaces it by the device path;
+    the shot loop hands it ``Shot.weights`` and ``Shot.trace_weights``).
+
+    ``eps``: the absolute floor ``>= 0`` under the trace norms; None: :func:`correlation_floor` of each call's ``d_obs``
+    at ``floor_percent``, a data-only number.  ``taps``: the one-sided ``b_0 .. b_R`` of ``B``, or None.  ``dtype``: round
+    ``B s``, ``B d`` (with taps) and ``g`` to it once each, as a device context of that dtype does (None: keep fp64).
+
+    ``correlations`` holds the ``rho_j`` of the last call (0 where a trace does not count).  Not a :class:`WeightedL2`:
+    there is no linear Gauss-Newton weight, and ``gauss_newton_hvp`` refuses it."""
+
+    def __init__(self, eps=None, taps=None, dtype=None, floor_percent=1.0):
+        if eps is not None and not (float(eps) >= 0.0 and np.isfinite(eps)):
+            raise ValueError("eps must be finite and >= 0")
+        if not (float(floor_percent) >= 0.0 and np.isfinite(floor_percent)):
+            raise ValueError("floor_percent must be finite and >= 0")
+        self.eps = None if eps is None else float(eps)
+        self.floor_percent = float(floor_percent)
+        self.taps = _checked_taps(taps)
+        self.dtype = None if dtype is None else np.dtype(dtype)
+        self.correlations = None
+
+    def eps_of(self, d_obs):
+        """the floor of a shot: ``eps``, or :func:`correlation_floor` of its observed data"""
+        return self.eps if self.eps is not None else correlation_floor(d_obs, self.floor_percent)
+
+    def _round(self, x):
+        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+
+    def filter(self, x):
+        """``B x`` (rounded to ``dtype`` once; without taps a copy of x)"""
+        return fir_time(x, None) if self.taps is None else self._round(fir_time(x, self.taps))
+
+    def sums(self, d_syn, d_obs, weights=None):
+        """``(a, b, c, sh, dh)`` of the definition: the per-trace sums and the weighted, filtered gathers"""
+        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
+        if s.ndim != 2 or s.shape != d.shape:
+            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
+        M = WeightedL2._weights(weights, s.shape)
+        sh, dh = self.filter(s), self.filter(d)
+        if M is not None:
+            sh, dh = M * sh, M * dh
+        return np.sum(sh * sh, axis=0), np.sum(dh * dh, axis=0), np.sum(sh * dh, axis=0), sh, dh
+
+    def __call__(self, d_syn, d_obs, weights=None, trace_weights=None):
+        a, b, c, sh, dh = self.sums(d_syn, d_obs, weights)
+        ntr = a.size
+        w = np.ones(ntr)
+        if trace_weights is not None:
+            w = np.asarray(trace_weights, np.float64)
+            if w.shape != (ntr,):
+                raise ValueError("trace_weights have shape %r, the data %d traces" % (w.shape, ntr))
+            if not np.all(np.isfinite(w)) or np.any(w < 0.0):
+                raise ValueError("trace_weights must be finite and >= 0")
+        eps = self.eps_of(d_obs)
+        a2, b2 = a + eps * eps, b + eps * eps
+        counts = (b > 0.0) & (a2 > 0.0)
+        nn = np.where(counts, np.sqrt(a2) * np.sqrt(b2), 1.0)
+        rho = np.where(counts, c / nn, 0.0)
+        alpha = np.where(counts, -w / nn, 0.0)
+        beta = np.where(counts, c / np.where(counts, a2, 1.0), 0.0)
+        self.correlations = rho
+        g = alpha * (dh - beta * sh)
+        if weights is not None:
+            g = np.asarray(weights, np.float64) * g
+        g = self._round(g)
+        return float(np.sum(np.where(counts, w * (1.0 - rho), 0.0))), (g if self.taps is None else fir_time(g, self.taps))
 
 
 def matched_wavelet(wavelet, f):

@@ -307,6 +307,33 @@ class Engine:
                                                 h.ctypes.data_as(C.c_void_p), h.size, int(power), float(eps), C.byref(J)))
         return J.value
 
+    def misfit_correlation(self, d_obs, eps=None, weights=None, taps=None, trace_weights=None, per_trace=False):
+        """Trace-normalised zero-lag correlation misfit of the last forward's seismograms, which reads phase only and
+        ignores the gain of every trace: with ``sh = M . B d_syn``, ``dh = M . B d_obs``,
+        ``rho_j = <sh_j, dh_j> / (sqrt(|sh_j|^2 + eps^2) sqrt(|dh_j|^2 + eps^2))`` per trace and
+        ``J = sum_j w_j (1 - rho_j)``.  ``eps >= 0`` is an absolute floor that must not depend on the synthetics; None:
+        ``datafit.correlation_floor(d_obs)``, 1 % of the largest trace norm of the observed data.  ``weights`` and
+        ``taps`` as in :meth:`misfit_weighted`; ``trace_weights``: the ``ntr`` weights ``w_j >= 0`` (None: 1), the only
+        way to down-weight a trace.  A trace whose weighted data are zero does not count.  The adjoint source
+        ``dJ/dd_syn`` is formed on the device and kept there for ``adjoint(None)``.  Returns J, with ``per_trace=True``
+        ``(J, rho)`` (``fwi_misfit_correlation``; the NumPy twin is :class:`datafit.NormalizedCorrelation`)."""
+        if eps is None:
+            from .datafit import correlation_floor
+            eps = correlation_floor(d_obs)
+        d_obs = self._host(d_obs, (self._nt, self._nrec))
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        twp = None
+        if trace_weights is not None:
+            tw = np.ascontiguousarray(trace_weights, dtype=np.float64)
+            if tw.shape != (self._nrec,):
+                raise ValueError("trace_weights must hold one weight per trace, shape (%d,)" % self._nrec)
+            twp = tw.ctypes.data_as(C.c_void_p)
+        rho = np.zeros(self._nrec) if per_trace else None
+        J = C.c_double(0.0)
+        self._chk(self._lib.fwi_misfit_correlation(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, twp, float(eps),
+                                                   C.byref(J), rho.ctypes.data_as(C.c_void_p) if per_trace else None))
+        return (J.value, rho) if per_trace else J.value
+
     def residual_weight(self, weights=None, taps=None):
         """The residual on the device (what ``born`` or a misfit call left for ``adjoint(None)``) := ``B M^2 B`` residual,
         the Gauss-Newton weight of :meth:`misfit_weighted` (``fwi_residual_weight``)."""

@@ -26,6 +26,9 @@ class Shot:
     rec_spread: object = None
     point_wavelet: np.ndarray | None = None  # (nt[, nsrc points]): the wavelets before spreading
     weights: np.ndarray | None = None  # (nt, nrec) data weights >= 0 of a datafit.WeightedL2 / MatchedL2 / EnvelopeL2 objective (None: 1)
+    # (nrec,) weights >= 0 per trace of a datafit.NormalizedCorrelation objective (None: 1).  A plain attribute to assign,
+    # not a field of the constructor: `weights` stays the last one
+    trace_weights = None
 
     @classmethod
     def at_coordinates(cls, src_xyz, wavelet, rec_xyz, shape, d_obs=None):
@@ -308,6 +311,12 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     engine that has ``misfit_envelope`` forms envelopes, misfit and adjoint source on the device, otherwise the NumPy
     twin does on the host.  Either branch uses ``objective.eps_of(d_obs)`` as the shot's floor.
 
+    A :class:`datafit.NormalizedCorrelation` objective (trace-normalised correlation: phase only, blind to the gain of a
+    trace) is handed ``Shot.weights`` and ``Shot.trace_weights``; under ``device_l2`` an engine that has
+    ``misfit_correlation`` forms the per-trace sums, the misfit and its adjoint source on the device (per node, or per
+    off-grid point where the engine spreads them), otherwise the NumPy twin does on the host.  Either branch uses
+    ``objective.eps_of(d_obs)`` as the shot's floor.
+
     ``device_l2`` (least squares only): form the residual and J on the device (``fwi_misfit_l2``) -- in the
     engine's dtype, i.e. with an fp32 engine ``d_obs`` is rounded to fp32 before the subtraction, which puts
     ~6e-8 |d| / |r| of relative noise on J and on the residual (visible to a line search only once |r| / |d|
@@ -333,11 +342,12 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
 def _sweep_shots(engine, shots, ex, objective, device_l2=True):
     """forward + adjoint of this rank's shots; returns the misfit, gradients summed into the
     (primary) engine's accumulator."""
-    from .datafit import EnvelopeL2, MatchedL2, WeightedL2
+    from .datafit import EnvelopeL2, MatchedL2, NormalizedCorrelation, WeightedL2
     from .objectives import l2
     weighted = isinstance(objective, WeightedL2)
     matched = isinstance(objective, MatchedL2)
     enveloped = isinstance(objective, EnvelopeL2)
+    correlated = isinstance(objective, NormalizedCorrelation)
 
     def one(e, i):
         s = shots[i]
@@ -367,6 +377,15 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True):
             j = e.misfit_envelope(s.d_obs, objective.hilbert, objective.power, objective.eps_of(s.d_obs), s.weights,
                                   objective.taps)
             e.adjoint(None)
+            return j
+        if device_l2 and correlated and hasattr(e, "misfit_correlation") and (s.rec_spread is None or s._on_device(e)):
+            # ... and so are the per-trace sums of the normalised correlation, its misfit and its adjoint source
+            j = e.misfit_correlation(s.d_obs, objective.eps_of(s.d_obs), s.weights, objective.taps, s.trace_weights)
+            e.adjoint(None)
+            return j
+        if correlated:
+            j, r = objective(d, s.d_obs, s.weights, s.trace_weights)
+            s.adjoint(e, r)
             return j
         j, r = objective(d, s.d_obs, s.weights) if (weighted or enveloped) else objective(d, s.d_obs)
         s.adjoint(e, r)

@@ -258,6 +258,33 @@ int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const v
                         const double *taps /* R + 1, or NULL */, int32_t R, const double *hilbert /* Q: h_1 .. h_Q */,
                         int32_t Q, int32_t power, double eps, double *J_out);
 
+/* Trace-normalised zero-lag correlation misfit on the device (Choi & Alkhalifah 2012): every misfit above is a difference
+ * of amplitudes; this one reads phase only and ignores the gain of every trace, which a constant-density acoustic engine
+ * cannot model on field data.  With s = d_syn of the last forward and d = d_obs, both (nt, ntr) as above, B and M as
+ * above, w_j >= 0 optional weights per trace (NULL: 1) and eps >= 0 an absolute floor that must not depend on s:
+ *     s' = B s,  d' = B d            (rounded to the context's dtype once, only when taps are given)
+ *     sh = M . s',  dh = M . d'
+ *     a_j = sum_n sh[n,j]^2    b_j = sum_n dh[n,j]^2    c_j = sum_n sh[n,j] dh[n,j]
+ *     ns_j = sqrt(a_j + eps^2)  nd_j = sqrt(b_j + eps^2)   rho_j = c_j / (ns_j nd_j)
+ *     trace j counts iff  b_j > 0 and a_j + eps^2 > 0;  otherwise J_j = 0, rho_j = 0 and its adjoint source is 0
+ *     J = sum_j w_j (1 - rho_j)
+ *     alpha_j = -w_j / (ns_j nd_j)     beta_j = c_j / ns_j^2
+ *     g = M . alpha_j (dh - beta_j sh)           (rounded to the dtype once)
+ *     r = dJ/ds = B g
+ * A scale per trace inside M cancels: w is the only way to down-weight a trace.  *J_out = J (the sum itself, not half of
+ * it); rho_out, if not NULL, receives the ntr values rho_j; r stays on the device as the residual of the next
+ * fwi_adjoint(ctx, NULL, ...).  The synthetics are left alone: the call can be repeated.  Everything between the loads
+ * and the roundings named above is fp64; a thread adds its 8 consecutive times in ascending order, a block its four
+ * waves in wave order, a trace its time tiles in ascending order and J its traces in a fixed order, without atomics:
+ * equal inputs give equal bits.  State rules, off-grid receivers (ntr is then the number of points) and work buffers as
+ * fwi_misfit_weighted.  FWI_EINVAL: a null J_out, a null d_obs with nrec > 0, the tap errors of fwi_misfit_weighted,
+ * eps < 0 or not finite, a trace weight that is negative or not finite.  The reference's CC measure (Pearson correlation
+ * per trace, averaged) is J / ntr at eps = 0, M = 1, B = I on mean-free traces. */
+int fwi_misfit_correlation(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                           const double *taps /* R + 1, or NULL */, int32_t R,
+                           const double *trace_weights /* ntr, or NULL */, double eps, double *J_out,
+                           double *rho_out /* ntr, or NULL */);
+
 /* gradient(): copy out the accumulated gradient, model-shaped, as dJ/dc
  * (FWI_WRT_VELOCITY) or dJ/d(1/c^2) (FWI_WRT_SLOWNESS2).
  * [SURVEY s.8(a-1) row gradient] */

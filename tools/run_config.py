@@ -78,6 +78,12 @@ def main():
     ap.add_argument("--envelope-floor-percent", type=float, default=1.0, metavar="X",
                     help="floor under the envelopes per shot: X / 100 of the largest amplitude of the shot's observed data "
                          "(datafit.envelope_floor), computed once and held through the run")
+    ap.add_argument("--correlation", type=float, nargs="?", const=1.0, default=None, metavar="FLOOR_PERCENT",
+                    help="trace-normalised correlation misfit, sum over traces of 1 - the zero-lag normalised correlation of "
+                         "synthetics and data: phase only, blind to the gain of a trace (datafit.NormalizedCorrelation, on "
+                         "the device); the floor under the trace norms per shot is FLOOR_PERCENT / 100 (default 1) of the "
+                         "largest trace norm of the shot's observed data (datafit.correlation_floor); composes with --bands "
+                         "and --mute-direct, not with --envelope or --match-source")
     a = ap.parse_args()
     bands = [float(f) for f in a.bands.split(",")] if a.bands else None
     if bands and (a.iters < 1 or a.checkpoint or a.resume):
@@ -92,6 +98,10 @@ def main():
         ap.error("--match-mu-percent P must be finite and >= 0")
     if a.envelope is not None and a.match_source is not None:
         ap.error("--envelope and --match-source are two misfits: choose one")
+    if a.correlation is not None and (a.envelope is not None or a.match_source is not None):
+        ap.error("--correlation, --envelope and --match-source are different misfits: choose one")
+    if a.correlation is not None and not (a.correlation >= 0.0 and np.isfinite(a.correlation)):
+        ap.error("--correlation FLOOR_PERCENT must be finite and >= 0")
     if (a.envelope is None) != (a.hilbert_fmin is None):
         ap.error("--envelope and --hilbert-fmin go together")
     if not (a.envelope_floor_percent >= 0.0 and np.isfinite(a.envelope_floor_percent)) or (
@@ -156,6 +166,8 @@ def main():
             return datafit.MatchedL2(a.match_source, match_mu, taps)
         if a.envelope is not None:  # (the floor: a data-only number per shot, datafit.envelope_floor of its d_obs)
             return datafit.EnvelopeL2(hilbert, a.envelope, None, taps, floor_percent=a.envelope_floor_percent)
+        if a.correlation is not None:  # (the floor: a data-only number per shot, datafit.correlation_floor of its d_obs)
+            return datafit.NormalizedCorrelation(None, taps, floor_percent=a.correlation)
         return datafit.WeightedL2(taps) if (taps is not None or a.mute_direct is not None) else None
 
     def filters_line(o, band=None):
@@ -262,7 +274,8 @@ def main():
                           "mute_sources_radius": a.mute_sources, "regularize": a.regularize,
                           "reg_weight": a.reg_weight, "reg_eps": reg_eps, "reg_prior": a.reg_prior, "bands_hz": bands,
                           "band_halfwidth": a.band_halfwidth if bands else None, "mute_direct": a.mute_direct,
-                          "match_source": a.match_source, "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
+                          "match_source": a.match_source, "correlation_floor_percent": a.correlation,
+                          "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
                           "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
                           "envelope_floor_percent": a.envelope_floor_percent if a.envelope is not None else None,
                           "match_mu_percent": a.match_mu_percent if a.match_source is not None else None, "log": log}))
