@@ -24,6 +24,7 @@
 #include "fwi_born.h"
 #include "fwi_data.h"
 #include "fwi_corr.h"
+#include "fwi_ttime.h"
 #include "fwi_envelope.h"
 #include "fwi_gather_tile.h"
 #include "fwi_illum.h"
@@ -203,6 +204,10 @@ struct fwi_ctx {
     // fwi_misfit_correlation (fwi_corr.hip): the per-tile sums and the terms of J, alpha / beta / rho, the trace weights
     void *corr_part = nullptr, *corr_coef = nullptr, *corr_tw = nullptr;
     size_t cap_corr_part = 0, cap_corr_coef = 0, cap_corr_tw = 0;
+    // fwi_misfit_traveltime (fwi_ttime.hip): the partial correlations and the terms of J, tau and the three coefficients
+    // of every trace, the picked lags, the trace weights
+    void *tt_part = nullptr, *tt_coef = nullptr, *tt_lag = nullptr, *tt_tw = nullptr;
+    size_t cap_tt_part = 0, cap_tt_coef = 0, cap_tt_lag = 0, cap_tt_tw = 0;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
     enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
     int resid_pts_in = RESID_PTS_NONE;
@@ -2026,6 +2031,59 @@ struct Impl {
         return FWI_OK;
     }
 
+    // s' = B d_syn, d' = B d_obs, c_j(k) the correlation of the weighted traces M s', M d' over the lags |k| <= Ke, tau_j
+    // the delay at its refined maximum, J = 1/2 sum_j w_j tau_j^2, r = B g where the adjoint sweep reads its amplitudes
+    // (fwi_ttime.h)
+    static int misfit_traveltime(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
+                                 const double *trace_weights, int K, double *J_out, double *tau_out, int32_t *lag_out) {
+        Misfit m(ctx);
+        double J = 0.0;
+        T *g = nullptr;
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        if (m.data) {
+            const size_t np = tt_partials(m.nt, m.ntr, K);
+            if ((rc = ensure(ctx, &ctx->tt_part, &ctx->cap_tt_part, np * sizeof(double))) ||
+                (rc = ensure(ctx, &ctx->tt_coef, &ctx->cap_tt_coef, (size_t)4 * m.ntr * sizeof(double))) ||
+                (rc = ensure(ctx, &ctx->tt_lag, &ctx->cap_tt_lag, (size_t)m.ntr * sizeof(int32_t))))
+                return rc;
+            const double *tw = nullptr;
+            if (trace_weights) {
+                if ((rc = ensure(ctx, &ctx->tt_tw, &ctx->cap_tt_tw, (size_t)m.ntr * sizeof(double)))) return rc;
+                // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
+                HIPCHK(ctx, hipMemcpyAsync(ctx->tt_tw, trace_weights, (size_t)m.ntr * sizeof(double), hipMemcpyHostToDevice,
+                                           ctx->stream));
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                tw = (const double *)ctx->tt_tw;
+            }
+            double *part = (double *)ctx->tt_part, *coef = (double *)ctx->tt_coef;
+            int32_t *lag = (int32_t *)ctx->tt_lag;
+            m.sum = part + (np - 1);  // the total of the terms 1/2 w_j tau_j^2: J itself
+            const T *s1, *d1;
+            if ((rc = m.prefilter(&s1, &d1))) return rc;
+            HIPCHK(ctx, launch_tt_xcorr<T>(part, s1, d1, m.w, K, m.nt, m.ntr, ctx->stream));
+            HIPCHK(ctx, launch_tt_pick(coef, lag, part, tw, ctx->cfg.dt, K, m.nt, m.ntr, ctx->stream));
+            // g reads d' at shifted rows, and without taps adjoint_source() IS d': g goes to the spare gather buffer, and
+            // finish() filters (with taps) or copies (without) it into place
+            g = (T *)ctx->data_tmp;
+            HIPCHK(ctx, launch_tt_source<T>(g, d1, m.w, coef, lag, m.nt, m.ntr, ctx->stream));
+        }
+        if ((rc = m.finish(g, &J))) return rc;
+        if (m.data && tau_out)
+            HIPCHK(ctx, hipMemcpyAsync(tau_out, ctx->tt_coef, (size_t)m.ntr * sizeof(double), hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        if (m.data && lag_out)
+            HIPCHK(ctx, hipMemcpyAsync(lag_out, ctx->tt_lag, (size_t)m.ntr * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        if (m.data && (tau_out || lag_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (!m.data) {  // no receivers or no samples: no trace counts
+            if (tau_out) std::fill(tau_out, tau_out + m.ntr, 0.0);
+            if (lag_out) std::fill(lag_out, lag_out + m.ntr, 0);
+        }
+        *J_out = J;
+        return FWI_OK;
+    }
+
     // device residual := B M^2 B residual: per node, or per off-grid point and scattered onto the nodes again
     static int residual_weight(fwi_ctx *ctx, const T *weights, const double *taps, int R) {
         const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
@@ -2534,7 +2592,8 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"data_part", ctx->data_part}, {"data_s", ctx->data_s}, {"data_d", ctx->data_d},
                   {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f},
                   {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h},
-                  {"corr_part", ctx->corr_part}, {"corr_coef", ctx->corr_coef}, {"corr_tw", ctx->corr_tw}};
+                  {"corr_part", ctx->corr_part}, {"corr_coef", ctx->corr_coef}, {"corr_tw", ctx->corr_tw},
+                  {"tt_part", ctx->tt_part}, {"tt_coef", ctx->tt_coef}, {"tt_lag", ctx->tt_lag}, {"tt_tw", ctx->tt_tw}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2764,6 +2823,27 @@ int fwi_misfit_correlation(fwi_ctx *ctx, const void *d_obs, const void *weights,
                                                     trace_weights, eps, J_out, rho_out),
                     Impl<double>::misfit_correlation(ctx, (const double *)d_obs, (const double *)weights, taps, R,
                                                      trace_weights, eps, J_out, rho_out));
+}
+
+int fwi_misfit_traveltime(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
+                          const double *trace_weights, int32_t max_lag, double *J_out, double *tau_out, int32_t *lag_out) {
+    if (int rc = misfit_callable(ctx, "fwi_misfit_traveltime", d_obs, J_out)) return rc;
+    if (int rc = data_args(ctx, "fwi_misfit_traveltime", taps, R)) return rc;
+    if (max_lag < 1 || max_lag > FWI_TT_KMAX)
+        return ctx->fail(FWI_EINVAL, "fwi_misfit_traveltime: max_lag=%d outside [1, %d]", (int)max_lag, FWI_TT_KMAX);
+    if (trace_weights && ctx->nrec) {
+        const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
+        for (int j = 0; j < ntr; ++j)
+            if (!(trace_weights[j] >= 0.0) || !std::isfinite(trace_weights[j]))
+                return ctx->fail(FWI_EINVAL, "fwi_misfit_traveltime: trace_weights[%d]=%g must be finite and >= 0", j,
+                                 trace_weights[j]);
+    }
+    if (int rc = misfit_synthetics(ctx, "fwi_misfit_traveltime", "or fwi_born ")) return rc;
+    return DISPATCH(ctx,
+                    Impl<float>::misfit_traveltime(ctx, (const float *)d_obs, (const float *)weights, taps, R,
+                                                   trace_weights, max_lag, J_out, tau_out, lag_out),
+                    Impl<double>::misfit_traveltime(ctx, (const double *)d_obs, (const double *)weights, taps, R,
+                                                    trace_weights, max_lag, J_out, tau_out, lag_out));
 }
 
 int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {

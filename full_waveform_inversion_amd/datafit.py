@@ -74,6 +74,30 @@ A scale per trace inside ``M`` cancels, so ``w`` is the only way to down-weight 
 floor, ``eps`` must not follow ``s``: :func:`correlation_floor` is a data-only choice.  With ``eps = 0``, no weights, no
 taps and mean-free traces, ``J / ntr`` and ``r / ntr`` are ``objectives.correlation(per_trace=True)``.  There is no
 Gauss-Newton weight of the form ``B M^2 B``: :class:`NormalizedCorrelation` is not a :class:`WeightedL2`.
+
+Cross-correlation traveltime misfit, :class:`TraveltimeL2` (``Engine.misfit_traveltime``, ``fwi_misfit_traveltime``,
+``csrc/fwi_ttime.hip``): every misfit above compares the data at zero lag; none measures how late an arrival is, which
+is what a poor starting model gets wrong first (Luo & Schuster 1991; the traveltime adjoint source of Tromp et al. 2005).
+It grows with the square of the time shift however many periods the shift spans, ignores each trace's gain and returns a
+physical number per trace, the delay in seconds.  With ``s = d_syn``, ``d = d_obs``, ``B``, ``M`` and ``w_j`` as above,
+``K = max_lag >= 1`` in samples, ``Ke = min(K, nt - 1)`` and ``dt`` the sampling interval:
+
+    s' = B s,  d' = B d            (rounded to the context dtype once, only when taps are given)
+    sh = M . s',  dh = M . d'
+    c_j(k) = sum_n sh[n + k, j] dh[n, j],   k = -Ke .. Ke       (terms with n + k outside [0, nt) omitted)
+    k*_j = the smallest k with c_j(k) = max_k c_j(k)
+    c-, c0, c+ = c_j(k* - 1), c_j(k*), c_j(k* + 1);   N = c- - c+,   Q = c- - 2 c0 + c+
+    trace j counts iff  |k*| < Ke, c0 > 0 and Q < 0;  otherwise tau_j = 0, J_j = 0 and its adjoint source is 0
+    delta_j = N / (2 Q) in [-1/2, 1/2],   tau_j = (k* + delta_j) dt,   J = 1/2 sum_j w_j tau_j^2        (s^2)
+    D- = (Q - N) / (2 Q^2),  D0 = N / Q^2,  D+ = (-Q - N) / (2 Q^2)
+    g[m, j] = M[m, j] w_j tau_j dt (D- dh[m - k* + 1, j] + D0 dh[m - k*, j] + D+ dh[m - k* - 1, j])
+    r = dJ/ds = B g                (g rounded to the dtype once; rows outside [0, nt) contribute 0)
+
+``tau > 0`` means the synthetics arrive late: for ``s(t) = d(t - tau)``, ``c`` peaks at ``+tau``.  A dead trace has
+``c = 0`` everywhere, so ``k* = -Ke`` and it does not count; neither does a trace shifted beyond the window.  The picked
+lag is locally constant and ``c`` is linear in ``sh``, so ``r`` is the exact gradient of this discrete ``J``.  ``J`` is
+not differentiable where a trace starts or stops counting; ``tau`` is continuous where ``k*`` moves between neighbouring
+lags (both parabolas then give ``delta = -+1/2`` at the same point).  No linear Gauss-Newton weight either.
 """
 from __future__ import annotations
 
@@ -83,6 +107,7 @@ import numpy as np
 
 R_MAX = 4096  # the largest half-width the device path accepts (fwi_misfit_weighted)
 L_MAX = 64    # the largest half-length of a matching filter the device path accepts (fwi_misfit_matched)
+K_MAX = 1024  # the largest window of lags, in samples, the device path accepts (fwi_misfit_traveltime)
 
 
 def _lowpass_raw(dt, f, R):
@@ -527,6 +552,114 @@ class NormalizedCorrelation:
             g = np.asarray(weights, np.float64) * g
         g = self._round(g)
         return float(np.sum(np.where(counts, w * (1.0 - rho), 0.0))), (g if self.taps is None else fir_time(g, self.taps))
+
+
+class TraveltimeL2:
+    """The cross-correlation traveltime misfit of the module's definition in fp64 NumPy,
+    ``objective(d_syn, d_obs, weights=None, trace_weights=None) -> (J, r)``, and the ``objective=`` that
+    ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_traveltime`` replaces it by the device path;
+    the shot loop hands it ``Shot.weights`` and ``Shot.trace_weights``).
+
+    ``dt``: the sampling interval in seconds.  ``max_lag``: the half-width ``K`` of the window of lags in samples,
+    ``1 .. K_MAX``.  ``taps``: the one-sided ``b_0 .. b_R`` of ``B``, or None.  ``dtype``: round ``B s``, ``B d`` (with taps)
+    and ``g`` to it once each, as a device context of that dtype does (None: keep fp64).
+
+    ``delays`` holds the ``tau_j`` of the last call in seconds (0 where a trace does not count), ``lags`` the picked
+    ``k*_j`` (counting or not) and ``counts`` which traces count.  ``J`` is not differentiable where a trace starts or
+    stops counting; ``tau`` is continuous where ``k*`` moves between neighbouring lags.  Not a :class:`WeightedL2`: there
+    is no linear Gauss-Newton weight, and ``gauss_newton_hvp`` refuses it."""
+
+    def __init__(self, dt, max_lag, taps=None, dtype=None):
+        if not (float(dt) > 0.0 and np.isfinite(dt)):
+            raise ValueError("dt must be > 0")
+        if int(max_lag) != max_lag or not 1 <= int(max_lag) <= K_MAX:
+            raise ValueError("max_lag must be an integer number of samples in [1, %d]" % K_MAX)
+        self.dt = float(dt)
+        self.max_lag = int(max_lag)
+        self.taps = _checked_taps(taps)
+        self.dtype = None if dtype is None else np.dtype(dtype)
+        self.delays = self.lags = self.counts = None
+
+    def _round(self, x):
+        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+
+    def filter(self, x):
+        """``B x`` (rounded to ``dtype`` once; without taps a copy of x)"""
+        return fir_time(x, None) if self.taps is None else self._round(fir_time(x, self.taps))
+
+    def correlations(self, d_syn, d_obs, weights=None, majorants=True):
+        """``(c, A, sh, dh)``: ``c[k + Ke, j] = c_j(k)`` of the definition for ``k = -Ke .. Ke``, its majorant
+        ``A[k + Ke, j] = sum_n |sh[n + k, j]| |dh[n, j]|`` (None without ``majorants``) and the weighted, filtered
+        gathers"""
+        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
+        if s.ndim != 2 or s.shape != d.shape:
+            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
+        M = WeightedL2._weights(weights, s.shape)
+        sh, dh = self.filter(s), self.filter(d)
+        if M is not None:
+            sh, dh = M * sh, M * dh
+        nt, ntr = s.shape
+        Ke = max(min(self.max_lag, nt - 1), 0)
+        c, A = np.zeros((2 * Ke + 1, ntr)), (np.zeros((2 * Ke + 1, ntr)) if majorants else None)
+        ash, adh = (np.abs(sh), np.abs(dh)) if majorants else (None, None)
+        for k in range(-Ke, Ke + 1):
+            a, b = (slice(k, nt), slice(0, nt - k)) if k >= 0 else (slice(0, nt + k), slice(-k, nt))
+            c[k + Ke] = np.sum(sh[a] * dh[b], axis=0)
+            if majorants:
+                A[k + Ke] = np.sum(ash[a] * adh[b], axis=0)
+        return c, A, sh, dh
+
+    def pick(self, c, trace_weights=None):
+        """``(lags, counts, tau, coef, w)`` from ``c``: ``coef[i + 1, j] = w_j tau_j dt D_i`` for ``i = -1, 0, 1``, with
+        ``(c-, c0, c+)`` stacked behind them in ``coef[3:6]``, and the trace weights as used"""
+        nlag, ntr = c.shape
+        Ke = (nlag - 1) // 2
+        w = np.ones(ntr)
+        if trace_weights is not None:
+            w = np.asarray(trace_weights, np.float64)
+            if w.shape != (ntr,):
+                raise ValueError("trace_weights have shape %r, the data %d traces" % (w.shape, ntr))
+            if not np.all(np.isfinite(w)) or np.any(w < 0.0):
+                raise ValueError("trace_weights must be finite and >= 0")
+        if ntr == 0:
+            return np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0), np.zeros((6, 0)), w
+        q = np.argmax(c, axis=0)  # the first maximum
+        j = np.arange(ntr)
+        inside = (q > 0) & (q < nlag - 1)
+        qs = np.where(inside, q, 1 if nlag >= 3 else 0)
+        cm = np.where(inside, c[np.maximum(qs - 1, 0), j], 0.0)
+        c0 = c[q, j]
+        cp = np.where(inside, c[np.minimum(qs + 1, nlag - 1), j], 0.0)
+        N, Q = cm - cp, cm - 2.0 * c0 + cp
+        counts = inside & (c0 > 0.0) & (Q < 0.0)
+        Qs = np.where(counts, Q, 1.0)
+        tau = np.where(counts, ((q - Ke).astype(np.float64) + N / (2.0 * Qs)) * self.dt, 0.0)
+        a, q2 = w * tau * self.dt, Qs * Qs
+        coef = np.zeros((6, ntr))
+        coef[0] = np.where(counts, a * ((Q - N) / (2.0 * q2)), 0.0)
+        coef[1] = np.where(counts, a * (N / q2), 0.0)
+        coef[2] = np.where(counts, a * ((-Q - N) / (2.0 * q2)), 0.0)
+        coef[3], coef[4], coef[5] = cm, c0, cp
+        return (q - Ke).astype(np.int32), counts, tau, coef, w
+
+    def __call__(self, d_syn, d_obs, weights=None, trace_weights=None):
+        c, _, _, dh = self.correlations(d_syn, d_obs, weights, majorants=False)
+        nt, ntr = dh.shape
+        lags, counts, tau, coef, w = self.pick(c, trace_weights)
+        self.lags, self.counts, self.delays = lags, counts, tau
+        # dh at the rows m - k* + 1, m - k*, m - k* - 1; rows outside [0, nt) contribute 0
+        g = np.zeros((nt, ntr))
+        if nt and ntr:
+            m = np.arange(nt)[:, None]
+            for i, off in enumerate((1, 0, -1)):
+                rows = m - lags[None, :].astype(np.int64) + off
+                ok = (rows >= 0) & (rows < nt)
+                g += coef[i] * np.where(ok, np.take_along_axis(dh, np.clip(rows, 0, nt - 1), axis=0), 0.0)
+        if weights is not None:
+            g = np.asarray(weights, np.float64) * g
+        g = self._round(g)
+        J = float(np.sum(np.where(counts, 0.5 * w * (tau * tau), 0.0)))
+        return J, (g if self.taps is None else fir_time(g, self.taps))
 
 
 def matched_wavelet(wavelet, f):

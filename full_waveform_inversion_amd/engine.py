@@ -334,6 +334,36 @@ class Engine:
                                                    C.byref(J), rho.ctypes.data_as(C.c_void_p) if per_trace else None))
         return (J.value, rho) if per_trace else J.value
 
+    def misfit_traveltime(self, d_obs, max_lag, weights=None, taps=None, trace_weights=None, per_trace=False):
+        """Cross-correlation traveltime misfit of the last forward's seismograms, which measures how late every trace is:
+        with ``sh = M . B d_syn``, ``dh = M . B d_obs`` and ``c_j(k) = sum_n sh[n + k, j] dh[n, j]`` over the lags
+        ``|k| <= min(max_lag, nt - 1)``, ``tau_j`` is ``dt`` times the lag of the first maximum of ``c_j``, refined by the
+        parabola through it and its two neighbours, and ``J = 1/2 sum_j w_j tau_j^2`` (s^2).  ``tau_j > 0``: the
+        synthetics arrive late.  ``max_lag`` is in samples, ``1 .. 1024``.  A trace counts only if its maximum is positive,
+        lies strictly inside the window and is a proper peak; otherwise its delay, its term of J and its adjoint source
+        are 0 (a dead trace; a shift beyond the window).  ``weights`` and ``taps`` as in :meth:`misfit_weighted`,
+        ``trace_weights`` as in :meth:`misfit_correlation`.  The adjoint source ``dJ/dd_syn`` is formed on the device and
+        kept there for ``adjoint(None)``.  Returns J, with ``per_trace=True`` ``(J, tau, lag)``: the ``ntr`` delays in
+        seconds and the picked lags ``k*`` of every trace, counting or not (``fwi_misfit_traveltime``; the NumPy twin is
+        :class:`datafit.TraveltimeL2`)."""
+        d_obs = self._host(d_obs, (self._nt, self._nrec))
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        if int(max_lag) != max_lag:
+            raise ValueError("max_lag must be an integer number of samples")
+        twp = None
+        if trace_weights is not None:
+            tw = np.ascontiguousarray(trace_weights, dtype=np.float64)
+            if tw.shape != (self._nrec,):
+                raise ValueError("trace_weights must hold one weight per trace, shape (%d,)" % self._nrec)
+            twp = tw.ctypes.data_as(C.c_void_p)
+        tau = np.zeros(self._nrec) if per_trace else None
+        lag = np.zeros(self._nrec, np.int32) if per_trace else None
+        J = C.c_double(0.0)
+        self._chk(self._lib.fwi_misfit_traveltime(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, twp, int(max_lag),
+                                                  C.byref(J), tau.ctypes.data_as(C.c_void_p) if per_trace else None,
+                                                  lag.ctypes.data_as(C.c_void_p) if per_trace else None))
+        return (J.value, tau, lag) if per_trace else J.value
+
     def residual_weight(self, weights=None, taps=None):
         """The residual on the device (what ``born`` or a misfit call left for ``adjoint(None)``) := ``B M^2 B`` residual,
         the Gauss-Newton weight of :meth:`misfit_weighted` (``fwi_residual_weight``)."""

@@ -285,6 +285,40 @@ int fwi_misfit_correlation(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, cons
                            const double *trace_weights /* ntr, or NULL */, double eps, double *J_out,
                            double *rho_out /* ntr, or NULL */);
 
+/* Cross-correlation traveltime misfit on the device (Luo & Schuster 1991; the traveltime adjoint source of Tromp et al.
+ * 2005): every misfit above compares the data at zero lag; this one measures HOW LATE each trace is, grows with the
+ * square of the time shift however many periods the shift spans, and ignores the gain of every trace.  With s = d_syn of
+ * the last forward and d = d_obs, both (nt, ntr) as above, B and M as above, w_j >= 0 optional weights per trace (NULL:
+ * 1), K = max_lag >= 1 in samples, Ke = min(K, nt - 1) and dt the context's time step:
+ *     s' = B s,  d' = B d            (rounded to the context's dtype once, only when taps are given)
+ *     sh = M . s',  dh = M . d'
+ *     c_j(k) = sum_n sh[n + k, j] dh[n, j],   k = -Ke .. Ke       (terms with n + k outside [0, nt) omitted)
+ *     k*_j = the smallest k with c_j(k) = max_k c_j(k)
+ *     c-, c0, c+ = c_j(k* - 1), c_j(k*), c_j(k* + 1);   N = c- - c+,   Q = c- - 2 c0 + c+
+ *     trace j counts iff  |k*| < Ke, c0 > 0 and Q < 0;  otherwise tau_j = 0, J_j = 0 and its adjoint source is 0
+ *     delta_j = N / (2 Q) in [-1/2, 1/2],   tau_j = (k* + delta_j) dt,   J = 1/2 sum_j w_j tau_j^2     (s^2)
+ *     D- = (Q - N) / (2 Q^2),  D0 = N / Q^2,  D+ = (-Q - N) / (2 Q^2)
+ *     g[m, j] = M[m, j] w_j tau_j dt (D- dh[m - k* + 1, j] + D0 dh[m - k*, j] + D+ dh[m - k* - 1, j])
+ *     r = dJ/ds = B g                (g rounded to the dtype once; rows outside [0, nt) contribute 0)
+ * tau > 0: the synthetics arrive late (for s(t) = d(t - tau), c peaks at +tau).  A dead trace has c = 0 everywhere, picks
+ * k* = -Ke and does not count; neither does a trace whose shift lies beyond the window (|k*| = Ke).  r is the exact
+ * gradient of this discrete J (the picked lag is locally constant, c is linear in sh).  J is NOT differentiable where a
+ * trace starts or stops counting; tau is continuous where k* moves between neighbouring lags.  *J_out = J; tau_out, if
+ * not NULL, receives the ntr delays in seconds (0 where a trace does not count), lag_out, if not NULL, the ntr picked
+ * lags k* (counting or not); r stays on the device as the residual of the next fwi_adjoint(ctx, NULL, ...).  The
+ * synthetics are left alone: the call can be repeated.  Everything between the loads and the roundings named above is
+ * fp64; c_j(k) is added by fma over ascending time within a time slice and over the slices in ascending order, the
+ * number of slices a function of (nt, ntr, Ke) only, the lags are scanned in ascending order and J adds its traces in a
+ * fixed order, without atomics: equal inputs give equal bits.  State rules, off-grid receivers (ntr is then the number of
+ * points) and work buffers as fwi_misfit_weighted.  FWI_EINVAL: a null J_out, a null d_obs with nrec > 0, the tap errors
+ * of fwi_misfit_weighted, max_lag < 1 or > FWI_TT_KMAX, a trace weight that is negative or not finite.  No receivers:
+ * J = 0 and nothing is launched; nt = 1: Ke = 0, no trace counts, J = 0 and r = 0. */
+#define FWI_TT_KMAX 1024
+int fwi_misfit_traveltime(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                          const double *taps /* R + 1, or NULL */, int32_t R,
+                          const double *trace_weights /* ntr, or NULL */, int32_t max_lag, double *J_out,
+                          double *tau_out /* ntr, or NULL */, int32_t *lag_out /* ntr, or NULL: k*, counting or not */);
+
 /* gradient(): copy out the accumulated gradient, model-shaped, as dJ/dc
  * (FWI_WRT_VELOCITY) or dJ/d(1/c^2) (FWI_WRT_SLOWNESS2).
  * [SURVEY s.8(a-1) row gradient] */

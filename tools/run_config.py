@@ -84,6 +84,12 @@ def main():
                          "the device); the floor under the trace norms per shot is FLOOR_PERCENT / 100 (default 1) of the "
                          "largest trace norm of the shot's observed data (datafit.correlation_floor); composes with --bands "
                          "and --mute-direct, not with --envelope or --match-source")
+    ap.add_argument("--traveltime", type=int, default=None, metavar="MAX_LAG",
+                    help="cross-correlation traveltime misfit, 1/2 the sum over traces of the squared delay at which the "
+                         "correlation of synthetics and data over the lags |k| <= MAX_LAG samples peaks: grows with the "
+                         "square of the time shift over any number of periods, blind to the gain of a trace "
+                         "(datafit.TraveltimeL2, on the device); composes with --bands and --mute-direct, not with "
+                         "--correlation, --envelope or --match-source")
     a = ap.parse_args()
     bands = [float(f) for f in a.bands.split(",")] if a.bands else None
     if bands and (a.iters < 1 or a.checkpoint or a.resume):
@@ -100,6 +106,10 @@ def main():
         ap.error("--envelope and --match-source are two misfits: choose one")
     if a.correlation is not None and (a.envelope is not None or a.match_source is not None):
         ap.error("--correlation, --envelope and --match-source are different misfits: choose one")
+    if a.traveltime is not None and (a.correlation is not None or a.envelope is not None or a.match_source is not None):
+        ap.error("--traveltime, --correlation, --envelope and --match-source are different misfits: choose one")
+    if a.traveltime is not None and not 1 <= a.traveltime <= datafit.K_MAX:
+        ap.error("--traveltime MAX_LAG must lie in [1, %d] samples" % datafit.K_MAX)
     if a.correlation is not None and not (a.correlation >= 0.0 and np.isfinite(a.correlation)):
         ap.error("--correlation FLOOR_PERCENT must be finite and >= 0")
     if (a.envelope is None) != (a.hilbert_fmin is None):
@@ -168,6 +178,8 @@ def main():
             return datafit.EnvelopeL2(hilbert, a.envelope, None, taps, floor_percent=a.envelope_floor_percent)
         if a.correlation is not None:  # (the floor: a data-only number per shot, datafit.correlation_floor of its d_obs)
             return datafit.NormalizedCorrelation(None, taps, floor_percent=a.correlation)
+        if a.traveltime is not None:
+            return datafit.TraveltimeL2(w.dt, a.traveltime, taps)
         return datafit.WeightedL2(taps) if (taps is not None or a.mute_direct is not None) else None
 
     def filters_line(o, band=None):
@@ -275,6 +287,7 @@ def main():
                           "reg_weight": a.reg_weight, "reg_eps": reg_eps, "reg_prior": a.reg_prior, "bands_hz": bands,
                           "band_halfwidth": a.band_halfwidth if bands else None, "mute_direct": a.mute_direct,
                           "match_source": a.match_source, "correlation_floor_percent": a.correlation,
+                          "traveltime_max_lag": a.traveltime,
                           "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
                           "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
                           "envelope_floor_percent": a.envelope_floor_percent if a.envelope is not None else None,
