@@ -27,6 +27,7 @@ BORN_MODES = {"auto": 0, "scatter": 1, "fused": 2}
 REG_KINDS = {"tikhonov": 0, "tv": 1}
 MATCH_LMAX = 64  # FWI_MATCH_LMAX
 TT_KMAX = 1024  # FWI_TT_KMAX
+OT_TRANSFORMS = {"linear": 0, "softplus": 1}  # FWI_OT_LINEAR, FWI_OT_SOFTPLUS
 UNIQUE_ID_BYTES = 128
 EINVAL = 1
 ERROR_NAMES = {1: "FWI_EINVAL", 2: "FWI_EHIP", 3: "FWI_ESTATE", 4: "FWI_ENOMEM", 5: "FWI_ECOMM"}
@@ -69,6 +70,7 @@ SIGNATURES = {
     "fwi_misfit_envelope": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _I32, _D, C.POINTER(_D)]),
     "fwi_misfit_correlation": (C.c_int, [_P, _P, _P, _P, _I32, _P, _D, C.POINTER(_D), _P]),
     "fwi_misfit_traveltime": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, C.POINTER(_D), _P, _P]),
+    "fwi_misfit_transport": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _D, C.POINTER(_D), _P, _P]),
     "fwi_gradient": (C.c_int, [_P, _I32, _P]),
     "fwi_gradient_reset": (C.c_int, [_P]),
     "fwi_gradient_add": (C.c_int, [_P, _P]),

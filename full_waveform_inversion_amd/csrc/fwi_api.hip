@@ -24,6 +24,7 @@
 #include "fwi_born.h"
 #include "fwi_data.h"
 #include "fwi_corr.h"
+#include "fwi_ot.h"
 #include "fwi_ttime.h"
 #include "fwi_envelope.h"
 #include "fwi_gather_tile.h"
@@ -208,6 +209,10 @@ struct fwi_ctx {
     // of every trace, the picked lags, the trace weights
     void *tt_part = nullptr, *tt_coef = nullptr, *tt_lag = nullptr, *tt_tw = nullptr;
     size_t cap_tt_part = 0, cap_tt_coef = 0, cap_tt_lag = 0, cap_tt_tw = 0;
+    // fwi_misfit_transport (fwi_ot.hip): densities, CDFs, potentials and every sum (ot_work_doubles), which traces count,
+    // the trace weights
+    void *ot_work = nullptr, *ot_counts = nullptr, *ot_tw = nullptr;
+    size_t cap_ot_work = 0, cap_ot_counts = 0, cap_ot_tw = 0;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
     enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
     int resid_pts_in = RESID_PTS_NONE;
@@ -2084,6 +2089,54 @@ struct Impl {
         return FWI_OK;
     }
 
+    // s' = B d_syn, d' = B d_obs, W_j the squared 2-Wasserstein distance between the weighted traces M s', M d' made
+    // positive and normalised to densities along time, J = 1/2 sum_j w_j W_j, r = B g where the adjoint sweep reads its
+    // amplitudes (fwi_ot.h)
+    static int misfit_transport(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
+                                const double *trace_weights, int transform, double param, double *J_out, double *w2_out,
+                                int32_t *counts_out) {
+        Misfit m(ctx);
+        double J = 0.0;
+        T *g = nullptr;
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        if (m.data) {
+            if ((rc = ensure(ctx, &ctx->ot_work, &ctx->cap_ot_work, ot_work_doubles(m.nt, m.ntr) * sizeof(double))) ||
+                (rc = ensure(ctx, &ctx->ot_counts, &ctx->cap_ot_counts, (size_t)m.ntr * sizeof(int32_t))))
+                return rc;
+            const double *tw = nullptr;
+            if (trace_weights) {
+                if ((rc = ensure(ctx, &ctx->ot_tw, &ctx->cap_ot_tw, (size_t)m.ntr * sizeof(double)))) return rc;
+                // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
+                HIPCHK(ctx, hipMemcpyAsync(ctx->ot_tw, trace_weights, (size_t)m.ntr * sizeof(double), hipMemcpyHostToDevice,
+                                           ctx->stream));
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                tw = (const double *)ctx->ot_tw;
+            }
+            double *work = (double *)ctx->ot_work;
+            m.sum = work + ot_total_at(m.nt, m.ntr);  // the total of the terms 1/2 w_j W_j: J itself
+            const T *s1, *d1;
+            if ((rc = m.prefilter(&s1, &d1))) return rc;
+            g = m.adjoint_source();  // in place of s' (with taps) or of d_obs (without): elementwise, written last
+            HIPCHK(ctx, launch_ot_misfit<T>(work, (int32_t *)ctx->ot_counts, g, s1, d1, m.w, tw, transform, param,
+                                            ctx->cfg.dt, m.nt, m.ntr, ctx->stream));
+        }
+        if ((rc = m.finish(g, &J))) return rc;
+        if (m.data && w2_out)
+            HIPCHK(ctx, hipMemcpyAsync(w2_out, (const double *)ctx->ot_work + ot_w2_at(m.nt, m.ntr),
+                                       (size_t)m.ntr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (m.data && counts_out)
+            HIPCHK(ctx, hipMemcpyAsync(counts_out, ctx->ot_counts, (size_t)m.ntr * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        if (m.data && (w2_out || counts_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (!m.data) {  // no receivers or no samples: no trace counts
+            if (w2_out) std::fill(w2_out, w2_out + m.ntr, 0.0);
+            if (counts_out) std::fill(counts_out, counts_out + m.ntr, 0);
+        }
+        *J_out = J;
+        return FWI_OK;
+    }
+
     // device residual := B M^2 B residual: per node, or per off-grid point and scattered onto the nodes again
     static int residual_weight(fwi_ctx *ctx, const T *weights, const double *taps, int R) {
         const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
@@ -2593,7 +2646,8 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f},
                   {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h},
                   {"corr_part", ctx->corr_part}, {"corr_coef", ctx->corr_coef}, {"corr_tw", ctx->corr_tw},
-                  {"tt_part", ctx->tt_part}, {"tt_coef", ctx->tt_coef}, {"tt_lag", ctx->tt_lag}, {"tt_tw", ctx->tt_tw}};
+                  {"tt_part", ctx->tt_part}, {"tt_coef", ctx->tt_coef}, {"tt_lag", ctx->tt_lag}, {"tt_tw", ctx->tt_tw},
+                  {"ot_work", ctx->ot_work}, {"ot_counts", ctx->ot_counts}, {"ot_tw", ctx->ot_tw}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2844,6 +2898,31 @@ int fwi_misfit_traveltime(fwi_ctx *ctx, const void *d_obs, const void *weights, 
                                                    trace_weights, max_lag, J_out, tau_out, lag_out),
                     Impl<double>::misfit_traveltime(ctx, (const double *)d_obs, (const double *)weights, taps, R,
                                                     trace_weights, max_lag, J_out, tau_out, lag_out));
+}
+
+int fwi_misfit_transport(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
+                         const double *trace_weights, int32_t transform, double param, double *J_out, double *w2_out,
+                         int32_t *counts_out) {
+    if (int rc = misfit_callable(ctx, "fwi_misfit_transport", d_obs, J_out)) return rc;
+    if (int rc = data_args(ctx, "fwi_misfit_transport", taps, R)) return rc;
+    if (transform != FWI_OT_LINEAR && transform != FWI_OT_SOFTPLUS)
+        return ctx->fail(FWI_EINVAL, "fwi_misfit_transport: transform=%d is neither FWI_OT_LINEAR nor FWI_OT_SOFTPLUS",
+                         (int)transform);
+    if (!(param > 0.0) || !std::isfinite(param))
+        return ctx->fail(FWI_EINVAL, "fwi_misfit_transport: param=%g must be finite and > 0", param);
+    if (trace_weights && ctx->nrec) {
+        const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
+        for (int j = 0; j < ntr; ++j)
+            if (!(trace_weights[j] >= 0.0) || !std::isfinite(trace_weights[j]))
+                return ctx->fail(FWI_EINVAL, "fwi_misfit_transport: trace_weights[%d]=%g must be finite and >= 0", j,
+                                 trace_weights[j]);
+    }
+    if (int rc = misfit_synthetics(ctx, "fwi_misfit_transport", "or fwi_born ")) return rc;
+    return DISPATCH(ctx,
+                    Impl<float>::misfit_transport(ctx, (const float *)d_obs, (const float *)weights, taps, R,
+                                                  trace_weights, transform, param, J_out, w2_out, counts_out),
+                    Impl<double>::misfit_transport(ctx, (const double *)d_obs, (const double *)weights, taps, R,
+                                                   trace_weights, transform, param, J_out, w2_out, counts_out));
 }
 
 int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {

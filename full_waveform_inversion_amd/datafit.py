@@ -98,6 +98,39 @@ physical number per trace, the delay in seconds.  With ``s = d_syn``, ``d = d_ob
 lag is locally constant and ``c`` is linear in ``sh``, so ``r`` is the exact gradient of this discrete ``J``.  ``J`` is
 not differentiable where a trace starts or stops counting; ``tau`` is continuous where ``k*`` moves between neighbouring
 lags (both parabolas then give ``delta = -+1/2`` at the same point).  No linear Gauss-Newton weight either.
+
+Trace-by-trace optimal-transport misfit, :class:`TransportW2` (``Engine.misfit_transport``, ``fwi_misfit_transport``,
+``csrc/fwi_ot.hip``): the envelope widens the basin by throwing the phase away, the traveltime misfit by reducing a trace
+to one picked number.  The quadratic Wasserstein distance between the traces as densities along time (Engquist & Froese
+2014; Yang, Engquist, Sun & Hamfeldt 2018) uses the whole trace, needs no pick and no window, and grows with the square
+of a time shift however many periods the shift spans.  With ``s = d_syn``, ``d = d_obs``, ``B``, ``M``, ``w_j`` and
+``dt`` as above and ``P`` a map onto positive numbers (below), per trace ``j``:
+
+    s' = B s,  d' = B d            (rounded to the context dtype once, only when taps are given)
+    sh = M . s',  dh = M . d'
+    p_n = P(sh[n, j]),  q_n = P(dh[n, j])
+    S_s = sum_n p_n,  S_d = sum_n q_n;   f_n = p_n / S_s,  g_n = q_n / S_d
+    F_n = sum_{i<=n} f_i,  G_n = sum_{i<=n} g_i                      n = 0 .. nt - 1
+    for n = 1 .. nt - 1, with the level y = F_{n-1}:
+        m+(n) = min(#{m : G_m <= y}, nt - 1),   m-(n) = min(#{m : G_m < y}, nt - 1)
+        a_n = 2 n - 1 - m+(n) - m-(n)                                an integer
+      and the same with f and g exchanged: n+(m), n-(m), b_m = 2 m - 1 - n+(m) - n-(m)
+    phi_0 = psi_0 = 0,  phi_n = sum_{i=1..n} a_i,  psi_m = sum_{i=1..m} b_i     integers, exact
+    W_j = dt^2 (sum_n phi_n f_n + sum_m psi_m g_m)                   (s^2)
+    J = 1/2 sum_j w_j W_j
+    phibar_j = sum_n phi_n f_n
+    g[n, j] = M[n, j] (w_j / 2) dt^2 (phi_n - phibar_j) / S_s  P'(sh[n, j])      (rounded to the dtype once)
+    r = dJ/ds = B g
+
+``W_j`` is the exact squared 2-Wasserstein distance between the atomic measures ``sum f_n delta(t_n)`` and
+``sum g_n delta(t_n)``, ``(phi, psi) dt^2`` an optimal pair of Kantorovich potentials, and ``r`` the gradient of this
+discrete ``J`` wherever no level ``F_n`` equals a level ``G_m``.  ``J`` is piecewise smooth: the gradient jumps where a
+level of ``F`` crosses a level of ``G``; at a tie the two-sided count ``m+ + m-`` selects the midpoint subgradient, so
+that ``d_obs == d_syn`` gives ``phi = psi = 0``, ``J = 0`` and ``r = 0`` exactly.  ``P`` is ``x + c`` (``linear``,
+``c = param > 0``) or ``log(1 + exp(b x)) / b`` (``softplus``, ``b = param > 0``); like ``eps`` above, ``param`` is
+absolute and must not follow ``s``.  A trace counts iff every ``p_n`` and ``q_n`` is finite and ``>= 0`` and both sums
+are finite and ``> 0``; otherwise ``W_j = 0``, its term of ``J`` is 0 and its adjoint source is 0 (under ``linear`` a
+trace that goes below ``-c`` drops out).  No linear Gauss-Newton weight either.
 """
 from __future__ import annotations
 
@@ -660,6 +693,154 @@ class TraveltimeL2:
         g = self._round(g)
         J = float(np.sum(np.where(counts, 0.5 * w * (tau * tau), 0.0)))
         return J, (g if self.taps is None else fir_time(g, self.taps))
+
+
+OT_TRANSFORMS = {"linear": 0, "softplus": 1}  # FWI_OT_LINEAR, FWI_OT_SOFTPLUS
+
+
+class TransportW2:
+    """The trace-by-trace optimal-transport (W2) misfit of the module's definition in fp64 NumPy,
+    ``objective(d_syn, d_obs, weights=None, trace_weights=None) -> (J, r)``, and the ``objective=`` that
+    ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_transport`` replaces it by the device path; the
+    shot loop hands it ``Shot.weights`` and ``Shot.trace_weights``).
+
+    ``dt``: the sampling interval in seconds.  ``transform``: ``"softplus"`` or ``"linear"``.  ``param``: the absolute
+    ``b`` or ``c`` of the transform, ``> 0``; None: :meth:`param_of` of each call's ``d_obs``, a data-only number,
+    ``b = sharpness / max|d_obs|`` or ``c = factor * max|d_obs|``.  The defaults ``sharpness = 4`` and ``factor = 10``
+    keep ``W`` strictly increasing with the shift of a Ricker wavelet through 60 samples (a sharpness
+    of 2 or a factor of 3 and less do not; the linear transform is nearly flat beyond 30 samples even so, and a factor
+    below 1 lets the observed data themselves violate positivity).  ``taps``: the one-sided ``b_0 .. b_R`` of ``B``, or
+    None.  ``dtype``: round ``B s``, ``B d`` (with taps) and ``g`` to it once each, as a device context of that dtype
+    does (None: keep fp64).
+
+    ``distances`` holds the ``W_j`` of the last call in s^2 (0 where a trace does not count) and ``counts`` which traces
+    count.  ``J`` is piecewise smooth: its gradient jumps where a level of ``F`` crosses a level of ``G``.  Not a
+    :class:`WeightedL2`: there is no linear Gauss-Newton weight, and ``gauss_newton_hvp`` refuses it."""
+
+    def __init__(self, dt, transform="softplus", param=None, taps=None, dtype=None, sharpness=4.0, factor=10.0):
+        if not (float(dt) > 0.0 and np.isfinite(dt)):
+            raise ValueError("dt must be > 0")
+        if transform not in OT_TRANSFORMS:
+            raise ValueError("transform must be one of %s" % sorted(OT_TRANSFORMS))
+        for name, v in (("param", param), ("sharpness", sharpness), ("factor", factor)):
+            if v is not None and not (float(v) > 0.0 and np.isfinite(v)):
+                raise ValueError("%s must be finite and > 0" % name)
+        self.dt = float(dt)
+        self.transform = transform
+        self.param = None if param is None else float(param)
+        self.sharpness, self.factor = float(sharpness), float(factor)
+        self.taps = _checked_taps(taps)
+        self.dtype = None if dtype is None else np.dtype(dtype)
+        self.distances = self.counts = None
+
+    def param_of(self, d_obs):
+        """the parameter of a shot: ``param``, or ``sharpness / max|d_obs|`` (softplus), ``factor * max|d_obs|`` (linear)"""
+        if self.param is not None:
+            return self.param
+        d = np.asarray(d_obs, np.float64)
+        peak = float(np.max(np.abs(d))) if d.size else 0.0
+        if not (peak > 0.0 and np.isfinite(peak)):
+            raise ValueError("d_obs is all zero or not finite: give param")
+        return self.sharpness / peak if self.transform == "softplus" else self.factor * peak
+
+    def _round(self, x):
+        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+
+    def filter(self, x):
+        """``B x`` (rounded to ``dtype`` once; without taps a copy of x)"""
+        return fir_time(x, None) if self.taps is None else self._round(fir_time(x, self.taps))
+
+    def positive(self, x, param):
+        """``(P(x), P'(x))`` of the transform"""
+        if self.transform == "linear":
+            return x + param, np.ones_like(x)
+        z = param * x
+        with np.errstate(over="ignore", invalid="ignore"):
+            e = np.exp(-np.abs(z))
+            return (np.maximum(z, 0.0) + np.log1p(e)) / param, np.where(x >= 0.0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+    def cdfs(self, d_syn, d_obs, weights=None, param=None):
+        """``(F, G, f, g, S_s, S_d, counts, dP, M)``: the normalised CDFs and densities ``(nt, ntr)``, the masses, which
+        traces count, ``P'(sh)`` and the weights as used.  A trace that does not count is given uniform densities, so
+        that everything downstream of it stays finite; its results are zeroed by the caller."""
+        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
+        if s.ndim != 2 or s.shape != d.shape:
+            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
+        M = WeightedL2._weights(weights, s.shape)
+        sh, dh = self.filter(s), self.filter(d)
+        if M is not None:
+            sh, dh = M * sh, M * dh
+        param = self.param_of(d_obs) if param is None else float(param)
+        p, dP = self.positive(sh, param)
+        q, _ = self.positive(dh, param)
+        with np.errstate(over="ignore", invalid="ignore"):
+            Ss, Sd = np.sum(p, axis=0), np.sum(q, axis=0)
+            counts = (np.all(np.isfinite(p) & (p >= 0.0), axis=0) & np.all(np.isfinite(q) & (q >= 0.0), axis=0)
+                      & np.isfinite(Ss) & np.isfinite(Sd) & (Ss > 0.0) & (Sd > 0.0))
+        p, q, dP = np.where(counts, p, 1.0), np.where(counts, q, 1.0), np.where(counts, dP, 0.0)
+        Ss, Sd = np.sum(p, axis=0), np.sum(q, axis=0)
+        return np.cumsum(p, axis=0) / Ss, np.cumsum(q, axis=0) / Sd, p / Ss, q / Sd, Ss, Sd, counts, dP, M
+
+    @staticmethod
+    def indices(F, G):
+        """``(m+, m-, n+, n-)``, each ``(nt - 1, ntr)`` int64: row ``n - 1`` holds the counts of the definition for the
+        level ``F_{n-1}`` among ``G`` (``m+``: ``<=``, ``m-``: ``<``), and for ``G_{m-1}`` among ``F`` (``n+``, ``n-``),
+        clipped at ``nt - 1``"""
+        nt, ntr = F.shape
+        L = max(nt - 1, 0)
+        out = [np.zeros((L, ntr), np.int64) for _ in range(4)]
+        for j in range(ntr):
+            for k, (X, Y) in enumerate(((F[:, j], G[:, j]), (G[:, j], F[:, j]))):
+                # the clip at nt - 1 leaves the last level out of the counts
+                out[2 * k][:, j] = np.searchsorted(Y[:L], X[:L], side="right")
+                out[2 * k + 1][:, j] = np.searchsorted(Y[:L], X[:L], side="left")
+        return tuple(out)
+
+    @classmethod
+    def potentials(cls, F, G):
+        """``(phi, psi)``: the integer Kantorovich potentials ``(nt, ntr)`` int64 in units of ``dt^2``"""
+        nt, ntr = F.shape
+        mp, mm, np_, nm = cls.indices(F, G)
+        base = (2 * np.arange(1, nt, dtype=np.int64) - 1)[:, None]
+        phi, psi = np.zeros((nt, ntr), np.int64), np.zeros((nt, ntr), np.int64)
+        if nt > 1:
+            phi[1:], psi[1:] = np.cumsum(base - mp - mm, axis=0), np.cumsum(base - np_ - nm, axis=0)
+        return phi, psi
+
+    def primal(self, F, G):
+        """``W_j`` in s^2 by the primal formula, independent of the potentials: ``dt^2`` times the integral over the
+        level ``u`` in (0, 1) of the squared distance between the two quantile functions, a sum over the merged
+        breakpoints of ``F`` and ``G``"""
+        nt, ntr = F.shape
+        L = max(nt - 1, 0)
+        W = np.zeros(ntr)
+        for j in range(ntr):
+            u = np.unique(np.clip(np.concatenate(([0.0], F[:L, j], G[:L, j], [1.0])), 0.0, 1.0))
+            mid = 0.5 * (u[1:] + u[:-1])
+            n, m = np.searchsorted(F[:L, j], mid, side="left"), np.searchsorted(G[:L, j], mid, side="left")
+            W[j] = self.dt * self.dt * float(np.sum(np.diff(u) * (n - m).astype(np.float64) ** 2))
+        return W
+
+    def __call__(self, d_syn, d_obs, weights=None, trace_weights=None):
+        F, G, f, g, Ss, _, counts, dP, M = self.cdfs(d_syn, d_obs, weights)
+        nt, ntr = F.shape
+        w = np.ones(ntr)
+        if trace_weights is not None:
+            w = np.asarray(trace_weights, np.float64)
+            if w.shape != (ntr,):
+                raise ValueError("trace_weights have shape %r, the data %d traces" % (w.shape, ntr))
+            if not np.all(np.isfinite(w)) or np.any(w < 0.0):
+                raise ValueError("trace_weights must be finite and >= 0")
+        phi, psi = self.potentials(F, G)
+        dt2 = self.dt * self.dt
+        phibar = np.sum(phi * f, axis=0)
+        W = np.where(counts, dt2 * (phibar + np.sum(psi * g, axis=0)), 0.0)
+        self.distances, self.counts = W, counts
+        src = np.where(counts, 0.5 * w * dt2 / Ss, 0.0) * (phi - phibar) * dP
+        if M is not None:
+            src = M * src
+        src = self._round(src)
+        return float(np.sum(0.5 * w * W)), (src if self.taps is None else fir_time(src, self.taps))
 
 
 def matched_wavelet(wavelet, f):

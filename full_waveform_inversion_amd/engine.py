@@ -364,6 +364,42 @@ class Engine:
                                                   lag.ctypes.data_as(C.c_void_p) if per_trace else None))
         return (J.value, tau, lag) if per_trace else J.value
 
+    def misfit_transport(self, d_obs, transform="softplus", param=None, weights=None, taps=None, trace_weights=None,
+                         per_trace=False):
+        """Trace-by-trace optimal-transport (W2) misfit of the last forward's seismograms, which compares whole traces as
+        densities along time and grows with the square of a time shift however many periods it spans: with
+        ``sh = M . B d_syn``, ``dh = M . B d_obs``, ``f = P(sh) / sum P(sh)`` and ``g = P(dh) / sum P(dh)`` per trace,
+        ``W_j`` is the squared 2-Wasserstein distance between ``f`` and ``g`` as measures on the time samples (s^2) and
+        ``J = 1/2 sum_j w_j W_j``.  ``transform``: ``"softplus"``, ``P(x) = log(1 + exp(b x)) / b`` with ``b = param``,
+        or ``"linear"``, ``P(x) = x + c`` with ``c = param``; ``param > 0`` is absolute and must not depend on the
+        synthetics; None: :meth:`datafit.TransportW2.param_of` of ``d_obs``.  A trace counts only if all its densities
+        are finite and ``>= 0`` with positive sums (under ``linear``: nothing below ``-c``); otherwise its distance, its
+        term of J and its adjoint source are 0.  ``weights`` and ``taps`` as in :meth:`misfit_weighted`,
+        ``trace_weights`` as in :meth:`misfit_correlation`.  The adjoint source ``dJ/dd_syn`` is formed on the device and
+        kept there for ``adjoint(None)``.  Returns J, with ``per_trace=True`` ``(J, w2, counts)``: the ``ntr`` distances
+        ``W_j`` and 1 / 0 per trace (``fwi_misfit_transport``; the NumPy twin is :class:`datafit.TransportW2`)."""
+        if transform not in _lib.OT_TRANSFORMS:
+            raise ValueError("transform must be one of %s" % sorted(_lib.OT_TRANSFORMS))
+        if param is None:
+            from .datafit import TransportW2
+            param = TransportW2(self.dt, transform).param_of(d_obs)
+        d_obs = self._host(d_obs, (self._nt, self._nrec))
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        twp = None
+        if trace_weights is not None:
+            tw = np.ascontiguousarray(trace_weights, dtype=np.float64)
+            if tw.shape != (self._nrec,):
+                raise ValueError("trace_weights must hold one weight per trace, shape (%d,)" % self._nrec)
+            twp = tw.ctypes.data_as(C.c_void_p)
+        w2 = np.zeros(self._nrec) if per_trace else None
+        counts = np.zeros(self._nrec, np.int32) if per_trace else None
+        J = C.c_double(0.0)
+        self._chk(self._lib.fwi_misfit_transport(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, twp,
+                                                 _lib.OT_TRANSFORMS[transform], float(param), C.byref(J),
+                                                 w2.ctypes.data_as(C.c_void_p) if per_trace else None,
+                                                 counts.ctypes.data_as(C.c_void_p) if per_trace else None))
+        return (J.value, w2, counts) if per_trace else J.value
+
     def residual_weight(self, weights=None, taps=None):
         """The residual on the device (what ``born`` or a misfit call left for ``adjoint(None)``) := ``B M^2 B`` residual,
         the Gauss-Newton weight of :meth:`misfit_weighted` (``fwi_residual_weight``)."""

@@ -322,6 +322,12 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     ``misfit_traveltime`` forms the correlations over ``objective.max_lag`` lags, the delays, the misfit and its adjoint
     source on the device, otherwise the NumPy twin does on the host.  ``objective.dt`` must be the engine's time step.
 
+    A :class:`datafit.TransportW2` objective (trace-by-trace optimal transport: whole traces as densities along time) is
+    handed ``Shot.weights`` and ``Shot.trace_weights`` as well; under ``device_l2`` an engine that has
+    ``misfit_transport`` forms the densities, the potentials, the misfit and its adjoint source on the device, otherwise
+    the NumPy twin does on the host.  Either branch uses ``objective.param_of(d_obs)`` as the shot's parameter;
+    ``objective.dt`` must be the engine's time step.
+
     ``device_l2`` (least squares only): form the residual and J on the device (``fwi_misfit_l2``) -- in the
     engine's dtype, i.e. with an fp32 engine ``d_obs`` is rounded to fp32 before the subtraction, which puts
     ~6e-8 |d| / |r| of relative noise on J and on the residual (visible to a line search only once |r| / |d|
@@ -347,13 +353,14 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
 def _sweep_shots(engine, shots, ex, objective, device_l2=True):
     """forward + adjoint of this rank's shots; returns the misfit, gradients summed into the
     (primary) engine's accumulator."""
-    from .datafit import EnvelopeL2, MatchedL2, NormalizedCorrelation, TraveltimeL2, WeightedL2
+    from .datafit import EnvelopeL2, MatchedL2, NormalizedCorrelation, TransportW2, TraveltimeL2, WeightedL2
     from .objectives import l2
     weighted = isinstance(objective, WeightedL2)
     matched = isinstance(objective, MatchedL2)
     enveloped = isinstance(objective, EnvelopeL2)
     correlated = isinstance(objective, NormalizedCorrelation)
     timed = isinstance(objective, TraveltimeL2)
+    transported = isinstance(objective, TransportW2)
 
     def one(e, i):
         s = shots[i]
@@ -394,7 +401,13 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True):
             j = e.misfit_traveltime(s.d_obs, objective.max_lag, s.weights, objective.taps, s.trace_weights)
             e.adjoint(None)
             return j
-        if correlated or timed:
+        if device_l2 and transported and hasattr(e, "misfit_transport") and (s.rec_spread is None or s._on_device(e)):
+            # ... and so are the densities, their CDFs, the potentials, the transport distances and the adjoint source
+            j = e.misfit_transport(s.d_obs, objective.transform, objective.param_of(s.d_obs), s.weights, objective.taps,
+                                   s.trace_weights)
+            e.adjoint(None)
+            return j
+        if correlated or timed or transported:
             j, r = objective(d, s.d_obs, s.weights, s.trace_weights)
             s.adjoint(e, r)
             return j

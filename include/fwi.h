@@ -319,6 +319,55 @@ int fwi_misfit_traveltime(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const
                           const double *trace_weights /* ntr, or NULL */, int32_t max_lag, double *J_out,
                           double *tau_out /* ntr, or NULL */, int32_t *lag_out /* ntr, or NULL: k*, counting or not */);
 
+/* Trace-by-trace optimal-transport (quadratic Wasserstein, W2) misfit on the device (Engquist & Froese 2014; Yang,
+ * Engquist, Sun & Hamfeldt 2018): the envelope widens the basin of attraction by dropping the phase, the traveltime
+ * misfit by reducing a trace to one pick; this one compares the whole traces as densities along time, needs no pick and
+ * no window, and grows with the square of a time shift however many periods the shift spans.  With s = d_syn of the last
+ * forward and d = d_obs, both (nt, ntr) as above, B, M and w_j exactly as in fwi_misfit_traveltime, dt the context's time
+ * step and P the positivisation below, per trace j:
+ *     s' = B s,  d' = B d            (rounded to the context's dtype once, only when taps are given)
+ *     sh = M . s',  dh = M . d'
+ *     p_n = P(sh[n,j]),  q_n = P(dh[n,j])
+ *     S_s = sum_n p_n,  S_d = sum_n q_n;   f_n = p_n / S_s,  g_n = q_n / S_d
+ *     F_n = sum_{i<=n} f_i,  G_n = sum_{i<=n} g_i                 n = 0 .. nt-1
+ *     for n = 1 .. nt-1, with the level y = F_{n-1}:
+ *         m+(n) = min(#{m : G_m <= y}, nt-1),   m-(n) = min(#{m : G_m < y}, nt-1)
+ *         a_n = 2n - 1 - m+(n) - m-(n)                            an integer
+ *       and the same with f and g exchanged: n+(m), n-(m), b_m = 2m - 1 - n+(m) - n-(m)
+ *     phi_0 = psi_0 = 0,  phi_n = sum_{i=1..n} a_i,  psi_m = sum_{i=1..m} b_i      integers, exact
+ *     W_j = dt^2 (sum_n phi_n f_n + sum_m psi_m g_m)              (s^2)
+ *     J = 1/2 sum_j w_j W_j
+ *     phibar_j = sum_n phi_n f_n
+ *     g[n,j] = M[n,j] (w_j / 2) dt^2 (phi_n - phibar_j) / S_s  P'(sh[n,j])     (rounded to the dtype once)
+ *     r = dJ/ds = B g
+ * W_j is the exact squared 2-Wasserstein distance between the atomic measures sum f_n delta(t_n) and sum g_n delta(t_n),
+ * (phi, psi) dt^2 an optimal pair of Kantorovich potentials, and r the gradient of this discrete J wherever no level F_n
+ * equals a level G_m.  J is piecewise smooth and NOT differentiable where a level of F crosses a level of G: the gradient
+ * jumps there.  At a tie the two-sided count m+ + m- selects the midpoint subgradient, so that d_obs == d_syn gives
+ * phi = psi = 0, J = 0 and r = 0 exactly.  Zero-mass atoms are allowed (they are ties).
+ * transform and param (absolute; like eps elsewhere param must not depend on s):
+ *     FWI_OT_LINEAR    P(x) = x + c,  P' = 1,  c = param > 0
+ *     FWI_OT_SOFTPLUS  P(x) = log(1 + exp(b x)) / b,  P'(x) = 1 / (1 + exp(-b x)),  b = param > 0; evaluated as
+ *                      (max(b x, 0) + log1p(exp(-|b x|))) / b, the sigmoid by the branch of the sign of x: no overflow
+ * A trace counts iff every p_n and q_n is finite and >= 0 and S_s, S_d are finite and > 0; otherwise W_j = 0, its term of
+ * J is 0 and its adjoint source is 0 (under FWI_OT_LINEAR a trace that goes below -c drops out; softplus only fails on
+ * non-finite data).  *J_out = J; w2_out, if not NULL, receives the ntr values W_j in s^2, counts_out, if not NULL, 1 for
+ * a trace that counts and 0 otherwise; r stays on the device as the residual of the next fwi_adjoint(ctx, NULL, ...).
+ * The synthetics are left alone: the call can be repeated.  Everything between the loads and the roundings named above is
+ * fp64, the potentials integers carried in fp64.  The time axis is cut into slices whose number is a function of
+ * (nt, ntr) only; S, the CDFs (as (offset of the slice + sum within the slice) / S, non-decreasing by construction), the
+ * potentials and the two dual sums are added over ascending time within a slice and over the slices in ascending order,
+ * and J adds its traces in a fixed order, without atomics: equal inputs give equal bits.  State rules, off-grid receivers
+ * (ntr is then the number of points) and work buffers as fwi_misfit_weighted.  FWI_EINVAL: a null J_out, a null d_obs
+ * with nrec > 0, the tap errors of fwi_misfit_weighted, an unknown transform, param <= 0 or not finite, a trace weight
+ * that is negative or not finite.  No receivers: J = 0 and nothing is launched; nt = 1: W = 0 and r = 0. */
+#define FWI_OT_LINEAR 0
+#define FWI_OT_SOFTPLUS 1
+int fwi_misfit_transport(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                         const double *taps /* R + 1, or NULL */, int32_t R,
+                         const double *trace_weights /* ntr, or NULL */, int32_t transform, double param, double *J_out,
+                         double *w2_out /* ntr, or NULL: W_j in s^2 */, int32_t *counts_out /* ntr, or NULL: 1 / 0 */);
+
 /* gradient(): copy out the accumulated gradient, model-shaped, as dJ/dc
  * (FWI_WRT_VELOCITY) or dJ/d(1/c^2) (FWI_WRT_SLOWNESS2).
  * [SURVEY s.8(a-1) row gradient] */

@@ -90,6 +90,15 @@ def main():
                          "square of the time shift over any number of periods, blind to the gain of a trace "
                          "(datafit.TraveltimeL2, on the device); composes with --bands and --mute-direct, not with "
                          "--correlation, --envelope or --match-source")
+    ap.add_argument("--transport", choices=sorted(datafit.OT_TRANSFORMS), default=None,
+                    help="trace-by-trace optimal-transport misfit, 1/2 the sum over traces of the squared 2-Wasserstein "
+                         "distance between synthetics and data made positive by the chosen transform and normalised to "
+                         "densities along time: uses the whole trace, needs no pick, grows with the square of the time "
+                         "shift over any number of periods (datafit.TransportW2, on the device); composes with --bands and "
+                         "--mute-direct, not with --traveltime, --correlation, --envelope or --match-source")
+    ap.add_argument("--transport-param", type=float, default=None, metavar="X",
+                    help="the absolute parameter of --transport: b of softplus, c of linear (default: per shot from its "
+                         "observed data, datafit.TransportW2.param_of, computed once and held through the run)")
     a = ap.parse_args()
     bands = [float(f) for f in a.bands.split(",")] if a.bands else None
     if bands and (a.iters < 1 or a.checkpoint or a.resume):
@@ -108,6 +117,13 @@ def main():
         ap.error("--correlation, --envelope and --match-source are different misfits: choose one")
     if a.traveltime is not None and (a.correlation is not None or a.envelope is not None or a.match_source is not None):
         ap.error("--traveltime, --correlation, --envelope and --match-source are different misfits: choose one")
+    if a.transport is not None and (a.traveltime is not None or a.correlation is not None or a.envelope is not None
+                                    or a.match_source is not None):
+        ap.error("--transport, --traveltime, --correlation, --envelope and --match-source are different misfits: choose one")
+    if a.transport_param is not None and a.transport is None:
+        ap.error("--transport-param needs --transport")
+    if a.transport_param is not None and not (a.transport_param > 0.0 and np.isfinite(a.transport_param)):
+        ap.error("--transport-param X must be finite and > 0")
     if a.traveltime is not None and not 1 <= a.traveltime <= datafit.K_MAX:
         ap.error("--traveltime MAX_LAG must lie in [1, %d] samples" % datafit.K_MAX)
     if a.correlation is not None and not (a.correlation >= 0.0 and np.isfinite(a.correlation)):
@@ -180,6 +196,8 @@ def main():
             return datafit.NormalizedCorrelation(None, taps, floor_percent=a.correlation)
         if a.traveltime is not None:
             return datafit.TraveltimeL2(w.dt, a.traveltime, taps)
+        if a.transport is not None:  # (the parameter: given, or a data-only number per shot, param_of of its d_obs)
+            return datafit.TransportW2(w.dt, a.transport, a.transport_param, taps)
         return datafit.WeightedL2(taps) if (taps is not None or a.mute_direct is not None) else None
 
     def filters_line(o, band=None):
@@ -288,6 +306,7 @@ def main():
                           "band_halfwidth": a.band_halfwidth if bands else None, "mute_direct": a.mute_direct,
                           "match_source": a.match_source, "correlation_floor_percent": a.correlation,
                           "traveltime_max_lag": a.traveltime,
+                          "transport": a.transport, "transport_param": a.transport_param,
                           "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
                           "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
                           "envelope_floor_percent": a.envelope_floor_percent if a.envelope is not None else None,
