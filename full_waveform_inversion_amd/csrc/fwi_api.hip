@@ -191,28 +191,28 @@ struct fwi_ctx {
                                  // by the first of those calls
     // the data misfits and fwi_residual_weight (Impl<T>::Misfit), each allocated by the first call that needs it: the
     // series between two passes (e; g1 of the envelope), the weights, the taps of B, the block partial sums of J (and
-    // their total), and the filtered synthetics s' and data d' of the misfits that filter first (with taps; s' later
-    // holds their adjoint source)
+    // their total), the filtered synthetics s' and data d' of the misfits that filter first (with taps; s' later holds
+    // their adjoint source), and the weights per trace of the misfits that take any
     void *data_tmp = nullptr, *data_w = nullptr, *data_taps = nullptr, *data_part = nullptr, *data_s = nullptr,
-         *data_d = nullptr;
-    size_t cap_data_tmp = 0, cap_data_w = 0, cap_data_taps = 0, cap_data_part = 0, cap_data_s = 0, cap_data_d = 0;
+         *data_d = nullptr, *data_tw = nullptr;
+    size_t cap_data_tmp = 0, cap_data_w = 0, cap_data_taps = 0, cap_data_part = 0, cap_data_s = 0, cap_data_d = 0,
+           cap_data_tw = 0;
     // fwi_misfit_matched (fwi_match.hip): the slices of the normal equations, G and b, the filter
     void *match_part = nullptr, *match_norm = nullptr, *match_f = nullptr;
     size_t cap_match_part = 0, cap_match_norm = 0, cap_match_f = 0;
     // fwi_misfit_envelope (fwi_envelope.hip): g2, the Hilbert taps
     void *env_g2 = nullptr, *env_h = nullptr;
     size_t cap_env_g2 = 0, cap_env_h = 0;
-    // fwi_misfit_correlation (fwi_corr.hip): the per-tile sums and the terms of J, alpha / beta / rho, the trace weights
-    void *corr_part = nullptr, *corr_coef = nullptr, *corr_tw = nullptr;
-    size_t cap_corr_part = 0, cap_corr_coef = 0, cap_corr_tw = 0;
+    // fwi_misfit_correlation (fwi_corr.hip): the per-tile sums and the terms of J, alpha / beta / rho
+    void *corr_part = nullptr, *corr_coef = nullptr;
+    size_t cap_corr_part = 0, cap_corr_coef = 0;
     // fwi_misfit_traveltime (fwi_ttime.hip): the partial correlations and the terms of J, tau and the three coefficients
-    // of every trace, the picked lags, the trace weights
-    void *tt_part = nullptr, *tt_coef = nullptr, *tt_lag = nullptr, *tt_tw = nullptr;
-    size_t cap_tt_part = 0, cap_tt_coef = 0, cap_tt_lag = 0, cap_tt_tw = 0;
-    // fwi_misfit_transport (fwi_ot.hip): densities, CDFs, potentials and every sum (ot_work_doubles), which traces count,
-    // the trace weights
-    void *ot_work = nullptr, *ot_counts = nullptr, *ot_tw = nullptr;
-    size_t cap_ot_work = 0, cap_ot_counts = 0, cap_ot_tw = 0;
+    // of every trace, the picked lags
+    void *tt_part = nullptr, *tt_coef = nullptr, *tt_lag = nullptr;
+    size_t cap_tt_part = 0, cap_tt_coef = 0, cap_tt_lag = 0;
+    // fwi_misfit_transport (fwi_ot.hip): densities, CDFs, potentials and every sum (ot_work_doubles), which traces count
+    void *ot_work = nullptr, *ot_counts = nullptr;
+    size_t cap_ot_work = 0, cap_ot_counts = 0;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
     enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
     int resid_pts_in = RESID_PTS_NONE;
@@ -1855,6 +1855,19 @@ struct Impl {
         // residual; with taps it takes the place of s', and finish() has B write r over the uploaded d_obs
         T *adjoint_source() const { return b ? (T *)ctx->data_s : resid; }
 
+        // *tw := the caller's ntr weights per trace on the device (ctx->data_tw), or nullptr where there are none (all 1)
+        int trace_weights(const double *host, const double **tw) {
+            *tw = nullptr;
+            if (!host) return FWI_OK;
+            const size_t bytes = (size_t)ntr * sizeof(double);
+            if (int rc = ensure(ctx, &ctx->data_tw, &ctx->cap_data_tw, bytes)) return rc;
+            // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
+            HIPCHK(ctx, hipMemcpyAsync(ctx->data_tw, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            *tw = (const double *)ctx->data_tw;
+            return FWI_OK;
+        }
+
         // resid := B src (src == resid: it is there already), onto the nodes, *ss := the sum of squares
         int finish(const T *src, double *ss) {
             const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
@@ -1869,6 +1882,21 @@ struct Impl {
             }
             ctx->have_dev_residual = true;
             ctx->resid_pts_in = (data && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
+            return FWI_OK;
+        }
+
+        // after finish(): up to two arrays of ntr numbers per trace to the caller (a null destination: not asked for),
+        // under one synchronise; without receivers or samples no trace counts and they are zeros
+        template <typename A, typename B = double>
+        int per_trace(A *out_a, const A *dev_a, B *out_b = nullptr, const B *dev_b = nullptr) {
+            if (!data) {
+                if (out_a) std::fill(out_a, out_a + ntr, A(0));
+                if (out_b) std::fill(out_b, out_b + ntr, B(0));
+                return FWI_OK;
+            }
+            if (out_a) HIPCHK(ctx, hipMemcpyAsync(out_a, dev_a, (size_t)ntr * sizeof(A), hipMemcpyDeviceToHost, ctx->stream));
+            if (out_b) HIPCHK(ctx, hipMemcpyAsync(out_b, dev_b, (size_t)ntr * sizeof(B), hipMemcpyDeviceToHost, ctx->stream));
+            if (out_a || out_b) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             return FWI_OK;
         }
     };
@@ -2008,15 +2036,8 @@ struct Impl {
             if ((rc = ensure(ctx, &ctx->corr_part, &ctx->cap_corr_part, np * sizeof(double))) ||
                 (rc = ensure(ctx, &ctx->corr_coef, &ctx->cap_corr_coef, (size_t)3 * m.ntr * sizeof(double))))
                 return rc;
-            const double *tw = nullptr;
-            if (trace_weights) {
-                if ((rc = ensure(ctx, &ctx->corr_tw, &ctx->cap_corr_tw, (size_t)m.ntr * sizeof(double)))) return rc;
-                // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
-                HIPCHK(ctx, hipMemcpyAsync(ctx->corr_tw, trace_weights, (size_t)m.ntr * sizeof(double),
-                                           hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                tw = (const double *)ctx->corr_tw;
-            }
+            const double *tw;
+            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
             double *part = (double *)ctx->corr_part, *coef = (double *)ctx->corr_coef;
             m.sum = part + (np - 1);  // the total of the terms w_j (1 - rho_j): J itself
             const T *s1, *d1;
@@ -2027,11 +2048,9 @@ struct Impl {
             HIPCHK(ctx, launch_corr_source<T>(g, s1, d1, m.w, coef, m.nt, m.ntr, ctx->stream));
         }
         if ((rc = m.finish(g, &J))) return rc;
-        if (m.data && rho_out) {
-            HIPCHK(ctx, hipMemcpyAsync(rho_out, (const double *)ctx->corr_coef + 2 * (size_t)m.ntr,
-                                       (size_t)m.ntr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
+        // without receivers or samples rho_out stays as the caller handed it in, as it always has (the two misfits below
+        // zero their per-trace outputs then): hence only with data
+        if (m.data && (rc = m.per_trace(rho_out, (const double *)ctx->corr_coef + 2 * (size_t)m.ntr))) return rc;
         *J_out = J;
         return FWI_OK;
     }
@@ -2052,15 +2071,8 @@ struct Impl {
                 (rc = ensure(ctx, &ctx->tt_coef, &ctx->cap_tt_coef, (size_t)4 * m.ntr * sizeof(double))) ||
                 (rc = ensure(ctx, &ctx->tt_lag, &ctx->cap_tt_lag, (size_t)m.ntr * sizeof(int32_t))))
                 return rc;
-            const double *tw = nullptr;
-            if (trace_weights) {
-                if ((rc = ensure(ctx, &ctx->tt_tw, &ctx->cap_tt_tw, (size_t)m.ntr * sizeof(double)))) return rc;
-                // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
-                HIPCHK(ctx, hipMemcpyAsync(ctx->tt_tw, trace_weights, (size_t)m.ntr * sizeof(double), hipMemcpyHostToDevice,
-                                           ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                tw = (const double *)ctx->tt_tw;
-            }
+            const double *tw;
+            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
             double *part = (double *)ctx->tt_part, *coef = (double *)ctx->tt_coef;
             int32_t *lag = (int32_t *)ctx->tt_lag;
             m.sum = part + (np - 1);  // the total of the terms 1/2 w_j tau_j^2: J itself
@@ -2073,18 +2085,9 @@ struct Impl {
             g = (T *)ctx->data_tmp;
             HIPCHK(ctx, launch_tt_source<T>(g, d1, m.w, coef, lag, m.nt, m.ntr, ctx->stream));
         }
-        if ((rc = m.finish(g, &J))) return rc;
-        if (m.data && tau_out)
-            HIPCHK(ctx, hipMemcpyAsync(tau_out, ctx->tt_coef, (size_t)m.ntr * sizeof(double), hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        if (m.data && lag_out)
-            HIPCHK(ctx, hipMemcpyAsync(lag_out, ctx->tt_lag, (size_t)m.ntr * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        if (m.data && (tau_out || lag_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (!m.data) {  // no receivers or no samples: no trace counts
-            if (tau_out) std::fill(tau_out, tau_out + m.ntr, 0.0);
-            if (lag_out) std::fill(lag_out, lag_out + m.ntr, 0);
-        }
+        if ((rc = m.finish(g, &J)) ||
+            (rc = m.per_trace(tau_out, (const double *)ctx->tt_coef, lag_out, (const int32_t *)ctx->tt_lag)))
+            return rc;
         *J_out = J;
         return FWI_OK;
     }
@@ -2098,41 +2101,25 @@ struct Impl {
         Misfit m(ctx);
         double J = 0.0;
         T *g = nullptr;
+        const double *w2 = nullptr;  // the distances W_j within the work array
         int rc = m.begin(d_obs, weights, taps, R);
         if (rc) return rc;
         if (m.data) {
             if ((rc = ensure(ctx, &ctx->ot_work, &ctx->cap_ot_work, ot_work_doubles(m.nt, m.ntr) * sizeof(double))) ||
                 (rc = ensure(ctx, &ctx->ot_counts, &ctx->cap_ot_counts, (size_t)m.ntr * sizeof(int32_t))))
                 return rc;
-            const double *tw = nullptr;
-            if (trace_weights) {
-                if ((rc = ensure(ctx, &ctx->ot_tw, &ctx->cap_ot_tw, (size_t)m.ntr * sizeof(double)))) return rc;
-                // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
-                HIPCHK(ctx, hipMemcpyAsync(ctx->ot_tw, trace_weights, (size_t)m.ntr * sizeof(double), hipMemcpyHostToDevice,
-                                           ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                tw = (const double *)ctx->ot_tw;
-            }
+            const double *tw;
+            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
             double *work = (double *)ctx->ot_work;
             m.sum = work + ot_total_at(m.nt, m.ntr);  // the total of the terms 1/2 w_j W_j: J itself
+            w2 = work + ot_w2_at(m.nt, m.ntr);
             const T *s1, *d1;
             if ((rc = m.prefilter(&s1, &d1))) return rc;
             g = m.adjoint_source();  // in place of s' (with taps) or of d_obs (without): elementwise, written last
             HIPCHK(ctx, launch_ot_misfit<T>(work, (int32_t *)ctx->ot_counts, g, s1, d1, m.w, tw, transform, param,
                                             ctx->cfg.dt, m.nt, m.ntr, ctx->stream));
         }
-        if ((rc = m.finish(g, &J))) return rc;
-        if (m.data && w2_out)
-            HIPCHK(ctx, hipMemcpyAsync(w2_out, (const double *)ctx->ot_work + ot_w2_at(m.nt, m.ntr),
-                                       (size_t)m.ntr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        if (m.data && counts_out)
-            HIPCHK(ctx, hipMemcpyAsync(counts_out, ctx->ot_counts, (size_t)m.ntr * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        if (m.data && (w2_out || counts_out)) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (!m.data) {  // no receivers or no samples: no trace counts
-            if (w2_out) std::fill(w2_out, w2_out + m.ntr, 0.0);
-            if (counts_out) std::fill(counts_out, counts_out + m.ntr, 0);
-        }
+        if ((rc = m.finish(g, &J)) || (rc = m.per_trace(w2_out, w2, counts_out, (const int32_t *)ctx->ot_counts))) return rc;
         *J_out = J;
         return FWI_OK;
     }
@@ -2385,6 +2372,12 @@ static int vec_regularizer(fwi_ctx *ctx, int32_t kind, const void *x, const void
     return FWI_OK;
 }
 
+// An array of the caller's in the context's dtype, as DISPATCH_CALL hands it to Impl<T>: const float * or const double *
+struct typed {
+    const void *p;
+    explicit typed(const void *q) : p(q) {}
+    template <typename T> operator const T *() const { return (const T *)p; }
+};
 
 extern "C" {
 
@@ -2642,12 +2635,12 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}, {"reg_part", ctx->reg_part},
                   {"sum_part", ctx->sum_part},
                   {"data_tmp", ctx->data_tmp}, {"data_w", ctx->data_w}, {"data_taps", ctx->data_taps},
-                  {"data_part", ctx->data_part}, {"data_s", ctx->data_s}, {"data_d", ctx->data_d},
+                  {"data_part", ctx->data_part}, {"data_s", ctx->data_s}, {"data_d", ctx->data_d}, {"data_tw", ctx->data_tw},
                   {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f},
                   {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h},
-                  {"corr_part", ctx->corr_part}, {"corr_coef", ctx->corr_coef}, {"corr_tw", ctx->corr_tw},
-                  {"tt_part", ctx->tt_part}, {"tt_coef", ctx->tt_coef}, {"tt_lag", ctx->tt_lag}, {"tt_tw", ctx->tt_tw},
-                  {"ot_work", ctx->ot_work}, {"ot_counts", ctx->ot_counts}, {"ot_tw", ctx->ot_tw}};
+                  {"corr_part", ctx->corr_part}, {"corr_coef", ctx->corr_coef},
+                  {"tt_part", ctx->tt_part}, {"tt_coef", ctx->tt_coef}, {"tt_lag", ctx->tt_lag},
+                  {"ot_work", ctx->ot_work}, {"ot_counts", ctx->ot_counts}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -2678,6 +2671,8 @@ void fwi_destroy(fwi_ctx *ctx) {
 }
 
 #define DISPATCH(ctx, expr32, expr64) ((ctx)->cfg.dtype == FWI_F32 ? (expr32) : (expr64))
+// ... of one member of Impl<float> or Impl<double>, with the argument list written once (the caller's arrays: typed(p))
+#define DISPATCH_CALL(ctx, fn, ...) DISPATCH(ctx, Impl<float>::fn(ctx, __VA_ARGS__), Impl<double>::fn(ctx, __VA_ARGS__))
 
 int fwi_set_model(fwi_ctx *ctx, const void *c_host) {
     if (!ctx) return FWI_EINVAL;
@@ -2800,8 +2795,7 @@ static int misfit_synthetics(fwi_ctx *ctx, const char *who, const char *also) {
 int fwi_misfit_l2(fwi_ctx *ctx, const void *d_obs, double *J_out) {
     if (int rc = misfit_callable(ctx, "fwi_misfit_l2", d_obs, J_out)) return rc;
     if (int rc = misfit_synthetics(ctx, "fwi_misfit_l2", "")) return rc;
-    return DISPATCH(ctx, Impl<float>::misfit_l2(ctx, (const float *)d_obs, J_out),
-                    Impl<double>::misfit_l2(ctx, (const double *)d_obs, J_out));
+    return DISPATCH_CALL(ctx, misfit_l2, typed(d_obs), J_out);
 }
 
 static int data_args(fwi_ctx *ctx, const char *who, const double *taps, int32_t R) {
@@ -2810,14 +2804,28 @@ static int data_args(fwi_ctx *ctx, const char *who, const double *taps, int32_t 
     return FWI_OK;
 }
 
+// the weights per trace, one per node receiver or per off-grid point (nullptr: none)
+static int trace_weight_args(fwi_ctx *ctx, const char *who, const double *trace_weights) {
+    if (!trace_weights || !ctx->nrec) return FWI_OK;
+    const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
+    for (int j = 0; j < ntr; ++j)
+        if (!(trace_weights[j] >= 0.0) || !std::isfinite(trace_weights[j]))
+            return ctx->fail(FWI_EINVAL, "%s: trace_weights[%d]=%g must be finite and >= 0", who, j, trace_weights[j]);
+    return FWI_OK;
+}
+
+// a scalar parameter `name` that must be finite and >= 0 (`positive`: > 0)
+static int nonneg_finite(fwi_ctx *ctx, const char *who, const char *name, double v, bool positive = false) {
+    if (std::isfinite(v) && (positive ? v > 0.0 : v >= 0.0)) return FWI_OK;
+    return ctx->fail(FWI_EINVAL, "%s: %s=%g must be finite and %s 0", who, name, v, positive ? ">" : ">=");
+}
+
 int fwi_misfit_weighted(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
                         double *J_out) {
     if (int rc = misfit_callable(ctx, "fwi_misfit_weighted", d_obs, J_out)) return rc;
     if (int rc = data_args(ctx, "fwi_misfit_weighted", taps, R)) return rc;
     if (int rc = misfit_synthetics(ctx, "fwi_misfit_weighted", "or fwi_born ")) return rc;
-    return DISPATCH(ctx,
-                    Impl<float>::misfit_weighted(ctx, (const float *)d_obs, (const float *)weights, taps, R, J_out),
-                    Impl<double>::misfit_weighted(ctx, (const double *)d_obs, (const double *)weights, taps, R, J_out));
+    return DISPATCH_CALL(ctx, misfit_weighted, typed(d_obs), typed(weights), taps, R, J_out);
 }
 
 int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R, int32_t L,
@@ -2826,16 +2834,12 @@ int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs, const void *weights, con
     if (int rc = data_args(ctx, "fwi_misfit_matched", taps, R)) return rc;
     if (L < 0 || L > FWI_MATCH_LMAX)
         return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: L=%d outside [0, %d]", (int)L, FWI_MATCH_LMAX);
-    if (!(mu >= 0.0) || !std::isfinite(mu)) return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: mu=%g must be finite and >= 0", mu);
+    if (int rc = nonneg_finite(ctx, "fwi_misfit_matched", "mu", mu)) return rc;
     if (f_in)
         for (int k = 0; k < 2 * L + 1; ++k)
             if (!std::isfinite(f_in[k])) return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: f_in[%d] is not finite", k);
     if (int rc = misfit_synthetics(ctx, "fwi_misfit_matched", "or fwi_born ")) return rc;
-    return DISPATCH(ctx,
-                    Impl<float>::misfit_matched(ctx, (const float *)d_obs, (const float *)weights, taps, R, L, mu, f_in,
-                                                f_out, normal_out, J_out),
-                    Impl<double>::misfit_matched(ctx, (const double *)d_obs, (const double *)weights, taps, R, L, mu, f_in,
-                                                 f_out, normal_out, J_out));
+    return DISPATCH_CALL(ctx, misfit_matched, typed(d_obs), typed(weights), taps, R, L, mu, f_in, f_out, normal_out, J_out);
 }
 
 int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
@@ -2846,37 +2850,21 @@ int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs, const void *weights, co
     for (int k = 0; k < Q; ++k)
         if (!std::isfinite(hilbert[k])) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: hilbert[%d] is not finite", k);
     if (power != 1 && power != 2) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: power=%d is neither 1 nor 2", (int)power);
-    if (!(eps >= 0.0) || !std::isfinite(eps))
-        return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: eps=%g must be finite and >= 0", eps);
+    if (int rc = nonneg_finite(ctx, "fwi_misfit_envelope", "eps", eps)) return rc;
     if (power == 1 && eps == 0.0)
         return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: power 1 needs eps > 0 (the envelope is not differentiable at 0)");
     if (int rc = misfit_synthetics(ctx, "fwi_misfit_envelope", "or fwi_born ")) return rc;
-    return DISPATCH(ctx,
-                    Impl<float>::misfit_envelope(ctx, (const float *)d_obs, (const float *)weights, taps, R, hilbert, Q,
-                                                 power, eps, J_out),
-                    Impl<double>::misfit_envelope(ctx, (const double *)d_obs, (const double *)weights, taps, R, hilbert, Q,
-                                                  power, eps, J_out));
+    return DISPATCH_CALL(ctx, misfit_envelope, typed(d_obs), typed(weights), taps, R, hilbert, Q, power, eps, J_out);
 }
 
 int fwi_misfit_correlation(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
                            const double *trace_weights, double eps, double *J_out, double *rho_out) {
     if (int rc = misfit_callable(ctx, "fwi_misfit_correlation", d_obs, J_out)) return rc;
     if (int rc = data_args(ctx, "fwi_misfit_correlation", taps, R)) return rc;
-    if (!(eps >= 0.0) || !std::isfinite(eps))
-        return ctx->fail(FWI_EINVAL, "fwi_misfit_correlation: eps=%g must be finite and >= 0", eps);
-    if (trace_weights && ctx->nrec) {
-        const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
-        for (int j = 0; j < ntr; ++j)
-            if (!(trace_weights[j] >= 0.0) || !std::isfinite(trace_weights[j]))
-                return ctx->fail(FWI_EINVAL, "fwi_misfit_correlation: trace_weights[%d]=%g must be finite and >= 0", j,
-                                 trace_weights[j]);
-    }
+    if (int rc = nonneg_finite(ctx, "fwi_misfit_correlation", "eps", eps)) return rc;
+    if (int rc = trace_weight_args(ctx, "fwi_misfit_correlation", trace_weights)) return rc;
     if (int rc = misfit_synthetics(ctx, "fwi_misfit_correlation", "or fwi_born ")) return rc;
-    return DISPATCH(ctx,
-                    Impl<float>::misfit_correlation(ctx, (const float *)d_obs, (const float *)weights, taps, R,
-                                                    trace_weights, eps, J_out, rho_out),
-                    Impl<double>::misfit_correlation(ctx, (const double *)d_obs, (const double *)weights, taps, R,
-                                                     trace_weights, eps, J_out, rho_out));
+    return DISPATCH_CALL(ctx, misfit_correlation, typed(d_obs), typed(weights), taps, R, trace_weights, eps, J_out, rho_out);
 }
 
 int fwi_misfit_traveltime(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
@@ -2885,19 +2873,10 @@ int fwi_misfit_traveltime(fwi_ctx *ctx, const void *d_obs, const void *weights, 
     if (int rc = data_args(ctx, "fwi_misfit_traveltime", taps, R)) return rc;
     if (max_lag < 1 || max_lag > FWI_TT_KMAX)
         return ctx->fail(FWI_EINVAL, "fwi_misfit_traveltime: max_lag=%d outside [1, %d]", (int)max_lag, FWI_TT_KMAX);
-    if (trace_weights && ctx->nrec) {
-        const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
-        for (int j = 0; j < ntr; ++j)
-            if (!(trace_weights[j] >= 0.0) || !std::isfinite(trace_weights[j]))
-                return ctx->fail(FWI_EINVAL, "fwi_misfit_traveltime: trace_weights[%d]=%g must be finite and >= 0", j,
-                                 trace_weights[j]);
-    }
+    if (int rc = trace_weight_args(ctx, "fwi_misfit_traveltime", trace_weights)) return rc;
     if (int rc = misfit_synthetics(ctx, "fwi_misfit_traveltime", "or fwi_born ")) return rc;
-    return DISPATCH(ctx,
-                    Impl<float>::misfit_traveltime(ctx, (const float *)d_obs, (const float *)weights, taps, R,
-                                                   trace_weights, max_lag, J_out, tau_out, lag_out),
-                    Impl<double>::misfit_traveltime(ctx, (const double *)d_obs, (const double *)weights, taps, R,
-                                                    trace_weights, max_lag, J_out, tau_out, lag_out));
+    return DISPATCH_CALL(ctx, misfit_traveltime, typed(d_obs), typed(weights), taps, R, trace_weights, max_lag, J_out,
+                         tau_out, lag_out);
 }
 
 int fwi_misfit_transport(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
@@ -2908,21 +2887,11 @@ int fwi_misfit_transport(fwi_ctx *ctx, const void *d_obs, const void *weights, c
     if (transform != FWI_OT_LINEAR && transform != FWI_OT_SOFTPLUS)
         return ctx->fail(FWI_EINVAL, "fwi_misfit_transport: transform=%d is neither FWI_OT_LINEAR nor FWI_OT_SOFTPLUS",
                          (int)transform);
-    if (!(param > 0.0) || !std::isfinite(param))
-        return ctx->fail(FWI_EINVAL, "fwi_misfit_transport: param=%g must be finite and > 0", param);
-    if (trace_weights && ctx->nrec) {
-        const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
-        for (int j = 0; j < ntr; ++j)
-            if (!(trace_weights[j] >= 0.0) || !std::isfinite(trace_weights[j]))
-                return ctx->fail(FWI_EINVAL, "fwi_misfit_transport: trace_weights[%d]=%g must be finite and >= 0", j,
-                                 trace_weights[j]);
-    }
+    if (int rc = nonneg_finite(ctx, "fwi_misfit_transport", "param", param, true)) return rc;
+    if (int rc = trace_weight_args(ctx, "fwi_misfit_transport", trace_weights)) return rc;
     if (int rc = misfit_synthetics(ctx, "fwi_misfit_transport", "or fwi_born ")) return rc;
-    return DISPATCH(ctx,
-                    Impl<float>::misfit_transport(ctx, (const float *)d_obs, (const float *)weights, taps, R,
-                                                  trace_weights, transform, param, J_out, w2_out, counts_out),
-                    Impl<double>::misfit_transport(ctx, (const double *)d_obs, (const double *)weights, taps, R,
-                                                   trace_weights, transform, param, J_out, w2_out, counts_out));
+    return DISPATCH_CALL(ctx, misfit_transport, typed(d_obs), typed(weights), taps, R, trace_weights, transform, param,
+                         J_out, w2_out, counts_out);
 }
 
 int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {
@@ -2936,8 +2905,7 @@ int fwi_residual_weight(fwi_ctx *ctx, const void *weights, const double *taps, i
         return ctx->fail(FWI_ESTATE, "fwi_residual_weight: no residual on the device (fwi_born, fwi_misfit_l2 or "
                                      "fwi_misfit_weighted leave one; fwi_adjoint uses it up)");
     (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::residual_weight(ctx, (const float *)weights, taps, R),
-                    Impl<double>::residual_weight(ctx, (const double *)weights, taps, R));
+    return DISPATCH_CALL(ctx, residual_weight, typed(weights), taps, R);
 }
 
 int fwi_gradient(fwi_ctx *ctx, int32_t wrt, void *g_out) {

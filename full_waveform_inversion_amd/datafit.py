@@ -238,6 +238,16 @@ class WeightedL2:
             raise ValueError("weights must be >= 0")
         return M
 
+    # What the shot loop asks of an objective (shots._sweep_shots): the engine method of its device path, that call for
+    # shot number i (returns J; the adjoint source stays on the device), and the host call (returns J and the residual)
+    engine_method = "misfit_weighted"
+
+    def device(self, engine, shot, i):
+        return engine.misfit_weighted(shot.d_obs, shot.weights, self.taps)
+
+    def host(self, d_syn, shot, i):
+        return self(d_syn, shot.d_obs, shot.weights)
+
     def __call__(self, d_syn, d_obs, weights=None):
         x = np.asarray(d_syn, np.float64) - np.asarray(d_obs, np.float64)
         M = self._weights(weights, x.shape)
@@ -252,6 +262,60 @@ class WeightedL2:
         M = self._weights(weights, x.shape)
         e = self.filter(x)
         return self.filter(e if M is None else M * M * e)
+
+
+class _Prefiltered:
+    """What the misfits that filter both gathers first share: ``taps`` and ``dtype``, the rounding a device context of
+    that dtype does, ``s' = B s`` and ``d' = B d`` with the checked weights."""
+
+    def _band(self, taps, dtype):
+        self.taps = _checked_taps(taps)
+        self.dtype = None if dtype is None else np.dtype(dtype)
+
+    def _round(self, x):
+        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+
+    def filter(self, x):
+        """``B x`` (rounded to ``dtype`` once)"""
+        return self._round(fir_time(x, self.taps))
+
+    def _prepared(self, d_syn, d_obs, weights):
+        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
+        if s.ndim != 2 or s.shape != d.shape:
+            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
+        return self.filter(s), self.filter(d), WeightedL2._weights(weights, s.shape)
+
+
+class _PerTrace(_Prefiltered):
+    """... and the sums over traces on top: the weighted gathers ``sh = M . s'`` and ``dh = M . d'``, the weights per trace
+    (the shot loop hands them ``Shot.trace_weights``) and the way from ``g`` to the residual ``B g``."""
+
+    def filter(self, x):
+        """``B x`` (rounded to ``dtype`` once; without taps a copy of x)"""
+        return fir_time(x, None) if self.taps is None else self._round(fir_time(x, self.taps))
+
+    def _weighted(self, d_syn, d_obs, weights):
+        """``(sh, dh, M)``"""
+        sh, dh, M = self._prepared(d_syn, d_obs, weights)
+        return (sh, dh, M) if M is None else (M * sh, M * dh, M)
+
+    @staticmethod
+    def _trace_weights(trace_weights, ntr):
+        """``w``: the checked weights per trace, or ones"""
+        w = np.ones(ntr) if trace_weights is None else np.asarray(trace_weights, np.float64)
+        if w.shape != (ntr,):
+            raise ValueError("trace_weights have shape %r, the data %d traces" % (w.shape, ntr))
+        if not np.all(np.isfinite(w)) or np.any(w < 0.0):
+            raise ValueError("trace_weights must be finite and >= 0")
+        return w
+
+    def _residual(self, g, weights):
+        """``B`` (``M . g`` rounded to ``dtype`` once)"""
+        g = self._round(g if weights is None else np.asarray(weights, np.float64) * g)
+        return g if self.taps is None else fir_time(g, self.taps)
+
+    def host(self, d_syn, shot, i):
+        return self(d_syn, shot.d_obs, shot.weights, shot.trace_weights)
 
 
 def _conv_time(x, f, transpose=False):
@@ -271,7 +335,7 @@ def _conv_time(x, f, transpose=False):
     return out
 
 
-class MatchedL2:
+class MatchedL2(_Prefiltered):
     """The matching-filter misfit of the module's definition in fp64 NumPy, and the ``objective=`` that
     ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_matched`` replaces it by the device path).
 
@@ -292,8 +356,7 @@ class MatchedL2:
         if mu_all.ndim != 1 or not np.all(np.isfinite(mu_all)) or np.any(mu_all < 0.0):
             raise ValueError("mu must be finite and >= 0 (a number, or one per shot)")
         self.mu = float(mu) if np.ndim(mu) == 0 else mu_all
-        self.taps = _checked_taps(taps)
-        self.dtype = None if dtype is None else np.dtype(dtype)
+        self._band(taps, dtype)
         self.filters = {}
 
     def mu_of(self, shot=None):
@@ -304,16 +367,14 @@ class MatchedL2:
             raise ValueError("mu is given per shot: the call needs shot=")
         return float(self.mu[shot])
 
-    def filter(self, x):
-        """``B x`` (rounded to ``dtype`` once)"""
-        y = fir_time(x, self.taps)
-        return y if self.dtype is None else y.astype(self.dtype).astype(np.float64)
+    engine_method = "misfit_matched"
 
-    def _prepared(self, d_syn, d_obs, weights):
-        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
-        if s.ndim != 2 or s.shape != d.shape:
-            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
-        return self.filter(s), self.filter(d), WeightedL2._weights(weights, s.shape)
+    def device(self, engine, shot, i):
+        J, self.filters[i] = engine.misfit_matched(shot.d_obs, self.L, self.mu_of(i), shot.weights, self.taps)
+        return J
+
+    def host(self, d_syn, shot, i):
+        return self(d_syn, shot.d_obs, shot.weights, shot=i)
 
     def normal(self, d_syn, d_obs, weights=None):
         """``(G, b)`` of the definition: ``G`` is ``K x K``, symmetric, without ``mu``."""
@@ -439,7 +500,7 @@ def envelope_floor(d_obs, percent=1.0):
     return float(percent) / 100.0 * (float(np.max(np.abs(d))) if d.size else 0.0)
 
 
-class EnvelopeL2:
+class EnvelopeL2(_Prefiltered):
     """The envelope misfit of the module's definition in fp64 NumPy, ``objective(d_syn, d_obs, weights=None) -> (J, r)``,
     and the ``objective=`` that ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_envelope`` replaces
     it by the device path).
@@ -461,19 +522,18 @@ class EnvelopeL2:
             raise ValueError("eps must be finite and >= 0, and > 0 for power 1")
         self.eps = None if eps is None else float(eps)
         self.floor_percent = float(floor_percent)
-        self.taps = _checked_taps(taps)
-        self.dtype = None if dtype is None else np.dtype(dtype)
+        self._band(taps, dtype)
 
     def eps_of(self, d_obs):
         """the floor of a shot: ``eps``, or :func:`envelope_floor` of its observed data"""
         return self.eps if self.eps is not None else envelope_floor(d_obs, self.floor_percent)
 
-    def _round(self, x):
-        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+    engine_method = "misfit_envelope"
 
-    def filter(self, x):
-        """``B x`` (rounded to ``dtype`` once)"""
-        return self._round(fir_time(x, self.taps))
+    def device(self, engine, shot, i):
+        return engine.misfit_envelope(shot.d_obs, self.hilbert, self.power, self.eps_of(shot.d_obs), shot.weights, self.taps)
+
+    host = WeightedL2.host
 
     def envelope2(self, x1, eps):
         """``(E(x')^2, H x')`` of an already filtered gather"""
@@ -481,14 +541,10 @@ class EnvelopeL2:
         return x1 * x1 + (hx * hx + eps * eps), hx
 
     def __call__(self, d_syn, d_obs, weights=None):
-        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
-        if s.ndim != 2 or s.shape != d.shape:
-            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
-        M = WeightedL2._weights(weights, s.shape)
-        eps = self.eps_of(d)
+        s1, d1, M = self._prepared(d_syn, d_obs, weights)
+        eps = self.eps_of(np.asarray(d_obs, np.float64))
         if self.power == 1 and not eps > 0.0:
             raise ValueError("power 1 needs eps > 0")
-        s1, d1 = self.filter(s), self.filter(d)
         es2, hs = self.envelope2(s1, eps)
         ed2, _ = self.envelope2(d1, eps)
         if self.power == 1:
@@ -516,7 +572,7 @@ def correlation_floor(d_obs, percent=1.0):
     return float(percent) / 100.0 * (float(np.sqrt(np.max(np.sum(d * d, axis=0)))) if d.size else 0.0)
 
 
-class NormalizedCorrelation:
+class NormalizedCorrelation(_PerTrace):
     """The trace-normalised correlation misfit of the module's definition in fp64 NumPy,
     ``objective(d_syn, d_obs, weights=None, trace_weights=None) -> (J, r)``, and the ``objective=`` that
     ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_correlation`` replaces it by the device path;
@@ -536,42 +592,26 @@ class NormalizedCorrelation:
             raise ValueError("floor_percent must be finite and >= 0")
         self.eps = None if eps is None else float(eps)
         self.floor_percent = float(floor_percent)
-        self.taps = _checked_taps(taps)
-        self.dtype = None if dtype is None else np.dtype(dtype)
+        self._band(taps, dtype)
         self.correlations = None
 
     def eps_of(self, d_obs):
         """the floor of a shot: ``eps``, or :func:`correlation_floor` of its observed data"""
         return self.eps if self.eps is not None else correlation_floor(d_obs, self.floor_percent)
 
-    def _round(self, x):
-        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+    engine_method = "misfit_correlation"
 
-    def filter(self, x):
-        """``B x`` (rounded to ``dtype`` once; without taps a copy of x)"""
-        return fir_time(x, None) if self.taps is None else self._round(fir_time(x, self.taps))
+    def device(self, engine, shot, i):
+        return engine.misfit_correlation(shot.d_obs, self.eps_of(shot.d_obs), shot.weights, self.taps, shot.trace_weights)
 
     def sums(self, d_syn, d_obs, weights=None):
         """``(a, b, c, sh, dh)`` of the definition: the per-trace sums and the weighted, filtered gathers"""
-        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
-        if s.ndim != 2 or s.shape != d.shape:
-            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
-        M = WeightedL2._weights(weights, s.shape)
-        sh, dh = self.filter(s), self.filter(d)
-        if M is not None:
-            sh, dh = M * sh, M * dh
+        sh, dh, _ = self._weighted(d_syn, d_obs, weights)
         return np.sum(sh * sh, axis=0), np.sum(dh * dh, axis=0), np.sum(sh * dh, axis=0), sh, dh
 
     def __call__(self, d_syn, d_obs, weights=None, trace_weights=None):
         a, b, c, sh, dh = self.sums(d_syn, d_obs, weights)
-        ntr = a.size
-        w = np.ones(ntr)
-        if trace_weights is not None:
-            w = np.asarray(trace_weights, np.float64)
-            if w.shape != (ntr,):
-                raise ValueError("trace_weights have shape %r, the data %d traces" % (w.shape, ntr))
-            if not np.all(np.isfinite(w)) or np.any(w < 0.0):
-                raise ValueError("trace_weights must be finite and >= 0")
+        w = self._trace_weights(trace_weights, a.size)
         eps = self.eps_of(d_obs)
         a2, b2 = a + eps * eps, b + eps * eps
         counts = (b > 0.0) & (a2 > 0.0)
@@ -580,14 +620,10 @@ class NormalizedCorrelation:
         alpha = np.where(counts, -w / nn, 0.0)
         beta = np.where(counts, c / np.where(counts, a2, 1.0), 0.0)
         self.correlations = rho
-        g = alpha * (dh - beta * sh)
-        if weights is not None:
-            g = np.asarray(weights, np.float64) * g
-        g = self._round(g)
-        return float(np.sum(np.where(counts, w * (1.0 - rho), 0.0))), (g if self.taps is None else fir_time(g, self.taps))
+        return float(np.sum(np.where(counts, w * (1.0 - rho), 0.0))), self._residual(alpha * (dh - beta * sh), weights)
 
 
-class TraveltimeL2:
+class TraveltimeL2(_PerTrace):
     """The cross-correlation traveltime misfit of the module's definition in fp64 NumPy,
     ``objective(d_syn, d_obs, weights=None, trace_weights=None) -> (J, r)``, and the ``objective=`` that
     ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_traveltime`` replaces it by the device path;
@@ -609,29 +645,20 @@ class TraveltimeL2:
             raise ValueError("max_lag must be an integer number of samples in [1, %d]" % K_MAX)
         self.dt = float(dt)
         self.max_lag = int(max_lag)
-        self.taps = _checked_taps(taps)
-        self.dtype = None if dtype is None else np.dtype(dtype)
+        self._band(taps, dtype)
         self.delays = self.lags = self.counts = None
 
-    def _round(self, x):
-        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+    engine_method = "misfit_traveltime"
 
-    def filter(self, x):
-        """``B x`` (rounded to ``dtype`` once; without taps a copy of x)"""
-        return fir_time(x, None) if self.taps is None else self._round(fir_time(x, self.taps))
+    def device(self, engine, shot, i):
+        return engine.misfit_traveltime(shot.d_obs, self.max_lag, shot.weights, self.taps, shot.trace_weights)
 
     def correlations(self, d_syn, d_obs, weights=None, majorants=True):
         """``(c, A, sh, dh)``: ``c[k + Ke, j] = c_j(k)`` of the definition for ``k = -Ke .. Ke``, its majorant
         ``A[k + Ke, j] = sum_n |sh[n + k, j]| |dh[n, j]|`` (None without ``majorants``) and the weighted, filtered
         gathers"""
-        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
-        if s.ndim != 2 or s.shape != d.shape:
-            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
-        M = WeightedL2._weights(weights, s.shape)
-        sh, dh = self.filter(s), self.filter(d)
-        if M is not None:
-            sh, dh = M * sh, M * dh
-        nt, ntr = s.shape
+        sh, dh, _ = self._weighted(d_syn, d_obs, weights)
+        nt, ntr = sh.shape
         Ke = max(min(self.max_lag, nt - 1), 0)
         c, A = np.zeros((2 * Ke + 1, ntr)), (np.zeros((2 * Ke + 1, ntr)) if majorants else None)
         ash, adh = (np.abs(sh), np.abs(dh)) if majorants else (None, None)
@@ -647,13 +674,7 @@ class TraveltimeL2:
         ``(c-, c0, c+)`` stacked behind them in ``coef[3:6]``, and the trace weights as used"""
         nlag, ntr = c.shape
         Ke = (nlag - 1) // 2
-        w = np.ones(ntr)
-        if trace_weights is not None:
-            w = np.asarray(trace_weights, np.float64)
-            if w.shape != (ntr,):
-                raise ValueError("trace_weights have shape %r, the data %d traces" % (w.shape, ntr))
-            if not np.all(np.isfinite(w)) or np.any(w < 0.0):
-                raise ValueError("trace_weights must be finite and >= 0")
+        w = self._trace_weights(trace_weights, ntr)
         if ntr == 0:
             return np.zeros(0, np.int32), np.zeros(0, bool), np.zeros(0), np.zeros((6, 0)), w
         q = np.argmax(c, axis=0)  # the first maximum
@@ -688,17 +709,13 @@ class TraveltimeL2:
                 rows = m - lags[None, :].astype(np.int64) + off
                 ok = (rows >= 0) & (rows < nt)
                 g += coef[i] * np.where(ok, np.take_along_axis(dh, np.clip(rows, 0, nt - 1), axis=0), 0.0)
-        if weights is not None:
-            g = np.asarray(weights, np.float64) * g
-        g = self._round(g)
-        J = float(np.sum(np.where(counts, 0.5 * w * (tau * tau), 0.0)))
-        return J, (g if self.taps is None else fir_time(g, self.taps))
+        return float(np.sum(np.where(counts, 0.5 * w * (tau * tau), 0.0))), self._residual(g, weights)
 
 
 OT_TRANSFORMS = {"linear": 0, "softplus": 1}  # FWI_OT_LINEAR, FWI_OT_SOFTPLUS
 
 
-class TransportW2:
+class TransportW2(_PerTrace):
     """The trace-by-trace optimal-transport (W2) misfit of the module's definition in fp64 NumPy,
     ``objective(d_syn, d_obs, weights=None, trace_weights=None) -> (J, r)``, and the ``objective=`` that
     ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_transport`` replaces it by the device path; the
@@ -729,8 +746,7 @@ class TransportW2:
         self.transform = transform
         self.param = None if param is None else float(param)
         self.sharpness, self.factor = float(sharpness), float(factor)
-        self.taps = _checked_taps(taps)
-        self.dtype = None if dtype is None else np.dtype(dtype)
+        self._band(taps, dtype)
         self.distances = self.counts = None
 
     def param_of(self, d_obs):
@@ -743,12 +759,11 @@ class TransportW2:
             raise ValueError("d_obs is all zero or not finite: give param")
         return self.sharpness / peak if self.transform == "softplus" else self.factor * peak
 
-    def _round(self, x):
-        return x if self.dtype is None else x.astype(self.dtype).astype(np.float64)
+    engine_method = "misfit_transport"
 
-    def filter(self, x):
-        """``B x`` (rounded to ``dtype`` once; without taps a copy of x)"""
-        return fir_time(x, None) if self.taps is None else self._round(fir_time(x, self.taps))
+    def device(self, engine, shot, i):
+        return engine.misfit_transport(shot.d_obs, self.transform, self.param_of(shot.d_obs), shot.weights, self.taps,
+                                       shot.trace_weights)
 
     def positive(self, x, param):
         """``(P(x), P'(x))`` of the transform"""
@@ -763,13 +778,7 @@ class TransportW2:
         """``(F, G, f, g, S_s, S_d, counts, dP, M)``: the normalised CDFs and densities ``(nt, ntr)``, the masses, which
         traces count, ``P'(sh)`` and the weights as used.  A trace that does not count is given uniform densities, so
         that everything downstream of it stays finite; its results are zeroed by the caller."""
-        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
-        if s.ndim != 2 or s.shape != d.shape:
-            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
-        M = WeightedL2._weights(weights, s.shape)
-        sh, dh = self.filter(s), self.filter(d)
-        if M is not None:
-            sh, dh = M * sh, M * dh
+        sh, dh, M = self._weighted(d_syn, d_obs, weights)
         param = self.param_of(d_obs) if param is None else float(param)
         p, dP = self.positive(sh, param)
         q, _ = self.positive(dh, param)
@@ -823,24 +832,14 @@ class TransportW2:
 
     def __call__(self, d_syn, d_obs, weights=None, trace_weights=None):
         F, G, f, g, Ss, _, counts, dP, M = self.cdfs(d_syn, d_obs, weights)
-        nt, ntr = F.shape
-        w = np.ones(ntr)
-        if trace_weights is not None:
-            w = np.asarray(trace_weights, np.float64)
-            if w.shape != (ntr,):
-                raise ValueError("trace_weights have shape %r, the data %d traces" % (w.shape, ntr))
-            if not np.all(np.isfinite(w)) or np.any(w < 0.0):
-                raise ValueError("trace_weights must be finite and >= 0")
+        w = self._trace_weights(trace_weights, F.shape[1])
         phi, psi = self.potentials(F, G)
         dt2 = self.dt * self.dt
         phibar = np.sum(phi * f, axis=0)
         W = np.where(counts, dt2 * (phibar + np.sum(psi * g, axis=0)), 0.0)
         self.distances, self.counts = W, counts
         src = np.where(counts, 0.5 * w * dt2 / Ss, 0.0) * (phi - phibar) * dP
-        if M is not None:
-            src = M * src
-        src = self._round(src)
-        return float(np.sum(0.5 * w * W)), (src if self.taps is None else fir_time(src, self.taps))
+        return float(np.sum(0.5 * w * W)), self._residual(src, M)
 
 
 def matched_wavelet(wavelet, f):

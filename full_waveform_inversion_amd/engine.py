@@ -241,17 +241,35 @@ class Engine:
             tp, R = taps.ctypes.data_as(C.c_void_p), taps.size - 1
         return wp, tp, R, (weights, taps)
 
+    def _trace_weights(self, trace_weights):
+        """(pointer, array) of the weights per trace, (None, None) without any"""
+        if trace_weights is None:
+            return None, None
+        tw = np.ascontiguousarray(trace_weights, dtype=np.float64)
+        if tw.shape != (self._nrec,):
+            raise ValueError("trace_weights must hold one weight per trace, shape (%d,)" % self._nrec)
+        return tw.ctypes.data_as(C.c_void_p), tw
+
+    def _per_trace(self, wanted, *dtypes):
+        """(arrays, pointers) of the optional outputs per trace: zeros of these dtypes, or no arrays and null pointers"""
+        arrays = tuple(np.zeros(self._nrec, t) for t in dtypes) if wanted else ()
+        return arrays, tuple(a.ctypes.data_as(C.c_void_p) for a in arrays) or (None,) * len(dtypes)
+
+    def _misfit(self, fn, d_obs, weights, taps, mid=(), outs=()):
+        """J of the data misfit ``fn(ctx, d_obs, weights, taps, R, *mid, &J, *outs)`` of the last forward's seismograms"""
+        d_obs = self._host(d_obs, (self._nt, self._nrec))
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        J = C.c_double(0.0)
+        self._chk(fn(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, *mid, C.byref(J), *outs))
+        return J.value
+
     def misfit_weighted(self, d_obs, weights=None, taps=None):
         """``J = 1/2 ||M . B (d_syn - d_obs)||^2`` for the last forward's seismograms: ``B`` the symmetric FIR filter along
         time with the one-sided ``taps`` ``b_0 .. b_R`` (None: the identity), ``M`` the ``weights >= 0`` of the data's
         shape (None: 1; a negative weight is NOT refused on the device and acts as its absolute value).  The adjoint
         source ``B (M^2 . B (d_syn - d_obs))`` is formed on the device and kept there for ``adjoint(None)``
         (``fwi_misfit_weighted``; the NumPy twin is :class:`datafit.WeightedL2`)."""
-        d_obs = self._host(d_obs, (self._nt, self._nrec))
-        wp, tp, R, _keep = self._data_args(weights, taps)
-        J = C.c_double(0.0)
-        self._chk(self._lib.fwi_misfit_weighted(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, C.byref(J)))
-        return J.value
+        return self._misfit(self._lib.fwi_misfit_weighted, d_obs, weights, taps)
 
     def misfit_matched(self, d_obs, L, mu, weights=None, taps=None, f=None, normal=False):
         """Matching-filter (source-independent) misfit of the last forward's seismograms: with ``s' = B d_syn``,
@@ -262,8 +280,6 @@ class Engine:
         given ``2 L + 1`` coefficients are used.  ``mu >= 0`` is absolute (``datafit.prewhitening``).  ``weights`` and
         ``taps`` as in :meth:`misfit_weighted`.  Returns ``(J, f)``, with ``normal=True`` ``(J, f, G, b)``, ``G`` the
         ``K x K`` normal matrix without ``mu`` (``fwi_misfit_matched``; the NumPy twin is :class:`datafit.MatchedL2`)."""
-        d_obs = self._host(d_obs, (self._nt, self._nrec))
-        wp, tp, R, _keep = self._data_args(weights, taps)
         if int(L) != L:
             raise ValueError("L must be an integer")
         L = int(L)
@@ -276,13 +292,11 @@ class Engine:
             fp = f.ctypes.data_as(C.c_void_p)
         f_out = np.zeros(K)
         nrm = np.zeros(K * K + K) if normal else None
-        J = C.c_double(0.0)
-        self._chk(self._lib.fwi_misfit_matched(
-            self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, L, float(mu), fp, f_out.ctypes.data_as(C.c_void_p),
-            nrm.ctypes.data_as(C.c_void_p) if normal else None, C.byref(J)))
+        J = self._misfit(self._lib.fwi_misfit_matched, d_obs, weights, taps, (
+            L, float(mu), fp, f_out.ctypes.data_as(C.c_void_p), nrm.ctypes.data_as(C.c_void_p) if normal else None))
         if normal:
-            return J.value, f_out, nrm[:K * K].reshape(K, K).copy(), nrm[K * K:].copy()
-        return J.value, f_out
+            return J, f_out, nrm[:K * K].reshape(K, K).copy(), nrm[K * K:].copy()
+        return J, f_out
 
     def misfit_envelope(self, d_obs, hilbert, power=1, eps=None, weights=None, taps=None):
         """Envelope misfit of the last forward's seismograms: with ``s' = B d_syn``, ``d' = B d_obs``, ``H`` the
@@ -295,17 +309,13 @@ class Engine:
         if eps is None:
             from .datafit import envelope_floor
             eps = envelope_floor(d_obs)
-        d_obs = self._host(d_obs, (self._nt, self._nrec))
-        wp, tp, R, _keep = self._data_args(weights, taps)
         h = np.ascontiguousarray(hilbert, dtype=np.float64)
         if h.ndim != 1 or h.size < 1:
             raise ValueError("hilbert must be the 1-D array h_1 .. h_Q")
         if int(power) != power:
             raise ValueError("power must be 1 or 2")
-        J = C.c_double(0.0)
-        self._chk(self._lib.fwi_misfit_envelope(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R,
-                                                h.ctypes.data_as(C.c_void_p), h.size, int(power), float(eps), C.byref(J)))
-        return J.value
+        return self._misfit(self._lib.fwi_misfit_envelope, d_obs, weights, taps,
+                            (h.ctypes.data_as(C.c_void_p), h.size, int(power), float(eps)))
 
     def misfit_correlation(self, d_obs, eps=None, weights=None, taps=None, trace_weights=None, per_trace=False):
         """Trace-normalised zero-lag correlation misfit of the last forward's seismograms, which reads phase only and
@@ -320,19 +330,10 @@ class Engine:
         if eps is None:
             from .datafit import correlation_floor
             eps = correlation_floor(d_obs)
-        d_obs = self._host(d_obs, (self._nt, self._nrec))
-        wp, tp, R, _keep = self._data_args(weights, taps)
-        twp = None
-        if trace_weights is not None:
-            tw = np.ascontiguousarray(trace_weights, dtype=np.float64)
-            if tw.shape != (self._nrec,):
-                raise ValueError("trace_weights must hold one weight per trace, shape (%d,)" % self._nrec)
-            twp = tw.ctypes.data_as(C.c_void_p)
-        rho = np.zeros(self._nrec) if per_trace else None
-        J = C.c_double(0.0)
-        self._chk(self._lib.fwi_misfit_correlation(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, twp, float(eps),
-                                                   C.byref(J), rho.ctypes.data_as(C.c_void_p) if per_trace else None))
-        return (J.value, rho) if per_trace else J.value
+        twp, _keep = self._trace_weights(trace_weights)
+        out, outp = self._per_trace(per_trace, np.float64)
+        J = self._misfit(self._lib.fwi_misfit_correlation, d_obs, weights, taps, (twp, float(eps)), outp)
+        return (J,) + out if per_trace else J
 
     def misfit_traveltime(self, d_obs, max_lag, weights=None, taps=None, trace_weights=None, per_trace=False):
         """Cross-correlation traveltime misfit of the last forward's seismograms, which measures how late every trace is:
@@ -346,23 +347,12 @@ class Engine:
         kept there for ``adjoint(None)``.  Returns J, with ``per_trace=True`` ``(J, tau, lag)``: the ``ntr`` delays in
         seconds and the picked lags ``k*`` of every trace, counting or not (``fwi_misfit_traveltime``; the NumPy twin is
         :class:`datafit.TraveltimeL2`)."""
-        d_obs = self._host(d_obs, (self._nt, self._nrec))
-        wp, tp, R, _keep = self._data_args(weights, taps)
         if int(max_lag) != max_lag:
             raise ValueError("max_lag must be an integer number of samples")
-        twp = None
-        if trace_weights is not None:
-            tw = np.ascontiguousarray(trace_weights, dtype=np.float64)
-            if tw.shape != (self._nrec,):
-                raise ValueError("trace_weights must hold one weight per trace, shape (%d,)" % self._nrec)
-            twp = tw.ctypes.data_as(C.c_void_p)
-        tau = np.zeros(self._nrec) if per_trace else None
-        lag = np.zeros(self._nrec, np.int32) if per_trace else None
-        J = C.c_double(0.0)
-        self._chk(self._lib.fwi_misfit_traveltime(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, twp, int(max_lag),
-                                                  C.byref(J), tau.ctypes.data_as(C.c_void_p) if per_trace else None,
-                                                  lag.ctypes.data_as(C.c_void_p) if per_trace else None))
-        return (J.value, tau, lag) if per_trace else J.value
+        twp, _keep = self._trace_weights(trace_weights)
+        out, outp = self._per_trace(per_trace, np.float64, np.int32)
+        J = self._misfit(self._lib.fwi_misfit_traveltime, d_obs, weights, taps, (twp, int(max_lag)), outp)
+        return (J,) + out if per_trace else J
 
     def misfit_transport(self, d_obs, transform="softplus", param=None, weights=None, taps=None, trace_weights=None,
                          per_trace=False):
@@ -383,22 +373,11 @@ class Engine:
         if param is None:
             from .datafit import TransportW2
             param = TransportW2(self.dt, transform).param_of(d_obs)
-        d_obs = self._host(d_obs, (self._nt, self._nrec))
-        wp, tp, R, _keep = self._data_args(weights, taps)
-        twp = None
-        if trace_weights is not None:
-            tw = np.ascontiguousarray(trace_weights, dtype=np.float64)
-            if tw.shape != (self._nrec,):
-                raise ValueError("trace_weights must hold one weight per trace, shape (%d,)" % self._nrec)
-            twp = tw.ctypes.data_as(C.c_void_p)
-        w2 = np.zeros(self._nrec) if per_trace else None
-        counts = np.zeros(self._nrec, np.int32) if per_trace else None
-        J = C.c_double(0.0)
-        self._chk(self._lib.fwi_misfit_transport(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R, twp,
-                                                 _lib.OT_TRANSFORMS[transform], float(param), C.byref(J),
-                                                 w2.ctypes.data_as(C.c_void_p) if per_trace else None,
-                                                 counts.ctypes.data_as(C.c_void_p) if per_trace else None))
-        return (J.value, w2, counts) if per_trace else J.value
+        twp, _keep = self._trace_weights(trace_weights)
+        out, outp = self._per_trace(per_trace, np.float64, np.int32)
+        J = self._misfit(self._lib.fwi_misfit_transport, d_obs, weights, taps,
+                         (twp, _lib.OT_TRANSFORMS[transform], float(param)), outp)
+        return (J,) + out if per_trace else J
 
     def residual_weight(self, weights=None, taps=None):
         """The residual on the device (what ``born`` or a misfit call left for ``adjoint(None)``) := ``B M^2 B`` residual,

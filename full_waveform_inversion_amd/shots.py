@@ -298,35 +298,18 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     ``objective(d_syn, d_obs) -> (J, dJ/dd_syn)``; default least squares 1/2 ||d_syn - d_obs||^2
     (see objectives.py for the reference's similarity measures as misfits).
 
-    A :class:`datafit.WeightedL2` objective (band-limited, weighted least squares) is handed each shot's
-    ``Shot.weights``; under ``device_l2`` an engine that has ``misfit_weighted`` forms its residual on the device too.
+    An objective of :mod:`datafit` -- ``WeightedL2``, ``MatchedL2``, ``EnvelopeL2``, ``NormalizedCorrelation``,
+    ``TraveltimeL2``, ``TransportW2`` or a subclass of one -- names its own two calls.  ``objective.host(d_syn, shot, i)``
+    is the NumPy twin with what its class takes from the shot: ``Shot.weights``, for the three sums over traces
+    ``Shot.trace_weights`` as well, for the matching filter ``shot=i``.  Under ``device_l2``, an engine that has the
+    method ``objective.engine_method`` (``misfit_weighted`` ... ``misfit_transport``) is called through
+    ``objective.device(engine, shot, i)`` instead: misfit and adjoint source are formed on the device, per node, or per
+    off-grid point where the engine spreads them.
 
-    A :class:`datafit.MatchedL2` objective (matching-filter, source-independent misfit) is handed ``Shot.weights`` as
-    well; an engine that has ``misfit_matched`` estimates and applies each shot's filter on the device, otherwise the
-    NumPy twin does on the host.  Its damping is ``objective.mu``: one number for every shot, or a sequence indexed like
-    ``shots`` (``datafit.prewhitening`` of each shot's data).  Either branch leaves shot ``i``'s filter in
-    ``objective.filters[i]``.
-
-    A :class:`datafit.EnvelopeL2` objective (envelope misfit, against cycle skipping) is handed ``Shot.weights`` too; an
-    engine that has ``misfit_envelope`` forms envelopes, misfit and adjoint source on the device, otherwise the NumPy
-    twin does on the host.  Either branch uses ``objective.eps_of(d_obs)`` as the shot's floor.
-
-    A :class:`datafit.NormalizedCorrelation` objective (trace-normalised correlation: phase only, blind to the gain of a
-    trace) is handed ``Shot.weights`` and ``Shot.trace_weights``; under ``device_l2`` an engine that has
-    ``misfit_correlation`` forms the per-trace sums, the misfit and its adjoint source on the device (per node, or per
-    off-grid point where the engine spreads them), otherwise the NumPy twin does on the host.  Either branch uses
-    ``objective.eps_of(d_obs)`` as the shot's floor.
-
-    A :class:`datafit.TraveltimeL2` objective (cross-correlation traveltime: how late every trace is, blind to its gain)
-    is handed ``Shot.weights`` and ``Shot.trace_weights`` as well; under ``device_l2`` an engine that has
-    ``misfit_traveltime`` forms the correlations over ``objective.max_lag`` lags, the delays, the misfit and its adjoint
-    source on the device, otherwise the NumPy twin does on the host.  ``objective.dt`` must be the engine's time step.
-
-    A :class:`datafit.TransportW2` objective (trace-by-trace optimal transport: whole traces as densities along time) is
-    handed ``Shot.weights`` and ``Shot.trace_weights`` as well; under ``device_l2`` an engine that has
-    ``misfit_transport`` forms the densities, the potentials, the misfit and its adjoint source on the device, otherwise
-    the NumPy twin does on the host.  Either branch uses ``objective.param_of(d_obs)`` as the shot's parameter;
-    ``objective.dt`` must be the engine's time step.
+    Either branch uses the same per-shot numbers, which depend on the data only: ``objective.mu_of(i)`` (one damping for
+    every shot, or a sequence indexed like ``shots``), ``objective.eps_of(d_obs)``, ``objective.param_of(d_obs)``; either
+    leaves shot ``i``'s matching filter in ``objective.filters[i]``.  ``objective.dt`` of a traveltime or transport
+    objective must be the engine's time step.
 
     ``device_l2`` (least squares only): form the residual and J on the device (``fwi_misfit_l2``) -- in the
     engine's dtype, i.e. with an fp32 engine ``d_obs`` is rounded to fp32 before the subtraction, which puts
@@ -353,65 +336,23 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
 def _sweep_shots(engine, shots, ex, objective, device_l2=True):
     """forward + adjoint of this rank's shots; returns the misfit, gradients summed into the
     (primary) engine's accumulator."""
-    from .datafit import EnvelopeL2, MatchedL2, NormalizedCorrelation, TransportW2, TraveltimeL2, WeightedL2
     from .objectives import l2
-    weighted = isinstance(objective, WeightedL2)
-    matched = isinstance(objective, MatchedL2)
-    enveloped = isinstance(objective, EnvelopeL2)
-    correlated = isinstance(objective, NormalizedCorrelation)
-    timed = isinstance(objective, TraveltimeL2)
-    transported = isinstance(objective, TransportW2)
+    # a datafit objective names its device call and its host call itself (datafit.WeightedL2.device, .host); plain least
+    # squares is a function with a device path, any other callable has none
+    own = hasattr(objective, "engine_method")
+    method = objective.engine_method if own else "misfit_l2" if objective is l2 else None
 
     def one(e, i):
         s = shots[i]
         if s.d_obs is None:
             raise ValueError("shot %d has no observed data on rank %d" % (i, ex.rank))
         d = s.forward(e, save=True)
-        if device_l2 and objective is l2 and hasattr(e, "misfit_l2") and (s.rec_spread is None or s._on_device(e)):
-            # least squares: residual and misfit are formed on the device (per node, or per off-grid point)
-            j = e.misfit_l2(s.d_obs)
+        if device_l2 and method and hasattr(e, method) and (s.rec_spread is None or s._on_device(e)):
+            # misfit and adjoint source are formed on the device (per node, or per off-grid point)
+            j = objective.device(e, s, i) if own else e.misfit_l2(s.d_obs)
             e.adjoint(None)
             return j
-        if device_l2 and weighted and hasattr(e, "misfit_weighted") and (s.rec_spread is None or s._on_device(e)):
-            j = e.misfit_weighted(s.d_obs, s.weights, objective.taps)  # ... filtered and weighted there as well
-            e.adjoint(None)
-            return j
-        if device_l2 and matched and hasattr(e, "misfit_matched") and (s.rec_spread is None or s._on_device(e)):
-            # ... and so is the matching filter: estimated, applied and eliminated there; the shot's f* is kept
-            j, objective.filters[i] = e.misfit_matched(s.d_obs, objective.L, objective.mu_of(i), s.weights, objective.taps)
-            e.adjoint(None)
-            return j
-        if matched:
-            j, r = objective(d, s.d_obs, s.weights, shot=i)
-            s.adjoint(e, r)
-            return j
-        if device_l2 and enveloped and hasattr(e, "misfit_envelope") and (s.rec_spread is None or s._on_device(e)):
-            # ... and so are the envelopes, their misfit and its adjoint source
-            j = e.misfit_envelope(s.d_obs, objective.hilbert, objective.power, objective.eps_of(s.d_obs), s.weights,
-                                  objective.taps)
-            e.adjoint(None)
-            return j
-        if device_l2 and correlated and hasattr(e, "misfit_correlation") and (s.rec_spread is None or s._on_device(e)):
-            # ... and so are the per-trace sums of the normalised correlation, its misfit and its adjoint source
-            j = e.misfit_correlation(s.d_obs, objective.eps_of(s.d_obs), s.weights, objective.taps, s.trace_weights)
-            e.adjoint(None)
-            return j
-        if device_l2 and timed and hasattr(e, "misfit_traveltime") and (s.rec_spread is None or s._on_device(e)):
-            # ... and so are the correlations over the window of lags, the picked delays, their misfit and its adjoint source
-            j = e.misfit_traveltime(s.d_obs, objective.max_lag, s.weights, objective.taps, s.trace_weights)
-            e.adjoint(None)
-            return j
-        if device_l2 and transported and hasattr(e, "misfit_transport") and (s.rec_spread is None or s._on_device(e)):
-            # ... and so are the densities, their CDFs, the potentials, the transport distances and the adjoint source
-            j = e.misfit_transport(s.d_obs, objective.transform, objective.param_of(s.d_obs), s.weights, objective.taps,
-                                   s.trace_weights)
-            e.adjoint(None)
-            return j
-        if correlated or timed or transported:
-            j, r = objective(d, s.d_obs, s.weights, s.trace_weights)
-            s.adjoint(e, r)
-            return j
-        j, r = objective(d, s.d_obs, s.weights) if (weighted or enveloped) else objective(d, s.d_obs)
+        j, r = objective.host(d, s, i) if own else objective(d, s.d_obs)
         s.adjoint(e, r)
         return j
 

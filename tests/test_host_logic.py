@@ -439,3 +439,171 @@ def test_engine_pool_propagates_worker_errors():
     with sh.EnginePool(lambda: OracleEngine(w.shape, w.h, w.dt, w.nt, order=w.order, npml=w.npml), 2) as pool:
         with pytest.raises(ValueError):
             sh.misfit_and_gradient(pool, w.c_init, shots)
+
+
+# -- the shot loop's choice between an objective's device call and its host twin ------------------------------------------
+
+class _Spread:
+    """off-grid receivers the engine does not take: the shot gathers the data and scatters the residual on the host"""
+
+    def __init__(self):
+        self.gathered, self.scattered = [], []
+
+    def gather(self, d):
+        self.gathered.append(d)
+        return d + 1.0
+
+    def scatter(self, r):
+        self.scattered.append(r)
+        return np.full((3, 2), 7.0)
+
+
+def _recording_engine(methods):
+    """forward, adjoint and the named ``misfit_*``, each noting its call; a device misfit returns J = 2.5 (matched: and
+    the filter), the forward a fresh gather"""
+    log = []
+
+    class Fake:
+        def set_model(self, model):
+            pass
+
+        def reset_gradient(self):
+            pass
+
+        def gradient(self, wrt):
+            return np.zeros(1)
+
+        def forward(self, model, src, rec, save=True):
+            log.append(("forward", np.zeros((3, 2))))
+            return log[-1][1]
+
+        def adjoint(self, residual):
+            log.append(("adjoint", residual))
+
+    def device(name):
+        def call(self, *a, **k):
+            log.append((name, a, k))
+            return (2.5, "f*%d" % len(log)) if name == "misfit_matched" else 2.5
+        return call
+
+    for name in methods:
+        setattr(Fake, name, device(name))
+    return Fake(), log
+
+
+def _recording_twin(cls, log, *a, **k):
+    """an objective of class ``cls`` (so: a subclass of it) whose host call notes its arguments and returns J = 1.25"""
+    class Twin(cls):
+        def __call__(self, *args, **kwargs):
+            log.append(("host", args, kwargs))
+            return 1.25, np.full((3, 2), float(len(log)))
+
+    return Twin(*a, **k)
+
+
+def _same_args(got, want):
+    return len(got) == len(want) and all(g is w or (not isinstance(w, np.ndarray) and g is not None and g == w)
+                                         for g, w in zip(got, want))
+
+
+def _loop_cases():
+    from full_waveform_inversion_amd import datafit as df
+    taps = np.array([0.5, 0.25])
+    return {
+        "weighted": ("misfit_weighted", df.WeightedL2, (taps,), {},
+                     lambda o, s, i: (s.d_obs, s.weights, o.taps), lambda s, i: ((s.weights,), {})),
+        "matched": ("misfit_matched", df.MatchedL2, (1, [0.5, 0.75], taps), {},
+                    lambda o, s, i: (s.d_obs, o.L, o.mu_of(i), s.weights, o.taps), lambda s, i: ((s.weights,), {"shot": i})),
+        "envelope": ("misfit_envelope", df.EnvelopeL2, (df.hilbert_taps(3),), {"power": 2, "taps": taps},
+                     lambda o, s, i: (s.d_obs, o.hilbert, o.power, o.eps_of(s.d_obs), s.weights, o.taps),
+                     lambda s, i: ((s.weights,), {})),
+        "correlation": ("misfit_correlation", df.NormalizedCorrelation, (), {"taps": taps},
+                        lambda o, s, i: (s.d_obs, o.eps_of(s.d_obs), s.weights, o.taps, s.trace_weights),
+                        lambda s, i: ((s.weights, s.trace_weights), {})),
+        "traveltime": ("misfit_traveltime", df.TraveltimeL2, (1e-3, 2, taps), {},
+                       lambda o, s, i: (s.d_obs, o.max_lag, s.weights, o.taps, s.trace_weights),
+                       lambda s, i: ((s.weights, s.trace_weights), {})),
+        "transport": ("misfit_transport", df.TransportW2, (1e-3, "linear"), {"taps": taps},
+                      lambda o, s, i: (s.d_obs, o.transform, o.param_of(s.d_obs), s.weights, o.taps, s.trace_weights),
+                      lambda s, i: ((s.weights, s.trace_weights), {})),
+    }
+
+
+def _loop_shots(off_grid):
+    shots = []
+    for i in range(2):
+        s = sh.Shot(np.zeros((1, 2), int), np.zeros(3), np.zeros((2, 2), int), np.full((3, 2), 1.0 + i),
+                    rec_spread=_Spread() if off_grid else None, weights=np.full((3, 2), 0.5))
+        s.trace_weights = np.array([1.0, 2.0 + i])
+        shots.append(s)
+    return shots
+
+
+@pytest.mark.parametrize("mode", ["device", "no_method", "device_l2_off", "off_grid"])
+@pytest.mark.parametrize("name", ["l2", "weighted", "matched", "envelope", "correlation", "traveltime", "transport"])
+def test_shot_loop_calls_the_device_misfit_or_the_host_twin(name, mode):
+    """``misfit_and_gradient`` takes an objective's device call -- the engine's method, once per shot, with the shot's
+    data, weights and the objective's per-shot numbers, then ``adjoint(None)`` -- exactly when ``device_l2`` is on, the
+    engine has the method and the receivers are nodes (or off-grid points the engine takes); otherwise the host twin
+    with the arguments of its class, then ``Shot.adjoint`` of its residual.  Every objective here is an instance of a
+    SUBCLASS of its datafit class (``_recording_twin``): subclasses take their class's path."""
+    from full_waveform_inversion_amd.objectives import l2
+    shots = _loop_shots(off_grid=mode == "off_grid")
+    if name == "l2":
+        method, device_args = "misfit_l2", lambda o, s, i: (s.d_obs,)
+    else:
+        method, cls, a, k, device_args, host_args = _loop_cases()[name]
+    e, log = _recording_engine([] if mode == "no_method" else [method])
+    objective = l2 if name == "l2" else _recording_twin(cls, log, *a, **k)
+    J, _ = sh.misfit_and_gradient(e, np.zeros(1), shots, objective=objective, device_l2=mode != "device_l2_off")
+    calls = iter(enumerate(log))
+    J_want = 0.0
+    for i, s in enumerate(shots):
+        _, fwd = next(calls)
+        assert fwd[0] == "forward"
+        if mode == "device":
+            at, call = next(calls)
+            assert call[0] == method and call[2] == {} and _same_args(call[1], device_args(objective, s, i))
+            _, adj = next(calls)
+            assert adj[0] == "adjoint" and adj[1] is None
+            assert name != "matched" or objective.filters[i] == "f*%d" % (at + 1)
+            J_want += 2.5
+            continue
+        d_syn = fwd[1]
+        if mode == "off_grid":
+            assert len(s.rec_spread.gathered) == 1 and s.rec_spread.gathered[0] is d_syn
+            d_syn = d_syn + 1.0
+        if name == "l2":  # the function itself: nothing to record, J and the residual are its own
+            J_s, r = l2(d_syn, s.d_obs)
+            J_want += J_s
+        else:
+            at, call = next(calls)
+            want_a, want_k = host_args(s, i)
+            assert call[0] == "host" and len(call[1]) == 2 + len(want_a) and call[2] == want_k
+            assert np.array_equal(call[1][0], d_syn) and (mode == "off_grid" or call[1][0] is d_syn)
+            assert call[1][1] is s.d_obs and _same_args(call[1][2:], want_a)
+            r = np.full((3, 2), at + 1.0)
+            J_want += 1.25
+        _, adj = next(calls)
+        assert adj[0] == "adjoint"
+        if mode == "off_grid":
+            assert len(s.rec_spread.scattered) == 1 and np.array_equal(adj[1], np.full((3, 2), 7.0))
+            r_seen = s.rec_spread.scattered[0]
+        else:
+            r_seen = adj[1]
+        assert np.array_equal(r_seen, r)
+    assert next(calls, None) is None and J == J_want
+
+
+def test_shot_loop_hands_a_plain_callable_the_two_gathers_only():
+    shots = _loop_shots(off_grid=False)
+    e, log = _recording_engine(["misfit_l2", "misfit_weighted"])
+    seen = []
+
+    def objective(d_syn, d_obs):
+        seen.append((d_syn, d_obs))
+        return 0.75, np.full((3, 2), 9.0)
+
+    J, _ = sh.misfit_and_gradient(e, np.zeros(1), shots, objective=objective)
+    assert [c[0] for c in log] == ["forward", "adjoint"] * 2 and all(np.all(c[1] == 9.0) for c in log[1::2])
+    assert all(d is log[2 * i][1] and o is s.d_obs for i, (s, (d, o)) in enumerate(zip(shots, seen))) and J == 1.5

@@ -111,15 +111,10 @@ def main():
         ap.error("--match-source L must lie in [0, %d]" % datafit.L_MAX)
     if not (a.match_mu_percent >= 0.0 and np.isfinite(a.match_mu_percent)):
         ap.error("--match-mu-percent P must be finite and >= 0")
-    if a.envelope is not None and a.match_source is not None:
-        ap.error("--envelope and --match-source are two misfits: choose one")
-    if a.correlation is not None and (a.envelope is not None or a.match_source is not None):
-        ap.error("--correlation, --envelope and --match-source are different misfits: choose one")
-    if a.traveltime is not None and (a.correlation is not None or a.envelope is not None or a.match_source is not None):
-        ap.error("--traveltime, --correlation, --envelope and --match-source are different misfits: choose one")
-    if a.transport is not None and (a.traveltime is not None or a.correlation is not None or a.envelope is not None
-                                    or a.match_source is not None):
-        ap.error("--transport, --traveltime, --correlation, --envelope and --match-source are different misfits: choose one")
+    misfits = [flag for flag in ("--transport", "--traveltime", "--correlation", "--envelope", "--match-source")
+               if getattr(a, flag[2:].replace("-", "_")) is not None]
+    if len(misfits) > 1:
+        ap.error("%s are different misfits: choose one" % " and ".join(misfits))
     if a.transport_param is not None and a.transport is None:
         ap.error("--transport-param needs --transport")
     if a.transport_param is not None and not (a.transport_param > 0.0 and np.isfinite(a.transport_param)):
