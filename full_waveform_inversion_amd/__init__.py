@@ -23,7 +23,8 @@ def configure(shape, h, dt, nt_max, **kw):
 
     forward / adjoint / gradient together are an inversion's evaluation, so the engine is the one
     :func:`shots.inversion_engine` makes: fp32 in the low-round-off increment form (1e-5 end to end) unless
-    ``update_form="standard"`` is passed -- the right choice for forward-only modelling, 4 B/update cheaper in 3-D."""
+    ``update_form="standard"`` is passed -- the right choice for forward-only modelling, 4 B/update cheaper in 3-D.
+    ``fourier=freqs`` (and ``fourier_batch``) pass through: the Fourier-compressed forward-term store."""
     global _default
     if _default is not None:
         _default.close()

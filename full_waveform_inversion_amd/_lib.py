@@ -28,6 +28,7 @@ REG_KINDS = {"tikhonov": 0, "tv": 1}
 MATCH_LMAX = 64  # FWI_MATCH_LMAX
 TT_KMAX = 1024  # FWI_TT_KMAX
 OT_TRANSFORMS = {"linear": 0, "softplus": 1}  # FWI_OT_LINEAR, FWI_OT_SOFTPLUS
+FOURIER_FMAX, FOURIER_BMAX = 64, 8  # FWI_FOURIER_FMAX, FWI_FOURIER_BMAX
 UNIQUE_ID_BYTES = 128
 EINVAL = 1
 ERROR_NAMES = {1: "FWI_EINVAL", 2: "FWI_EHIP", 3: "FWI_ESTATE", 4: "FWI_ENOMEM", 5: "FWI_ECOMM"}
@@ -104,6 +105,9 @@ SIGNATURES = {
     "fwi_illumination": (C.c_int, [_P, _I32, _P]),
     "fwi_illumination_vec": (C.c_int, [_P, _I32, _I32]),
     "fwi_allreduce_illumination": (C.c_int, [_P]),
+    "fwi_set_fourier_store": (C.c_int, [_P, _I32, _P, _I32]),
+    "fwi_fourier_spectrum": (C.c_int, [_P, _I32, _P, _P]),
+    "fwi_store_bytes": (C.c_int, [_P, C.POINTER(_I64)]),
     "fwi_vec_mul": (C.c_int, [_P, _I32, _I32]),
     "fwi_vec_recip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_vec_smooth": (C.c_int, [_P, _I32, C.POINTER(_D)]),

@@ -28,6 +28,7 @@
 #include "fwi_ttime.h"
 #include "fwi_envelope.h"
 #include "fwi_gather_tile.h"
+#include "fwi_fourier.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
 #include "fwi_match.h"
@@ -48,6 +49,10 @@ const double COEF8[] = {-205.0 / 72.0, 8.0 / 5.0, -1.0 / 5.0, 8.0 / 315.0, -1.0 
 const double DCOEF2[] = {1.0 / 2.0};
 const double DCOEF4[] = {2.0 / 3.0, -1.0 / 12.0};
 const double DCOEF8[] = {4.0 / 5.0, -1.0 / 5.0, 4.0 / 105.0, -1.0 / 280.0};
+// Fourier store: a frequency within this relative distance of 1 / (2 S dt) is the Nyquist frequency of the sampled axis
+// (weight 1 / N; fourier.NYQUIST_RTOL of the NumPy twin), and none may lie further above it
+constexpr double FOURIER_NYQUIST_RTOL = 1e-9;
+static_assert(FWI_FOURIER_BMAX == FOURIER_BMAX, "batch limit of the ABI and of the kernels");
 
 std::string vformat(const char *fmt, va_list ap) {
     char buf[512];
@@ -133,6 +138,16 @@ struct fwi_ctx {
     // source-side illumination (fwi_set_illumination): compact accumulator of sum q^2 over the imaging steps of every
     // fwi_adjoint(image) since the last fwi_gradient_reset; nullptr = disabled (the default: no launch, no memory)
     void *h_acc = nullptr;
+    // Fourier-compressed forward-term store (fwi_set_fourier_store; fwi_fourier.hip): four_freqs.size() = F > 0 while
+    // it is on.  2 F compact accumulator volumes (Re Q_k, Im Q_k), four_batch + 1 compact ring slots (sample j in slot
+    // j % (four_batch + 1)) and the twiddle table of the running sweep, all allocated by the first fwi_forward(save)
+    std::vector<double> four_freqs;
+    int four_batch = 0;
+    void *four_acc = nullptr, *four_ring = nullptr, *four_tw = nullptr;
+    int four_rows = 0;        // rows per frequency of four_tw: ceil(nt_max / istride) + FOURIER_BMAX - 1
+    bool four_sweep = false;  // the running sweep goes through the Fourier store: one step per launch
+    std::vector<double> four_tw_host;
+    size_t store_held = 0;    // device bytes held for the forward store of whichever kind (fwi_store_bytes)
     // Born modelling (fwi_born): w = dC / C of the last perturbation, compact; allocated by the first fwi_born call
     void *born_w = nullptr;
     // ... on a bf16 store: (nt, nsrc) amplitudes w(x_s) wav^n_s of the source's exact share (launch_born_source_share)
@@ -1025,14 +1040,16 @@ struct Impl {
         }
     }
 
+    // (never on a sweep that writes or reads the Fourier store, fwi_ctx::four_sweep: its transforms sit between single steps)
     static bool use_fused(const fwi_ctx *ctx, int nt) {
-        return ctx->fused2d && nt % FUSED2D_STEPS == 0 && (ctx->ckpt == 0 || ctx->ckpt % FUSED2D_STEPS == 0);
+        return ctx->fused2d && !ctx->four_sweep && nt % FUSED2D_STEPS == 0 &&
+               (ctx->ckpt == 0 || ctx->ckpt % FUSED2D_STEPS == 0);
     }
 
     // Steps taken by the fused kernel when nt is not a multiple of FUSED2D_STEPS (store-all mode only): the
     // first nt - nt % FUSED2D_STEPS; the remaining 1-3 steps go one per launch.  0 = not applicable.
     static int mixed_fused_steps(const fwi_ctx *ctx, int nt) {
-        if (!ctx->fused2d || ctx->ckpt != 0 || nt % FUSED2D_STEPS == 0) return 0;
+        if (!ctx->fused2d || ctx->four_sweep || ctx->ckpt != 0 || nt % FUSED2D_STEPS == 0) return 0;
         return nt - nt % FUSED2D_STEPS;
     }
 
@@ -1232,14 +1249,76 @@ struct Impl {
         return FWI_OK;
     }
 
+    // Fourier store: the accumulators, the ring and the device table, all or nothing, by the first forward(save)
+    static int fourier_alloc(fwi_ctx *ctx) {
+        if (ctx->four_acc) return FWI_OK;
+        const GridDesc &g = ctx->gd;
+        const size_t F = ctx->four_freqs.size(), vol = (size_t)g.npts * sizeof(T);
+        const int rows = (ctx->cfg.nt_max + ctx->istride - 1) / ctx->istride + FOURIER_BMAX - 1;
+        struct { void **p; size_t bytes; } want[] = {{&ctx->four_acc, 2 * F * vol},
+                                                     {&ctx->four_ring, (size_t)(ctx->four_batch + 1) * vol},
+                                                     {&ctx->four_tw, F * rows * 2 * sizeof(double)}};
+        size_t total = 0, fr = 0, tot = 0;
+        for (auto &w : want) total += w.bytes;
+        HIPCHK(ctx, hipMemGetInfo(&fr, &tot));
+        hipError_t e = hipSuccess;
+        if (total <= fr)
+            for (auto &w : want)
+                // (zeroed: the pad columns of a ring slot are the step kernels' to write or to leave)
+                if ((e = hipMalloc(w.p, w.bytes)) != hipSuccess ||
+                    (e = hipMemsetAsync(*w.p, 0, w.bytes, ctx->stream)) != hipSuccess)
+                    break;
+        if (total > fr || e != hipSuccess) {
+            (void)hipGetLastError();
+            for (auto &w : want) {
+                if (*w.p) (void)hipFree(*w.p);
+                *w.p = nullptr;
+            }
+            return ctx->fail(FWI_ENOMEM,
+                             "Fourier forward-term store needs %.1f GiB (%d frequencies, batch %d) but only %.1f GiB are "
+                             "free; fewer frequencies or a smaller batch need less",
+                             total / 1073741824.0, (int)F, ctx->four_batch, fr / 1073741824.0);
+        }
+        ctx->four_rows = rows;
+        ctx->store_held = want[0].bytes + want[1].bytes;
+        return FWI_OK;
+    }
+
+    // The table of one sweep over N = ceil(nt / S) samples, formed in fp64 and uploaded before the time loop begins (a
+    // captured loop then holds launches only): block k, row j = (cos theta_kj, sin theta_kj), theta_kj = 2 pi f_k j S dt
+    // with f_k j S dt reduced to its fractional part first; `synthesis`: both times w_k = 1 / N at f_k = 0 and at the
+    // Nyquist frequency 1 / (2 S dt) of the sampled axis, else 2 / N.  The rows from N on stay zero.
+    static int fourier_table(fwi_ctx *ctx, int nt, bool synthesis) {
+        const int S = ctx->istride, N = (nt + S - 1) / S, rows = ctx->four_rows, F = (int)ctx->four_freqs.size();
+        const double sdt = (double)S * ctx->cfg.dt;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the upload of the sweep before may still read the host copy
+        std::vector<double> &t = ctx->four_tw_host;
+        t.assign((size_t)F * rows * 2, 0.0);
+        for (int k = 0; k < F; ++k) {
+            const double f = ctx->four_freqs[k];
+            const bool edge = f == 0.0 || std::fabs(2.0 * f * sdt - 1.0) <= FOURIER_NYQUIST_RTOL;
+            const double w = synthesis ? (edge ? 1.0 : 2.0) / N : 1.0;
+            for (int j = 0; j < N; ++j) {
+                const double x = f * sdt * j, th = 2.0 * M_PI * (x - std::floor(x));
+                t[((size_t)k * rows + j) * 2] = w * std::cos(th);
+                t[((size_t)k * rows + j) * 2 + 1] = w * std::sin(th);
+            }
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->four_tw, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        return FWI_OK;
+    }
+
     static int forward(fwi_ctx *ctx, int32_t nt, int32_t nsrc, const int32_t *src_idx,
                        const T *wavelet, int32_t nrec, const int32_t *rec_idx, int32_t save,
                        T *seis_out) {
         const GridDesc &g = ctx->gd;
         const int K = ctx->ckpt;  // 0 = store every step's imaging term, K > 0 = snapshot every K steps
+        const bool four = save && !ctx->four_freqs.empty();  // ... or their Fourier coefficients (K = 0 then)
+        ctx->four_sweep = four;
         int rc;
         if ((rc = upload_points(ctx, nsrc, src_idx, nrec, rec_idx))) return rc;
-        if (save && K == 0 && !ctx->q_store) {
+        if (four && (rc = fourier_alloc(ctx))) return rc;
+        if (save && K == 0 && !four && !ctx->q_store) {
             const size_t slots = ((size_t)ctx->cfg.nt_max + ctx->istride - 1) / ctx->istride;
             const size_t bytes = slots * g.npts * ctx->qes;
             size_t fr = 0, tot = 0;
@@ -1250,6 +1329,7 @@ struct Impl {
                                  "set ckpt_interval (recomputation) or image_stride (decimated imaging)",
                                  bytes / 1073741824.0, ctx->cfg.nt_max, fr / 1073741824.0);
             HIPCHK(ctx, hipMalloc(&ctx->q_store, bytes));
+            ctx->store_held = bytes;
         }
         if (save && K > 0 && !ctx->ckpt_ready) {
             // snapshots of (u^n, u^{n-1}) per segment, K + 1 imaging-term slots, the recomputation's field
@@ -1292,6 +1372,7 @@ struct Impl {
                                  total / 1073741824.0, ctx->cfg.nt_max, K, fr / 1073741824.0);
             }
             ctx->ckpt_ready = true;
+            ctx->store_held = total;
         }
         // the pinned staging buffer at its final size for this shot, before any copy is queued on it
         if ((rc = stage_reserve(ctx, (size_t)nt * std::max(std::max(nsrc, nrec), 1) * sizeof(T)))) return rc;
@@ -1328,6 +1409,10 @@ struct Impl {
         // odd count goes through the single-step kernel)
         const int npair = (ctx->pair3d && !save && base_args(ctx, 0).damp == 0) ? (nt & ~1) : 0;
         if ((fused || nfused || npair) && (rc = zero_fields(ctx, spare[0], spare[1]))) return rc;
+        if (four) {
+            if ((rc = fourier_table(ctx, nt, false))) return rc;
+            HIPCHK(ctx, hipMemsetAsync(ctx->four_acc, 0, 2 * ctx->four_freqs.size() * (size_t)g.npts * sizeof(T), s));
+        }
         TimeLoop loop(ctx);
         if ((rc = loop.begin())) return rc;
         if (npair) {
@@ -1351,6 +1436,21 @@ struct Impl {
                     rc = run_steps(ctx, sw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1),
                                    none, noq);
                 if (rc) return rc;
+            }
+        } else if (four) {
+            // one step per launch; q^{jS} goes to ring slot j % (B + 1), and every B samples (and behind the last, partial
+            // batch) the analysis adds the batch to the accumulators
+            const int ks = ctx->istride, B = ctx->four_batch, R = B + 1, N = (nt + ks - 1) / ks;
+            T *ring = (T *)ctx->four_ring;
+            auto qo = [&](int n) -> T * { return n % ks == 0 ? ring + (size_t)((n / ks) % R) * g.npts : nullptr; };
+            for (int j0 = 0; j0 < N; j0 += B) {
+                const int nb = std::min(B, N - j0), n0 = j0 * ks, n1 = std::min((int)nt, (j0 + nb) * ks);
+                if ((rc = run_steps(ctx, sw, n0, 1, n1 - n0, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1), qo,
+                                    noq)))
+                    return rc;
+                HIPCHK(ctx, launch_fourier_analyse<T>((T *)ctx->four_acc, ring, g.npts, R, j0 % R, j0, nb,
+                                                      (const double *)ctx->four_tw, ctx->four_rows,
+                                                      (int)ctx->four_freqs.size(), s));
             }
         } else if (fused) {
             if ((rc = run_fused(ctx, sw, spare, 0, 1, nt, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1),
@@ -1395,6 +1495,8 @@ struct Impl {
             return rc;  // (residual == nullptr: the one fwi_misfit_l2 left in ctx->amp)
         ctx->have_dev_residual = false;  // consumed: ctx->series is about to be overwritten
         ctx->have_syn = false;           // ... by this sweep's source-side series (fwi_misfit_l2 must not read them)
+        const bool four = image && !ctx->four_freqs.empty();  // imaging against the Fourier store: one step per launch
+        ctx->four_sweep = four;
         const T rs = (T)(1.0 / std::pow(ctx->cfg.h, g.ndim));
         if ((rc = zero_fields(ctx, ctx->u[0], ctx->u[1]))) return rc;
         Sweep sw;
@@ -1412,6 +1514,7 @@ struct Impl {
         const int nfused = mixed_fused_steps(ctx, nt);
         void *spare[2] = {ctx->fx[0], ctx->fx[1]};
         if ((fused || nfused) && (rc = zero_fields(ctx, spare[0], spare[1]))) return rc;
+        if (four && (rc = fourier_table(ctx, nt, true))) return rc;
         TimeLoop loop(ctx);
         if ((rc = loop.begin())) return rc;
         const T *q0 = nullptr;  // q^0, for the last pairing (mu^1 with q^0)
@@ -1513,6 +1616,28 @@ struct Impl {
                 HIPCHK(ctx, hipMemcpyAsync(carry, q_store, (size_t)g.npts * sizeof(T), hipMemcpyDeviceToDevice, s));
             }
             q0 = carry;
+        } else if (four) {
+            // Fourier store: batch by batch (last to first) the synthesis rebuilds the band-limited q~ of the batch's samples
+            // in their ring slots, then the adjoint steps n = (j0 + nb) S - 1 .. j0 S of the batch run with the lagged
+            // pairing.  The first of them pairs with the lowest sample of the batch above: with B + 1 slots that one is
+            // still there (a batch fills B consecutive slots), so nothing is carried.  plan() starts afresh per batch: a
+            // pairing deferred across the boundary would need the second-lowest sample of the batch above, whose slot
+            // this batch's synthesis has just taken.
+            const int ks = ctx->istride, B = ctx->four_batch, R = B + 1, N = (nt + ks - 1) / ks;
+            T *ring = (T *)ctx->four_ring;
+            for (int j0 = ((N - 1) / B) * B; j0 >= 0; j0 -= B) {
+                const int nb = std::min(B, N - j0), lo = j0 * ks, hi = std::min(nt, (j0 + nb) * ks) - 1;
+                HIPCHK(ctx, launch_fourier_synthesise<T>(ring, (const T *)ctx->four_acc, g.npts, R, j0 % R, j0, nb,
+                                                         (const double *)ctx->four_tw, ctx->four_rows,
+                                                         (int)ctx->four_freqs.size(), s));
+                plan(hi, lo, [&](int n) -> const T * {
+                    return (n + 1 < nt && (n + 1) % ks == 0) ? ring + (size_t)(((n + 1) / ks) % R) * g.npts : nullptr;
+                });
+                auto qi = [&](int n, const T *&p, const T *&p2) { p = pq[hi - n]; p2 = pq2[hi - n]; };
+                if ((rc = run_steps(ctx, sw, hi, -1, hi - lo + 1, ctx->rec, amp, &ctx->src, series, rs, none, qi)))
+                    return rc;
+            }
+            q0 = ring;  // sample 0: slot 0, written by the synthesis of the lowest batch
         } else {
             // steps nt-1 .. nfused one per launch (all of them when nfused == 0), lagged pairing; the pairing owed
             // at the lower end, (mu^{nfused+1}, q^{nfused}), is the "last pairing" of that run
@@ -2626,7 +2751,8 @@ void fwi_destroy(fwi_ctx *ctx) {
         const char *member;
         void *p;
     } fields[] = {{"u", ctx->u[0]}, {"u", ctx->u[1]}, {"C", ctx->C}, {"c_dev", ctx->c_dev}, {"dz", ctx->dz}, {"dy", ctx->dy},
-                  {"dx", ctx->dx}, {"q_store", ctx->q_store}, {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc}, {"born_w", ctx->born_w},
+                  {"dx", ctx->dx}, {"q_store", ctx->q_store}, {"four_acc", ctx->four_acc}, {"four_ring", ctx->four_ring},
+                  {"four_tw", ctx->four_tw}, {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc}, {"born_w", ctx->born_w},
                   {"g_out", ctx->g_out}, {"red", ctx->red}, {"amp", ctx->amp}, {"series", ctx->series}, {"wav", ctx->wav},
                   {"snap", ctx->snap}, {"fwd", ctx->fwd[0]}, {"fwd", ctx->fwd[1]}, {"fx", ctx->fx[0]}, {"fx", ctx->fx[1]},
                   {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
@@ -3096,6 +3222,9 @@ static int born_callable(fwi_ctx *ctx, const char *who, bool imaging, int32_t wr
         return ctx->fail(FWI_EINVAL, "%s: FWI_BORN_FUSED: this context has no fused Born path (3-D fp32 O(8) stream "
                                      "kernel without the CPML only)", who);
     *fused = mode == FWI_BORN_FUSED || (mode == FWI_BORN_AUTO && BORN_AUTO_IS_FUSED && born_fused_supported(ctx));
+    if (!ctx->four_freqs.empty())
+        return ctx->fail(FWI_ESTATE, "%s: this context keeps the forward term as Fourier coefficients "
+                                     "(fwi_set_fourier_store), which no Born sweep reads; switch it off first", who);
     if (!ctx->have_forward || !ctx->have_q)
         return ctx->fail(FWI_ESTATE, "%s: needs fwi_forward(save=1) on this context first", who);
     return FWI_OK;
@@ -3208,6 +3337,9 @@ int fwi_allreduce_gradient(fwi_ctx *ctx) {
 
 int fwi_set_illumination(fwi_ctx *ctx, int32_t on) {
     if (!ctx) return FWI_EINVAL;
+    if (on && !ctx->four_freqs.empty())
+        return ctx->fail(FWI_EINVAL, "fwi_set_illumination: not available with the Fourier forward-term store "
+                                     "(fwi_set_fourier_store): the band-limited term is no measure of the illumination");
     (void)hipSetDevice(ctx->cfg.device);
     const size_t bytes = (size_t)ctx->gd.npts * ctx->esize;
     if (on && !ctx->h_acc) {
@@ -3226,6 +3358,99 @@ int fwi_set_illumination(fwi_ctx *ctx, int32_t on) {
         ctx->h_acc = nullptr;
         HIPCHK(ctx, hipFree(p));
     }
+    return FWI_OK;
+}
+
+// Frees the arrays of the Fourier store; the context is back on its configured store.
+static int fourier_release(fwi_ctx *ctx) {
+    if (ctx->four_acc || ctx->four_ring || ctx->four_tw)
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // no sweep still uses them
+    for (void **p : {&ctx->four_acc, &ctx->four_ring, &ctx->four_tw}) {
+        void *q = *p;
+        *p = nullptr;
+        if (q) HIPCHK(ctx, hipFree(q));
+    }
+    if (!ctx->four_freqs.empty()) {
+        ctx->store_held = 0;
+        ctx->have_q = false;
+    }
+    ctx->four_freqs.clear();
+    ctx->four_batch = ctx->four_rows = 0;
+    ctx->four_sweep = false;
+    return FWI_OK;
+}
+
+int fwi_set_fourier_store(fwi_ctx *ctx, int32_t nfreq, const double *freqs_hz, int32_t batch) {
+    if (!ctx) return FWI_EINVAL;
+    (void)hipSetDevice(ctx->cfg.device);
+    if (nfreq == 0) return fourier_release(ctx);
+    if (nfreq < 0 || nfreq > FWI_FOURIER_FMAX)
+        return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: nfreq=%d outside [0, %d]", (int)nfreq, FWI_FOURIER_FMAX);
+    if (!freqs_hz) return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: null frequencies");
+    if (batch < 1 || batch > FWI_FOURIER_BMAX)
+        return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: batch=%d outside [1, %d]", (int)batch, FWI_FOURIER_BMAX);
+    if (ctx->ckpt > 0)
+        return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: not available with ckpt_interval > 0 (checkpointing recomputes "
+                                     "the forward term; the Fourier store replaces it)");
+    if (ctx->qbf16)
+        return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: not available with store_dtype = bf16 (the coefficients are "
+                                     "kept in the field's type)");
+    if (ctx->h_acc)
+        return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: not available while illumination is enabled "
+                                     "(fwi_set_illumination): the band-limited term is no measure of it");
+    const double nyq = 1.0 / (2.0 * ctx->istride * ctx->cfg.dt);
+    for (int k = 0; k < nfreq; ++k) {
+        const double f = freqs_hz[k];
+        if (!std::isfinite(f)) return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: frequency %d is not finite", k);
+        if (f < 0.0) return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: frequency %d is negative (%g Hz)", k, f);
+        if (f > nyq * (1.0 + FOURIER_NYQUIST_RTOL))
+            return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: frequency %d (%g Hz) is above the Nyquist frequency %g Hz "
+                                         "of the sampled time axis (image_stride %d, dt %g s)", k, f, nyq, ctx->istride,
+                             ctx->cfg.dt);
+        for (int m = 0; m < k; ++m)
+            if (freqs_hz[m] == f)
+                return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: frequencies %d and %d are equal (%g Hz)", m, k, f);
+    }
+    if (int rc = fourier_release(ctx)) return rc;
+    if (ctx->q_store) {  // the native store of an earlier forward: its memory is what this store is there to save
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        void *q = ctx->q_store;
+        ctx->q_store = nullptr;
+        HIPCHK(ctx, hipFree(q));
+    }
+    ctx->store_held = 0;
+    ctx->have_q = false;
+    ctx->four_freqs.assign(freqs_hz, freqs_hz + nfreq);
+    ctx->four_batch = batch;
+    return FWI_OK;
+}
+
+int fwi_fourier_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (ctx->four_freqs.empty())
+        return ctx->fail(FWI_ESTATE, "fwi_fourier_spectrum: the Fourier store is off (fwi_set_fourier_store)");
+    if (k < 0 || k >= (int)ctx->four_freqs.size())
+        return ctx->fail(FWI_EINVAL, "fwi_fourier_spectrum: frequency index %d outside [0, %d)", (int)k,
+                         (int)ctx->four_freqs.size());
+    if (!re_out || !im_out) return ctx->fail(FWI_EINVAL, "fwi_fourier_spectrum: null output");
+    if (!ctx->have_q || !ctx->four_acc)
+        return ctx->fail(FWI_ESTATE, "fwi_fourier_spectrum: needs fwi_forward(save=1) on this context first");
+    (void)hipSetDevice(ctx->cfg.device);
+    const char *re = (const char *)ctx->four_acc + (size_t)2 * k * ctx->gd.npts * ctx->esize;
+    const char *im = re + (size_t)ctx->gd.npts * ctx->esize;
+    for (int c = 0; c < 2; ++c) {  // (one staging array: the first copy leaves it before the second repack)
+        if (int rc = DISPATCH(ctx, Impl<float>::download_compact(ctx, c ? im_out : re_out, c ? im : re),
+                              Impl<double>::download_compact(ctx, c ? im_out : re_out, c ? im : re)))
+            return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return FWI_OK;
+}
+
+int fwi_store_bytes(fwi_ctx *ctx, int64_t *bytes_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!bytes_out) return ctx->fail(FWI_EINVAL, "fwi_store_bytes: null output");
+    *bytes_out = (int64_t)ctx->store_held;
     return FWI_OK;
 }
 

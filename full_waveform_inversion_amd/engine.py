@@ -48,12 +48,15 @@ class Engine:
     ``store_dtype="bf16"`` halves the forward-term store of an fp32 engine.
     ``illumination=True`` accumulates the source-side illumination (the pseudo-Hessian diagonal) beside the gradient:
     :meth:`illumination`; off by default, when it costs nothing.
+    ``fourier=freqs`` (Hz) keeps ``len(freqs)`` Fourier coefficients of the forward term per cell instead of its history
+    (:meth:`set_fourier_store`): ``2 F + fourier_batch + 1`` model-sized arrays, and a gradient of the forward term
+    band-passed to those frequencies (:mod:`full_waveform_inversion_amd.fourier`).
     """
 
     def __init__(self, shape, h, dt, nt_max, order=8, npml=0, sigma_max=None, dtype="float32",
                  device=0, kernel="auto", zchunk=0, ckpt_interval=0, image_stride=1, update_form="standard",
                  abc="sponge", pml_alpha_max=0.0, store_dtype="native", launch_mode="auto",
-                 illumination=False):
+                 illumination=False, fourier=None, fourier_batch=8):
         shape = tuple(int(s) for s in shape)
         if len(shape) not in (2, 3):
             raise ValueError("shape must be (nz, nx) or (nz, ny, nx)")
@@ -78,6 +81,9 @@ class Engine:
         self._launch_mode = _lib.LAUNCH_MODES[launch_mode]
         self.pml_alpha_max = float(pml_alpha_max)
         self._illum = bool(illumination)
+        self._fourier = None if fourier is None else np.ascontiguousarray(np.atleast_1d(fourier), dtype=np.float64)
+        # samples per transform launch.  8: the fastest at every F measured, profiles/fourier_probe.json
+        self._fourier_batch = int(fourier_batch)
         self._lib = _lib.load()
         self._ctx = None
         self._nsrc = self._nrec = self._nt = 0
@@ -101,6 +107,8 @@ class Engine:
         self._ctx = ctx
         if self._illum:
             self._chk(self._lib.fwi_set_illumination(ctx, 1))
+        if self._fourier is not None:
+            self._set_fourier()
 
     def close(self):
         if self._ctx is not None:
@@ -409,9 +417,9 @@ class Engine:
     def set_illumination(self, on):
         """Switch the illumination accumulator on (allocated and zeroed) or off (freed); takes effect with the next
         adjoint sweep.  A context that does not exist yet gets it when it is created."""
-        self._illum = bool(on)
         if self._ctx is not None:
-            self._chk(self._lib.fwi_set_illumination(self._ctx, int(self._illum)))
+            self._chk(self._lib.fwi_set_illumination(self._ctx, int(bool(on))))  # (refused with the Fourier store)
+        self._illum = bool(on)
 
     def illumination(self, wrt="velocity"):
         """H summed over the adjoint sweeps since ``reset_gradient``: ``(S / dt^4) sum_n q^n(x)^2`` for
@@ -428,6 +436,60 @@ class Engine:
 
     def allreduce_illumination(self):
         self._chk(self._lib.fwi_allreduce_illumination(self._c))
+
+    # -- Fourier-compressed forward-term store (include/fwi.h fwi_set_fourier_store) ------------------
+    def _set_fourier(self):
+        f = self._fourier
+        if f is None:
+            self._chk(self._lib.fwi_set_fourier_store(self._ctx, 0, None, 0))
+        else:
+            self._chk(self._lib.fwi_set_fourier_store(self._ctx, f.size, f.ctypes.data_as(C.c_void_p), self._fourier_batch))
+
+    @property
+    def fourier_freqs(self):
+        """The frequencies (Hz) of the Fourier store, None while the engine keeps its configured store."""
+        return None if self._fourier is None else self._fourier.copy()
+
+    def set_fourier_store(self, freqs, batch=None):
+        """Keep the forward term as its Fourier coefficients at ``freqs`` (Hz; 1 .. 64 of them, each in
+        ``[0, 1 / (2 image_stride dt)]``) from the next ``forward(save=True)`` on, ``batch`` (1 .. 8; None: as it is)
+        samples per transform launch; ``freqs=None`` frees the coefficients and returns to the configured store.  What an
+        earlier forward stored is discarded.  Refused with ``ckpt_interval > 0``, ``store_dtype="bf16"`` and while
+        illumination is on.  A context that does not exist yet gets the store when it is created."""
+        if freqs is not None:
+            freqs = np.ascontiguousarray(np.atleast_1d(freqs), dtype=np.float64)
+            if freqs.ndim != 1:
+                raise ValueError("freqs must be a 1-D array of frequencies in Hz")
+        old = self._fourier, self._fourier_batch
+        self._fourier = freqs
+        if batch is not None:
+            self._fourier_batch = int(batch)
+        if self._ctx is not None:
+            try:
+                self._set_fourier()
+            except _lib.FwiError:
+                self._fourier, self._fourier_batch = old  # a refused call leaves the context as it was
+                raise
+
+    def fourier_spectrum(self):
+        """``Q_k`` of the last ``forward(save=True)`` as a complex ``(F, *shape)`` array: the monochromatic forward terms
+        ``sum_j q^{jS} exp(-i 2 pi f_k j S dt)`` (``fwi_fourier_spectrum``)."""
+        if self._fourier is None:
+            raise _lib.FwiError(3, "fourier_spectrum: the Fourier store is off (set_fourier_store)")
+        out = np.zeros((self._fourier.size,) + self.shape, np.complex64 if self.dtype == np.float32 else np.complex128)
+        re, im = np.zeros(self.shape, self.dtype), np.zeros(self.shape, self.dtype)
+        for k in range(self._fourier.size):
+            self._chk(self._lib.fwi_fourier_spectrum(self._c, k, re.ctypes.data_as(C.c_void_p),
+                                                     im.ctypes.data_as(C.c_void_p)))
+            out[k] = re + 1j * im
+        return out
+
+    def store_bytes(self):
+        """Device bytes held for the forward store of whichever kind (``fwi_store_bytes``); 0 before the first
+        ``forward(save=True)`` allocates it."""
+        n = C.c_int64(0)
+        self._chk(self._lib.fwi_store_bytes(self._c, C.byref(n)))
+        return int(n.value)
 
     # -- Born modelling (include/fwi.h fwi_born, fwi_born_imaging) -----------------------------------
     born_leaves_residual = True  # ``born`` keeps J dm on the device as the residual of ``adjoint(None)``

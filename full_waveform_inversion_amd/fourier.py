@@ -1,0 +1,119 @@
+"""The Fourier-compressed forward-term store in NumPy: the definition of ``fwi_set_fourier_store`` (include/fwi.h) and
+the fp64 twin of its two device transforms (csrc/fwi_fourier.hip).
+
+With ``S`` the image stride and ``N = ceil(nt / S)``, sample ``j`` of the forward term is time step ``n = j S``.  For the
+frequencies ``f_k >= 0`` (Hz) and the phases ``theta_kj = 2 pi f_k j S dt``::
+
+    analysis    Q_k(x)     = sum_j q^{jS}(x) (cos theta_kj - i sin theta_kj)
+    synthesis   q~^{jS}(x) = sum_k w_k (Re Q_k(x) cos theta_kj - Im Q_k(x) sin theta_kj)
+    weights     w_k = 1 / N where f_k = 0 or f_k = 1 / (2 S dt), the Nyquist frequency of the sampled axis; else 2 / N
+
+On the bin frequencies ``k / (N S dt)``, ``k = 0 .. floor(N / 2)``, synthesis after analysis is the orthogonal projection
+of the sampled history onto those bins, and the identity with all of them.  With fewer bins the gradient is that of the
+forward term band-passed to the bins kept: an approximation of the full gradient, as good as the bins cover the band of
+the source.  :func:`fourier_bins` lists the bins inside a band.  For a Ricker wavelet of peak frequency ``f0``, whose
+amplitude spectrum is ``f^2 exp(-f^2 / f0^2)``, the band ``[0, 2.5 f0]`` leaves out 1.4e-4 of the wavelet's energy and
+3.0e-3 of that of its second derivative in time, which is what the forward term is away from the source; ``[0, 3 f0]``
+leaves out 9.5e-7 and 4.0e-5.  Frequencies off the bins are allowed (phase-sensitive
+detection); the result is then no projection.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+NYQUIST_RTOL = 1e-9  # FOURIER_NYQUIST_RTOL of the engine: how close to 1 / (2 S dt) counts as the Nyquist frequency
+
+
+def n_samples(nt, stride):
+    """``N = ceil(nt / S)``: the samples ``j = 0 .. N - 1`` are the time steps ``j S < nt``."""
+    nt, stride = int(nt), max(1, int(stride))
+    if nt < 1:
+        raise ValueError("nt must be >= 1")
+    return (nt + stride - 1) // stride
+
+
+def fourier_bins(nt, dt, stride, fmin, fmax):
+    """The bin frequencies ``k / (N S dt)``, ``k = 0 .. floor(N / 2)``, with ``fmin <= f <= fmax`` (Hz; both ends count,
+    to 1e-12 of the sampling rate), ascending.  Empty when the band holds no bin; ``fmax`` above the Nyquist frequency ends
+    at the highest bin."""
+    S = max(1, int(stride))
+    N = n_samples(nt, S)
+    f = np.arange(N // 2 + 1) / (N * S * float(dt))
+    tol = 1e-12 / (S * float(dt))
+    return f[(f >= float(fmin) - tol) & (f <= float(fmax) + tol)]
+
+
+def _freqs(nt, stride, dt, freqs):
+    S = max(1, int(stride))
+    f = np.atleast_1d(np.asarray(freqs, np.float64))
+    if f.ndim != 1 or f.size < 1:
+        raise ValueError("freqs must be a non-empty 1-D array of frequencies in Hz")
+    nyq = 1.0 / (2.0 * S * float(dt))
+    if not np.all(np.isfinite(f)) or np.any(f < 0) or np.any(f > nyq * (1.0 + NYQUIST_RTOL)):
+        raise ValueError("frequencies must be finite, >= 0 and at most the Nyquist frequency %g Hz" % nyq)
+    if np.unique(f).size != f.size:
+        raise ValueError("frequencies must differ")
+    return f, S, n_samples(nt, S)
+
+
+def phases(nt, stride, dt, freqs):
+    """``theta_kj`` as ``(F, N)``, from the fractional part of ``f_k j S dt`` (the engine's table does the same)."""
+    f, S, N = _freqs(nt, stride, dt, freqs)
+    x = (f * (S * float(dt)))[:, None] * np.arange(N)[None, :]
+    return 2.0 * np.pi * (x - np.floor(x))
+
+
+def weights(nt, stride, dt, freqs):
+    """``w_k``: ``1 / N`` at ``f_k = 0`` and at the Nyquist frequency ``1 / (2 S dt)``, else ``2 / N``."""
+    f, S, N = _freqs(nt, stride, dt, freqs)
+    edge = (f == 0.0) | (np.abs(2.0 * f * S * float(dt) - 1.0) <= NYQUIST_RTOL)
+    return np.where(edge, 1.0, 2.0) / N
+
+
+def analyse(samples, nt, stride, dt, freqs, dtype=np.float64, batch=None):
+    """``Q_k`` as a complex ``(F, ...)`` array from the samples ``q^{jS}``, ``(N, ...)``.
+
+    ``dtype`` and ``batch`` restate the device's arithmetic: the samples and the accumulators are held in ``dtype``, the
+    sums over a batch of ``batch`` samples (None: all at once) are taken in fp64 and added to the accumulators once per
+    batch."""
+    th = phases(nt, stride, dt, freqs)
+    F, N = th.shape
+    dtype = np.dtype(dtype)
+    q = np.asarray(samples)
+    if q.shape[0] != N:
+        raise ValueError("expected the N = %d samples of the time axis, got %d" % (N, q.shape[0]))
+    q = q.astype(dtype).astype(np.float64)
+    B = N if batch is None else max(1, int(batch))
+    re = np.zeros((F,) + q.shape[1:], dtype)
+    im = np.zeros((F,) + q.shape[1:], dtype)
+    for j0 in range(0, N, B):
+        sl = slice(j0, min(N, j0 + B))
+        re = (re.astype(np.float64) + np.tensordot(np.cos(th[:, sl]), q[sl], axes=1)).astype(dtype)
+        im = (im.astype(np.float64) - np.tensordot(np.sin(th[:, sl]), q[sl], axes=1)).astype(dtype)
+    return re + 1j * im
+
+
+def synthesise(Q, nt, stride, dt, freqs, dtype=np.float64):
+    """The band-limited samples ``q~^{jS}`` as ``(N, ...)`` in ``dtype`` from ``Q_k``, ``(F, ...)`` complex; the sums run in
+    fp64."""
+    th = phases(nt, stride, dt, freqs)
+    w = weights(nt, stride, dt, freqs)
+    Q = np.asarray(Q)
+    if Q.shape[0] != th.shape[0]:
+        raise ValueError("expected one coefficient array per frequency")
+    re, im = Q.real.astype(np.float64), Q.imag.astype(np.float64)
+    out = np.tensordot((w[:, None] * np.cos(th)).T, re, axes=1) - np.tensordot((w[:, None] * np.sin(th)).T, im, axes=1)
+    return out.astype(np.dtype(dtype))
+
+
+def project(q_history, nt, stride, dt, freqs, dtype=np.float64, batch=None):
+    """What the imaging condition reads with the Fourier store in the place of the history ``q^n``, ``(nt, ...)``: the rows
+    ``n = j S`` hold ``synthesise(analyse(.))`` of those rows, the rows in between (which the imaging never reads) zeros."""
+    q = np.asarray(q_history)
+    S = max(1, int(stride))
+    if q.shape[0] != int(nt):
+        raise ValueError("expected the nt = %d steps of the history, got %d" % (int(nt), q.shape[0]))
+    Q = analyse(q[::S], nt, S, dt, freqs, dtype, batch)
+    out = np.zeros(q.shape, np.dtype(dtype))
+    out[::S] = synthesise(Q, nt, S, dt, freqs, dtype)
+    return out

@@ -83,7 +83,9 @@ def inversion_engine(shape, h, dt, nt_max, **kw):
     (tests/test_gpu_parity.py::test_end_to_end_fp32_increment_form_flat_1e5) at +4 B/update in 3-D (157 vs 110 ms per
     256^3 shot-gradient) and +2.5 % in 2-D.  Forward-only modelling and the headline bench keep the standard form
     (``Engine``'s default).  fp64 engines need neither; options the increment form does not combine with (the bf16
-    store, an explicit 2-D "stream" kernel) fall back to the standard form.
+    store, an explicit 2-D "stream" kernel) fall back to the standard form.  Every other keyword goes to ``Engine`` as it
+    is: ``fourier=freqs, fourier_batch=B`` make it keep the forward term as Fourier coefficients
+    (``Engine.set_fourier_store``).
     """
     from .engine import Engine
     if "update_form" not in kw:

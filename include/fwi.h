@@ -39,6 +39,7 @@ extern "C" {
 /* Stays 14 with the Born calls (fwi_born, fwi_born_vec, fwi_born_path; fwi_born_imaging, fwi_born_imaging_vec): they
  * are purely additive -- new symbols, fwi_config and every existing call unchanged -- so a client built against the
  * earlier 14 keeps working. */
+/* ... and with the Fourier store (fwi_set_fourier_store, fwi_fourier_spectrum, fwi_store_bytes), additive in the same way. */
 #define FWI_ABI_VERSION 14
 
 enum { FWI_F32 = 0, FWI_F64 = 1 };
@@ -416,6 +417,44 @@ int fwi_set_illumination(fwi_ctx *ctx, int32_t on);  /* on != 0: allocate and ze
 int fwi_illumination(fwi_ctx *ctx, int32_t wrt, void *out);        /* model-shaped host buffer, context dtype */
 int fwi_illumination_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot); /* slot := H, as fwi_illumination() */
 int fwi_allreduce_illumination(fwi_ctx *ctx);  /* in-place sum over the ranks of fwi_comm_init */
+
+/* Fourier-compressed forward-term store: instead of the N = ceil(nt / S) sampled forward terms q^{jS} (S = image stride,
+ * sample j = time step jS) the context keeps F discrete Fourier coefficients of them per cell, accumulated during
+ * fwi_forward(save != 0), and fwi_adjoint(image != 0) rebuilds the band-limited term from them batch by batch, just ahead
+ * of the imaging steps that read it.  Memory: 2 F + batch + 1 model-sized arrays instead of N; no second forward sweep.
+ * With theta_kj = 2 pi f_k j S dt:
+ *     analysis    Q_k(x)    = sum_j q^{jS}(x) (cos theta_kj - i sin theta_kj)
+ *     synthesis   q~^{jS}(x) = sum_k w_k (Re Q_k(x) cos theta_kj - Im Q_k(x) sin theta_kj)
+ *     weights     w_k = 1 / N where f_k = 0 or f_k = 1 / (2 S dt) (the Nyquist frequency of the sampled axis, to a
+ *                 relative 1e-9), else 2 / N
+ * The imaging condition pairs mu^{n+1} with q~^n exactly where it pairs it with q^n on the configured store, with the
+ * same weight S; fwi_gradient and everything above it are unchanged.  On the bin frequencies f_k = k / (N S dt),
+ * k = 0 .. floor(N / 2), q~ is the orthogonal projection of the sampled history onto those bins: all of them give the
+ * configured store's gradient back (to round-off), fewer give the gradient of the forward term band-passed to the bins
+ * kept -- an APPROXIMATION of the full gradient, as good as the bins cover the band of the source (fourier.fourier_bins
+ * of the Python package lists the bins inside a band).  Frequencies off the bins are allowed (phase-sensitive
+ * detection); q~ is then no projection.
+ * fwi_set_fourier_store: nfreq = 0 frees the arrays and returns the context to its configured store.  Otherwise
+ * 1 <= nfreq <= FWI_FOURIER_FMAX frequencies in Hz and 1 <= batch <= FWI_FOURIER_BMAX samples per transform launch
+ * (batch + 1 ring slots: more slots, fewer passes over the 2 F accumulators).  FWI_EINVAL, with the reason in
+ * fwi_last_error, for a frequency that is negative, not finite, equal to another one or above the Nyquist frequency,
+ * for a context with ckpt_interval > 0 or store_dtype = bf16, and while illumination is enabled; fwi_set_illumination(on)
+ * fails the same way on a context with this store, and fwi_born* on it are FWI_ESTATE.  The call discards what an
+ * earlier forward stored (the configured store's memory too).  The arrays are allocated by the first
+ * fwi_forward(save != 0) (FWI_ENOMEM when they do not fit); that sweep and fwi_adjoint(image != 0) run one time step per
+ * launch, sweeps that store or read nothing keep their fast paths.  Any number of adjoint sweeps may follow one forward.
+ * The coefficients are kept in the context dtype; the batch sums and the synthesis run in fp64 registers.
+ * fwi_fourier_spectrum: Q_k of the last fwi_forward(save != 0), real and imaginary part as model-shaped host buffers of
+ * the context dtype -- the monochromatic forward terms, for quality control and frequency-domain work.
+ * fwi_store_bytes: device bytes currently held for the forward store of whichever kind (the configured store, the
+ * checkpoint buffers, or the 2 F + batch + 1 arrays of this one; its twiddle table, F (N + 7) pairs of doubles, is not
+ * counted); 0 before the first fwi_forward(save != 0) allocates it.  No reference counterpart. */
+#define FWI_FOURIER_FMAX 64
+#define FWI_FOURIER_BMAX 8
+int fwi_set_fourier_store(fwi_ctx *ctx, int32_t nfreq, const double *freqs_hz, int32_t batch);
+int fwi_fourier_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out);
+int fwi_store_bytes(fwi_ctx *ctx, int64_t *bytes_out);
+
 /* Elementwise vector operations for a diagonal preconditioner (pad columns of the compact layout stay 0). */
 int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x);               /* y := x * y */
 int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b);    /* y := a / (y + b) */

@@ -31,6 +31,12 @@ def main():
     ap.add_argument("--abc", default="sponge", choices=["sponge", "cpml"], help="absorbing border (fwi_config.abc)")
     ap.add_argument("--image-stride", type=int, default=1,
                     help="imaging condition every S-th step (fwi_config.image_stride)")
+    ap.add_argument("--fourier-store", default=None, metavar="FMIN,FMAX",
+                    help="keep the forward term as its Fourier coefficients on the bins of the sampled time axis inside "
+                         "[FMIN, FMAX] Hz (fourier.fourier_bins; at most 64) instead of its history: the gradient of the "
+                         "forward term band-passed to them (Engine.set_fourier_store)")
+    ap.add_argument("--fourier-batch", type=int, default=8, metavar="B",
+                    help="samples per transform launch of --fourier-store, 1 .. 8 (B + 1 ring slots)")
     ap.add_argument("--update-form", default="auto", choices=["auto", "increment", "standard"],
                     help="fp32 update form; auto = shots.inversion_engine's choice (increment: 1e-5 end to end)")
     ap.add_argument("--launch-mode", default="auto", choices=["auto", "stream", "graph"])
@@ -152,6 +158,17 @@ def main():
     from full_waveform_inversion_amd import default_sigma_max
     sigma = default_sigma_max(float(w.c.max()), w.h, w.npml)
     uf = {} if a.update_form == "auto" else {"update_form": a.update_form}
+    if a.fourier_store is not None:
+        from full_waveform_inversion_amd import fourier
+        try:
+            fmin, fmax = (float(v) for v in a.fourier_store.split(","))
+        except ValueError:
+            ap.error("--fourier-store takes FMIN,FMAX in Hz")
+        bins = fourier.fourier_bins(w.nt, w.dt, a.image_stride, fmin, fmax)
+        if not 1 <= bins.size <= 64:
+            ap.error("--fourier-store: [%g, %g] Hz holds %d bins of the sampled time axis (1 .. 64 allowed; the bins "
+                     "lie 1 / (nt dt) apart)" % (fmin, fmax, bins.size))
+        uf.update(fourier=bins, fourier_batch=a.fourier_batch)
     pool = sh.EnginePool(lambda: sh.inversion_engine(w.shape, w.h, w.dt, w.nt, order=w.order, npml=w.npml, device=local,
                                                      sigma_max=sigma, image_stride=a.image_stride, abc=a.abc,
                                                      launch_mode=a.launch_mode, **uf,
