@@ -29,6 +29,7 @@ MATCH_LMAX = 64  # FWI_MATCH_LMAX
 TT_KMAX = 1024  # FWI_TT_KMAX
 OT_TRANSFORMS = {"linear": 0, "softplus": 1}  # FWI_OT_LINEAR, FWI_OT_SOFTPLUS
 FOURIER_FMAX, FOURIER_BMAX = 64, 8  # FWI_FOURIER_FMAX, FWI_FOURIER_BMAX
+SPEC_KINDS = {"l2": 0, "phase": 1, "logamp": 2, "log": 3}  # FWI_SPEC_L2, FWI_SPEC_PHASE, FWI_SPEC_LOGAMP, FWI_SPEC_LOG
 UNIQUE_ID_BYTES = 128
 EINVAL = 1
 ERROR_NAMES = {1: "FWI_EINVAL", 2: "FWI_EHIP", 3: "FWI_ESTATE", 4: "FWI_ENOMEM", 5: "FWI_ECOMM"}
@@ -72,6 +73,7 @@ SIGNATURES = {
     "fwi_misfit_correlation": (C.c_int, [_P, _P, _P, _P, _I32, _P, _D, C.POINTER(_D), _P]),
     "fwi_misfit_traveltime": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, C.POINTER(_D), _P, _P]),
     "fwi_misfit_transport": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _D, C.POINTER(_D), _P, _P]),
+    "fwi_misfit_spectral": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _I32, _D, _P, _P, C.POINTER(_D), _P, _P, _P]),
     "fwi_gradient": (C.c_int, [_P, _I32, _P]),
     "fwi_gradient_reset": (C.c_int, [_P]),
     "fwi_gradient_add": (C.c_int, [_P, _P]),

@@ -24,6 +24,7 @@
 #include "fwi_born.h"
 #include "fwi_data.h"
 #include "fwi_corr.h"
+#include "fwi_spec.h"
 #include "fwi_ot.h"
 #include "fwi_ttime.h"
 #include "fwi_envelope.h"
@@ -228,6 +229,12 @@ struct fwi_ctx {
     // fwi_misfit_transport (fwi_ot.hip): densities, CDFs, potentials and every sum (ot_work_doubles), which traces count
     void *ot_work = nullptr, *ot_counts = nullptr;
     size_t cap_ot_work = 0, cap_ot_counts = 0;
+    // fwi_misfit_spectral (fwi_spec.hip): the segment sums, G / phi / a and the terms of J, which pairs count, the
+    // frequency weights, and the twiddle table with the (nt, frequencies) it was formed for (dt is the context's)
+    void *spec_part = nullptr, *spec_coef = nullptr, *spec_counts = nullptr, *spec_fw = nullptr, *spec_table = nullptr;
+    size_t cap_spec_part = 0, cap_spec_coef = 0, cap_spec_counts = 0, cap_spec_fw = 0, cap_spec_table = 0;
+    int spec_table_nt = 0;
+    std::vector<double> spec_table_freqs, spec_table_host;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
     enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
     int resid_pts_in = RESID_PTS_NONE;
@@ -2249,6 +2256,94 @@ struct Impl {
         return FWI_OK;
     }
 
+    // The twiddles of fwi_misfit_spectral, formed in fp64 as fourier_table forms the store's (from the fractional part of
+    // f_k n dt) and kept on the context: block k, row n = (cos theta_kn, sin theta_kn), the rows from nt on zero
+    // (spec_table_rows).  Rebuilt only when nt or the frequencies change.
+    static int spectral_table(fwi_ctx *ctx, int nt, int F, const double *freqs) {
+        if (ctx->spec_table && ctx->spec_table_nt == nt && ctx->spec_table_freqs.size() == (size_t)F &&
+            std::equal(freqs, freqs + F, ctx->spec_table_freqs.begin()))
+            return FWI_OK;
+        const int rows = spec_table_rows(nt);
+        ctx->spec_table_nt = 0;  // no table until the new one is complete
+        if (int rc = ensure(ctx, &ctx->spec_table, &ctx->cap_spec_table, spec_table_doubles(nt, F) * sizeof(double)))
+            return rc;
+        std::vector<double> &t = ctx->spec_table_host;
+        t.assign(spec_table_doubles(nt, F), 0.0);
+        for (int k = 0; k < F; ++k)
+            for (int n = 0; n < nt; ++n) {
+                const double x = freqs[k] * ctx->cfg.dt * n, th = 2.0 * M_PI * (x - std::floor(x));
+                t[((size_t)k * rows + n) * 2] = std::cos(th);
+                t[((size_t)k * rows + n) * 2 + 1] = std::sin(th);
+            }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->spec_table, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->spec_table_nt = nt;
+        ctx->spec_table_freqs.assign(freqs, freqs + F);
+        return FWI_OK;
+    }
+
+    // s' = B d_syn, d' = B d_obs, S_kj and O_kj the Fourier coefficients of the weighted traces M s', M d' at the F
+    // frequencies, J the sum over the pairs (k, j) of the terms of `kind`, r = B g where the adjoint sweep reads its
+    // amplitudes (fwi_spec.h)
+    static int misfit_spectral(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, int F,
+                               const double *freqs, int kind, double eps, const double *freq_weights,
+                               const double *trace_weights, double *J_out, double *phase_out, double *logamp_out,
+                               uint8_t *counts_out) {
+        Misfit m(ctx);
+        double J = 0.0;
+        T *g = nullptr;
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        const size_t npair = (size_t)F * m.ntr;
+        if (m.data) {
+            if ((rc = ensure(ctx, &ctx->spec_part, &ctx->cap_spec_part, spec_partials(m.nt, m.ntr, F) * sizeof(double))) ||
+                (rc = ensure(ctx, &ctx->spec_coef, &ctx->cap_spec_coef, spec_coef_doubles(m.ntr, F) * sizeof(double))) ||
+                (rc = ensure(ctx, &ctx->spec_counts, &ctx->cap_spec_counts, npair)) ||
+                (rc = spectral_table(ctx, m.nt, F, freqs)))
+                return rc;
+            const double *tw, *fw = nullptr;
+            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
+            if (freq_weights) {
+                if ((rc = ensure(ctx, &ctx->spec_fw, &ctx->cap_spec_fw, (size_t)F * sizeof(double)))) return rc;
+                // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
+                HIPCHK(ctx, hipMemcpyAsync(ctx->spec_fw, freq_weights, (size_t)F * sizeof(double), hipMemcpyHostToDevice,
+                                           ctx->stream));
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                fw = (const double *)ctx->spec_fw;
+            }
+            double *part = (double *)ctx->spec_part, *coef = (double *)ctx->spec_coef;
+            const double *table = (const double *)ctx->spec_table;
+            m.sum = coef + spec_total_at(m.ntr, F);  // the total of the terms of J: J itself
+            const T *s1, *d1;
+            if ((rc = m.prefilter(&s1, &d1))) return rc;
+            HIPCHK(ctx, launch_spec_analysis<T>(part, s1, d1, m.w, table, F, m.nt, m.ntr, ctx->stream));
+            HIPCHK(ctx, launch_spec_coeffs(coef, (uint8_t *)ctx->spec_counts, part, fw, tw, kind, eps, F, m.nt, m.ntr,
+                                           ctx->stream));
+            g = m.adjoint_source();  // in place of s' (with taps) or of d_obs (without): both are used up
+            HIPCHK(ctx, launch_spec_source<T>(g, m.w, coef, table, F, m.nt, m.ntr, ctx->stream));
+        }
+        if ((rc = m.finish(g, &J))) return rc;
+        // the three (F, ntr) outputs under one synchronise; without receivers or samples no pair counts: zeros
+        if (!m.data) {
+            if (phase_out) std::fill(phase_out, phase_out + npair, 0.0);
+            if (logamp_out) std::fill(logamp_out, logamp_out + npair, 0.0);
+            if (counts_out) std::fill(counts_out, counts_out + npair, (uint8_t)0);
+        } else if (phase_out || logamp_out || counts_out) {
+            const double *coef = (const double *)ctx->spec_coef;
+            if (phase_out)
+                HIPCHK(ctx, hipMemcpyAsync(phase_out, coef + spec_phase_at(m.ntr, F), npair * sizeof(double),
+                                           hipMemcpyDeviceToHost, ctx->stream));
+            if (logamp_out)
+                HIPCHK(ctx, hipMemcpyAsync(logamp_out, coef + spec_logamp_at(m.ntr, F), npair * sizeof(double),
+                                           hipMemcpyDeviceToHost, ctx->stream));
+            if (counts_out)
+                HIPCHK(ctx, hipMemcpyAsync(counts_out, ctx->spec_counts, npair, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        *J_out = J;
+        return FWI_OK;
+    }
+
     // device residual := B M^2 B residual: per node, or per off-grid point and scattered onto the nodes again
     static int residual_weight(fwi_ctx *ctx, const T *weights, const double *taps, int R) {
         const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
@@ -2766,7 +2861,9 @@ void fwi_destroy(fwi_ctx *ctx) {
                   {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h},
                   {"corr_part", ctx->corr_part}, {"corr_coef", ctx->corr_coef},
                   {"tt_part", ctx->tt_part}, {"tt_coef", ctx->tt_coef}, {"tt_lag", ctx->tt_lag},
-                  {"ot_work", ctx->ot_work}, {"ot_counts", ctx->ot_counts}};
+                  {"ot_work", ctx->ot_work}, {"ot_counts", ctx->ot_counts},
+                  {"spec_part", ctx->spec_part}, {"spec_coef", ctx->spec_coef}, {"spec_counts", ctx->spec_counts},
+                  {"spec_fw", ctx->spec_fw}, {"spec_table", ctx->spec_table}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
@@ -3018,6 +3115,45 @@ int fwi_misfit_transport(fwi_ctx *ctx, const void *d_obs, const void *weights, c
     if (int rc = misfit_synthetics(ctx, "fwi_misfit_transport", "or fwi_born ")) return rc;
     return DISPATCH_CALL(ctx, misfit_transport, typed(d_obs), typed(weights), taps, R, trace_weights, transform, param,
                          J_out, w2_out, counts_out);
+}
+
+int fwi_misfit_spectral(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
+                        int32_t nfreq, const double *freqs_hz, int32_t kind, double eps, const double *freq_weights,
+                        const double *trace_weights, double *J_out, double *phase_out, double *logamp_out,
+                        uint8_t *counts_out) {
+    const char *who = "fwi_misfit_spectral";
+    if (int rc = misfit_callable(ctx, who, d_obs, J_out)) return rc;
+    if (int rc = data_args(ctx, who, taps, R)) return rc;
+    if (nfreq < 1 || nfreq > FWI_FOURIER_FMAX)
+        return ctx->fail(FWI_EINVAL, "%s: nfreq=%d outside [1, %d]", who, (int)nfreq, FWI_FOURIER_FMAX);
+    if (!freqs_hz) return ctx->fail(FWI_EINVAL, "%s: null frequencies", who);
+    if (kind != FWI_SPEC_L2 && kind != FWI_SPEC_PHASE && kind != FWI_SPEC_LOGAMP && kind != FWI_SPEC_LOG)
+        return ctx->fail(FWI_EINVAL, "%s: kind=%d is none of FWI_SPEC_L2, FWI_SPEC_PHASE, FWI_SPEC_LOGAMP, FWI_SPEC_LOG", who,
+                         (int)kind);
+    const bool phase = kind == FWI_SPEC_PHASE || kind == FWI_SPEC_LOG;
+    const double nyq = 1.0 / (2.0 * ctx->cfg.dt);
+    for (int k = 0; k < nfreq; ++k) {
+        const double f = freqs_hz[k];
+        if (!std::isfinite(f)) return ctx->fail(FWI_EINVAL, "%s: frequency %d is not finite", who, k);
+        if (f < 0.0) return ctx->fail(FWI_EINVAL, "%s: frequency %d is negative (%g Hz)", who, k, f);
+        if (f > nyq * (1.0 + FOURIER_NYQUIST_RTOL))
+            return ctx->fail(FWI_EINVAL, "%s: frequency %d (%g Hz) is above the Nyquist frequency %g Hz (dt %g s)", who, k, f,
+                             nyq, ctx->cfg.dt);
+        if (phase && (f == 0.0 || std::fabs(2.0 * f * ctx->cfg.dt - 1.0) <= FOURIER_NYQUIST_RTOL))
+            return ctx->fail(FWI_EINVAL, "%s: frequency %d (%g Hz) is 0 or the Nyquist frequency, where the spectrum is real "
+                                         "and has no phase to compare (kinds PHASE and LOG)", who, k, f);
+        for (int m = 0; m < k; ++m)
+            if (freqs_hz[m] == f) return ctx->fail(FWI_EINVAL, "%s: frequencies %d and %d are equal (%g Hz)", who, m, k, f);
+    }
+    if (int rc = nonneg_finite(ctx, who, "eps", eps)) return rc;
+    if (freq_weights)
+        for (int k = 0; k < nfreq; ++k)
+            if (!(freq_weights[k] >= 0.0) || !std::isfinite(freq_weights[k]))
+                return ctx->fail(FWI_EINVAL, "%s: freq_weights[%d]=%g must be finite and >= 0", who, k, freq_weights[k]);
+    if (int rc = trace_weight_args(ctx, who, trace_weights)) return rc;
+    if (int rc = misfit_synthetics(ctx, who, "or fwi_born ")) return rc;
+    return DISPATCH_CALL(ctx, misfit_spectral, typed(d_obs), typed(weights), taps, R, nfreq, freqs_hz, kind, eps,
+                         freq_weights, trace_weights, J_out, phase_out, logamp_out, counts_out);
 }
 
 int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {

@@ -131,6 +131,15 @@ that ``d_obs == d_syn`` gives ``phi = psi = 0``, ``J = 0`` and ``r = 0`` exactly
 absolute and must not follow ``s``.  A trace counts iff every ``p_n`` and ``q_n`` is finite and ``>= 0`` and both sums
 are finite and ``> 0``; otherwise ``W_j = 0``, its term of ``J`` is 0 and its adjoint source is 0 (under ``linear`` a
 trace that goes below ``-c`` drops out).  No linear Gauss-Newton weight either.
+
+Frequency-domain (spectral) misfit, :class:`SpectralMisfit` (``Engine.misfit_spectral``, ``fwi_misfit_spectral``,
+``csrc/fwi_spec.hip``): every misfit above compares traces in the time domain.  This one compares the discrete Fourier
+coefficients of the weighted, filtered gathers at up to 64 frequencies of the caller's choice -- their difference, their
+phases, their logarithmic amplitudes or both (the logarithmic misfit of Shin & Min 2006) -- with a weight per frequency
+and per trace: the data side of frequency-domain FWI from time-domain modelling, whose model side is the Fourier store
+(:mod:`fourier`).  The definition stands in the class's docstring, in the words of ``include/fwi.h``;
+:func:`spectral_floor`, :func:`whitening_weights` and :func:`laplace_damping` are its data-only helpers.  No linear
+Gauss-Newton weight is offered either.
 """
 from __future__ import annotations
 
@@ -840,6 +849,167 @@ class TransportW2(_PerTrace):
         self.distances, self.counts = W, counts
         src = np.where(counts, 0.5 * w * dt2 / Ss, 0.0) * (phi - phibar) * dP
         return float(np.sum(0.5 * w * W)), self._residual(src, M)
+
+
+SPECTRAL_KINDS = ("l2", "phase", "logamp", "log")
+
+
+def _spectral_tables(nt, dt, freqs, kind):
+    """``(f, cos theta, sin theta)``, the tables ``(F, nt)``; the frequencies checked as ``fwi_misfit_spectral`` does"""
+    from . import fourier
+    from ._lib import FOURIER_FMAX
+    f = np.atleast_1d(np.asarray(freqs, np.float64))
+    if f.ndim != 1 or not 1 <= f.size <= FOURIER_FMAX:
+        raise ValueError("freqs must hold 1 .. %d frequencies in Hz" % FOURIER_FMAX)
+    th = fourier.phases(nt, 1, dt, f)  # (finite, >= 0, distinct, at most the Nyquist frequency: checked there)
+    if kind in ("phase", "log") and np.any((f == 0.0) | (np.abs(2.0 * f * float(dt) - 1.0) <= fourier.NYQUIST_RTOL)):
+        raise ValueError("kinds 'phase' and 'log' take no frequency of 0 or at the Nyquist frequency: the spectrum is "
+                         "real there")
+    return f, np.cos(th), np.sin(th)
+
+
+def spectrum(x, dt, freqs):
+    """``X_kj = sum_n x[n, j] (cos theta_kn - i sin theta_kn)``, ``theta_kn = 2 pi frac(f_k n dt)``: the ``(F, ntr)``
+    complex Fourier coefficients of the ``(nt, ntr)`` gather at the frequencies ``freqs`` (Hz), in fp64."""
+    x = np.asarray(x, np.float64)
+    if x.ndim != 2:
+        raise ValueError("the gather must be (nt, ntr)")
+    _, c, s = _spectral_tables(x.shape[0], dt, freqs, "l2")
+    return c @ x - 1j * (s @ x)
+
+
+def spectral_floor(d_obs, dt, freqs, percent=1.0, weights=None):
+    """``percent / 100 * max_kj |O_kj|`` of the (weighted) observed data: a floor ``eps`` for :class:`SpectralMisfit`
+    that depends on the data only -- like :func:`correlation_floor`, compute it once per shot and hold it."""
+    if not (float(percent) >= 0.0 and np.isfinite(percent)):
+        raise ValueError("percent must be finite and >= 0")
+    d = np.asarray(d_obs, np.float64)
+    if d.ndim != 2:
+        raise ValueError("d_obs must be (nt, ntr)")
+    M = WeightedL2._weights(weights, d.shape)
+    return float(percent) / 100.0 * (float(np.max(np.abs(spectrum(d if M is None else M * d, dt, freqs)))) if d.size else 0.0)
+
+
+def laplace_damping(nt, dt, sigma):
+    """The ``(nt, 1)`` weights ``exp(-sigma n dt)`` of a Laplace-Fourier misfit (``sigma >= 0`` in 1/s), to be multiplied
+    into ``Shot.weights``."""
+    if not (float(sigma) >= 0.0 and np.isfinite(sigma) and float(dt) > 0.0 and np.isfinite(dt) and int(nt) >= 1):
+        raise ValueError("nt >= 1, dt > 0 and a finite sigma >= 0")
+    return np.exp(-float(sigma) * float(dt) * np.arange(int(nt), dtype=np.float64))[:, None]
+
+
+def whitening_weights(d_obs, dt, freqs, percent=1.0):
+    """``fw_k = 1 / (mean_j |O_kj|^2 + floor)``, ``floor = (percent / 100)^2 max_k mean_j |O_kj|^2``: frequency weights
+    that whiten the spectrum of the observed data, so that its weak frequencies are not drowned out (data-only)."""
+    if not (float(percent) >= 0.0 and np.isfinite(percent)):
+        raise ValueError("percent must be finite and >= 0")
+    p = np.mean(np.abs(spectrum(d_obs, dt, freqs)) ** 2, axis=1)
+    denom = p + (float(percent) / 100.0) ** 2 * float(np.max(p))
+    if not np.all(denom > 0.0):
+        raise ValueError("the observed data have no energy at a frequency and percent = 0: no weight to give")
+    return 1.0 / denom
+
+
+class SpectralMisfit(_PerTrace):
+    """The frequency-domain (spectral) misfit in fp64 NumPy, ``objective(d_syn, d_obs, weights=None, trace_weights=None)
+    -> (J, r)``, and the ``objective=`` that ``shots.misfit_and_gradient`` recognises (an engine that has
+    ``misfit_spectral`` replaces it by the device path; the shot loop hands it ``Shot.weights`` and
+    ``Shot.trace_weights``).  The definition (``include/fwi.h`` ``fwi_misfit_spectral``, ``csrc/fwi_spec.hip``):
+
+        sh = M . B d_syn,  dh = M . B d_obs    (M, B as in NormalizedCorrelation; B s, B d rounded to the dtype once)
+        theta_kn = 2 pi frac(f_k n dt)         formed in fp64 from the fractional part, as fourier.phases does
+        S_kj = sum_n sh[n,j] (cos theta_kn - i sin theta_kn)        O_kj likewise from dh
+        w_kj = fw_k * tw_j                     fw: F weights per frequency (none: 1), tw: ntr weights per trace (none: 1),
+                                               all finite and >= 0
+        kind L2      J = 1/2 sum_kj w_kj |S_kj - O_kj|^2                        G_kj = w_kj (S_kj - O_kj)
+        kind LOGAMP  a_kj = 1/2 ln((|S_kj|^2 + eps^2) / (|O_kj|^2 + eps^2))
+                     J = 1/2 sum w a^2                                           G_kj = w_kj a_kj S_kj / (|S_kj|^2 + eps^2)
+        kind PHASE   phi_kj = atan2(Im(S_kj conj O_kj), Re(S_kj conj O_kj)) in (-pi, pi]
+                     J = 1/2 sum w phi^2                                         G_kj = w_kj phi_kj (i S_kj) / |S_kj|^2
+        kind LOG     the sum of LOGAMP and PHASE (the logarithmic misfit), over the pairs that count under PHASE
+        g[n,j] = M[n,j] sum_k (Re G_kj cos theta_kn - Im G_kj sin theta_kn)     (rounded to the dtype once)
+        r = dJ/ds = B g
+
+    Under PHASE and LOG a pair ``(k, j)`` counts iff ``|S_kj|^2 > eps^2`` and ``|O_kj|^2 > eps^2``; otherwise its term of
+    ``J`` and its ``G`` are 0.  Under L2 and LOGAMP every pair counts.  ``eps >= 0`` is in the units of ``|S|`` and must
+    not follow ``s``.  ``Im(S conj O) = S_i O_r - S_r O_i`` is formed from two rounded products, so that equal gathers
+    give ``J = 0`` and ``r = 0`` exactly for every kind.  PHASE is exactly invariant under a gain on the synthetics.
+    ``J`` is not differentiable where ``phi = +-pi`` (a cycle skip at that frequency) nor where a pair starts or stops
+    counting, and ``phi`` wraps: a shift beyond half a period of ``f_k`` reads as a smaller one of the other sign.
+
+    ``dt``: the sampling interval in seconds.  ``freqs``: the ``1 .. 64`` frequencies in Hz (``fourier.fourier_bins(nt,
+    dt, 1, fmin, fmax)`` lists the bins of a band).  ``kind``: one of ``"l2"``, ``"phase"``, ``"logamp"``, ``"log"``.
+    ``eps``: the floor; None: :func:`spectral_floor` of each call's ``d_obs`` and weights at ``floor_percent``.  ``taps``:
+    the one-sided ``b_0 .. b_R`` of ``B``, or None.  ``dtype``: round ``B s``, ``B d`` (with taps) and ``g`` to it once
+    each, as a device context of that dtype does (None: keep fp64).  ``freq_weights``: the ``fw_k``, or None
+    (:func:`whitening_weights`).
+
+    ``spectra`` holds ``(S, O)`` of the last call, ``phases`` its ``phi_kj`` (wherever the pair passes the counting rule
+    of PHASE, whatever the kind; 0 elsewhere), ``logamps`` its ``a_kj`` (wherever the kind uses it or the pair passes that
+    rule; 0 elsewhere) and ``counts`` which pairs count under ``kind``, each ``(F, ntr)``.  Not a :class:`WeightedL2`:
+    ``gauss_newton_hvp`` refuses it (a Gauss-Newton weight for kind L2 is out of scope)."""
+
+    def __init__(self, dt, freqs, kind="l2", eps=None, taps=None, dtype=None, freq_weights=None, floor_percent=1.0):
+        if not (float(dt) > 0.0 and np.isfinite(dt)):
+            raise ValueError("dt must be > 0")
+        if kind not in SPECTRAL_KINDS:
+            raise ValueError("kind must be one of %r" % (SPECTRAL_KINDS,))
+        if eps is not None and not (float(eps) >= 0.0 and np.isfinite(eps)):
+            raise ValueError("eps must be finite and >= 0")
+        if not (float(floor_percent) >= 0.0 and np.isfinite(floor_percent)):
+            raise ValueError("floor_percent must be finite and >= 0")
+        self.dt, self.kind = float(dt), kind
+        self.freqs = _spectral_tables(1, self.dt, freqs, kind)[0].copy()  # (checked)
+        self.freq_weights = None
+        if freq_weights is not None:
+            fw = np.asarray(freq_weights, np.float64)
+            if fw.shape != self.freqs.shape or not np.all(np.isfinite(fw)) or np.any(fw < 0.0):
+                raise ValueError("freq_weights must be %d finite weights >= 0" % self.freqs.size)
+            self.freq_weights = fw
+        self.eps = None if eps is None else float(eps)
+        self.floor_percent = float(floor_percent)
+        self._band(taps, dtype)
+        self.spectra = self.phases = self.logamps = self.counts = None
+
+    def eps_of(self, d_obs, weights=None):
+        """the floor of a shot: ``eps``, or :func:`spectral_floor` of its observed data and weights"""
+        if self.eps is not None:
+            return self.eps
+        return spectral_floor(d_obs, self.dt, self.freqs, self.floor_percent, weights)
+
+    engine_method = "misfit_spectral"
+
+    def device(self, engine, shot, i):
+        return engine.misfit_spectral(shot.d_obs, self.freqs, self.kind, self.eps_of(shot.d_obs, shot.weights),
+                                      shot.weights, self.taps, self.freq_weights, shot.trace_weights)
+
+    def __call__(self, d_syn, d_obs, weights=None, trace_weights=None):
+        sh, dh, _ = self._weighted(d_syn, d_obs, weights)
+        nt, ntr = sh.shape
+        _, c, s = _spectral_tables(nt, self.dt, self.freqs, self.kind)
+        fw = np.ones(self.freqs.size) if self.freq_weights is None else self.freq_weights
+        w = fw[:, None] * self._trace_weights(trace_weights, ntr)[None, :]
+        e2 = self.eps_of(d_obs, weights) ** 2
+        Sr, Si, Or, Oi = c @ sh, -(s @ sh), c @ dh, -(s @ dh)
+        s2, o2 = Sr * Sr + Si * Si, Or * Or + Oi * Oi
+        both = (s2 > e2) & (o2 > e2)  # the counting rule of PHASE and LOG
+        amp = np.ones_like(both) if self.kind == "logamp" else both if self.kind == "log" else np.zeros_like(both)
+        ph = both if self.kind in ("phase", "log") else np.zeros_like(both)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a = np.where(amp | both, 0.5 * np.log((s2 + e2) / (o2 + e2)), 0.0)
+            # (two rounded products and their difference: equal spectra give exactly 0)
+            phi = np.where(both, np.arctan2(Si * Or - Sr * Oi, Sr * Or + Si * Oi), 0.0)
+            ca = np.where(amp, w * a / (s2 + e2), 0.0)
+            cp = np.where(ph, w * phi / s2, 0.0)
+        Gr, Gi = ca * Sr - cp * Si, ca * Si + cp * Sr
+        terms = np.where(amp, 0.5 * w * a * a, 0.0) + np.where(ph, 0.5 * w * phi * phi, 0.0)
+        if self.kind == "l2":
+            Dr, Di = Sr - Or, Si - Oi
+            Gr, Gi, terms = w * Dr, w * Di, 0.5 * w * (Dr * Dr + Di * Di)
+        self.spectra = (Sr + 1j * Si, Or + 1j * Oi)
+        self.phases, self.logamps = phi, a
+        self.counts = np.ones_like(both) if self.kind in ("l2", "logamp") else both
+        return float(np.sum(terms)), self._residual(c.T @ Gr - s.T @ Gi, weights)
 
 
 def matched_wavelet(wavelet, f):

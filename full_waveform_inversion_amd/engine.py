@@ -387,6 +387,43 @@ class Engine:
                          (twp, _lib.OT_TRANSFORMS[transform], float(param)), outp)
         return (J,) + out if per_trace else J
 
+    def misfit_spectral(self, d_obs, freqs, kind="l2", eps=0.0, weights=None, taps=None, freq_weights=None,
+                        trace_weights=None, per_pair=False):
+        """Frequency-domain (spectral) misfit of the last forward's seismograms: with ``sh = M . B d_syn``,
+        ``dh = M . B d_obs`` and ``S_kj``, ``O_kj`` their discrete Fourier coefficients at the ``F <= 64`` frequencies
+        ``freqs`` (Hz; ``fourier.fourier_bins(nt, dt, 1, fmin, fmax)`` lists the bins of a band, off-bin frequencies
+        are allowed), ``J = 1/2 sum_kj fw_k tw_j m_kj^2`` with ``m = |S - O|`` (``kind="l2"``), the phase difference
+        ``phi`` in (-pi, pi] (``"phase"``), the logarithmic amplitude ratio ``a = 1/2 ln((|S|^2 + eps^2) / (|O|^2 +
+        eps^2))`` (``"logamp"``) or both (``"log"``, the logarithmic misfit).  ``eps >= 0`` is an absolute floor in the
+        units of ``|S|`` that must not depend on the synthetics (``datafit.spectral_floor``); under ``"phase"`` and
+        ``"log"`` a pair counts only if ``|S|^2 > eps^2`` and ``|O|^2 > eps^2``.  ``weights`` and ``taps`` as in
+        :meth:`misfit_weighted` (``datafit.laplace_damping`` gives the weights of a Laplace-Fourier misfit);
+        ``freq_weights``: the ``F`` weights ``fw_k >= 0`` (None: 1; ``datafit.whitening_weights``); ``trace_weights`` as
+        in :meth:`misfit_correlation`.  ``phi`` wraps: a shift beyond half a period of ``f_k`` reads as a smaller one of
+        the other sign, and J is not differentiable at ``phi = +-pi``.  The adjoint source ``dJ/dd_syn`` is formed on
+        the device and kept there for ``adjoint(None)``.  Returns J, with ``per_pair=True`` ``(J, phi, a, counts)``, each
+        ``(F, ntr)`` (``fwi_misfit_spectral``; the NumPy twin is :class:`datafit.SpectralMisfit`)."""
+        if kind not in _lib.SPEC_KINDS:
+            raise ValueError("kind must be one of %s" % sorted(_lib.SPEC_KINDS))
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(freqs, np.float64)))
+        if f.ndim != 1 or f.size < 1:
+            raise ValueError("freqs must be a non-empty 1-D array of frequencies in Hz")
+        fwp = fw = None
+        if freq_weights is not None:
+            fw = np.ascontiguousarray(freq_weights, dtype=np.float64)
+            if fw.shape != f.shape:
+                raise ValueError("freq_weights must hold one weight per frequency, shape (%d,)" % f.size)
+            fwp = fw.ctypes.data_as(C.c_void_p)
+        twp, _keep = self._trace_weights(trace_weights)
+        out = outp = ()
+        if per_pair:
+            out = tuple(np.zeros((f.size, self._nrec), t) for t in (np.float64, np.float64, np.uint8))
+            outp = tuple(a.ctypes.data_as(C.c_void_p) for a in out)
+        J = self._misfit(self._lib.fwi_misfit_spectral, d_obs, weights, taps,
+                         (f.size, f.ctypes.data_as(C.c_void_p), _lib.SPEC_KINDS[kind], float(eps), fwp, twp),
+                         outp or (None, None, None))
+        return (J,) + out if per_pair else J
+
     def residual_weight(self, weights=None, taps=None):
         """The residual on the device (what ``born`` or a misfit call left for ``adjoint(None)``) := ``B M^2 B`` residual,
         the Gauss-Newton weight of :meth:`misfit_weighted` (``fwi_residual_weight``)."""

@@ -301,10 +301,11 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     (see objectives.py for the reference's similarity measures as misfits).
 
     An objective of :mod:`datafit` -- ``WeightedL2``, ``MatchedL2``, ``EnvelopeL2``, ``NormalizedCorrelation``,
-    ``TraveltimeL2``, ``TransportW2`` or a subclass of one -- names its own two calls.  ``objective.host(d_syn, shot, i)``
-    is the NumPy twin with what its class takes from the shot: ``Shot.weights``, for the three sums over traces
-    ``Shot.trace_weights`` as well, for the matching filter ``shot=i``.  Under ``device_l2``, an engine that has the
-    method ``objective.engine_method`` (``misfit_weighted`` ... ``misfit_transport``) is called through
+    ``TraveltimeL2``, ``TransportW2``, ``SpectralMisfit`` or a subclass of one -- names its own two calls.
+    ``objective.host(d_syn, shot, i)`` is the NumPy twin with what its class takes from the shot: ``Shot.weights``, for
+    the sums over traces and the spectral misfit ``Shot.trace_weights`` as well, for the matching filter ``shot=i``.
+    Under ``device_l2``, an engine that has the
+    method ``objective.engine_method`` (``misfit_weighted`` ... ``misfit_spectral``) is called through
     ``objective.device(engine, shot, i)`` instead: misfit and adjoint source are formed on the device, per node, or per
     off-grid point where the engine spreads them.
 

@@ -369,6 +369,57 @@ int fwi_misfit_transport(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const 
                          const double *trace_weights /* ntr, or NULL */, int32_t transform, double param, double *J_out,
                          double *w2_out /* ntr, or NULL: W_j in s^2 */, int32_t *counts_out /* ntr, or NULL: 1 / 0 */);
 
+/* Frequency-domain (spectral) data misfit on the device: every misfit above compares traces in the time domain; this
+ * one compares their discrete Fourier coefficients at F frequencies of the caller's choice, amplitude and phase together
+ * or apart (the logarithmic and phase-only misfits of Shin & Min 2006 and Bednar, Shin & Pyun 2007), with a weight per
+ * frequency.  It is the data side of frequency-domain FWI from time-domain modelling, whose model side is
+ * fwi_set_fourier_store.  With s = d_syn of the last forward and d = d_obs, both (nt, ntr) as above:
+ *     sh = M . B d_syn,  dh = M . B d_obs    M (per-sample weights, or none) and B (taps, or none) exactly as in
+ *                                            fwi_misfit_correlation; B s and B d are rounded to the context's dtype once,
+ *                                            only when taps are given; ntr is the number of receivers, or of receiver
+ *                                            points after fwi_forward_spread
+ *     theta_kn = 2 pi frac(f_k n dt)         formed on the host in fp64 from the fractional part, as the table of
+ *                                            fwi_set_fourier_store is; f_k: the F frequencies in Hz
+ *     S_kj = sum_n sh[n,j] (cos theta_kn - i sin theta_kn)        O_kj likewise from dh
+ *     w_kj = fw_k * tw_j                     fw: F weights per frequency (NULL: 1), tw: ntr weights per trace (NULL: 1),
+ *                                            all finite and >= 0
+ *     kind L2      J = 1/2 sum_kj w_kj |S_kj - O_kj|^2                         G_kj = w_kj (S_kj - O_kj)
+ *     kind LOGAMP  a_kj = 1/2 ln((|S_kj|^2 + eps^2) / (|O_kj|^2 + eps^2))
+ *                  J = 1/2 sum w a^2                                            G_kj = w_kj a_kj S_kj / (|S_kj|^2 + eps^2)
+ *     kind PHASE   phi_kj = atan2(Im(S_kj conj O_kj), Re(S_kj conj O_kj)) in (-pi, pi]
+ *                  J = 1/2 sum w phi^2                                          G_kj = w_kj phi_kj (i S_kj) / |S_kj|^2
+ *     kind LOG     the sum of LOGAMP and PHASE (the logarithmic misfit), over the pairs that count under PHASE
+ *     g[n,j] = M[n,j] sum_k (Re G_kj cos theta_kn - Im G_kj sin theta_kn)      (rounded to the dtype once)
+ *     r = dJ/ds = B g                        the residual of the next fwi_adjoint(ctx, NULL, ...)
+ * Which pairs count: under PHASE and LOG a pair (k, j) counts iff |S_kj|^2 > eps^2 and |O_kj|^2 > eps^2; otherwise its
+ * term of J and its G are 0.  Under L2 and LOGAMP every pair counts (LOGAMP with eps = 0 is then infinite where a
+ * coefficient vanishes: give it a floor).  eps >= 0 is in the units of |S| and, like every floor above, must not depend
+ * on s.  Im(S conj O) = S_i O_r - S_r O_i is formed from two rounded products, never a fused one: equal gathers give
+ * J = 0 and a zero adjoint source exactly, for every kind.  PHASE is exactly invariant under a gain on the synthetics.
+ * J is NOT differentiable where phi = +-pi (a cycle skip at that frequency) nor where a pair starts or stops counting,
+ * and phi wraps: a time shift beyond half a period of f_k reads as a smaller one of the other sign.  Per-frequency
+ * weights whiten the spectrum; an exponential damping exp(-sigma n dt) inside M gives the Laplace-Fourier misfit.
+ * *J_out = J.  The three optional outputs are (F, ntr), frequency the slow axis: phase_out receives phi_kj wherever the
+ * pair passes the counting rule of PHASE (whatever the kind) and 0 elsewhere; logamp_out receives a_kj wherever the kind
+ * uses it or the pair passes that rule and 0 elsewhere; counts_out 1 for a pair that counts under `kind` and 0 otherwise.
+ * The synthetics are left alone: the call can be repeated.  Everything between the loads and the roundings named above
+ * is fp64: a thread adds its 16 consecutive times by fma in ascending order, a block its 16 waves in wave order, a pair
+ * its time segments of 256 rows in ascending order, the source its frequencies by fma in ascending order and J its terms
+ * in a fixed order, without atomics: equal inputs give equal bits.  The table of twiddles is kept on the context and
+ * rebuilt only when nt or the frequencies change.  State rules, off-grid receivers and work buffers as
+ * fwi_misfit_weighted.  FWI_EINVAL, with the reason in the message: a null J_out, a null d_obs with nrec > 0, the tap
+ * errors of fwi_misfit_weighted, nfreq outside [1, FWI_FOURIER_FMAX], null frequencies, a frequency that is negative, not
+ * finite, equal to another or above 1 / (2 dt); under PHASE or LOG a frequency of 0 or within 1e-9 (relative) of
+ * 1 / (2 dt), where S is real; an unknown kind; eps or a weight that is negative or not finite.  No receivers: J = 0,
+ * the outputs are zeros and nothing is launched. */
+enum { FWI_SPEC_L2 = 0, FWI_SPEC_PHASE = 1, FWI_SPEC_LOGAMP = 2, FWI_SPEC_LOG = 3 };
+int fwi_misfit_spectral(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                        const double *taps /* R + 1, or NULL */, int32_t R, int32_t nfreq,
+                        const double *freqs_hz /* nfreq */, int32_t kind, double eps,
+                        const double *freq_weights /* nfreq, or NULL */, const double *trace_weights /* ntr, or NULL */,
+                        double *J_out, double *phase_out /* (F, ntr) or NULL */, double *logamp_out /* (F, ntr) or NULL */,
+                        uint8_t *counts_out /* (F, ntr) or NULL */);
+
 /* gradient(): copy out the accumulated gradient, model-shaped, as dJ/dc
  * (FWI_WRT_VELOCITY) or dJ/d(1/c^2) (FWI_WRT_SLOWNESS2).
  * [SURVEY s.8(a-1) row gradient] */

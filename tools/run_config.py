@@ -105,8 +105,38 @@ def main():
     ap.add_argument("--transport-param", type=float, default=None, metavar="X",
                     help="the absolute parameter of --transport: b of softplus, c of linear (default: per shot from its "
                          "observed data, datafit.TransportW2.param_of, computed once and held through the run)")
+    ap.add_argument("--spectral", choices=datafit.SPECTRAL_KINDS, default=None,
+                    help="frequency-domain misfit on the bins of --spectral-band: 1/2 the sum over frequencies and traces "
+                         "of the squared difference of the Fourier coefficients (l2), of their phases (phase), of their "
+                         "logarithmic amplitudes (logamp) or of both (log, the logarithmic misfit) "
+                         "(datafit.SpectralMisfit, on the device); composes with --bands and --mute-direct, not with the "
+                         "other misfits")
+    ap.add_argument("--spectral-band", default=None, metavar="FMIN,FMAX",
+                    help="the band of --spectral in Hz: the 1 .. 64 bins k / (nt dt) inside it (fourier.fourier_bins); "
+                         "without it, with --fourier-store, the bins of the store")
+    ap.add_argument("--spectral-floor-percent", type=float, default=1.0, metavar="X",
+                    help="floor under the coefficients per shot: X / 100 of the largest coefficient of the shot's (weighted) "
+                         "observed data (datafit.spectral_floor), computed once per evaluation from the data alone")
+    ap.add_argument("--spectral-whiten", action="store_true",
+                    help="frequency weights 1 / (mean power of the observed data at the frequency + 1e-4 of the largest): "
+                         "the weak frequencies count like the strong ones (datafit.whitening_weights; one rank)")
     a = ap.parse_args()
     bands = [float(f) for f in a.bands.split(",")] if a.bands else None
+    if a.spectral is None and (a.spectral_band is not None or a.spectral_whiten):
+        ap.error("--spectral-band / --spectral-whiten need --spectral")
+    if a.spectral is not None and a.spectral_band is None and a.fourier_store is None:
+        ap.error("--spectral needs --spectral-band FMIN,FMAX (or --fourier-store, whose bins it then takes)")
+    if not (a.spectral_floor_percent >= 0.0 and np.isfinite(a.spectral_floor_percent)):
+        ap.error("--spectral-floor-percent X must be finite and >= 0")
+    if a.spectral_whiten and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--spectral-whiten takes its weights from this rank's data: it runs on one rank")
+    spectral_band = None
+    if a.spectral_band is not None:
+        try:
+            spectral_band = tuple(float(v) for v in a.spectral_band.split(","))
+            assert len(spectral_band) == 2
+        except (ValueError, AssertionError):
+            ap.error("--spectral-band takes FMIN,FMAX in Hz")
     if bands and (a.iters < 1 or a.checkpoint or a.resume):
         ap.error("--bands needs --iters > 0 and runs without --checkpoint / --resume (one optimiser state per band)")
     if bands and (a.precondition is not None or a.smooth is not None or a.mute_sources is not None
@@ -117,7 +147,7 @@ def main():
         ap.error("--match-source L must lie in [0, %d]" % datafit.L_MAX)
     if not (a.match_mu_percent >= 0.0 and np.isfinite(a.match_mu_percent)):
         ap.error("--match-mu-percent P must be finite and >= 0")
-    misfits = [flag for flag in ("--transport", "--traveltime", "--correlation", "--envelope", "--match-source")
+    misfits = [flag for flag in ("--spectral", "--transport", "--traveltime", "--correlation", "--envelope", "--match-source")
                if getattr(a, flag[2:].replace("-", "_")) is not None]
     if len(misfits) > 1:
         ap.error("%s are different misfits: choose one" % " and ".join(misfits))
@@ -169,6 +199,17 @@ def main():
             ap.error("--fourier-store: [%g, %g] Hz holds %d bins of the sampled time axis (1 .. 64 allowed; the bins "
                      "lie 1 / (nt dt) apart)" % (fmin, fmax, bins.size))
         uf.update(fourier=bins, fourier_batch=a.fourier_batch)
+    spectral_freqs = None
+    if a.spectral is not None:
+        from full_waveform_inversion_amd import fourier
+        spectral_freqs = uf["fourier"] if spectral_band is None else fourier.fourier_bins(w.nt, w.dt, 1, *spectral_band)
+        if not 1 <= spectral_freqs.size <= 64:
+            ap.error("--spectral-band: the band holds %d bins of the time axis (1 .. 64 allowed; the bins lie 1 / (nt dt) "
+                     "apart)" % spectral_freqs.size)
+        try:
+            datafit.SpectralMisfit(w.dt, spectral_freqs, a.spectral)
+        except ValueError as err:
+            ap.error("--spectral %s: %s" % (a.spectral, err))
     pool = sh.EnginePool(lambda: sh.inversion_engine(w.shape, w.h, w.dt, w.nt, order=w.order, npml=w.npml, device=local,
                                                      sigma_max=sigma, image_stride=a.image_stride, abc=a.abc,
                                                      launch_mode=a.launch_mode, **uf,
@@ -198,8 +239,17 @@ def main():
         match_mu = [datafit.prewhitening(s.d_obs, s.weights, a.match_mu_percent) if s.d_obs is not None else 0.0
                     for s in shots]
 
+    spectral_fw = None
+    if a.spectral_whiten:  # data-only numbers, fixed for the run: the mean power over this rank's shots
+        power = [1.0 / datafit.whitening_weights(s.d_obs, w.dt, spectral_freqs, 0.0) for s in shots if s.d_obs is not None]
+        power = np.mean(power, axis=0)
+        spectral_fw = 1.0 / (power + 1e-4 * float(power.max()))
+
     def objective_of(taps):
         """the misfit of one stage: a fresh object per band (a MatchedL2 keeps the shots' filters of ITS band)"""
+        if a.spectral is not None:  # (the floor: a data-only number per shot, datafit.spectral_floor of its d_obs)
+            return datafit.SpectralMisfit(w.dt, spectral_freqs, a.spectral, None, taps, freq_weights=spectral_fw,
+                                          floor_percent=a.spectral_floor_percent)
         if a.match_source is not None:
             return datafit.MatchedL2(a.match_source, match_mu, taps)
         if a.envelope is not None:  # (the floor: a data-only number per shot, datafit.envelope_floor of its d_obs)
@@ -317,7 +367,10 @@ def main():
                           "reg_weight": a.reg_weight, "reg_eps": reg_eps, "reg_prior": a.reg_prior, "bands_hz": bands,
                           "band_halfwidth": a.band_halfwidth if bands else None, "mute_direct": a.mute_direct,
                           "match_source": a.match_source, "correlation_floor_percent": a.correlation,
-                          "traveltime_max_lag": a.traveltime,
+                          "traveltime_max_lag": a.traveltime, "spectral": a.spectral,
+                          "spectral_freqs_hz": None if spectral_freqs is None else [float(f) for f in spectral_freqs],
+                          "spectral_floor_percent": a.spectral_floor_percent if a.spectral is not None else None,
+                          "spectral_whiten": a.spectral_whiten,
                           "transport": a.transport, "transport_param": a.transport_param,
                           "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
                           "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
