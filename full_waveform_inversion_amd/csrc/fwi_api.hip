@@ -344,6 +344,48 @@ int ensure(fwi_ctx *ctx, void **p, size_t *cap, size_t bytes) {
     return FWI_OK;
 }
 
+// ... and for a group of buffers of `bytes` each that share one capacity
+int ensure_all(fwi_ctx *ctx, std::initializer_list<void **> group, size_t *cap, size_t bytes) {
+    if (*cap >= bytes && std::all_of(group.begin(), group.end(), [](void **p) { return *p != nullptr; })) return FWI_OK;
+    for (void **p : group) {
+        if (*p) HIPCHK(ctx, hipFree(*p));
+        *p = nullptr;
+        HIPCHK(ctx, hipMalloc(p, bytes ? bytes : 16));
+    }
+    *cap = bytes;
+    return FWI_OK;
+}
+
+// All-or-nothing device allocation: every entry of `want` with bytes (entries of none are skipped), `zero` ones cleared on
+// the context's stream, provided their sum fits into the free memory.  FWI_ENOMEM without a message where it does not fit
+// or an allocation fails: whatever was allocated is freed again, every pointer is null, and the caller reports *total
+// against *free_bytes in its own words.
+struct Want {
+    void **p;
+    size_t bytes;
+    bool zero;
+};
+int alloc_all(fwi_ctx *ctx, std::initializer_list<Want> want, size_t *total, size_t *free_bytes) {
+    size_t device_bytes = 0;
+    *total = 0;
+    for (const Want &w : want) *total += w.bytes;
+    HIPCHK(ctx, hipMemGetInfo(free_bytes, &device_bytes));
+    hipError_t e = hipSuccess;
+    if (*total <= *free_bytes)
+        for (const Want &w : want) {
+            if (!w.bytes) continue;
+            if ((e = hipMalloc(w.p, w.bytes)) != hipSuccess) break;
+            if (w.zero && (e = hipMemsetAsync(*w.p, 0, w.bytes, ctx->stream)) != hipSuccess) break;
+        }
+    if (*total <= *free_bytes && e == hipSuccess) return FWI_OK;
+    (void)hipGetLastError();
+    for (const Want &w : want) {
+        if (*w.p) (void)hipFree(*w.p);
+        *w.p = nullptr;
+    }
+    return FWI_ENOMEM;
+}
+
 // the block partials (and their total) of the fixed-order sums (launch_dot, launch_residual_l2): allocated on first use
 int sum_partials(fwi_ctx *ctx, double **part) {
     if (!ctx->sum_part) HIPCHK(ctx, hipMalloc(&ctx->sum_part, (size_t)(SUM_MAX_BLOCKS + 1) * sizeof(double)));
@@ -652,15 +694,9 @@ struct Impl {
         int rcode;
         if ((rcode = flatten(ctx, idx, n, p, c))) return rcode;
         const size_t need = (size_t)n * 8 + 16;
-        if (ps.cap < need) {
-            for (void **q : {&ps.pidx, &ps.cidx, &ps.cu, &ps.cq, &ps.s_pidx, &ps.s_cidx, &ps.s_cu, &ps.s_cq,
-                             &ps.s_col, &ps.s_run}) {
-                if (*q) HIPCHK(ctx, hipFree(*q));
-                *q = nullptr;
-                HIPCHK(ctx, hipMalloc(q, need));
-            }
-            ps.cap = need;
-        }
+        if ((rcode = ensure_all(ctx, {&ps.pidx, &ps.cidx, &ps.cu, &ps.cq, &ps.s_pidx, &ps.s_cidx, &ps.s_cu, &ps.s_cq,
+                                      &ps.s_col, &ps.s_run}, &ps.cap, need)))
+            return rcode;
         auto up = [&](void *d, const void *h, size_t b) {
             return b ? hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
         };
@@ -710,12 +746,7 @@ struct Impl {
                 run[k] = (k == 0 || sp[k - 1] != sp[k] || tile[ord[k - 1]] != tile[ord[k]]) ? len : 0;
             }
             const size_t sb = start.size() * sizeof(int);
-            if (ps.cap_start < sb) {
-                if (ps.s_start) HIPCHK(ctx, hipFree(ps.s_start));
-                ps.s_start = nullptr;
-                HIPCHK(ctx, hipMalloc(&ps.s_start, sb));
-                ps.cap_start = sb;
-            }
+            if ((rcode = ensure(ctx, &ps.s_start, &ps.cap_start, sb))) return rcode;
             HIPCHK(ctx, up(ps.s_start, start.data(), sb));
             HIPCHK(ctx, up(ps.s_pidx, sp.data(), (size_t)n * 8));
             HIPCHK(ctx, up(ps.s_cidx, sc.data(), (size_t)n * 8));
@@ -791,23 +822,10 @@ struct Impl {
                 fint[k] = e.interior; fcidx[k] = c[e.col]; fcu[k] = cu[e.col]; fcq[k] = cq[e.col];
             }
             const size_t fneed = ne * 8 + 16, sneed = (size_t)(ntile + 1) * sizeof(int);
-            if (ps.fcap < fneed) {
-                for (void **q : {&ps.fi_lz, &ps.fi_lx, &ps.fi_col, &ps.fi_int, &ps.fi_cidx, &ps.fi_cu, &ps.fi_cq,
-                                 &ps.fi_run, &ps.fr_lz, &ps.fr_lx, &ps.fr_col}) {
-                    if (*q) HIPCHK(ctx, hipFree(*q));
-                    *q = nullptr;
-                    HIPCHK(ctx, hipMalloc(q, fneed));
-                }
-                ps.fcap = fneed;
-            }
-            if (ps.fcap_start < sneed) {
-                for (void **q : {&ps.fi_start, &ps.fr_start}) {
-                    if (*q) HIPCHK(ctx, hipFree(*q));
-                    *q = nullptr;
-                    HIPCHK(ctx, hipMalloc(q, sneed));
-                }
-                ps.fcap_start = sneed;
-            }
+            if ((rcode = ensure_all(ctx, {&ps.fi_lz, &ps.fi_lx, &ps.fi_col, &ps.fi_int, &ps.fi_cidx, &ps.fi_cu, &ps.fi_cq,
+                                          &ps.fi_run, &ps.fr_lz, &ps.fr_lx, &ps.fr_col}, &ps.fcap, fneed)) ||
+                (rcode = ensure_all(ctx, {&ps.fi_start, &ps.fr_start}, &ps.fcap_start, sneed)))
+                return rcode;
             HIPCHK(ctx, up(ps.fi_start, fst.data(), sneed));
             HIPCHK(ctx, up(ps.fr_start, rst.data(), sneed));
             HIPCHK(ctx, up(ps.fi_lz, flz.data(), ne * sizeof(int)));
@@ -869,18 +887,9 @@ struct Impl {
                     pent.insert(pent.end(), per[k].begin(), per[k].end());
                 }
                 const size_t sb = pst.size() * sizeof(int), eb = pent.size() * sizeof(Pair3dInj) + 16;
-                if (ps.pcap_start < sb) {
-                    if (ps.pr_start) HIPCHK(ctx, hipFree(ps.pr_start));
-                    ps.pr_start = nullptr;
-                    HIPCHK(ctx, hipMalloc(&ps.pr_start, sb));
-                    ps.pcap_start = sb;
-                }
-                if (ps.pcap < eb) {
-                    if (ps.pr_ent) HIPCHK(ctx, hipFree(ps.pr_ent));
-                    ps.pr_ent = nullptr;
-                    HIPCHK(ctx, hipMalloc(&ps.pr_ent, eb));
-                    ps.pcap = eb;
-                }
+                if ((rcode = ensure(ctx, &ps.pr_start, &ps.pcap_start, sb)) ||
+                    (rcode = ensure(ctx, &ps.pr_ent, &ps.pcap, eb)))
+                    return rcode;
                 HIPCHK(ctx, up(ps.pr_start, pst.data(), sb));
                 HIPCHK(ctx, up(ps.pr_ent, pent.data(), pent.size() * sizeof(Pair3dInj)));
             }
@@ -1176,12 +1185,7 @@ struct Impl {
         if (rc) return rc;
         hipEvent_t e0 = nullptr, e1 = nullptr;  // (every failure from here on leaves through `done`, which destroys them)
         const fwi_ctx::PointSet nobody;
-        auto none = [](int) -> T * { return nullptr; };
-        auto noq = [](int, const T *&p, const T *&p2) { p = p2 = nullptr; };
-        Sweep sw;
-        sw.f[0] = ctx->u[0];
-        sw.f[1] = ctx->u[1];
-        sw.v = ctx->vf;
+        Sweep sw = main_sweep(ctx);
         int nstep = 0;
         auto timed = [&](int n, float *us) -> int {  // n time steps of the real launch sequence, no sources, no receivers
             sw.v = ctx->vf;  // (a movable array itself in increment form)
@@ -1256,38 +1260,120 @@ struct Impl {
         return FWI_OK;
     }
 
+    // What the three sweeps (forward, adjoint, born) share on the host.  Everything here that queues a memset is called
+    // before TimeLoop::begin(); save_segment / restore_segment queue device-to-device copies only and run inside the loop.
+
+    static T *none(int) { return nullptr; }                                  // run_steps: no q_out ...
+    static void noq(int, const T *&p, const T *&p2) { p = p2 = nullptr; }  // ... and no q_in
+
+    static Sweep main_sweep(fwi_ctx *ctx) {
+        Sweep sw;
+        sw.f[0] = ctx->u[0];
+        sw.f[1] = ctx->u[1];
+        sw.v = ctx->vf;
+        return sw;
+    }
+
+    // the sweep in u[] / vf from zeroed fields and memory variables
+    static int start_sweep(fwi_ctx *ctx, Sweep &sw) {
+        int rc = zero_fields(ctx, ctx->u[0], ctx->u[1]);
+        if (rc) return rc;
+        sw = main_sweep(ctx);
+        if (ctx->inc) HIPCHK(ctx, hipMemsetAsync(ctx->vf, 0, (size_t)ctx->gd.ptot * sizeof(T), ctx->stream));
+        return ctx->cpml ? pml_zero(ctx) : FWI_OK;
+    }
+
+    // the checkpointed forward recomputation: its own fields and its own set of memory variables
+    static Sweep recompute_sweep(fwi_ctx *ctx) {
+        Sweep fw;
+        fw.f[0] = ctx->fwd[0];
+        fw.f[1] = ctx->fwd[1];
+        fw.v = ctx->fwv;
+        fw.pml_fw = true;
+        return fw;
+    }
+
+    // snapshot `seg` of a checkpointed forward: two padded fields, (u^n0, u^{n0-1}) or, increment form, (u^n0, v^n0)
+    static T *snapshot(fwi_ctx *ctx, int seg) {
+        const GridDesc &g = ctx->gd;
+        return (T *)ctx->snap + (size_t)seg * 2 * g.ptot;
+    }
+
+    static int save_segment(fwi_ctx *ctx, const Sweep &sw, int seg) {
+        const size_t n = (size_t)ctx->gd.ptot;
+        T *sn = snapshot(ctx, seg);
+        HIPCHK(ctx, hipMemcpyAsync(sn, sw.f[sw.cur], n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(sn + n, ctx->inc ? sw.v : sw.f[sw.cur ^ 1], n * sizeof(T), hipMemcpyDeviceToDevice,
+                                   ctx->stream));
+        return ctx->cpml ? pml_snapshot(ctx, seg, false, false) : FWI_OK;
+    }
+
+    // ... and back into the recomputation sweep, which starts over from it
+    static int restore_segment(fwi_ctx *ctx, Sweep &fw, int seg) {
+        const size_t n = (size_t)ctx->gd.ptot;
+        const T *sn = snapshot(ctx, seg);
+        fw.cur = 0;
+        fw.prev_n = -1;
+        HIPCHK(ctx, hipMemcpyAsync(fw.f[0], sn, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->inc ? fw.v : fw.f[1], sn + n, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        return ctx->cpml ? pml_snapshot(ctx, seg, true, true) : FWI_OK;
+    }
+
+    // The fused and the two-step launches swap the buffers of a sweep with its spare pair: the context owns whichever
+    // the sweep ended with (a no-op after a sweep that swapped nothing).  After the loops, never on an error return.
+    static void adopt(fwi_ctx *ctx, const Sweep &sw, void *const *spare) {
+        ctx->u[0] = sw.f[0];
+        ctx->u[1] = sw.f[1];
+        ctx->fx[0] = spare[0];
+        ctx->fx[1] = spare[1];
+        ctx->vf = sw.v;
+    }
+
+    static void adopt_recompute(fwi_ctx *ctx, const Sweep &fw, void *const *fspare) {
+        ctx->fwd[0] = fw.f[0];
+        ctx->fwd[1] = fw.f[1];
+        ctx->fwx[0] = fspare[0];
+        ctx->fwx[1] = fspare[1];
+        ctx->fwv = fw.v;
+    }
+
+    // Where the forward term q^n of step n lives, by the kind of store the context holds
+    struct Store {
+        char *q;        // q_store
+        T *ring;        // Fourier store: the B + 1 ring slots
+        size_t slot_bytes;  // of the native store, which may hold bf16
+        int64_t npts;
+        int S, K, R;
+        explicit Store(const fwi_ctx *ctx)
+            : q((char *)ctx->q_store), ring((T *)ctx->four_ring), slot_bytes((size_t)ctx->gd.npts * ctx->qes),
+              npts(ctx->gd.npts), S(ctx->istride), K(ctx->ckpt), R(ctx->four_batch + 1) {}
+        // native store: q^n is kept for n % S == 0, in slot n / S
+        void *slot(int n) const { return q + (size_t)(n / S) * slot_bytes; }
+        size_t bytes(int nt) const { return ((size_t)nt + S - 1) / S * slot_bytes; }
+        // checkpointed: K slots for the steps of the segment that begins at n0 (n may lie below n0: run_fused's q_base
+        // is the slot of step 0), then the carry
+        T *seg_slot(int n, int n0) const { return (T *)q + (int64_t)(n - n0) * npts; }
+        T *carry() const { return (T *)q + (int64_t)K * npts; }
+        // Fourier store: sample j = n / S in ring slot j % (B + 1)
+        T *ring_slot(int n) const { return ring + (int64_t)((n / S) % R) * npts; }
+    };
+
     // Fourier store: the accumulators, the ring and the device table, all or nothing, by the first forward(save)
     static int fourier_alloc(fwi_ctx *ctx) {
         if (ctx->four_acc) return FWI_OK;
-        const GridDesc &g = ctx->gd;
-        const size_t F = ctx->four_freqs.size(), vol = (size_t)g.npts * sizeof(T);
+        const size_t F = ctx->four_freqs.size(), vol = (size_t)ctx->gd.npts * sizeof(T);
         const int rows = (ctx->cfg.nt_max + ctx->istride - 1) / ctx->istride + FOURIER_BMAX - 1;
-        struct { void **p; size_t bytes; } want[] = {{&ctx->four_acc, 2 * F * vol},
-                                                     {&ctx->four_ring, (size_t)(ctx->four_batch + 1) * vol},
-                                                     {&ctx->four_tw, F * rows * 2 * sizeof(double)}};
-        size_t total = 0, fr = 0, tot = 0;
-        for (auto &w : want) total += w.bytes;
-        HIPCHK(ctx, hipMemGetInfo(&fr, &tot));
-        hipError_t e = hipSuccess;
-        if (total <= fr)
-            for (auto &w : want)
-                // (zeroed: the pad columns of a ring slot are the step kernels' to write or to leave)
-                if ((e = hipMalloc(w.p, w.bytes)) != hipSuccess ||
-                    (e = hipMemsetAsync(*w.p, 0, w.bytes, ctx->stream)) != hipSuccess)
-                    break;
-        if (total > fr || e != hipSuccess) {
-            (void)hipGetLastError();
-            for (auto &w : want) {
-                if (*w.p) (void)hipFree(*w.p);
-                *w.p = nullptr;
-            }
-            return ctx->fail(FWI_ENOMEM,
+        const size_t acc = 2 * F * vol, ring = (size_t)(ctx->four_batch + 1) * vol;
+        size_t total, fr;
+        // (zeroed: the pad columns of a ring slot are the step kernels' to write or to leave)
+        if (int rc = alloc_all(ctx, {{&ctx->four_acc, acc, true}, {&ctx->four_ring, ring, true},
+                                     {&ctx->four_tw, F * rows * 2 * sizeof(double), true}}, &total, &fr))
+            return rc != FWI_ENOMEM ? rc : ctx->fail(FWI_ENOMEM,
                              "Fourier forward-term store needs %.1f GiB (%d frequencies, batch %d) but only %.1f GiB are "
                              "free; fewer frequencies or a smaller batch need less",
                              total / 1073741824.0, (int)F, ctx->four_batch, fr / 1073741824.0);
-        }
         ctx->four_rows = rows;
-        ctx->store_held = want[0].bytes + want[1].bytes;
+        ctx->store_held = acc + ring;
         return FWI_OK;
     }
 
@@ -1325,59 +1411,39 @@ struct Impl {
         int rc;
         if ((rc = upload_points(ctx, nsrc, src_idx, nrec, rec_idx))) return rc;
         if (four && (rc = fourier_alloc(ctx))) return rc;
+        size_t total, fr;
         if (save && K == 0 && !four && !ctx->q_store) {
-            const size_t slots = ((size_t)ctx->cfg.nt_max + ctx->istride - 1) / ctx->istride;
-            const size_t bytes = slots * g.npts * ctx->qes;
-            size_t fr = 0, tot = 0;
-            HIPCHK(ctx, hipMemGetInfo(&fr, &tot));
-            if (bytes > fr)
-                return ctx->fail(FWI_ENOMEM,
+            if ((rc = alloc_all(ctx, {{&ctx->q_store, Store(ctx).bytes(ctx->cfg.nt_max), false}}, &total, &fr)))
+                return rc != FWI_ENOMEM ? rc : ctx->fail(FWI_ENOMEM,
                                  "forward-term store needs %.1f GiB (nt_max=%d) but only %.1f GiB are free; "
                                  "set ckpt_interval (recomputation) or image_stride (decimated imaging)",
-                                 bytes / 1073741824.0, ctx->cfg.nt_max, fr / 1073741824.0);
-            HIPCHK(ctx, hipMalloc(&ctx->q_store, bytes));
-            ctx->store_held = bytes;
+                                 total / 1073741824.0, ctx->cfg.nt_max, fr / 1073741824.0);
+            ctx->store_held = total;
         }
         if (save && K > 0 && !ctx->ckpt_ready) {
             // snapshots of (u^n, u^{n-1}) per segment, K + 1 imaging-term slots, the recomputation's field
             // pair(s).  All or nothing: a partial set would let a later adjoint run on null buffers.
             const int nseg = (ctx->cfg.nt_max + K - 1) / K;
             const size_t fb = (size_t)g.ptot * sizeof(T);
-            struct { void **p; size_t bytes; bool zero; } want[] = {
-                {&ctx->snap, (size_t)nseg * 2 * fb, false},
-                {&ctx->q_store, (size_t)(K + 1) * g.npts * sizeof(T), false},  // K slots + carry
-                // (padded fields are zeroed at allocation: in increment form fwd[1] only ever receives interior points and its
-                // halo must read 0 -- found by the option fuzz reusing device memory of earlier contexts; the others are
-                // overwritten whole before use, but fwi_check_padding looks at every padded field of the context)
-                {&ctx->fwd[0], fb, true},
-                {&ctx->fwd[1], fb, true}, {&ctx->fwv, ctx->inc ? fb : 0, true},
-                {&ctx->fwx[0], ctx->fused2d ? fb : 0, true}, {&ctx->fwx[1], ctx->fused2d ? fb : 0, true},
-                {&ctx->pml_psi_fw[0], ctx->pml_bytes[0], false}, {&ctx->pml_zeta_fw[0], ctx->pml_bytes[0], false},
-                {&ctx->pml_psi_fw[1], ctx->pml_bytes[1], false}, {&ctx->pml_zeta_fw[1], ctx->pml_bytes[1], false},
-                {&ctx->pml_psi_fw[2], ctx->pml_bytes[2], false}, {&ctx->pml_zeta_fw[2], ctx->pml_bytes[2], false},
-                {&ctx->pml_snap, (size_t)nseg * 2 * (ctx->pml_bytes[0] + ctx->pml_bytes[1] + ctx->pml_bytes[2]), false}};
-            ctx->pml_snap_stride = 2 * (ctx->pml_bytes[0] + ctx->pml_bytes[1] + ctx->pml_bytes[2]);
-            size_t total = 0, fr = 0, tot = 0;
-            for (auto &w : want) total += w.bytes;
-            HIPCHK(ctx, hipMemGetInfo(&fr, &tot));
-            hipError_t e = hipSuccess;
-            if (total <= fr)
-                for (auto &w : want) {
-                    if (!w.bytes) continue;
-                    if ((e = hipMalloc(w.p, w.bytes)) != hipSuccess) break;
-                    if (w.zero && (e = hipMemsetAsync(*w.p, 0, w.bytes, ctx->stream)) != hipSuccess) break;
-                }
-            if (total > fr || e != hipSuccess) {
-                (void)hipGetLastError();
-                for (auto &w : want) {
-                    if (*w.p) (void)hipFree(*w.p);
-                    *w.p = nullptr;
-                }
-                return ctx->fail(FWI_ENOMEM,
+            const size_t *pb = ctx->pml_bytes;
+            ctx->pml_snap_stride = 2 * (pb[0] + pb[1] + pb[2]);
+            if ((rc = alloc_all(ctx, {
+                     {&ctx->snap, (size_t)nseg * 2 * fb, false},
+                     {&ctx->q_store, (size_t)(K + 1) * g.npts * sizeof(T), false},  // K slots + carry
+                     // (padded fields are zeroed at allocation: in increment form fwd[1] only ever receives interior points and
+                     // its halo must read 0 -- found by the option fuzz reusing device memory of earlier contexts; the others
+                     // are overwritten whole before use, but fwi_check_padding looks at every padded field of the context)
+                     {&ctx->fwd[0], fb, true},
+                     {&ctx->fwd[1], fb, true}, {&ctx->fwv, ctx->inc ? fb : 0, true},
+                     {&ctx->fwx[0], ctx->fused2d ? fb : 0, true}, {&ctx->fwx[1], ctx->fused2d ? fb : 0, true},
+                     {&ctx->pml_psi_fw[0], pb[0], false}, {&ctx->pml_zeta_fw[0], pb[0], false},
+                     {&ctx->pml_psi_fw[1], pb[1], false}, {&ctx->pml_zeta_fw[1], pb[1], false},
+                     {&ctx->pml_psi_fw[2], pb[2], false}, {&ctx->pml_zeta_fw[2], pb[2], false},
+                     {&ctx->pml_snap, (size_t)nseg * ctx->pml_snap_stride, false}}, &total, &fr)))
+                return rc != FWI_ENOMEM ? rc : ctx->fail(FWI_ENOMEM,
                                  "checkpoint buffers need %.1f GiB (nt_max=%d, ckpt_interval=%d) but only %.1f GiB "
                                  "are free; a ckpt_interval near sqrt(2 nt_max) needs the least memory",
                                  total / 1073741824.0, ctx->cfg.nt_max, K, fr / 1073741824.0);
-            }
             ctx->ckpt_ready = true;
             ctx->store_held = total;
         }
@@ -1397,17 +1463,11 @@ struct Impl {
         ctx->have_dev_residual = false;
         hipStream_t s = ctx->stream;
         if (nsrc && (rc = upload_amplitudes(ctx, ctx->wav, wavelet, nt, nsrc, ctx->src_sp))) return rc;
-        if ((rc = zero_fields(ctx, ctx->u[0], ctx->u[1]))) return rc;
         Sweep sw;
-        sw.f[0] = ctx->u[0];
-        sw.f[1] = ctx->u[1];
-        sw.v = ctx->vf;
-        if (ctx->inc) HIPCHK(ctx, hipMemsetAsync(ctx->vf, 0, (size_t)g.ptot * sizeof(T), ctx->stream));
-        if (ctx->cpml && (rc = pml_zero(ctx))) return rc;
+        if ((rc = start_sweep(ctx, sw))) return rc;
+        const Store st(ctx);
         T *q_store = (T *)ctx->q_store;
         T *series = (T *)ctx->series;
-        auto none = [](int) -> T * { return nullptr; };
-        auto noq = [](int, const T *&p, const T *&p2) { p = p2 = nullptr; };
         const bool fused = use_fused(ctx, nt);  // 2-D: FUSED2D_STEPS time steps per launch
         // a step count that is not a multiple of FUSED2D_STEPS: the bulk fused, the last 1-3 steps one per launch
         const int nfused = mixed_fused_steps(ctx, nt);
@@ -1430,11 +1490,7 @@ struct Impl {
                 return rc;
         } else if (save && K > 0) {
             for (int n0 = 0, seg = 0; n0 < nt; n0 += K, ++seg) {
-                T *sn = (T *)ctx->snap + (size_t)seg * 2 * g.ptot;  // (u^n0, u^{n0-1})
-                HIPCHK(ctx, hipMemcpyAsync(sn, sw.f[sw.cur], (size_t)g.ptot * sizeof(T), hipMemcpyDeviceToDevice, s));
-                HIPCHK(ctx, hipMemcpyAsync(sn + g.ptot, ctx->inc ? sw.v : sw.f[sw.cur ^ 1], (size_t)g.ptot * sizeof(T),
-                                           hipMemcpyDeviceToDevice, s));  // (u^n0, u^{n0-1}) or, increment form, (u^n0, v^n0)
-                if (ctx->cpml && (rc = pml_snapshot(ctx, seg, false, false))) return rc;
+                if ((rc = save_segment(ctx, sw, seg))) return rc;
                 const int cnt = std::min(K, nt - n0);
                 if (fused)
                     rc = run_fused(ctx, sw, spare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, &ctx->rec, series,
@@ -1448,14 +1504,13 @@ struct Impl {
             // one step per launch; q^{jS} goes to ring slot j % (B + 1), and every B samples (and behind the last, partial
             // batch) the analysis adds the batch to the accumulators
             const int ks = ctx->istride, B = ctx->four_batch, R = B + 1, N = (nt + ks - 1) / ks;
-            T *ring = (T *)ctx->four_ring;
-            auto qo = [&](int n) -> T * { return n % ks == 0 ? ring + (size_t)((n / ks) % R) * g.npts : nullptr; };
+            auto qo = [&](int n) -> T * { return n % ks == 0 ? st.ring_slot(n) : nullptr; };
             for (int j0 = 0; j0 < N; j0 += B) {
                 const int nb = std::min(B, N - j0), n0 = j0 * ks, n1 = std::min((int)nt, (j0 + nb) * ks);
                 if ((rc = run_steps(ctx, sw, n0, 1, n1 - n0, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1), qo,
                                     noq)))
                     return rc;
-                HIPCHK(ctx, launch_fourier_analyse<T>((T *)ctx->four_acc, ring, g.npts, R, j0 % R, j0, nb,
+                HIPCHK(ctx, launch_fourier_analyse<T>((T *)ctx->four_acc, st.ring, g.npts, R, j0 % R, j0, nb,
                                                       (const double *)ctx->four_tw, ctx->four_rows,
                                                       (int)ctx->four_freqs.size(), s));
             }
@@ -1465,9 +1520,7 @@ struct Impl {
                 return rc;
         } else {
             const int ks = ctx->istride;  // q^n is kept for n % ks == 0, in slot n / ks
-            auto qo = [&](int n) -> T * {  // (slot addresses in bytes: the store may hold bf16)
-                return (save && n % ks == 0) ? (T *)((char *)q_store + (size_t)(n / ks) * g.npts * ctx->qes) : nullptr;
-            };
+            auto qo = [&](int n) -> T * { return (save && n % ks == 0) ? (T *)st.slot(n) : nullptr; };
             if (nfused && (rc = run_fused(ctx, sw, spare, 0, 1, nfused, ctx->src, (const T *)ctx->wav, &ctx->rec, series,
                                           T(1), save ? 1 : 0, q_store)))
                 return rc;
@@ -1477,13 +1530,7 @@ struct Impl {
         }
         if ((rc = flush_record(ctx, sw, ctx->rec, series, T(1)))) return rc;
         if ((rc = loop.end())) return rc;
-        if (fused || nfused || npair) {  // the buffer pairs may have changed roles: keep ownership consistent
-            ctx->u[0] = sw.f[0];
-            ctx->u[1] = sw.f[1];
-            ctx->fx[0] = spare[0];
-            ctx->fx[1] = spare[1];
-            if (ctx->inc) ctx->vf = sw.v;
-        }
+        adopt(ctx, sw, spare);
         if ((rc = download_samples(ctx, (nrec && seis_out) ? seis_out : nullptr, ctx->series, nt, nrec, ctx->rec_sp,
                                    &ctx->pts_d, &ctx->cap_pts_d)))
             return rc;
@@ -1505,21 +1552,18 @@ struct Impl {
         const bool four = image && !ctx->four_freqs.empty();  // imaging against the Fourier store: one step per launch
         ctx->four_sweep = four;
         const T rs = (T)(1.0 / std::pow(ctx->cfg.h, g.ndim));
-        if ((rc = zero_fields(ctx, ctx->u[0], ctx->u[1]))) return rc;
         Sweep sw;
-        sw.f[0] = ctx->u[0];
-        sw.f[1] = ctx->u[1];
-        sw.v = ctx->vf;
-        if (ctx->inc) HIPCHK(ctx, hipMemsetAsync(ctx->vf, 0, (size_t)g.ptot * sizeof(T), ctx->stream));
-        if (ctx->cpml && (rc = pml_zero(ctx))) return rc;
+        if ((rc = start_sweep(ctx, sw))) return rc;
+        const Store st(ctx);
         T *q_store = (T *)ctx->q_store;
         T *series = (T *)ctx->series;
         const T *amp = (const T *)ctx->amp;
-        auto none = [](int) -> T * { return nullptr; };
-        auto noq = [](int, const T *&p, const T *&p2) { p = p2 = nullptr; };
         const bool fused = use_fused(ctx, nt);
         const int nfused = mixed_fused_steps(ctx, nt);
         void *spare[2] = {ctx->fx[0], ctx->fx[1]};
+        // checkpointed: the forward recomputation, which ping-pongs between its own two buffer pairs (fwd, fwx) when fused
+        Sweep fw = recompute_sweep(ctx);
+        void *fspare[2] = {ctx->fwx[0], ctx->fwx[1]};
         if ((fused || nfused) && (rc = zero_fields(ctx, spare[0], spare[1]))) return rc;
         if (four && (rc = fourier_table(ctx, nt, true))) return rc;
         TimeLoop loop(ctx);
@@ -1549,80 +1593,42 @@ struct Impl {
             }
         };
         bool imaged_all = false;  // the fused kernel pairs mu^{n+1} with q^n inside the launch (no lag)
-        if (fused && image && K > 0) {
-            // checkpointed, fused: recompute each segment's forward storing q into the slot buffer,
-            // then sweep the segment backwards imaging against those slots (no carry: nothing lags).
-            // The recomputation ping-pongs between its own two buffer pairs (fwd, fwx).
-            Sweep fw;
-            fw.f[0] = ctx->fwd[0];
-            fw.f[1] = ctx->fwd[1];
-            fw.v = ctx->fwv;
-            fw.pml_fw = true;
-            void *fspare[2] = {ctx->fwx[0], ctx->fwx[1]};
-            const int nseg = (nt + K - 1) / K;
-            for (int seg = nseg - 1; seg >= 0; --seg) {
-                const int n0 = seg * K, cnt = std::min(K, nt - n0);
-                const T *sn = (const T *)ctx->snap + (size_t)seg * 2 * g.ptot;
-                fw.cur = 0;
-                HIPCHK(ctx, hipMemcpyAsync(fw.f[0], sn, (size_t)g.ptot * sizeof(T), hipMemcpyDeviceToDevice, s));
-                HIPCHK(ctx, hipMemcpyAsync(ctx->inc ? fw.v : fw.f[1], sn + g.ptot, (size_t)g.ptot * sizeof(T),
-                                           hipMemcpyDeviceToDevice, s));
-                if (ctx->cpml && (rc = pml_snapshot(ctx, seg, true, true))) return rc;
-                T *qb = q_store - (size_t)n0 * g.npts;  // slot (n - n0) == qb + n * npts
-                if ((rc = run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr,
-                                    T(0), 1, qb)))
+        if (image && K > 0) {
+            // Checkpointed: per segment (last to first) restore the snapshot, recompute the forward steps storing q into the
+            // K-slot buffer, then take the adjoint steps of that segment against those slots.  Fused, nothing lags.  One
+            // step per launch, q^{n+1} at a segment's first adjoint step is the first q of the segment processed before,
+            // kept in the carry slot.
+            for (int seg = (nt + K - 1) / K - 1; seg >= 0; --seg) {
+                const int n0 = seg * K, cnt = std::min(K, nt - n0), hi = n0 + cnt - 1;
+                if ((rc = restore_segment(ctx, fw, seg))) return rc;
+                auto qo = [&](int n) -> T * { return st.seg_slot(n, n0); };
+                rc = fused ? run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), 1,
+                                       st.seg_slot(0, n0))
+                           : run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), qo, noq);
+                if (rc) return rc;
+                if ((rc = illum_accumulate(ctx, q_store, cnt))) return rc;  // slots 0 .. cnt - 1, before they are reused
+                if (fused) {
+                    if ((rc = run_fused(ctx, sw, spare, hi, -1, cnt, ctx->rec, amp, &ctx->src, series, rs, 2,
+                                        st.seg_slot(0, n0))))
+                        return rc;
+                    continue;
+                }
+                plan(hi, n0, [&](int n) -> const T * {
+                    if (n + 1 >= nt) return nullptr;
+                    return (n + 1 < n0 + cnt) ? st.seg_slot(n + 1, n0) : st.carry();
+                });
+                auto qi = [&](int n, const T *&p, const T *&p2) { p = pq[hi - n]; p2 = pq2[hi - n]; };
+                if ((rc = run_steps(ctx, sw, hi, -1, cnt, ctx->rec, amp, &ctx->src, series, rs, none, qi)))
                     return rc;
-                if ((rc = illum_accumulate(ctx, q_store, cnt))) return rc;  // this segment's slots, before they are reused
-                if ((rc = run_fused(ctx, sw, spare, n0 + cnt - 1, -1, cnt, ctx->rec, amp, &ctx->src, series, rs, 2,
-                                    qb)))
-                    return rc;
+                HIPCHK(ctx, hipMemcpyAsync(st.carry(), q_store, (size_t)g.npts * sizeof(T), hipMemcpyDeviceToDevice, s));
             }
-            ctx->fwd[0] = fw.f[0];
-            ctx->fwd[1] = fw.f[1];
-            ctx->fwx[0] = fspare[0];
-            ctx->fwx[1] = fspare[1];
-            if (ctx->inc) ctx->fwv = fw.v;
-            imaged_all = true;
+            imaged_all = fused;
+            q0 = st.carry();  // (one step per launch: the last pairing is still owed)
         } else if (fused) {
             if ((rc = run_fused(ctx, sw, spare, nt - 1, -1, nt, ctx->rec, amp, &ctx->src, series, rs, image ? 2 : 0,
                                 q_store)))
                 return rc;
             imaged_all = true;
-        } else if (image && K > 0) {
-            // Checkpointed: per segment (last to first) restore the snapshot, recompute the forward
-            // steps storing q into the K-slot buffer, then take the adjoint steps of that segment.
-            // At a segment's first adjoint step q^{n+1} is the first q of the segment processed
-            // before, kept in the carry slot.
-            T *carry = q_store + (size_t)K * g.npts;
-            const int nseg = (nt + K - 1) / K;
-            for (int seg = nseg - 1; seg >= 0; --seg) {
-                const int n0 = seg * K, cnt = std::min(K, nt - n0);
-                const T *sn = (const T *)ctx->snap + (size_t)seg * 2 * g.ptot;
-                HIPCHK(ctx, hipMemcpyAsync(ctx->fwd[0], sn, (size_t)g.ptot * sizeof(T), hipMemcpyDeviceToDevice, s));
-                HIPCHK(ctx, hipMemcpyAsync(ctx->inc ? ctx->fwv : ctx->fwd[1], sn + g.ptot, (size_t)g.ptot * sizeof(T),
-                                           hipMemcpyDeviceToDevice, s));
-                Sweep fw;
-                fw.f[0] = ctx->fwd[0];
-                fw.f[1] = ctx->fwd[1];
-                fw.v = ctx->fwv;
-                fw.pml_fw = true;
-                if (ctx->cpml && (rc = pml_snapshot(ctx, seg, true, true))) return rc;
-                auto qo = [&](int n) -> T * { return q_store + (size_t)(n - n0) * g.npts; };
-                if ((rc = run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), qo,
-                                    noq)))
-                    return rc;
-                if ((rc = illum_accumulate(ctx, q_store, cnt))) return rc;  // slots 0 .. cnt - 1 (not the carry)
-                const int hi = n0 + cnt - 1;
-                plan(hi, n0, [&](int n) -> const T * {
-                    if (n + 1 >= nt) return nullptr;
-                    return (n + 1 < n0 + cnt) ? q_store + (size_t)(n + 1 - n0) * g.npts : carry;
-                });
-                auto qi = [&](int n, const T *&p, const T *&p2) { p = pq[hi - n]; p2 = pq2[hi - n]; };
-                if ((rc = run_steps(ctx, sw, hi, -1, cnt, ctx->rec, amp, &ctx->src, series, rs, none, qi)))
-                    return rc;
-                HIPCHK(ctx, hipMemcpyAsync(carry, q_store, (size_t)g.npts * sizeof(T), hipMemcpyDeviceToDevice, s));
-            }
-            q0 = carry;
         } else if (four) {
             // Fourier store: batch by batch (last to first) the synthesis rebuilds the band-limited q~ of the batch's samples
             // in their ring slots, then the adjoint steps n = (j0 + nb) S - 1 .. j0 S of the batch run with the lagged
@@ -1631,33 +1637,30 @@ struct Impl {
             // pairing deferred across the boundary would need the second-lowest sample of the batch above, whose slot
             // this batch's synthesis has just taken.
             const int ks = ctx->istride, B = ctx->four_batch, R = B + 1, N = (nt + ks - 1) / ks;
-            T *ring = (T *)ctx->four_ring;
             for (int j0 = ((N - 1) / B) * B; j0 >= 0; j0 -= B) {
                 const int nb = std::min(B, N - j0), lo = j0 * ks, hi = std::min(nt, (j0 + nb) * ks) - 1;
-                HIPCHK(ctx, launch_fourier_synthesise<T>(ring, (const T *)ctx->four_acc, g.npts, R, j0 % R, j0, nb,
+                HIPCHK(ctx, launch_fourier_synthesise<T>(st.ring, (const T *)ctx->four_acc, g.npts, R, j0 % R, j0, nb,
                                                          (const double *)ctx->four_tw, ctx->four_rows,
                                                          (int)ctx->four_freqs.size(), s));
                 plan(hi, lo, [&](int n) -> const T * {
-                    return (n + 1 < nt && (n + 1) % ks == 0) ? ring + (size_t)(((n + 1) / ks) % R) * g.npts : nullptr;
+                    return (n + 1 < nt && (n + 1) % ks == 0) ? st.ring_slot(n + 1) : nullptr;
                 });
                 auto qi = [&](int n, const T *&p, const T *&p2) { p = pq[hi - n]; p2 = pq2[hi - n]; };
                 if ((rc = run_steps(ctx, sw, hi, -1, hi - lo + 1, ctx->rec, amp, &ctx->src, series, rs, none, qi)))
                     return rc;
             }
-            q0 = ring;  // sample 0: slot 0, written by the synthesis of the lowest batch
+            q0 = st.ring_slot(0);  // sample 0: slot 0, written by the synthesis of the lowest batch
         } else {
             // steps nt-1 .. nfused one per launch (all of them when nfused == 0), lagged pairing; the pairing owed
             // at the lower end, (mu^{nfused+1}, q^{nfused}), is the "last pairing" of that run
             const int ks = ctx->istride;
             plan(nt - 1, nfused, [&](int n) -> const T * {
-                return (image && n + 1 < nt && (n + 1) % ks == 0)
-                           ? (const T *)((const char *)q_store + (size_t)((n + 1) / ks) * g.npts * ctx->qes)
-                           : nullptr;
+                return (image && n + 1 < nt && (n + 1) % ks == 0) ? (const T *)st.slot(n + 1) : nullptr;
             });
             auto qi = [&](int n, const T *&p, const T *&p2) { p = pq[nt - 1 - n]; p2 = pq2[nt - 1 - n]; };
             if ((rc = run_steps(ctx, sw, nt - 1, -1, nt - nfused, ctx->rec, amp, &ctx->src, series, rs, none, qi)))
                 return rc;
-            q0 = (nfused % ks == 0) ? (const T *)((const char *)q_store + (size_t)(nfused / ks) * g.npts * ctx->qes) : nullptr;
+            q0 = (nfused % ks == 0) ? (const T *)st.slot(nfused) : nullptr;
             if (nfused) {
                 // ... then the first nfused steps, FUSED2D_STEPS per launch (pairing inside the launch, no lag)
                 if ((rc = flush_record(ctx, sw, ctx->src, series, rs))) return rc;
@@ -1670,13 +1673,8 @@ struct Impl {
                 imaged_all = true;
             }
         }
-        if (fused || nfused) {  // the buffer pairs may have changed roles: keep ownership consistent
-            ctx->u[0] = sw.f[0];
-            ctx->u[1] = sw.f[1];
-            ctx->fx[0] = spare[0];
-            ctx->fx[1] = spare[1];
-            if (ctx->inc) ctx->vf = sw.v;
-        }
+        adopt(ctx, sw, spare);
+        adopt_recompute(ctx, fw, fspare);
         if ((rc = flush_record(ctx, sw, ctx->src, series, rs))) return rc;
         if (image && !imaged_all)  // the last pairing: mu^1 with q^0
             HIPCHK(ctx, launch_image<T>(g, (const T *)sw.f[sw.cur], q0, (T *)ctx->g_acc, ctx->qbf16, s));
@@ -1745,16 +1743,10 @@ struct Impl {
         }
         ctx->have_syn = false;           // ctx->series is about to hold dd instead of the forward's synthetics
         ctx->have_dev_residual = false;  // ... and ctx->amp a copy of it, once the sweep has ended
-        if ((rc = zero_fields(ctx, ctx->u[0], ctx->u[1]))) return rc;
         Sweep sw;
-        sw.f[0] = ctx->u[0];
-        sw.f[1] = ctx->u[1];
-        sw.v = ctx->vf;
-        if (ctx->inc) HIPCHK(ctx, hipMemsetAsync(ctx->vf, 0, (size_t)g.ptot * sizeof(T), s));
-        if (ctx->cpml && (rc = pml_zero(ctx))) return rc;
+        if ((rc = start_sweep(ctx, sw))) return rc;
+        const Store st(ctx);
         T *series = (T *)ctx->series;
-        auto none = [](int) -> T * { return nullptr; };
-        auto noq = [](int, const T *&p, const T *&p2) { p = p2 = nullptr; };
         const int damp = base_args(ctx, 0).damp;
         // steps first .. first + cnt - 1 of the Born sweep; slot(n): what the store holds of step n (n % S == 0)
         auto born_steps = [&](int first, int cnt, auto slot) -> int {
@@ -1796,43 +1788,19 @@ struct Impl {
         TimeLoop loop(ctx);
         if ((rc = loop.begin())) return rc;
         if (K > 0) {
-            Sweep fw;
-            fw.f[0] = ctx->fwd[0];
-            fw.f[1] = ctx->fwd[1];
-            fw.v = ctx->fwv;
-            fw.pml_fw = true;
-            T *const qs = (T *)ctx->q_store;
+            Sweep fw = recompute_sweep(ctx);
             for (int n0 = 0, seg = 0; n0 < nt; n0 += K, ++seg) {
                 const int cnt = std::min(K, nt - n0);
-                const T *sn = (const T *)ctx->snap + (size_t)seg * 2 * g.ptot;
-                fw.cur = 0;
-                fw.prev_n = -1;
-                HIPCHK(ctx, hipMemcpyAsync(fw.f[0], sn, (size_t)g.ptot * sizeof(T), hipMemcpyDeviceToDevice, s));
-                HIPCHK(ctx, hipMemcpyAsync(ctx->inc ? fw.v : fw.f[1], sn + g.ptot, (size_t)g.ptot * sizeof(T),
-                                           hipMemcpyDeviceToDevice, s));
-                if (ctx->cpml && (rc = pml_snapshot(ctx, seg, true, true))) return rc;
-                if (fused2d) {
-                    rc = run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), 1,
-                                   qs - (size_t)n0 * g.npts);  // slot (n - n0)
-                } else {
-                    auto qo = [&](int n) -> T * { return qs + (size_t)(n - n0) * g.npts; };
-                    rc = run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), qo, noq);
-                }
-                if (rc) return rc;
-                if ((rc = born_steps(n0, cnt, [&](int n) -> const void * { return qs + (size_t)(n - n0) * g.npts; })))
-                    return rc;
+                if ((rc = restore_segment(ctx, fw, seg))) return rc;
+                auto qo = [&](int n) -> T * { return st.seg_slot(n, n0); };
+                rc = fused2d ? run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), 1,
+                                         st.seg_slot(0, n0))
+                             : run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), qo, noq);
+                if (rc || (rc = born_steps(n0, cnt, [&](int n) -> const void * { return st.seg_slot(n, n0); }))) return rc;
             }
-            if (fused2d) {  // the recomputation's buffer pairs may have changed roles: keep ownership consistent
-                ctx->fwd[0] = fw.f[0];
-                ctx->fwd[1] = fw.f[1];
-                ctx->fwx[0] = fspare[0];
-                ctx->fwx[1] = fspare[1];
-                if (ctx->inc) ctx->fwv = fw.v;
-            }
+            adopt_recompute(ctx, fw, fspare);
         } else {
-            const char *const qs = (const char *)ctx->q_store;  // (slot addresses in bytes: the store may hold bf16)
-            const size_t slot_bytes = (size_t)g.npts * ctx->qes;
-            if ((rc = born_steps(0, nt, [&](int n) -> const void * { return qs + (size_t)(n / S) * slot_bytes; }))) return rc;
+            if ((rc = born_steps(0, nt, [&](int n) -> const void * { return st.slot(n); }))) return rc;
         }
         if ((rc = flush_record(ctx, sw, ctx->rec, series, T(1)))) return rc;
         if ((rc = loop.end())) return rc;
@@ -2943,14 +2911,7 @@ static int set_spread(fwi_ctx *ctx, fwi_ctx::SpreadSet &sp, int32_t npts, int32_
         for (int m = a; m < b; ++m) owner[m] = p;
     }
     const size_t need = (size_t)std::max(nnodes, npts + 1) * 8 + 16;
-    if (sp.cap < need) {
-        for (void **q : {&sp.pt_start, &sp.owner, &sp.weight}) {
-            if (*q) HIPCHK(ctx, hipFree(*q));
-            *q = nullptr;
-            HIPCHK(ctx, hipMalloc(q, need));
-        }
-        sp.cap = need;
-    }
+    if (int rc = ensure_all(ctx, {&sp.pt_start, &sp.owner, &sp.weight}, &sp.cap, need)) return rc;
     HIPCHK(ctx, hipMemcpyAsync(sp.pt_start, pt_start, (size_t)(npts + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(sp.owner, owner.data(), (size_t)nnodes * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(sp.weight, weight, (size_t)nnodes * ctx->esize, hipMemcpyHostToDevice, ctx->stream));
