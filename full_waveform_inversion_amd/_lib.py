@@ -110,6 +110,13 @@ SIGNATURES = {
     "fwi_set_fourier_store": (C.c_int, [_P, _I32, _P, _I32]),
     "fwi_fourier_spectrum": (C.c_int, [_P, _I32, _P, _P]),
     "fwi_store_bytes": (C.c_int, [_P, C.POINTER(_I64)]),
+    "fwi_adjoint_spectral": (C.c_int, [_P, _P, _P]),
+    "fwi_fourier_image": (C.c_int, [_P, _P]),
+    "fwi_fourier_gradient": (C.c_int, [_P, _I32, _P, _P]),
+    "fwi_fourier_gradient_vec": (C.c_int, [_P, _I32, _P, _I32]),
+    "fwi_fourier_adjoint_spectrum": (C.c_int, [_P, _I32, _P, _P]),
+    "fwi_fourier_illumination": (C.c_int, [_P, _I32, _P, _P]),
+    "fwi_fourier_illumination_vec": (C.c_int, [_P, _I32, _P, _I32]),
     "fwi_vec_mul": (C.c_int, [_P, _I32, _I32]),
     "fwi_vec_recip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_vec_smooth": (C.c_int, [_P, _I32, C.POINTER(_D)]),

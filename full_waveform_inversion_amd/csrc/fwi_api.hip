@@ -30,6 +30,7 @@
 #include "fwi_envelope.h"
 #include "fwi_gather_tile.h"
 #include "fwi_fourier.h"
+#include "fwi_fimage.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
 #include "fwi_match.h"
@@ -148,6 +149,12 @@ struct fwi_ctx {
     int four_rows = 0;        // rows per frequency of four_tw: ceil(nt_max / istride) + FOURIER_BMAX - 1
     bool four_sweep = false;  // the running sweep goes through the Fourier store: one step per launch
     std::vector<double> four_tw_host;
+    // Spectral imaging (fwi_adjoint_spectral; fwi_fimage.hip): 2 F compact accumulator volumes (Re M_k, Im M_k) of the
+    // adjoint field, allocated by the first fwi_adjoint_spectral; have_m: they hold the M_k that go with the Q_k of the
+    // latest forward(save).  four_w: the F weights a_k w_k of the running image / illumination pass on the device.
+    void *four_adj = nullptr, *four_w = nullptr;
+    bool have_m = false;
+    std::vector<double> four_w_host;
     size_t store_held = 0;    // device bytes held for the forward store of whichever kind (fwi_store_bytes)
     // Born modelling (fwi_born): w = dC / C of the last perturbation, compact; allocated by the first fwi_born call
     void *born_w = nullptr;
@@ -1459,6 +1466,7 @@ struct Impl {
         ctx->nrec = nrec;
         ctx->have_forward = false;
         ctx->have_q = false;
+        ctx->have_m = false;
         ctx->have_syn = false;
         ctx->have_dev_residual = false;
         hipStream_t s = ctx->stream;
@@ -1540,7 +1548,23 @@ struct Impl {
         return FWI_OK;
     }
 
-    static int adjoint(fwi_ctx *ctx, const T *residual, int32_t image, T *adj_src_out) {
+    // Spectral imaging: the 2 F accumulators of the adjoint field, all or nothing, by the first fwi_adjoint_spectral
+    static int fourier_adjoint_alloc(fwi_ctx *ctx) {
+        if (ctx->four_adj) return FWI_OK;
+        const size_t F = ctx->four_freqs.size(), bytes = 2 * F * (size_t)ctx->gd.npts * sizeof(T);
+        size_t total, fr;
+        if (int rc = alloc_all(ctx, {{&ctx->four_adj, bytes, true}}, &total, &fr))
+            return rc != FWI_ENOMEM ? rc : ctx->fail(FWI_ENOMEM,
+                             "fwi_adjoint_spectral: the adjoint accumulators need %.1f GiB (%d frequencies) but only "
+                             "%.1f GiB are free; fewer frequencies need less",
+                             total / 1073741824.0, (int)F, fr / 1073741824.0);
+        ctx->store_held += bytes;
+        return FWI_OK;
+    }
+
+    // `spectral` (fwi_adjoint_spectral; image = 0 then): the sweep of image = 0 one step per launch, with the Fourier
+    // analysis of the adjoint field at the imaging samples riding behind it.  g_acc is not touched.
+    static int adjoint(fwi_ctx *ctx, const T *residual, int32_t image, T *adj_src_out, bool spectral = false) {
         const GridDesc &g = ctx->gd;
         const int nt = ctx->nt, K = ctx->ckpt;
         hipStream_t s = ctx->stream;
@@ -1550,7 +1574,8 @@ struct Impl {
         ctx->have_dev_residual = false;  // consumed: ctx->series is about to be overwritten
         ctx->have_syn = false;           // ... by this sweep's source-side series (fwi_misfit_l2 must not read them)
         const bool four = image && !ctx->four_freqs.empty();  // imaging against the Fourier store: one step per launch
-        ctx->four_sweep = four;
+        ctx->four_sweep = four || spectral;
+        if (spectral && (rc = fourier_adjoint_alloc(ctx))) return rc;
         const T rs = (T)(1.0 / std::pow(ctx->cfg.h, g.ndim));
         Sweep sw;
         if ((rc = start_sweep(ctx, sw))) return rc;
@@ -1566,6 +1591,11 @@ struct Impl {
         void *fspare[2] = {ctx->fwx[0], ctx->fwx[1]};
         if ((fused || nfused) && (rc = zero_fields(ctx, spare[0], spare[1]))) return rc;
         if (four && (rc = fourier_table(ctx, nt, true))) return rc;
+        if (spectral) {
+            ctx->have_m = false;
+            if ((rc = fourier_table(ctx, nt, false))) return rc;
+            HIPCHK(ctx, hipMemsetAsync(ctx->four_adj, 0, 2 * ctx->four_freqs.size() * (size_t)g.npts * sizeof(T), s));
+        }
         TimeLoop loop(ctx);
         if ((rc = loop.begin())) return rc;
         const T *q0 = nullptr;  // q^0, for the last pairing (mu^1 with q^0)
@@ -1650,6 +1680,24 @@ struct Impl {
                     return rc;
             }
             q0 = st.ring_slot(0);  // sample 0: slot 0, written by the synthesis of the lowest batch
+        } else if (spectral) {
+            // Spectral imaging: batch by batch (last to first) the adjoint steps n = (j0 + nb) S - 1 .. j0 S run without
+            // imaging; behind every sampled step n = j S the field it has just written, mu^{jS+1} (what the imaging
+            // condition pairs with q^{jS}), is packed into ring slot j % (B + 1), which the forward sweep no longer needs,
+            // and behind the lowest sample of the batch the analysis adds the batch to the adjoint accumulators
+            const int ks = ctx->istride, B = ctx->four_batch, R = B + 1, N = (nt + ks - 1) / ks;
+            for (int j0 = ((N - 1) / B) * B; j0 >= 0; j0 -= B) {
+                const int nb = std::min(B, N - j0);
+                for (int j = j0 + nb - 1; j >= j0; --j) {
+                    const int hi = std::min(nt, (j + 1) * ks) - 1, lo = j * ks;
+                    if ((rc = run_steps(ctx, sw, hi, -1, hi - lo + 1, ctx->rec, amp, &ctx->src, series, rs, none, noq)))
+                        return rc;
+                    HIPCHK(ctx, launch_fimage_pack<T>(g, (const T *)sw.f[sw.cur], st.ring_slot(lo), s));
+                }
+                HIPCHK(ctx, launch_fourier_analyse<T>((T *)ctx->four_adj, st.ring, g.npts, R, j0 % R, j0, nb,
+                                                      (const double *)ctx->four_tw, ctx->four_rows,
+                                                      (int)ctx->four_freqs.size(), s));
+            }
         } else {
             // steps nt-1 .. nfused one per launch (all of them when nfused == 0), lagged pairing; the pairing owed
             // at the lower end, (mu^{nfused+1}, q^{nfused}), is the "last pairing" of that run
@@ -1693,8 +1741,67 @@ struct Impl {
                                                      ctx->nsrc, ctx->istride, s));
         }
         if ((rc = loop.end())) return rc;
-        return download_samples(ctx, (adj_src_out && ctx->nsrc) ? adj_src_out : nullptr, ctx->series, nt, ctx->nsrc,
-                                ctx->src_sp, nullptr, nullptr);
+        if ((rc = download_samples(ctx, (adj_src_out && ctx->nsrc) ? adj_src_out : nullptr, ctx->series, nt, ctx->nsrc,
+                                   ctx->src_sp, nullptr, nullptr)))
+            return rc;
+        ctx->have_m = spectral || ctx->have_m;
+        return FWI_OK;
+    }
+
+    // The weights a_k w_k of one image / illumination pass on the device (w_k as fourier_table's synthesis weights, for
+    // the N samples of the last forward); `fw` = nullptr: a_k = 1
+    static int fourier_weights(fwi_ctx *ctx, const double *fw) {
+        const int S = ctx->istride, N = (ctx->nt + S - 1) / S, F = (int)ctx->four_freqs.size();
+        const double sdt = (double)S * ctx->cfg.dt;
+        if (!ctx->four_w) HIPCHK(ctx, hipMalloc(&ctx->four_w, FWI_FOURIER_FMAX * sizeof(double)));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the upload of the pass before may still read the host copy
+        std::vector<double> &a = ctx->four_w_host;
+        a.assign(F, 0.0);
+        for (int k = 0; k < F; ++k) {
+            const double f = ctx->four_freqs[k];
+            const bool edge = f == 0.0 || std::fabs(2.0 * f * sdt - 1.0) <= FOURIER_NYQUIST_RTOL;
+            a[k] = (fw ? fw[k] : 1.0) * ((edge ? 1.0 : 2.0) / N);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->four_w, a.data(), F * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        return FWI_OK;
+    }
+
+    // dst = beta dst + sum_k a_k w_k Re(Q_k conj M_k) (`illum`: |Q_k|^2) in the units of g_acc
+    static int fourier_sum(fwi_ctx *ctx, const double *fw, bool illum, void *dst, int beta) {
+        int rc = fourier_weights(ctx, fw);
+        if (rc) return rc;
+        const int F = (int)ctx->four_freqs.size();
+        if (illum)
+            HIPCHK(ctx, launch_fimage_illuminate<T>((T *)dst, (const T *)ctx->four_acc, (const double *)ctx->four_w,
+                                                    ctx->gd.npts, F, beta, ctx->stream));
+        else
+            HIPCHK(ctx, launch_fimage_image<T>((T *)dst, (const T *)ctx->four_acc, (const T *)ctx->four_adj,
+                                               (const double *)ctx->four_w, ctx->gd.npts, F, beta, ctx->stream));
+        return FWI_OK;
+    }
+
+    static int fourier_image(fwi_ctx *ctx, const double *fw) {
+        int rc = fourier_sum(ctx, fw, false, ctx->g_acc, 1);
+        if (rc) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return FWI_OK;
+    }
+
+    // the gradient (`illum`: the illumination) of that sum alone into the compact device array `dev`, which is
+    // ctx->g_out and goes on to the host array `out`, or a vector slot (out = nullptr)
+    static int fourier_finalize(fwi_ctx *ctx, int32_t wrt, const double *fw, bool illum, void *dev, T *out) {
+        int rc = fourier_sum(ctx, fw, illum, dev, 0);
+        if (rc) return rc;
+        const double dt2 = ctx->cfg.dt * ctx->cfg.dt, S = (double)ctx->istride;
+        if (illum)
+            HIPCHK(ctx, launch_illum_finalize<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, S / (dt2 * dt2),
+                                                 wrt == FWI_WRT_VELOCITY, ctx->stream));
+        else
+            HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2,
+                                                    wrt == FWI_WRT_VELOCITY, ctx->stream));
+        if (out && (rc = download_compact(ctx, out, dev))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return FWI_OK;
     }
 
     // Born modelling dd = J dm (include/fwi.h, fwi_born / fwi_born_imaging).  dm comes from the host (`dm_host`) or from a
@@ -2815,7 +2922,8 @@ void fwi_destroy(fwi_ctx *ctx) {
         void *p;
     } fields[] = {{"u", ctx->u[0]}, {"u", ctx->u[1]}, {"C", ctx->C}, {"c_dev", ctx->c_dev}, {"dz", ctx->dz}, {"dy", ctx->dy},
                   {"dx", ctx->dx}, {"q_store", ctx->q_store}, {"four_acc", ctx->four_acc}, {"four_ring", ctx->four_ring},
-                  {"four_tw", ctx->four_tw}, {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc}, {"born_w", ctx->born_w},
+                  {"four_tw", ctx->four_tw}, {"four_adj", ctx->four_adj}, {"four_w", ctx->four_w},
+                  {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc}, {"born_w", ctx->born_w},
                   {"g_out", ctx->g_out}, {"red", ctx->red}, {"amp", ctx->amp}, {"series", ctx->series}, {"wav", ctx->wav},
                   {"snap", ctx->snap}, {"fwd", ctx->fwd[0]}, {"fwd", ctx->fwd[1]}, {"fx", ctx->fx[0]}, {"fx", ctx->fx[1]},
                   {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
@@ -3460,9 +3568,9 @@ int fwi_set_illumination(fwi_ctx *ctx, int32_t on) {
 
 // Frees the arrays of the Fourier store; the context is back on its configured store.
 static int fourier_release(fwi_ctx *ctx) {
-    if (ctx->four_acc || ctx->four_ring || ctx->four_tw)
+    if (ctx->four_acc || ctx->four_ring || ctx->four_tw || ctx->four_adj || ctx->four_w)
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // no sweep still uses them
-    for (void **p : {&ctx->four_acc, &ctx->four_ring, &ctx->four_tw}) {
+    for (void **p : {&ctx->four_acc, &ctx->four_ring, &ctx->four_tw, &ctx->four_adj, &ctx->four_w}) {
         void *q = *p;
         *p = nullptr;
         if (q) HIPCHK(ctx, hipFree(q));
@@ -3474,6 +3582,7 @@ static int fourier_release(fwi_ctx *ctx) {
     ctx->four_freqs.clear();
     ctx->four_batch = ctx->four_rows = 0;
     ctx->four_sweep = false;
+    ctx->have_m = false;
     return FWI_OK;
 }
 
@@ -3534,6 +3643,107 @@ int fwi_fourier_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out) {
         return ctx->fail(FWI_ESTATE, "fwi_fourier_spectrum: needs fwi_forward(save=1) on this context first");
     (void)hipSetDevice(ctx->cfg.device);
     const char *re = (const char *)ctx->four_acc + (size_t)2 * k * ctx->gd.npts * ctx->esize;
+    const char *im = re + (size_t)ctx->gd.npts * ctx->esize;
+    for (int c = 0; c < 2; ++c) {  // (one staging array: the first copy leaves it before the second repack)
+        if (int rc = DISPATCH(ctx, Impl<float>::download_compact(ctx, c ? im_out : re_out, c ? im : re),
+                              Impl<double>::download_compact(ctx, c ? im_out : re_out, c ? im : re)))
+            return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return FWI_OK;
+}
+
+// What the entry points of spectral imaging begin with: a Fourier context that holds the Q_k of a forward(save) and, with
+// `need_m`, the M_k of an fwi_adjoint_spectral that followed it.
+static int fourier_callable(fwi_ctx *ctx, const char *who, bool need_m) {
+    if (ctx->four_freqs.empty())
+        return ctx->fail(FWI_ESTATE, "%s: the Fourier store is off (fwi_set_fourier_store)", who);
+    if (!ctx->have_forward || !ctx->have_q || !ctx->four_acc)
+        return ctx->fail(FWI_ESTATE, "%s: needs fwi_forward(save=1) on this context first", who);
+    if (need_m && (!ctx->have_m || !ctx->four_adj))
+        return ctx->fail(FWI_ESTATE, "%s: needs an fwi_adjoint_spectral after the latest fwi_forward(save=1)", who);
+    return FWI_OK;
+}
+
+// the F weights of the caller (nullptr: ones): finite, and with `nonneg` >= 0
+static int fourier_weight_args(fwi_ctx *ctx, const char *who, const double *fw, bool nonneg) {
+    if (!fw) return FWI_OK;
+    for (int k = 0; k < (int)ctx->four_freqs.size(); ++k) {
+        if (!std::isfinite(fw[k])) return ctx->fail(FWI_EINVAL, "%s: freq_weights[%d] is not finite", who, k);
+        if (nonneg && fw[k] < 0.0) return ctx->fail(FWI_EINVAL, "%s: freq_weights[%d]=%g is negative", who, k, fw[k]);
+    }
+    return FWI_OK;
+}
+
+static int wrt_and_model(fwi_ctx *ctx, const char *who, int32_t wrt) {
+    if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
+        return ctx->fail(FWI_EINVAL, "%s: unknown parametrisation %d", who, (int)wrt);
+    if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "%s: no model set", who);
+    return FWI_OK;
+}
+
+int fwi_adjoint_spectral(fwi_ctx *ctx, const void *residual, void *adj_src_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (int rc = fourier_callable(ctx, "fwi_adjoint_spectral", false)) return rc;
+    if (ctx->nrec && !residual && !ctx->have_dev_residual)
+        return ctx->fail(FWI_EINVAL, "fwi_adjoint_spectral: null residual (and no fwi_misfit_l2 residual on the device)");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, Impl<float>::adjoint(ctx, (const float *)residual, 0, (float *)adj_src_out, true),
+                    Impl<double>::adjoint(ctx, (const double *)residual, 0, (double *)adj_src_out, true));
+}
+
+int fwi_fourier_image(fwi_ctx *ctx, const double *freq_weights) {
+    if (!ctx) return FWI_EINVAL;
+    if (int rc = fourier_callable(ctx, "fwi_fourier_image", true)) return rc;
+    if (int rc = fourier_weight_args(ctx, "fwi_fourier_image", freq_weights, false)) return rc;
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH_CALL(ctx, fourier_image, freq_weights);
+}
+
+// `illum`: fwi_fourier_illumination[_vec], else fwi_fourier_gradient[_vec]; `out`: the host array, nullptr for `dev`
+static int fourier_finalize(fwi_ctx *ctx, const char *who, bool illum, int32_t wrt, const double *fw, void *dev,
+                            void *out) {
+    if (int rc = fourier_callable(ctx, who, !illum)) return rc;
+    if (int rc = fourier_weight_args(ctx, who, fw, illum)) return rc;
+    if (int rc = wrt_and_model(ctx, who, wrt)) return rc;
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, Impl<float>::fourier_finalize(ctx, wrt, fw, illum, dev, (float *)out),
+                    Impl<double>::fourier_finalize(ctx, wrt, fw, illum, dev, (double *)out));
+}
+
+int fwi_fourier_gradient(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, void *out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_gradient: null output");
+    return fourier_finalize(ctx, "fwi_fourier_gradient", false, wrt, freq_weights, ctx->g_out, out);
+}
+
+int fwi_fourier_gradient_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, int32_t slot) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, v, slot);
+    return fourier_finalize(ctx, "fwi_fourier_gradient_vec", false, wrt, freq_weights, v, nullptr);
+}
+
+int fwi_fourier_illumination(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, void *out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_illumination: null output");
+    return fourier_finalize(ctx, "fwi_fourier_illumination", true, wrt, freq_weights, ctx->g_out, out);
+}
+
+int fwi_fourier_illumination_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, int32_t slot) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, v, slot);
+    return fourier_finalize(ctx, "fwi_fourier_illumination_vec", true, wrt, freq_weights, v, nullptr);
+}
+
+int fwi_fourier_adjoint_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (int rc = fourier_callable(ctx, "fwi_fourier_adjoint_spectrum", true)) return rc;
+    if (k < 0 || k >= (int)ctx->four_freqs.size())
+        return ctx->fail(FWI_EINVAL, "fwi_fourier_adjoint_spectrum: frequency index %d outside [0, %d)", (int)k,
+                         (int)ctx->four_freqs.size());
+    if (!re_out || !im_out) return ctx->fail(FWI_EINVAL, "fwi_fourier_adjoint_spectrum: null output");
+    (void)hipSetDevice(ctx->cfg.device);
+    const char *re = (const char *)ctx->four_adj + (size_t)2 * k * ctx->gd.npts * ctx->esize;
     const char *im = re + (size_t)ctx->gd.npts * ctx->esize;
     for (int c = 0; c < 2; ++c) {  // (one staging array: the first copy leaves it before the second repack)
         if (int rc = DISPATCH(ctx, Impl<float>::download_compact(ctx, c ? im_out : re_out, c ? im : re),

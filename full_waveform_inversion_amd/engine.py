@@ -521,6 +521,94 @@ class Engine:
             out[k] = re + 1j * im
         return out
 
+    # -- spectral imaging on the Fourier store (include/fwi.h fwi_adjoint_spectral) -------------------------------
+    def _freq_weights(self, freq_weights):
+        """(pointer, array) of the ``F`` weights per frequency, (None, None) without any (or without a store: the call
+        that follows refuses)"""
+        if freq_weights is None or self._fourier is None:
+            return None, None
+        fw = np.ascontiguousarray(freq_weights, dtype=np.float64)
+        if fw.shape != self._fourier.shape:
+            raise ValueError("freq_weights must hold one weight per frequency, shape (%d,)" % self._fourier.size)
+        return fw.ctypes.data_as(C.c_void_p), fw
+
+    def adjoint_spectral(self, residual=None, freq_weights=None, image=True):
+        """:meth:`adjoint` of a Fourier-store engine with the imaging done in the frequency domain: the sweep of
+        ``adjoint(residual, image=False)`` (the same ``F^T residual``, bit for bit) with the Fourier coefficients ``M_k`` of
+        the adjoint field accumulated behind it (``fwi_adjoint_spectral``), then, with ``image``, the gradient accumulator
+        ``+= sum_k a_k w_k Re(Q_k conj M_k)`` with ``a = freq_weights`` (None: 1; ``fwi_fourier_image``).  With unit
+        weights that is what ``adjoint(residual)`` adds on this engine, to round-off.  The per-frequency terms stay
+        readable: :meth:`fourier_gradient`, :meth:`fourier_gradients`, :meth:`fourier_adjoint_spectrum`."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        rp = None
+        if residual is not None:
+            residual = self._host(residual, (self._nt, self._nrec))
+            rp = residual.ctypes.data_as(C.c_void_p)
+        out = np.zeros((self._nt, self._nsrc), self.dtype)
+        self._chk(self._lib.fwi_adjoint_spectral(self._c, rp, out.ctypes.data_as(C.c_void_p)))
+        if image:
+            self._chk(self._lib.fwi_fourier_image(self._c, fwp))
+        return out
+
+    def fourier_image(self, freq_weights=None):
+        """Gradient accumulator ``+= sum_k a_k w_k Re(Q_k conj M_k)`` of the last :meth:`adjoint_spectral`
+        (``fwi_fourier_image``): what ``adjoint_spectral(image=True)`` ends with, for a sweep run with ``image=False``."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        self._chk(self._lib.fwi_fourier_image(self._c, fwp))
+
+    def fourier_gradient(self, freq_weights=None, wrt="velocity"):
+        """``sum_k a_k g_k`` of the last :meth:`adjoint_spectral`, model-shaped: the gradient :meth:`gradient` would return
+        if the accumulator held that shot's spectral image alone (``fwi_fourier_gradient``).  The accumulator is not
+        touched."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        g = np.zeros(self.shape, self.dtype)
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        self._chk(self._lib.fwi_fourier_gradient(self._c, w, fwp, g.ctypes.data_as(C.c_void_p)))
+        return g
+
+    def fourier_gradient_vec(self, slot, freq_weights=None, wrt="velocity"):
+        """Vector ``slot`` := :meth:`fourier_gradient` on the device."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        self._chk(self._lib.fwi_fourier_gradient_vec(self._c, w, fwp, slot))
+
+    def fourier_gradients(self, wrt="velocity"):
+        """Every per-frequency gradient ``g_k`` of the last :meth:`adjoint_spectral` as ``(F, *shape)``."""
+        if self._fourier is None:
+            raise _lib.FwiError(3, "fourier_gradients: the Fourier store is off (set_fourier_store)")
+        eye = np.eye(self._fourier.size)
+        return np.stack([self.fourier_gradient(eye[k], wrt) for k in range(self._fourier.size)])
+
+    def fourier_adjoint_spectrum(self):
+        """``M_k`` of the last :meth:`adjoint_spectral` as a complex ``(F, *shape)`` array: the monochromatic adjoint
+        fields ``sum_j mu^{jS+1} exp(-i 2 pi f_k j S dt)`` (``fwi_fourier_adjoint_spectrum``)."""
+        if self._fourier is None:
+            raise _lib.FwiError(3, "fourier_adjoint_spectrum: the Fourier store is off (set_fourier_store)")
+        out = np.zeros((self._fourier.size,) + self.shape, np.complex64 if self.dtype == np.float32 else np.complex128)
+        re, im = np.zeros(self.shape, self.dtype), np.zeros(self.shape, self.dtype)
+        for k in range(self._fourier.size):
+            self._chk(self._lib.fwi_fourier_adjoint_spectrum(self._c, k, re.ctypes.data_as(C.c_void_p),
+                                                             im.ctypes.data_as(C.c_void_p)))
+            out[k] = re + 1j * im
+        return out
+
+    def fourier_illumination(self, freq_weights=None, wrt="velocity"):
+        """``(S / dt^4) sum_k a_k w_k |Q_k|^2`` of the last ``forward(save=True)`` (times ``(2 / c^3)^2`` for
+        ``wrt="velocity"``), in the units of :meth:`illumination` (``fwi_fourier_illumination``); ``a = freq_weights >= 0``
+        (None: 1).  On bin frequencies this is the illumination of the band-limited forward term, with all bins that of
+        the term itself; off the bins it is this formula.  One shot's; the caller sums over shots."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        h = np.zeros(self.shape, self.dtype)
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        self._chk(self._lib.fwi_fourier_illumination(self._c, w, fwp, h.ctypes.data_as(C.c_void_p)))
+        return h
+
+    def fourier_illumination_vec(self, slot, freq_weights=None, wrt="velocity"):
+        """Vector ``slot`` := :meth:`fourier_illumination` on the device."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        self._chk(self._lib.fwi_fourier_illumination_vec(self._c, w, fwp, slot))
+
     def store_bytes(self):
         """Device bytes held for the forward store of whichever kind (``fwi_store_bytes``); 0 before the first
         ``forward(save=True)`` allocates it."""

@@ -70,12 +70,12 @@ def weights(nt, stride, dt, freqs):
     return np.where(edge, 1.0, 2.0) / N
 
 
-def analyse(samples, nt, stride, dt, freqs, dtype=np.float64, batch=None):
+def analyse(samples, nt, stride, dt, freqs, dtype=np.float64, batch=None, reverse=False):
     """``Q_k`` as a complex ``(F, ...)`` array from the samples ``q^{jS}``, ``(N, ...)``.
 
     ``dtype`` and ``batch`` restate the device's arithmetic: the samples and the accumulators are held in ``dtype``, the
     sums over a batch of ``batch`` samples (None: all at once) are taken in fp64 and added to the accumulators once per
-    batch."""
+    batch.  ``reverse``: the same batches, the last one first (the order of a reverse sweep)."""
     th = phases(nt, stride, dt, freqs)
     F, N = th.shape
     dtype = np.dtype(dtype)
@@ -86,7 +86,7 @@ def analyse(samples, nt, stride, dt, freqs, dtype=np.float64, batch=None):
     B = N if batch is None else max(1, int(batch))
     re = np.zeros((F,) + q.shape[1:], dtype)
     im = np.zeros((F,) + q.shape[1:], dtype)
-    for j0 in range(0, N, B):
+    for j0 in (range(0, N, B)[::-1] if reverse else range(0, N, B)):
         sl = slice(j0, min(N, j0 + B))
         re = (re.astype(np.float64) + np.tensordot(np.cos(th[:, sl]), q[sl], axes=1)).astype(dtype)
         im = (im.astype(np.float64) - np.tensordot(np.sin(th[:, sl]), q[sl], axes=1)).astype(dtype)
@@ -117,3 +117,61 @@ def project(q_history, nt, stride, dt, freqs, dtype=np.float64, batch=None):
     out = np.zeros(q.shape, np.dtype(dtype))
     out[::S] = synthesise(Q, nt, S, dt, freqs, dtype)
     return out
+
+
+# -- spectral imaging (fwi_adjoint_spectral, fwi_fourier_image, fwi_fourier_illumination; csrc/fwi_fimage.hip) ----------
+#
+# With ``M_k`` the analysis of the adjoint field at the imaging samples, ``mu^{jS+1}`` (what the imaging condition pairs
+# with ``q^{jS}``), the band-limited imaging sum is a sum over frequencies, for ANY set of them::
+#
+#     sum_j mu^{jS+1} q~^{jS} = sum_k w_k Re(Q_k conj M_k) = sum_k w_k (Re Q_k Re M_k + Im Q_k Im M_k)
+#
+# (insert the synthesis and exchange the sums).  On bin frequencies Parseval also gives ``sum_j (q~^{jS})^2 = sum_k w_k
+# |Q_k|^2``, the illumination of the band-limited term; off the bins that identity does NOT hold and
+# :func:`spectral_illumination` is a definition.
+
+def adjoint_spectrum(mu_samples, nt, stride, dt, freqs, dtype=np.float64, batch=None):
+    """``M_k`` as a complex ``(F, ...)`` array from the samples ``mu^{jS+1}``, ``(N, ...)``: :func:`analyse`, its batches
+    in the order of the reverse sweep."""
+    return analyse(mu_samples, nt, stride, dt, freqs, dtype, batch, reverse=True)
+
+
+def _weighted(Q, nt, stride, dt, freqs, freq_weights):
+    a = weights(nt, stride, dt, freqs)
+    Q = np.asarray(Q)
+    if Q.shape[0] != a.size:
+        raise ValueError("expected one coefficient array per frequency")
+    if freq_weights is not None:
+        fw = np.asarray(freq_weights, np.float64)
+        if fw.shape != a.shape:
+            raise ValueError("freq_weights must hold one weight per frequency, shape (%d,)" % a.size)
+        a = fw * a
+    return a, Q
+
+
+def spectral_image(Q, M, nt, stride, dt, freqs, freq_weights=None, dtype=np.float64):
+    """``sum_k a_k w_k Re(Q_k conj M_k)`` in the units of the imaging sum ``sum_j mu^{jS+1} q^{jS}`` (times
+    ``-S / dt^2`` it is the gradient w.r.t. ``1 / c^2``); ``a = freq_weights`` (None: 1).  ``dtype`` restates the
+    device's arithmetic: the coefficients are held in ``dtype``, the sum runs in fp64 with k ascending and is rounded to
+    ``dtype`` once."""
+    a, Q = _weighted(Q, nt, stride, dt, freqs, freq_weights)
+    M = np.asarray(M)
+    dtype = np.dtype(dtype)
+    part = lambda z: z.astype(dtype).astype(np.float64)  # noqa: E731
+    s = np.zeros(Q.shape[1:], np.float64)
+    for k in range(a.size):
+        s = s + a[k] * (part(Q[k].real) * part(M[k].real) + part(Q[k].imag) * part(M[k].imag))
+    return s.astype(dtype)
+
+
+def spectral_illumination(Q, nt, stride, dt, freqs, freq_weights=None, dtype=np.float64):
+    """``sum_k a_k w_k |Q_k|^2`` in the units of ``sum_j (q^{jS})^2`` (times ``S / dt^4`` it is
+    ``Engine.fourier_illumination(wrt="slowness2")``).  On bin frequencies, with unit ``a``, this equals
+    ``sum_j (q~^{jS})^2``; off the bins it does not.  ``dtype`` as in :func:`spectral_image`."""
+    a, Q = _weighted(Q, nt, stride, dt, freqs, freq_weights)
+    dtype = np.dtype(dtype)
+    part = lambda z: z.astype(dtype).astype(np.float64)  # noqa: E731
+    s = np.zeros(Q.shape[1:], np.float64)
+    for k in range(a.size):
+        s = s + a[k] * (part(Q[k].real) ** 2 + part(Q[k].imag) ** 2)
+    return s.astype(dtype)

@@ -121,6 +121,10 @@ class NoExchange:
             return engine.illumination_vec(slot, wrt)
         return engine.illumination(wrt)
 
+    def reduce_array(self, a):
+        """The sum over the ranks of a host array that has no device accumulator (the spectral illumination)."""
+        return a
+
 
 class RcclExchange:
     """Production exchange: RCCL all-reduce (over xGMI) of the device-side accumulators.
@@ -133,6 +137,7 @@ class RcclExchange:
 
     def __init__(self, engine, rdzv):
         self.rank, self.world = rdzv.rank, rdzv.world
+        self.rdzv = rdzv
         uid = rdzv.broadcast(type(engine).comm_unique_id() if self.rank == 0 else None)
         err = ""
         try:
@@ -166,6 +171,11 @@ class RcclExchange:
         engine.allreduce_illumination()
         return NoExchange.reduce_illumination(self, engine, wrt, slot)
 
+    def reduce_array(self, a):
+        """As :meth:`NoExchange.reduce_array`, over the control plane: the Fourier store has no illumination accumulator
+        on the device for RCCL to sum, and this runs once per preconditioner."""
+        return self.rdzv.allreduce_array(a).reshape(np.shape(a))
+
 
 class HostExchange:
     """Sum on host arrays over the control plane (:class:`rendezvous.Rendezvous`): the path the CPU-only
@@ -185,6 +195,9 @@ class HostExchange:
         if slot is None:
             return H
         engine.vec_upload(slot, H)
+
+    def reduce_array(self, a):
+        return self.rdzv.allreduce_array(a).reshape(np.shape(a))
 
 
 class EnginePool:
@@ -293,8 +306,35 @@ class _Illuminated:
                 e.set_illumination(False)
 
 
+class _Spectral:
+    """Spectral imaging of one evaluation (``spectral_imaging=True``): every shot's adjoint is
+    ``Engine.adjoint_spectral(residual, freq_weights)``, and with ``illum`` the shots' ``Engine.fourier_illumination`` are
+    summed on the host, per engine (a pool drives each engine from one thread) and then over engines and ranks."""
+
+    def __init__(self, engine, freq_weights, wrt, illum):
+        for e in _engines(engine):
+            if getattr(e, "fourier_freqs", None) is None or not hasattr(e, "adjoint_spectral"):
+                raise ValueError("spectral_imaging needs engines that keep the Fourier store (Engine(fourier=freqs))")
+        self.freq_weights, self.wrt, self.illum = freq_weights, wrt, bool(illum)
+        self.H = {}
+
+    def adjoint(self, e, shot, residual):
+        if residual is not None and shot.rec_spread is not None and not shot._on_device(e):
+            residual = shot.rec_spread.scatter(residual)
+        e.adjoint_spectral(None if residual is None else np.ascontiguousarray(residual), self.freq_weights)
+        if self.illum:
+            h = np.asarray(e.fourier_illumination(self.freq_weights, self.wrt), np.float64)
+            self.H[id(e)] = self.H[id(e)] + h if id(e) in self.H else h
+
+    def illumination(self, engine, ex):
+        """H of this evaluation summed over shots, engines and ranks (zeros on a rank that owned no shot)"""
+        engs = _engines(engine)
+        H = sum((self.H[id(e)] for e in engs if id(e) in self.H), np.zeros(engs[0].shape))
+        return ex.reduce_array(H)
+
+
 def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", objective=None, device_l2=True,
-                        illumination=False):
+                        illumination=False, spectral_imaging=False, freq_weights=None):
     """J = sum_shots objective(F_s(model), d_obs,s) and dJ/dmodel, summed over all ranks.
 
     ``objective(d_syn, d_obs) -> (J, dJ/dd_syn)``; default least squares 1/2 ||d_syn - d_obs||^2
@@ -321,24 +361,34 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
 
     ``illumination=True``: returns ``(J, g, H)`` with H the source-side illumination of the same sweeps, in the same
     parametrisation as g, summed over all ranks (``Engine.illumination``): no extra propagation.
+
+    ``spectral_imaging=True`` (engines that keep the Fourier store): every shot's adjoint is
+    ``Engine.adjoint_spectral(residual, freq_weights)``, the gradient formed per frequency with the weights
+    ``freq_weights`` (None: 1).  ``illumination=True`` is then allowed on such engines and sums
+    ``Engine.fourier_illumination(freq_weights, wrt)`` over shots, engines and ranks (on the host: the Fourier store has
+    no accumulator of it on the device).  Without ``spectral_imaging`` nothing changes, and a Fourier engine refuses
+    ``illumination=True``.
     """
     from .objectives import l2
     objective = objective or l2
     ex = exchange or NoExchange()
-    with _Illuminated(engine, illumination):
+    spectral = _Spectral(engine, freq_weights, wrt, illumination) if spectral_imaging else None
+    with _Illuminated(engine, illumination and spectral is None):
         for e in _engines(engine):
             e.set_model(model)
             e.reset_gradient()
-        misfit = _sweep_shots(engine, shots, ex, objective, device_l2)
+        misfit = _sweep_shots(engine, shots, ex, objective, device_l2, spectral)
         out = ex.reduce(_engines(engine)[0], misfit, wrt)[::-1]
-        if illumination:
+        if illumination and spectral is not None:
+            out = out + (spectral.illumination(engine, ex),)
+        elif illumination:
             out = out + (ex.reduce_illumination(_engines(engine)[0], wrt),)
     return out
 
 
-def _sweep_shots(engine, shots, ex, objective, device_l2=True):
+def _sweep_shots(engine, shots, ex, objective, device_l2=True, spectral=None):
     """forward + adjoint of this rank's shots; returns the misfit, gradients summed into the
-    (primary) engine's accumulator."""
+    (primary) engine's accumulator.  ``spectral`` (:class:`_Spectral`): the adjoint is its spectral one."""
     from .objectives import l2
     # a datafit objective names its device call and its host call itself (datafit.WeightedL2.device, .host); plain least
     # squares is a function with a device path, any other callable has none
@@ -353,10 +403,16 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True):
         if device_l2 and method and hasattr(e, method) and (s.rec_spread is None or s._on_device(e)):
             # misfit and adjoint source are formed on the device (per node, or per off-grid point)
             j = objective.device(e, s, i) if own else e.misfit_l2(s.d_obs)
-            e.adjoint(None)
+            if spectral is not None:
+                spectral.adjoint(e, s, None)
+            else:
+                e.adjoint(None)
             return j
         j, r = objective.host(d, s, i) if own else objective(d, s.d_obs)
-        s.adjoint(e, r)
+        if spectral is not None:
+            spectral.adjoint(e, s, r)
+        else:
+            s.adjoint(e, r)
         return j
 
     mine = partition_shots(len(shots), ex.rank, ex.world)
@@ -369,15 +425,18 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True):
 
 
 def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=None, wrt="velocity",
-                               objective=None, device_l2=True, illum_slot=None):
+                               objective=None, device_l2=True, illum_slot=None, spectral_imaging=False,
+                               freq_weights=None):
     """Like :func:`misfit_and_gradient`, with the model read from and the gradient written to
     device-resident vectors (``Engine.vec_*``): no model-sized array crosses PCIe.  ``illum_slot``: the vector
-    that receives the illumination H of the same sweeps (see :func:`misfit_and_gradient`)."""
+    that receives the illumination H of the same sweeps (see :func:`misfit_and_gradient`).  ``spectral_imaging`` and
+    ``freq_weights`` as there; the spectral illumination is summed on the host and uploaded into ``illum_slot``."""
     from .objectives import l2
     objective = objective or l2
     ex = exchange or NoExchange()
     engs = _engines(engine)
-    with _Illuminated(engine, illum_slot is not None):
+    spectral = _Spectral(engine, freq_weights, wrt, illum_slot is not None) if spectral_imaging else None
+    with _Illuminated(engine, illum_slot is not None and spectral is None):
         engs[0].set_model_vec(model_slot)
         if len(engs) > 1:  # the optimiser's vectors live in the primary engine: hand the model over
             model = engs[0].vec_download(model_slot)
@@ -385,10 +444,12 @@ def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=No
                 e.set_model(model)
         for e in engs:
             e.reset_gradient()
-        misfit = _sweep_shots(engine, shots, ex, objective, device_l2)
+        misfit = _sweep_shots(engine, shots, ex, objective, device_l2, spectral)
         misfit = ex.reduce_device(engs[0], misfit)
         engs[0].gradient_vec(grad_slot, wrt)
-        if illum_slot is not None:
+        if illum_slot is not None and spectral is not None:
+            engs[0].vec_upload(illum_slot, spectral.illumination(engine, ex))
+        elif illum_slot is not None:
             ex.reduce_illumination(engs[0], wrt, illum_slot)
     return misfit
 

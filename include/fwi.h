@@ -40,6 +40,8 @@ extern "C" {
  * are purely additive -- new symbols, fwi_config and every existing call unchanged -- so a client built against the
  * earlier 14 keeps working. */
 /* ... and with the Fourier store (fwi_set_fourier_store, fwi_fourier_spectrum, fwi_store_bytes), additive in the same way. */
+/* ... and with spectral imaging on it (fwi_adjoint_spectral, fwi_fourier_image, fwi_fourier_gradient[_vec],
+ * fwi_fourier_adjoint_spectrum, fwi_fourier_illumination[_vec]). */
 #define FWI_ABI_VERSION 14
 
 enum { FWI_F32 = 0, FWI_F64 = 1 };
@@ -505,6 +507,39 @@ int fwi_allreduce_illumination(fwi_ctx *ctx);  /* in-place sum over the ranks of
 int fwi_set_fourier_store(fwi_ctx *ctx, int32_t nfreq, const double *freqs_hz, int32_t batch);
 int fwi_fourier_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out);
 int fwi_store_bytes(fwi_ctx *ctx, int64_t *bytes_out);
+
+/* Spectral imaging on the Fourier store: the gradient formed in the frequency domain, per frequency (Sirgue, Etgen and
+ * Albertin, 2008), instead of by synthesis plus time-domain imaging.  With M_k the same analysis applied to the adjoint
+ * field at the imaging samples,
+ *     M_k(x) = sum_j mu^{jS+1}(x) (cos theta_kj - i sin theta_kj)       (mu^{jS+1}: what the imaging pairs with q^{jS})
+ * the band-limited imaging sum of fwi_adjoint(image != 0) is, exactly and for any set of frequencies,
+ *     sum_j mu^{jS+1} q~^{jS} = sum_k w_k Re(Q_k conj M_k) = sum_k w_k (Re Q_k Re M_k + Im Q_k Im M_k)
+ * in the units of the gradient accumulator, so the terms of the sum are the per-frequency gradients g_k.
+ * fwi_adjoint_spectral: the reverse sweep of fwi_adjoint(ctx, residual, 0, adj_src_out) -- same residual handling
+ * (residual == NULL, off-grid point sets), adj_src_out bit-identical -- one time step per launch, with M_k accumulated
+ * behind it into 2 F further model-sized arrays (allocated by the first call, FWI_ENOMEM when they do not fit; zeroed by
+ * every call; fwi_store_bytes counts them from then on, fwi_set_fourier_store frees them).  The adjoint field is packed
+ * into the ring slots the forward sweep no longer needs.  The gradient accumulator is not touched.
+ * fwi_fourier_image: gradient accumulator += sum_k a_k w_k Re(Q_k conj M_k), a_k = freq_weights[k] (NULL: ones);
+ * fwi_gradient*, fwi_gradient_add and fwi_allreduce_gradient follow as after fwi_adjoint(image != 0).
+ * fwi_fourier_gradient[_vec]: the gradient fwi_gradient[_vec] would return if the accumulator held that sum alone (scale
+ * -S / dt^2, same `wrt`); the accumulator is not touched.  One-hot weights give g_k.
+ * fwi_fourier_adjoint_spectrum: M_k, as fwi_fourier_spectrum returns Q_k.
+ * fwi_fourier_illumination[_vec]: H_m = (S / dt^4) sum_k a_k w_k |Q_k|^2, H_c = H_m (2 / c^3)^2, in the units and with the
+ * `wrt` of fwi_illumination; needs only the fwi_forward(save != 0).  When every f_k is a bin of the sampled axis this is
+ * the illumination (S / dt^4) sum_j (q~^{jS})^2 of the band-limited term (Parseval), with all bins that of the stored
+ * term; off the bins it is this formula and no such sum.
+ * FWI_ESTATE, with the reason in fwi_last_error: the Fourier store is off; no fwi_forward(save != 0) since it was set; for
+ * the image, the gradient and the adjoint spectrum, no fwi_adjoint_spectral after the latest fwi_forward(save != 0).
+ * FWI_EINVAL: a weight that is not finite, a negative weight of the illumination, k outside [0, F).  fwi_adjoint(image != 0)
+ * on the same context is unchanged and may follow or precede these calls.  No reference counterpart. */
+int fwi_adjoint_spectral(fwi_ctx *ctx, const void *residual, void *adj_src_out);
+int fwi_fourier_image(fwi_ctx *ctx, const double *freq_weights /* F, or NULL = ones */);
+int fwi_fourier_gradient(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, void *out);
+int fwi_fourier_gradient_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, int32_t slot);
+int fwi_fourier_adjoint_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out);
+int fwi_fourier_illumination(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, void *out);
+int fwi_fourier_illumination_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, int32_t slot);
 
 /* Elementwise vector operations for a diagonal preconditioner (pad columns of the compact layout stay 0). */
 int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x);               /* y := x * y */

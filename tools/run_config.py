@@ -37,6 +37,13 @@ def main():
                          "forward term band-passed to them (Engine.set_fourier_store)")
     ap.add_argument("--fourier-batch", type=int, default=8, metavar="B",
                     help="samples per transform launch of --fourier-store, 1 .. 8 (B + 1 ring slots)")
+    ap.add_argument("--fourier-imaging", nargs="?", const="plain", default=None, choices=["plain", "whiten"],
+                    metavar="whiten",
+                    help="with --fourier-store: form the gradient in the frequency domain, per frequency "
+                         "(Engine.adjoint_spectral) instead of re-synthesising the forward term; --precondition then takes "
+                         "the spectral illumination (Engine.fourier_illumination).  `whiten`: weight the per-frequency "
+                         "gradients by 1 / (mean power of the observed data at the frequency + 1e-4 of the largest), scaled "
+                         "to mean 1 (datafit.whitening_weights; one rank).  Composes with --spectral and --precondition")
     ap.add_argument("--update-form", default="auto", choices=["auto", "increment", "standard"],
                     help="fp32 update form; auto = shots.inversion_engine's choice (increment: 1e-5 end to end)")
     ap.add_argument("--launch-mode", default="auto", choices=["auto", "stream", "graph"])
@@ -130,6 +137,10 @@ def main():
         ap.error("--spectral-floor-percent X must be finite and >= 0")
     if a.spectral_whiten and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--spectral-whiten takes its weights from this rank's data: it runs on one rank")
+    if a.fourier_imaging is not None and a.fourier_store is None:
+        ap.error("--fourier-imaging needs --fourier-store FMIN,FMAX (it images on the store's frequencies)")
+    if a.fourier_imaging == "whiten" and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--fourier-imaging whiten takes its weights from this rank's data: it runs on one rank")
     spectral_band = None
     if a.spectral_band is not None:
         try:
@@ -245,6 +256,16 @@ def main():
         power = np.mean(power, axis=0)
         spectral_fw = 1.0 / (power + 1e-4 * float(power.max()))
 
+    # spectral imaging: the keywords every evaluation below hands to the shot loop
+    imaging = {}
+    if a.fourier_imaging is not None:
+        imaging = {"spectral_imaging": True}
+        if a.fourier_imaging == "whiten":  # data-only numbers, fixed for the run: the mean power over this rank's shots
+            power = [1.0 / datafit.whitening_weights(s.d_obs, w.dt, uf["fourier"], 0.0) for s in shots if s.d_obs is not None]
+            power = np.mean(power, axis=0)
+            fw = 1.0 / (power + 1e-4 * float(power.max()))
+            imaging["freq_weights"] = fw / float(fw.mean())
+
     def objective_of(taps):
         """the misfit of one stage: a fresh object per band (a MatchedL2 keeps the shots' filters of ITS band)"""
         if a.spectral is not None:  # (the floor: a data-only number per shot, datafit.spectral_floor of its d_obs)
@@ -275,7 +296,7 @@ def main():
 
     def fg(m):
         evals[0] += 1
-        return sh.misfit_and_gradient(pool, m, shots, ex, objective=obj[0])
+        return sh.misfit_and_gradient(pool, m, shots, ex, objective=obj[0], **imaging)
 
     eps = a.precondition
     first_H = []
@@ -284,7 +305,7 @@ def main():
         if eps is None or first_H:
             return fg(m)
         evals[0] += 1
-        J, g, H = sh.misfit_and_gradient(pool, m, shots, ex, objective=obj[0], illumination=True)
+        J, g, H = sh.misfit_and_gradient(pool, m, shots, ex, objective=obj[0], illumination=True, **imaging)
         first_H.append(H)
         return J, g
 
@@ -305,7 +326,7 @@ def main():
 
             def fg_band(xs, gs):
                 evals[0] += 1
-                return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex, objective=obj[0])
+                return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex, objective=obj[0], **imaging)
             x, _, lg = lbfgs_device(e, fg_band, x, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
                                     bounds=bounds)
             filters_line(obj[0], f_hz)
@@ -315,13 +336,14 @@ def main():
     elif a.iters > 0 and not a.host_lbfgs:
         pslot = lbfgs_device_slots(5) if eps is not None else None
         h0 = sh.smoothing_h0_device(pool, h0_sigma, mask=mute, precond_slot=pslot) if use_h0 else None
-        fg_p = sh.preconditioned_fg_device(pool, shots, pslot, eps, ex, objective=obj[0]) if eps is not None else None
+        fg_p = (sh.preconditioned_fg_device(pool, shots, pslot, eps, ex, objective=obj[0], **imaging)
+                if eps is not None else None)
 
         def fg_dev(xs, gs):
             evals[0] += 1
             if fg_p is not None:
                 return fg_p(xs, gs)
-            return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex, objective=obj[0])
+            return sh.misfit_and_gradient_device(pool, xs, gs, shots, ex, objective=obj[0], **imaging)
         extra = 0
         if a.regularize is not None:
             xs0 = rg.prior_slot(5, pslot, h0) if reg_prior is not None else None
@@ -370,7 +392,7 @@ def main():
                           "traveltime_max_lag": a.traveltime, "spectral": a.spectral,
                           "spectral_freqs_hz": None if spectral_freqs is None else [float(f) for f in spectral_freqs],
                           "spectral_floor_percent": a.spectral_floor_percent if a.spectral is not None else None,
-                          "spectral_whiten": a.spectral_whiten,
+                          "spectral_whiten": a.spectral_whiten, "fourier_imaging": a.fourier_imaging,
                           "transport": a.transport, "transport_param": a.transport_param,
                           "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
                           "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
