@@ -1464,12 +1464,7 @@ struct Impl {
         ctx->nt = nt;
         ctx->nsrc = nsrc;
         ctx->nrec = nrec;
-        ctx->have_forward = false;
-        ctx->have_q = false;
-        ctx->have_m = false;
-        ctx->have_syn = false;
-        ctx->have_dev_residual = false;
-        hipStream_t s = ctx->stream;
+        hipStream_t s = ctx->stream;  // (no shot to speak of from here to the end: drop_forward, the callers' first statement)
         if (nsrc && (rc = upload_amplitudes(ctx, ctx->wav, wavelet, nt, nsrc, ctx->src_sp))) return rc;
         Sweep sw;
         if ((rc = start_sweep(ctx, sw))) return rc;
@@ -1730,8 +1725,10 @@ struct Impl {
             // the store holds C L u rounded to bf16; the source's own share C w / h^D of the forward term is paired
             // exactly, in closed form: g(x_s) += cq_s sum_n mu^{n+1}(x_s) w_s^n, with mu at the sources = the series
             // this sweep has just recorded (scaled by rs)
-            HIPCHK(ctx, launch_source_image<T>((const T *)ctx->series, (const T *)ctx->wav, (const int64_t *)ctx->src.cidx,
-                                               (const T *)ctx->src.cq, (T *)ctx->g_acc, nt, ctx->nsrc, ctx->istride,
+            // (per node, in the sorted order of the source set: two sources on one node add in a fixed order)
+            HIPCHK(ctx, launch_source_image<T>((const T *)ctx->series, (const T *)ctx->wav, (const int64_t *)ctx->src.s_cidx,
+                                               (const T *)ctx->src.s_cq, (const int *)ctx->src.s_col,
+                                               (const int *)ctx->src.s_run, (T *)ctx->g_acc, nt, ctx->nsrc, ctx->istride,
                                                (T)(1.0 / (double)rs), s));
         if (image && K == 0) {  // the whole store: the ceil(nt / S) slots of this shot, once
             if ((rc = illum_accumulate(ctx, q_store, (nt + ctx->istride - 1) / ctx->istride))) return rc;
@@ -2981,9 +2978,19 @@ int fwi_set_model(fwi_ctx *ctx, const void *c_host) {
                     Impl<double>::set_model(ctx, (const double *)c_host));
 }
 
+// What a forward call begins with (include/fwi.h, "a forward call that fails"): the shot before it is given up before
+// the first argument is looked at, so that no error return -- a refused argument, a receiver outside the grid found after
+// the source set has been replaced, an allocation that does not fit -- leaves flags that describe the old shot beside
+// point sets, sizes or buffers of the new one.
+static void drop_forward(fwi_ctx *ctx) {
+    ctx->have_forward = ctx->have_q = ctx->have_m = ctx->have_syn = ctx->have_dev_residual = false;
+    ctx->resid_pts_in = fwi_ctx::RESID_PTS_NONE;
+}
+
 int fwi_forward(fwi_ctx *ctx, int32_t nt, int32_t nsrc, const int32_t *src_idx, const void *wavelet,
                 int32_t nrec, const int32_t *rec_idx, int32_t save, void *seis_out) {
     if (!ctx) return FWI_EINVAL;
+    drop_forward(ctx);
     if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_forward: call fwi_set_model first");
     if (nt < 1 || nt > ctx->cfg.nt_max)
         return ctx->fail(FWI_EINVAL, "fwi_forward: nt=%d outside [1, nt_max=%d]", nt, ctx->cfg.nt_max);
@@ -3033,6 +3040,7 @@ int fwi_forward_spread(fwi_ctx *ctx, int32_t nt, int32_t nsrc_pts, int32_t nsrc_
                        int32_t nrec_nodes, const int32_t *rec_idx, const int32_t *rec_pt_start, const void *rec_weight,
                        int32_t save, void *seis_out) {
     if (!ctx) return FWI_EINVAL;
+    drop_forward(ctx);
     if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_forward_spread: call fwi_set_model first");
     if (nt < 1 || nt > ctx->cfg.nt_max)
         return ctx->fail(FWI_EINVAL, "fwi_forward_spread: nt=%d outside [1, nt_max=%d]", nt, ctx->cfg.nt_max);
@@ -3568,13 +3576,8 @@ int fwi_set_illumination(fwi_ctx *ctx, int32_t on) {
 
 // Frees the arrays of the Fourier store; the context is back on its configured store.
 static int fourier_release(fwi_ctx *ctx) {
-    if (ctx->four_acc || ctx->four_ring || ctx->four_tw || ctx->four_adj || ctx->four_w)
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // no sweep still uses them
-    for (void **p : {&ctx->four_acc, &ctx->four_ring, &ctx->four_tw, &ctx->four_adj, &ctx->four_w}) {
-        void *q = *p;
-        *p = nullptr;
-        if (q) HIPCHK(ctx, hipFree(q));
-    }
+    // the state first: a synchronise or a free that the runtime refuses must not leave a context that says it holds
+    // Q_k or M_k beside arrays already given up (fwi_adjoint(image) would synthesise from a null pointer)
     if (!ctx->four_freqs.empty()) {
         ctx->store_held = 0;
         ctx->have_q = false;
@@ -3583,6 +3586,13 @@ static int fourier_release(fwi_ctx *ctx) {
     ctx->four_batch = ctx->four_rows = 0;
     ctx->four_sweep = false;
     ctx->have_m = false;
+    if (ctx->four_acc || ctx->four_ring || ctx->four_tw || ctx->four_adj || ctx->four_w)
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // no sweep still uses them
+    for (void **p : {&ctx->four_acc, &ctx->four_ring, &ctx->four_tw, &ctx->four_adj, &ctx->four_w}) {
+        void *q = *p;
+        *p = nullptr;
+        if (q) HIPCHK(ctx, hipFree(q));
+    }
     return FWI_OK;
 }
 
@@ -3618,14 +3628,14 @@ int fwi_set_fourier_store(fwi_ctx *ctx, int32_t nfreq, const double *freqs_hz, i
                 return ctx->fail(FWI_EINVAL, "fwi_set_fourier_store: frequencies %d and %d are equal (%g Hz)", m, k, f);
     }
     if (int rc = fourier_release(ctx)) return rc;
+    ctx->store_held = 0;
+    ctx->have_q = false;  // (before the free below can fail: the store it speaks of is about to go)
     if (ctx->q_store) {  // the native store of an earlier forward: its memory is what this store is there to save
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         void *q = ctx->q_store;
         ctx->q_store = nullptr;
         HIPCHK(ctx, hipFree(q));
     }
-    ctx->store_held = 0;
-    ctx->have_q = false;
     ctx->four_freqs.assign(freqs_hz, freqs_hz + nfreq);
     ctx->four_batch = batch;
     return FWI_OK;

@@ -144,8 +144,8 @@ template <typename T>
 hipError_t launch_image(const GridDesc &g, const T *u, const T *q, T *gacc, int q_bf16, hipStream_t s);
 // bf16 store: gacc[cidx[s]] += cq[s] * inv_rs * sum_{n % stride == 0} adj_series[n, s] * wav[n, s]
 template <typename T>
-hipError_t launch_source_image(const T *adj_series, const T *wav, const int64_t *cidx, const T *cq, T *gacc, int nt,
-                               int nsrc, int stride, T inv_rs, hipStream_t s);
+hipError_t launch_source_image(const T *adj_series, const T *wav, const int64_t *s_cidx, const T *s_cq, const int *s_col,
+                               const int *s_run, T *gacc, int nt, int nsrc, int stride, T inv_rs, hipStream_t s);
 // out[i] = gacc[i] * scale * (wrt_velocity ? -2 / c[i]^3 : 1); 0 in the pad columns
 template <typename T>
 hipError_t launch_finalize_gradient(const GridDesc &g, const T *gacc, const T *c, T *out, double scale,

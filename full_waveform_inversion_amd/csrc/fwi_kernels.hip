@@ -508,24 +508,35 @@ __device__ __forceinline__ T q_elem(const T *q, int64_t i, int bf16) {
     return q[i];
 }
 
-// g[x_s] += sum_n mu^{n+1}(x_s) * cq_s * w^n_s: the part of the imaging term that is the source itself (bf16 store)
+// g[x_s] += sum_n mu^{n+1}(x_s) * cq_s * w^n_s: the part of the imaging term that is the source itself (bf16 store).
+// One thread per NODE, over the copy of the source set sorted by node (upload_set: the entries of a node are consecutive,
+// `run` holds their number at the first of them and 0 at the others, `col` the entry's column of the series): the shares
+// of the sources that sit on one node are added in that order, as the injection adds them, and by a plain store -- an
+// atomicAdd per source left the order of two such sources, and with it the last bit of the gradient there, to the hardware.
 template <typename T>
-__global__ void source_image_kernel(const T *adj_series, const T *wav, const int64_t *cidx, const T *cq, T *gacc,
-                                    int nt, int nsrc, int stride, T inv_rs) {
-    const int sidx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (sidx >= nsrc) return;
-    double acc = 0.0;
-    for (int n = 0; n < nt; n += stride)
-        acc += (double)adj_series[(int64_t)n * nsrc + sidx] * (double)wav[(int64_t)n * nsrc + sidx];
-    atomicAdd(gacc + cidx[sidx], (T)(acc * (double)inv_rs * (double)cq[sidx]));
+__global__ void source_image_kernel(const T *adj_series, const T *wav, const int64_t *s_cidx, const T *s_cq,
+                                    const int *s_col, const int *s_run, T *gacc, int nt, int nsrc, int stride, T inv_rs) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nsrc) return;
+    const int len = s_run[k];
+    if (len == 0) return;
+    T g = gacc[s_cidx[k]];
+    for (int j = k; j < k + len; ++j) {
+        const int sidx = s_col[j];
+        double acc = 0.0;
+        for (int n = 0; n < nt; n += stride)
+            acc += (double)adj_series[(int64_t)n * nsrc + sidx] * (double)wav[(int64_t)n * nsrc + sidx];
+        g += (T)(acc * (double)inv_rs * (double)s_cq[j]);
+    }
+    gacc[s_cidx[k]] = g;
 }
 
 template <typename T>
-hipError_t launch_source_image(const T *adj_series, const T *wav, const int64_t *cidx, const T *cq, T *gacc, int nt,
-                               int nsrc, int stride, T inv_rs, hipStream_t s) {
+hipError_t launch_source_image(const T *adj_series, const T *wav, const int64_t *s_cidx, const T *s_cq, const int *s_col,
+                               const int *s_run, T *gacc, int nt, int nsrc, int stride, T inv_rs, hipStream_t s) {
     if (nsrc <= 0) return hipSuccess;
-    hipLaunchKernelGGL(source_image_kernel<T>, dim3((nsrc + 63) / 64), dim3(64), 0, s, adj_series, wav, cidx, cq, gacc,
-                       nt, nsrc, stride, inv_rs);
+    hipLaunchKernelGGL(source_image_kernel<T>, dim3((nsrc + 63) / 64), dim3(64), 0, s, adj_series, wav, s_cidx, s_cq, s_col,
+                       s_run, gacc, nt, nsrc, stride, inv_rs);
     return hipGetLastError();
 }
 
@@ -815,8 +826,8 @@ hipError_t launch_absmax(const T *x, int64_t n, double *out, hipStream_t s) {
 #define FWI_INSTANTIATE(T)                                                                          \
     template hipError_t launch_record<T>(const T *, const int64_t *, T *, T, int, hipStream_t);    \
     template hipError_t launch_image<T>(const GridDesc &, const T *, const T *, T *, int, hipStream_t); \
-    template hipError_t launch_source_image<T>(const T *, const T *, const int64_t *, const T *, T *, int, int, int, T, \
-                                               hipStream_t);                                        \
+    template hipError_t launch_source_image<T>(const T *, const T *, const int64_t *, const T *, const int *, const int *, \
+                                               T *, int, int, int, T, hipStream_t);                 \
     template hipError_t launch_finalize_gradient<T>(const GridDesc &, const T *, const T *, T *, double, int, \
                                                     hipStream_t);                                  \
     template hipError_t launch_repack<T>(const GridDesc &, T *, const T *, int, hipStream_t);       \

@@ -166,6 +166,21 @@ int fwi_forward_spread(fwi_ctx *ctx, int32_t nt, int32_t nsrc_pts, int32_t nsrc_
                        int32_t nrec_nodes, const int32_t *rec_idx, const int32_t *rec_pt_start, const void *rec_weight,
                        int32_t save, void *seis_out);
 
+/* A forward call that fails.  fwi_forward and fwi_forward_spread give up the shot before them as their first act, so
+ * whatever they return an error for -- a refused argument (nt, a null buffer), a point outside the grid, a point set
+ * with more than 8 nodes, a store that does not fit -- the context is left WITHOUT A FORWARD: fwi_adjoint,
+ * fwi_adjoint_spectral, fwi_born*, every fwi_misfit_*, fwi_residual_weight and the fwi_fourier_* calls that need Q_k or
+ * M_k return FWI_ESTATE until the next forward succeeds.  The model, the gradient and illumination accumulators, the
+ * vectors, the launch mode and the Fourier settings are untouched.  (The point sets, the sizes and the series buffers
+ * are replaced one by one on the way and a receiver is looked at after the sources are in place: a context that still
+ * called the old shot its forward would sweep the new points with the old counts.)
+ * The other calls that replace state need no such rule, each for its own reason.  fwi_adjoint and fwi_born* mark the
+ * synthetics and the device residual as used up before their first launch and only read the store: after an error inside
+ * the sweep the forward and its store are still those of the last fwi_forward, and the call may be repeated with a
+ * residual of the caller's.  fwi_adjoint_spectral drops the M_k before it zeroes them.  fwi_set_fourier_store checks all
+ * of its arguments before it touches anything, then forgets what the context stored (Q_k, M_k, the configured store)
+ * BEFORE it frees the arrays: a free the runtime refuses leaves a context that says it has no store. */
+
 /* adjoint(residual): reverse-time propagation of residual (nt, nrec) injected
  * at the receivers of the last forward.  image != 0 accumulates the zero-lag
  * forward x adjoint correlation into the gradient accumulator.  residual == NULL
