@@ -117,6 +117,10 @@ SIGNATURES = {
     "fwi_fourier_adjoint_spectrum": (C.c_int, [_P, _I32, _P, _P]),
     "fwi_fourier_illumination": (C.c_int, [_P, _I32, _P, _P]),
     "fwi_fourier_illumination_vec": (C.c_int, [_P, _I32, _P, _I32]),
+    "fwi_fourier_offset_image": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "fwi_fourier_offset_image_vec": (C.c_int, [_P, _I32, _I32, _P, _I32]),
+    "fwi_fourier_lag_image": (C.c_int, [_P, _D, _P, _P]),
+    "fwi_fourier_lag_image_vec": (C.c_int, [_P, _D, _P, _I32]),
     "fwi_vec_mul": (C.c_int, [_P, _I32, _I32]),
     "fwi_vec_recip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_vec_smooth": (C.c_int, [_P, _I32, C.POINTER(_D)]),

@@ -31,6 +31,7 @@
 #include "fwi_gather_tile.h"
 #include "fwi_fourier.h"
 #include "fwi_fimage.h"
+#include "fwi_feximage.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
 #include "fwi_match.h"
@@ -151,7 +152,8 @@ struct fwi_ctx {
     std::vector<double> four_tw_host;
     // Spectral imaging (fwi_adjoint_spectral; fwi_fimage.hip): 2 F compact accumulator volumes (Re M_k, Im M_k) of the
     // adjoint field, allocated by the first fwi_adjoint_spectral; have_m: they hold the M_k that go with the Q_k of the
-    // latest forward(save).  four_w: the F weights a_k w_k of the running image / illumination pass on the device.
+    // latest forward(save).  four_w: the F weights a_k w_k of the running image / illumination pass on the device (the
+    // 2 F of a time-lag image, fwi_feximage.hip; room for 2 FWI_FOURIER_FMAX doubles).
     void *four_adj = nullptr, *four_w = nullptr;
     bool have_m = false;
     std::vector<double> four_w_host;
@@ -1746,20 +1748,27 @@ struct Impl {
     }
 
     // The weights a_k w_k of one image / illumination pass on the device (w_k as fourier_table's synthesis weights, for
-    // the N samples of the last forward); `fw` = nullptr: a_k = 1
-    static int fourier_weights(fwi_ctx *ctx, const double *fw) {
+    // the N samples of the last forward); `fw` = nullptr: a_k = 1.  With `tau` (a time-lag image) the table holds 2 F
+    // entries instead, C_k = a_k w_k cos phi_k at k and D_k = a_k w_k sin phi_k at F + k, phi_k = 2 pi f_k tau formed in
+    // fp64 from the fractional part of f_k tau as fourier_table forms its phases (tau = 0: C_k = a_k w_k, D_k = 0).
+    static int fourier_weights(fwi_ctx *ctx, const double *fw, const double *tau = nullptr) {
         const int S = ctx->istride, N = (ctx->nt + S - 1) / S, F = (int)ctx->four_freqs.size();
         const double sdt = (double)S * ctx->cfg.dt;
-        if (!ctx->four_w) HIPCHK(ctx, hipMalloc(&ctx->four_w, FWI_FOURIER_FMAX * sizeof(double)));
+        if (!ctx->four_w) HIPCHK(ctx, hipMalloc(&ctx->four_w, 2 * FWI_FOURIER_FMAX * sizeof(double)));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the upload of the pass before may still read the host copy
         std::vector<double> &a = ctx->four_w_host;
-        a.assign(F, 0.0);
+        a.assign(tau ? 2 * F : F, 0.0);
         for (int k = 0; k < F; ++k) {
             const double f = ctx->four_freqs[k];
             const bool edge = f == 0.0 || std::fabs(2.0 * f * sdt - 1.0) <= FOURIER_NYQUIST_RTOL;
             a[k] = (fw ? fw[k] : 1.0) * ((edge ? 1.0 : 2.0) / N);
+            if (tau) {
+                const double x = f * *tau, th = 2.0 * M_PI * (x - std::floor(x));
+                a[F + k] = a[k] * std::sin(th);
+                a[k] = a[k] * std::cos(th);
+            }
         }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->four_w, a.data(), F * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->four_w, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         return FWI_OK;
     }
 
@@ -1796,6 +1805,27 @@ struct Impl {
         else
             HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2,
                                                     wrt == FWI_WRT_VELOCITY, ctx->stream));
+        if (out && (rc = download_compact(ctx, out, dev))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return FWI_OK;
+    }
+
+    // One lag of an extended image (fwi_feximage.h) into `dev`, through the sum, the scaling and the download of
+    // fourier_finalize(wrt = FWI_WRT_SLOWNESS2): the offset image of `h` cells along `axis` (0 = z, 1 = y, 2 = x of the
+    // GridDesc), or with `tau` the time-lag image.  Q_k, M_k and the gradient accumulator are read at most.
+    static int fourier_extended(fwi_ctx *ctx, int axis, int64_t h, const double *tau, const double *fw, void *dev, T *out) {
+        int rc = fourier_weights(ctx, fw, tau);
+        if (rc) return rc;
+        const int F = (int)ctx->four_freqs.size();
+        const T *q = (const T *)ctx->four_acc, *m = (const T *)ctx->four_adj;
+        if (tau)
+            HIPCHK(ctx, launch_feximage_lag<T>((T *)dev, q, m, (const double *)ctx->four_w, ctx->gd.npts, F, ctx->stream));
+        else
+            HIPCHK(ctx, launch_feximage_offset<T>(ctx->gd, (T *)dev, q, m, (const double *)ctx->four_w, F, axis, h,
+                                                  ctx->stream));
+        const double dt2 = ctx->cfg.dt * ctx->cfg.dt, S = (double)ctx->istride;
+        HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2, 0,
+                                                ctx->stream));
         if (out && (rc = download_compact(ctx, out, dev))) return rc;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return FWI_OK;
@@ -3743,6 +3773,49 @@ int fwi_fourier_illumination_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_w
     if (!ctx) return FWI_EINVAL;
     VEC_OR_FAIL(ctx, v, slot);
     return fourier_finalize(ctx, "fwi_fourier_illumination_vec", true, wrt, freq_weights, v, nullptr);
+}
+
+// `tau`: fwi_fourier_lag_image[_vec], else fwi_fourier_offset_image[_vec] of `h` cells along `axis` of the grid order;
+// `out`: the host array, nullptr for `dev`
+static int fourier_extended(fwi_ctx *ctx, const char *who, int32_t axis, int32_t h, const double *tau, const double *fw,
+                            void *dev, void *out) {
+    if (int rc = fourier_callable(ctx, who, true)) return rc;
+    if (!tau && (axis < 0 || axis >= ctx->gd.ndim))
+        return ctx->fail(FWI_EINVAL, "%s: axis=%d outside [0, %d)", who, (int)axis, ctx->gd.ndim);
+    if (tau && !std::isfinite(*tau)) return ctx->fail(FWI_EINVAL, "%s: tau is not finite", who);
+    if (int rc = fourier_weight_args(ctx, who, fw, false)) return rc;
+    if (tau)
+        for (double f : ctx->four_freqs)
+            if (!std::isfinite(f * *tau))
+                return ctx->fail(FWI_EINVAL, "%s: tau=%g s leaves no finite phase at %g Hz", who, *tau, f);
+    (void)hipSetDevice(ctx->cfg.device);
+    const int ax = tau ? 0 : axis == ctx->gd.ndim - 1 ? 2 : ctx->gd.ndim == 3 ? axis : 0;  // grid order z, [y,] x
+    return DISPATCH(ctx, Impl<float>::fourier_extended(ctx, ax, h, tau, fw, dev, (float *)out),
+                    Impl<double>::fourier_extended(ctx, ax, h, tau, fw, dev, (double *)out));
+}
+
+int fwi_fourier_offset_image(fwi_ctx *ctx, int32_t axis, int32_t h, const double *freq_weights, void *out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_offset_image: null output");
+    return fourier_extended(ctx, "fwi_fourier_offset_image", axis, h, nullptr, freq_weights, ctx->g_out, out);
+}
+
+int fwi_fourier_offset_image_vec(fwi_ctx *ctx, int32_t axis, int32_t h, const double *freq_weights, int32_t slot) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, v, slot);
+    return fourier_extended(ctx, "fwi_fourier_offset_image_vec", axis, h, nullptr, freq_weights, v, nullptr);
+}
+
+int fwi_fourier_lag_image(fwi_ctx *ctx, double tau, const double *freq_weights, void *out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_lag_image: null output");
+    return fourier_extended(ctx, "fwi_fourier_lag_image", 0, 0, &tau, freq_weights, ctx->g_out, out);
+}
+
+int fwi_fourier_lag_image_vec(fwi_ctx *ctx, double tau, const double *freq_weights, int32_t slot) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, v, slot);
+    return fourier_extended(ctx, "fwi_fourier_lag_image_vec", 0, 0, &tau, freq_weights, v, nullptr);
 }
 
 int fwi_fourier_adjoint_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out) {

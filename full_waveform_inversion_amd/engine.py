@@ -609,6 +609,64 @@ class Engine:
         w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
         self._chk(self._lib.fwi_fourier_illumination_vec(self._c, w, fwp, slot))
 
+    # -- extended images on the Fourier store (include/fwi.h fwi_fourier_offset_image, fwi_fourier_lag_image) -----
+    def _axis(self, axis):
+        """Grid axis ``0 .. ndim - 1`` from an index or ``"z"`` / ``"y"`` / ``"x"`` (``"y"``: 3-D only)"""
+        if isinstance(axis, str):
+            names = "zyx" if len(self.shape) == 3 else "zx"
+            if len(axis) != 1 or axis not in names:
+                raise ValueError("axis must be an index or one of %s" % ", ".join(repr(n) for n in names))
+            return names.index(axis)
+        return int(axis)
+
+    def fourier_offset_image_vec(self, slot, axis, h, freq_weights=None):
+        """Vector ``slot`` := the subsurface-offset image ``E_h`` of the last :meth:`adjoint_spectral` on the device
+        (``fwi_fourier_offset_image_vec``; one lag of :meth:`fourier_offset_images`)."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        self._chk(self._lib.fwi_fourier_offset_image_vec(self._c, self._axis(axis), int(h), fwp, slot))
+
+    def fourier_offset_images(self, axis, offsets, freq_weights=None):
+        """Subsurface-offset common-image gather of the last :meth:`adjoint_spectral` as ``(len(offsets), *shape)``: for
+        every integer ``h`` of ``offsets`` (cells along ``axis``, an index in grid order or ``"z"`` / ``"y"`` / ``"x"``)
+
+            ``E_h(x) = -(S / dt^2) sum_k a_k w_k Re(Q_k(x - h e) conj M_k(x + h e))``
+
+        in the units of ``fourier_gradient(wrt="slowness2")``, zero wherever ``x - h e`` or ``x + h e`` leaves the grid
+        (``fwi_fourier_offset_image``).  ``h = 0`` is that gradient, bit for bit.  For any set of frequencies this is the
+        band-limited imaging sum ``sum_j mu^{jS+1}(x + h e) q~^{jS}(x - h e)``.  One streaming pass over the resident
+        coefficients per lag, no further sweep; ``a = freq_weights`` (None: 1).  One shot's; the caller sums over shots
+        (:func:`shots.extended_image`)."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        ax = self._axis(axis)
+        offsets = [int(h) for h in np.atleast_1d(offsets)]
+        E = np.zeros((len(offsets),) + self.shape, self.dtype)
+        for l, h in enumerate(offsets):
+            self._chk(self._lib.fwi_fourier_offset_image(self._c, ax, h, fwp, E[l].ctypes.data_as(C.c_void_p)))
+        return E
+
+    def fourier_lag_image_vec(self, slot, tau, freq_weights=None):
+        """Vector ``slot`` := the time-lag image ``E_tau`` of the last :meth:`adjoint_spectral` on the device
+        (``fwi_fourier_lag_image_vec``; one lag of :meth:`fourier_lag_images`)."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        self._chk(self._lib.fwi_fourier_lag_image_vec(self._c, float(tau), fwp, slot))
+
+    def fourier_lag_images(self, taus, freq_weights=None):
+        """Time-lag common-image gather of the last :meth:`adjoint_spectral` as ``(len(taus), *shape)``: for every finite
+        ``tau`` of ``taus`` (seconds)
+
+            ``E_tau(x) = -(S / dt^2) sum_k a_k w_k Re(Q_k(x) conj M_k(x) exp(-i 2 pi f_k tau))``
+
+        in the units of ``fourier_gradient(wrt="slowness2")`` (``fwi_fourier_lag_image``); ``tau = 0`` is that gradient,
+        bit for bit.  Where every frequency is a bin of the sampled axis and ``tau = m S dt`` this is the imaging sum with
+        the sampled forward term delayed circularly by ``m`` samples; off the bins, or at any other ``tau``, it is this
+        formula and no such sum.  One streaming pass per lag; ``a = freq_weights`` (None: 1)."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        taus = [float(t) for t in np.atleast_1d(taus)]
+        E = np.zeros((len(taus),) + self.shape, self.dtype)
+        for l, tau in enumerate(taus):
+            self._chk(self._lib.fwi_fourier_lag_image(self._c, tau, fwp, E[l].ctypes.data_as(C.c_void_p)))
+        return E
+
     def store_bytes(self):
         """Device bytes held for the forward store of whichever kind (``fwi_store_bytes``); 0 before the first
         ``forward(save=True)`` allocates it."""

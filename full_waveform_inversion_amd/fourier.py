@@ -175,3 +175,77 @@ def spectral_illumination(Q, nt, stride, dt, freqs, freq_weights=None, dtype=np.
     for k in range(a.size):
         s = s + a[k] * (part(Q[k].real) ** 2 + part(Q[k].imag) ** 2)
     return s.astype(dtype)
+
+
+# -- extended images (fwi_fourier_offset_image, fwi_fourier_lag_image; csrc/fwi_feximage.hip) ---------------------------
+#
+# The same exchange of sums with the two fields read at different cells, ``x - h e`` and ``x + h e``, gives the
+# subsurface-offset image, again for ANY set of frequencies::
+#
+#     sum_j mu^{jS+1}(x + h e) q~^{jS}(x - h e) = sum_k w_k Re(Q_k(x - h e) conj M_k(x + h e))
+#
+# A delay of the forward term by ``tau`` multiplies ``Q_k`` by ``exp(-i 2 pi f_k tau)``.  On bin frequencies and with
+# ``tau = m S dt`` that is the circular shift of the sampled ``q~`` by ``m`` samples, and :func:`lag_image` is the imaging
+# sum of the shifted term; off the bins, or at any other ``tau``, it is a definition and no such sum (only ``tau = 0`` is
+# the imaging sum for every frequency set).
+
+def offset_image(Q, M, nt, stride, dt, freqs, axis, h, freq_weights=None, dtype=np.float64):
+    """``sum_k a_k w_k Re(Q_k(x - h e) conj M_k(x + h e))`` for the integer ``h`` (cells along the model axis ``axis``,
+    0 = the first axis after the frequencies), zero wherever ``x - h e`` or ``x + h e`` lies outside the grid; in the units
+    of the imaging sum, as :func:`spectral_image`, which it equals bit for bit at ``h = 0``.  ``dtype`` as there."""
+    a, Q = _weighted(Q, nt, stride, dt, freqs, freq_weights)
+    M = np.asarray(M)
+    dtype = np.dtype(dtype)
+    axis, h = int(axis), int(h)
+    if not 0 <= axis < Q.ndim - 1:
+        raise ValueError("axis %d outside [0, %d)" % (axis, Q.ndim - 1))
+    n = Q.shape[1 + axis]
+    out = np.zeros(Q.shape[1:], dtype)
+    if 2 * abs(h) >= n:
+        return out
+    # the cells x with abs(h) <= x_a < n - abs(h); Q is read at x - h, M at x + h
+    cut = lambda lo: (slice(None),) * axis + (slice(lo, lo + n - 2 * abs(h)),)  # noqa: E731
+    part = lambda z: z.astype(dtype).astype(np.float64)  # noqa: E731
+    s = np.zeros(out[cut(abs(h))].shape, np.float64)
+    for k in range(a.size):
+        q, m = Q[k][cut(abs(h) - h)], M[k][cut(abs(h) + h)]
+        s = s + a[k] * (part(q.real) * part(m.real) + part(q.imag) * part(m.imag))
+    out[cut(abs(h))] = s.astype(dtype)
+    return out
+
+
+def lag_image(Q, M, nt, stride, dt, freqs, tau, freq_weights=None, dtype=np.float64):
+    """``sum_k a_k w_k Re(Q_k conj(M_k) exp(-i 2 pi f_k tau))`` for a finite ``tau`` in seconds, in the units of the imaging
+    sum, as :func:`spectral_image`, which it equals bit for bit at ``tau = 0``.  With ``P_k = Q_k conj M_k`` the terms are
+    ``a_k w_k (Re P_k cos phi_k + Im P_k sin phi_k)``, ``phi_k = 2 pi f_k tau`` from the fractional part of ``f_k tau`` (as
+    :func:`phases`).  On bin frequencies with ``tau = m S dt`` this is ``sum_j mu^{jS+1} q~^{((j - m) mod N) S}``; off the
+    bins, or at any other ``tau``, it is this formula and no such sum.  ``dtype`` as in :func:`spectral_image`."""
+    a, Q = _weighted(Q, nt, stride, dt, freqs, freq_weights)
+    M = np.asarray(M)
+    dtype = np.dtype(dtype)
+    tau = float(tau)
+    if not np.isfinite(tau):
+        raise ValueError("tau must be finite")
+    f, _, _ = _freqs(nt, stride, dt, freqs)
+    x = f * tau
+    phi = 2.0 * np.pi * (x - np.floor(x))
+    c, d = a * np.cos(phi), a * np.sin(phi)
+    part = lambda z: z.astype(dtype).astype(np.float64)  # noqa: E731
+    s = np.zeros(Q.shape[1:], np.float64)
+    for k in range(a.size):
+        qr, qi, mr, mi = part(Q[k].real), part(Q[k].imag), part(M[k].real), part(M[k].imag)
+        s = s + c[k] * (qr * mr + qi * mi) + d[k] * (qi * mr - qr * mi)
+    return s.astype(dtype)
+
+
+def focusing(E, lags):
+    """``sum_l lag_l^2 |E_l|^2 / sum_l |E_l|^2`` of a gather ``E``, ``(len(lags), ...)``, with ``|.|^2`` summed over the
+    whole image: the energy-weighted mean squared lag, 0 for a gather focused at zero lag, in the units of ``lags``
+    squared.  nan for a gather that is zero everywhere."""
+    lags = np.asarray(lags, np.float64)
+    E = np.asarray(E)
+    if lags.ndim != 1 or E.shape[:1] != lags.shape:
+        raise ValueError("expected one image per lag")
+    e = np.sum(np.abs(E.astype(np.float64)).reshape(lags.size, -1) ** 2, axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(np.sum(lags ** 2 * e) / np.sum(e))

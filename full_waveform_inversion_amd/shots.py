@@ -318,10 +318,15 @@ class _Spectral:
         self.freq_weights, self.wrt, self.illum = freq_weights, wrt, bool(illum)
         self.H = {}
 
-    def adjoint(self, e, shot, residual):
+    @staticmethod
+    def _residual(e, shot, residual):
+        """the host residual as ``adjoint_spectral`` takes it (None: the one the misfit left on the device)"""
         if residual is not None and shot.rec_spread is not None and not shot._on_device(e):
             residual = shot.rec_spread.scatter(residual)
-        e.adjoint_spectral(None if residual is None else np.ascontiguousarray(residual), self.freq_weights)
+        return None if residual is None else np.ascontiguousarray(residual)
+
+    def adjoint(self, e, shot, residual):
+        e.adjoint_spectral(self._residual(e, shot, residual), self.freq_weights)
         if self.illum:
             h = np.asarray(e.fourier_illumination(self.freq_weights, self.wrt), np.float64)
             self.H[id(e)] = self.H[id(e)] + h if id(e) in self.H else h
@@ -422,6 +427,56 @@ def _sweep_shots(engine, shots, ex, objective, device_l2=True, spectral=None):
             engine.primary.gradient_add_from(other)
         return misfit
     return float(sum(one(engine, i) for i in mine))
+
+
+class _Extended(_Spectral):
+    """The adjoint of :func:`extended_image`: ``Engine.adjoint_spectral(residual, image=False)``, then the shot's gather
+    added to its engine's fp64 sum on the host (a pool drives each engine from one thread)."""
+
+    def __init__(self, engine, freq_weights, kind, lags, axis):
+        super().__init__(engine, freq_weights, "slowness2", False)
+        if kind not in ("offset", "time"):
+            raise ValueError("kind must be 'offset' or 'time'")
+        if kind == "offset" and axis is None:
+            raise ValueError("an offset gather needs its axis")
+        self.kind, self.lags, self.axis = kind, np.atleast_1d(lags), axis
+        self.E = {}
+
+    def adjoint(self, e, shot, residual):
+        e.adjoint_spectral(self._residual(e, shot, residual), image=False)
+        if self.kind == "offset":
+            E = e.fourier_offset_images(self.axis, self.lags, self.freq_weights)
+        else:
+            E = e.fourier_lag_images(self.lags, self.freq_weights)
+        E = np.asarray(E, np.float64)
+        self.E[id(e)] = self.E[id(e)] + E if id(e) in self.E else E
+
+    def gather(self, engine, ex):
+        """E of this evaluation summed over shots, engines and ranks (zeros on a rank that owned no shot)"""
+        engs = _engines(engine)
+        E = sum((self.E[id(e)] for e in engs if id(e) in self.E), np.zeros((self.lags.size,) + tuple(engs[0].shape)))
+        return ex.reduce_array(E)
+
+
+def extended_image(engine, model, shots, kind, lags, axis=None, exchange=None, objective=None, freq_weights=None):
+    """``(J, E)``: the misfit of :func:`misfit_and_gradient` and the extended image of the shots at ``model``, summed over
+    shots, pool engines and ranks, ``(len(lags), *shape)`` in fp64 and in the units of
+    ``Engine.fourier_gradient(wrt="slowness2")``.  ``kind="offset"``: ``lags`` are integer subsurface offsets in cells along
+    ``axis`` (``Engine.fourier_offset_images``); ``kind="time"``: ``lags`` are time lags in seconds
+    (``Engine.fourier_lag_images``).  Every shot takes the per-shot path of ``spectral_imaging=True``: forward, residual
+    by ``objective``, then ``Engine.adjoint_spectral(image=False)`` and one streaming pass per lag; the gathers are summed
+    on the host as the Fourier illumination is.  The gradient accumulators are reset and stay zero.  Energy that focuses at
+    zero lag says that ``model`` is kinematically right (``fourier.focusing``).  Engines without the Fourier store raise
+    ``ValueError``."""
+    from .objectives import l2
+    ex = exchange or NoExchange()
+    ext = _Extended(engine, freq_weights, kind, lags, axis)
+    for e in _engines(engine):
+        e.set_model(model)
+        e.reset_gradient()
+    misfit = _sweep_shots(engine, shots, ex, objective or l2, True, ext)
+    J = float(np.asarray(ex.reduce_array(np.array([misfit]))).ravel()[0])
+    return J, ext.gather(engine, ex)
 
 
 def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=None, wrt="velocity",

@@ -42,6 +42,7 @@ extern "C" {
 /* ... and with the Fourier store (fwi_set_fourier_store, fwi_fourier_spectrum, fwi_store_bytes), additive in the same way. */
 /* ... and with spectral imaging on it (fwi_adjoint_spectral, fwi_fourier_image, fwi_fourier_gradient[_vec],
  * fwi_fourier_adjoint_spectrum, fwi_fourier_illumination[_vec]). */
+/* ... and with the extended images (fwi_fourier_offset_image[_vec], fwi_fourier_lag_image[_vec]). */
 #define FWI_ABI_VERSION 14
 
 enum { FWI_F32 = 0, FWI_F64 = 1 };
@@ -555,6 +556,31 @@ int fwi_fourier_gradient_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_weigh
 int fwi_fourier_adjoint_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out);
 int fwi_fourier_illumination(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, void *out);
 int fwi_fourier_illumination_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, int32_t slot);
+
+/* Extended images on the Fourier store: subsurface-offset (Rickett and Sava, 2002) and time-lag (Sava and Fomel, 2006)
+ * common-image gathers of the last fwi_adjoint_spectral, one lag per call, each one streaming pass over the resident Q_k
+ * and M_k (the bytes of one fwi_fourier_gradient call) and no further sweep.  a_k = freq_weights[k] (NULL: ones), w_k the
+ * synthesis weights above, S the image stride, e_a the unit vector of grid axis a (grid order: 0 .. ndim - 1 = z, [y,] x);
+ * both in the units of fwi_fourier_gradient(FWI_WRT_SLOWNESS2), and at zero lag (h = 0, tau = 0) bit-identical to it.
+ * fwi_fourier_offset_image[_vec]: for an integer h in cells, of either sign,
+ *     E_h(x) = -(S / dt^2) sum_k a_k w_k (Re Q_k(x - h e_a) Re M_k(x + h e_a) + Im Q_k(x - h e_a) Im M_k(x + h e_a))
+ * and E_h(x) = 0 wherever x - h e_a or x + h e_a lies outside the grid (its extent n_a, not the padded row of the device
+ * layout).  |h| is not limited; past (n_a - 1) / 2 the image is all zeros.  For any set of frequencies this equals
+ * -(S / dt^2) sum_j mu^{jS+1}(x + h e_a) q~^{jS}(x - h e_a), the band-limited imaging sum of the shifted fields.
+ * fwi_fourier_lag_image[_vec]: for a finite tau in seconds,
+ *     E_tau(x) = -(S / dt^2) sum_k a_k w_k Re(Q_k(x) conj(M_k(x)) exp(-i 2 pi f_k tau))
+ * Where every f_k is a bin of the sampled axis and tau = m S dt, this is the imaging sum with the sampled q~ shifted
+ * circularly by m samples (the forward term delayed by tau).  Off the bins, or at any other tau, it is THIS FORMULA AND
+ * NO SUCH SUM (as fwi_fourier_illumination off the bins); only tau = 0 is the gradient for every frequency set.
+ * `out`: a model-shaped host buffer of the context dtype; `slot`: a vector of fwi_vec_create (pad columns zero).  Neither
+ * the gradient accumulator nor Q_k or M_k is touched, and any number of calls may follow one fwi_adjoint_spectral.
+ * FWI_ESTATE as for fwi_fourier_gradient: the store is off, no fwi_forward(save != 0), no fwi_adjoint_spectral since the
+ * latest one.  FWI_EINVAL, naming the argument: axis outside [0, ndim), tau not finite (or so large that f_k tau is
+ * not), a weight that is not finite, a null `out`, a slot that does not exist.  No reference counterpart. */
+int fwi_fourier_offset_image(fwi_ctx *ctx, int32_t axis, int32_t h, const double *freq_weights, void *out);
+int fwi_fourier_offset_image_vec(fwi_ctx *ctx, int32_t axis, int32_t h, const double *freq_weights, int32_t slot);
+int fwi_fourier_lag_image(fwi_ctx *ctx, double tau, const double *freq_weights, void *out);
+int fwi_fourier_lag_image_vec(fwi_ctx *ctx, double tau, const double *freq_weights, int32_t slot);
 
 /* Elementwise vector operations for a diagonal preconditioner (pad columns of the compact layout stay 0). */
 int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x);               /* y := x * y */

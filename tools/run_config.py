@@ -44,6 +44,11 @@ def main():
                          "the spectral illumination (Engine.fourier_illumination).  `whiten`: weight the per-frequency "
                          "gradients by 1 / (mean power of the observed data at the frequency + 1e-4 of the largest), scaled "
                          "to mean 1 (datafit.whitening_weights; one rank).  Composes with --spectral and --precondition")
+    ap.add_argument("--extended-image", default=None, metavar="offset:AXIS:L | time:DTAU:L",
+                    help="with --fourier-store: the extended image of the final model (shots.extended_image), the 2 L + 1 "
+                         "lags -L .. L of a subsurface-offset gather along AXIS (z, y or x; lags in cells) or of a time-lag "
+                         "gather in steps of DTAU seconds; written to --extended-out with its lags and fourier.focusing")
+    ap.add_argument("--extended-out", default=None, metavar="PATH", help="the .npz file of --extended-image (rank 0 writes)")
     ap.add_argument("--update-form", default="auto", choices=["auto", "increment", "standard"],
                     help="fp32 update form; auto = shots.inversion_engine's choice (increment: 1e-5 end to end)")
     ap.add_argument("--launch-mode", default="auto", choices=["auto", "stream", "graph"])
@@ -139,6 +144,26 @@ def main():
         ap.error("--spectral-whiten takes its weights from this rank's data: it runs on one rank")
     if a.fourier_imaging is not None and a.fourier_store is None:
         ap.error("--fourier-imaging needs --fourier-store FMIN,FMAX (it images on the store's frequencies)")
+    extended = None
+    if a.extended_image is not None:
+        if a.fourier_store is None:
+            ap.error("--extended-image needs --fourier-store FMIN,FMAX (it images on the store's frequencies)")
+        if a.extended_out is None:
+            ap.error("--extended-image needs --extended-out PATH")
+        try:
+            kind, step, half = a.extended_image.split(":")
+            half = int(half)
+            assert kind in ("offset", "time") and half >= 0
+            if kind == "offset":
+                assert step in ("z", "y", "x")
+                extended = ("offset", np.arange(-half, half + 1), step)
+            else:
+                assert np.isfinite(float(step)) and float(step) > 0
+                extended = ("time", float(step) * np.arange(-half, half + 1), None)
+        except (ValueError, AssertionError):
+            ap.error("--extended-image takes offset:AXIS:L (AXIS z, y or x) or time:DTAU:L (DTAU > 0 seconds), L >= 0")
+    elif a.extended_out is not None:
+        ap.error("--extended-out needs --extended-image")
     if a.fourier_imaging == "whiten" and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--fourier-imaging whiten takes its weights from this rank's data: it runs on one rank")
     spectral_band = None
@@ -331,7 +356,7 @@ def main():
                                     bounds=bounds)
             filters_line(obj[0], f_hz)
             return x, lg
-        _, logs = datafit.frequency_continuation(run_band, m0, bands)  # (the band itself is handed on: no taps_of)
+        m_final, logs = datafit.frequency_continuation(run_band, m0, bands)  # (the band itself is handed on: no taps_of)
         log = [{"band_hz": f, "log": lg} for f, lg in zip(bands, logs)]
     elif a.iters > 0 and not a.host_lbfgs:
         pslot = lbfgs_device_slots(5) if eps is not None else None
@@ -349,7 +374,7 @@ def main():
             xs0 = rg.prior_slot(5, pslot, h0) if reg_prior is not None else None
             extra = 0 if xs0 is None else 1
             fg_dev = rg.regularized_fg_device(pool, fg_dev, a.reg_weight, a.regularize, 1.0, reg_eps, xs0, reg_prior)
-        _, _, log = lbfgs_device(e, fg_dev, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
+        m_final, _, log = lbfgs_device(e, fg_dev, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
                                  bounds=bounds, checkpoint=ckpt, resume=a.resume or None, precond_slot=pslot, h0=h0,
                                  extra_slots=extra)
     elif a.iters > 0:
@@ -368,14 +393,23 @@ def main():
         h0 = sh.smoothing_h0(h0_sigma, mask=mute, precond=p_of_run if eps is not None else None) if use_h0 else None
         if a.regularize is not None:
             fg_host = rg.regularized_fg(fg_host, a.reg_weight, a.regularize, 1.0, reg_eps, reg_prior)
-        _, _, log = lbfgs(fg_host, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
+        m_final, _, log = lbfgs(fg_host, m0, maxiter=a.iters, history=5, first_step=0.02 * float(m0.max()),
                           bounds=bounds, dot=e.dot, checkpoint=ckpt, resume=a.resume or None,
                           precond=pc_keep if pc is not None else None, h0=h0)
     else:
         fg1 = fg if a.regularize is None else rg.regularized_fg(fg, a.reg_weight, a.regularize, 1.0, reg_eps, reg_prior)
         J, g = fg1(m0)
+        m_final = m0
         log = [{"iter": 0, "f": J, "gnorm": float(np.sqrt(e.dot(g, g)))}]
     el = time.perf_counter() - t0
+    if extended is not None:  # the gather of the final model, with the misfit and the weights of the last stage
+        from full_waveform_inversion_amd import fourier
+        kind, lags, axis = extended
+        _, E = sh.extended_image(pool, np.asarray(m_final, np.float32), shots, kind, lags, axis, ex, obj[0],
+                                 imaging.get("freq_weights"))
+        if rank == 0:
+            np.savez(a.extended_out, gather=E, lags=lags, kind=kind, axis="" if axis is None else axis,
+                     focusing=fourier.focusing(E, lags))
     if not bands:
         filters_line(obj[0])
     if rank == 0:
