@@ -24,6 +24,7 @@ ABCS = {"sponge": 0, "cpml": 1}
 STORE_DTYPES = {"native": 0, "bf16": 1}
 LAUNCH_MODES = {"auto": 0, "stream": 1, "graph": 2}
 BORN_MODES = {"auto": 0, "scatter": 1, "fused": 2}
+EXT_KINDS = {"offset": 0, "timelag": 1, "time": 1}  # FWI_EXT_OFFSET, FWI_EXT_TIMELAG ("time": the name shots.extended_image uses)
 REG_KINDS = {"tikhonov": 0, "tv": 1}
 MATCH_LMAX = 64  # FWI_MATCH_LMAX
 TT_KMAX = 1024  # FWI_TT_KMAX
@@ -130,6 +131,10 @@ SIGNATURES = {
     "fwi_born_imaging": (C.c_int, [_P, _I32, _P, _I32, _P]),
     "fwi_born_imaging_vec": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "fwi_born_path": (C.c_char_p, [_P]),
+    "fwi_fourier_born": (C.c_int, [_P, _I32, _P, _P, _I32, _P]),
+    "fwi_fourier_born_vec": (C.c_int, [_P, _I32, _I32, _P, _I32, _P]),
+    "fwi_fourier_born_extended": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P]),
+    "fwi_fourier_born_extended_vec": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P]),
     "fwi_mc_score": (C.c_int, [_I32, _I32, _I32, _I32, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P,
                                C.POINTER(_D)]),
     "fwi_mc_forward": (C.c_int, [_I32, _I32, _I32, _I32, _I64, _P, _P, _P]),

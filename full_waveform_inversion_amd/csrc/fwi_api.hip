@@ -32,6 +32,7 @@
 #include "fwi_fourier.h"
 #include "fwi_fimage.h"
 #include "fwi_feximage.h"
+#include "fwi_fbornx.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
 #include "fwi_match.h"
@@ -1389,8 +1390,9 @@ struct Impl {
     // The table of one sweep over N = ceil(nt / S) samples, formed in fp64 and uploaded before the time loop begins (a
     // captured loop then holds launches only): block k, row j = (cos theta_kj, sin theta_kj), theta_kj = 2 pi f_k j S dt
     // with f_k j S dt reduced to its fractional part first; `synthesis`: both times w_k = 1 / N at f_k = 0 and at the
-    // Nyquist frequency 1 / (2 S dt) of the sampled axis, else 2 / N.  The rows from N on stay zero.
-    static int fourier_table(fwi_ctx *ctx, int nt, bool synthesis) {
+    // Nyquist frequency 1 / (2 S dt) of the sampled axis, else 2 / N, times the caller's a_k = fw[k] (nullptr: ones; the
+    // Fourier Born sweeps).  The rows from N on stay zero.
+    static int fourier_table(fwi_ctx *ctx, int nt, bool synthesis, const double *fw = nullptr) {
         const int S = ctx->istride, N = (nt + S - 1) / S, rows = ctx->four_rows, F = (int)ctx->four_freqs.size();
         const double sdt = (double)S * ctx->cfg.dt;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the upload of the sweep before may still read the host copy
@@ -1399,7 +1401,7 @@ struct Impl {
         for (int k = 0; k < F; ++k) {
             const double f = ctx->four_freqs[k];
             const bool edge = f == 0.0 || std::fabs(2.0 * f * sdt - 1.0) <= FOURIER_NYQUIST_RTOL;
-            const double w = synthesis ? (edge ? 1.0 : 2.0) / N : 1.0;
+            const double w = (synthesis ? (edge ? 1.0 : 2.0) / N : 1.0) * (fw ? fw[k] : 1.0);
             for (int j = 0; j < N; ++j) {
                 const double x = f * sdt * j, th = 2.0 * M_PI * (x - std::floor(x));
                 t[((size_t)k * rows + j) * 2] = w * std::cos(th);
@@ -1751,7 +1753,8 @@ struct Impl {
     // the N samples of the last forward); `fw` = nullptr: a_k = 1.  With `tau` (a time-lag image) the table holds 2 F
     // entries instead, C_k = a_k w_k cos phi_k at k and D_k = a_k w_k sin phi_k at F + k, phi_k = 2 pi f_k tau formed in
     // fp64 from the fractional part of f_k tau as fourier_table forms its phases (tau = 0: C_k = a_k w_k, D_k = 0).
-    static int fourier_weights(fwi_ctx *ctx, const double *fw, const double *tau = nullptr) {
+    // `unit`: a_k w_k = 1, the bare phases (cos phi_k, sin phi_k) of an extended Born source (fwi_fbornx.h).
+    static int fourier_weights(fwi_ctx *ctx, const double *fw, const double *tau = nullptr, bool unit = false) {
         const int S = ctx->istride, N = (ctx->nt + S - 1) / S, F = (int)ctx->four_freqs.size();
         const double sdt = (double)S * ctx->cfg.dt;
         if (!ctx->four_w) HIPCHK(ctx, hipMalloc(&ctx->four_w, 2 * FWI_FOURIER_FMAX * sizeof(double)));
@@ -1761,7 +1764,7 @@ struct Impl {
         for (int k = 0; k < F; ++k) {
             const double f = ctx->four_freqs[k];
             const bool edge = f == 0.0 || std::fabs(2.0 * f * sdt - 1.0) <= FOURIER_NYQUIST_RTOL;
-            a[k] = (fw ? fw[k] : 1.0) * ((edge ? 1.0 : 2.0) / N);
+            a[k] = unit ? 1.0 : (fw ? fw[k] : 1.0) * ((edge ? 1.0 : 2.0) / N);
             if (tau) {
                 const double x = f * *tau, th = 2.0 * M_PI * (x - std::floor(x));
                 a[F + k] = a[k] * std::sin(th);
@@ -1848,19 +1851,32 @@ struct Impl {
     //  - ckpt_interval K > 0: segment by segment in ascending order, the forward state is restored from its snapshot and
     //    the segment's q^n are recomputed into the slot buffer by the recomputation fields of the adjoint (fwd, fwv, fwx,
     //    the forward set of memory variables); the Born field then sweeps those slots in u[], vf and the main set.
-    static int born(fwi_ctx *ctx, int32_t wrt, const T *dm_host, const void *dm_dev, bool fused, T *seis_out) {
+    //  - Fourier store (`spec`: fwi_fourier_born*, the 2 F coefficient volumes the source is synthesised from, Q_k or the
+    //    extended spectrum P_k of fwi_fbornx.h; `a`: the a_k folded into the synthesis table): batch by batch in
+    //    ascending order the synthesis rebuilds the batch's samples in their ring slots, which the stored steps then read
+    //    as they read a native slot.  Neither dm_host nor dm_dev (the extended sweep): dm = 1, w = -c^2 S.
+    static int born(fwi_ctx *ctx, int32_t wrt, const T *dm_host, const void *dm_dev, bool fused, T *seis_out,
+                    const T *spec = nullptr, const double *a = nullptr) {
         const GridDesc &g = ctx->gd;
         const int nt = ctx->nt, nrec = ctx->nrec, S = ctx->istride, K = ctx->ckpt;
         hipStream_t s = ctx->stream;
         int rc;
         if (!ctx->born_w) HIPCHK(ctx, hipMalloc(&ctx->born_w, (size_t)g.npts * sizeof(T)));
         if (dm_host && (rc = upload_compact(ctx, ctx->born_w, dm_host))) return rc;
+        if (!dm_host && !dm_dev) {  // ones, pad columns zero: 1 / (0 + 1)
+            HIPCHK(ctx, hipMemsetAsync(ctx->born_w, 0, (size_t)g.npts * sizeof(T), s));
+            HIPCHK(ctx, launch_vec_recip<T>(g, (T *)ctx->born_w, 1.0, 1.0, s));
+        }
         if (S > 1)
-            HIPCHK(ctx, launch_born_weight_strided<T>(g, (const T *)(dm_host ? ctx->born_w : dm_dev), (const T *)ctx->c_dev,
+            HIPCHK(ctx, launch_born_weight_strided<T>(g, (const T *)(dm_dev ? dm_dev : ctx->born_w), (const T *)ctx->c_dev,
                                                       (T *)ctx->born_w, wrt == FWI_WRT_VELOCITY, S, s));
         else
-            HIPCHK(ctx, launch_born_weight<T>(g, (const T *)(dm_host ? ctx->born_w : dm_dev), (const T *)ctx->c_dev,
+            HIPCHK(ctx, launch_born_weight<T>(g, (const T *)(dm_dev ? dm_dev : ctx->born_w), (const T *)ctx->c_dev,
                                               (T *)ctx->born_w, wrt == FWI_WRT_VELOCITY, s));
+        if (spec) {
+            ctx->four_sweep = true;
+            if ((rc = fourier_table(ctx, nt, true, a))) return rc;
+        }
         const fwi_ctx::PointSet nobody;
         const fwi_ctx::PointSet *share = &nobody;  // bf16 store: the sources, injected with the share's amplitudes
         const T *share_amp = nullptr;
@@ -1933,6 +1949,16 @@ struct Impl {
                 if (rc || (rc = born_steps(n0, cnt, [&](int n) -> const void * { return st.seg_slot(n, n0); }))) return rc;
             }
             adopt_recompute(ctx, fw, fspare);
+        } else if (spec) {
+            // (born_steps' fused path takes all the steps it is given in one run_steps call when S = 1: a batch at a time)
+            const int B = ctx->four_batch, R = B + 1, N = (nt + S - 1) / S;
+            for (int j0 = 0; j0 < N; j0 += B) {
+                const int nb = std::min(B, N - j0), n0 = j0 * S, n1 = std::min(nt, (j0 + nb) * S);
+                HIPCHK(ctx, launch_fourier_synthesise<T>(st.ring, spec, g.npts, R, j0 % R, j0, nb,
+                                                         (const double *)ctx->four_tw, ctx->four_rows,
+                                                         (int)ctx->four_freqs.size(), s));
+                if ((rc = born_steps(n0, n1 - n0, [&](int n) -> const void * { return st.ring_slot(n); }))) return rc;
+            }
         } else {
             if ((rc = born_steps(0, nt, [&](int n) -> const void * { return st.slot(n); }))) return rc;
         }
@@ -1959,6 +1985,35 @@ struct Impl {
         ctx->have_dev_residual = true;
         ctx->resid_pts_in = (nrec && sp.npts) ? fwi_ctx::RESID_PTS_D : fwi_ctx::RESID_PTS_NONE;
         return FWI_OK;
+    }
+
+    // Extended Born modelling (fwi_fourier_born_extended[_vec]): the spectrum P_k of the gather goes, one lag per launch
+    // (fwi_fbornx.h), into the 2 F volumes that hold M_k, which it destroys; the Born sweep then synthesises its source
+    // from P_k with w = -c^2 S.  The images come from the host (`images_host`, nlag model-shaped arrays one behind the
+    // other, each through born_w) or from device vectors (`images_dev`).  `axis`: 0 = z, 1 = y, 2 = x of the GridDesc.
+    static int fourier_born_extended(fwi_ctx *ctx, bool lag, int axis, int nlag, const int32_t *offsets, const double *taus,
+                                     const T *images_host, const void *const *images_dev, const double *a, bool fused,
+                                     T *seis_out) {
+        const GridDesc &g = ctx->gd;
+        const int F = (int)ctx->four_freqs.size();
+        int rc = fourier_adjoint_alloc(ctx);
+        if (rc) return rc;
+        ctx->have_m = false;
+        if (!ctx->born_w) HIPCHK(ctx, hipMalloc(&ctx->born_w, (size_t)g.npts * sizeof(T)));
+        const size_t nlog = (size_t)g.nz * g.ny * g.nx;
+        for (int l = 0; l < nlag; ++l) {
+            const T *img = images_dev ? (const T *)images_dev[l] : (const T *)ctx->born_w;
+            if (images_host && (rc = upload_compact(ctx, ctx->born_w, images_host + l * nlog))) return rc;
+            if (lag) {
+                if ((rc = fourier_weights(ctx, nullptr, &taus[l], true))) return rc;
+                HIPCHK(ctx, launch_fbornx_lag<T>((T *)ctx->four_adj, (const T *)ctx->four_acc, img,
+                                                 (const double *)ctx->four_w, g.npts, F, l > 0, ctx->stream));
+            } else {
+                HIPCHK(ctx, launch_fbornx_offset<T>(g, (T *)ctx->four_adj, (const T *)ctx->four_acc, img, F, axis,
+                                                    (int64_t)offsets[l], l > 0, ctx->stream));
+            }
+        }
+        return born(ctx, FWI_WRT_SLOWNESS2, nullptr, nullptr, fused, seis_out, (const T *)ctx->four_adj, a);
     }
 
     // illumination accumulator += sum of the squares of `nslots` store slots (no-op while illumination is disabled)
@@ -3514,6 +3569,106 @@ int fwi_born_imaging_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, 
 }
 
 const char *fwi_born_path(const fwi_ctx *ctx) { return ctx ? ctx->born_path : ""; }
+
+static int fourier_callable(fwi_ctx *ctx, const char *who, bool need_m);
+static int fourier_weight_args(fwi_ctx *ctx, const char *who, const double *fw, bool nonneg);
+
+// the argument and state checks the Born calls on the Fourier store share; *fused as born_callable sets it
+static int fourier_born_callable(fwi_ctx *ctx, const char *who, int32_t mode, const double *fw, bool *fused) {
+    if (mode != FWI_BORN_AUTO && mode != FWI_BORN_SCATTER && mode != FWI_BORN_FUSED)
+        return ctx->fail(FWI_EINVAL, "%s: unknown mode %d", who, (int)mode);
+    if (mode == FWI_BORN_FUSED && !born_fused_supported(ctx))
+        return ctx->fail(FWI_EINVAL, "%s: FWI_BORN_FUSED: this context has no fused Born path (3-D fp32 O(8) stream "
+                                     "kernel without the CPML only)", who);
+    *fused = mode == FWI_BORN_FUSED || (mode == FWI_BORN_AUTO && BORN_AUTO_IS_FUSED && born_fused_supported(ctx));
+    if (int rc = fourier_callable(ctx, who, false)) return rc;
+    return fourier_weight_args(ctx, who, fw, false);
+}
+
+// `dm_host`: fwi_fourier_born, else the device vector `dm_dev` of fwi_fourier_born_vec
+static int fourier_born(fwi_ctx *ctx, const char *who, int32_t wrt, const void *dm_host, const void *dm_dev,
+                        const double *fw, int32_t mode, void *seis_out) {
+    if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
+        return ctx->fail(FWI_EINVAL, "%s: unknown parametrisation %d", who, (int)wrt);
+    bool fused = false;
+    if (int rc = fourier_born_callable(ctx, who, mode, fw, &fused)) return rc;
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH(ctx, Impl<float>::born(ctx, wrt, (const float *)dm_host, dm_dev, fused, (float *)seis_out,
+                                           (const float *)ctx->four_acc, fw),
+                    Impl<double>::born(ctx, wrt, (const double *)dm_host, dm_dev, fused, (double *)seis_out,
+                                       (const double *)ctx->four_acc, fw));
+}
+
+int fwi_fourier_born(fwi_ctx *ctx, int32_t wrt, const void *dm_host, const double *freq_weights, int32_t mode,
+                     void *seis_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!dm_host) return ctx->fail(FWI_EINVAL, "fwi_fourier_born: null model perturbation");
+    return fourier_born(ctx, "fwi_fourier_born", wrt, dm_host, nullptr, freq_weights, mode, seis_out);
+}
+
+int fwi_fourier_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, const double *freq_weights, int32_t mode,
+                         void *seis_out) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, v, slot);
+    return fourier_born(ctx, "fwi_fourier_born_vec", wrt, nullptr, v, freq_weights, mode, seis_out);
+}
+
+// `images_host`: fwi_fourier_born_extended, else the vector slots `slots` of fwi_fourier_born_extended_vec
+static int fourier_born_extended(fwi_ctx *ctx, const char *who, int32_t kind, int32_t axis, int32_t nlag,
+                                 const int32_t *offsets, const double *taus, const void *images_host,
+                                 const int32_t *slots, const double *fw, int32_t mode, void *seis_out) {
+    if (kind != FWI_EXT_OFFSET && kind != FWI_EXT_TIMELAG)
+        return ctx->fail(FWI_EINVAL, "%s: unknown kind %d", who, (int)kind);
+    const bool lag = kind == FWI_EXT_TIMELAG;
+    if (nlag < 1) return ctx->fail(FWI_EINVAL, "%s: nlag=%d is below 1", who, (int)nlag);
+    if (lag ? !taus : !offsets) return ctx->fail(FWI_EINVAL, "%s: null %s", who, lag ? "taus" : "offsets");
+    if (!lag && (axis < 0 || axis >= ctx->gd.ndim))
+        return ctx->fail(FWI_EINVAL, "%s: axis=%d outside [0, %d)", who, (int)axis, ctx->gd.ndim);
+    std::vector<const void *> dev;
+    for (int l = 0; slots && l < nlag; ++l) {
+        dev.push_back(vec_slot(ctx, slots[l]));
+        if (!dev.back())
+            return ctx->fail(FWI_EINVAL, "%s: slots[%d]: vector slot %d does not exist", who, l, (int)slots[l]);
+    }
+    for (int l = 0; l < nlag; ++l) {
+        if (lag && !std::isfinite(taus[l])) return ctx->fail(FWI_EINVAL, "%s: taus[%d] is not finite", who, l);
+        for (int m = 0; m < l; ++m)
+            if (lag ? taus[m] == taus[l] : offsets[m] == offsets[l])
+                return ctx->fail(FWI_EINVAL, "%s: %s[%d] repeats %s[%d]", who, lag ? "taus" : "offsets", l,
+                                 lag ? "taus" : "offsets", m);
+    }
+    bool fused = false;
+    if (int rc = fourier_born_callable(ctx, who, mode, fw, &fused)) return rc;
+    for (int l = 0; lag && l < nlag; ++l)
+        for (double f : ctx->four_freqs)
+            if (!std::isfinite(f * taus[l]))
+                return ctx->fail(FWI_EINVAL, "%s: taus[%d]=%g s leaves no finite phase at %g Hz", who, l, taus[l], f);
+    (void)hipSetDevice(ctx->cfg.device);
+    const int ax = lag ? 0 : axis == ctx->gd.ndim - 1 ? 2 : ctx->gd.ndim == 3 ? axis : 0;  // grid order z, [y,] x
+    const void *const *d = slots ? dev.data() : nullptr;
+    return DISPATCH(ctx, Impl<float>::fourier_born_extended(ctx, lag, ax, nlag, offsets, taus, (const float *)images_host, d,
+                                                            fw, fused, (float *)seis_out),
+                    Impl<double>::fourier_born_extended(ctx, lag, ax, nlag, offsets, taus, (const double *)images_host, d,
+                                                        fw, fused, (double *)seis_out));
+}
+
+int fwi_fourier_born_extended(fwi_ctx *ctx, int32_t kind, int32_t axis, int32_t nlag, const int32_t *offsets,
+                              const double *taus, const void *images_host, const double *freq_weights, int32_t mode,
+                              void *seis_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!images_host) return ctx->fail(FWI_EINVAL, "fwi_fourier_born_extended: null images");
+    return fourier_born_extended(ctx, "fwi_fourier_born_extended", kind, axis, nlag, offsets, taus, images_host, nullptr,
+                                 freq_weights, mode, seis_out);
+}
+
+int fwi_fourier_born_extended_vec(fwi_ctx *ctx, int32_t kind, int32_t axis, int32_t nlag, const int32_t *offsets,
+                                  const double *taus, const int32_t *slots, const double *freq_weights, int32_t mode,
+                                  void *seis_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!slots) return ctx->fail(FWI_EINVAL, "fwi_fourier_born_extended_vec: null slots");
+    return fourier_born_extended(ctx, "fwi_fourier_born_extended_vec", kind, axis, nlag, offsets, taus, nullptr, slots,
+                                 freq_weights, mode, seis_out);
+}
 
 int fwi_comm_unique_id(void *id_out) {
     static_assert(sizeof(ncclUniqueId) == FWI_UNIQUE_ID_BYTES, "ncclUniqueId size");

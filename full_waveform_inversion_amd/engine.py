@@ -715,6 +715,77 @@ class Engine:
         call = self._born_call(operator, True)
         return self._born(lambda w, m, o: call(self._c, w, int(slot), m, o), wrt, mode, download)
 
+    # -- Born and extended Born modelling on the Fourier store (include/fwi.h fwi_fourier_born) -------
+    def fourier_born(self, dm, freq_weights=None, wrt="velocity", mode="auto", download=True):
+        """:meth:`born` ``(operator="imaging")`` of a Fourier-store engine, which refuses :meth:`born` itself: the Born
+        data ``J_a dm`` as ``(nt, nrec)`` with the scattering source synthesised from the coefficients ``Q_k`` of the last
+        ``forward(save=True)``, ``q~_a = sum_k a_k w_k Re(Q_k exp(i theta_kj))``, ``a = freq_weights`` (None: 1;
+        ``fwi_fourier_born``).  With ``a = 1`` the exact transpose of ``adjoint(image=True)`` + ``gradient`` on this
+        engine, with any ``a`` that of ``adjoint_spectral`` + ``fourier_gradient(a)``: ``J_a^T J_a`` is symmetric positive
+        semi-definite.  ``Q_k``, ``M_k`` and the gradient accumulator are not touched; the data stay on the device as the
+        residual of the next ``adjoint(None)`` or ``adjoint_spectral(None)``.  ``mode``, ``download``: as :meth:`born`."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        dm = self._host(dm, self.shape)
+        call = self._lib.fwi_fourier_born
+        return self._born(lambda w, m, o: call(self._c, w, dm.ctypes.data_as(C.c_void_p), fwp, m, o), wrt, mode, download)
+
+    def fourier_born_vec(self, slot, freq_weights=None, wrt="velocity", mode="auto", download=True):
+        """:meth:`fourier_born` with ``dm`` read from the device vector ``slot``."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        call = self._lib.fwi_fourier_born_vec
+        return self._born(lambda w, m, o: call(self._c, w, int(slot), fwp, m, o), wrt, mode, download)
+
+    def _ext_lags(self, kind, lags, axis):
+        """(kind code, grid axis, n, offsets pointer, taus pointer, keep-alive) of an extended Born call"""
+        if kind not in _lib.EXT_KINDS:
+            raise ValueError("kind must be 'offset' or 'timelag'")
+        lags = np.atleast_1d(lags)
+        if lags.ndim != 1 or lags.size < 1:
+            raise ValueError("lags must hold at least one lag")
+        if kind == "offset":
+            if axis is None:
+                raise ValueError("axis is required for kind='offset'")
+            if not np.all(np.equal(np.mod(lags, 1), 0)):
+                raise ValueError("the lags of kind='offset' are whole numbers of cells")
+            arr = np.ascontiguousarray(lags, dtype=np.int32)
+            return _lib.EXT_KINDS[kind], self._axis(axis), arr.size, arr.ctypes.data_as(C.c_void_p), None, arr
+        arr = np.ascontiguousarray(lags, dtype=np.float64)
+        return _lib.EXT_KINDS[kind], 0, arr.size, None, arr.ctypes.data_as(C.c_void_p), arr
+
+    def fourier_born_extended(self, kind, lags, images, axis=None, freq_weights=None, mode="auto", download=True):
+        """Extended Born modelling (demigration) on a Fourier-store engine: the data ``J_ext E`` as ``(nt, nrec)`` of the
+        gather ``images`` (``(len(lags), *shape)``, in the units of :meth:`fourier_offset_images` /
+        :meth:`fourier_lag_images`), defined as the exact transpose of those calls (``fwi_fourier_born_extended``):
+        ``<J_ext E, r> = sum_l <E_l, image_l(r)>`` for every residual ``r``.  ``kind="offset"``: ``lags`` are integers in
+        cells along ``axis`` (an index in grid order or ``"z"`` / ``"y"`` / ``"x"``); ``kind="timelag"`` (or ``"time"``,
+        as :func:`shots.extended_image` names it): ``lags`` are seconds.  The extended scattering spectrum ``P_k(y) = sum_l E_l(y - h_l e) Q_k(y - 2 h_l e)`` (time lag:
+        ``E_l Q_k exp(-i 2 pi f_k tau_l)``) is written INTO THE ARRAYS THAT HOLD ``M_k``: :meth:`fourier_gradient`, the
+        extended images and :meth:`fourier_adjoint_spectrum` are refused until the next :meth:`adjoint_spectral`.  The
+        sweep then injects ``S (-c^2) sum_k a_k w_k Re(P_k exp(i theta_kj))``.  With the single lag 0 and
+        ``images[0] = dm`` it equals ``fourier_born(dm, wrt="slowness2")`` to round-off.  The data stay on the device as
+        the residual of the next ``adjoint_spectral(None)``."""
+        k, ax, n, op, tp, _lags = self._ext_lags(kind, lags, axis)
+        fwp, _keep = self._freq_weights(freq_weights)
+        images = self._host(images, (n,) + self.shape)
+        call = self._lib.fwi_fourier_born_extended
+        out = np.zeros((self._nt, self._nrec), self.dtype) if download else None
+        self._chk(call(self._c, k, ax, n, op, tp, images.ctypes.data_as(C.c_void_p), fwp, _lib.BORN_MODES[mode],
+                       out.ctypes.data_as(C.c_void_p) if download else None))
+        return out
+
+    def fourier_born_extended_vec(self, kind, lags, slots, axis=None, freq_weights=None, mode="auto", download=True):
+        """:meth:`fourier_born_extended` with the gather read from the device vectors ``slots``, one per lag."""
+        k, ax, n, op, tp, _lags = self._ext_lags(kind, lags, axis)
+        fwp, _keep = self._freq_weights(freq_weights)
+        sl = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int32)
+        if sl.shape != (n,):
+            raise ValueError("slots must hold one vector slot per lag, shape (%d,)" % n)
+        out = np.zeros((self._nt, self._nrec), self.dtype) if download else None
+        self._chk(self._lib.fwi_fourier_born_extended_vec(self._c, k, ax, n, op, tp, sl.ctypes.data_as(C.c_void_p), fwp,
+                                                          _lib.BORN_MODES[mode],
+                                                          out.ctypes.data_as(C.c_void_p) if download else None))
+        return out
+
     @property
     def born_path(self):
         """Name of the path the last Born sweep took ("scatter" or "fused"; "none" before the first)."""

@@ -238,6 +238,76 @@ def lag_image(Q, M, nt, stride, dt, freqs, tau, freq_weights=None, dtype=np.floa
     return s.astype(dtype)
 
 
+# -- Born and extended Born modelling (fwi_fourier_born, fwi_fourier_born_extended; csrc/fwi_fbornx.hip) ---------------
+#
+# The transposes of the imaging paths above take their scattering source from the coefficients.  The transpose of the
+# band-limited imaging sum with the weights ``a`` reads ``q~_a``, the synthesis with ``a_k w_k`` in the place of ``w_k``.
+# The transpose of an extended image moves the shift onto the source: with ``y = x + h e`` the pairing
+# ``mu(x + h e) E(x) q~(x - h e)`` is ``mu(y) E(y - h e) q~(y - 2 h e)``, so the spectrum of the extended source is
+# ``P_k(y) = E(y - h e) Q_k(y - 2 h e)``; a delay of the forward term by ``tau`` gives ``P_k = E Q_k exp(-i 2 pi f_k tau)``.
+
+def born_source(Q, nt, stride, dt, freqs, freq_weights=None, dtype=np.float64):
+    """The sampled scattering term ``q~_a^{jS} = sum_k a_k w_k (Re Q_k cos theta_kj - Im Q_k sin theta_kj)`` of
+    ``Engine.fourier_born`` as ``(N, ...)`` in ``dtype``; ``a = freq_weights`` (None: 1, then this is :func:`synthesise`).
+    ``dtype`` restates the device's arithmetic: the coefficients are held in ``dtype``, the sums run in fp64 and every
+    sample is rounded to ``dtype`` once."""
+    a, Q = _weighted(Q, nt, stride, dt, freqs, freq_weights)
+    th = phases(nt, stride, dt, freqs)
+    dtype = np.dtype(dtype)
+    re, im = Q.real.astype(dtype).astype(np.float64), Q.imag.astype(dtype).astype(np.float64)
+    out = np.tensordot((a[:, None] * np.cos(th)).T, re, axes=1) - np.tensordot((a[:, None] * np.sin(th)).T, im, axes=1)
+    return out.astype(dtype)
+
+
+def extended_source(Q, images, kind, lags, nt, stride, dt, freqs, axis=None, dtype=np.float64):
+    """The extended scattering spectrum ``P_k`` of ``Engine.fourier_born_extended`` as a complex ``(F, ...)`` array from the
+    gather ``images``, ``(len(lags), ...)``.  ``kind="offset"``: ``P_k(y) = sum_l E_l(y - h_l e) Q_k(y - 2 h_l e)`` over the
+    integer lags whose two shifted cells lie in the grid (``axis``: the model axis, 0 = the first after the frequencies);
+    ``kind="timelag"``: ``P_k = sum_l E_l Q_k exp(-i 2 pi f_k tau_l)``, the phase from the fractional part of ``f_k tau``.
+    ``born_source(P, ...)`` of the result, times ``-c^2 S``, is the scattering source of the sweep.  ``dtype`` restates the
+    device's arithmetic: images, ``Q`` and ``P`` are held in ``dtype``, each lag's product is formed in fp64 and added to
+    ``P`` with one rounding."""
+    f, _, _ = _freqs(nt, stride, dt, freqs)
+    Q = np.asarray(Q)
+    E = np.asarray(images)
+    lags = np.atleast_1d(lags)
+    if Q.shape[0] != f.size:
+        raise ValueError("expected one coefficient array per frequency")
+    if E.shape != (lags.size,) + Q.shape[1:]:
+        raise ValueError("expected one image per lag, shape %s" % ((lags.size,) + Q.shape[1:],))
+    if kind not in ("offset", "timelag"):
+        raise ValueError("kind must be 'offset' or 'timelag'")
+    dtype = np.dtype(dtype)
+    part = lambda z: np.asarray(z).astype(dtype).astype(np.float64)  # noqa: E731
+    qr, qi = part(Q.real), part(Q.imag)
+    pr, pi = np.zeros(Q.shape, dtype), np.zeros(Q.shape, dtype)
+    for l, lag in enumerate(lags):
+        e = part(E[l])
+        if kind == "timelag":
+            if not np.isfinite(lag):
+                raise ValueError("tau must be finite")
+            x = f * float(lag)
+            phi = (2.0 * np.pi * (x - np.floor(x))).reshape((-1,) + (1,) * e.ndim)
+            pr = (pr.astype(np.float64) + e * (qr * np.cos(phi) + qi * np.sin(phi))).astype(dtype)
+            pi = (pi.astype(np.float64) + e * (qi * np.cos(phi) - qr * np.sin(phi))).astype(dtype)
+            continue
+        ax, h = int(axis), int(lag)
+        if not 0 <= ax < e.ndim:
+            raise ValueError("axis %d outside [0, %d)" % (ax, e.ndim))
+        n = e.shape[ax]
+        if 2 * abs(h) >= n:
+            continue
+        # the cells y with y, y - h and y - 2 h in [0, n): max(0, 2 h) <= y_a < n + min(0, 2 h)
+        m = n - 2 * abs(h)
+        cut = lambda lo, lead: (slice(None),) * (ax + lead) + (slice(lo, lo + m),)  # noqa: E731
+        y0 = max(0, 2 * h)
+        es = e[cut(y0 - h, 0)]
+        dst, src = cut(y0, 1), cut(y0 - 2 * h, 1)
+        pr[dst] = (pr[dst].astype(np.float64) + es * qr[src]).astype(dtype)
+        pi[dst] = (pi[dst].astype(np.float64) + es * qi[src]).astype(dtype)
+    return pr + 1j * pi
+
+
 def focusing(E, lags):
     """``sum_l lag_l^2 |E_l|^2 / sum_l |E_l|^2`` of a gather ``E``, ``(len(lags), ...)``, with ``|.|^2`` summed over the
     whole image: the energy-weighted mean squared lag, 0 for a gather focused at zero lag, in the units of ``lags``

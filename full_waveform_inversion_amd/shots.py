@@ -68,6 +68,13 @@ class Shot:
             return d
         return self.rec_spread.gather(d)
 
+    def fourier_born(self, engine, dm, freq_weights=None, wrt="velocity", download=True):
+        """:meth:`born` on an engine that keeps the Fourier store: ``Engine.fourier_born(dm, freq_weights, wrt)``"""
+        d = engine.fourier_born(dm, freq_weights, wrt, download=download)
+        if d is None or self._on_device(engine) or self.rec_spread is None:
+            return d
+        return self.rec_spread.gather(d)
+
     def _residual_stays(self, engine):
         """``engine.born`` leaves exactly this shot's ``J dm`` on the device as the residual of ``adjoint(None)``"""
         return getattr(engine, "born_leaves_residual", False) and (self.rec_spread is None or self._on_device(engine))
@@ -479,6 +486,67 @@ def extended_image(engine, model, shots, kind, lags, axis=None, exchange=None, o
     return J, ext.gather(engine, ex)
 
 
+def _extended_born_one(e, s, kind, lags, images, axis, freq_weights, download):
+    """``J_ext,s E`` of one shot after its ``forward(save=True)``, per point where the shot has off-grid receivers"""
+    d = e.fourier_born_extended(kind, lags, images, axis, freq_weights, download=download)
+    return d if d is None or s._on_device(e) or s.rec_spread is None else s.rec_spread.gather(d)
+
+
+def extended_born(engine, model, shots, kind, lags, images, axis=None, exchange=None, freq_weights=None):
+    """Extended Born modelling (demigration) of the gather ``images``, ``(len(lags), *shape)`` in the units of
+    :func:`extended_image`: the per-shot data ``J_ext,s E`` as a list indexed like ``shots`` (None for the shots of other
+    ranks), each ``(nt, nrec)``.  ``kind``, ``lags``, ``axis`` as in :func:`extended_image`; per shot ``forward(save=True)``
+    and ``Engine.fourier_born_extended``.  ``model=None`` keeps the model the engines hold.  Engines without the Fourier
+    store raise ``ValueError``."""
+    ex = exchange or NoExchange()
+    _Extended(engine, freq_weights, kind, lags, axis)  # (the argument checks)
+    for e in _engines(engine):
+        if model is not None:
+            e.set_model(model)
+    out = [None] * len(shots)
+
+    def one(e, i):
+        shots[i].forward(e, save=True)
+        out[i] = _extended_born_one(e, shots[i], kind, lags, images, axis, freq_weights, True)
+
+    mine = partition_shots(len(shots), ex.rank, ex.world)
+    if isinstance(engine, EnginePool):
+        engine.map_shots(mine, one)
+    else:
+        for i in mine:
+            one(engine, i)
+    return out
+
+
+def extended_hvp(engine, model, shots, kind, lags, images, axis=None, exchange=None, freq_weights=None):
+    """``sum_s J_ext,s^T J_ext,s E`` as ``(len(lags), *shape)`` in fp64, summed over shots, pool engines and ranks as
+    :func:`extended_image` sums its gather: the normal operator of extended least-squares migration, symmetric positive
+    semi-definite, which ``newton.cg`` inverts for a gather.  Per shot ``forward(save=True)``,
+    ``Engine.fourier_born_extended`` (the data stay on the device), ``Engine.adjoint_spectral(None, image=False)`` and one
+    streaming pass per lag: three sweeps per shot and product.  ``freq_weights`` weigh both operators.  ``model=None``
+    keeps the model the engines hold.  The gradient accumulators are not touched."""
+    ex = exchange or NoExchange()
+    ext = _Extended(engine, freq_weights, kind, lags, axis)
+    for e in _engines(engine):
+        if model is not None:
+            e.set_model(model)
+
+    def one(e, i):
+        s = shots[i]
+        s.forward(e, save=True)
+        stays = s._residual_stays(e)
+        d = _extended_born_one(e, s, kind, lags, images, axis, freq_weights, not stays)
+        ext.adjoint(e, s, None if stays else d)
+
+    mine = partition_shots(len(shots), ex.rank, ex.world)
+    if isinstance(engine, EnginePool):
+        engine.map_shots(mine, one)
+    else:
+        for i in mine:
+            one(engine, i)
+    return ext.gather(engine, ex)
+
+
 def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=None, wrt="velocity",
                                objective=None, device_l2=True, illum_slot=None, spectral_imaging=False,
                                freq_weights=None):
@@ -509,10 +577,11 @@ def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=No
     return misfit
 
 
-def _hvp_sweep(engine, shots, ex, born_one, objective=None):
+def _hvp_sweep(engine, shots, ex, born_one, objective=None, spectral=None):
     """forward(save) + Born + adjoint(imaging) of this rank's shots; ``born_one(e, s, download)`` applies J_s.  With a
     ``datafit.WeightedL2`` objective its weight ``W_s = B M_s^2 B`` acts on the Born data between the two: on the device
-    where the residual stays there and the engine has ``residual_weight``, else through the host twin."""
+    where the residual stays there and the engine has ``residual_weight``, else through the host twin.  ``spectral``
+    (:class:`_Spectral`): the adjoint is its spectral one."""
     from .datafit import WeightedL2
     if objective is not None and not isinstance(objective, WeightedL2):
         raise ValueError("objective must be a datafit.WeightedL2 (or None: plain least squares)")
@@ -524,10 +593,17 @@ def _hvp_sweep(engine, shots, ex, born_one, objective=None):
             born_one(e, s, False)
             if objective is not None:
                 e.residual_weight(s.weights, objective.taps)
-            e.adjoint(None)
+            if spectral is not None:
+                spectral.adjoint(e, s, None)
+            else:
+                e.adjoint(None)
         else:
             d = born_one(e, s, True)
-            s.adjoint(e, d if objective is None else objective.normal(d, s.weights))
+            r = d if objective is None else objective.normal(d, s.weights)
+            if spectral is not None:
+                spectral.adjoint(e, s, r)
+            else:
+                s.adjoint(e, r)
 
     mine = partition_shots(len(shots), ex.rank, ex.world)
     if isinstance(engine, EnginePool):
@@ -539,7 +615,24 @@ def _hvp_sweep(engine, shots, ex, born_one, objective=None):
             one(engine, i)
 
 
-def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity", objective=None):
+def _fourier_hvp(engine, freq_weights, spectral_imaging, wrt):
+    """(the engines keep the Fourier store, the :class:`_Spectral` of the product or None).  On Fourier engines the Born
+    operator is ``fourier_born`` with the weights of the adjoint that follows it: ``adjoint`` (unit weights) or, with
+    ``spectral_imaging``, ``adjoint_spectral(freq_weights)``."""
+    four = all(getattr(e, "fourier_freqs", None) is not None for e in _engines(engine))
+    if not four:
+        if freq_weights is not None or spectral_imaging:
+            raise ValueError("freq_weights and spectral_imaging need engines that keep the Fourier store "
+                             "(Engine(fourier=freqs))")
+        return False, None
+    if freq_weights is not None and not spectral_imaging:
+        raise ValueError("freq_weights needs spectral_imaging=True: adjoint(image) transposes the Born operator of unit "
+                         "weights only")
+    return True, _Spectral(engine, freq_weights, wrt, False) if spectral_imaging else None
+
+
+def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity", objective=None, freq_weights=None,
+                     spectral_imaging=False):
     """Gauss-Newton Hessian-vector product ``H v = sum_s J_s^T J_s v`` at ``model`` (with ``objective`` a
     ``datafit.WeightedL2``: ``sum_s J_s^T W_s J_s v``, ``W_s = B M_s^2 B``), summed over all ranks: ``v`` and
     the result are model-shaped and in the parametrisation ``wrt``.  Per shot ``forward(save=True)``, ``born``,
@@ -548,26 +641,38 @@ def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity", obj
     ``adjoint`` + ``gradient``: H is symmetric positive semi-definite on every engine -- ``image_stride``, the bf16
     store and checkpointing included -- and is today's product, bit for bit, on a plain one.
     OVERWRITES the gradient accumulator of the engine(s) (``reset_gradient`` first, like :func:`misfit_and_gradient`).
-    ``model=None`` keeps the model the engines already hold.  The shots need no observed data."""
+    ``model=None`` keeps the model the engines already hold.  The shots need no observed data.
+
+    Engines that keep the Fourier store (``fourier_freqs`` is not None): J is ``Engine.fourier_born``, the transpose of
+    ``adjoint`` on that store; with ``spectral_imaging=True`` the product is ``J_a^T J_a`` through
+    ``fourier_born(v, freq_weights)`` and ``adjoint_spectral(freq_weights)``, ``a = freq_weights`` (None: 1).  On every
+    other engine the two arguments must keep their defaults and nothing changes."""
     ex = exchange or NoExchange()
     engs = _engines(engine)
+    four, spectral = _fourier_hvp(engine, freq_weights, spectral_imaging, wrt)
     for e in engs:
         if model is not None:
             e.set_model(model)
         e.reset_gradient()
-    _hvp_sweep(engine, shots, ex, lambda e, s, download: s.born(e, v, wrt, download=download, operator="imaging"),
-               objective)
+    if four:
+        born_one = lambda e, s, download: s.fourier_born(e, v, freq_weights, wrt, download=download)  # noqa: E731
+    else:
+        born_one = lambda e, s, download: s.born(e, v, wrt, download=download, operator="imaging")  # noqa: E731
+    _hvp_sweep(engine, shots, ex, born_one, objective, spectral)
     return ex.reduce(engs[0], 0.0, wrt)[0]
 
 
-def gauss_newton_hvp_device(engine, model_slot, v_slot, out_slot, shots, exchange=None, wrt="velocity", objective=None):
+def gauss_newton_hvp_device(engine, model_slot, v_slot, out_slot, shots, exchange=None, wrt="velocity", objective=None,
+                            freq_weights=None, spectral_imaging=False):
     """:func:`gauss_newton_hvp` on device vectors (``Engine.vec_*``): the model is read from ``model_slot`` (None: the
     model the engines hold), v from ``v_slot`` and ``H v`` is written to ``out_slot``; the Born data stay on the device
     as the adjoint's residual, so no model- or data-sized array crosses PCIe (the further engines of a pool receive the
     model and v from the primary one through the host).  OVERWRITES the gradient accumulator; three sweeps per shot.
-    ``objective`` as in :func:`gauss_newton_hvp`: its weight is applied by ``Engine.residual_weight`` on the device."""
+    ``objective`` as in :func:`gauss_newton_hvp`: its weight is applied by ``Engine.residual_weight`` on the device.
+    ``freq_weights``, ``spectral_imaging``: as there, on engines that keep the Fourier store (``fourier_born_vec``)."""
     ex = exchange or NoExchange()
     engs = _engines(engine)
+    four, spectral = _fourier_hvp(engine, freq_weights, spectral_imaging, wrt)
     if model_slot is not None:
         engs[0].set_model_vec(model_slot)
     if len(engs) > 1:  # the vectors live in the primary engine: hand model and v over
@@ -581,11 +686,16 @@ def gauss_newton_hvp_device(engine, model_slot, v_slot, out_slot, shots, exchang
 
     def born_one(e, s, download):
         if e is not engs[0]:
+            if four:
+                return s.fourier_born(e, v, freq_weights, wrt, download=download)
             return s.born(e, v, wrt, download=download, operator="imaging")
-        d = e.born_vec(v_slot, wrt, download=download, operator="imaging")
+        if four:
+            d = e.fourier_born_vec(v_slot, freq_weights, wrt, download=download)
+        else:
+            d = e.born_vec(v_slot, wrt, download=download, operator="imaging")
         return d if d is None or s._on_device(e) or s.rec_spread is None else s.rec_spread.gather(d)
 
-    _hvp_sweep(engine, shots, ex, born_one, objective)
+    _hvp_sweep(engine, shots, ex, born_one, objective, spectral)
     ex.reduce_device(engs[0], 0.0)
     engs[0].gradient_vec(out_slot, wrt)
 

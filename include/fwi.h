@@ -673,6 +673,53 @@ int fwi_born_imaging_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, 
 const char *fwi_born_path(const fwi_ctx *ctx);  /* static name of the path the last Born sweep took: "scatter", "fused";
                                                    "none" before the first */
 
+/* Born and extended Born modelling on the Fourier store (fwi_set_fourier_store), whose fwi_born* stay FWI_ESTATE: the
+ * recursion of fwi_born_imaging with the scattering source synthesised, batch by batch in forward time order, from the
+ * coefficients the store holds.  theta_kj, w_k, Q_k, M_k, S as above; a_k = freq_weights[k] (NULL: ones), folded into
+ * the synthesis table on the host.
+ * fwi_fourier_born[_vec]:
+ *     dq^n = C (L du^n + the CPML terms of du^n) + [n % S == 0] S w q~_a^n
+ *     q~_a^{jS}(x) = sum_k a_k w_k (Re Q_k(x) cos theta_kj - Im Q_k(x) sin theta_kj),   w as for fwi_born
+ * With a = 1 this is the exact transpose of fwi_adjoint(image != 0) + fwi_gradient on this context, with any a that of
+ * fwi_adjoint_spectral + fwi_fourier_gradient(freq_weights = a): H_a = J_a^T J_a is symmetric positive semi-definite.
+ * It reads Q_k and never writes it; M_k and the gradient accumulator are not touched, and a following adjoint of either
+ * kind returns the bits it would have returned without the call in between.
+ * fwi_fourier_born_extended[_vec]: extended Born modelling (demigration), the exact transpose of
+ * fwi_fourier_offset_image / fwi_fourier_lag_image: for a gather (E_l), l = 0 .. nlag - 1, in the units of those calls,
+ * and every residual r,   <J_ext E, r> = sum_l <E_l, offset_image_{h_l}(r)>   (or lag_image_{tau_l}(r)).
+ * `kind`: FWI_EXT_OFFSET with `offsets` (nlag integers h_l in cells along grid axis `axis`, of either sign and any size;
+ * `taus` is ignored) or FWI_EXT_TIMELAG with `taus` (nlag finite tau_l in seconds; `offsets` and `axis` are ignored).
+ * `images_host`: nlag model-shaped arrays of the context dtype, one behind the other; `slots`: nlag vector slots.  The
+ * extended scattering spectrum is formed one lag per launch,
+ *     offset   P_k(y) = sum_l E_l(y - h_l e_a) Q_k(y - 2 h_l e_a)    over the l whose y - h_l e_a and y - 2 h_l e_a are
+ *                                                                    cells of the grid (a lag that has none adds nothing)
+ *     lag      P_k(y) = sum_l E_l(y) Q_k(y) exp(-i 2 pi f_k tau_l)
+ * (fp64 between the loads and one rounding to the context dtype per lag), and the Born sweep above runs with the source
+ *     [n = jS]  S (-c(y)^2) sum_k a_k w_k (Re P_k(y) cos theta_kj - Im P_k(y) sin theta_kj):
+ * the factor -c^2 sits at the injection cell y.  With the single lag h = 0 (or tau = 0) and E_0 = dm the call equals
+ * fwi_fourier_born(FWI_WRT_SLOWNESS2, dm) to round-off, not bit for bit.
+ * P_k IS WRITTEN INTO THE 2 F ARRAYS THAT HOLD M_k (allocated here if no fwi_adjoint_spectral has run yet;
+ * fwi_store_bytes counts them): the extended call destroys M_k, and fwi_fourier_gradient*, fwi_fourier_image,
+ * fwi_fourier_offset_image*, fwi_fourier_lag_image* and fwi_fourier_adjoint_spectrum are FWI_ESTATE until the next
+ * fwi_adjoint_spectral -- the call a Gauss-Newton loop makes next anyway.  Q_k is read only.
+ * All four: the state rules, `mode` (FWI_BORN_FUSED on the same contexts), fwi_born_path, timing and launch_mode of
+ * fwi_born_imaging; one time step per launch, the fused path too; dd stays on the device as the residual of the next
+ * fwi_adjoint(ctx, NULL, ...) or fwi_adjoint_spectral(ctx, NULL, ...), and the forward's synthetics are gone for
+ * fwi_misfit_* afterwards.  FWI_ESTATE: the store is off, or no fwi_forward(save != 0) since it was set.  FWI_EINVAL,
+ * naming the argument and touching nothing: an unknown wrt, kind or mode; axis outside [0, ndim); nlag < 1; a null
+ * pointer; a slot that does not exist; a tau or weight that is not finite; a repeated lag.  No reference counterpart. */
+enum { FWI_EXT_OFFSET = 0, FWI_EXT_TIMELAG = 1 };
+int fwi_fourier_born(fwi_ctx *ctx, int32_t wrt, const void *dm_host, const double *freq_weights, int32_t mode,
+                     void *seis_out /* (nt, nrec) or NULL */);
+int fwi_fourier_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, const double *freq_weights, int32_t mode,
+                         void *seis_out);
+int fwi_fourier_born_extended(fwi_ctx *ctx, int32_t kind, int32_t axis, int32_t nlag, const int32_t *offsets,
+                              const double *taus, const void *images_host, const double *freq_weights, int32_t mode,
+                              void *seis_out);
+int fwi_fourier_born_extended_vec(fwi_ctx *ctx, int32_t kind, int32_t axis, int32_t nlag, const int32_t *offsets,
+                                  const double *taus, const int32_t *slots, const double *freq_weights, int32_t mode,
+                                  void *seis_out);
+
 /* Shot-parallel exchange: one RCCL communicator per context, sum of the
  * gradient accumulators over ranks (in place, on device).  The reference's
  * only counterpart is the gather-by-concatenation of Monte Carlo samples,
