@@ -30,6 +30,7 @@ MATCH_LMAX = 64  # FWI_MATCH_LMAX
 TT_KMAX = 1024  # FWI_TT_KMAX
 OT_TRANSFORMS = {"linear": 0, "softplus": 1}  # FWI_OT_LINEAR, FWI_OT_SOFTPLUS
 FOURIER_FMAX, FOURIER_BMAX = 64, 8  # FWI_FOURIER_FMAX, FWI_FOURIER_BMAX
+SPLIT_SAME, SPLIT_OPPOSITE, SPLIT_HILBERT, SPLIT_RMAX = 0, 1, 2, 64  # FWI_SPLIT_*, FWI_SPLIT_RMAX
 SPEC_KINDS = {"l2": 0, "phase": 1, "logamp": 2, "log": 3}  # FWI_SPEC_L2, FWI_SPEC_PHASE, FWI_SPEC_LOGAMP, FWI_SPEC_LOG
 UNIQUE_ID_BYTES = 128
 EINVAL = 1
@@ -122,6 +123,8 @@ SIGNATURES = {
     "fwi_fourier_offset_image_vec": (C.c_int, [_P, _I32, _I32, _P, _I32]),
     "fwi_fourier_lag_image": (C.c_int, [_P, _D, _P, _P]),
     "fwi_fourier_lag_image_vec": (C.c_int, [_P, _D, _P, _I32]),
+    "fwi_fourier_split_image": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "fwi_fourier_split_image_vec": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32]),
     "fwi_vec_mul": (C.c_int, [_P, _I32, _I32]),
     "fwi_vec_recip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_vec_smooth": (C.c_int, [_P, _I32, C.POINTER(_D)]),

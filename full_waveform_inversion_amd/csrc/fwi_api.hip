@@ -32,6 +32,7 @@
 #include "fwi_fourier.h"
 #include "fwi_fimage.h"
 #include "fwi_feximage.h"
+#include "fwi_fsplit.h"
 #include "fwi_fbornx.h"
 #include "fwi_illum.h"
 #include "fwi_kernels.h"
@@ -154,7 +155,8 @@ struct fwi_ctx {
     // Spectral imaging (fwi_adjoint_spectral; fwi_fimage.hip): 2 F compact accumulator volumes (Re M_k, Im M_k) of the
     // adjoint field, allocated by the first fwi_adjoint_spectral; have_m: they hold the M_k that go with the Q_k of the
     // latest forward(save).  four_w: the F weights a_k w_k of the running image / illumination pass on the device (the
-    // 2 F of a time-lag image, fwi_feximage.hip; room for 2 FWI_FOURIER_FMAX doubles).
+    // 2 F of a time-lag image, fwi_feximage.hip; the F of a split image with its taps behind them at FWI_FOURIER_FMAX,
+    // fwi_fsplit.hip; room for 2 FWI_FOURIER_FMAX doubles).
     void *four_adj = nullptr, *four_w = nullptr;
     bool have_m = false;
     std::vector<double> four_w_host;
@@ -1754,7 +1756,9 @@ struct Impl {
     // entries instead, C_k = a_k w_k cos phi_k at k and D_k = a_k w_k sin phi_k at F + k, phi_k = 2 pi f_k tau formed in
     // fp64 from the fractional part of f_k tau as fourier_table forms its phases (tau = 0: C_k = a_k w_k, D_k = 0).
     // `unit`: a_k w_k = 1, the bare phases (cos phi_k, sin phi_k) of an extended Born source (fwi_fbornx.h).
-    static int fourier_weights(fwi_ctx *ctx, const double *fw, const double *tau = nullptr, bool unit = false) {
+    // `taps` (a split image, fwi_fsplit.h): the `ntaps` <= FWI_SPLIT_RMAX taps follow at FWI_FOURIER_FMAX.
+    static int fourier_weights(fwi_ctx *ctx, const double *fw, const double *tau = nullptr, bool unit = false,
+                               const double *taps = nullptr, int ntaps = 0) {
         const int S = ctx->istride, N = (ctx->nt + S - 1) / S, F = (int)ctx->four_freqs.size();
         const double sdt = (double)S * ctx->cfg.dt;
         if (!ctx->four_w) HIPCHK(ctx, hipMalloc(&ctx->four_w, 2 * FWI_FOURIER_FMAX * sizeof(double)));
@@ -1770,6 +1774,10 @@ struct Impl {
                 a[F + k] = a[k] * std::sin(th);
                 a[k] = a[k] * std::cos(th);
             }
+        }
+        if (taps) {
+            a.resize(FWI_FOURIER_FMAX, 0.0);
+            a.insert(a.end(), taps, taps + ntaps);
         }
         HIPCHK(ctx, hipMemcpyAsync(ctx->four_w, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         return FWI_OK;
@@ -1829,6 +1837,26 @@ struct Impl {
         const double dt2 = ctx->cfg.dt * ctx->cfg.dt, S = (double)ctx->istride;
         HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2, 0,
                                                 ctx->stream));
+        if (out && (rc = download_compact(ctx, out, dev))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return FWI_OK;
+    }
+
+    // One part of the split image (fwi_fsplit.h) into `dev`, through the sum, the scaling and the download of
+    // fourier_finalize: `axis` 0 = z, 1 = y, 2 = x of the GridDesc, `taps` the `ntaps` < n_axis taps that can touch a cell.
+    // Q_k, M_k and the gradient accumulator are read at most.
+    static int fourier_split(fwi_ctx *ctx, int32_t wrt, int axis, const double *taps, int ntaps, double alpha, double beta,
+                             const double *fw, void *dev, T *out) {
+        static_assert(FSPLIT_RMAX == FWI_SPLIT_RMAX && FWI_SPLIT_RMAX <= FWI_FOURIER_FMAX, "the taps share four_w");
+        int rc = fourier_weights(ctx, fw, nullptr, false, taps, ntaps);
+        if (rc) return rc;
+        const int F = (int)ctx->four_freqs.size();
+        const double *w = (const double *)ctx->four_w;
+        HIPCHK(ctx, launch_fsplit<T>(ctx->gd, (T *)dev, (const T *)ctx->four_acc, (const T *)ctx->four_adj, w, F, axis,
+                                     w + FWI_FOURIER_FMAX, ntaps, alpha, beta, ctx->stream));
+        const double dt2 = ctx->cfg.dt * ctx->cfg.dt, S = (double)ctx->istride;
+        HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2,
+                                                wrt == FWI_WRT_VELOCITY, ctx->stream));
         if (out && (rc = download_compact(ctx, out, dev))) return rc;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return FWI_OK;
@@ -3971,6 +3999,46 @@ int fwi_fourier_lag_image_vec(fwi_ctx *ctx, double tau, const double *freq_weigh
     if (!ctx) return FWI_EINVAL;
     VEC_OR_FAIL(ctx, v, slot);
     return fourier_extended(ctx, "fwi_fourier_lag_image_vec", 0, 0, &tau, freq_weights, v, nullptr);
+}
+
+// fwi_fourier_split_image[_vec]; `out`: the host array, nullptr for `dev`
+static int fourier_split(fwi_ctx *ctx, const char *who, int32_t wrt, int32_t part, int32_t axis, int32_t ntaps,
+                         const double *taps, const double *fw, void *dev, void *out) {
+    if (int rc = fourier_callable(ctx, who, true)) return rc;
+    if (part != FWI_SPLIT_SAME && part != FWI_SPLIT_OPPOSITE && part != FWI_SPLIT_HILBERT)
+        return ctx->fail(FWI_EINVAL, "%s: unknown part %d", who, (int)part);
+    if (axis < 0 || axis >= ctx->gd.ndim)
+        return ctx->fail(FWI_EINVAL, "%s: axis=%d outside [0, %d)", who, (int)axis, ctx->gd.ndim);
+    if (ntaps < 1 || ntaps > FWI_SPLIT_RMAX)
+        return ctx->fail(FWI_EINVAL, "%s: ntaps=%d outside [1, %d]", who, (int)ntaps, FWI_SPLIT_RMAX);
+    if (!taps) return ctx->fail(FWI_EINVAL, "%s: null taps", who);
+    for (int r = 0; r < ntaps; ++r)
+        if (!std::isfinite(taps[r])) return ctx->fail(FWI_EINVAL, "%s: taps[%d] is not finite", who, r);
+    if (int rc = fourier_weight_args(ctx, who, fw, false)) return rc;
+    if (int rc = wrt_and_model(ctx, who, wrt)) return rc;
+    (void)hipSetDevice(ctx->cfg.device);
+    const int ax = axis == ctx->gd.ndim - 1 ? 2 : ctx->gd.ndim == 3 ? axis : 0;  // grid order z, [y,] x
+    const int n = ax == 0 ? ctx->gd.nz : ax == 1 ? ctx->gd.ny : ctx->gd.nx;
+    int R = std::min<int>(ntaps, n - 1);  // a tap at r >= n touches no cell, a trailing zero tap is skipped
+    while (R > 0 && taps[R - 1] == 0.0) --R;
+    const double alpha = part == FWI_SPLIT_HILBERT ? 0.0 : 0.5;
+    const double beta = part == FWI_SPLIT_HILBERT ? 1.0 : part == FWI_SPLIT_SAME ? 0.5 : -0.5;
+    return DISPATCH(ctx, Impl<float>::fourier_split(ctx, wrt, ax, taps, R, alpha, beta, fw, dev, (float *)out),
+                    Impl<double>::fourier_split(ctx, wrt, ax, taps, R, alpha, beta, fw, dev, (double *)out));
+}
+
+int fwi_fourier_split_image(fwi_ctx *ctx, int32_t wrt, int32_t part, int32_t axis, int32_t ntaps, const double *taps,
+                            const double *freq_weights, void *out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_split_image: null output");
+    return fourier_split(ctx, "fwi_fourier_split_image", wrt, part, axis, ntaps, taps, freq_weights, ctx->g_out, out);
+}
+
+int fwi_fourier_split_image_vec(fwi_ctx *ctx, int32_t wrt, int32_t part, int32_t axis, int32_t ntaps, const double *taps,
+                                const double *freq_weights, int32_t slot) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, v, slot);
+    return fourier_split(ctx, "fwi_fourier_split_image_vec", wrt, part, axis, ntaps, taps, freq_weights, v, nullptr);
 }
 
 int fwi_fourier_adjoint_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out) {

@@ -667,6 +667,59 @@ class Engine:
             self._chk(self._lib.fwi_fourier_lag_image(self._c, tau, fwp, E[l].ctypes.data_as(C.c_void_p)))
         return E
 
+    # -- tomographic / migration split of the Fourier-store gradient (include/fwi.h fwi_fourier_split_image) ---------
+    _SPLIT_PARTS = {"same": _lib.SPLIT_SAME, "opposite": _lib.SPLIT_OPPOSITE, "hilbert": _lib.SPLIT_HILBERT}
+
+    def _split_args(self, part, axis, taps, wrt):
+        if part not in self._SPLIT_PARTS:
+            raise ValueError("part must be one of 'same', 'opposite', 'hilbert'")
+        t = np.ascontiguousarray(np.asarray(taps, np.float64))
+        if t.ndim != 1:
+            raise ValueError("taps must be the 1-D one-sided taps t_1 .. t_R")
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        return w, self._SPLIT_PARTS[part], self._axis(axis), t.size, t.ctypes.data_as(C.c_void_p), t
+
+    def fourier_split_image_vec(self, slot, part, axis, taps, freq_weights=None, wrt="velocity"):
+        """Vector ``slot`` := one part of the split of :meth:`fourier_gradient` on the device
+        (``fwi_fourier_split_image_vec``); ``part``: ``"same"``, ``"opposite"`` or ``"hilbert"``, as
+        :meth:`fourier_split_image`."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        w, p, ax, n, tp, _t = self._split_args(part, axis, taps, wrt)
+        self._chk(self._lib.fwi_fourier_split_image_vec(self._c, w, p, ax, n, tp, fwp, slot))
+
+    def fourier_split_image(self, part, axis, taps, freq_weights=None, wrt="velocity"):
+        """One part of the split of :meth:`fourier_gradient` along ``axis`` (an index in grid order or ``"z"`` / ``"y"`` /
+        ``"x"``), model-shaped (``fwi_fourier_split_image``).  With ``H`` the antisymmetric FIR of the one-sided ``taps``
+        ``t_1 .. t_R`` along that axis (``datafit.hilbert_taps(R)``: a Hilbert transformer; zero extension at the grid's
+        faces, zero taps skipped, at most ``_lib.SPLIT_RMAX`` taps)
+
+            ``part(x) = kappa sum_k a_k w_k [alpha Re(Q_k conj M_k) + beta Re(H Q_k conj H M_k)]``
+
+        with ``(alpha, beta) = (1/2, 1/2)`` for ``"same"`` (the pairs of equal direction along the axis: low wavenumber,
+        tomographic), ``(1/2, -1/2)`` for ``"opposite"`` (high wavenumber, migration) and ``(0, 1)`` for ``"hilbert"``;
+        ``kappa`` and ``wrt`` as in :meth:`fourier_gradient`, which ``same + opposite`` equals to round-off.  Neither part
+        is the gradient of the misfit: they are the two halves of it.  One streaming pass over the resident coefficients,
+        no further sweep; nothing on the context is written.  One shot's; the caller sums over shots
+        (:func:`shots.split_gradient`)."""
+        fwp, _keep = self._freq_weights(freq_weights)
+        w, p, ax, n, tp, _t = self._split_args(part, axis, taps, wrt)
+        g = np.zeros(self.shape, self.dtype)
+        self._chk(self._lib.fwi_fourier_split_image(self._c, w, p, ax, n, tp, fwp, g.ctypes.data_as(C.c_void_p)))
+        return g
+
+    def fourier_gradient_split(self, axis, taps, freq_weights=None, wrt="velocity"):
+        """``(tomographic, migration)``: the ``"same"`` and ``"opposite"`` parts of :meth:`fourier_split_image`.  Their sum
+        is :meth:`fourier_gradient` to round-off; neither is the gradient of the misfit, they are the two halves of it.
+        Below about ``2 / (R + 1)`` cycles per cell along the axis the filter's transition band leaves energy in both,
+        and zero extension distorts the ``R`` cells next to each face."""
+        return (self.fourier_split_image("same", axis, taps, freq_weights, wrt),
+                self.fourier_split_image("opposite", axis, taps, freq_weights, wrt))
+
+    def fourier_hilbert_image(self, axis, taps, freq_weights=None, wrt="velocity"):
+        """``X = kappa sum_k a_k w_k Re(H Q_k conj H M_k)``, the ``"hilbert"`` part of :meth:`fourier_split_image`:
+        ``tomographic = (g + X) / 2`` and ``migration = (g - X) / 2`` with ``g`` of :meth:`fourier_gradient`."""
+        return self.fourier_split_image("hilbert", axis, taps, freq_weights, wrt)
+
     def store_bytes(self):
         """Device bytes held for the forward store of whichever kind (``fwi_store_bytes``); 0 before the first
         ``forward(save=True)`` allocates it."""

@@ -238,6 +238,92 @@ def lag_image(Q, M, nt, stride, dt, freqs, tau, freq_weights=None, dtype=np.floa
     return s.astype(dtype)
 
 
+# -- tomographic / migration split (fwi_fourier_split_image; csrc/fwi_fsplit.hip) ---------------------------------------
+#
+# With ``H`` a Hilbert transformer along one grid axis, ``U^+- = (U +- i H U) / 2`` are the parts of a coefficient ``U``
+# with positive and negative wavenumber along that axis.  The pairs of equal and of opposite direction are then::
+#
+#     Re(Q+ conj M+) + Re(Q- conj M-) = (Re(Q conj M) + Re(HQ conj HM)) / 2      low wavenumber: tomographic
+#     Re(Q+ conj M-) + Re(Q- conj M+) = (Re(Q conj M) - Re(HQ conj HM)) / 2      high wavenumber: migration
+#
+# (expand the products; the cross terms ``Im(HQ conj M) - Im(Q conj HM)`` cancel in the first sum and never enter the
+# second), so the one new quantity is ``X = sum_k a_k w_k Re(HQ_k conj HM_k)``.  ``H`` is the FIR of
+# ``datafit.hilbert_taps``: antisymmetric, zero-extended at the faces of the grid.
+
+SPLIT_RMAX = 64  # FWI_SPLIT_RMAX
+_SPLIT = {"same": (0.5, 0.5), "opposite": (0.5, -0.5), "hilbert": (0.0, 1.0)}
+
+
+def hilbert_axis(u, taps, axis):
+    """``(H u)(i) = sum_r t_r (u(i - r) - u(i + r))`` along ``axis`` of the real fp64 array ``u`` for the one-sided taps
+    ``t_1 .. t_R``: cells outside the array contribute nothing, taps that are exactly zero are skipped (as
+    ``datafit.hilbert_time`` skips them), the sum runs with ``r`` ascending."""
+    u = np.asarray(u, np.float64)
+    t = np.asarray(taps, np.float64)
+    if t.ndim != 1:
+        raise ValueError("taps must be the 1-D one-sided taps t_1 .. t_R")
+    axis = int(axis)
+    if not 0 <= axis < u.ndim:
+        raise ValueError("axis %d outside [0, %d)" % (axis, u.ndim))
+    n = u.shape[axis]
+    cut = lambda lo, hi: (slice(None),) * axis + (slice(lo, hi),)  # noqa: E731
+    # every cell adds t_r (u(i - r) - u(i + r)) in one step, an absent neighbour as 0: the device's order
+    out = np.zeros_like(u)
+    for r in range(1, min(t.size, n - 1) + 1):
+        if t[r - 1] != 0.0:
+            d = np.zeros_like(u)
+            d[cut(r, n)] += u[cut(0, n - r)]
+            d[cut(0, n - r)] -= u[cut(r, n)]
+            out += t[r - 1] * d
+    return out
+
+
+def split_image(Q, M, nt, stride, dt, freqs, axis, taps, part, freq_weights=None, dtype=np.float64):
+    """One part of the split of :func:`spectral_image` along the model axis ``axis`` (0 = the first axis after the
+    frequencies), in its units::
+
+        sum_k a_k w_k [alpha Re(Q_k conj M_k) + beta Re(H Q_k conj H M_k)]
+
+    with ``H`` of :func:`hilbert_axis` on ``Re`` and ``Im`` separately and ``(alpha, beta) = (1/2, 1/2)`` for
+    ``part="same"`` (tomographic), ``(1/2, -1/2)`` for ``"opposite"`` (migration), ``(0, 1)`` for ``"hilbert"``.
+    ``same + opposite`` is :func:`spectral_image` to round-off.  At most ``SPLIT_RMAX`` taps.  ``dtype`` restates the
+    device's arithmetic: the coefficients are held in ``dtype``; the filter sums (``r`` ascending, zero taps skipped), the
+    products ``p = Re HQ Re HM + Im HQ Im HM`` and ``t = Re Q Re M + Im Q Im M`` and the sum over k (ascending, each term
+    ``a_k (alpha t + beta p)``) run in fp64, and the result is rounded to ``dtype`` once."""
+    a, Q = _weighted(Q, nt, stride, dt, freqs, freq_weights)
+    M = np.asarray(M)
+    dtype = np.dtype(dtype)
+    if part not in _SPLIT:
+        raise ValueError("part must be one of 'same', 'opposite', 'hilbert'")
+    alpha, beta = _SPLIT[part]
+    t = np.asarray(taps, np.float64)
+    if t.ndim != 1 or not 1 <= t.size <= SPLIT_RMAX or not np.all(np.isfinite(t)):
+        raise ValueError("taps must be a finite 1-D array t_1 .. t_R, R in [1, %d]" % SPLIT_RMAX)
+    axis = int(axis)
+    if not 0 <= axis < Q.ndim - 1:
+        raise ValueError("axis %d outside [0, %d)" % (axis, Q.ndim - 1))
+    part_ = lambda z: z.astype(dtype).astype(np.float64)  # noqa: E731
+    s = np.zeros(Q.shape[1:], np.float64)
+    for k in range(a.size):
+        qr, qi, mr, mi = part_(Q[k].real), part_(Q[k].imag), part_(M[k].real), part_(M[k].imag)
+        p = hilbert_axis(qr, t, axis) * hilbert_axis(mr, t, axis) + hilbert_axis(qi, t, axis) * hilbert_axis(mi, t, axis)
+        s = s + a[k] * (alpha * (qr * mr + qi * mi) + beta * p)
+    return s.astype(dtype)
+
+
+def split_halfwidth(cycles_per_cell):
+    """``R = ceil(2 / kappa) - 1``: the half-width at which ``datafit.hilbert_taps(R)`` is good (within 2e-3 of a Hilbert
+    transformer) from ``kappa`` cycles per cell to Nyquist minus ``kappa`` along the axis; below ``kappa`` the split
+    leaves energy in both parts.  Raises above ``SPLIT_RMAX``."""
+    kappa = float(cycles_per_cell)
+    if not 0.0 < kappa < 0.5:
+        raise ValueError("cycles_per_cell = %g outside (0, Nyquist = 0.5)" % kappa)
+    R = max(int(np.ceil(round(2.0 / kappa, 9))) - 1, 1)
+    if R > SPLIT_RMAX:
+        raise ValueError("%g cycles per cell needs R = %d taps, above %d: raise it" % (kappa, R, SPLIT_RMAX))
+    return R
+
+
 # -- Born and extended Born modelling (fwi_fourier_born, fwi_fourier_born_extended; csrc/fwi_fbornx.hip) ---------------
 #
 # The transposes of the imaging paths above take their scattering source from the coefficients.  The transpose of the

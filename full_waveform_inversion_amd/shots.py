@@ -486,6 +486,51 @@ def extended_image(engine, model, shots, kind, lags, axis=None, exchange=None, o
     return J, ext.gather(engine, ex)
 
 
+class _Split(_Spectral):
+    """The adjoint of :func:`split_gradient`: ``Engine.adjoint_spectral(residual, image=False)``, then the shot's two parts
+    added to its engine's fp64 sums on the host (a pool drives each engine from one thread)."""
+
+    def __init__(self, engine, freq_weights, wrt, axis, taps):
+        super().__init__(engine, freq_weights, wrt, False)
+        self.axis, self.taps = axis, np.ascontiguousarray(np.asarray(taps, np.float64))
+        self.G = {}
+
+    def adjoint(self, e, shot, residual):
+        e.adjoint_spectral(self._residual(e, shot, residual), image=False)
+        G = np.stack(e.fourier_gradient_split(self.axis, self.taps, self.freq_weights, self.wrt)).astype(np.float64)
+        self.G[id(e)] = self.G[id(e)] + G if id(e) in self.G else G
+
+    def parts(self, engine, ex):
+        """Both parts of this evaluation summed over shots, engines and ranks (zeros on a rank that owned no shot)"""
+        engs = _engines(engine)
+        G = sum((self.G[id(e)] for e in engs if id(e) in self.G), np.zeros((2,) + tuple(engs[0].shape)))
+        return ex.reduce_array(G)
+
+
+def split_gradient(engine, model, shots, axis, taps, exchange=None, objective=None, freq_weights=None, wrt="velocity"):
+    """``(J, g_same, g_opposite)``: the misfit of :func:`misfit_and_gradient` and the two parts of the split of its
+    spectral gradient along ``axis`` (``Engine.fourier_gradient_split`` with the one-sided ``taps``, e.g.
+    ``datafit.hilbert_taps(fourier.split_halfwidth(kappa))``), summed over shots, pool engines and ranks the way
+    :func:`extended_image` sums its gathers, model-shaped in fp64.  ``g_same`` pairs forward and adjoint coefficients
+    that travel the same way along the axis (low wavenumber: the transmission paths, the tomographic part),
+    ``g_opposite`` those that travel in opposite directions (high wavenumber: the reflectors, the migration part).
+    NEITHER PART IS THE GRADIENT OF THE MISFIT: they are the two halves of it, ``g_same + g_opposite`` is the gradient of
+    ``misfit_and_gradient(spectral_imaging=True, freq_weights=freq_weights, wrt=wrt)`` to round-off, and no line search
+    may treat one of them as a gradient of ``J``.  Every shot takes the per-shot path of ``spectral_imaging=True``:
+    forward, residual by ``objective``, ``Engine.adjoint_spectral(image=False)`` and two streaming passes.  The gradient
+    accumulators are reset and stay zero.  Engines without the Fourier store raise ``ValueError``."""
+    from .objectives import l2
+    ex = exchange or NoExchange()
+    split = _Split(engine, freq_weights, wrt, axis, taps)
+    for e in _engines(engine):
+        e.set_model(model)
+        e.reset_gradient()
+    misfit = _sweep_shots(engine, shots, ex, objective or l2, True, split)
+    J = float(np.asarray(ex.reduce_array(np.array([misfit]))).ravel()[0])
+    G = split.parts(engine, ex)
+    return J, G[0], G[1]
+
+
 def _extended_born_one(e, s, kind, lags, images, axis, freq_weights, download):
     """``J_ext,s E`` of one shot after its ``forward(save=True)``, per point where the shot has off-grid receivers"""
     d = e.fourier_born_extended(kind, lags, images, axis, freq_weights, download=download)

@@ -582,6 +582,39 @@ int fwi_fourier_offset_image_vec(fwi_ctx *ctx, int32_t axis, int32_t h, const do
 int fwi_fourier_lag_image(fwi_ctx *ctx, double tau, const double *freq_weights, void *out);
 int fwi_fourier_lag_image_vec(fwi_ctx *ctx, double tau, const double *freq_weights, int32_t slot);
 
+/* The tomographic / migration split of fwi_fourier_gradient (wavefield-decomposition imaging: Liu et al., 2011; the
+ * background update of reflection waveform inversion: Xu et al., 2012), one streaming pass over the resident Q_k and M_k
+ * with an antisymmetric FIR along one grid axis, no further sweep and no model-sized storage.  The state rules are those
+ * of fwi_fourier_gradient (after fwi_forward(save != 0) and fwi_adjoint_spectral).  With the one-sided taps
+ * t_1 .. t_R = taps[0 .. ntaps - 1] (datafit.hilbert_taps in Python: an FIR Hilbert transformer) and the grid axis a
+ * (grid order: 0 .. ndim - 1 = z, [y,] x),
+ *     (H u)(i) = sum_{r = 1 .. R} t_r (u(i - r) - u(i + r))      along axis a,
+ * where cells outside [0, n_a) contribute nothing (zero extension against the GRID's extent, not the padded row of the
+ * device layout), taps that are exactly zero are skipped, and H acts on Re and Im separately:
+ *     part(x) = kappa sum_k a_k w_k [ alpha (Re Q_k Re M_k + Im Q_k Im M_k) + beta (Re HQ_k Re HM_k + Im HQ_k Im HM_k) ]
+ * (alpha, beta) = (1/2, 1/2) for FWI_SPLIT_SAME: with U^+- = (U +- i H U) / 2 the parts of positive and negative
+ * wavenumber along the axis, this is Re(Q+ conj M+) + Re(Q- conj M-), the pairs that travel the same way (low wavenumber,
+ * tomographic); (1/2, -1/2) for FWI_SPLIT_OPPOSITE: Re(Q+ conj M-) + Re(Q- conj M+), the pairs that travel in opposite
+ * directions (high wavenumber, migration); (0, 1) for FWI_SPLIT_HILBERT: the image of the filtered coefficients alone.
+ * kappa and the `wrt` scaling are exactly those of fwi_fourier_gradient; a_k = freq_weights[k] (NULL: ones).  SAME +
+ * OPPOSITE equals fwi_fourier_gradient(freq_weights, wrt) to round-off.  NEITHER PART IS THE GRADIENT OF THE MISFIT: they
+ * are the two halves of it.  1 <= ntaps <= FWI_SPLIT_RMAX; ntaps may exceed n_a, the excess taps touch nothing.  The
+ * transition band of the FIR leaves |k_a| below about 2 / (R + 1) cycles per cell in neither part cleanly, and zero
+ * extension distorts the R cells next to each face of the axis.
+ * `out`: a model-shaped host buffer of the context dtype (staged through the array fwi_fourier_gradient stages through);
+ * `slot`: a vector of fwi_vec_create (pad columns zero).  Neither the gradient accumulator nor Q_k or M_k is written, and
+ * any number of calls may follow one fwi_adjoint_spectral.
+ * FWI_ESTATE as for fwi_fourier_gradient: the store is off, no fwi_forward(save != 0), no fwi_adjoint_spectral since the
+ * latest one, or fwi_fourier_born_extended has overwritten M_k since.  FWI_EINVAL, naming the argument and touching
+ * nothing: an unknown wrt or part, axis outside [0, ndim), ntaps outside [1, FWI_SPLIT_RMAX], null taps, a tap or weight
+ * that is not finite, a null `out`, a slot that does not exist.  No reference counterpart. */
+enum { FWI_SPLIT_SAME = 0, FWI_SPLIT_OPPOSITE = 1, FWI_SPLIT_HILBERT = 2 };
+#define FWI_SPLIT_RMAX 64
+int fwi_fourier_split_image(fwi_ctx *ctx, int32_t wrt, int32_t part, int32_t axis, int32_t ntaps, const double *taps,
+                            const double *freq_weights /* F, or NULL = ones */, void *out);
+int fwi_fourier_split_image_vec(fwi_ctx *ctx, int32_t wrt, int32_t part, int32_t axis, int32_t ntaps, const double *taps,
+                                const double *freq_weights, int32_t slot);
+
 /* Elementwise vector operations for a diagonal preconditioner (pad columns of the compact layout stay 0). */
 int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x);               /* y := x * y */
 int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b);    /* y := a / (y + b) */

@@ -49,6 +49,12 @@ def main():
                          "lags -L .. L of a subsurface-offset gather along AXIS (z, y or x; lags in cells) or of a time-lag "
                          "gather in steps of DTAU seconds; written to --extended-out with its lags and fourier.focusing")
     ap.add_argument("--extended-out", default=None, metavar="PATH", help="the .npz file of --extended-image (rank 0 writes)")
+    ap.add_argument("--split-gradient", default=None, metavar="AXIS:R",
+                    help="with --fourier-store: the tomographic (same direction) and migration (opposite direction) parts "
+                         "of the final model's spectral gradient along AXIS (z, y or x), with datafit.hilbert_taps(R), "
+                         "1 <= R <= 64 (shots.split_gradient); neither part is the gradient of the misfit, the "
+                         "optimiser never sees them; needs --split-out")
+    ap.add_argument("--split-out", default=None, metavar="PATH", help="the .npz file of --split-gradient (rank 0 writes)")
     ap.add_argument("--update-form", default="auto", choices=["auto", "increment", "standard"],
                     help="fp32 update form; auto = shots.inversion_engine's choice (increment: 1e-5 end to end)")
     ap.add_argument("--launch-mode", default="auto", choices=["auto", "stream", "graph"])
@@ -164,6 +170,20 @@ def main():
             ap.error("--extended-image takes offset:AXIS:L (AXIS z, y or x) or time:DTAU:L (DTAU > 0 seconds), L >= 0")
     elif a.extended_out is not None:
         ap.error("--extended-out needs --extended-image")
+    split = None
+    if a.split_gradient is not None:
+        if a.fourier_store is None:
+            ap.error("--split-gradient needs --fourier-store FMIN,FMAX (it splits the image of the store's frequencies)")
+        if a.split_out is None:
+            ap.error("--split-gradient needs --split-out PATH")
+        try:
+            axis, half = a.split_gradient.split(":")
+            assert axis in ("z", "y", "x") and 1 <= int(half) <= 64
+            split = (axis, int(half))
+        except (ValueError, AssertionError):
+            ap.error("--split-gradient takes AXIS:R (AXIS z, y or x; 1 <= R <= 64 taps)")
+    elif a.split_out is not None:
+        ap.error("--split-out needs --split-gradient")
     if a.fourier_imaging == "whiten" and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--fourier-imaging whiten takes its weights from this rank's data: it runs on one rank")
     spectral_band = None
@@ -410,6 +430,13 @@ def main():
         if rank == 0:
             np.savez(a.extended_out, gather=E, lags=lags, kind=kind, axis="" if axis is None else axis,
                      focusing=fourier.focusing(E, lags))
+    if split is not None:  # both parts of the final model's gradient, with the misfit and the weights of the last stage
+        from full_waveform_inversion_amd import datafit as df
+        axis, half = split
+        J, g_same, g_opposite = sh.split_gradient(pool, np.asarray(m_final, np.float32), shots, axis, df.hilbert_taps(half),
+                                                  ex, obj[0], imaging.get("freq_weights"))
+        if rank == 0:
+            np.savez(a.split_out, same=g_same, opposite=g_opposite, axis=axis, halfwidth=half, misfit=J)
     if not bands:
         filters_line(obj[0])
     if rank == 0:
