@@ -1804,11 +1804,10 @@ struct Impl {
         return FWI_OK;
     }
 
-    // the gradient (`illum`: the illumination) of that sum alone into the compact device array `dev`, which is
-    // ctx->g_out and goes on to the host array `out`, or a vector slot (out = nullptr)
-    static int fourier_finalize(fwi_ctx *ctx, int32_t wrt, const double *fw, bool illum, void *dev, T *out) {
-        int rc = fourier_sum(ctx, fw, illum, dev, 0);
-        if (rc) return rc;
+    // The tail of every image on the Fourier store: the sum over k that stands in the compact device array `dev` is scaled
+    // there into the gradient (`illum`: the illumination) in the parametrisation `wrt`; `dev` is ctx->g_out and goes on to
+    // the host array `out`, or a vector slot (out = nullptr).
+    static int fourier_tail(fwi_ctx *ctx, int32_t wrt, bool illum, void *dev, T *out) {
         const double dt2 = ctx->cfg.dt * ctx->cfg.dt, S = (double)ctx->istride;
         if (illum)
             HIPCHK(ctx, launch_illum_finalize<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, S / (dt2 * dt2),
@@ -1816,13 +1815,19 @@ struct Impl {
         else
             HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2,
                                                     wrt == FWI_WRT_VELOCITY, ctx->stream));
-        if (out && (rc = download_compact(ctx, out, dev))) return rc;
+        if (out)
+            if (int rc = download_compact(ctx, out, dev)) return rc;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return FWI_OK;
     }
 
-    // One lag of an extended image (fwi_feximage.h) into `dev`, through the sum, the scaling and the download of
-    // fourier_finalize(wrt = FWI_WRT_SLOWNESS2): the offset image of `h` cells along `axis` (0 = z, 1 = y, 2 = x of the
+    // the gradient (`illum`: the illumination) of that sum alone into `dev`
+    static int fourier_finalize(fwi_ctx *ctx, int32_t wrt, const double *fw, bool illum, void *dev, T *out) {
+        int rc = fourier_sum(ctx, fw, illum, dev, 0);
+        return rc ? rc : fourier_tail(ctx, wrt, illum, dev, out);
+    }
+
+    // One lag of an extended image (fwi_feximage.h) into `dev`, through the sum and fourier_tail(wrt = FWI_WRT_SLOWNESS2): the offset image of `h` cells along `axis` (0 = z, 1 = y, 2 = x of the
     // GridDesc), or with `tau` the time-lag image.  Q_k, M_k and the gradient accumulator are read at most.
     static int fourier_extended(fwi_ctx *ctx, int axis, int64_t h, const double *tau, const double *fw, void *dev, T *out) {
         int rc = fourier_weights(ctx, fw, tau);
@@ -1834,16 +1839,10 @@ struct Impl {
         else
             HIPCHK(ctx, launch_feximage_offset<T>(ctx->gd, (T *)dev, q, m, (const double *)ctx->four_w, F, axis, h,
                                                   ctx->stream));
-        const double dt2 = ctx->cfg.dt * ctx->cfg.dt, S = (double)ctx->istride;
-        HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2, 0,
-                                                ctx->stream));
-        if (out && (rc = download_compact(ctx, out, dev))) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
+        return fourier_tail(ctx, FWI_WRT_SLOWNESS2, false, dev, out);
     }
 
-    // One part of the split image (fwi_fsplit.h) into `dev`, through the sum, the scaling and the download of
-    // fourier_finalize: `axis` 0 = z, 1 = y, 2 = x of the GridDesc, `taps` the `ntaps` < n_axis taps that can touch a cell.
+    // One part of the split image (fwi_fsplit.h) into `dev`, through the sum and fourier_tail: `axis` 0 = z, 1 = y, 2 = x of the GridDesc, `taps` the `ntaps` < n_axis taps that can touch a cell.
     // Q_k, M_k and the gradient accumulator are read at most.
     static int fourier_split(fwi_ctx *ctx, int32_t wrt, int axis, const double *taps, int ntaps, double alpha, double beta,
                              const double *fw, void *dev, T *out) {
@@ -1854,12 +1853,7 @@ struct Impl {
         const double *w = (const double *)ctx->four_w;
         HIPCHK(ctx, launch_fsplit<T>(ctx->gd, (T *)dev, (const T *)ctx->four_acc, (const T *)ctx->four_adj, w, F, axis,
                                      w + FWI_FOURIER_FMAX, ntaps, alpha, beta, ctx->stream));
-        const double dt2 = ctx->cfg.dt * ctx->cfg.dt, S = (double)ctx->istride;
-        HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2,
-                                                wrt == FWI_WRT_VELOCITY, ctx->stream));
-        if (out && (rc = download_compact(ctx, out, dev))) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
+        return fourier_tail(ctx, wrt, false, dev, out);
     }
 
     // Born modelling dd = J dm (include/fwi.h, fwi_born / fwi_born_imaging).  dm comes from the host (`dm_host`) or from a
@@ -3641,6 +3635,26 @@ int fwi_fourier_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, const double *
     return fourier_born(ctx, "fwi_fourier_born_vec", wrt, nullptr, v, freq_weights, mode, seis_out);
 }
 
+// The axis of the GridDesc (0 = z, 1 = y, 2 = x) of the caller's `axis` in grid order z, [y,] x, in *ax; refused outside it.
+static int fourier_axis(fwi_ctx *ctx, const char *who, int32_t axis, int *ax) {
+    if (axis < 0 || axis >= ctx->gd.ndim)
+        return ctx->fail(FWI_EINVAL, "%s: axis=%d outside [0, %d)", who, (int)axis, ctx->gd.ndim);
+    *ax = axis == ctx->gd.ndim - 1 ? 2 : ctx->gd.ndim == 3 ? axis : 0;
+    return FWI_OK;
+}
+
+// A time lag `tau` (l < 0), or taus[l]: that it is finite, or with `phase` that it leaves a finite phase at every
+// frequency of the store.  Two calls, because the entry points check other arguments in between.
+static int fourier_tau_ok(fwi_ctx *ctx, const char *who, double tau, int l, bool phase) {
+    char name[32] = "tau";
+    if (l >= 0) snprintf(name, sizeof name, "taus[%d]", l);
+    if (!phase) return std::isfinite(tau) ? FWI_OK : ctx->fail(FWI_EINVAL, "%s: %s is not finite", who, name);
+    for (double f : ctx->four_freqs)
+        if (!std::isfinite(f * tau))
+            return ctx->fail(FWI_EINVAL, "%s: %s=%g s leaves no finite phase at %g Hz", who, name, tau, f);
+    return FWI_OK;
+}
+
 // `images_host`: fwi_fourier_born_extended, else the vector slots `slots` of fwi_fourier_born_extended_vec
 static int fourier_born_extended(fwi_ctx *ctx, const char *who, int32_t kind, int32_t axis, int32_t nlag,
                                  const int32_t *offsets, const double *taus, const void *images_host,
@@ -3650,8 +3664,9 @@ static int fourier_born_extended(fwi_ctx *ctx, const char *who, int32_t kind, in
     const bool lag = kind == FWI_EXT_TIMELAG;
     if (nlag < 1) return ctx->fail(FWI_EINVAL, "%s: nlag=%d is below 1", who, (int)nlag);
     if (lag ? !taus : !offsets) return ctx->fail(FWI_EINVAL, "%s: null %s", who, lag ? "taus" : "offsets");
-    if (!lag && (axis < 0 || axis >= ctx->gd.ndim))
-        return ctx->fail(FWI_EINVAL, "%s: axis=%d outside [0, %d)", who, (int)axis, ctx->gd.ndim);
+    int ax = 0;
+    if (!lag)
+        if (int rc = fourier_axis(ctx, who, axis, &ax)) return rc;
     std::vector<const void *> dev;
     for (int l = 0; slots && l < nlag; ++l) {
         dev.push_back(vec_slot(ctx, slots[l]));
@@ -3659,7 +3674,8 @@ static int fourier_born_extended(fwi_ctx *ctx, const char *who, int32_t kind, in
             return ctx->fail(FWI_EINVAL, "%s: slots[%d]: vector slot %d does not exist", who, l, (int)slots[l]);
     }
     for (int l = 0; l < nlag; ++l) {
-        if (lag && !std::isfinite(taus[l])) return ctx->fail(FWI_EINVAL, "%s: taus[%d] is not finite", who, l);
+        if (lag)
+            if (int rc = fourier_tau_ok(ctx, who, taus[l], l, false)) return rc;
         for (int m = 0; m < l; ++m)
             if (lag ? taus[m] == taus[l] : offsets[m] == offsets[l])
                 return ctx->fail(FWI_EINVAL, "%s: %s[%d] repeats %s[%d]", who, lag ? "taus" : "offsets", l,
@@ -3668,11 +3684,8 @@ static int fourier_born_extended(fwi_ctx *ctx, const char *who, int32_t kind, in
     bool fused = false;
     if (int rc = fourier_born_callable(ctx, who, mode, fw, &fused)) return rc;
     for (int l = 0; lag && l < nlag; ++l)
-        for (double f : ctx->four_freqs)
-            if (!std::isfinite(f * taus[l]))
-                return ctx->fail(FWI_EINVAL, "%s: taus[%d]=%g s leaves no finite phase at %g Hz", who, l, taus[l], f);
+        if (int rc = fourier_tau_ok(ctx, who, taus[l], l, true)) return rc;
     (void)hipSetDevice(ctx->cfg.device);
-    const int ax = lag ? 0 : axis == ctx->gd.ndim - 1 ? 2 : ctx->gd.ndim == 3 ? axis : 0;  // grid order z, [y,] x
     const void *const *d = slots ? dev.data() : nullptr;
     return DISPATCH(ctx, Impl<float>::fourier_born_extended(ctx, lag, ax, nlag, offsets, taus, (const float *)images_host, d,
                                                             fw, fused, (float *)seis_out),
@@ -3963,16 +3976,12 @@ int fwi_fourier_illumination_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_w
 static int fourier_extended(fwi_ctx *ctx, const char *who, int32_t axis, int32_t h, const double *tau, const double *fw,
                             void *dev, void *out) {
     if (int rc = fourier_callable(ctx, who, true)) return rc;
-    if (!tau && (axis < 0 || axis >= ctx->gd.ndim))
-        return ctx->fail(FWI_EINVAL, "%s: axis=%d outside [0, %d)", who, (int)axis, ctx->gd.ndim);
-    if (tau && !std::isfinite(*tau)) return ctx->fail(FWI_EINVAL, "%s: tau is not finite", who);
+    int ax = 0;
+    if (int rc = tau ? fourier_tau_ok(ctx, who, *tau, -1, false) : fourier_axis(ctx, who, axis, &ax)) return rc;
     if (int rc = fourier_weight_args(ctx, who, fw, false)) return rc;
     if (tau)
-        for (double f : ctx->four_freqs)
-            if (!std::isfinite(f * *tau))
-                return ctx->fail(FWI_EINVAL, "%s: tau=%g s leaves no finite phase at %g Hz", who, *tau, f);
+        if (int rc = fourier_tau_ok(ctx, who, *tau, -1, true)) return rc;
     (void)hipSetDevice(ctx->cfg.device);
-    const int ax = tau ? 0 : axis == ctx->gd.ndim - 1 ? 2 : ctx->gd.ndim == 3 ? axis : 0;  // grid order z, [y,] x
     return DISPATCH(ctx, Impl<float>::fourier_extended(ctx, ax, h, tau, fw, dev, (float *)out),
                     Impl<double>::fourier_extended(ctx, ax, h, tau, fw, dev, (double *)out));
 }
@@ -4007,8 +4016,8 @@ static int fourier_split(fwi_ctx *ctx, const char *who, int32_t wrt, int32_t par
     if (int rc = fourier_callable(ctx, who, true)) return rc;
     if (part != FWI_SPLIT_SAME && part != FWI_SPLIT_OPPOSITE && part != FWI_SPLIT_HILBERT)
         return ctx->fail(FWI_EINVAL, "%s: unknown part %d", who, (int)part);
-    if (axis < 0 || axis >= ctx->gd.ndim)
-        return ctx->fail(FWI_EINVAL, "%s: axis=%d outside [0, %d)", who, (int)axis, ctx->gd.ndim);
+    int ax = 0;
+    if (int rc = fourier_axis(ctx, who, axis, &ax)) return rc;
     if (ntaps < 1 || ntaps > FWI_SPLIT_RMAX)
         return ctx->fail(FWI_EINVAL, "%s: ntaps=%d outside [1, %d]", who, (int)ntaps, FWI_SPLIT_RMAX);
     if (!taps) return ctx->fail(FWI_EINVAL, "%s: null taps", who);
@@ -4017,7 +4026,6 @@ static int fourier_split(fwi_ctx *ctx, const char *who, int32_t wrt, int32_t par
     if (int rc = fourier_weight_args(ctx, who, fw, false)) return rc;
     if (int rc = wrt_and_model(ctx, who, wrt)) return rc;
     (void)hipSetDevice(ctx->cfg.device);
-    const int ax = axis == ctx->gd.ndim - 1 ? 2 : ctx->gd.ndim == 3 ? axis : 0;  // grid order z, [y,] x
     const int n = ax == 0 ? ctx->gd.nz : ax == 1 ? ctx->gd.ny : ctx->gd.nx;
     int R = std::min<int>(ntaps, n - 1);  // a tap at r >= n touches no cell, a trailing zero tap is skipped
     while (R > 0 && taps[R - 1] == 0.0) --R;

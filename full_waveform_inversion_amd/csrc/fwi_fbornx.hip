@@ -15,81 +15,42 @@
 // whose cells passes reads nothing and (first lag) writes zeros.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "fwi_fbornx.h"
+#include "fwi_fstore_device.h"
 
 namespace fwi {
 
 namespace {
 
-constexpr int FBX_BLOCK = 256;
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-    T e[V];
-};
-
-// the V cells at p: one vector read, or (`elem`) the cells of `mask` one by one, the others 0 and never addressed
-template <typename T, int V>
-__device__ __forceinline__ Pack<T, V> fbx_load(const T *__restrict__ p, unsigned mask, bool elem) {
-    using P = Pack<T, V>;
-    if (!elem) return *(const P *)p;
-    P r;
-#pragma unroll
-    for (int e = 0; e < V; ++e) r.e[e] = (mask >> e & 1u) ? p[e] : T(0);
-    return r;
-}
+using namespace fstore;
 
 // axis: 0 = z, 1 = y, 2 = x.  ELEM = false: 2 h e is a whole number of vectors (any h along z or y, 2 h % V == 0 along x).
 template <typename T, int V, bool ELEM>
-__global__ __launch_bounds__(FBX_BLOCK) void fbornx_offset(GridDesc g, T *__restrict__ p, const T *__restrict__ q,
-                                                           const T *__restrict__ img, int F, int axis, int64_t h,
-                                                           int beta) {
+__global__ __launch_bounds__(BLOCK) void fbornx_offset(GridDesc g, T *__restrict__ p, const T *__restrict__ q,
+                                                       const T *__restrict__ img, int F, int axis, int64_t h,
+                                                       int beta) {
     using P = Pack<T, V>;
-    const int64_t npts = g.npts;
+    const int64_t npts = g.npts, sh = shift_elems(g, axis, h);
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = tid; i < npts / V; i += nthr) {
         const int64_t i0 = i * V, row = i0 / g.cx;  // row = z * ny + y
         const int x = (int)(i0 - row * g.cx);
-        unsigned mask = 0;  // bit e: cell y = x + e and its shifted cells y - h, y - 2 h lie in the grid
-        if (axis == 2) {
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int64_t c1 = x + e - h, c2 = x + e - 2 * h;
-                if (x + e < g.nx && c1 >= 0 && c1 < g.nx && c2 >= 0 && c2 < g.nx) mask |= 1u << e;
-            }
-        } else {
-            const int64_t c = axis == 0 ? row / g.ny : row % g.ny, n = axis == 0 ? g.nz : g.ny;
-            if (c - h >= 0 && c - h < n && c - 2 * h >= 0 && c - 2 * h < n) {
-#pragma unroll
-                for (int e = 0; e < V; ++e)
-                    if (x + e < g.nx) mask |= 1u << e;
-            }
-        }
+        const unsigned mask = shift_mask<V>(g, row, x, axis, -h, -2 * h);  // of the cells y = x + e: y - h, y - 2 h
         T *pk = p + i0;  // Re, Im of frequency k: pk, pk + npts
         if (mask == 0) {
-            if (!beta) {
-                P z;
-#pragma unroll
-                for (int e = 0; e < V; ++e) z.e[e] = T(0);
-                for (int k = 0; k < 2 * F; ++k) *(P *)(pk + k * npts) = z;
-            }
+            if (!beta)
+                for (int k = 0; k < 2 * F; ++k) *(P *)(pk + k * npts) = zero_pack<T, V>();
             continue;
         }
-        // (|2 h| < n from here on: the shifts in elements fit, and the shifted vectors lie inside the volume)
-        const int64_t sh = h * (axis == 2 ? 1 : axis == 1 ? (int64_t)g.cx : (int64_t)g.ny * g.cx);
-        const P ev = fbx_load<T, V>(img + i0 - sh, mask, axis == 2 && h % V != 0);
-        const T *qk = q + i0 - 2 * sh;
+        // (|2 h| < n from here on: sh and 2 sh are the shifts in elements, and the shifted vectors lie in the volume)
+        const T *ek = img + i0 - sh, *qk = q + i0 - 2 * sh;
+        const P ev = axis == 2 && h % V != 0 ? load<T, V, true>(ek, mask) : load<T, V, false>(ek, mask);
         for (int k = 0; k < F; ++k) {
-            const P qr = fbx_load<T, V>(qk, mask, ELEM), qi = fbx_load<T, V>(qk + npts, mask, ELEM);
-            P pr, pi;
+            const P qr = load<T, V, ELEM>(qk, mask), qi = load<T, V, ELEM>(qk + npts, mask);
+            P pr = zero_pack<T, V>(), pi = pr;
             if (beta) {
                 pr = *(const P *)pk;
                 pi = *(const P *)(pk + npts);
-            } else {
-#pragma unroll
-                for (int e = 0; e < V; ++e) pr.e[e] = pi.e[e] = T(0);
             }
 #pragma unroll
             for (int e = 0; e < V; ++e) {
@@ -107,9 +68,9 @@ __global__ __launch_bounds__(FBX_BLOCK) void fbornx_offset(GridDesc g, T *__rest
 }
 
 template <typename T, int V>
-__global__ __launch_bounds__(FBX_BLOCK) void fbornx_lag(T *__restrict__ p, const T *__restrict__ q,
-                                                        const T *__restrict__ img, const double *__restrict__ cs,
-                                                        int64_t npts, int F, int beta) {
+__global__ __launch_bounds__(BLOCK) void fbornx_lag(T *__restrict__ p, const T *__restrict__ q,
+                                                    const T *__restrict__ img, const double *__restrict__ cs,
+                                                    int64_t npts, int F, int beta) {
     using P = Pack<T, V>;
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = tid; i < npts / V; i += nthr) {
@@ -119,13 +80,10 @@ __global__ __launch_bounds__(FBX_BLOCK) void fbornx_lag(T *__restrict__ p, const
         T *pk = p + i0;
         for (int k = 0; k < F; ++k) {
             const P qr = *(const P *)qk, qi = *(const P *)(qk + npts);
-            P pr, pi;
+            P pr = zero_pack<T, V>(), pi = pr;
             if (beta) {
                 pr = *(const P *)pk;
                 pi = *(const P *)(pk + npts);
-            } else {
-#pragma unroll
-                for (int e = 0; e < V; ++e) pr.e[e] = pi.e[e] = T(0);
             }
             const double ck = cs[k], sk = cs[F + k];
 #pragma unroll
@@ -142,27 +100,16 @@ __global__ __launch_bounds__(FBX_BLOCK) void fbornx_lag(T *__restrict__ p, const
     }
 }
 
-int fbx_blocks(int64_t work) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(1 << 20, (work + FBX_BLOCK - 1) / FBX_BLOCK));
-}
-
-template <typename T>
-bool fbx_volumes_ok(const T *p, const T *q, const T *img, int64_t npts, int F) {
-    constexpr int VEC = 16 / (int)sizeof(T);
-    return npts > 0 && npts % VEC == 0 && F >= 1 && p && q && img && p != q &&
-           ((uintptr_t)p | (uintptr_t)q | (uintptr_t)img) % 16 == 0;
-}
-
 }  // namespace
 
 template <typename T>
 hipError_t launch_fbornx_offset(const GridDesc &g, T *p, const T *q, const T *img, int F, int axis, int64_t h, int beta,
                                 hipStream_t s) {
     constexpr int VEC = 16 / (int)sizeof(T);
-    if (!fbx_volumes_ok(p, q, img, g.npts, F) || g.cx % 4 != 0 || g.nx > g.cx || axis < 0 || axis > 2 ||
+    if (!volumes_ok<T>(g.npts, F, p, q, img) || p == q || g.cx % 4 != 0 || g.nx > g.cx || axis < 0 || axis > 2 ||
         g.npts != (int64_t)g.nz * g.ny * g.cx || h > INT32_MAX || h < INT32_MIN)
         return hipErrorInvalidValue;
-    const dim3 grid(fbx_blocks(g.npts / VEC)), block(FBX_BLOCK);
+    const dim3 grid(blocks(g.npts / VEC)), block(BLOCK);
     if (axis == 2 && (2 * h) % VEC != 0)
         hipLaunchKernelGGL((fbornx_offset<T, VEC, true>), grid, block, 0, s, g, p, q, img, F, axis, h, beta);
     else
@@ -174,9 +121,8 @@ template <typename T>
 hipError_t launch_fbornx_lag(T *p, const T *q, const T *img, const double *cs, int64_t npts, int F, int beta,
                              hipStream_t s) {
     constexpr int VEC = 16 / (int)sizeof(T);
-    if (!fbx_volumes_ok(p, q, img, npts, F) || !cs) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((fbornx_lag<T, VEC>), dim3(fbx_blocks(npts / VEC)), dim3(FBX_BLOCK), 0, s, p, q, img, cs, npts, F,
-                       beta);
+    if (!volumes_ok<T>(npts, F, p, q, img) || p == q || !cs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((fbornx_lag<T, VEC>), dim3(blocks(npts / VEC)), dim3(BLOCK), 0, s, p, q, img, cs, npts, F, beta);
     return hipGetLastError();
 }
 

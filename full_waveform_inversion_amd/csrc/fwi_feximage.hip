@@ -22,96 +22,48 @@
 // is formed from it; a thread none of whose cells passes reads nothing and writes zeros, and so do the pad columns.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "fwi_feximage.h"
+#include "fwi_fstore_device.h"
 
 namespace fwi {
 
 namespace {
 
-constexpr int FEX_BLOCK = 256;
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-    T e[V];
-};
-
-// the V cells at p: one vector read, or (ELEM) the cells of `mask` one by one, the others 0 and never addressed
-template <typename T, int V, bool ELEM>
-__device__ __forceinline__ Pack<T, V> fex_load(const T *__restrict__ p, unsigned mask) {
-    using P = Pack<T, V>;
-    if (!ELEM) return *(const P *)p;
-    P r;
-#pragma unroll
-    for (int e = 0; e < V; ++e) r.e[e] = (mask >> e & 1u) ? p[e] : T(0);
-    return r;
-}
+using namespace fstore;
 
 // axis: 0 = z, 1 = y, 2 = x.  ELEM = false: h e is a whole number of vectors (any h along z or y, h % V == 0 along x).
 template <typename T, int V, bool ELEM>
-__global__ __launch_bounds__(FEX_BLOCK) void feximage_offset(GridDesc g, T *__restrict__ dst, const T *__restrict__ q,
-                                                             const T *__restrict__ m, const double *__restrict__ a,
-                                                             int F, int axis, int64_t h) {
+__global__ __launch_bounds__(BLOCK) void feximage_offset(GridDesc g, T *__restrict__ dst, const T *__restrict__ q,
+                                                         const T *__restrict__ m, const double *__restrict__ a, int F,
+                                                         int axis, int64_t h) {
     using P = Pack<T, V>;
-    const int64_t npts = g.npts;
+    const int64_t npts = g.npts, sh = shift_elems(g, axis, h);
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = tid; i < npts / V; i += nthr) {
         const int64_t i0 = i * V, row = i0 / g.cx;  // row = z * ny + y
         const int x = (int)(i0 - row * g.cx);
-        unsigned mask = 0;  // bit e: cell x + e and both of its shifted cells lie in the grid
-        if (axis == 2) {
-#pragma unroll
-            for (int e = 0; e < V; ++e) {
-                const int64_t lo = x + e - h, hi = x + e + h;
-                if (lo >= 0 && lo < g.nx && hi >= 0 && hi < g.nx) mask |= 1u << e;
-            }
-        } else {
-            const int64_t c = axis == 0 ? row / g.ny : row % g.ny, n = axis == 0 ? g.nz : g.ny;
-            if (c - h >= 0 && c - h < n && c + h >= 0 && c + h < n) {
-#pragma unroll
-                for (int e = 0; e < V; ++e)
-                    if (x + e < g.nx) mask |= 1u << e;
-            }
-        }
-        P d;
+        const unsigned mask = shift_mask<V>(g, row, x, axis, -h, h);
         if (mask == 0) {
-#pragma unroll
-            for (int e = 0; e < V; ++e) d.e[e] = T(0);
-            *(P *)(dst + i0) = d;
+            *(P *)(dst + i0) = zero_pack<T, V>();
             continue;
         }
-        // (|h| < n from here on: the shift in elements fits, and both shifted vectors lie inside the volume)
-        const int64_t sh = h * (axis == 2 ? 1 : axis == 1 ? (int64_t)g.cx : (int64_t)g.ny * g.cx);
-        const T *qk = q + i0 - sh, *mk = m + i0 + sh;  // Re, Im of frequency k: qk, qk + npts
-        P qr0 = fex_load<T, V, ELEM>(qk, mask), qi0 = fex_load<T, V, ELEM>(qk + npts, mask);
-        P mr0 = fex_load<T, V, ELEM>(mk, mask), mi0 = fex_load<T, V, ELEM>(mk + npts, mask);
+        // (|h| < n from here on: sh is the shift in elements, and both shifted vectors lie inside the volume)
         double s[V];
 #pragma unroll
         for (int e = 0; e < V; ++e) s[e] = 0.0;
+        Walk<T, V, ELEM, true> w(q + i0 - sh, m + i0 + sh, npts, mask);
 #pragma unroll 1
         for (int k = 0; k < F; ++k) {
-            P qr1 = qr0, qi1 = qi0, mr1 = mr0, mi1 = mi0;  // the next frequency's vectors, in flight under this one's sums
-            if (k + 1 < F) {
-                qr1 = fex_load<T, V, ELEM>(qk + 2 * npts, mask);
-                qi1 = fex_load<T, V, ELEM>(qk + 3 * npts, mask);
-                mr1 = fex_load<T, V, ELEM>(mk + 2 * npts, mask);
-                mi1 = fex_load<T, V, ELEM>(mk + 3 * npts, mask);
-            }
+            w.prefetch(k + 1 < F);
             const double ak = a[k];
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-                double t = (double)qr0.e[e] * (double)mr0.e[e];
-                t = fma((double)qi0.e[e], (double)mi0.e[e], t);
+                const double t = re_qconjm((double)w.qr.e[e], (double)w.qi.e[e], (double)w.mr.e[e], (double)w.mi.e[e]);
                 s[e] = fma(ak, t, s[e]);
             }
-            qr0 = qr1;
-            qi0 = qi1;
-            mr0 = mr1;
-            mi0 = mi1;
-            qk += 2 * npts;
-            mk += 2 * npts;
+            w.next();
         }
+        P d;
 #pragma unroll
         for (int e = 0; e < V; ++e) d.e[e] = (mask >> e & 1u) ? (T)s[e] : T(0);
         *(P *)(dst + i0) = d;
@@ -119,42 +71,31 @@ __global__ __launch_bounds__(FEX_BLOCK) void feximage_offset(GridDesc g, T *__re
 }
 
 template <typename T, int V>
-__global__ __launch_bounds__(FEX_BLOCK) void feximage_lag(T *__restrict__ dst, const T *__restrict__ q,
-                                                          const T *__restrict__ m, const double *__restrict__ cd,
-                                                          int64_t npts, int F) {
+__global__ __launch_bounds__(BLOCK) void feximage_lag(T *__restrict__ dst, const T *__restrict__ q,
+                                                      const T *__restrict__ m, const double *__restrict__ cd,
+                                                      int64_t npts, int F) {
     using P = Pack<T, V>;
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = tid; i < npts / V; i += nthr) {
         const int64_t i0 = i * V;
-        const T *qk = q + i0, *mk = m + i0;  // Re, Im of frequency k: qk, qk + npts
-        P qr0 = *(const P *)qk, qi0 = *(const P *)(qk + npts), mr0 = *(const P *)mk, mi0 = *(const P *)(mk + npts);
         double s[V];
 #pragma unroll
         for (int e = 0; e < V; ++e) s[e] = 0.0;
+        Walk<T, V, false, true> w(q + i0, m + i0, npts, 0u);
 #pragma unroll 1
         for (int k = 0; k < F; ++k) {
-            P qr1 = qr0, qi1 = qi0, mr1 = mr0, mi1 = mi0;  // the next frequency's vectors, in flight under this one's sums
-            if (k + 1 < F) {
-                qr1 = *(const P *)(qk + 2 * npts);
-                qi1 = *(const P *)(qk + 3 * npts);
-                mr1 = *(const P *)(mk + 2 * npts);
-                mi1 = *(const P *)(mk + 3 * npts);
-            }
+            w.prefetch(k + 1 < F);
             const double ck = cd[k], dk = cd[F + k];
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-                const double qr = (double)qr0.e[e], qi = (double)qi0.e[e], mr = (double)mr0.e[e], mi = (double)mi0.e[e];
-                const double pr = fma(qi, mi, qr * mr);
+                const double qr = (double)w.qr.e[e], qi = (double)w.qi.e[e];
+                const double mr = (double)w.mr.e[e], mi = (double)w.mi.e[e];
+                const double pr = re_qconjm(qr, qi, mr, mi);
                 const double pi = fma(qi, mr, -(qr * mi));
                 s[e] = fma(ck, pr, s[e]);
                 s[e] = fma(dk, pi, s[e]);
             }
-            qr0 = qr1;
-            qi0 = qi1;
-            mr0 = mr1;
-            mi0 = mi1;
-            qk += 2 * npts;
-            mk += 2 * npts;
+            w.next();
         }
         P d;
 #pragma unroll
@@ -163,27 +104,16 @@ __global__ __launch_bounds__(FEX_BLOCK) void feximage_lag(T *__restrict__ dst, c
     }
 }
 
-int fex_blocks(int64_t work) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(1 << 20, (work + FEX_BLOCK - 1) / FEX_BLOCK));
-}
-
-template <typename T>
-bool fex_volumes_ok(const T *dst, const T *q, const T *m, const double *w, int64_t npts, int F) {
-    constexpr int VEC = 16 / (int)sizeof(T);
-    return npts > 0 && npts % VEC == 0 && F >= 1 && dst && q && m && w &&
-           ((uintptr_t)dst | (uintptr_t)q | (uintptr_t)m) % 16 == 0;
-}
-
 }  // namespace
 
 template <typename T>
 hipError_t launch_feximage_offset(const GridDesc &g, T *dst, const T *q, const T *m, const double *a, int F, int axis,
                                   int64_t h, hipStream_t s) {
     constexpr int VEC = 16 / (int)sizeof(T);
-    if (!fex_volumes_ok(dst, q, m, a, g.npts, F) || g.cx % 4 != 0 || g.nx > g.cx || axis < 0 || axis > 2 ||
+    if (!volumes_ok<T>(g.npts, F, dst, q, m) || !a || g.cx % 4 != 0 || g.nx > g.cx || axis < 0 || axis > 2 ||
         g.npts != (int64_t)g.nz * g.ny * g.cx)
         return hipErrorInvalidValue;
-    const dim3 grid(fex_blocks(g.npts / VEC)), block(FEX_BLOCK);
+    const dim3 grid(blocks(g.npts / VEC)), block(BLOCK);
     if (axis == 2 && h % VEC != 0)
         hipLaunchKernelGGL((feximage_offset<T, VEC, true>), grid, block, 0, s, g, dst, q, m, a, F, axis, h);
     else
@@ -194,9 +124,8 @@ hipError_t launch_feximage_offset(const GridDesc &g, T *dst, const T *q, const T
 template <typename T>
 hipError_t launch_feximage_lag(T *dst, const T *q, const T *m, const double *cd, int64_t npts, int F, hipStream_t s) {
     constexpr int VEC = 16 / (int)sizeof(T);
-    if (!fex_volumes_ok(dst, q, m, cd, npts, F)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((feximage_lag<T, VEC>), dim3(fex_blocks(npts / VEC)), dim3(FEX_BLOCK), 0, s, dst, q, m, cd, npts,
-                       F);
+    if (!volumes_ok<T>(npts, F, dst, q, m) || !cd) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((feximage_lag<T, VEC>), dim3(blocks(npts / VEC)), dim3(BLOCK), 0, s, dst, q, m, cd, npts, F);
     return hipGetLastError();
 }
 

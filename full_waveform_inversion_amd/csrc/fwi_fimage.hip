@@ -12,26 +12,20 @@
 //   then        dst = T(s) (beta = 0) or T(double(dst) + s) (beta = 1)
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "fwi_fimage.h"
+#include "fwi_fstore_device.h"
 
 namespace fwi {
 
 namespace {
 
-constexpr int FIMAGE_BLOCK = 256;
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-    T e[V];
-};
+using namespace fstore;
 
 // The V cells from compact element i0 on lie in one row (the row stride cx is a multiple of 4).  Where they are all grid
 // cells and their padded address is 16-byte aligned they come in one vector read, else in V scalar reads, which
 // neighbouring lanes coalesce.
 template <typename T, int V>
-__global__ __launch_bounds__(FIMAGE_BLOCK) void fimage_pack(GridDesc g, const T *__restrict__ u, T *__restrict__ slot) {
+__global__ __launch_bounds__(BLOCK) void fimage_pack(GridDesc g, const T *__restrict__ u, T *__restrict__ slot) {
     using P = Pack<T, V>;
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = tid; i < g.npts / V; i += nthr) {
@@ -52,47 +46,28 @@ __global__ __launch_bounds__(FIMAGE_BLOCK) void fimage_pack(GridDesc g, const T 
 
 // MODE 0: image (q and m), MODE 1: illuminate (q alone; m is not read)
 template <typename T, int V, int MODE>
-__global__ __launch_bounds__(FIMAGE_BLOCK) void fimage_sum(T *__restrict__ dst, const T *__restrict__ q,
-                                                           const T *__restrict__ m, const double *__restrict__ a,
-                                                           int64_t npts, int F, int beta) {
+__global__ __launch_bounds__(BLOCK) void fimage_sum(T *__restrict__ dst, const T *__restrict__ q,
+                                                    const T *__restrict__ m, const double *__restrict__ a, int64_t npts,
+                                                    int F, int beta) {
     using P = Pack<T, V>;
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = tid; i < npts / V; i += nthr) {
         const int64_t i0 = i * V;
-        const T *qk = q + i0, *mk = m + i0;  // Re, Im of frequency k: qk, qk + npts
-        P qr0 = *(const P *)qk, qi0 = *(const P *)(qk + npts), mr0 = qr0, mi0 = qi0;
-        if (MODE == 0) {
-            mr0 = *(const P *)mk;
-            mi0 = *(const P *)(mk + npts);
-        }
         double s[V];
 #pragma unroll
         for (int e = 0; e < V; ++e) s[e] = 0.0;
+        Walk<T, V, false, MODE == 0> w(q + i0, m + i0, npts, 0u);
 #pragma unroll 1
         for (int k = 0; k < F; ++k) {
-            P qr1 = qr0, qi1 = qi0, mr1 = mr0, mi1 = mi0;  // the next frequency's vectors, in flight under this one's sums
-            if (k + 1 < F) {
-                qr1 = *(const P *)(qk + 2 * npts);
-                qi1 = *(const P *)(qk + 3 * npts);
-                if (MODE == 0) {
-                    mr1 = *(const P *)(mk + 2 * npts);
-                    mi1 = *(const P *)(mk + 3 * npts);
-                }
-            }
+            w.prefetch(k + 1 < F);
+            const P &mr = MODE == 0 ? w.mr : w.qr, &mi = MODE == 0 ? w.mi : w.qi;  // illuminate: M_k is Q_k
             const double ak = a[k];
 #pragma unroll
             for (int e = 0; e < V; ++e) {
-                const double re = (double)qr0.e[e], im = (double)qi0.e[e];
-                double t = re * (MODE == 0 ? (double)mr0.e[e] : re);
-                t = fma(im, MODE == 0 ? (double)mi0.e[e] : im, t);
+                const double t = re_qconjm((double)w.qr.e[e], (double)w.qi.e[e], (double)mr.e[e], (double)mi.e[e]);
                 s[e] = fma(ak, t, s[e]);
             }
-            qr0 = qr1;
-            qi0 = qi1;
-            mr0 = mr1;
-            mi0 = mi1;
-            qk += 2 * npts;
-            mk += 2 * npts;
+            w.next();
         }
         P d;
         if (beta) {
@@ -107,18 +82,12 @@ __global__ __launch_bounds__(FIMAGE_BLOCK) void fimage_sum(T *__restrict__ dst, 
     }
 }
 
-int fimage_blocks(int64_t work) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(1 << 20, (work + FIMAGE_BLOCK - 1) / FIMAGE_BLOCK));
-}
-
 template <typename T, int MODE>
 hipError_t launch_sum(T *dst, const T *q, const T *m, const double *a, int64_t npts, int F, int beta, hipStream_t s) {
     constexpr int VEC = 16 / (int)sizeof(T);
-    if (npts <= 0 || npts % VEC != 0 || F < 1 || (beta != 0 && beta != 1) || !dst || !q || !m || !a ||
-        ((uintptr_t)dst | (uintptr_t)q | (uintptr_t)m) % 16 != 0)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL((fimage_sum<T, VEC, MODE>), dim3(fimage_blocks(npts / VEC)), dim3(FIMAGE_BLOCK), 0, s, dst, q, m, a,
-                       npts, F, beta);
+    if (!volumes_ok<T>(npts, F, dst, q, m) || (beta != 0 && beta != 1) || !a) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((fimage_sum<T, VEC, MODE>), dim3(blocks(npts / VEC)), dim3(BLOCK), 0, s, dst, q, m, a, npts, F,
+                       beta);
     return hipGetLastError();
 }
 
@@ -128,7 +97,7 @@ template <typename T>
 hipError_t launch_fimage_pack(const GridDesc &g, const T *u, T *slot, hipStream_t s) {
     constexpr int VEC = 16 / (int)sizeof(T);
     if (g.npts <= 0 || g.cx % 4 != 0 || !u || !slot || (uintptr_t)slot % 16 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((fimage_pack<T, VEC>), dim3(fimage_blocks(g.npts / VEC)), dim3(FIMAGE_BLOCK), 0, s, g, u, slot);
+    hipLaunchKernelGGL((fimage_pack<T, VEC>), dim3(blocks(g.npts / VEC)), dim3(BLOCK), 0, s, g, u, slot);
     return hipGetLastError();
 }
 

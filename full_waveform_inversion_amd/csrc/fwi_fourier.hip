@@ -14,20 +14,14 @@
 //   synthesis  o_b = 0; for k = 0 .. F - 1: o_b = fma(Re_k, c_bk, o_b); o_b = fma(-Im_k, s_bk, o_b); then slot_b = T(o_b)
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "fwi_fourier.h"
+#include "fwi_fstore_device.h"
 
 namespace fwi {
 
 namespace {
 
-constexpr int FOURIER_BLOCK = 256;
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-    T e[V];
-};
+using namespace fstore;
 
 // slot of sample j0 + b, from j = slot0 + b with slot0 = j0 % ring_slots and b < ring_slots
 __device__ __forceinline__ int ring_slot(int j, int ring_slots) { return j < ring_slots ? j : j - ring_slots; }
@@ -132,29 +126,38 @@ __device__ __forceinline__ void synthesise_cells(T *__restrict__ ring, const T *
 
 // V cells per thread: 16 / sizeof(T) where every volume starts 16-byte aligned (npts % V == 0), else 1
 template <typename T, int V>
-__global__ __launch_bounds__(FOURIER_BLOCK) void fourier_analyse(T *acc, const T *ring, int64_t npts, int ring_slots,
-                                                                 int slot0, int j0, int nb, const double *tw, int tw_rows,
-                                                                 int F) {
+__global__ __launch_bounds__(BLOCK) void fourier_analyse(T *acc, const T *ring, int64_t npts, int ring_slots, int slot0,
+                                                         int j0, int nb, const double *tw, int tw_rows, int F) {
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = tid; i < npts / V; i += nthr)
         analyse_cells<T, V>(acc, ring, npts, i * V, ring_slots, slot0, j0, nb, tw, tw_rows, F);
 }
 
 template <typename T, int V>
-__global__ __launch_bounds__(FOURIER_BLOCK) void fourier_synthesise(T *ring, const T *acc, int64_t npts, int ring_slots,
-                                                                    int slot0, int j0, int nb, const double *tw,
-                                                                    int tw_rows, int F) {
+__global__ __launch_bounds__(BLOCK) void fourier_synthesise(T *ring, const T *acc, int64_t npts, int ring_slots,
+                                                            int slot0, int j0, int nb, const double *tw, int tw_rows,
+                                                            int F) {
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = tid; i < npts / V; i += nthr)
         synthesise_cells<T, V>(ring, acc, npts, i * V, ring_slots, slot0, j0, nb, tw, tw_rows, F);
 }
 
-int fourier_blocks(int64_t work) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(1 << 20, (work + FOURIER_BLOCK - 1) / FOURIER_BLOCK));
-}
+// either transform: `wide` with 16 / sizeof(T) cells per thread where npts allows it, else `one`; `out` is the volume
+// set it writes (acc of the analysis, ring of the synthesis), `in` the one it reads
+template <typename T>
+using Transform = void (*)(T *, const T *, int64_t, int, int, int, int, const double *, int, int);
 
-bool fourier_args_ok(int64_t npts, int ring_slots, int slot0, int j0, int nb, int F) {
-    return npts > 0 && ring_slots >= 1 && j0 >= 0 && nb >= 1 && nb <= FOURIER_BMAX && nb <= ring_slots && F >= 1;
+template <typename T>
+hipError_t launch_transform(Transform<T> wide, Transform<T> one, T *out, const T *in, int64_t npts, int ring_slots,
+                            int slot0, int j0, int nb, const double *tw, int tw_rows, int F, hipStream_t s) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    if (npts <= 0 || ring_slots < 1 || j0 < 0 || nb < 1 || nb > FOURIER_BMAX || nb > ring_slots || F < 1 ||
+        j0 + FOURIER_BMAX > tw_rows || !out || !in || !tw)
+        return hipErrorInvalidValue;
+    const bool vec = npts % VEC == 0;
+    hipLaunchKernelGGL(vec ? wide : one, dim3(blocks(vec ? npts / VEC : npts)), dim3(BLOCK), 0, s, out, in, npts,
+                       ring_slots, slot0, j0, nb, tw, tw_rows, F);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -162,31 +165,15 @@ bool fourier_args_ok(int64_t npts, int ring_slots, int slot0, int j0, int nb, in
 template <typename T>
 hipError_t launch_fourier_analyse(T *acc, const T *ring, int64_t npts, int ring_slots, int slot0, int j0, int nb,
                                   const double *tw, int tw_rows, int F, hipStream_t s) {
-    constexpr int VEC = 16 / (int)sizeof(T);
-    if (!fourier_args_ok(npts, ring_slots, slot0, j0, nb, F) || j0 + FOURIER_BMAX > tw_rows || !acc || !ring || !tw)
-        return hipErrorInvalidValue;
-    if (npts % VEC == 0)
-        hipLaunchKernelGGL((fourier_analyse<T, VEC>), dim3(fourier_blocks(npts / VEC)), dim3(FOURIER_BLOCK), 0, s, acc,
-                           ring, npts, ring_slots, slot0, j0, nb, tw, tw_rows, F);
-    else
-        hipLaunchKernelGGL((fourier_analyse<T, 1>), dim3(fourier_blocks(npts)), dim3(FOURIER_BLOCK), 0, s, acc, ring, npts,
-                           ring_slots, slot0, j0, nb, tw, tw_rows, F);
-    return hipGetLastError();
+    return launch_transform<T>(fourier_analyse<T, 16 / (int)sizeof(T)>, fourier_analyse<T, 1>, acc, ring, npts, ring_slots,
+                               slot0, j0, nb, tw, tw_rows, F, s);
 }
 
 template <typename T>
 hipError_t launch_fourier_synthesise(T *ring, const T *acc, int64_t npts, int ring_slots, int slot0, int j0, int nb,
                                      const double *tw, int tw_rows, int F, hipStream_t s) {
-    constexpr int VEC = 16 / (int)sizeof(T);
-    if (!fourier_args_ok(npts, ring_slots, slot0, j0, nb, F) || j0 + FOURIER_BMAX > tw_rows || !acc || !ring || !tw)
-        return hipErrorInvalidValue;
-    if (npts % VEC == 0)
-        hipLaunchKernelGGL((fourier_synthesise<T, VEC>), dim3(fourier_blocks(npts / VEC)), dim3(FOURIER_BLOCK), 0, s, ring,
-                           acc, npts, ring_slots, slot0, j0, nb, tw, tw_rows, F);
-    else
-        hipLaunchKernelGGL((fourier_synthesise<T, 1>), dim3(fourier_blocks(npts)), dim3(FOURIER_BLOCK), 0, s, ring, acc,
-                           npts, ring_slots, slot0, j0, nb, tw, tw_rows, F);
-    return hipGetLastError();
+    return launch_transform<T>(fourier_synthesise<T, 16 / (int)sizeof(T)>, fourier_synthesise<T, 1>, ring, acc, npts,
+                               ring_slots, slot0, j0, nb, tw, tw_rows, F, s);
 }
 
 #define FWI_FOURIER_INSTANTIATE(T)                                                                                  \

@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "fwi_fsplit.h"
+#include "fwi_fstore_device.h"
 
 namespace fwi {
 
@@ -44,18 +45,8 @@ constexpr int FSPLIT_RPT = (FSPLIT_CHUNK + 2 * FSPLIT_RMAX + FSPLIT_PHASES - 1) 
 constexpr int FSPLIT_WAVES = FSPLIT_BLOCK / 64;
 static_assert(FSPLIT_CHUNK % FSPLIT_PHASES == 0 && FSPLIT_RMAX <= 64, "tiling of fsplit_march / halo of fsplit_row");
 
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-    T e[V];
-};
-
-template <typename T, int V>
-__device__ __forceinline__ Pack<T, V> fsplit_zero() {
-    Pack<T, V> p;
-#pragma unroll
-    for (int e = 0; e < V; ++e) p.e[e] = T(0);
-    return p;
-}
+using fstore::Pack;
+using fstore::zero_pack;
 
 // The per-step sums of one cell's V elements from its filtered (hq, hm) and own (qc, mc) coefficients.
 template <typename T, int V>
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(FSPLIT_BLOCK) void fsplit_march(T *__restrict__ dst
     const T *qs = q + base + (i0 - R + phase) * stride, *ms = m + base + (i0 - R + phase) * stride;
 #pragma unroll
     for (int j = 0; j < FSPLIT_RPT; ++j) {
-        pq[j] = pm[j] = fsplit_zero<T, V>();
+        pq[j] = pm[j] = zero_pack<T, V>();
         if (rows >> j & 1u) {
             pq[j] = *(const P *)(qs + (int64_t)j * FSPLIT_PHASES * stride);
             pm[j] = *(const P *)(ms + (int64_t)j * FSPLIT_PHASES * stride);
@@ -218,7 +209,7 @@ __global__ __launch_bounds__(FSPLIT_BLOCK) void fsplit_row(T *__restrict__ dst, 
         if (live && x + e < nx) mask |= 1u << e;
 
     const T *qs = q + row * cx, *ms = m + row * cx;
-    P pq = fsplit_zero<T, V>(), pm = pq;  // the next step's cells, in flight under this step's sums
+    P pq = zero_pack<T, V>(), pm = pq;  // the next step's cells, in flight under this step's sums
     T pql = T(0), pqr = T(0), pml = T(0), pmr = T(0);
     if (mask) {
         pq = *(const P *)(qs + x);
@@ -293,9 +284,8 @@ template <typename T>
 hipError_t launch_fsplit(const GridDesc &g, T *dst, const T *q, const T *m, const double *a, int F, int axis,
                          const double *taps, int ntaps, double alpha, double beta, hipStream_t s) {
     constexpr int V = 16 / (int)sizeof(T);
-    if (g.npts <= 0 || g.npts % V != 0 || F < 1 || !dst || !q || !m || !a || !taps ||
-        ((uintptr_t)dst | (uintptr_t)q | (uintptr_t)m) % 16 != 0 || g.cx % 4 != 0 || g.nx > g.cx || axis < 0 || axis > 2 ||
-        g.npts != (int64_t)g.nz * g.ny * g.cx || ntaps < 0 || ntaps > FSPLIT_RMAX)
+    if (!fstore::volumes_ok<T>(g.npts, F, dst, q, m) || !a || !taps || g.cx % 4 != 0 || g.nx > g.cx || axis < 0 ||
+        axis > 2 || g.npts != (int64_t)g.nz * g.ny * g.cx || ntaps < 0 || ntaps > FSPLIT_RMAX)
         return hipErrorInvalidValue;
     const int n = axis == 0 ? g.nz : axis == 1 ? g.ny : g.nx;
     if (ntaps >= std::max(n, 1)) return hipErrorInvalidValue;  // the caller drops the taps that touch nothing
