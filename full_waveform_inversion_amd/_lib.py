@@ -31,6 +31,7 @@ TT_KMAX = 1024  # FWI_TT_KMAX
 OT_TRANSFORMS = {"linear": 0, "softplus": 1}  # FWI_OT_LINEAR, FWI_OT_SOFTPLUS
 FOURIER_FMAX, FOURIER_BMAX = 64, 8  # FWI_FOURIER_FMAX, FWI_FOURIER_BMAX
 SPLIT_SAME, SPLIT_OPPOSITE, SPLIT_HILBERT, SPLIT_RMAX = 0, 1, 2, 64  # FWI_SPLIT_*, FWI_SPLIT_RMAX
+SHIFT_SUM_MAX = 64  # FWI_SHIFT_SUM_MAX
 SPEC_KINDS = {"l2": 0, "phase": 1, "logamp": 2, "log": 3}  # FWI_SPEC_L2, FWI_SPEC_PHASE, FWI_SPEC_LOGAMP, FWI_SPEC_LOG
 UNIQUE_ID_BYTES = 128
 EINVAL = 1
@@ -129,6 +130,7 @@ SIGNATURES = {
     "fwi_vec_recip": (C.c_int, [_P, _I32, _D, _D]),
     "fwi_vec_smooth": (C.c_int, [_P, _I32, C.POINTER(_D)]),
     "fwi_vec_regularizer": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _D, _D, C.POINTER(_D), _D, C.POINTER(_D)]),
+    "fwi_vec_shift_sum": (C.c_int, [_P, _I32, _I32, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_D), _D]),
     "fwi_born": (C.c_int, [_P, _I32, _P, _I32, _P]),
     "fwi_born_vec": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "fwi_born_imaging": (C.c_int, [_P, _I32, _P, _I32, _P]),

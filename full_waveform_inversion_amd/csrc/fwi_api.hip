@@ -39,6 +39,7 @@
 #include "fwi_match.h"
 #include "fwi_match_solve.h"
 #include "fwi_reg.h"
+#include "fwi_slant.h"
 #include "fwi_smooth.h"
 
 using namespace fwi;
@@ -4164,6 +4165,44 @@ int fwi_vec_smooth(fwi_ctx *ctx, int32_t y, const double *sigma) {
     if (!ctx->smooth_tmp) HIPCHK(ctx, hipMalloc(&ctx->smooth_tmp, (size_t)g.npts * ctx->esize));
     return DISPATCH(ctx, vec_smooth_passes<float>(ctx, vy, axis, R, w, npass),
                     vec_smooth_passes<double>(ctx, vy, axis, R, w, npass));
+}
+
+int fwi_vec_shift_sum(fwi_ctx *ctx, int32_t dst, int32_t nsrc, const int32_t *src_slots, const double *shifts,
+                      const double *weights, double beta) {
+    if (!ctx) return FWI_EINVAL;
+    void *vd = vec_slot(ctx, dst);
+    if (!vd) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: dst: vector slot %d does not exist", (int)dst);
+    if (nsrc < 1 || nsrc > FWI_SHIFT_SUM_MAX)
+        return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: nsrc = %d must be in [1, %d]", (int)nsrc, FWI_SHIFT_SUM_MAX);
+    if (!src_slots) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: null src_slots");
+    if (!shifts) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: null shifts");
+    if (!std::isfinite(beta)) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: beta = %g must be finite", beta);
+    static_assert(FWI_SHIFT_SUM_MAX == SLANT_MAX, "include/fwi.h and fwi_slant.h disagree");
+    const GridDesc &g = ctx->gd;
+    SlantTable t = {};
+    int kept = 0;
+    for (int i = 0; i < nsrc; ++i) {
+        const void *vs = vec_slot(ctx, src_slots[i]);
+        const double s = shifts[i], w = weights ? weights[i] : 1.0;
+        if (!vs)
+            return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: src_slots[%d]: vector slot %d does not exist", i,
+                             (int)src_slots[i]);
+        if (vs == vd)
+            return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: src_slots[%d] is dst (slot %d)", i, (int)dst);
+        if (!std::isfinite(s)) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: shifts[%d] = %g must be finite", i, s);
+        if (!std::isfinite(w)) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: weights[%d] = %g must be finite", i, w);
+        if (std::fabs(s) >= (double)g.nz + 1.0) continue;  // wholly outside the grid: tested before n is formed
+        const double n = std::floor(s), f = s - n;
+        t.src[kept] = vs;
+        t.n[kept] = (int64_t)n;
+        t.c0[kept] = w * (1.0 - f);
+        t.c1[kept] = w * f;
+        ++kept;
+    }
+    (void)hipSetDevice(ctx->cfg.device);
+    HIPCHK(ctx, DISPATCH(ctx, launch_slant_sum<float>(g, (float *)vd, t, kept, beta, ctx->stream),
+                         launch_slant_sum<double>(g, (double *)vd, t, kept, beta, ctx->stream)));
+    return FWI_OK;
 }
 
 int fwi_vec_regularizer(fwi_ctx *ctx, int32_t kind, int32_t x, int32_t x0, int32_t v, int32_t out, double alpha,

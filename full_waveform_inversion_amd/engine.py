@@ -959,6 +959,67 @@ class Engine:
                                                 C.byref(val)))
         return val.value
 
+    def vec_shift_sum(self, dst, srcs, shifts, weights=None, beta=0.0):
+        """Slot ``dst := beta dst + sum_i weights[i] S_{shifts[i]} srcs[i]`` on the device (``fwi_vec_shift_sum``): every
+        source slot shifted along depth (the first axis of ``shape``) by a real number of cells, linearly interpolated
+        between the two nearest planes, planes outside the grid counting as zero.  At most ``_lib.SHIFT_SUM_MAX`` sources,
+        none of them ``dst``; ``weights=None``: ones.  The fp64 twin is :func:`fourier.shift_sum`."""
+        src = np.ascontiguousarray(np.atleast_1d(srcs), dtype=np.int32)
+        s = np.ascontiguousarray(np.atleast_1d(shifts), dtype=np.float64)
+        if src.ndim != 1 or s.shape != src.shape:
+            raise _lib.FwiError(_lib.EINVAL, "vec_shift_sum: shifts must hold one shift per source slot, got %r and %r"
+                                % (src.shape, s.shape))
+        wp = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.atleast_1d(weights), dtype=np.float64)
+            if w.shape != src.shape:
+                raise _lib.FwiError(_lib.EINVAL, "vec_shift_sum: weights must hold one weight per source slot, got %r"
+                                    % (w.shape,))
+            wp = w.ctypes.data_as(C.POINTER(C.c_double))
+        self._chk(self._lib.fwi_vec_shift_sum(self._c, int(dst), int(src.size), src.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              s.ctypes.data_as(C.POINTER(C.c_double)), wp, float(beta)))
+
+    def angle_gather_vec(self, angle_slots, lag_slots, offsets, tangents, taper=None, transpose=False):
+        """The slant stack between an offset gather in ``lag_slots`` (half-offsets ``offsets``, whole cells) and an
+        angle gather in ``angle_slots`` (``tangents = tan(gamma)``), on the device (:func:`fourier.angle_gather`):
+
+            ``A_j = sum_l t_l S_{p_j h_l} E_l``, or with ``transpose``  ``E_l = t_l sum_j S_{-p_j h_l} A_j``
+
+        with ``t = taper`` (None: ones).  One :meth:`vec_shift_sum` per slot written; more than ``_lib.SHIFT_SUM_MAX``
+        sources are cut into chunks of that many, added up with ``beta = 1`` from the second chunk on.  The slots read
+        are unchanged; no slot may be on both sides."""
+        a = [int(s) for s in np.atleast_1d(angle_slots)]
+        e = [int(s) for s in np.atleast_1d(lag_slots)]
+        h = np.atleast_1d(np.asarray(offsets, np.float64))
+        p = np.atleast_1d(np.asarray(tangents, np.float64))
+        t = np.ones(h.size) if taper is None else np.atleast_1d(np.asarray(taper, np.float64))
+        if h.shape != (len(e),) or p.shape != (len(a),) or t.shape != h.shape:
+            raise _lib.FwiError(_lib.EINVAL, "angle_gather_vec: one offset (and taper weight) per lag slot and one "
+                                "tangent per angle slot, got %d offsets, %d weights, %d lag slots; %d tangents, %d angle "
+                                "slots" % (h.size, t.size, len(e), p.size, len(a)))
+        if np.any(h != np.round(h)):
+            raise _lib.FwiError(_lib.EINVAL, "angle_gather_vec: offsets must be whole cells")
+        if transpose:
+            calls = [(e[l], a, -(p * h[l]), np.full(p.size, t[l])) for l in range(h.size)]
+        else:
+            calls = [(a[j], e, p[j] * h, t) for j in range(p.size)]
+        M = _lib.SHIFT_SUM_MAX
+        for dst, srcs, shifts, w in calls:
+            for k in range(0, len(srcs), M):
+                self.vec_shift_sum(dst, srcs[k:k + M], shifts[k:k + M], w[k:k + M], 0.0 if k == 0 else 1.0)
+
+    def gather_moment(self, slots, lags, power=2):
+        """``(sum_l |lag_l|^power <E_l, E_l>, sum_l <E_l, E_l>)`` of the gather in ``slots`` from :meth:`vec_dot`, nothing
+        downloaded.  The ratio at ``power=2`` is :func:`fourier.focusing`; half the first number at ``power=2`` is the
+        differential-semblance functional of the gather."""
+        slots = [int(s) for s in np.atleast_1d(slots)]
+        lags = np.atleast_1d(np.asarray(lags, np.float64))
+        if lags.shape != (len(slots),):
+            raise _lib.FwiError(_lib.EINVAL, "gather_moment: one lag per slot, got %d lags and %d slots"
+                                % (lags.size, len(slots)))
+        e = np.array([self.vec_dot(s, s) for s in slots])
+        return float(np.sum(np.abs(lags) ** power * e)), float(np.sum(e))
+
     def vec_clip(self, x, lo, hi):
         self._chk(self._lib.fwi_vec_clip(self._c, x, float(lo), float(hi)))
 

@@ -405,3 +405,106 @@ def focusing(E, lags):
     e = np.sum(np.abs(E.astype(np.float64)).reshape(lags.size, -1) ** 2, axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
         return float(np.sum(lags ** 2 * e) / np.sum(e))
+
+
+# -- angle-domain gathers (fwi_vec_shift_sum; csrc/fwi_slant.hip) ------------------------------------------------------
+#
+# A slant stack of a subsurface-offset gather over depth and half-offset (Sava and Fomel 2003).  Depth is the first model
+# axis, the half-offsets ``h_l`` are whole cells along a horizontal axis and share the grid spacing with depth, so the
+# tangents ``p_j = tan(gamma_j)`` are dimensionless::
+#
+#     S_s a (z, .) = (1 - f) a(z + n, .) + f a(z + n + 1, .),   n = floor(s), f = s - n
+#     A_j  = sum_l t_l S_{p_j h_l} E_l            angle gather; t: an optional taper over the lags
+#     E'_l = t_l sum_j S_{-p_j h_l} A_j           its exact transpose
+#
+# A tap outside ``0 .. nz - 1`` contributes zero and the other still counts, the second tap is not counted when its
+# coefficient is zero, ``|s| >= nz + 1`` gives zeros: with this masking ``S_s^T = S_{-s}`` exactly.  The transform is
+# kinematic: a plain slant stack with no rho filter and no claim on amplitudes.  An event that is flat across ``j`` says
+# that the model is right; the sign of ``gamma`` is a convention of this definition.  The horizontal axis of the offsets
+# does not enter, it only selects which gather was formed.
+
+SHIFT_SUM_MAX = 64  # FWI_SHIFT_SUM_MAX: the sources of one device call (the twin takes any number)
+
+
+def tangents(degrees):
+    """``tan(gamma)`` of the angles ``gamma`` in degrees, ``|gamma| < 90``, as a 1-D fp64 array."""
+    g = np.atleast_1d(np.asarray(degrees, np.float64))
+    if g.ndim != 1 or not np.all(np.abs(g) < 90.0):
+        raise ValueError("angles must be a 1-D array of degrees inside (-90, 90)")
+    return np.tan(np.deg2rad(g))
+
+
+def _shift_coeffs(s, w):
+    """``(n, c0, c1)`` of the shift ``s`` and the weight ``w`` as the engine's host path forms them in fp64"""
+    s, w = float(s), float(w)
+    if not np.isfinite(s) or not np.isfinite(w):
+        raise ValueError("shifts and weights must be finite")
+    n = int(np.floor(s))
+    f = s - n
+    return n, w * (1.0 - f), w * f
+
+
+def shift_sum(srcs, shifts, weights=None, beta=0.0, dst=None):
+    """``beta dst + sum_i w_i S_{s_i} src_i`` in fp64: the twin of ``Engine.vec_shift_sum``.  ``srcs``: ``(nsrc, *shape)``
+    with depth the first model axis; ``shifts``: ``nsrc`` finite numbers of cells; ``weights``: ``nsrc`` (None: ones).
+    With ``beta == 0`` ``dst`` is not read.  The sum runs per cell with the sources ascending, the first tap of a source
+    before its second, as on the device (which fuses each multiply-add and rounds to its dtype once at the end)."""
+    srcs = np.asarray(srcs, np.float64)
+    shifts = np.atleast_1d(np.asarray(shifts, np.float64))
+    if srcs.ndim < 2 or shifts.shape != srcs.shape[:1]:
+        raise ValueError("expected one shift per source, srcs as (nsrc, *shape)")
+    w = np.ones(shifts.size) if weights is None else np.atleast_1d(np.asarray(weights, np.float64))
+    if w.shape != shifts.shape:
+        raise ValueError("weights must hold one weight per source")
+    beta = float(beta)
+    if not np.isfinite(beta):
+        raise ValueError("beta must be finite")
+    nz = srcs.shape[1]
+    z = np.arange(nz)
+    acc = np.zeros(srcs.shape[1:], np.float64)
+    for i in range(shifts.size):
+        n, c0, c1 = _shift_coeffs(shifts[i], w[i])
+        if abs(float(shifts[i])) >= nz + 1:
+            continue
+        for off, c in ((n, c0), (n + 1, c1)):
+            if off == n + 1 and c == 0.0:
+                continue
+            ok = (z + off >= 0) & (z + off < nz)
+            acc[z[ok]] = acc[z[ok]] + c * srcs[i][z[ok] + off]
+    if beta == 0.0:
+        return acc
+    if dst is None:
+        raise ValueError("beta != 0 needs dst")
+    dst = np.asarray(dst, np.float64)
+    if dst.shape != acc.shape:
+        raise ValueError("dst must have the shape of one source")
+    return beta * dst + acc
+
+
+def _gather_args(G, offsets, n, taper):
+    G = np.asarray(G, np.float64)
+    h = np.atleast_1d(np.asarray(offsets, np.float64))
+    if h.ndim != 1 or not np.all(h == np.round(h)):
+        raise ValueError("offsets must be a 1-D array of whole cells")
+    if G.ndim < 2 or G.shape[0] != n:
+        raise ValueError("expected %d images, got shape %s" % (n, G.shape))
+    t = np.ones(h.size) if taper is None else np.atleast_1d(np.asarray(taper, np.float64))
+    if t.shape != h.shape or not np.all(np.isfinite(t)):
+        raise ValueError("taper must hold one finite weight per offset")
+    return G, h, t
+
+
+def angle_gather(E, offsets, tangents, taper=None):
+    """``A_j = sum_l t_l S_{p_j h_l} E_l`` as ``(len(tangents), *shape)`` fp64 from the offset gather ``E``,
+    ``(len(offsets), *shape)``, of the integer half-offsets ``offsets`` (``Engine.fourier_offset_images``)."""
+    p = np.atleast_1d(np.asarray(tangents, np.float64))
+    E, h, t = _gather_args(E, offsets, np.size(offsets), taper)
+    return np.stack([shift_sum(E, pj * h, t) for pj in p])
+
+
+def angle_gather_adjoint(A, offsets, tangents, taper=None):
+    """``E'_l = t_l sum_j S_{-p_j h_l} A_j`` as ``(len(offsets), *shape)`` fp64: the exact transpose of
+    :func:`angle_gather`, ``<A, T E> = <T^T A, E>`` to round-off."""
+    p = np.atleast_1d(np.asarray(tangents, np.float64))
+    A, h, t = _gather_args(A, offsets, p.size, taper)
+    return np.stack([shift_sum(A, -(p * h[l]), np.full(p.size, t[l])) for l in range(h.size)])

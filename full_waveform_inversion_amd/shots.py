@@ -486,6 +486,81 @@ def extended_image(engine, model, shots, kind, lags, axis=None, exchange=None, o
     return J, ext.gather(engine, ex)
 
 
+class _AngleGather(_Spectral):
+    """The adjoint of :func:`angle_gather`: ``Engine.adjoint_spectral(residual, image=False)``, then every lag of the
+    shot's offset gather formed in a scratch slot and added to that lag's slot on the device (an engine's first shot
+    writes the lag slots themselves); nothing is downloaded per shot.  A pool drives each engine from one thread."""
+
+    def __init__(self, engine, freq_weights, axis, offsets, tangents, slot0, taper):
+        super().__init__(engine, freq_weights, "slowness2", False)
+        self.axis = axis
+        self.offsets = [int(h) for h in np.atleast_1d(offsets)]
+        self.tangents = np.atleast_1d(np.asarray(tangents, np.float64))
+        self.taper = taper
+        L, n = len(self.offsets), self.tangents.size
+        self.lag_slots = list(range(int(slot0), int(slot0) + L))
+        self.angle_slots = list(range(int(slot0) + L, int(slot0) + L + n))
+        self.scratch = int(slot0) + L + n
+        self.seen = set()
+
+    def adjoint(self, e, shot, residual):
+        e.adjoint_spectral(self._residual(e, shot, residual), image=False)
+        first = id(e) not in self.seen
+        for slot, h in zip(self.lag_slots, self.offsets):
+            e.fourier_offset_image_vec(slot if first else self.scratch, self.axis, h, self.freq_weights)
+            if not first:
+                e.vec_axpby(slot, 1.0, self.scratch, 1.0)
+        self.seen.add(id(e))
+
+    def _download(self, engine, ex, slots):
+        engs = _engines(engine)
+        out = np.zeros((len(slots),) + tuple(engs[0].shape))
+        for e in engs:
+            if id(e) in self.seen:
+                out += np.stack([np.asarray(e.vec_download(s), np.float64) for s in slots])
+        return ex.reduce_array(out)
+
+    def gathers(self, engine, ex, return_offsets):
+        """(A, E or None) of this evaluation summed over shots, engines and ranks (zeros on a rank that owned no shot)"""
+        for e in _engines(engine):
+            if id(e) in self.seen:
+                e.angle_gather_vec(self.angle_slots, self.lag_slots, self.offsets, self.tangents, self.taper)
+        A = self._download(engine, ex, self.angle_slots)
+        return A, self._download(engine, ex, self.lag_slots) if return_offsets else None
+
+
+def angle_gather(engine, model, shots, axis, offsets, tangents, slot0=0, exchange=None, objective=None,
+                 freq_weights=None, taper=None, return_offsets=False):
+    """``(J, A)``: the misfit of :func:`misfit_and_gradient` and the angle-domain common-image gather of the shots at
+    ``model``, ``(len(tangents), *shape)`` in fp64, summed over shots, pool engines and ranks:
+
+        ``A_j = sum_l t_l S_{p_j h_l} E_l``  (``fourier.angle_gather``)
+
+    the slant stack over depth and half-offset of the subsurface-offset gather ``E`` of :func:`extended_image` with
+    ``kind="offset"`` along ``axis``; ``offsets``: integer half-offsets ``h_l`` in cells, ``tangents``: ``p_j = tan
+    gamma_j`` (``fourier.tangents``), ``taper``: ``t_l`` (None: ones).  Every shot takes the per-shot path of
+    :func:`extended_image`, but its gather stays on the device: each lag is formed by
+    ``Engine.fourier_offset_image_vec`` and added to that lag's vector slot, and after the engine's last shot
+    ``Engine.angle_gather_vec`` runs the transform there.  Only the angle images are downloaded (with
+    ``return_offsets=True`` the summed offset gather too: ``(J, A, E)``).  The sum over shots is therefore formed on the
+    device in the context's dtype; :func:`extended_image` keeps its fp64 sum on the host.  Uses the
+    ``len(offsets) + len(tangents) + 1`` vector slots from ``slot0`` on (lags, angles, one scratch) of every engine,
+    which the caller has created (``Engine.vec_create`` frees every slot, so it is not called here; a missing slot is
+    the engine's own error).  The transform is kinematic: an event that is flat across the angles says that ``model`` is
+    right.  The gradient accumulators are reset and stay zero.  Engines without the Fourier store raise
+    ``ValueError``."""
+    from .objectives import l2
+    ex = exchange or NoExchange()
+    ang = _AngleGather(engine, freq_weights, axis, offsets, tangents, slot0, taper)
+    for e in _engines(engine):
+        e.set_model(model)
+        e.reset_gradient()
+    misfit = _sweep_shots(engine, shots, ex, objective or l2, True, ang)
+    J = float(np.asarray(ex.reduce_array(np.array([misfit]))).ravel()[0])
+    A, E = ang.gathers(engine, ex, return_offsets)
+    return (J, A, E) if return_offsets else (J, A)
+
+
 class _Split(_Spectral):
     """The adjoint of :func:`split_gradient`: ``Engine.adjoint_spectral(residual, image=False)``, then the shot's two parts
     added to its engine's fp64 sums on the host (a pool drives each engine from one thread)."""

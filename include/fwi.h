@@ -652,6 +652,26 @@ int fwi_vec_regularizer(fwi_ctx *ctx, int32_t kind, int32_t x, int32_t x0 /* -1:
                         int32_t out /* -1: value only */, double alpha, double beta, const double *weight /* ndim */,
                         double eps, double *value_out /* R(d), or NULL */);
 
+/* A weighted sum of vector slots shifted along z (depth, the first grid axis) by real numbers of cells, stream-ordered
+ * like fwi_vec_axpby: the slant stack that turns a subsurface-offset gather into an angle-domain gather, and its exact
+ * transpose.  For a finite s let n = floor(s) and f = s - n, formed in fp64:
+ *   (S_s a)(z, .) = (1 - f) a(z + n, .) + f a(z + n + 1, .),
+ * where a tap whose plane lies outside 0 .. nz - 1 contributes zero (the other tap still counts), the second tap is
+ * neither read nor counted when f == 0, and |s| >= nz + 1 gives zeros (n is held in 64 bits and tested against the grid
+ * before any address is formed from it).  With this masking S_s^T = S_{-s} exactly.  The call computes
+ *   dst := beta dst + sum_{i < nsrc} weights[i] S_{shifts[i]} src_slots[i]
+ * with one fp64 sum per cell: sources ascending, per source s = fma(w (1 - f), first tap, s) then s = fma(w f, second
+ * tap, s), at the end dst = (beta == 0 ? s : fma(beta, dst, s)) rounded once to the context's dtype.  Nothing is shared
+ * or atomic: equal inputs give equal bits on every call and rank.  With beta == 0 the old contents of dst are not read.
+ * Pad columns of dst are written as zeros.  The same source may appear twice.  A source shifted out of the grid
+ * entirely is skipped; with all of them skipped dst := beta dst still happens.  Needs no model, forward or Fourier
+ * store.  FWI_EINVAL, naming the argument and touching nothing: a slot that does not exist; nsrc outside
+ * [1, FWI_SHIFT_SUM_MAX]; a null src_slots or shifts; a shift, weight or beta that is not finite; dst among the
+ * sources.  No reference counterpart. */
+#define FWI_SHIFT_SUM_MAX 64
+int fwi_vec_shift_sum(fwi_ctx *ctx, int32_t dst, int32_t nsrc, const int32_t *src_slots, const double *shifts,
+                      const double *weights /* nsrc, or NULL = ones */, double beta);
+
 /* Born (linearised) modelling dd = J dm: the exact derivative of the discrete fwi_forward along a model perturbation,
  * whose exact transpose is fwi_adjoint(image) + fwi_gradient.  With C = dt^2 c^2 and q^n the forward term the store of
  * fwi_forward(save != 0) holds for every step (q^n = C (L u^n + PML terms + src^n)):

@@ -49,6 +49,13 @@ def main():
                          "lags -L .. L of a subsurface-offset gather along AXIS (z, y or x; lags in cells) or of a time-lag "
                          "gather in steps of DTAU seconds; written to --extended-out with its lags and fourier.focusing")
     ap.add_argument("--extended-out", default=None, metavar="PATH", help="the .npz file of --extended-image (rank 0 writes)")
+    ap.add_argument("--angle-gather", default=None, metavar="AXIS:L:NANG:MAXDEG",
+                    help="with --fourier-store: the angle-domain common-image gather of the final model "
+                         "(shots.angle_gather): the 2 L + 1 subsurface half-offsets -L .. L in cells along AXIS (y or x) "
+                         "are summed over the shots on the device and slant-stacked there to NANG angles from -MAXDEG to "
+                         "MAXDEG degrees; written to --angle-out with its tangents, its offsets and "
+                         "Engine.gather_moment of the offset gather")
+    ap.add_argument("--angle-out", default=None, metavar="PATH", help="the .npz file of --angle-gather (rank 0 writes)")
     ap.add_argument("--split-gradient", default=None, metavar="AXIS:R",
                     help="with --fourier-store: the tomographic (same direction) and migration (opposite direction) parts "
                          "of the final model's spectral gradient along AXIS (z, y or x), with datafit.hilbert_taps(R), "
@@ -170,6 +177,23 @@ def main():
             ap.error("--extended-image takes offset:AXIS:L (AXIS z, y or x) or time:DTAU:L (DTAU > 0 seconds), L >= 0")
     elif a.extended_out is not None:
         ap.error("--extended-out needs --extended-image")
+    angle = None
+    if a.angle_gather is not None:
+        if a.fourier_store is None:
+            ap.error("--angle-gather needs --fourier-store FMIN,FMAX (it images on the store's frequencies)")
+        if a.angle_out is None:
+            ap.error("--angle-gather needs --angle-out PATH")
+        try:
+            axis, half, nang, maxdeg = a.angle_gather.split(":")
+            half, nang, maxdeg = int(half), int(nang), float(maxdeg)
+            assert axis in ("y", "x") and half >= 0 and nang >= 1 and 0.0 <= maxdeg < 90.0
+            assert 2 * half + 1 + nang + 1 <= 256
+            angle = (axis, np.arange(-half, half + 1), np.linspace(-maxdeg, maxdeg, nang) if nang > 1 else np.zeros(1))
+        except (ValueError, AssertionError):
+            ap.error("--angle-gather takes AXIS:L:NANG:MAXDEG (AXIS y or x, L >= 0 cells, NANG >= 1 angles, 0 <= MAXDEG "
+                     "< 90 degrees; 2 L + NANG + 2 <= 256 vector slots)")
+    elif a.angle_out is not None:
+        ap.error("--angle-out needs --angle-gather")
     split = None
     if a.split_gradient is not None:
         if a.fourier_store is None:
@@ -430,6 +454,20 @@ def main():
         if rank == 0:
             np.savez(a.extended_out, gather=E, lags=lags, kind=kind, axis="" if axis is None else axis,
                      focusing=fourier.focusing(E, lags))
+    if angle is not None:  # the angle gather of the final model, with the misfit and the weights of the last stage
+        from full_waveform_inversion_amd import fourier
+        axis, offsets, degrees = angle
+        tangents = fourier.tangents(degrees)
+        for eng in pool.engines:  # the optimiser is done with its vectors: vec_create frees them
+            eng.vec_create(offsets.size + tangents.size + 1)
+        _, A, E = sh.angle_gather(pool, np.asarray(m_final, np.float32), shots, axis, offsets, tangents, 0, ex, obj[0],
+                                  imaging.get("freq_weights"), return_offsets=True)
+        for l in range(offsets.size):  # the summed offset gather, in the primary engine's lag slots
+            e.vec_upload(l, E[l].astype(e.dtype))
+        moment = e.gather_moment(range(offsets.size), offsets)
+        if rank == 0:
+            np.savez(a.angle_out, gather=A, tangents=tangents, degrees=degrees, offsets=offsets, axis=axis,
+                     gather_moment=np.array(moment))
     if split is not None:  # both parts of the final model's gradient, with the misfit and the weights of the last stage
         from full_waveform_inversion_amd import datafit as df
         axis, half = split
