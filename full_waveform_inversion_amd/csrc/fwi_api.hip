@@ -1,48 +1,25 @@
-// C-ABI of the engine (include/fwi.h): context, device memory, time loops,
-// RCCL exchange.  Host-side runtime only; the arithmetic is in fwi_kernels.hip.
+// C-ABI of the engine (include/fwi.h): context, device memory, time loops.  Host-side runtime only; the arithmetic is in
+// fwi_kernels.hip.  The calls that run no time loop have their own units over the same context (fwi_host.h):
+// fwi_api_misfit.hip, fwi_api_fourier.hip, fwi_api_vec.hip and fwi_api_comm.hip (the RCCL exchange).
 //
 // No reference counterpart (the reference has neither a native layer nor this
 // path); the entry points are the ones BASELINE.json's
 // north_star names.  The time loop mirrors oracle/fwi_oracle.py::_propagate
 // one-to-one so the parity tests can compare every intermediate.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <string>
 #include <type_traits>
-#include <vector>
 
-#include "../../include/fwi.h"
+#include "fwi_host.h"
 #include "fwi_born.h"
-#include "fwi_data.h"
-#include "fwi_corr.h"
-#include "fwi_spec.h"
-#include "fwi_ot.h"
-#include "fwi_ttime.h"
-#include "fwi_envelope.h"
-#include "fwi_gather_tile.h"
 #include "fwi_fourier.h"
 #include "fwi_fimage.h"
-#include "fwi_feximage.h"
-#include "fwi_fsplit.h"
 #include "fwi_fbornx.h"
 #include "fwi_illum.h"
-#include "fwi_kernels.h"
-#include "fwi_match.h"
-#include "fwi_match_solve.h"
-#include "fwi_reg.h"
-#include "fwi_slant.h"
-#include "fwi_smooth.h"
-
-using namespace fwi;
 
 namespace {
 
@@ -55,243 +32,7 @@ const double COEF8[] = {-205.0 / 72.0, 8.0 / 5.0, -1.0 / 5.0, 8.0 / 315.0, -1.0 
 const double DCOEF2[] = {1.0 / 2.0};
 const double DCOEF4[] = {2.0 / 3.0, -1.0 / 12.0};
 const double DCOEF8[] = {4.0 / 5.0, -1.0 / 5.0, 4.0 / 105.0, -1.0 / 280.0};
-// Fourier store: a frequency within this relative distance of 1 / (2 S dt) is the Nyquist frequency of the sampled axis
-// (weight 1 / N; fourier.NYQUIST_RTOL of the NumPy twin), and none may lie further above it
-constexpr double FOURIER_NYQUIST_RTOL = 1e-9;
 static_assert(FWI_FOURIER_BMAX == FOURIER_BMAX, "batch limit of the ABI and of the kernels");
-
-std::string vformat(const char *fmt, va_list ap) {
-    char buf[512];
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    return buf;
-}
-
-}  // namespace
-
-struct fwi_ctx {
-    fwi_config cfg;
-    GridDesc gd;
-    int kernel = K_POINT;
-    StreamTuning tune{8, 0, 1, 256};
-    size_t esize = 4;  // bytes per element
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool have_loop_time = false;
-    // FWI_LAUNCH_GRAPH: the time loop of a sweep is captured and launched as one hipGraph.  The executable graph of
-    // the last sweep is kept until the next sweep (or destroy) replaces it -- it may still be running when the call
-    // that launched it returns its samples.
-    bool graph_mode = false;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    double host_submit_ms = 0.0, host_graph_ms = 0.0;
-
-    // device fields
-    void *u[2] = {nullptr, nullptr};  // padded wavefields (ping-pong)
-    bool inc = false;                 // increment form: state (u, v = u - u_prev); u[] ping-pongs u, v lives in vf
-    void *vf = nullptr, *fwv = nullptr;  // v of the running sweep / of the checkpointed forward recomputation
-    // 3-D temporal blocking (fwi_pair3d.hip): forward sweeps without imaging advance two steps per pass
-    bool qbf16 = false;  // forward-term store in bf16 (fp32 3-D stream contexts)
-    size_t qes = 4;      // bytes per stored forward-term element
-    bool pair3d = false;
-    int pair_zc = 0, pair_tw = 256;
-    int fused_skipd = -1;  // Fused2dArgs::skipd (FWI_FUSED2D_SKIPD, read at create)
-    int *fused_order = nullptr;  // Fused2dArgs::tile_order (device; grids of more than one round of tiles with a border)
-    int fused_ft = FUSED2D_TILE;  // interior tile edge of the fused 2-D kernel (fused2d_pick_tile; 64 with CPML / increment)
-    // convolutional PML: memory variables per axis (z, y, x), compact over that axis' border, and 1-D coefficients
-    bool cpml = false;
-    bool xpml = false;  // 3-D fp32 stream contexts: the x border's recursion runs inside the step kernel
-    int pml_lines = 0;  // axes (z = 1, y = 2) whose border runs as one line launch per step (pml_line_axes)
-    // ... whose term T_d the line launch hands to the step kernel: arrays compact over the axis' shell (StepArgs::pml_tz /
-    // pml_ty; scratch within one time step, so one pair serves every sweep of the context)
-    void *pml_tz = nullptr, *pml_ty = nullptr;
-    void *pml_psi[3] = {nullptr, nullptr, nullptr}, *pml_zeta[3] = {nullptr, nullptr, nullptr};
-    // Placement of the four small arrays the 3-D CPML step kernel streams beside the fields (the x border's psi and zeta,
-    // the handed-over terms tz and ty): each sits `place_shift` bytes into an allocation `place_pad` bytes longer than
-    // the array, at the position Impl::tune_placement measured as the fastest (0 = untuned; see there)
-    // (place_kind 2, increment-form contexts without CPML: the fields v and C instead -- worth 1.5 - 3 % there, the
-    // per-process spread of that form is not theirs to fix; the u buffers change roles with others and stay put)
-    int place_kind = 0;
-    size_t place_pad = 0;
-    int nmov = 0;                 // the movable arrays in search order: the member that points at them, their size,
-    void **mov_slot[8] = {};      // how far into their allocation they currently sit
-    size_t mov_bytes[8] = {}, mov_shift[8] = {};
-    void movable(void **slot, size_t bytes) {
-        if (place_pad && nmov < 8) {
-            mov_slot[nmov] = slot;
-            mov_bytes[nmov] = bytes;
-            mov_shift[nmov++] = 0;
-        }
-    }
-    float place_us[2] = {0.f, 0.f};  // step time before / after the placement search (fwi_placement_info)
-    // with checkpointing: the memory variables of the forward recomputation (the running adjoint sweep keeps its own
-    // in the set above) and, per snapshot, a copy of the forward set (psi then zeta, axis by axis)
-    void *pml_psi_fw[3] = {nullptr, nullptr, nullptr}, *pml_zeta_fw[3] = {nullptr, nullptr, nullptr};
-    // 2-D contexts that carry the CPML inside the fused launch: the set of arrays the launch writes (swapped with the
-    // set it read after every launch; zeroed once -- the pad columns of the z border's rows are never written)
-    void *pml_spare_psi[3] = {nullptr, nullptr, nullptr}, *pml_spare_zeta[3] = {nullptr, nullptr, nullptr};
-    void *pml_snap = nullptr;
-    size_t pml_snap_stride = 0;  // bytes of one snapshot of the memory variables
-    void *pml_a[3] = {nullptr, nullptr, nullptr}, *pml_b[3] = {nullptr, nullptr, nullptr};
-    size_t pml_bytes[3] = {0, 0, 0};
-    void *C = nullptr;                // padded dt^2 c^2
-    void *c_dev = nullptr;            // compact velocity
-    void *dz = nullptr, *dy = nullptr, *dx = nullptr;
-    void *q_store = nullptr;  // nt_max x npts forward terms
-    int istride = 1;          // imaging stride: the forward term is stored / correlated every istride-th step
-    void *logical = nullptr;  // nz x ny x nx staging array for host <-> compact copies when cx != nx
-    void *g_acc = nullptr;    // compact gradient accumulator
-    void *g_out = nullptr;    // compact scratch for fwi_gradient (and fwi_illumination)
-    // source-side illumination (fwi_set_illumination): compact accumulator of sum q^2 over the imaging steps of every
-    // fwi_adjoint(image) since the last fwi_gradient_reset; nullptr = disabled (the default: no launch, no memory)
-    void *h_acc = nullptr;
-    // Fourier-compressed forward-term store (fwi_set_fourier_store; fwi_fourier.hip): four_freqs.size() = F > 0 while
-    // it is on.  2 F compact accumulator volumes (Re Q_k, Im Q_k), four_batch + 1 compact ring slots (sample j in slot
-    // j % (four_batch + 1)) and the twiddle table of the running sweep, all allocated by the first fwi_forward(save)
-    std::vector<double> four_freqs;
-    int four_batch = 0;
-    void *four_acc = nullptr, *four_ring = nullptr, *four_tw = nullptr;
-    int four_rows = 0;        // rows per frequency of four_tw: ceil(nt_max / istride) + FOURIER_BMAX - 1
-    bool four_sweep = false;  // the running sweep goes through the Fourier store: one step per launch
-    std::vector<double> four_tw_host;
-    // Spectral imaging (fwi_adjoint_spectral; fwi_fimage.hip): 2 F compact accumulator volumes (Re M_k, Im M_k) of the
-    // adjoint field, allocated by the first fwi_adjoint_spectral; have_m: they hold the M_k that go with the Q_k of the
-    // latest forward(save).  four_w: the F weights a_k w_k of the running image / illumination pass on the device (the
-    // 2 F of a time-lag image, fwi_feximage.hip; the F of a split image with its taps behind them at FWI_FOURIER_FMAX,
-    // fwi_fsplit.hip; room for 2 FWI_FOURIER_FMAX doubles).
-    void *four_adj = nullptr, *four_w = nullptr;
-    bool have_m = false;
-    std::vector<double> four_w_host;
-    size_t store_held = 0;    // device bytes held for the forward store of whichever kind (fwi_store_bytes)
-    // Born modelling (fwi_born): w = dC / C of the last perturbation, compact; allocated by the first fwi_born call
-    void *born_w = nullptr;
-    // ... on a bf16 store: (nt, nsrc) amplitudes w(x_s) wav^n_s of the source's exact share (launch_born_source_share)
-    void *born_src = nullptr;
-    size_t cap_born_src = 0;
-    const char *born_path = "none";  // path of the last Born sweep (fwi_born_path)
-    double *red = nullptr;    // reduction scalars
-
-    // host copies
-    std::vector<double> pz, py, px;
-    bool have_model = false;
-
-    // per-shot point sets (device) and their sizes
-    int nt = 0, nsrc = 0, nrec = 0;
-    bool have_forward = false, have_q = false;
-    bool have_syn = false;  // ctx->series still holds the last forward's synthetics (an adjoint sweep records its
-                            // source-side series into the same buffer)
-    bool have_dev_residual = false;  // ctx->amp holds the residual fwi_misfit_l2 formed on the device
-    // A point set on the device: original order (sampling, POINT-kernel injection) and the
-    // copy sorted by stream-kernel tile with its CSR offsets (fused injection).
-    struct PointSet {
-        int n = 0;
-        void *pidx = nullptr, *cidx = nullptr, *cu = nullptr, *cq = nullptr;
-        void *s_start = nullptr, *s_pidx = nullptr, *s_cidx = nullptr, *s_cu = nullptr, *s_cq = nullptr,
-             *s_col = nullptr, *s_run = nullptr;
-        size_t cap = 0, cap_start = 0;
-        // tables for the 2-D fused kernel: injection entries per tile (extended region) and
-        // sampling entries per tile (interior)
-        void *fi_start = nullptr, *fi_lz = nullptr, *fi_lx = nullptr, *fi_col = nullptr, *fi_int = nullptr,
-             *fi_cidx = nullptr, *fi_cu = nullptr, *fi_cq = nullptr, *fi_run = nullptr;
-        void *fr_start = nullptr, *fr_lz = nullptr, *fr_lx = nullptr, *fr_col = nullptr;
-        size_t fcap = 0, fcap_start = 0;
-        // entries of the 3-D two-step kernel, CSR over its workgroups
-        void *pr_start = nullptr, *pr_ent = nullptr;
-        size_t pcap = 0, pcap_start = 0;
-    } src, rec;
-    // Off-grid points of the last forward (fwi_forward_spread): per point set the CSR over points, the owner of
-    // every node entry and its interpolation weight; time series cross the boundary per POINT and are scattered /
-    // gathered on the device.  npts = 0: node-based call.
-    struct SpreadSet {
-        int npts = 0;
-        void *pt_start = nullptr, *owner = nullptr, *weight = nullptr;
-        size_t cap = 0;
-    } src_sp, rec_sp;
-    void *pts_a = nullptr;   // (nt, npts) per-point series being uploaded / downloaded
-    void *pts_d = nullptr;   // (nt, nrec points) gathered synthetics of the last forward (fwi_misfit_l2)
-    size_t cap_pts_a = 0, cap_pts_d = 0;
-    void *wav = nullptr;     // (nt, nsrc) source wavelets of the last forward (kept for recomputation)
-    void *amp = nullptr;     // (nt, nrec) residual being back-propagated
-    void *series = nullptr;  // (nt, n) sampled series of the running sweep
-    size_t cap_wav = 0, cap_amp = 0, cap_series = 0;
-    std::vector<void *> vecs;  // optimiser vectors (compact, model-sized)
-    void *smooth_tmp = nullptr;  // compact ping-pong vector of fwi_vec_smooth; allocated by its first call
-    void *reg_part = nullptr;    // block partial sums (and their total) of fwi_vec_regularizer; allocated by its first call
-    void *sum_part = nullptr;    // the same of fwi_vec_dot, fwi_dot and fwi_misfit_l2 (SUM_MAX_BLOCKS + 1 doubles); allocated
-                                 // by the first of those calls
-    // the data misfits and fwi_residual_weight (Impl<T>::Misfit), each allocated by the first call that needs it: the
-    // series between two passes (e; g1 of the envelope), the weights, the taps of B, the block partial sums of J (and
-    // their total), the filtered synthetics s' and data d' of the misfits that filter first (with taps; s' later holds
-    // their adjoint source), and the weights per trace of the misfits that take any
-    void *data_tmp = nullptr, *data_w = nullptr, *data_taps = nullptr, *data_part = nullptr, *data_s = nullptr,
-         *data_d = nullptr, *data_tw = nullptr;
-    size_t cap_data_tmp = 0, cap_data_w = 0, cap_data_taps = 0, cap_data_part = 0, cap_data_s = 0, cap_data_d = 0,
-           cap_data_tw = 0;
-    // fwi_misfit_matched (fwi_match.hip): the slices of the normal equations, G and b, the filter
-    void *match_part = nullptr, *match_norm = nullptr, *match_f = nullptr;
-    size_t cap_match_part = 0, cap_match_norm = 0, cap_match_f = 0;
-    // fwi_misfit_envelope (fwi_envelope.hip): g2, the Hilbert taps
-    void *env_g2 = nullptr, *env_h = nullptr;
-    size_t cap_env_g2 = 0, cap_env_h = 0;
-    // fwi_misfit_correlation (fwi_corr.hip): the per-tile sums and the terms of J, alpha / beta / rho
-    void *corr_part = nullptr, *corr_coef = nullptr;
-    size_t cap_corr_part = 0, cap_corr_coef = 0;
-    // fwi_misfit_traveltime (fwi_ttime.hip): the partial correlations and the terms of J, tau and the three coefficients
-    // of every trace, the picked lags
-    void *tt_part = nullptr, *tt_coef = nullptr, *tt_lag = nullptr;
-    size_t cap_tt_part = 0, cap_tt_coef = 0, cap_tt_lag = 0;
-    // fwi_misfit_transport (fwi_ot.hip): densities, CDFs, potentials and every sum (ot_work_doubles), which traces count
-    void *ot_work = nullptr, *ot_counts = nullptr;
-    size_t cap_ot_work = 0, cap_ot_counts = 0;
-    // fwi_misfit_spectral (fwi_spec.hip): the segment sums, G / phi / a and the terms of J, which pairs count, the
-    // frequency weights, and the twiddle table with the (nt, frequencies) it was formed for (dt is the context's)
-    void *spec_part = nullptr, *spec_coef = nullptr, *spec_counts = nullptr, *spec_fw = nullptr, *spec_table = nullptr;
-    size_t cap_spec_part = 0, cap_spec_coef = 0, cap_spec_counts = 0, cap_spec_fw = 0, cap_spec_table = 0;
-    int spec_table_nt = 0;
-    std::vector<double> spec_table_freqs, spec_table_host;
-    // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
-    enum { RESID_PTS_NONE = 0, RESID_PTS_A = 1, RESID_PTS_D = 2 };
-    int resid_pts_in = RESID_PTS_NONE;
-    void *pin = nullptr;     // pinned host staging for the time series
-    size_t cap_pin = 0;
-    // checkpointing (SURVEY s.8f-3): snapshot of (u^n, u^{n-1}) every `ckpt` steps instead of the
-    // imaging term of every step; q_store then holds ckpt + 1 slots and fwd[] the recomputed fields
-    int ckpt = 0;
-    bool ckpt_ready = false;  // every checkpoint buffer below is allocated
-    void *snap = nullptr, *fwd[2] = {nullptr, nullptr};
-    // 2-D temporal blocking: second buffer pair the fused kernel writes into, and whether it is used
-    bool fused2d = false;
-    void *fx[2] = {nullptr, nullptr};   // second pair for the time sweep in flight
-    void *fwx[2] = {nullptr, nullptr};  // second pair for the checkpointed forward recomputation
-
-    ncclComm_t comm = nullptr;
-    int nranks = 1;
-
-    std::string err;
-
-    int fail(int code, const char *fmt, ...) {
-        va_list ap;
-        va_start(ap, fmt);
-        err = vformat(fmt, ap);
-        va_end(ap);
-        return code;
-    }
-};
-
-#define HIPCHK(ctx, call)                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return (ctx)->fail(e_ == hipErrorOutOfMemory ? FWI_ENOMEM : FWI_EHIP, "%s: %s",   \
-                               #call, hipGetErrorString(e_));                                 \
-    } while (0)
-
-#define NCCLCHK(ctx, call)                                                                    \
-    do {                                                                                      \
-        ncclResult_t r_ = (call);                                                             \
-        if (r_ != ncclSuccess) return (ctx)->fail(FWI_ECOMM, "%s: %s", #call, ncclGetErrorString(r_)); \
-    } while (0)
-
-namespace {
 
 void profile(std::vector<double> &p, int n, int npml, double sigma_max, double dt) {
     p.assign(n, 0.0);
@@ -326,6 +67,10 @@ int stage_reserve(fwi_ctx *ctx, size_t bytes) {
     return FWI_OK;
 }
 
+}  // namespace
+
+namespace fwi {
+
 int upload_series(fwi_ctx *ctx, void *dst, const void *src, size_t bytes) {
     if (!bytes) return FWI_OK;
     int rc = stage_reserve(ctx, bytes);
@@ -335,6 +80,62 @@ int upload_series(fwi_ctx *ctx, void *dst, const void *src, size_t bytes) {
     HIPCHK(ctx, hipMemcpyAsync(dst, ctx->pin, bytes, hipMemcpyHostToDevice, ctx->stream));
     return FWI_OK;
 }
+
+int ensure(fwi_ctx *ctx, Buf &b, size_t bytes) {
+    if (b.cap >= bytes && b.p) return FWI_OK;
+    if (b.p) HIPCHK(ctx, hipFree(b.p));
+    b.p = nullptr;
+    HIPCHK(ctx, hipMalloc(&b.p, bytes ? bytes : 16));
+    b.cap = bytes;
+    return FWI_OK;
+}
+
+// the block partials (and their total) of the fixed-order sums (launch_dot, launch_residual_l2): allocated on first use
+int sum_partials(fwi_ctx *ctx, double **part) {
+    if (!ctx->sum_part) HIPCHK(ctx, hipMalloc(&ctx->sum_part, (size_t)(SUM_MAX_BLOCKS + 1) * sizeof(double)));
+    *part = (double *)ctx->sum_part;
+    return FWI_OK;
+}
+
+// Host arrays are model-shaped (row stride nx); compact device arrays have row stride cx (nx
+// rounded up to 4, pad columns zero).  Equal for nx % 4 == 0: one plain copy.  Otherwise the
+// contiguous array goes through a device staging buffer and a repack kernel.
+template <typename T>
+int upload_compact(fwi_ctx *ctx, void *dst, const void *host) {
+    const GridDesc &g = ctx->gd;
+    if (g.cx == g.nx) {
+        HIPCHK(ctx, hipMemcpyAsync(dst, host, (size_t)g.npts * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        return FWI_OK;
+    }
+    const size_t nlog = (size_t)g.nz * g.ny * g.nx;
+    if (!ctx->logical) HIPCHK(ctx, hipMalloc(&ctx->logical, nlog * sizeof(T)));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->logical, host, nlog * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, launch_repack<T>(g, (T *)dst, (const T *)ctx->logical, 1, ctx->stream));
+    return FWI_OK;
+}
+
+template <typename T>
+int download_compact(fwi_ctx *ctx, void *host, const void *src) {
+    const GridDesc &g = ctx->gd;
+    if (g.cx == g.nx) {
+        HIPCHK(ctx, hipMemcpyAsync(host, src, (size_t)g.npts * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        return FWI_OK;
+    }
+    const size_t nlog = (size_t)g.nz * g.ny * g.nx;
+    if (!ctx->logical) HIPCHK(ctx, hipMalloc(&ctx->logical, nlog * sizeof(T)));
+    HIPCHK(ctx, launch_repack<T>(g, (T *)ctx->logical, (const T *)src, 0, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(host, ctx->logical, nlog * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    return FWI_OK;
+}
+
+template int upload_compact<float>(fwi_ctx *, void *, const void *);
+template int upload_compact<double>(fwi_ctx *, void *, const void *);
+template int download_compact<float>(fwi_ctx *, void *, const void *);
+template int download_compact<double>(fwi_ctx *, void *, const void *);
+
+}  // namespace fwi
+
+namespace {
 
 // device -> caller; synchronises the stream
 int download_series(fwi_ctx *ctx, void *dst, const void *src, size_t bytes) {
@@ -348,16 +149,7 @@ int download_series(fwi_ctx *ctx, void *dst, const void *src, size_t bytes) {
     return FWI_OK;
 }
 
-int ensure(fwi_ctx *ctx, void **p, size_t *cap, size_t bytes) {
-    if (*cap >= bytes && *p) return FWI_OK;
-    if (*p) HIPCHK(ctx, hipFree(*p));
-    *p = nullptr;
-    HIPCHK(ctx, hipMalloc(p, bytes ? bytes : 16));
-    *cap = bytes;
-    return FWI_OK;
-}
-
-// ... and for a group of buffers of `bytes` each that share one capacity
+// ensure for a group of plain pointers of `bytes` each that share one capacity
 int ensure_all(fwi_ctx *ctx, std::initializer_list<void **> group, size_t *cap, size_t bytes) {
     if (*cap >= bytes && std::all_of(group.begin(), group.end(), [](void **p) { return *p != nullptr; })) return FWI_OK;
     for (void **p : group) {
@@ -397,13 +189,6 @@ int alloc_all(fwi_ctx *ctx, std::initializer_list<Want> want, size_t *total, siz
         *w.p = nullptr;
     }
     return FWI_ENOMEM;
-}
-
-// the block partials (and their total) of the fixed-order sums (launch_dot, launch_residual_l2): allocated on first use
-int sum_partials(fwi_ctx *ctx, double **part) {
-    if (!ctx->sum_part) HIPCHK(ctx, hipMalloc(&ctx->sum_part, (size_t)(SUM_MAX_BLOCKS + 1) * sizeof(double)));
-    *part = (double *)ctx->sum_part;
-    return FWI_OK;
 }
 
 // The time loop of one sweep, either submitted launch by launch or captured into a hipGraph and launched once
@@ -538,10 +323,10 @@ struct Impl {
     static int upload_amplitudes(fwi_ctx *ctx, void *dst, const void *host, int nt, int nnodes,
                                  const fwi_ctx::SpreadSet &sp) {
         if (sp.npts == 0) return upload_series(ctx, dst, host, (size_t)nt * nnodes * sizeof(T));
-        int rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, (size_t)nt * sp.npts * sizeof(T));
+        int rc = ensure(ctx, ctx->pts_a, (size_t)nt * sp.npts * sizeof(T));
         if (rc) return rc;
-        if ((rc = upload_series(ctx, ctx->pts_a, host, (size_t)nt * sp.npts * sizeof(T)))) return rc;
-        HIPCHK(ctx, launch_scatter_series<T>((const T *)ctx->pts_a, (T *)dst, (const int *)sp.owner, (const T *)sp.weight,
+        if ((rc = upload_series(ctx, ctx->pts_a.p, host, (size_t)nt * sp.npts * sizeof(T)))) return rc;
+        HIPCHK(ctx, launch_scatter_series<T>((const T *)ctx->pts_a.p, (T *)dst, (const int *)sp.owner, (const T *)sp.weight,
                                              nt, sp.npts, nnodes, ctx->stream));
         return FWI_OK;
     }
@@ -549,15 +334,14 @@ struct Impl {
     // the per-node device series `src` (nt x nnodes) -> the caller, per node or gathered per point; `keep` (or
     // nullptr) receives the device copy of what was handed out
     static int download_samples(fwi_ctx *ctx, void *host, const void *src, int nt, int nnodes,
-                                const fwi_ctx::SpreadSet &sp, void **keep, size_t *keep_cap) {
+                                const fwi_ctx::SpreadSet &sp, Buf *keep) {
         if (sp.npts == 0) return download_series(ctx, host, src, host ? (size_t)nt * nnodes * sizeof(T) : 0);
-        void **buf = keep ? keep : &ctx->pts_a;
-        size_t *cap = keep ? keep_cap : &ctx->cap_pts_a;
-        int rc = ensure(ctx, buf, cap, (size_t)nt * sp.npts * sizeof(T));
+        Buf &buf = keep ? *keep : ctx->pts_a;
+        int rc = ensure(ctx, buf, (size_t)nt * sp.npts * sizeof(T));
         if (rc) return rc;
-        HIPCHK(ctx, launch_gather_series<T>((const T *)src, (T *)*buf, (const int *)sp.pt_start, (const T *)sp.weight, nt,
+        HIPCHK(ctx, launch_gather_series<T>((const T *)src, (T *)buf.p, (const int *)sp.pt_start, (const T *)sp.weight, nt,
                                             sp.npts, nnodes, ctx->stream));
-        return download_series(ctx, host, *buf, host ? (size_t)nt * sp.npts * sizeof(T) : 0);
+        return download_series(ctx, host, buf.p, host ? (size_t)nt * sp.npts * sizeof(T) : 0);
     }
 
     static PmlArgs<T> pml_args(fwi_ctx *ctx, const Sweep &sw, T *q_out) {
@@ -618,39 +402,10 @@ struct Impl {
         return FWI_OK;
     }
 
-    // Host arrays are model-shaped (row stride nx); compact device arrays have row stride cx (nx
-    // rounded up to 4, pad columns zero).  Equal for nx % 4 == 0: one plain copy.  Otherwise the
-    // contiguous array goes through a device staging buffer and a repack kernel.
-    static int upload_compact(fwi_ctx *ctx, void *dst, const void *host) {
-        const GridDesc &g = ctx->gd;
-        if (g.cx == g.nx) {
-            HIPCHK(ctx, hipMemcpyAsync(dst, host, (size_t)g.npts * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            return FWI_OK;
-        }
-        const size_t nlog = (size_t)g.nz * g.ny * g.nx;
-        if (!ctx->logical) HIPCHK(ctx, hipMalloc(&ctx->logical, nlog * sizeof(T)));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->logical, host, nlog * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, launch_repack<T>(g, (T *)dst, (const T *)ctx->logical, 1, ctx->stream));
-        return FWI_OK;
-    }
-
-    static int download_compact(fwi_ctx *ctx, void *host, const void *src) {
-        const GridDesc &g = ctx->gd;
-        if (g.cx == g.nx) {
-            HIPCHK(ctx, hipMemcpyAsync(host, src, (size_t)g.npts * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-            return FWI_OK;
-        }
-        const size_t nlog = (size_t)g.nz * g.ny * g.nx;
-        if (!ctx->logical) HIPCHK(ctx, hipMalloc(&ctx->logical, nlog * sizeof(T)));
-        HIPCHK(ctx, launch_repack<T>(g, (T *)ctx->logical, (const T *)src, 0, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(host, ctx->logical, nlog * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        return FWI_OK;
-    }
-
     static int set_model(fwi_ctx *ctx, const T *c) {
         // compact H2D copy, then validation + padded C = dt^2 c^2 on the device (the halo of C
         // was zeroed at creation and is never written)
-        int rc = upload_compact(ctx, ctx->c_dev, c);
+        int rc = upload_compact<T>(ctx, ctx->c_dev, c);
         if (rc) return rc;
         return finish_model(ctx);
     }
@@ -759,8 +514,8 @@ struct Impl {
                 run[k] = (k == 0 || sp[k - 1] != sp[k] || tile[ord[k - 1]] != tile[ord[k]]) ? len : 0;
             }
             const size_t sb = start.size() * sizeof(int);
-            if ((rcode = ensure(ctx, &ps.s_start, &ps.cap_start, sb))) return rcode;
-            HIPCHK(ctx, up(ps.s_start, start.data(), sb));
+            if ((rcode = ensure(ctx, ps.s_start, sb))) return rcode;
+            HIPCHK(ctx, up(ps.s_start.p, start.data(), sb));
             HIPCHK(ctx, up(ps.s_pidx, sp.data(), (size_t)n * 8));
             HIPCHK(ctx, up(ps.s_cidx, sc.data(), (size_t)n * 8));
             HIPCHK(ctx, up(ps.s_cu, scu.data(), (size_t)n * sizeof(T)));
@@ -900,11 +655,9 @@ struct Impl {
                     pent.insert(pent.end(), per[k].begin(), per[k].end());
                 }
                 const size_t sb = pst.size() * sizeof(int), eb = pent.size() * sizeof(Pair3dInj) + 16;
-                if ((rcode = ensure(ctx, &ps.pr_start, &ps.pcap_start, sb)) ||
-                    (rcode = ensure(ctx, &ps.pr_ent, &ps.pcap, eb)))
-                    return rcode;
-                HIPCHK(ctx, up(ps.pr_start, pst.data(), sb));
-                HIPCHK(ctx, up(ps.pr_ent, pent.data(), pent.size() * sizeof(Pair3dInj)));
+                if ((rcode = ensure(ctx, ps.pr_start, sb)) || (rcode = ensure(ctx, ps.pr_ent, eb))) return rcode;
+                HIPCHK(ctx, up(ps.pr_start.p, pst.data(), sb));
+                HIPCHK(ctx, up(ps.pr_ent.p, pent.data(), pent.size() * sizeof(Pair3dInj)));
             }
         }
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // host vectors go out of scope
@@ -935,8 +688,8 @@ struct Impl {
                 a.npml = b.npml;
                 a.dz_scale = b.dz_scale;
                 if (inj.n > 0) {
-                    a.inj_start = (const int *)inj.pr_start;
-                    a.inj = (const Pair3dInj *)inj.pr_ent;
+                    a.inj_start = (const int *)inj.pr_start.p;
+                    a.inj = (const Pair3dInj *)inj.pr_ent.p;
                     a.inj_amp0 = amp + (size_t)n * inj.n;
                     a.inj_amp1 = amp + (size_t)(n + 1) * inj.n;
                 }
@@ -1107,7 +860,7 @@ struct Impl {
             a.q_out = q_out(n);
             q_in(n, a.q_in, a.q_in2);
             if (inj.n > 0) {
-                a.inj_start = (const int *)inj.s_start;
+                a.inj_start = (const int *)inj.s_start.p;
                 a.inj_pidx = (const int64_t *)inj.s_pidx;
                 a.inj_cidx = (const int64_t *)inj.s_cidx;
                 a.inj_cu = (const T *)inj.s_cu;
@@ -1463,21 +1216,19 @@ struct Impl {
         }
         // the pinned staging buffer at its final size for this shot, before any copy is queued on it
         if ((rc = stage_reserve(ctx, (size_t)nt * std::max(std::max(nsrc, nrec), 1) * sizeof(T)))) return rc;
-        if ((rc = ensure(ctx, &ctx->wav, &ctx->cap_wav, (size_t)nt * std::max(nsrc, 1) * sizeof(T)))) return rc;
-        if ((rc = ensure(ctx, &ctx->amp, &ctx->cap_amp, (size_t)nt * std::max(nrec, 1) * sizeof(T)))) return rc;
-        if ((rc = ensure(ctx, &ctx->series, &ctx->cap_series,
-                         (size_t)nt * std::max(std::max(nsrc, nrec), 1) * sizeof(T))))
-            return rc;
+        if ((rc = ensure(ctx, ctx->wav, (size_t)nt * std::max(nsrc, 1) * sizeof(T)))) return rc;
+        if ((rc = ensure(ctx, ctx->amp, (size_t)nt * std::max(nrec, 1) * sizeof(T)))) return rc;
+        if ((rc = ensure(ctx, ctx->series, (size_t)nt * std::max(std::max(nsrc, nrec), 1) * sizeof(T)))) return rc;
         ctx->nt = nt;
         ctx->nsrc = nsrc;
         ctx->nrec = nrec;
         hipStream_t s = ctx->stream;  // (no shot to speak of from here to the end: drop_forward, the callers' first statement)
-        if (nsrc && (rc = upload_amplitudes(ctx, ctx->wav, wavelet, nt, nsrc, ctx->src_sp))) return rc;
+        if (nsrc && (rc = upload_amplitudes(ctx, ctx->wav.p, wavelet, nt, nsrc, ctx->src_sp))) return rc;
         Sweep sw;
         if ((rc = start_sweep(ctx, sw))) return rc;
         const Store st(ctx);
         T *q_store = (T *)ctx->q_store;
-        T *series = (T *)ctx->series;
+        T *series = (T *)ctx->series.p;
         const bool fused = use_fused(ctx, nt);  // 2-D: FUSED2D_STEPS time steps per launch
         // a step count that is not a multiple of FUSED2D_STEPS: the bulk fused, the last 1-3 steps one per launch
         const int nfused = mixed_fused_steps(ctx, nt);
@@ -1493,9 +1244,9 @@ struct Impl {
         TimeLoop loop(ctx);
         if ((rc = loop.begin())) return rc;
         if (npair) {
-            if ((rc = run_pairs(ctx, sw, spare, 0, npair, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1))))
+            if ((rc = run_pairs(ctx, sw, spare, 0, npair, ctx->src, (const T *)ctx->wav.p, &ctx->rec, series, T(1))))
                 return rc;
-            if ((rc = run_steps(ctx, sw, npair, 1, nt - npair, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1),
+            if ((rc = run_steps(ctx, sw, npair, 1, nt - npair, ctx->src, (const T *)ctx->wav.p, &ctx->rec, series, T(1),
                                 none, noq)))
                 return rc;
         } else if (save && K > 0) {
@@ -1503,10 +1254,10 @@ struct Impl {
                 if ((rc = save_segment(ctx, sw, seg))) return rc;
                 const int cnt = std::min(K, nt - n0);
                 if (fused)
-                    rc = run_fused(ctx, sw, spare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, &ctx->rec, series,
+                    rc = run_fused(ctx, sw, spare, n0, 1, cnt, ctx->src, (const T *)ctx->wav.p, &ctx->rec, series,
                                    T(1), 0, nullptr);
                 else
-                    rc = run_steps(ctx, sw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1),
+                    rc = run_steps(ctx, sw, n0, 1, cnt, ctx->src, (const T *)ctx->wav.p, &ctx->rec, series, T(1),
                                    none, noq);
                 if (rc) return rc;
             }
@@ -1517,7 +1268,7 @@ struct Impl {
             auto qo = [&](int n) -> T * { return n % ks == 0 ? st.ring_slot(n) : nullptr; };
             for (int j0 = 0; j0 < N; j0 += B) {
                 const int nb = std::min(B, N - j0), n0 = j0 * ks, n1 = std::min((int)nt, (j0 + nb) * ks);
-                if ((rc = run_steps(ctx, sw, n0, 1, n1 - n0, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1), qo,
+                if ((rc = run_steps(ctx, sw, n0, 1, n1 - n0, ctx->src, (const T *)ctx->wav.p, &ctx->rec, series, T(1), qo,
                                     noq)))
                     return rc;
                 HIPCHK(ctx, launch_fourier_analyse<T>((T *)ctx->four_acc, st.ring, g.npts, R, j0 % R, j0, nb,
@@ -1525,24 +1276,24 @@ struct Impl {
                                                       (int)ctx->four_freqs.size(), s));
             }
         } else if (fused) {
-            if ((rc = run_fused(ctx, sw, spare, 0, 1, nt, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1),
+            if ((rc = run_fused(ctx, sw, spare, 0, 1, nt, ctx->src, (const T *)ctx->wav.p, &ctx->rec, series, T(1),
                                 save ? 1 : 0, q_store)))
                 return rc;
         } else {
             const int ks = ctx->istride;  // q^n is kept for n % ks == 0, in slot n / ks
             auto qo = [&](int n) -> T * { return (save && n % ks == 0) ? (T *)st.slot(n) : nullptr; };
-            if (nfused && (rc = run_fused(ctx, sw, spare, 0, 1, nfused, ctx->src, (const T *)ctx->wav, &ctx->rec, series,
+            if (nfused && (rc = run_fused(ctx, sw, spare, 0, 1, nfused, ctx->src, (const T *)ctx->wav.p, &ctx->rec, series,
                                           T(1), save ? 1 : 0, q_store)))
                 return rc;
-            if ((rc = run_steps(ctx, sw, nfused, 1, nt - nfused, ctx->src, (const T *)ctx->wav, &ctx->rec, series, T(1),
+            if ((rc = run_steps(ctx, sw, nfused, 1, nt - nfused, ctx->src, (const T *)ctx->wav.p, &ctx->rec, series, T(1),
                                 qo, noq)))
                 return rc;
         }
         if ((rc = flush_record(ctx, sw, ctx->rec, series, T(1)))) return rc;
         if ((rc = loop.end())) return rc;
         adopt(ctx, sw, spare);
-        if ((rc = download_samples(ctx, (nrec && seis_out) ? seis_out : nullptr, ctx->series, nt, nrec, ctx->rec_sp,
-                                   &ctx->pts_d, &ctx->cap_pts_d)))
+        if ((rc = download_samples(ctx, (nrec && seis_out) ? seis_out : nullptr, ctx->series.p, nt, nrec, ctx->rec_sp,
+                                   &ctx->pts_d)))
             return rc;
         ctx->have_forward = true;
         ctx->have_syn = true;
@@ -1571,7 +1322,7 @@ struct Impl {
         const int nt = ctx->nt, K = ctx->ckpt;
         hipStream_t s = ctx->stream;
         int rc;
-        if (ctx->nrec && residual && (rc = upload_amplitudes(ctx, ctx->amp, residual, nt, ctx->nrec, ctx->rec_sp)))
+        if (ctx->nrec && residual && (rc = upload_amplitudes(ctx, ctx->amp.p, residual, nt, ctx->nrec, ctx->rec_sp)))
             return rc;  // (residual == nullptr: the one fwi_misfit_l2 left in ctx->amp)
         ctx->have_dev_residual = false;  // consumed: ctx->series is about to be overwritten
         ctx->have_syn = false;           // ... by this sweep's source-side series (fwi_misfit_l2 must not read them)
@@ -1583,8 +1334,8 @@ struct Impl {
         if ((rc = start_sweep(ctx, sw))) return rc;
         const Store st(ctx);
         T *q_store = (T *)ctx->q_store;
-        T *series = (T *)ctx->series;
-        const T *amp = (const T *)ctx->amp;
+        T *series = (T *)ctx->series.p;
+        const T *amp = (const T *)ctx->amp.p;
         const bool fused = use_fused(ctx, nt);
         const int nfused = mixed_fused_steps(ctx, nt);
         void *spare[2] = {ctx->fx[0], ctx->fx[1]};
@@ -1634,9 +1385,9 @@ struct Impl {
                 const int n0 = seg * K, cnt = std::min(K, nt - n0), hi = n0 + cnt - 1;
                 if ((rc = restore_segment(ctx, fw, seg))) return rc;
                 auto qo = [&](int n) -> T * { return st.seg_slot(n, n0); };
-                rc = fused ? run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), 1,
+                rc = fused ? run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav.p, nullptr, nullptr, T(0), 1,
                                        st.seg_slot(0, n0))
-                           : run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), qo, noq);
+                           : run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav.p, nullptr, nullptr, T(0), qo, noq);
                 if (rc) return rc;
                 if ((rc = illum_accumulate(ctx, q_store, cnt))) return rc;  // slots 0 .. cnt - 1, before they are reused
                 if (fused) {
@@ -1733,128 +1484,23 @@ struct Impl {
             // exactly, in closed form: g(x_s) += cq_s sum_n mu^{n+1}(x_s) w_s^n, with mu at the sources = the series
             // this sweep has just recorded (scaled by rs)
             // (per node, in the sorted order of the source set: two sources on one node add in a fixed order)
-            HIPCHK(ctx, launch_source_image<T>((const T *)ctx->series, (const T *)ctx->wav, (const int64_t *)ctx->src.s_cidx,
+            HIPCHK(ctx, launch_source_image<T>((const T *)ctx->series.p, (const T *)ctx->wav.p, (const int64_t *)ctx->src.s_cidx,
                                                (const T *)ctx->src.s_cq, (const int *)ctx->src.s_col,
                                                (const int *)ctx->src.s_run, (T *)ctx->g_acc, nt, ctx->nsrc, ctx->istride,
                                                (T)(1.0 / (double)rs), s));
         if (image && K == 0) {  // the whole store: the ceil(nt / S) slots of this shot, once
             if ((rc = illum_accumulate(ctx, q_store, (nt + ctx->istride - 1) / ctx->istride))) return rc;
             if (ctx->h_acc && ctx->qbf16 && ctx->nsrc > 0)  // the source's exact share at its nodes (closed form)
-                HIPCHK(ctx, launch_illum_source_bf16((float *)ctx->h_acc, ctx->q_store, g.npts, (const float *)ctx->wav,
+                HIPCHK(ctx, launch_illum_source_bf16((float *)ctx->h_acc, ctx->q_store, g.npts, (const float *)ctx->wav.p,
                                                      (const int64_t *)ctx->src.cidx, (const float *)ctx->src.cq, nt,
                                                      ctx->nsrc, ctx->istride, s));
         }
         if ((rc = loop.end())) return rc;
-        if ((rc = download_samples(ctx, (adj_src_out && ctx->nsrc) ? adj_src_out : nullptr, ctx->series, nt, ctx->nsrc,
-                                   ctx->src_sp, nullptr, nullptr)))
+        if ((rc = download_samples(ctx, (adj_src_out && ctx->nsrc) ? adj_src_out : nullptr, ctx->series.p, nt, ctx->nsrc,
+                                   ctx->src_sp, nullptr)))
             return rc;
         ctx->have_m = spectral || ctx->have_m;
         return FWI_OK;
-    }
-
-    // The weights a_k w_k of one image / illumination pass on the device (w_k as fourier_table's synthesis weights, for
-    // the N samples of the last forward); `fw` = nullptr: a_k = 1.  With `tau` (a time-lag image) the table holds 2 F
-    // entries instead, C_k = a_k w_k cos phi_k at k and D_k = a_k w_k sin phi_k at F + k, phi_k = 2 pi f_k tau formed in
-    // fp64 from the fractional part of f_k tau as fourier_table forms its phases (tau = 0: C_k = a_k w_k, D_k = 0).
-    // `unit`: a_k w_k = 1, the bare phases (cos phi_k, sin phi_k) of an extended Born source (fwi_fbornx.h).
-    // `taps` (a split image, fwi_fsplit.h): the `ntaps` <= FWI_SPLIT_RMAX taps follow at FWI_FOURIER_FMAX.
-    static int fourier_weights(fwi_ctx *ctx, const double *fw, const double *tau = nullptr, bool unit = false,
-                               const double *taps = nullptr, int ntaps = 0) {
-        const int S = ctx->istride, N = (ctx->nt + S - 1) / S, F = (int)ctx->four_freqs.size();
-        const double sdt = (double)S * ctx->cfg.dt;
-        if (!ctx->four_w) HIPCHK(ctx, hipMalloc(&ctx->four_w, 2 * FWI_FOURIER_FMAX * sizeof(double)));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the upload of the pass before may still read the host copy
-        std::vector<double> &a = ctx->four_w_host;
-        a.assign(tau ? 2 * F : F, 0.0);
-        for (int k = 0; k < F; ++k) {
-            const double f = ctx->four_freqs[k];
-            const bool edge = f == 0.0 || std::fabs(2.0 * f * sdt - 1.0) <= FOURIER_NYQUIST_RTOL;
-            a[k] = unit ? 1.0 : (fw ? fw[k] : 1.0) * ((edge ? 1.0 : 2.0) / N);
-            if (tau) {
-                const double x = f * *tau, th = 2.0 * M_PI * (x - std::floor(x));
-                a[F + k] = a[k] * std::sin(th);
-                a[k] = a[k] * std::cos(th);
-            }
-        }
-        if (taps) {
-            a.resize(FWI_FOURIER_FMAX, 0.0);
-            a.insert(a.end(), taps, taps + ntaps);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->four_w, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        return FWI_OK;
-    }
-
-    // dst = beta dst + sum_k a_k w_k Re(Q_k conj M_k) (`illum`: |Q_k|^2) in the units of g_acc
-    static int fourier_sum(fwi_ctx *ctx, const double *fw, bool illum, void *dst, int beta) {
-        int rc = fourier_weights(ctx, fw);
-        if (rc) return rc;
-        const int F = (int)ctx->four_freqs.size();
-        if (illum)
-            HIPCHK(ctx, launch_fimage_illuminate<T>((T *)dst, (const T *)ctx->four_acc, (const double *)ctx->four_w,
-                                                    ctx->gd.npts, F, beta, ctx->stream));
-        else
-            HIPCHK(ctx, launch_fimage_image<T>((T *)dst, (const T *)ctx->four_acc, (const T *)ctx->four_adj,
-                                               (const double *)ctx->four_w, ctx->gd.npts, F, beta, ctx->stream));
-        return FWI_OK;
-    }
-
-    static int fourier_image(fwi_ctx *ctx, const double *fw) {
-        int rc = fourier_sum(ctx, fw, false, ctx->g_acc, 1);
-        if (rc) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
-    }
-
-    // The tail of every image on the Fourier store: the sum over k that stands in the compact device array `dev` is scaled
-    // there into the gradient (`illum`: the illumination) in the parametrisation `wrt`; `dev` is ctx->g_out and goes on to
-    // the host array `out`, or a vector slot (out = nullptr).
-    static int fourier_tail(fwi_ctx *ctx, int32_t wrt, bool illum, void *dev, T *out) {
-        const double dt2 = ctx->cfg.dt * ctx->cfg.dt, S = (double)ctx->istride;
-        if (illum)
-            HIPCHK(ctx, launch_illum_finalize<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, S / (dt2 * dt2),
-                                                 wrt == FWI_WRT_VELOCITY, ctx->stream));
-        else
-            HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)dev, (const T *)ctx->c_dev, (T *)dev, -S / dt2,
-                                                    wrt == FWI_WRT_VELOCITY, ctx->stream));
-        if (out)
-            if (int rc = download_compact(ctx, out, dev)) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
-    }
-
-    // the gradient (`illum`: the illumination) of that sum alone into `dev`
-    static int fourier_finalize(fwi_ctx *ctx, int32_t wrt, const double *fw, bool illum, void *dev, T *out) {
-        int rc = fourier_sum(ctx, fw, illum, dev, 0);
-        return rc ? rc : fourier_tail(ctx, wrt, illum, dev, out);
-    }
-
-    // One lag of an extended image (fwi_feximage.h) into `dev`, through the sum and fourier_tail(wrt = FWI_WRT_SLOWNESS2): the offset image of `h` cells along `axis` (0 = z, 1 = y, 2 = x of the
-    // GridDesc), or with `tau` the time-lag image.  Q_k, M_k and the gradient accumulator are read at most.
-    static int fourier_extended(fwi_ctx *ctx, int axis, int64_t h, const double *tau, const double *fw, void *dev, T *out) {
-        int rc = fourier_weights(ctx, fw, tau);
-        if (rc) return rc;
-        const int F = (int)ctx->four_freqs.size();
-        const T *q = (const T *)ctx->four_acc, *m = (const T *)ctx->four_adj;
-        if (tau)
-            HIPCHK(ctx, launch_feximage_lag<T>((T *)dev, q, m, (const double *)ctx->four_w, ctx->gd.npts, F, ctx->stream));
-        else
-            HIPCHK(ctx, launch_feximage_offset<T>(ctx->gd, (T *)dev, q, m, (const double *)ctx->four_w, F, axis, h,
-                                                  ctx->stream));
-        return fourier_tail(ctx, FWI_WRT_SLOWNESS2, false, dev, out);
-    }
-
-    // One part of the split image (fwi_fsplit.h) into `dev`, through the sum and fourier_tail: `axis` 0 = z, 1 = y, 2 = x of the GridDesc, `taps` the `ntaps` < n_axis taps that can touch a cell.
-    // Q_k, M_k and the gradient accumulator are read at most.
-    static int fourier_split(fwi_ctx *ctx, int32_t wrt, int axis, const double *taps, int ntaps, double alpha, double beta,
-                             const double *fw, void *dev, T *out) {
-        static_assert(FSPLIT_RMAX == FWI_SPLIT_RMAX && FWI_SPLIT_RMAX <= FWI_FOURIER_FMAX, "the taps share four_w");
-        int rc = fourier_weights(ctx, fw, nullptr, false, taps, ntaps);
-        if (rc) return rc;
-        const int F = (int)ctx->four_freqs.size();
-        const double *w = (const double *)ctx->four_w;
-        HIPCHK(ctx, launch_fsplit<T>(ctx->gd, (T *)dev, (const T *)ctx->four_acc, (const T *)ctx->four_adj, w, F, axis,
-                                     w + FWI_FOURIER_FMAX, ntaps, alpha, beta, ctx->stream));
-        return fourier_tail(ctx, wrt, false, dev, out);
     }
 
     // Born modelling dd = J dm (include/fwi.h, fwi_born / fwi_born_imaging).  dm comes from the host (`dm_host`) or from a
@@ -1885,7 +1531,7 @@ struct Impl {
         hipStream_t s = ctx->stream;
         int rc;
         if (!ctx->born_w) HIPCHK(ctx, hipMalloc(&ctx->born_w, (size_t)g.npts * sizeof(T)));
-        if (dm_host && (rc = upload_compact(ctx, ctx->born_w, dm_host))) return rc;
+        if (dm_host && (rc = upload_compact<T>(ctx, ctx->born_w, dm_host))) return rc;
         if (!dm_host && !dm_dev) {  // ones, pad columns zero: 1 / (0 + 1)
             HIPCHK(ctx, hipMemsetAsync(ctx->born_w, 0, (size_t)g.npts * sizeof(T), s));
             HIPCHK(ctx, launch_vec_recip<T>(g, (T *)ctx->born_w, 1.0, 1.0, s));
@@ -1905,11 +1551,11 @@ struct Impl {
         const T *share_amp = nullptr;
         if (ctx->qbf16 && ctx->nsrc > 0) {
             if constexpr (std::is_same<T, float>::value) {
-                if ((rc = ensure(ctx, &ctx->born_src, &ctx->cap_born_src, (size_t)nt * ctx->nsrc * sizeof(T)))) return rc;
+                if ((rc = ensure(ctx, ctx->born_src, (size_t)nt * ctx->nsrc * sizeof(T)))) return rc;
                 HIPCHK(ctx, launch_born_source_share((const float *)ctx->born_w, (const int64_t *)ctx->src.cidx,
-                                                     (const float *)ctx->wav, (float *)ctx->born_src, nt, ctx->nsrc, s));
+                                                     (const float *)ctx->wav.p, (float *)ctx->born_src.p, nt, ctx->nsrc, s));
                 share = &ctx->src;
-                share_amp = (const T *)ctx->born_src;
+                share_amp = (const T *)ctx->born_src.p;
             } else {
                 return ctx->fail(FWI_ESTATE, "the bf16 store is fp32 only");
             }
@@ -1919,7 +1565,7 @@ struct Impl {
         Sweep sw;
         if ((rc = start_sweep(ctx, sw))) return rc;
         const Store st(ctx);
-        T *series = (T *)ctx->series;
+        T *series = (T *)ctx->series.p;
         const int damp = base_args(ctx, 0).damp;
         // steps first .. first + cnt - 1 of the Born sweep; slot(n): what the store holds of step n (n % S == 0)
         auto born_steps = [&](int first, int cnt, auto slot) -> int {
@@ -1966,9 +1612,9 @@ struct Impl {
                 const int cnt = std::min(K, nt - n0);
                 if ((rc = restore_segment(ctx, fw, seg))) return rc;
                 auto qo = [&](int n) -> T * { return st.seg_slot(n, n0); };
-                rc = fused2d ? run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), 1,
+                rc = fused2d ? run_fused(ctx, fw, fspare, n0, 1, cnt, ctx->src, (const T *)ctx->wav.p, nullptr, nullptr, T(0), 1,
                                          st.seg_slot(0, n0))
-                             : run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav, nullptr, nullptr, T(0), qo, noq);
+                             : run_steps(ctx, fw, n0, 1, cnt, ctx->src, (const T *)ctx->wav.p, nullptr, nullptr, T(0), qo, noq);
                 if (rc || (rc = born_steps(n0, cnt, [&](int n) -> const void * { return st.seg_slot(n, n0); }))) return rc;
             }
             adopt_recompute(ctx, fw, fspare);
@@ -1991,18 +1637,18 @@ struct Impl {
         // dd stays on the device as the residual of the next fwi_adjoint(ctx, NULL, ...): per node in ctx->amp (off-grid
         // receivers: gathered per point for the caller, then spread back onto the nodes, as fwi_misfit_l2 does)
         const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
-        const void *out = ctx->series;
+        const void *out = ctx->series.p;
         size_t out_bytes = (size_t)nt * nrec * sizeof(T);
         if (nrec && sp.npts) {
-            if ((rc = ensure(ctx, &ctx->pts_d, &ctx->cap_pts_d, (size_t)nt * sp.npts * sizeof(T)))) return rc;
-            HIPCHK(ctx, launch_gather_series<T>((const T *)ctx->series, (T *)ctx->pts_d, (const int *)sp.pt_start,
+            if ((rc = ensure(ctx, ctx->pts_d, (size_t)nt * sp.npts * sizeof(T)))) return rc;
+            HIPCHK(ctx, launch_gather_series<T>((const T *)ctx->series.p, (T *)ctx->pts_d.p, (const int *)sp.pt_start,
                                                 (const T *)sp.weight, nt, sp.npts, nrec, s));
-            HIPCHK(ctx, launch_scatter_series<T>((const T *)ctx->pts_d, (T *)ctx->amp, (const int *)sp.owner,
+            HIPCHK(ctx, launch_scatter_series<T>((const T *)ctx->pts_d.p, (T *)ctx->amp.p, (const int *)sp.owner,
                                                  (const T *)sp.weight, nt, sp.npts, nrec, s));
-            out = ctx->pts_d;
+            out = ctx->pts_d.p;
             out_bytes = (size_t)nt * sp.npts * sizeof(T);
         } else if (nrec) {
-            HIPCHK(ctx, hipMemcpyAsync(ctx->amp, ctx->series, out_bytes, hipMemcpyDeviceToDevice, s));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->amp.p, ctx->series.p, out_bytes, hipMemcpyDeviceToDevice, s));
         }
         if ((rc = download_series(ctx, seis_out, out, (nrec && seis_out) ? out_bytes : 0))) return rc;
         ctx->have_dev_residual = true;
@@ -2026,9 +1672,9 @@ struct Impl {
         const size_t nlog = (size_t)g.nz * g.ny * g.nx;
         for (int l = 0; l < nlag; ++l) {
             const T *img = images_dev ? (const T *)images_dev[l] : (const T *)ctx->born_w;
-            if (images_host && (rc = upload_compact(ctx, ctx->born_w, images_host + l * nlog))) return rc;
+            if (images_host && (rc = upload_compact<T>(ctx, ctx->born_w, images_host + l * nlog))) return rc;
             if (lag) {
-                if ((rc = fourier_weights(ctx, nullptr, &taus[l], true))) return rc;
+                if ((rc = fourier_weights<T>(ctx, nullptr, &taus[l], true))) return rc;
                 HIPCHK(ctx, launch_fbornx_lag<T>((T *)ctx->four_adj, (const T *)ctx->four_acc, img,
                                                  (const double *)ctx->four_w, g.npts, F, l > 0, ctx->stream));
             } else {
@@ -2045,574 +1691,6 @@ struct Impl {
         HIPCHK(ctx, launch_illum_accumulate<T>((T *)ctx->h_acc, store, ctx->gd.npts, nslots, ctx->qbf16 ? 1 : 0,
                                                ctx->stream));
         return FWI_OK;
-    }
-
-    // H_m = (S / dt^4) acc (the per-step factor of the gradient, S / dt^2, times the 1 / dt^2 of q ~ dt^2 d2u/dt2),
-    // H_c = H_m (2 / c^3)^2, into the compact device array `dev`
-    static int illumination_vec(fwi_ctx *ctx, int32_t wrt, void *dev) {
-        const double dt2 = ctx->cfg.dt * ctx->cfg.dt;
-        HIPCHK(ctx, launch_illum_finalize<T>(ctx->gd, (const T *)ctx->h_acc, (const T *)ctx->c_dev, (T *)dev,
-                                             (double)ctx->istride / (dt2 * dt2), wrt == FWI_WRT_VELOCITY, ctx->stream));
-        return FWI_OK;
-    }
-
-    static int illumination(fwi_ctx *ctx, int32_t wrt, T *out) {
-        int rc = illumination_vec(ctx, wrt, ctx->g_out);
-        if (rc || (rc = download_compact(ctx, out, ctx->g_out))) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
-    }
-
-    static int gradient_vec(fwi_ctx *ctx, int32_t wrt, void *dev) {
-        const double scale = -(double)ctx->istride / (ctx->cfg.dt * ctx->cfg.dt);  // istride: quadrature weight
-        HIPCHK(ctx, launch_finalize_gradient<T>(ctx->gd, (const T *)ctx->g_acc, (const T *)ctx->c_dev, (T *)dev, scale,
-                                                wrt == FWI_WRT_VELOCITY, ctx->stream));
-        return FWI_OK;
-    }
-
-    // weights (nt, ntr) and taps b_0 .. b_R of the caller -> the device; the buffers of the two filter passes.  R_out:
-    // the half-width that meets samples (taps beyond nt - 1 are not uploaded)
-    static int data_prepare(fwi_ctx *ctx, const T *weights, const double *taps, int R, int nt, int ntr, const T **w_dev,
-                            const double **taps_dev, int *R_out) {
-        const size_t n = (size_t)nt * ntr;
-        int rc;
-        if ((rc = ensure(ctx, &ctx->data_tmp, &ctx->cap_data_tmp, n * sizeof(T)))) return rc;
-        if ((rc = ensure(ctx, &ctx->data_part, &ctx->cap_data_part, (size_t)(gather_blocks(nt, ntr) + 1) * sizeof(double))))
-            return rc;
-        *w_dev = nullptr;
-        if (weights) {
-            if ((rc = ensure(ctx, &ctx->data_w, &ctx->cap_data_w, n * sizeof(T)))) return rc;
-            if ((rc = upload_series(ctx, ctx->data_w, weights, n * sizeof(T)))) return rc;
-            *w_dev = (const T *)ctx->data_w;
-        }
-        *taps_dev = nullptr;
-        *R_out = 0;
-        if (taps) {
-            *R_out = std::min(R, nt - 1);
-            const size_t bytes = (size_t)(*R_out + 1) * sizeof(double);
-            if ((rc = ensure(ctx, &ctx->data_taps, &ctx->cap_data_taps, bytes))) return rc;
-            // the taps are the caller's pageable memory: the copy is complete before anything that can fail and return
-            // follows it (at most 32 KB, in the stream's order behind the uploads above)
-            HIPCHK(ctx, hipMemcpyAsync(ctx->data_taps, taps, bytes, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            *taps_dev = (const double *)ctx->data_taps;
-        }
-        return FWI_OK;
-    }
-
-    // What the data misfits share around their own launches: where the gathers lie, the upload of d_obs, the filter B
-    // before and after, the scatter onto the nodes, the read-back of the sum of squares and the state of the device
-    // residual.  Off-grid receivers: everything per POINT (against the gathered synthetics kept by the forward); the
-    // residual is then scattered onto the nodes, where the adjoint sweep injects it.
-    struct Misfit {
-        fwi_ctx *ctx;
-        int nt = 0, ntr = 0;
-        size_t n = 0;
-        bool data = false;          // there are receivers and samples: otherwise nothing is launched
-        T *resid = nullptr;         // d_obs after begin(), the residual after finish(): ctx->amp, or ctx->pts_a per point
-        const T *syn = nullptr;     // the synthetics of the last forward: ctx->series, or ctx->pts_d per point
-        const T *w = nullptr;       // data_prepare's: the weights, the taps of B, the half-width that meets samples
-        const double *b = nullptr;
-        int Re = 0;
-        double *part = nullptr;     // gather_blocks + 1 doubles: the block sums of a gather kernel and their total,
-        const double *sum = nullptr;  // ... which is what finish() reads back
-
-        explicit Misfit(fwi_ctx *c) : ctx(c) {}
-
-        // Whatever residual the device held goes with the upload of d_obs: none is left until finish() has succeeded.
-        int begin(const T *d_obs) {
-            const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
-            nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
-            n = (size_t)nt * ntr;
-            data = n && ctx->nrec;
-            ctx->have_dev_residual = false;
-            ctx->resid_pts_in = fwi_ctx::RESID_PTS_NONE;
-            if (!data) return FWI_OK;
-            resid = (T *)ctx->amp, syn = (const T *)ctx->series;
-            if (sp.npts) {
-                if (int rc = ensure(ctx, &ctx->pts_a, &ctx->cap_pts_a, n * sizeof(T))) return rc;
-                resid = (T *)ctx->pts_a, syn = (const T *)ctx->pts_d;
-            }
-            return upload_series(ctx, resid, d_obs, n * sizeof(T));
-        }
-
-        // ... and the weights, the taps and the buffers of the filter passes
-        int begin(const T *d_obs, const T *weights, const double *taps, int R) {
-            int rc = begin(d_obs);
-            if (rc || !data || (rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
-            part = (double *)ctx->data_part;
-            sum = part + gather_blocks(nt, ntr);
-            return FWI_OK;
-        }
-
-        int filter(T *out, const T *in) {
-            HIPCHK(ctx, launch_fir_time<T>(out, in, nullptr, nullptr, nullptr, b, Re, nt, ntr, nullptr, false, ctx->stream));
-            return FWI_OK;
-        }
-
-        // s1, d1: the synthetics and the data; with taps s' = B d_syn and d' = B d_obs, each rounded to T once
-        int prefilter(const T **s1, const T **d1) {
-            *s1 = syn, *d1 = resid;
-            if (!b) return FWI_OK;
-            int rc;
-            if ((rc = ensure(ctx, &ctx->data_s, &ctx->cap_data_s, n * sizeof(T))) ||
-                (rc = ensure(ctx, &ctx->data_d, &ctx->cap_data_d, n * sizeof(T))) ||
-                (rc = filter((T *)ctx->data_s, syn)) || (rc = filter((T *)ctx->data_d, resid)))
-                return rc;
-            *s1 = (const T *)ctx->data_s, *d1 = (const T *)ctx->data_d;
-            return FWI_OK;
-        }
-
-        // where a misfit that prefilters writes its adjoint source once s' and d' are used up: without taps it is the
-        // residual; with taps it takes the place of s', and finish() has B write r over the uploaded d_obs
-        T *adjoint_source() const { return b ? (T *)ctx->data_s : resid; }
-
-        // *tw := the caller's ntr weights per trace on the device (ctx->data_tw), or nullptr where there are none (all 1)
-        int trace_weights(const double *host, const double **tw) {
-            *tw = nullptr;
-            if (!host) return FWI_OK;
-            const size_t bytes = (size_t)ntr * sizeof(double);
-            if (int rc = ensure(ctx, &ctx->data_tw, &ctx->cap_data_tw, bytes)) return rc;
-            // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
-            HIPCHK(ctx, hipMemcpyAsync(ctx->data_tw, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            *tw = (const double *)ctx->data_tw;
-            return FWI_OK;
-        }
-
-        // resid := B src (src == resid: it is there already), onto the nodes, *ss := the sum of squares
-        int finish(const T *src, double *ss) {
-            const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
-            if (data) {
-                if (src != resid)
-                    if (int rc = filter(resid, src)) return rc;
-                if (sp.npts)
-                    HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
-                                                         (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
-                HIPCHK(ctx, hipMemcpyAsync(ss, sum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            }
-            ctx->have_dev_residual = true;
-            ctx->resid_pts_in = (data && sp.npts) ? fwi_ctx::RESID_PTS_A : fwi_ctx::RESID_PTS_NONE;
-            return FWI_OK;
-        }
-
-        // after finish(): up to two arrays of ntr numbers per trace to the caller (a null destination: not asked for),
-        // under one synchronise; without receivers or samples no trace counts and they are zeros
-        template <typename A, typename B = double>
-        int per_trace(A *out_a, const A *dev_a, B *out_b = nullptr, const B *dev_b = nullptr) {
-            if (!data) {
-                if (out_a) std::fill(out_a, out_a + ntr, A(0));
-                if (out_b) std::fill(out_b, out_b + ntr, B(0));
-                return FWI_OK;
-            }
-            if (out_a) HIPCHK(ctx, hipMemcpyAsync(out_a, dev_a, (size_t)ntr * sizeof(A), hipMemcpyDeviceToHost, ctx->stream));
-            if (out_b) HIPCHK(ctx, hipMemcpyAsync(out_b, dev_b, (size_t)ntr * sizeof(B), hipMemcpyDeviceToHost, ctx->stream));
-            if (out_a || out_b) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            return FWI_OK;
-        }
-    };
-
-    // d_obs -> the residual buffer, then residual := d_syn - d_obs and J = 1/2 sum residual^2, all on the device
-    static int misfit_l2(fwi_ctx *ctx, const T *d_obs, double *J_out) {
-        Misfit m(ctx);
-        double ss = 0.0;
-        int rc = m.begin(d_obs);
-        if (rc) return rc;
-        if (m.data) {
-            if ((rc = sum_partials(ctx, &m.part))) return rc;
-            m.sum = m.part + sum_blocks((int64_t)m.n);
-            HIPCHK(ctx, launch_residual_l2<T>(m.syn, m.resid, (int64_t)m.n, m.part, ctx->stream));
-        }
-        if ((rc = m.finish(m.resid, &ss))) return rc;
-        *J_out = 0.5 * ss;
-        return FWI_OK;
-    }
-
-    // e = M . B (d_syn - d_obs), J = 1/2 sum e^2, r = B (M . e) where the adjoint sweep reads its amplitudes
-    static int misfit_weighted(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, double *J_out) {
-        Misfit m(ctx);
-        double ss = 0.0;
-        int rc = m.begin(d_obs, weights, taps, R);
-        if (rc) return rc;
-        if (m.data) {
-            // neither taps nor weights: e is the plain residual and the call is fwi_misfit_l2 with a fixed-order sum, so
-            // J is summed as there, from the residual as stored; otherwise from the unrounded e
-            const bool plain = !m.w && !m.b;
-            T *e = (T *)ctx->data_tmp;
-            HIPCHK(ctx, launch_fir_time<T>(e, m.syn, m.resid, nullptr, m.w, m.b, m.Re, m.nt, m.ntr, m.part, plain,
-                                           ctx->stream));
-            HIPCHK(ctx, launch_fir_time<T>(m.resid, e, nullptr, m.w, nullptr, m.b, m.Re, m.nt, m.ntr, nullptr, false,
-                                           ctx->stream));
-        }
-        if ((rc = m.finish(m.resid, &ss))) return rc;
-        *J_out = 0.5 * ss;
-        return FWI_OK;
-    }
-
-    // s' = B d_syn, d' = B d_obs, e = M . (C_f s' - d'), J = 1/2 sum e^2 + mu/2 |f|^2, r = B C_f^T (M . e) where the
-    // adjoint sweep reads its amplitudes; f given, or the minimiser (G + mu I)^-1 b of J
-    static int misfit_matched(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, int L, double mu,
-                              const double *f_in, double *f_out, double *normal_out, double *J_out) {
-        const int K = 2 * L + 1;
-        std::vector<double> f(K, 0.0), nrm((size_t)K * K + K, 0.0);
-        if (f_in) std::copy(f_in, f_in + K, f.begin());
-        Misfit m(ctx);
-        const T *s1 = nullptr, *d1 = nullptr;
-        int rc = m.begin(d_obs, weights, taps, R);
-        if (rc) return rc;
-        if (m.data) {
-            if ((rc = ensure(ctx, &ctx->match_f, &ctx->cap_match_f, (size_t)K * sizeof(double)))) return rc;
-            if ((rc = m.prefilter(&s1, &d1))) return rc;
-            if (!f_in || normal_out) {
-                if ((rc = ensure(ctx, &ctx->match_part, &ctx->cap_match_part,
-                                 (size_t)match_normal_partials(m.nt, m.ntr, L) * sizeof(double))))
-                    return rc;
-                if ((rc = ensure(ctx, &ctx->match_norm, &ctx->cap_match_norm, nrm.size() * sizeof(double)))) return rc;
-                HIPCHK(ctx, launch_match_normal<T>((double *)ctx->match_norm, (double *)ctx->match_part, s1, d1, m.w, L,
-                                                   m.nt, m.ntr, ctx->stream));
-                HIPCHK(ctx, hipMemcpyAsync(nrm.data(), ctx->match_norm, nrm.size() * sizeof(double),
-                                           hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            }
-        }
-        if (!f_in && match_solve(nrm.data(), nrm.data() + (size_t)K * K, K, mu, f.data()))
-            return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: the normal matrix G + mu I (L=%d, mu=%g) is not positive "
-                                         "definite: raise mu", L, mu);
-        double ss = 0.0;
-        T *ct = nullptr;
-        if (m.data) {
-            // (the filter is this call's pageable memory: the copy is complete before anything that can return follows)
-            HIPCHK(ctx, hipMemcpyAsync(ctx->match_f, f.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice,
-                                       ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            const double *fd = (const double *)ctx->match_f;
-            T *e = (T *)ctx->data_tmp;
-            HIPCHK(ctx, launch_match_apply<T>(e, s1, d1, nullptr, m.w, fd, L, false, m.nt, m.ntr, m.part, ctx->stream));
-            ct = m.adjoint_source();  // C_f^T (M . e)
-            HIPCHK(ctx, launch_match_apply<T>(ct, e, nullptr, m.w, nullptr, fd, L, true, m.nt, m.ntr, nullptr, ctx->stream));
-        }
-        if ((rc = m.finish(ct, &ss))) return rc;
-        double ff = 0.0;
-        for (int k = 0; k < K; ++k) ff += f[k] * f[k];
-        *J_out = 0.5 * ss + 0.5 * mu * ff;
-        if (f_out) std::copy(f.begin(), f.end(), f_out);
-        if (normal_out) std::copy(nrm.begin(), nrm.end(), normal_out);
-        return FWI_OK;
-    }
-
-    // s' = B d_syn, d' = B d_obs, e = M . (E(s')^p - E(d')^p), J = 1/2 sum e^2, r = B (g1 - H g2) where the adjoint sweep
-    // reads its amplitudes (fwi_envelope.h)
-    static int misfit_envelope(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
-                               const double *hilbert, int Q, int power, double eps, double *J_out) {
-        Misfit m(ctx);
-        double ss = 0.0;
-        T *q = nullptr;
-        int rc = m.begin(d_obs, weights, taps, R);
-        if (rc) return rc;
-        if (m.data) {
-            if ((rc = ensure(ctx, &ctx->env_g2, &ctx->cap_env_g2, m.n * sizeof(T)))) return rc;
-            // the taps that meet samples; are the even ones all zero (a Hilbert transformer's are)?
-            const int Qe = std::max(std::min(Q, m.nt - 1), 1);
-            bool odd_only = true;
-            for (int k = 2; k <= Qe; k += 2) odd_only = odd_only && hilbert[k - 1] == 0.0;
-            if ((rc = ensure(ctx, &ctx->env_h, &ctx->cap_env_h, (size_t)Qe * sizeof(double)))) return rc;
-            // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
-            HIPCHK(ctx, hipMemcpyAsync(ctx->env_h, hilbert, (size_t)Qe * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            const double *hd = (const double *)ctx->env_h;
-            const T *s1, *d1;
-            if ((rc = m.prefilter(&s1, &d1))) return rc;
-            T *g1 = (T *)ctx->data_tmp, *g2 = (T *)ctx->env_g2;
-            HIPCHK(ctx, launch_env_forward<T>(g1, g2, s1, d1, m.w, hd, Qe, odd_only, power, eps, m.nt, m.ntr, m.part,
-                                              ctx->stream));
-            q = m.adjoint_source();  // g1 - H g2
-            HIPCHK(ctx, launch_env_adjoint<T>(q, g1, g2, hd, Qe, odd_only, m.nt, m.ntr, ctx->stream));
-        }
-        if ((rc = m.finish(q, &ss))) return rc;
-        *J_out = 0.5 * ss;
-        return FWI_OK;
-    }
-
-    // s' = B d_syn, d' = B d_obs, rho_j the normalised zero-lag correlation of the weighted traces M s', M d' with the
-    // floor eps, J = sum_j w_j (1 - rho_j), r = B g where the adjoint sweep reads its amplitudes (fwi_corr.h)
-    static int misfit_correlation(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
-                                  const double *trace_weights, double eps, double *J_out, double *rho_out) {
-        Misfit m(ctx);
-        double J = 0.0;
-        T *g = nullptr;
-        int rc = m.begin(d_obs, weights, taps, R);
-        if (rc) return rc;
-        if (m.data) {
-            const size_t np = corr_partials(m.nt, m.ntr);
-            if ((rc = ensure(ctx, &ctx->corr_part, &ctx->cap_corr_part, np * sizeof(double))) ||
-                (rc = ensure(ctx, &ctx->corr_coef, &ctx->cap_corr_coef, (size_t)3 * m.ntr * sizeof(double))))
-                return rc;
-            const double *tw;
-            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
-            double *part = (double *)ctx->corr_part, *coef = (double *)ctx->corr_coef;
-            m.sum = part + (np - 1);  // the total of the terms w_j (1 - rho_j): J itself
-            const T *s1, *d1;
-            if ((rc = m.prefilter(&s1, &d1))) return rc;
-            HIPCHK(ctx, launch_corr_sums<T>(part, s1, d1, m.w, m.nt, m.ntr, ctx->stream));
-            HIPCHK(ctx, launch_corr_coeffs(coef, part, tw, eps, m.nt, m.ntr, ctx->stream));
-            g = m.adjoint_source();  // in place of s' (with taps) or of d_obs (without): elementwise
-            HIPCHK(ctx, launch_corr_source<T>(g, s1, d1, m.w, coef, m.nt, m.ntr, ctx->stream));
-        }
-        if ((rc = m.finish(g, &J))) return rc;
-        // without receivers or samples rho_out stays as the caller handed it in, as it always has (the two misfits below
-        // zero their per-trace outputs then): hence only with data
-        if (m.data && (rc = m.per_trace(rho_out, (const double *)ctx->corr_coef + 2 * (size_t)m.ntr))) return rc;
-        *J_out = J;
-        return FWI_OK;
-    }
-
-    // s' = B d_syn, d' = B d_obs, c_j(k) the correlation of the weighted traces M s', M d' over the lags |k| <= Ke, tau_j
-    // the delay at its refined maximum, J = 1/2 sum_j w_j tau_j^2, r = B g where the adjoint sweep reads its amplitudes
-    // (fwi_ttime.h)
-    static int misfit_traveltime(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
-                                 const double *trace_weights, int K, double *J_out, double *tau_out, int32_t *lag_out) {
-        Misfit m(ctx);
-        double J = 0.0;
-        T *g = nullptr;
-        int rc = m.begin(d_obs, weights, taps, R);
-        if (rc) return rc;
-        if (m.data) {
-            const size_t np = tt_partials(m.nt, m.ntr, K);
-            if ((rc = ensure(ctx, &ctx->tt_part, &ctx->cap_tt_part, np * sizeof(double))) ||
-                (rc = ensure(ctx, &ctx->tt_coef, &ctx->cap_tt_coef, (size_t)4 * m.ntr * sizeof(double))) ||
-                (rc = ensure(ctx, &ctx->tt_lag, &ctx->cap_tt_lag, (size_t)m.ntr * sizeof(int32_t))))
-                return rc;
-            const double *tw;
-            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
-            double *part = (double *)ctx->tt_part, *coef = (double *)ctx->tt_coef;
-            int32_t *lag = (int32_t *)ctx->tt_lag;
-            m.sum = part + (np - 1);  // the total of the terms 1/2 w_j tau_j^2: J itself
-            const T *s1, *d1;
-            if ((rc = m.prefilter(&s1, &d1))) return rc;
-            HIPCHK(ctx, launch_tt_xcorr<T>(part, s1, d1, m.w, K, m.nt, m.ntr, ctx->stream));
-            HIPCHK(ctx, launch_tt_pick(coef, lag, part, tw, ctx->cfg.dt, K, m.nt, m.ntr, ctx->stream));
-            // g reads d' at shifted rows, and without taps adjoint_source() IS d': g goes to the spare gather buffer, and
-            // finish() filters (with taps) or copies (without) it into place
-            g = (T *)ctx->data_tmp;
-            HIPCHK(ctx, launch_tt_source<T>(g, d1, m.w, coef, lag, m.nt, m.ntr, ctx->stream));
-        }
-        if ((rc = m.finish(g, &J)) ||
-            (rc = m.per_trace(tau_out, (const double *)ctx->tt_coef, lag_out, (const int32_t *)ctx->tt_lag)))
-            return rc;
-        *J_out = J;
-        return FWI_OK;
-    }
-
-    // s' = B d_syn, d' = B d_obs, W_j the squared 2-Wasserstein distance between the weighted traces M s', M d' made
-    // positive and normalised to densities along time, J = 1/2 sum_j w_j W_j, r = B g where the adjoint sweep reads its
-    // amplitudes (fwi_ot.h)
-    static int misfit_transport(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
-                                const double *trace_weights, int transform, double param, double *J_out, double *w2_out,
-                                int32_t *counts_out) {
-        Misfit m(ctx);
-        double J = 0.0;
-        T *g = nullptr;
-        const double *w2 = nullptr;  // the distances W_j within the work array
-        int rc = m.begin(d_obs, weights, taps, R);
-        if (rc) return rc;
-        if (m.data) {
-            if ((rc = ensure(ctx, &ctx->ot_work, &ctx->cap_ot_work, ot_work_doubles(m.nt, m.ntr) * sizeof(double))) ||
-                (rc = ensure(ctx, &ctx->ot_counts, &ctx->cap_ot_counts, (size_t)m.ntr * sizeof(int32_t))))
-                return rc;
-            const double *tw;
-            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
-            double *work = (double *)ctx->ot_work;
-            m.sum = work + ot_total_at(m.nt, m.ntr);  // the total of the terms 1/2 w_j W_j: J itself
-            w2 = work + ot_w2_at(m.nt, m.ntr);
-            const T *s1, *d1;
-            if ((rc = m.prefilter(&s1, &d1))) return rc;
-            g = m.adjoint_source();  // in place of s' (with taps) or of d_obs (without): elementwise, written last
-            HIPCHK(ctx, launch_ot_misfit<T>(work, (int32_t *)ctx->ot_counts, g, s1, d1, m.w, tw, transform, param,
-                                            ctx->cfg.dt, m.nt, m.ntr, ctx->stream));
-        }
-        if ((rc = m.finish(g, &J)) || (rc = m.per_trace(w2_out, w2, counts_out, (const int32_t *)ctx->ot_counts))) return rc;
-        *J_out = J;
-        return FWI_OK;
-    }
-
-    // The twiddles of fwi_misfit_spectral, formed in fp64 as fourier_table forms the store's (from the fractional part of
-    // f_k n dt) and kept on the context: block k, row n = (cos theta_kn, sin theta_kn), the rows from nt on zero
-    // (spec_table_rows).  Rebuilt only when nt or the frequencies change.
-    static int spectral_table(fwi_ctx *ctx, int nt, int F, const double *freqs) {
-        if (ctx->spec_table && ctx->spec_table_nt == nt && ctx->spec_table_freqs.size() == (size_t)F &&
-            std::equal(freqs, freqs + F, ctx->spec_table_freqs.begin()))
-            return FWI_OK;
-        const int rows = spec_table_rows(nt);
-        ctx->spec_table_nt = 0;  // no table until the new one is complete
-        if (int rc = ensure(ctx, &ctx->spec_table, &ctx->cap_spec_table, spec_table_doubles(nt, F) * sizeof(double)))
-            return rc;
-        std::vector<double> &t = ctx->spec_table_host;
-        t.assign(spec_table_doubles(nt, F), 0.0);
-        for (int k = 0; k < F; ++k)
-            for (int n = 0; n < nt; ++n) {
-                const double x = freqs[k] * ctx->cfg.dt * n, th = 2.0 * M_PI * (x - std::floor(x));
-                t[((size_t)k * rows + n) * 2] = std::cos(th);
-                t[((size_t)k * rows + n) * 2 + 1] = std::sin(th);
-            }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->spec_table, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->spec_table_nt = nt;
-        ctx->spec_table_freqs.assign(freqs, freqs + F);
-        return FWI_OK;
-    }
-
-    // s' = B d_syn, d' = B d_obs, S_kj and O_kj the Fourier coefficients of the weighted traces M s', M d' at the F
-    // frequencies, J the sum over the pairs (k, j) of the terms of `kind`, r = B g where the adjoint sweep reads its
-    // amplitudes (fwi_spec.h)
-    static int misfit_spectral(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, int F,
-                               const double *freqs, int kind, double eps, const double *freq_weights,
-                               const double *trace_weights, double *J_out, double *phase_out, double *logamp_out,
-                               uint8_t *counts_out) {
-        Misfit m(ctx);
-        double J = 0.0;
-        T *g = nullptr;
-        int rc = m.begin(d_obs, weights, taps, R);
-        if (rc) return rc;
-        const size_t npair = (size_t)F * m.ntr;
-        if (m.data) {
-            if ((rc = ensure(ctx, &ctx->spec_part, &ctx->cap_spec_part, spec_partials(m.nt, m.ntr, F) * sizeof(double))) ||
-                (rc = ensure(ctx, &ctx->spec_coef, &ctx->cap_spec_coef, spec_coef_doubles(m.ntr, F) * sizeof(double))) ||
-                (rc = ensure(ctx, &ctx->spec_counts, &ctx->cap_spec_counts, npair)) ||
-                (rc = spectral_table(ctx, m.nt, F, freqs)))
-                return rc;
-            const double *tw, *fw = nullptr;
-            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
-            if (freq_weights) {
-                if ((rc = ensure(ctx, &ctx->spec_fw, &ctx->cap_spec_fw, (size_t)F * sizeof(double)))) return rc;
-                // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
-                HIPCHK(ctx, hipMemcpyAsync(ctx->spec_fw, freq_weights, (size_t)F * sizeof(double), hipMemcpyHostToDevice,
-                                           ctx->stream));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                fw = (const double *)ctx->spec_fw;
-            }
-            double *part = (double *)ctx->spec_part, *coef = (double *)ctx->spec_coef;
-            const double *table = (const double *)ctx->spec_table;
-            m.sum = coef + spec_total_at(m.ntr, F);  // the total of the terms of J: J itself
-            const T *s1, *d1;
-            if ((rc = m.prefilter(&s1, &d1))) return rc;
-            HIPCHK(ctx, launch_spec_analysis<T>(part, s1, d1, m.w, table, F, m.nt, m.ntr, ctx->stream));
-            HIPCHK(ctx, launch_spec_coeffs(coef, (uint8_t *)ctx->spec_counts, part, fw, tw, kind, eps, F, m.nt, m.ntr,
-                                           ctx->stream));
-            g = m.adjoint_source();  // in place of s' (with taps) or of d_obs (without): both are used up
-            HIPCHK(ctx, launch_spec_source<T>(g, m.w, coef, table, F, m.nt, m.ntr, ctx->stream));
-        }
-        if ((rc = m.finish(g, &J))) return rc;
-        // the three (F, ntr) outputs under one synchronise; without receivers or samples no pair counts: zeros
-        if (!m.data) {
-            if (phase_out) std::fill(phase_out, phase_out + npair, 0.0);
-            if (logamp_out) std::fill(logamp_out, logamp_out + npair, 0.0);
-            if (counts_out) std::fill(counts_out, counts_out + npair, (uint8_t)0);
-        } else if (phase_out || logamp_out || counts_out) {
-            const double *coef = (const double *)ctx->spec_coef;
-            if (phase_out)
-                HIPCHK(ctx, hipMemcpyAsync(phase_out, coef + spec_phase_at(m.ntr, F), npair * sizeof(double),
-                                           hipMemcpyDeviceToHost, ctx->stream));
-            if (logamp_out)
-                HIPCHK(ctx, hipMemcpyAsync(logamp_out, coef + spec_logamp_at(m.ntr, F), npair * sizeof(double),
-                                           hipMemcpyDeviceToHost, ctx->stream));
-            if (counts_out)
-                HIPCHK(ctx, hipMemcpyAsync(counts_out, ctx->spec_counts, npair, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        *J_out = J;
-        return FWI_OK;
-    }
-
-    // device residual := B M^2 B residual: per node, or per off-grid point and scattered onto the nodes again
-    static int residual_weight(fwi_ctx *ctx, const T *weights, const double *taps, int R) {
-        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
-        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
-        if (!ctx->nrec || !nt || !ntr) return FWI_OK;
-        void *resid = ctx->amp;
-        if (sp.npts) {
-            if (ctx->resid_pts_in == fwi_ctx::RESID_PTS_NONE)
-                return ctx->fail(FWI_ESTATE, "fwi_residual_weight: the residual's per-point series were not kept "
-                                             "(off-grid receivers): weight it on the host");
-            resid = ctx->resid_pts_in == fwi_ctx::RESID_PTS_A ? ctx->pts_a : ctx->pts_d;
-        }
-        int rc, Re;
-        const T *w;
-        const double *b;
-        if ((rc = data_prepare(ctx, weights, taps, R, nt, ntr, &w, &b, &Re))) return rc;
-        HIPCHK(ctx, launch_fir_time<T>((T *)ctx->data_tmp, (const T *)resid, nullptr, nullptr, w, b, Re, nt, ntr, nullptr,
-                                       false, ctx->stream));
-        HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)ctx->data_tmp, nullptr, w, nullptr, b, Re, nt, ntr, nullptr,
-                                       false, ctx->stream));
-        if (sp.npts)
-            HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp, (const int *)sp.owner,
-                                                 (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
-    }
-
-    static int vec_dot(fwi_ctx *ctx, const void *x, const void *y, double *out) {
-        double *part;
-        int rc = sum_partials(ctx, &part);
-        if (rc) return rc;
-        HIPCHK(ctx, launch_dot<T>((const T *)x, (const T *)y, ctx->gd.npts, part, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out, part + sum_blocks(ctx->gd.npts), sizeof(double), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
-    }
-
-    static int vec_absmax(fwi_ctx *ctx, const void *x, double *out) {
-        HIPCHK(ctx, hipMemsetAsync(ctx->red, 0, sizeof(double), ctx->stream));
-        HIPCHK(ctx, launch_absmax<T>((const T *)x, ctx->gd.npts, ctx->red, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(out, ctx->red, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
-    }
-
-    static int vec_axpby(fwi_ctx *ctx, void *y, double a, const void *x, double b) {
-        HIPCHK(ctx, launch_axpby<T>((T *)y, a, (const T *)x, b, ctx->gd.npts, ctx->stream));
-        return FWI_OK;
-    }
-
-    static int vec_clip(fwi_ctx *ctx, void *x, double lo, double hi) {
-        HIPCHK(ctx, launch_clip<T>(ctx->gd, (T *)x, lo, hi, ctx->stream));
-        return FWI_OK;
-    }
-
-    static int gradient(fwi_ctx *ctx, int32_t wrt, T *out) {
-        const GridDesc &g = ctx->gd;
-        const double scale = -(double)ctx->istride / (ctx->cfg.dt * ctx->cfg.dt);  // istride: quadrature weight
-        HIPCHK(ctx, launch_finalize_gradient<T>(g, (const T *)ctx->g_acc, (const T *)ctx->c_dev,
-                                                (T *)ctx->g_out, scale, wrt == FWI_WRT_VELOCITY, ctx->stream));
-        int rc = download_compact(ctx, out, ctx->g_out);
-        if (rc) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return FWI_OK;
-    }
-
-    static int dot(fwi_ctx *ctx, const T *a, const T *b, int64_t n, double *out) {
-        double *part;
-        int rc = sum_partials(ctx, &part);
-        if (rc) return rc;
-        void *da = nullptr, *db = nullptr;
-        HIPCHK(ctx, hipMalloc(&da, (size_t)n * sizeof(T)));
-        hipError_t e = hipMalloc(&db, (size_t)n * sizeof(T));
-        if (e != hipSuccess) {
-            (void)hipFree(da);
-            return ctx->fail(FWI_ENOMEM, "hipMalloc: %s", hipGetErrorString(e));
-        }
-        do {
-            if ((e = hipMemcpyAsync(da, a, (size_t)n * sizeof(T), hipMemcpyHostToDevice, ctx->stream))) break;
-            if ((e = hipMemcpyAsync(db, b, (size_t)n * sizeof(T), hipMemcpyHostToDevice, ctx->stream))) break;
-            if ((e = launch_dot<T>((const T *)da, (const T *)db, n, part, ctx->stream))) break;
-            if ((e = hipMemcpyAsync(out, part + sum_blocks(n), sizeof(double), hipMemcpyDeviceToHost, ctx->stream))) break;
-            e = hipStreamSynchronize(ctx->stream);
-        } while (0);
-        if (e != hipSuccess) rc = ctx->fail(FWI_EHIP, "fwi_dot: %s", hipGetErrorString(e));
-        (void)hipFree(da);
-        (void)hipFree(db);
-        return rc;
     }
 };
 
@@ -2740,44 +1818,6 @@ bool parse_fixed_placement(const char *s, int k[8]) {
 }
 
 }  // namespace
-
-template <typename T>
-static int vec_smooth_passes(fwi_ctx *ctx, void *vy, const int *axis, const int *R, const double (*w)[SMOOTH_RMAX + 1],
-                             int npass) {
-    // ping-pong between the vector and the context's spare one; an odd number of passes ends in the spare: copied back
-    T *cur = (T *)vy, *other = (T *)ctx->smooth_tmp;
-    for (int p = 0; p < npass; ++p) {
-        T wt[SMOOTH_RMAX + 1];
-        for (int k = 0; k <= R[p]; ++k) wt[k] = (T)w[p][k];
-        HIPCHK(ctx, launch_smooth_axis<T>(ctx->gd, other, cur, axis[p], R[p], wt, ctx->stream));
-        std::swap(cur, other);
-    }
-    if (cur != (T *)vy)
-        HIPCHK(ctx, hipMemcpyAsync(vy, cur, (size_t)ctx->gd.npts * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
-    return FWI_OK;
-}
-
-template <typename T>
-static int vec_regularizer(fwi_ctx *ctx, int32_t kind, const void *x, const void *x0, const void *v, void *out,
-                           double alpha, double beta, const double w[3], double eps, double *value_out) {
-    const int64_t nb = reg_blocks<T>(ctx->gd);
-    if (!ctx->reg_part) HIPCHK(ctx, hipMalloc(&ctx->reg_part, (size_t)(nb + 1) * sizeof(double)));
-    double *part = (double *)ctx->reg_part;
-    HIPCHK(ctx, launch_regularizer<T>(ctx->gd, kind, (T *)out, (const T *)x, (const T *)x0, (const T *)v, alpha, beta, w,
-                                      eps, part, ctx->stream));
-    if (value_out) {
-        HIPCHK(ctx, hipMemcpyAsync(value_out, part + nb, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return FWI_OK;
-}
-
-// An array of the caller's in the context's dtype, as DISPATCH_CALL hands it to Impl<T>: const float * or const double *
-struct typed {
-    const void *p;
-    explicit typed(const void *q) : p(q) {}
-    template <typename T> operator const T *() const { return (const T *)p; }
-};
 
 extern "C" {
 
@@ -3016,41 +2056,38 @@ void fwi_destroy(fwi_ctx *ctx) {
     int k = 0;
     for (fwi_ctx::PointSet *ps : {&ctx->src, &ctx->rec}) {
         int j = 0;
-        for (void *p : {ps->pidx, ps->cidx, ps->cu, ps->cq, ps->s_start, ps->s_pidx, ps->s_cidx, ps->s_cu,
+        for (void *p : {ps->pidx, ps->cidx, ps->cu, ps->cq, ps->s_start.p, ps->s_pidx, ps->s_cidx, ps->s_cu,
                         ps->s_cq, ps->s_col, ps->s_run, ps->fi_run, ps->fi_start, ps->fi_lz, ps->fi_lx, ps->fi_col, ps->fi_int,
-                        ps->fi_cidx, ps->fi_cu, ps->fi_cq, ps->fr_start, ps->fr_lz, ps->fr_lx, ps->fr_col, ps->pr_start,
-                        ps->pr_ent})
+                        ps->fi_cidx, ps->fi_cu, ps->fi_cq, ps->fr_start, ps->fr_lz, ps->fr_lx, ps->fr_col, ps->pr_start.p,
+                        ps->pr_ent.p})
             release(ps == &ctx->src ? "src" : "rec", j++, p);
     }
+    // the fields of fwi_create and of the sweeps; the on-demand buffers of the families follow from their lists (fwi_host.h)
     const struct {
         const char *member;
         void *p;
     } fields[] = {{"u", ctx->u[0]}, {"u", ctx->u[1]}, {"C", ctx->C}, {"c_dev", ctx->c_dev}, {"dz", ctx->dz}, {"dy", ctx->dy},
-                  {"dx", ctx->dx}, {"q_store", ctx->q_store}, {"four_acc", ctx->four_acc}, {"four_ring", ctx->four_ring},
-                  {"four_tw", ctx->four_tw}, {"four_adj", ctx->four_adj}, {"four_w", ctx->four_w},
+                  {"dx", ctx->dx}, {"q_store", ctx->q_store},
                   {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc}, {"born_w", ctx->born_w},
-                  {"g_out", ctx->g_out}, {"red", ctx->red}, {"amp", ctx->amp}, {"series", ctx->series}, {"wav", ctx->wav},
+                  {"g_out", ctx->g_out}, {"red", ctx->red},
                   {"snap", ctx->snap}, {"fwd", ctx->fwd[0]}, {"fwd", ctx->fwd[1]}, {"fx", ctx->fx[0]}, {"fx", ctx->fx[1]},
                   {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
                   {"pml_snap", ctx->pml_snap}, {"pml_tz", ctx->pml_tz}, {"pml_ty", ctx->pml_ty},
-                  {"fused_order", ctx->fused_order}, {"pts_a", ctx->pts_a}, {"pts_d", ctx->pts_d},
-                  {"born_src", ctx->born_src}, {"smooth_tmp", ctx->smooth_tmp}, {"reg_part", ctx->reg_part},
-                  {"sum_part", ctx->sum_part},
-                  {"data_tmp", ctx->data_tmp}, {"data_w", ctx->data_w}, {"data_taps", ctx->data_taps},
-                  {"data_part", ctx->data_part}, {"data_s", ctx->data_s}, {"data_d", ctx->data_d}, {"data_tw", ctx->data_tw},
-                  {"match_part", ctx->match_part}, {"match_norm", ctx->match_norm}, {"match_f", ctx->match_f},
-                  {"env_g2", ctx->env_g2}, {"env_h", ctx->env_h},
-                  {"corr_part", ctx->corr_part}, {"corr_coef", ctx->corr_coef},
-                  {"tt_part", ctx->tt_part}, {"tt_coef", ctx->tt_coef}, {"tt_lag", ctx->tt_lag},
-                  {"ot_work", ctx->ot_work}, {"ot_counts", ctx->ot_counts},
-                  {"spec_part", ctx->spec_part}, {"spec_coef", ctx->spec_coef}, {"spec_counts", ctx->spec_counts},
-                  {"spec_fw", ctx->spec_fw}, {"spec_table", ctx->spec_table}};
+                  {"fused_order", ctx->fused_order}};
     const char *prev = "";
     for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
         k = strcmp(prev, f.member) ? 0 : k + 1;
         prev = f.member;
         release(f.member, k, f.p);
     }
+#define RELEASE_BUF(name) release(#name, 0, ctx->name.p);
+#define RELEASE_PTR(name) release(#name, 0, ctx->name);
+    FWI_SHOT_BUFS(RELEASE_BUF)
+    FWI_VEC_PTRS(RELEASE_PTR)
+    FWI_FOURIER_PTRS(RELEASE_PTR)
+    FWI_MISFIT_BUFS(RELEASE_BUF)
+#undef RELEASE_BUF
+#undef RELEASE_PTR
     k = 0;
     for (void *v : ctx->vecs) release("vecs", k++, v);
     for (int d = 0; d < 3; ++d) {
@@ -3073,10 +2110,6 @@ void fwi_destroy(fwi_ctx *ctx) {
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
-
-#define DISPATCH(ctx, expr32, expr64) ((ctx)->cfg.dtype == FWI_F32 ? (expr32) : (expr64))
-// ... of one member of Impl<float> or Impl<double>, with the argument list written once (the caller's arrays: typed(p))
-#define DISPATCH_CALL(ctx, fn, ...) DISPATCH(ctx, Impl<float>::fn(ctx, __VA_ARGS__), Impl<double>::fn(ctx, __VA_ARGS__))
 
 int fwi_set_model(fwi_ctx *ctx, const void *c_host) {
     if (!ctx) return FWI_EINVAL;
@@ -3181,336 +2214,11 @@ int fwi_adjoint(fwi_ctx *ctx, const void *residual, int32_t image, void *adj_src
                     Impl<double>::adjoint(ctx, (const double *)residual, image, (double *)adj_src_out));
 }
 
-// The checks every data misfit begins with: a forward run to compare, and the arguments all of them take (`out`: J_out,
-// or nullptr where another mandatory pointer is null).
-static int misfit_callable(fwi_ctx *ctx, const char *who, const void *d_obs, const void *out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->have_forward) return ctx->fail(FWI_ESTATE, "%s: no forward run whose data to compare", who);
-    if (!out || (ctx->nrec && !d_obs)) return ctx->fail(FWI_EINVAL, "%s: null argument", who);
-    return FWI_OK;
-}
-
-// ... and the one they end with, after their own parameters: the synthetics are still there (`also`: what else, besides
-// an fwi_adjoint, the entry point names as having overwritten them).  Selects the device.
-static int misfit_synthetics(fwi_ctx *ctx, const char *who, const char *also) {
-    if (!ctx->have_syn)
-        return ctx->fail(FWI_ESTATE, "%s: the synthetics of the last forward are gone (an fwi_adjoint %shas run since): "
-                                     "call it between fwi_forward and fwi_adjoint", who, also);
-    (void)hipSetDevice(ctx->cfg.device);
-    return FWI_OK;
-}
-
-int fwi_misfit_l2(fwi_ctx *ctx, const void *d_obs, double *J_out) {
-    if (int rc = misfit_callable(ctx, "fwi_misfit_l2", d_obs, J_out)) return rc;
-    if (int rc = misfit_synthetics(ctx, "fwi_misfit_l2", "")) return rc;
-    return DISPATCH_CALL(ctx, misfit_l2, typed(d_obs), J_out);
-}
-
-static int data_args(fwi_ctx *ctx, const char *who, const double *taps, int32_t R) {
-    if (R < 0 || R > FIR_RMAX) return ctx->fail(FWI_EINVAL, "%s: R=%d outside [0, %d]", who, (int)R, FIR_RMAX);
-    if (R > 0 && !taps) return ctx->fail(FWI_EINVAL, "%s: null taps with R=%d", who, (int)R);
-    return FWI_OK;
-}
-
-// the weights per trace, one per node receiver or per off-grid point (nullptr: none)
-static int trace_weight_args(fwi_ctx *ctx, const char *who, const double *trace_weights) {
-    if (!trace_weights || !ctx->nrec) return FWI_OK;
-    const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
-    for (int j = 0; j < ntr; ++j)
-        if (!(trace_weights[j] >= 0.0) || !std::isfinite(trace_weights[j]))
-            return ctx->fail(FWI_EINVAL, "%s: trace_weights[%d]=%g must be finite and >= 0", who, j, trace_weights[j]);
-    return FWI_OK;
-}
-
-// a scalar parameter `name` that must be finite and >= 0 (`positive`: > 0)
-static int nonneg_finite(fwi_ctx *ctx, const char *who, const char *name, double v, bool positive = false) {
-    if (std::isfinite(v) && (positive ? v > 0.0 : v >= 0.0)) return FWI_OK;
-    return ctx->fail(FWI_EINVAL, "%s: %s=%g must be finite and %s 0", who, name, v, positive ? ">" : ">=");
-}
-
-int fwi_misfit_weighted(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
-                        double *J_out) {
-    if (int rc = misfit_callable(ctx, "fwi_misfit_weighted", d_obs, J_out)) return rc;
-    if (int rc = data_args(ctx, "fwi_misfit_weighted", taps, R)) return rc;
-    if (int rc = misfit_synthetics(ctx, "fwi_misfit_weighted", "or fwi_born ")) return rc;
-    return DISPATCH_CALL(ctx, misfit_weighted, typed(d_obs), typed(weights), taps, R, J_out);
-}
-
-int fwi_misfit_matched(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R, int32_t L,
-                       double mu, const double *f_in, double *f_out, double *normal_out, double *J_out) {
-    if (int rc = misfit_callable(ctx, "fwi_misfit_matched", d_obs, J_out)) return rc;
-    if (int rc = data_args(ctx, "fwi_misfit_matched", taps, R)) return rc;
-    if (L < 0 || L > FWI_MATCH_LMAX)
-        return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: L=%d outside [0, %d]", (int)L, FWI_MATCH_LMAX);
-    if (int rc = nonneg_finite(ctx, "fwi_misfit_matched", "mu", mu)) return rc;
-    if (f_in)
-        for (int k = 0; k < 2 * L + 1; ++k)
-            if (!std::isfinite(f_in[k])) return ctx->fail(FWI_EINVAL, "fwi_misfit_matched: f_in[%d] is not finite", k);
-    if (int rc = misfit_synthetics(ctx, "fwi_misfit_matched", "or fwi_born ")) return rc;
-    return DISPATCH_CALL(ctx, misfit_matched, typed(d_obs), typed(weights), taps, R, L, mu, f_in, f_out, normal_out, J_out);
-}
-
-int fwi_misfit_envelope(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
-                        const double *hilbert, int32_t Q, int32_t power, double eps, double *J_out) {
-    if (int rc = misfit_callable(ctx, "fwi_misfit_envelope", d_obs, hilbert ? J_out : nullptr)) return rc;
-    if (int rc = data_args(ctx, "fwi_misfit_envelope", taps, R)) return rc;
-    if (Q < 1 || Q > FIR_RMAX) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: Q=%d outside [1, %d]", (int)Q, FIR_RMAX);
-    for (int k = 0; k < Q; ++k)
-        if (!std::isfinite(hilbert[k])) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: hilbert[%d] is not finite", k);
-    if (power != 1 && power != 2) return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: power=%d is neither 1 nor 2", (int)power);
-    if (int rc = nonneg_finite(ctx, "fwi_misfit_envelope", "eps", eps)) return rc;
-    if (power == 1 && eps == 0.0)
-        return ctx->fail(FWI_EINVAL, "fwi_misfit_envelope: power 1 needs eps > 0 (the envelope is not differentiable at 0)");
-    if (int rc = misfit_synthetics(ctx, "fwi_misfit_envelope", "or fwi_born ")) return rc;
-    return DISPATCH_CALL(ctx, misfit_envelope, typed(d_obs), typed(weights), taps, R, hilbert, Q, power, eps, J_out);
-}
-
-int fwi_misfit_correlation(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
-                           const double *trace_weights, double eps, double *J_out, double *rho_out) {
-    if (int rc = misfit_callable(ctx, "fwi_misfit_correlation", d_obs, J_out)) return rc;
-    if (int rc = data_args(ctx, "fwi_misfit_correlation", taps, R)) return rc;
-    if (int rc = nonneg_finite(ctx, "fwi_misfit_correlation", "eps", eps)) return rc;
-    if (int rc = trace_weight_args(ctx, "fwi_misfit_correlation", trace_weights)) return rc;
-    if (int rc = misfit_synthetics(ctx, "fwi_misfit_correlation", "or fwi_born ")) return rc;
-    return DISPATCH_CALL(ctx, misfit_correlation, typed(d_obs), typed(weights), taps, R, trace_weights, eps, J_out, rho_out);
-}
-
-int fwi_misfit_traveltime(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
-                          const double *trace_weights, int32_t max_lag, double *J_out, double *tau_out, int32_t *lag_out) {
-    if (int rc = misfit_callable(ctx, "fwi_misfit_traveltime", d_obs, J_out)) return rc;
-    if (int rc = data_args(ctx, "fwi_misfit_traveltime", taps, R)) return rc;
-    if (max_lag < 1 || max_lag > FWI_TT_KMAX)
-        return ctx->fail(FWI_EINVAL, "fwi_misfit_traveltime: max_lag=%d outside [1, %d]", (int)max_lag, FWI_TT_KMAX);
-    if (int rc = trace_weight_args(ctx, "fwi_misfit_traveltime", trace_weights)) return rc;
-    if (int rc = misfit_synthetics(ctx, "fwi_misfit_traveltime", "or fwi_born ")) return rc;
-    return DISPATCH_CALL(ctx, misfit_traveltime, typed(d_obs), typed(weights), taps, R, trace_weights, max_lag, J_out,
-                         tau_out, lag_out);
-}
-
-int fwi_misfit_transport(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
-                         const double *trace_weights, int32_t transform, double param, double *J_out, double *w2_out,
-                         int32_t *counts_out) {
-    if (int rc = misfit_callable(ctx, "fwi_misfit_transport", d_obs, J_out)) return rc;
-    if (int rc = data_args(ctx, "fwi_misfit_transport", taps, R)) return rc;
-    if (transform != FWI_OT_LINEAR && transform != FWI_OT_SOFTPLUS)
-        return ctx->fail(FWI_EINVAL, "fwi_misfit_transport: transform=%d is neither FWI_OT_LINEAR nor FWI_OT_SOFTPLUS",
-                         (int)transform);
-    if (int rc = nonneg_finite(ctx, "fwi_misfit_transport", "param", param, true)) return rc;
-    if (int rc = trace_weight_args(ctx, "fwi_misfit_transport", trace_weights)) return rc;
-    if (int rc = misfit_synthetics(ctx, "fwi_misfit_transport", "or fwi_born ")) return rc;
-    return DISPATCH_CALL(ctx, misfit_transport, typed(d_obs), typed(weights), taps, R, trace_weights, transform, param,
-                         J_out, w2_out, counts_out);
-}
-
-int fwi_misfit_spectral(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
-                        int32_t nfreq, const double *freqs_hz, int32_t kind, double eps, const double *freq_weights,
-                        const double *trace_weights, double *J_out, double *phase_out, double *logamp_out,
-                        uint8_t *counts_out) {
-    const char *who = "fwi_misfit_spectral";
-    if (int rc = misfit_callable(ctx, who, d_obs, J_out)) return rc;
-    if (int rc = data_args(ctx, who, taps, R)) return rc;
-    if (nfreq < 1 || nfreq > FWI_FOURIER_FMAX)
-        return ctx->fail(FWI_EINVAL, "%s: nfreq=%d outside [1, %d]", who, (int)nfreq, FWI_FOURIER_FMAX);
-    if (!freqs_hz) return ctx->fail(FWI_EINVAL, "%s: null frequencies", who);
-    if (kind != FWI_SPEC_L2 && kind != FWI_SPEC_PHASE && kind != FWI_SPEC_LOGAMP && kind != FWI_SPEC_LOG)
-        return ctx->fail(FWI_EINVAL, "%s: kind=%d is none of FWI_SPEC_L2, FWI_SPEC_PHASE, FWI_SPEC_LOGAMP, FWI_SPEC_LOG", who,
-                         (int)kind);
-    const bool phase = kind == FWI_SPEC_PHASE || kind == FWI_SPEC_LOG;
-    const double nyq = 1.0 / (2.0 * ctx->cfg.dt);
-    for (int k = 0; k < nfreq; ++k) {
-        const double f = freqs_hz[k];
-        if (!std::isfinite(f)) return ctx->fail(FWI_EINVAL, "%s: frequency %d is not finite", who, k);
-        if (f < 0.0) return ctx->fail(FWI_EINVAL, "%s: frequency %d is negative (%g Hz)", who, k, f);
-        if (f > nyq * (1.0 + FOURIER_NYQUIST_RTOL))
-            return ctx->fail(FWI_EINVAL, "%s: frequency %d (%g Hz) is above the Nyquist frequency %g Hz (dt %g s)", who, k, f,
-                             nyq, ctx->cfg.dt);
-        if (phase && (f == 0.0 || std::fabs(2.0 * f * ctx->cfg.dt - 1.0) <= FOURIER_NYQUIST_RTOL))
-            return ctx->fail(FWI_EINVAL, "%s: frequency %d (%g Hz) is 0 or the Nyquist frequency, where the spectrum is real "
-                                         "and has no phase to compare (kinds PHASE and LOG)", who, k, f);
-        for (int m = 0; m < k; ++m)
-            if (freqs_hz[m] == f) return ctx->fail(FWI_EINVAL, "%s: frequencies %d and %d are equal (%g Hz)", who, m, k, f);
-    }
-    if (int rc = nonneg_finite(ctx, who, "eps", eps)) return rc;
-    if (freq_weights)
-        for (int k = 0; k < nfreq; ++k)
-            if (!(freq_weights[k] >= 0.0) || !std::isfinite(freq_weights[k]))
-                return ctx->fail(FWI_EINVAL, "%s: freq_weights[%d]=%g must be finite and >= 0", who, k, freq_weights[k]);
-    if (int rc = trace_weight_args(ctx, who, trace_weights)) return rc;
-    if (int rc = misfit_synthetics(ctx, who, "or fwi_born ")) return rc;
-    return DISPATCH_CALL(ctx, misfit_spectral, typed(d_obs), typed(weights), taps, R, nfreq, freqs_hz, kind, eps,
-                         freq_weights, trace_weights, J_out, phase_out, logamp_out, counts_out);
-}
-
-int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {
-    return match_solve(G, b, K, mu, f_out) ? FWI_EINVAL : FWI_OK;
-}
-
-int fwi_residual_weight(fwi_ctx *ctx, const void *weights, const double *taps, int32_t R) {
-    if (!ctx) return FWI_EINVAL;
-    if (int rc = data_args(ctx, "fwi_residual_weight", taps, R)) return rc;
-    if (!ctx->have_dev_residual)
-        return ctx->fail(FWI_ESTATE, "fwi_residual_weight: no residual on the device (fwi_born, fwi_misfit_l2 or "
-                                     "fwi_misfit_weighted leave one; fwi_adjoint uses it up)");
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH_CALL(ctx, residual_weight, typed(weights), taps, R);
-}
-
-int fwi_gradient(fwi_ctx *ctx, int32_t wrt, void *g_out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!g_out) return ctx->fail(FWI_EINVAL, "fwi_gradient: null output");
-    if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
-        return ctx->fail(FWI_EINVAL, "fwi_gradient: unknown parametrisation %d", wrt);
-    if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_gradient: no model set");
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::gradient(ctx, wrt, (float *)g_out),
-                    Impl<double>::gradient(ctx, wrt, (double *)g_out));
-}
-
-int fwi_gradient_reset(fwi_ctx *ctx) {
-    if (!ctx) return FWI_EINVAL;
-    (void)hipSetDevice(ctx->cfg.device);
-    HIPCHK(ctx, hipMemsetAsync(ctx->g_acc, 0, (size_t)ctx->gd.npts * ctx->esize, ctx->stream));
-    if (ctx->h_acc) HIPCHK(ctx, hipMemsetAsync(ctx->h_acc, 0, (size_t)ctx->gd.npts * ctx->esize, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FWI_OK;
-}
-
-int fwi_gradient_add(fwi_ctx *dst, fwi_ctx *src) {
-    if (!dst || !src) return FWI_EINVAL;
-    if (dst == src) return dst->fail(FWI_EINVAL, "fwi_gradient_add: dst and src are the same context");
-    if (dst->cfg.device != src->cfg.device || dst->cfg.dtype != src->cfg.dtype || dst->gd.npts != src->gd.npts ||
-        dst->gd.nx != src->gd.nx || dst->gd.nz != src->gd.nz)
-        return dst->fail(FWI_EINVAL, "fwi_gradient_add: contexts differ in device, dtype or shape");
-    if (!dst->h_acc != !src->h_acc)
-        return dst->fail(FWI_EINVAL, "fwi_gradient_add: illumination is enabled in one context only");
-    (void)hipSetDevice(dst->cfg.device);
-    HIPCHK(dst, hipStreamSynchronize(src->stream));  // src's adjoint sweeps are complete
-    int rc = DISPATCH(dst, Impl<float>::vec_axpby(dst, dst->g_acc, 1.0, src->g_acc, 1.0),
-                      Impl<double>::vec_axpby(dst, dst->g_acc, 1.0, src->g_acc, 1.0));
-    if (rc) return rc;
-    if (dst->h_acc && (rc = DISPATCH(dst, Impl<float>::vec_axpby(dst, dst->h_acc, 1.0, src->h_acc, 1.0),
-                                     Impl<double>::vec_axpby(dst, dst->h_acc, 1.0, src->h_acc, 1.0))))
-        return rc;
-    HIPCHK(dst, hipStreamSynchronize(dst->stream));
-    return FWI_OK;
-}
-
-int fwi_dot(fwi_ctx *ctx, const void *a, const void *b, int64_t n, double *out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!a || !b || !out || n < 0) return ctx->fail(FWI_EINVAL, "fwi_dot: bad argument");
-    if (n == 0) {
-        *out = 0.0;
-        return FWI_OK;
-    }
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::dot(ctx, (const float *)a, (const float *)b, n, out),
-                    Impl<double>::dot(ctx, (const double *)a, (const double *)b, n, out));
-}
-
-static void *vec_slot(fwi_ctx *ctx, int32_t slot) {
-    return (slot >= 0 && slot < (int32_t)ctx->vecs.size()) ? ctx->vecs[slot] : nullptr;
-}
-
-#define VEC_OR_FAIL(ctx, name, slot)                                                            \
-    void *name = vec_slot(ctx, slot);                                                           \
-    if (!name) return (ctx)->fail(FWI_EINVAL, "%s: vector slot %d does not exist", __func__, (int)(slot))
-
-int fwi_vec_create(fwi_ctx *ctx, int32_t count) {
-    if (!ctx) return FWI_EINVAL;
-    if (count < 0 || count > 256) return ctx->fail(FWI_EINVAL, "fwi_vec_create: count must be in [0, 256]");
-    (void)hipSetDevice(ctx->cfg.device);
-    for (void *v : ctx->vecs)
-        if (v) (void)hipFree(v);
-    ctx->vecs.assign(count, nullptr);
-    const size_t bytes = (size_t)ctx->gd.npts * ctx->esize;
-    for (int i = 0; i < count; ++i) {
-        HIPCHK(ctx, hipMalloc(&ctx->vecs[i], bytes));
-        HIPCHK(ctx, hipMemsetAsync(ctx->vecs[i], 0, bytes, ctx->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FWI_OK;
-}
-
-int fwi_vec_upload(fwi_ctx *ctx, int32_t slot, const void *host) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    if (!host) return ctx->fail(FWI_EINVAL, "fwi_vec_upload: null buffer");
-    (void)hipSetDevice(ctx->cfg.device);
-    int rc = DISPATCH(ctx, Impl<float>::upload_compact(ctx, v, host), Impl<double>::upload_compact(ctx, v, host));
-    if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FWI_OK;
-}
-
-int fwi_vec_download(fwi_ctx *ctx, int32_t slot, void *host) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    if (!host) return ctx->fail(FWI_EINVAL, "fwi_vec_download: null buffer");
-    (void)hipSetDevice(ctx->cfg.device);
-    int rc = DISPATCH(ctx, Impl<float>::download_compact(ctx, host, v), Impl<double>::download_compact(ctx, host, v));
-    if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FWI_OK;
-}
-
-int fwi_vec_copy(fwi_ctx *ctx, int32_t dst, int32_t src) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, d, dst);
-    VEC_OR_FAIL(ctx, s, src);
-    (void)hipSetDevice(ctx->cfg.device);
-    if (d != s)
-        HIPCHK(ctx, hipMemcpyAsync(d, s, (size_t)ctx->gd.npts * ctx->esize, hipMemcpyDeviceToDevice, ctx->stream));
-    return FWI_OK;
-}
-
-int fwi_vec_axpby(fwi_ctx *ctx, int32_t y, double a, int32_t x, double b) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, vy, y);
-    VEC_OR_FAIL(ctx, vx, x);
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::vec_axpby(ctx, vy, a, vx, b), Impl<double>::vec_axpby(ctx, vy, a, vx, b));
-}
-
-int fwi_vec_dot(fwi_ctx *ctx, int32_t x, int32_t y, double *out) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, vx, x);
-    VEC_OR_FAIL(ctx, vy, y);
-    if (!out) return ctx->fail(FWI_EINVAL, "fwi_vec_dot: null output");
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::vec_dot(ctx, vx, vy, out), Impl<double>::vec_dot(ctx, vx, vy, out));
-}
-
-int fwi_vec_absmax(fwi_ctx *ctx, int32_t x, double *out) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, vx, x);
-    if (!out) return ctx->fail(FWI_EINVAL, "fwi_vec_absmax: null output");
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::vec_absmax(ctx, vx, out), Impl<double>::vec_absmax(ctx, vx, out));
-}
-
-int fwi_vec_clip(fwi_ctx *ctx, int32_t x, double lo, double hi) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, vx, x);
-    if (!(lo <= hi)) return ctx->fail(FWI_EINVAL, "fwi_vec_clip: lo > hi");
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::vec_clip(ctx, vx, lo, hi), Impl<double>::vec_clip(ctx, vx, lo, hi));
-}
-
 int fwi_set_model_vec(fwi_ctx *ctx, int32_t slot) {
     if (!ctx) return FWI_EINVAL;
     VEC_OR_FAIL(ctx, v, slot);
     (void)hipSetDevice(ctx->cfg.device);
     return DISPATCH(ctx, Impl<float>::set_model_vec(ctx, v), Impl<double>::set_model_vec(ctx, v));
-}
-
-int fwi_gradient_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
-        return ctx->fail(FWI_EINVAL, "fwi_gradient_vec: unknown parametrisation %d", wrt);
-    if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_gradient_vec: no model set");
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::gradient_vec(ctx, wrt, v), Impl<double>::gradient_vec(ctx, wrt, v));
 }
 
 // FWI_BORN_AUTO on a context that has both paths: decided by measurement (tools/born_probe.py; on the
@@ -3593,9 +2301,6 @@ int fwi_born_imaging_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, int32_t mode, 
 
 const char *fwi_born_path(const fwi_ctx *ctx) { return ctx ? ctx->born_path : ""; }
 
-static int fourier_callable(fwi_ctx *ctx, const char *who, bool need_m);
-static int fourier_weight_args(fwi_ctx *ctx, const char *who, const double *fw, bool nonneg);
-
 // the argument and state checks the Born calls on the Fourier store share; *fused as born_callable sets it
 static int fourier_born_callable(fwi_ctx *ctx, const char *who, int32_t mode, const double *fw, bool *fused) {
     if (mode != FWI_BORN_AUTO && mode != FWI_BORN_SCATTER && mode != FWI_BORN_FUSED)
@@ -3634,26 +2339,6 @@ int fwi_fourier_born_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot, const double *
     if (!ctx) return FWI_EINVAL;
     VEC_OR_FAIL(ctx, v, slot);
     return fourier_born(ctx, "fwi_fourier_born_vec", wrt, nullptr, v, freq_weights, mode, seis_out);
-}
-
-// The axis of the GridDesc (0 = z, 1 = y, 2 = x) of the caller's `axis` in grid order z, [y,] x, in *ax; refused outside it.
-static int fourier_axis(fwi_ctx *ctx, const char *who, int32_t axis, int *ax) {
-    if (axis < 0 || axis >= ctx->gd.ndim)
-        return ctx->fail(FWI_EINVAL, "%s: axis=%d outside [0, %d)", who, (int)axis, ctx->gd.ndim);
-    *ax = axis == ctx->gd.ndim - 1 ? 2 : ctx->gd.ndim == 3 ? axis : 0;
-    return FWI_OK;
-}
-
-// A time lag `tau` (l < 0), or taus[l]: that it is finite, or with `phase` that it leaves a finite phase at every
-// frequency of the store.  Two calls, because the entry points check other arguments in between.
-static int fourier_tau_ok(fwi_ctx *ctx, const char *who, double tau, int l, bool phase) {
-    char name[32] = "tau";
-    if (l >= 0) snprintf(name, sizeof name, "taus[%d]", l);
-    if (!phase) return std::isfinite(tau) ? FWI_OK : ctx->fail(FWI_EINVAL, "%s: %s is not finite", who, name);
-    for (double f : ctx->four_freqs)
-        if (!std::isfinite(f * tau))
-            return ctx->fail(FWI_EINVAL, "%s: %s=%g s leaves no finite phase at %g Hz", who, name, tau, f);
-    return FWI_OK;
 }
 
 // `images_host`: fwi_fourier_born_extended, else the vector slots `slots` of fwi_fourier_born_extended_vec
@@ -3712,69 +2397,6 @@ int fwi_fourier_born_extended_vec(fwi_ctx *ctx, int32_t kind, int32_t axis, int3
                                  freq_weights, mode, seis_out);
 }
 
-int fwi_comm_unique_id(void *id_out) {
-    static_assert(sizeof(ncclUniqueId) == FWI_UNIQUE_ID_BYTES, "ncclUniqueId size");
-    if (!id_out) return FWI_EINVAL;
-    ncclUniqueId id;
-    if (ncclGetUniqueId(&id) != ncclSuccess) return FWI_ECOMM;
-    memcpy(id_out, &id, sizeof id);
-    return FWI_OK;
-}
-
-int fwi_comm_init(fwi_ctx *ctx, int32_t rank, int32_t nranks, const void *id) {
-    if (!ctx) return FWI_EINVAL;
-    if (!id || nranks < 1 || rank < 0 || rank >= nranks)
-        return ctx->fail(FWI_EINVAL, "fwi_comm_init: bad rank %d of %d", rank, nranks);
-    (void)hipSetDevice(ctx->cfg.device);
-    if (ctx->comm) {
-        (void)ncclCommDestroy(ctx->comm);
-        ctx->comm = nullptr;
-    }
-    ncclUniqueId uid;
-    memcpy(&uid, id, sizeof uid);
-    ncclResult_t r = ncclCommInitRank(&ctx->comm, nranks, uid, rank);
-    if (r != ncclSuccess) {
-        ctx->comm = nullptr;
-        ctx->nranks = 1;
-        return ctx->fail(FWI_ECOMM, "ncclCommInitRank(rank %d of %d): %s", rank, nranks, ncclGetErrorString(r));
-    }
-    ctx->nranks = nranks;
-    return FWI_OK;
-}
-
-int fwi_comm_info(fwi_ctx *ctx, int32_t *nranks_out, int32_t *rank_out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->comm) return ctx->fail(FWI_ESTATE, "fwi_comm_info: call fwi_comm_init first");
-    int n = 0, r = -1;
-    NCCLCHK(ctx, ncclCommCount(ctx->comm, &n));
-    NCCLCHK(ctx, ncclCommUserRank(ctx->comm, &r));
-    if (nranks_out) *nranks_out = n;
-    if (rank_out) *rank_out = r;
-    return FWI_OK;
-}
-
-int fwi_comm_abort(fwi_ctx *ctx) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->comm) return FWI_OK;
-    (void)hipSetDevice(ctx->cfg.device);
-    ncclComm_t c = ctx->comm;
-    ctx->comm = nullptr;
-    ctx->nranks = 1;
-    NCCLCHK(ctx, ncclCommAbort(c));
-    return FWI_OK;
-}
-
-int fwi_allreduce_gradient(fwi_ctx *ctx) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->comm) return ctx->fail(FWI_ESTATE, "fwi_allreduce_gradient: call fwi_comm_init first");
-    (void)hipSetDevice(ctx->cfg.device);
-    NCCLCHK(ctx, ncclAllReduce(ctx->g_acc, ctx->g_acc, (size_t)ctx->gd.npts,
-                               ctx->cfg.dtype == FWI_F32 ? ncclFloat32 : ncclFloat64, ncclSum, ctx->comm,
-                               ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FWI_OK;
-}
-
 int fwi_set_illumination(fwi_ctx *ctx, int32_t on) {
     if (!ctx) return FWI_EINVAL;
     if (on && !ctx->four_freqs.empty())
@@ -3813,9 +2435,12 @@ static int fourier_release(fwi_ctx *ctx) {
     ctx->four_batch = ctx->four_rows = 0;
     ctx->four_sweep = false;
     ctx->have_m = false;
-    if (ctx->four_acc || ctx->four_ring || ctx->four_tw || ctx->four_adj || ctx->four_w)
+#define ADDRESS_OF(name) &ctx->name,
+    void **const arrays[] = {FWI_FOURIER_PTRS(ADDRESS_OF)};
+#undef ADDRESS_OF
+    if (std::any_of(std::begin(arrays), std::end(arrays), [](void **p) { return *p != nullptr; }))
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // no sweep still uses them
-    for (void **p : {&ctx->four_acc, &ctx->four_ring, &ctx->four_tw, &ctx->four_adj, &ctx->four_w}) {
+    for (void **p : arrays) {
         void *q = *p;
         *p = nullptr;
         if (q) HIPCHK(ctx, hipFree(q));
@@ -3868,57 +2493,6 @@ int fwi_set_fourier_store(fwi_ctx *ctx, int32_t nfreq, const double *freqs_hz, i
     return FWI_OK;
 }
 
-int fwi_fourier_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out) {
-    if (!ctx) return FWI_EINVAL;
-    if (ctx->four_freqs.empty())
-        return ctx->fail(FWI_ESTATE, "fwi_fourier_spectrum: the Fourier store is off (fwi_set_fourier_store)");
-    if (k < 0 || k >= (int)ctx->four_freqs.size())
-        return ctx->fail(FWI_EINVAL, "fwi_fourier_spectrum: frequency index %d outside [0, %d)", (int)k,
-                         (int)ctx->four_freqs.size());
-    if (!re_out || !im_out) return ctx->fail(FWI_EINVAL, "fwi_fourier_spectrum: null output");
-    if (!ctx->have_q || !ctx->four_acc)
-        return ctx->fail(FWI_ESTATE, "fwi_fourier_spectrum: needs fwi_forward(save=1) on this context first");
-    (void)hipSetDevice(ctx->cfg.device);
-    const char *re = (const char *)ctx->four_acc + (size_t)2 * k * ctx->gd.npts * ctx->esize;
-    const char *im = re + (size_t)ctx->gd.npts * ctx->esize;
-    for (int c = 0; c < 2; ++c) {  // (one staging array: the first copy leaves it before the second repack)
-        if (int rc = DISPATCH(ctx, Impl<float>::download_compact(ctx, c ? im_out : re_out, c ? im : re),
-                              Impl<double>::download_compact(ctx, c ? im_out : re_out, c ? im : re)))
-            return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return FWI_OK;
-}
-
-// What the entry points of spectral imaging begin with: a Fourier context that holds the Q_k of a forward(save) and, with
-// `need_m`, the M_k of an fwi_adjoint_spectral that followed it.
-static int fourier_callable(fwi_ctx *ctx, const char *who, bool need_m) {
-    if (ctx->four_freqs.empty())
-        return ctx->fail(FWI_ESTATE, "%s: the Fourier store is off (fwi_set_fourier_store)", who);
-    if (!ctx->have_forward || !ctx->have_q || !ctx->four_acc)
-        return ctx->fail(FWI_ESTATE, "%s: needs fwi_forward(save=1) on this context first", who);
-    if (need_m && (!ctx->have_m || !ctx->four_adj))
-        return ctx->fail(FWI_ESTATE, "%s: needs an fwi_adjoint_spectral after the latest fwi_forward(save=1)", who);
-    return FWI_OK;
-}
-
-// the F weights of the caller (nullptr: ones): finite, and with `nonneg` >= 0
-static int fourier_weight_args(fwi_ctx *ctx, const char *who, const double *fw, bool nonneg) {
-    if (!fw) return FWI_OK;
-    for (int k = 0; k < (int)ctx->four_freqs.size(); ++k) {
-        if (!std::isfinite(fw[k])) return ctx->fail(FWI_EINVAL, "%s: freq_weights[%d] is not finite", who, k);
-        if (nonneg && fw[k] < 0.0) return ctx->fail(FWI_EINVAL, "%s: freq_weights[%d]=%g is negative", who, k, fw[k]);
-    }
-    return FWI_OK;
-}
-
-static int wrt_and_model(fwi_ctx *ctx, const char *who, int32_t wrt) {
-    if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
-        return ctx->fail(FWI_EINVAL, "%s: unknown parametrisation %d", who, (int)wrt);
-    if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "%s: no model set", who);
-    return FWI_OK;
-}
-
 int fwi_adjoint_spectral(fwi_ctx *ctx, const void *residual, void *adj_src_out) {
     if (!ctx) return FWI_EINVAL;
     if (int rc = fourier_callable(ctx, "fwi_adjoint_spectral", false)) return rc;
@@ -3929,334 +2503,11 @@ int fwi_adjoint_spectral(fwi_ctx *ctx, const void *residual, void *adj_src_out) 
                     Impl<double>::adjoint(ctx, (const double *)residual, 0, (double *)adj_src_out, true));
 }
 
-int fwi_fourier_image(fwi_ctx *ctx, const double *freq_weights) {
-    if (!ctx) return FWI_EINVAL;
-    if (int rc = fourier_callable(ctx, "fwi_fourier_image", true)) return rc;
-    if (int rc = fourier_weight_args(ctx, "fwi_fourier_image", freq_weights, false)) return rc;
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH_CALL(ctx, fourier_image, freq_weights);
-}
-
-// `illum`: fwi_fourier_illumination[_vec], else fwi_fourier_gradient[_vec]; `out`: the host array, nullptr for `dev`
-static int fourier_finalize(fwi_ctx *ctx, const char *who, bool illum, int32_t wrt, const double *fw, void *dev,
-                            void *out) {
-    if (int rc = fourier_callable(ctx, who, !illum)) return rc;
-    if (int rc = fourier_weight_args(ctx, who, fw, illum)) return rc;
-    if (int rc = wrt_and_model(ctx, who, wrt)) return rc;
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::fourier_finalize(ctx, wrt, fw, illum, dev, (float *)out),
-                    Impl<double>::fourier_finalize(ctx, wrt, fw, illum, dev, (double *)out));
-}
-
-int fwi_fourier_gradient(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, void *out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_gradient: null output");
-    return fourier_finalize(ctx, "fwi_fourier_gradient", false, wrt, freq_weights, ctx->g_out, out);
-}
-
-int fwi_fourier_gradient_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, int32_t slot) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    return fourier_finalize(ctx, "fwi_fourier_gradient_vec", false, wrt, freq_weights, v, nullptr);
-}
-
-int fwi_fourier_illumination(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, void *out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_illumination: null output");
-    return fourier_finalize(ctx, "fwi_fourier_illumination", true, wrt, freq_weights, ctx->g_out, out);
-}
-
-int fwi_fourier_illumination_vec(fwi_ctx *ctx, int32_t wrt, const double *freq_weights, int32_t slot) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    return fourier_finalize(ctx, "fwi_fourier_illumination_vec", true, wrt, freq_weights, v, nullptr);
-}
-
-// `tau`: fwi_fourier_lag_image[_vec], else fwi_fourier_offset_image[_vec] of `h` cells along `axis` of the grid order;
-// `out`: the host array, nullptr for `dev`
-static int fourier_extended(fwi_ctx *ctx, const char *who, int32_t axis, int32_t h, const double *tau, const double *fw,
-                            void *dev, void *out) {
-    if (int rc = fourier_callable(ctx, who, true)) return rc;
-    int ax = 0;
-    if (int rc = tau ? fourier_tau_ok(ctx, who, *tau, -1, false) : fourier_axis(ctx, who, axis, &ax)) return rc;
-    if (int rc = fourier_weight_args(ctx, who, fw, false)) return rc;
-    if (tau)
-        if (int rc = fourier_tau_ok(ctx, who, *tau, -1, true)) return rc;
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::fourier_extended(ctx, ax, h, tau, fw, dev, (float *)out),
-                    Impl<double>::fourier_extended(ctx, ax, h, tau, fw, dev, (double *)out));
-}
-
-int fwi_fourier_offset_image(fwi_ctx *ctx, int32_t axis, int32_t h, const double *freq_weights, void *out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_offset_image: null output");
-    return fourier_extended(ctx, "fwi_fourier_offset_image", axis, h, nullptr, freq_weights, ctx->g_out, out);
-}
-
-int fwi_fourier_offset_image_vec(fwi_ctx *ctx, int32_t axis, int32_t h, const double *freq_weights, int32_t slot) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    return fourier_extended(ctx, "fwi_fourier_offset_image_vec", axis, h, nullptr, freq_weights, v, nullptr);
-}
-
-int fwi_fourier_lag_image(fwi_ctx *ctx, double tau, const double *freq_weights, void *out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_lag_image: null output");
-    return fourier_extended(ctx, "fwi_fourier_lag_image", 0, 0, &tau, freq_weights, ctx->g_out, out);
-}
-
-int fwi_fourier_lag_image_vec(fwi_ctx *ctx, double tau, const double *freq_weights, int32_t slot) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    return fourier_extended(ctx, "fwi_fourier_lag_image_vec", 0, 0, &tau, freq_weights, v, nullptr);
-}
-
-// fwi_fourier_split_image[_vec]; `out`: the host array, nullptr for `dev`
-static int fourier_split(fwi_ctx *ctx, const char *who, int32_t wrt, int32_t part, int32_t axis, int32_t ntaps,
-                         const double *taps, const double *fw, void *dev, void *out) {
-    if (int rc = fourier_callable(ctx, who, true)) return rc;
-    if (part != FWI_SPLIT_SAME && part != FWI_SPLIT_OPPOSITE && part != FWI_SPLIT_HILBERT)
-        return ctx->fail(FWI_EINVAL, "%s: unknown part %d", who, (int)part);
-    int ax = 0;
-    if (int rc = fourier_axis(ctx, who, axis, &ax)) return rc;
-    if (ntaps < 1 || ntaps > FWI_SPLIT_RMAX)
-        return ctx->fail(FWI_EINVAL, "%s: ntaps=%d outside [1, %d]", who, (int)ntaps, FWI_SPLIT_RMAX);
-    if (!taps) return ctx->fail(FWI_EINVAL, "%s: null taps", who);
-    for (int r = 0; r < ntaps; ++r)
-        if (!std::isfinite(taps[r])) return ctx->fail(FWI_EINVAL, "%s: taps[%d] is not finite", who, r);
-    if (int rc = fourier_weight_args(ctx, who, fw, false)) return rc;
-    if (int rc = wrt_and_model(ctx, who, wrt)) return rc;
-    (void)hipSetDevice(ctx->cfg.device);
-    const int n = ax == 0 ? ctx->gd.nz : ax == 1 ? ctx->gd.ny : ctx->gd.nx;
-    int R = std::min<int>(ntaps, n - 1);  // a tap at r >= n touches no cell, a trailing zero tap is skipped
-    while (R > 0 && taps[R - 1] == 0.0) --R;
-    const double alpha = part == FWI_SPLIT_HILBERT ? 0.0 : 0.5;
-    const double beta = part == FWI_SPLIT_HILBERT ? 1.0 : part == FWI_SPLIT_SAME ? 0.5 : -0.5;
-    return DISPATCH(ctx, Impl<float>::fourier_split(ctx, wrt, ax, taps, R, alpha, beta, fw, dev, (float *)out),
-                    Impl<double>::fourier_split(ctx, wrt, ax, taps, R, alpha, beta, fw, dev, (double *)out));
-}
-
-int fwi_fourier_split_image(fwi_ctx *ctx, int32_t wrt, int32_t part, int32_t axis, int32_t ntaps, const double *taps,
-                            const double *freq_weights, void *out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!out) return ctx->fail(FWI_EINVAL, "fwi_fourier_split_image: null output");
-    return fourier_split(ctx, "fwi_fourier_split_image", wrt, part, axis, ntaps, taps, freq_weights, ctx->g_out, out);
-}
-
-int fwi_fourier_split_image_vec(fwi_ctx *ctx, int32_t wrt, int32_t part, int32_t axis, int32_t ntaps, const double *taps,
-                                const double *freq_weights, int32_t slot) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    return fourier_split(ctx, "fwi_fourier_split_image_vec", wrt, part, axis, ntaps, taps, freq_weights, v, nullptr);
-}
-
-int fwi_fourier_adjoint_spectrum(fwi_ctx *ctx, int32_t k, void *re_out, void *im_out) {
-    if (!ctx) return FWI_EINVAL;
-    if (int rc = fourier_callable(ctx, "fwi_fourier_adjoint_spectrum", true)) return rc;
-    if (k < 0 || k >= (int)ctx->four_freqs.size())
-        return ctx->fail(FWI_EINVAL, "fwi_fourier_adjoint_spectrum: frequency index %d outside [0, %d)", (int)k,
-                         (int)ctx->four_freqs.size());
-    if (!re_out || !im_out) return ctx->fail(FWI_EINVAL, "fwi_fourier_adjoint_spectrum: null output");
-    (void)hipSetDevice(ctx->cfg.device);
-    const char *re = (const char *)ctx->four_adj + (size_t)2 * k * ctx->gd.npts * ctx->esize;
-    const char *im = re + (size_t)ctx->gd.npts * ctx->esize;
-    for (int c = 0; c < 2; ++c) {  // (one staging array: the first copy leaves it before the second repack)
-        if (int rc = DISPATCH(ctx, Impl<float>::download_compact(ctx, c ? im_out : re_out, c ? im : re),
-                              Impl<double>::download_compact(ctx, c ? im_out : re_out, c ? im : re)))
-            return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return FWI_OK;
-}
-
 int fwi_store_bytes(fwi_ctx *ctx, int64_t *bytes_out) {
     if (!ctx) return FWI_EINVAL;
     if (!bytes_out) return ctx->fail(FWI_EINVAL, "fwi_store_bytes: null output");
     *bytes_out = (int64_t)ctx->store_held;
     return FWI_OK;
-}
-
-#define ILLUM_READABLE(ctx, who, wrt)                                                                              \
-    do {                                                                                                           \
-        if ((wrt) != FWI_WRT_VELOCITY && (wrt) != FWI_WRT_SLOWNESS2)                                               \
-            return (ctx)->fail(FWI_EINVAL, "%s: unknown parametrisation %d", who, (int)(wrt));                     \
-        if (!(ctx)->h_acc) return (ctx)->fail(FWI_ESTATE, "%s: illumination is disabled (fwi_set_illumination)", who); \
-        if (!(ctx)->have_model) return (ctx)->fail(FWI_ESTATE, "%s: no model set", who);                          \
-    } while (0)
-
-int fwi_illumination(fwi_ctx *ctx, int32_t wrt, void *out) {
-    if (!ctx) return FWI_EINVAL;
-    if (!out) return ctx->fail(FWI_EINVAL, "fwi_illumination: null output");
-    ILLUM_READABLE(ctx, "fwi_illumination", wrt);
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::illumination(ctx, wrt, (float *)out),
-                    Impl<double>::illumination(ctx, wrt, (double *)out));
-}
-
-int fwi_illumination_vec(fwi_ctx *ctx, int32_t wrt, int32_t slot) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, v, slot);
-    ILLUM_READABLE(ctx, "fwi_illumination_vec", wrt);
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, Impl<float>::illumination_vec(ctx, wrt, v), Impl<double>::illumination_vec(ctx, wrt, v));
-}
-
-int fwi_allreduce_illumination(fwi_ctx *ctx) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->comm) return ctx->fail(FWI_ESTATE, "fwi_allreduce_illumination: call fwi_comm_init first");
-    if (!ctx->h_acc) return ctx->fail(FWI_ESTATE, "fwi_allreduce_illumination: illumination is disabled");
-    (void)hipSetDevice(ctx->cfg.device);
-    NCCLCHK(ctx, ncclAllReduce(ctx->h_acc, ctx->h_acc, (size_t)ctx->gd.npts,
-                               ctx->cfg.dtype == FWI_F32 ? ncclFloat32 : ncclFloat64, ncclSum, ctx->comm,
-                               ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FWI_OK;
-}
-
-int fwi_vec_mul(fwi_ctx *ctx, int32_t y, int32_t x) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, vy, y);
-    VEC_OR_FAIL(ctx, vx, x);
-    (void)hipSetDevice(ctx->cfg.device);
-    HIPCHK(ctx, DISPATCH(ctx, launch_vec_mul<float>(ctx->gd, (float *)vy, (const float *)vx, ctx->stream),
-                         launch_vec_mul<double>(ctx->gd, (double *)vy, (const double *)vx, ctx->stream)));
-    return FWI_OK;
-}
-
-int fwi_vec_recip(fwi_ctx *ctx, int32_t y, double a, double b) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, vy, y);
-    (void)hipSetDevice(ctx->cfg.device);
-    HIPCHK(ctx, DISPATCH(ctx, launch_vec_recip<float>(ctx->gd, (float *)vy, a, b, ctx->stream),
-                         launch_vec_recip<double>(ctx->gd, (double *)vy, a, b, ctx->stream)));
-    return FWI_OK;
-}
-
-int fwi_vec_smooth(fwi_ctx *ctx, int32_t y, const double *sigma) {
-    if (!ctx) return FWI_EINVAL;
-    VEC_OR_FAIL(ctx, vy, y);
-    if (!sigma) return ctx->fail(FWI_EINVAL, "fwi_vec_smooth: null sigma");
-    const GridDesc &g = ctx->gd;
-    const int nd = g.ndim;
-    int axis[3], R[3], npass = 0;
-    double w[3][SMOOTH_RMAX + 1];
-    // applied in the order x, y, z; sigma is in grid order (z, [y,] x)
-    for (int d = nd - 1; d >= 0; --d) {
-        const double sg = sigma[d];
-        const int ax = (nd == 2 && d == 1) ? 2 : d;  // internal axis: 0 = z, 1 = y, 2 = x
-        const int n = ax == 0 ? g.nz : ax == 1 ? g.ny : g.nx;
-        if (!std::isfinite(sg) || sg < 0.0)
-            return ctx->fail(FWI_EINVAL, "fwi_vec_smooth: sigma[%d] = %g must be finite and >= 0", d, sg);
-        if (3.0 * sg + 0.5 >= (double)(SMOOTH_RMAX + 1))
-            return ctx->fail(FWI_EINVAL, "fwi_vec_smooth: sigma[%d] = %g gives a radius above %d (apply the operator twice)",
-                             d, sg, SMOOTH_RMAX);
-        const int r = smooth_radius(sg);
-        if (r > n)
-            return ctx->fail(FWI_EINVAL, "fwi_vec_smooth: sigma[%d] = %g gives radius %d, the axis has %d cells "
-                             "(one reflection only)", d, sg, r, n);
-        if (r == 0) continue;  // the identity on this axis: no launch
-        axis[npass] = ax;
-        R[npass] = r;
-        smooth_weights(sg, r, w[npass]);
-        ++npass;
-    }
-    if (npass == 0) return FWI_OK;
-    (void)hipSetDevice(ctx->cfg.device);
-    if (!ctx->smooth_tmp) HIPCHK(ctx, hipMalloc(&ctx->smooth_tmp, (size_t)g.npts * ctx->esize));
-    return DISPATCH(ctx, vec_smooth_passes<float>(ctx, vy, axis, R, w, npass),
-                    vec_smooth_passes<double>(ctx, vy, axis, R, w, npass));
-}
-
-int fwi_vec_shift_sum(fwi_ctx *ctx, int32_t dst, int32_t nsrc, const int32_t *src_slots, const double *shifts,
-                      const double *weights, double beta) {
-    if (!ctx) return FWI_EINVAL;
-    void *vd = vec_slot(ctx, dst);
-    if (!vd) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: dst: vector slot %d does not exist", (int)dst);
-    if (nsrc < 1 || nsrc > FWI_SHIFT_SUM_MAX)
-        return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: nsrc = %d must be in [1, %d]", (int)nsrc, FWI_SHIFT_SUM_MAX);
-    if (!src_slots) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: null src_slots");
-    if (!shifts) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: null shifts");
-    if (!std::isfinite(beta)) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: beta = %g must be finite", beta);
-    static_assert(FWI_SHIFT_SUM_MAX == SLANT_MAX, "include/fwi.h and fwi_slant.h disagree");
-    const GridDesc &g = ctx->gd;
-    SlantTable t = {};
-    int kept = 0;
-    for (int i = 0; i < nsrc; ++i) {
-        const void *vs = vec_slot(ctx, src_slots[i]);
-        const double s = shifts[i], w = weights ? weights[i] : 1.0;
-        if (!vs)
-            return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: src_slots[%d]: vector slot %d does not exist", i,
-                             (int)src_slots[i]);
-        if (vs == vd)
-            return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: src_slots[%d] is dst (slot %d)", i, (int)dst);
-        if (!std::isfinite(s)) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: shifts[%d] = %g must be finite", i, s);
-        if (!std::isfinite(w)) return ctx->fail(FWI_EINVAL, "fwi_vec_shift_sum: weights[%d] = %g must be finite", i, w);
-        if (std::fabs(s) >= (double)g.nz + 1.0) continue;  // wholly outside the grid: tested before n is formed
-        const double n = std::floor(s), f = s - n;
-        t.src[kept] = vs;
-        t.n[kept] = (int64_t)n;
-        t.c0[kept] = w * (1.0 - f);
-        t.c1[kept] = w * f;
-        ++kept;
-    }
-    (void)hipSetDevice(ctx->cfg.device);
-    HIPCHK(ctx, DISPATCH(ctx, launch_slant_sum<float>(g, (float *)vd, t, kept, beta, ctx->stream),
-                         launch_slant_sum<double>(g, (double *)vd, t, kept, beta, ctx->stream)));
-    return FWI_OK;
-}
-
-int fwi_vec_regularizer(fwi_ctx *ctx, int32_t kind, int32_t x, int32_t x0, int32_t v, int32_t out, double alpha,
-                        double beta, const double *weight, double eps, double *value_out) {
-    if (!ctx) return FWI_EINVAL;
-    if (kind != FWI_REG_TIKHONOV && kind != FWI_REG_TV)
-        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: unknown kind %d", (int)kind);
-    void *vx = vec_slot(ctx, x), *vx0 = nullptr, *vv = nullptr, *vout = nullptr;
-    if (!vx) return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: x: vector slot %d does not exist", (int)x);
-    if (x0 != -1 && !(vx0 = vec_slot(ctx, x0)))
-        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: x0: vector slot %d does not exist", (int)x0);
-    if (v != -1 && !(vv = vec_slot(ctx, v)))
-        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: v: vector slot %d does not exist", (int)v);
-    if (out != -1 && !(vout = vec_slot(ctx, out)))
-        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: out: vector slot %d does not exist", (int)out);
-    if (vout && (vout == vx || vout == vx0 || vout == vv))
-        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: out (slot %d) must not alias %s", (int)out,
-                         vout == vx ? "x" : vout == vx0 ? "x0" : "v");
-    if (!vout && !value_out)
-        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: out == -1 and value_out == NULL: nothing to do");
-    if (!weight) return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: null weight");
-    const int nd = ctx->gd.ndim;
-    for (int d = 0; d < nd; ++d)
-        if (!std::isfinite(weight[d]) || weight[d] < 0.0)
-            return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: weight[%d] = %g must be finite and >= 0", d, weight[d]);
-    if (kind == FWI_REG_TV && (!std::isfinite(eps) || eps <= 0.0))
-        return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: eps = %g must be finite and > 0 for total variation", eps);
-    if (!std::isfinite(alpha)) return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: alpha = %g must be finite", alpha);
-    if (!std::isfinite(beta)) return ctx->fail(FWI_EINVAL, "fwi_vec_regularizer: beta = %g must be finite", beta);
-    const double w[3] = {weight[0], nd == 3 ? weight[1] : 0.0, weight[nd - 1]};  // z, y, x
-    if (kind != FWI_REG_TV) eps = 0.0;
-    (void)hipSetDevice(ctx->cfg.device);
-    return DISPATCH(ctx, vec_regularizer<float>(ctx, kind, vx, vx0, vv, vout, alpha, beta, w, eps, value_out),
-                    vec_regularizer<double>(ctx, kind, vx, vx0, vv, vout, alpha, beta, w, eps, value_out));
-}
-
-static int allreduce_scalars(fwi_ctx *ctx, double *vals, int32_t n, ncclRedOp_t op, const char *who) {
-    if (!ctx) return FWI_EINVAL;
-    if (!ctx->comm) return ctx->fail(FWI_ESTATE, "%s: call fwi_comm_init first", who);
-    if (!vals || n < 1 || n > 8) return ctx->fail(FWI_EINVAL, "%s: n must be in [1, 8]", who);
-    (void)hipSetDevice(ctx->cfg.device);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->red, vals, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    NCCLCHK(ctx, ncclAllReduce(ctx->red, ctx->red, (size_t)n, ncclFloat64, op, ctx->comm, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(vals, ctx->red, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return FWI_OK;
-}
-
-int fwi_allreduce_f64(fwi_ctx *ctx, double *vals, int32_t n) {
-    return allreduce_scalars(ctx, vals, n, ncclSum, "fwi_allreduce_f64");
-}
-
-int fwi_allreduce_f64_max(fwi_ctx *ctx, double *vals, int32_t n) {
-    return allreduce_scalars(ctx, vals, n, ncclMax, "fwi_allreduce_f64_max");
 }
 
 int fwi_last_loop_ms(fwi_ctx *ctx, double *ms_out) {

@@ -1,6 +1,6 @@
 // Trace-normalised zero-lag correlation misfit (fwi_misfit_correlation) of (nt, ntr) trace gathers, time the slow axis,
 // the trace index the fast one: the per-trace sums of squares and products, the coefficients of every trace and the
-// adjoint source.  Internal launch interface between fwi_api.hip and fwi_corr.hip.
+// adjoint source.  Internal launch interface between fwi_api_misfit.hip and fwi_corr.hip.
 //
 //   sh = M . s,  dh = M . d                        (s, d: the gathers after the filter B, where there is one)
 //   a_j = sum_n sh[n,j]^2    b_j = sum_n dh[n,j]^2    c_j = sum_n sh[n,j] dh[n,j]

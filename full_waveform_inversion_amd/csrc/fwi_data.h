@@ -1,6 +1,6 @@
 // Band-limited, weighted least-squares data misfit (fwi_misfit_weighted, fwi_residual_weight): a symmetric FIR filter
 // along time applied to (nt, ntr) trace gathers, time the slow axis, the trace index the fast one.  Internal launch
-// interface between fwi_api.hip and fwi_data.hip.
+// interface between fwi_api_misfit.hip and fwi_data.hip.
 //
 //   (B x)[n, j] = sum_{k = -R .. R} b_|k| x[n + k, j],   terms with n + k outside [0, nt) omitted (zero extension):
 //   B is a symmetric matrix, B^T = B.

@@ -1,6 +1,6 @@
 // Envelope data misfit (fwi_misfit_envelope): an antisymmetric (Hilbert) FIR filter along time applied to (nt, ntr)
 // trace gathers, time the slow axis, the trace index the fast one, the envelopes of two gathers and the adjoint source
-// of their difference.  Internal launch interface between fwi_api.hip and fwi_envelope.hip.
+// of their difference.  Internal launch interface between fwi_api_misfit.hip and fwi_envelope.hip.
 //
 //   (H x)[n, j] = sum_{k = 1 .. Q} h_k (x[n - k, j] - x[n + k, j]),   terms outside [0, nt) omitted (zero extension):
 //   H is an antisymmetric matrix, H^T = -H.

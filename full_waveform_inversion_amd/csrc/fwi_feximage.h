@@ -1,6 +1,6 @@
 // Extended images on the Fourier store (include/fwi.h, fwi_fourier_offset_image[_vec] and fwi_fourier_lag_image[_vec]):
 // subsurface-offset and time-lag common-image gathers from the coefficients Q_k of the forward term and M_k of the
-// adjoint field, one lag per launch.  Internal launch interface between fwi_api.hip and fwi_feximage.hip.
+// adjoint field, one lag per launch.  Internal launch interface between fwi_api_fourier.hip and fwi_feximage.hip.
 //
 //   offset  dst(x) = sum_k a_k (Re Q_k(x - h e) Re M_k(x + h e) + Im Q_k(x - h e) Im M_k(x + h e))
 //           where x - h e and x + h e are both cells of the grid, 0 elsewhere and in the pad columns

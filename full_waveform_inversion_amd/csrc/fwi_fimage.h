@@ -1,6 +1,6 @@
 // Spectral imaging on the Fourier-compressed forward-term store (include/fwi.h, fwi_adjoint_spectral and
 // fwi_fourier_image / _gradient / _illumination): the gradient is formed per frequency from the coefficients Q_k of the
-// forward term and M_k of the adjoint field.  Internal launch interface between fwi_api.hip and fwi_fimage.hip.
+// forward term and M_k of the adjoint field.  Internal launch interface between the host units (fwi_api.hip, fwi_api_fourier.hip) and fwi_fimage.hip.
 //
 //   pack        slot(x) = mu(x) for the grid's cells, 0 in the pad columns: a padded field into one compact ring slot
 //   image       dst(x) = beta dst(x) + sum_k a_k (Re Q_k(x) Re M_k(x) + Im Q_k(x) Im M_k(x))

@@ -1,5 +1,5 @@
 // The tomographic / migration split of the spectral image on the Fourier store (include/fwi.h,
-// fwi_fourier_split_image[_vec]).  Internal launch interface between fwi_api.hip and fwi_fsplit.hip.
+// fwi_fourier_split_image[_vec]).  Internal launch interface between fwi_api_fourier.hip and fwi_fsplit.hip.
 //
 // With the one-sided taps t_1 .. t_R and an axis a of the grid, (H u)(i) = sum_{r = 1 .. R} t_r (u(i - r) - u(i + r))
 // along that axis, cells outside [0, n_a) of the GRID contributing nothing (zero extension; the pad columns of a compact

@@ -1,5 +1,5 @@
 // Source-side illumination (the diagonal of the pseudo-Hessian, Shin et al. 2001) and the two vector operations that
-// turn it into a preconditioner.  Internal launch interface between fwi_api.hip and fwi_illum.hip.
+// turn it into a preconditioner.  Internal launch interface between the host units (fwi_api.hip, fwi_api_fourier.hip, fwi_api_vec.hip) and fwi_illum.hip.
 //
 //   acc(x) += sum over nslots compact store slots of q(x)^2      (slot k at store + k * npts * qes bytes)
 //   H_m(x)  = (S / dt^4) acc(x)                                  (finalize, S = image stride)

@@ -1,6 +1,6 @@
 // Matching-filter (source-independent) data misfit (fwi_misfit_matched): the normal equations of a short two-sided
 // filter along time between two (nt, ntr) gathers, and the filter's convolution / correlation with a gather.  Time is
-// the slow axis, the trace index the fast one.  Internal launch interface between fwi_api.hip and fwi_match.hip.
+// the slow axis, the trace index the fast one.  Internal launch interface between fwi_api_misfit.hip and fwi_match.hip.
 //
 //   f = (f_-L .. f_L), K = 2 L + 1 coefficients, stored f[k + L]
 //   (C_f x)[n, j]   = sum_{k = -L .. L} f_k x[n - k, j]      terms with n - k outside [0, nt) omitted

@@ -1,7 +1,7 @@
 // Trace-by-trace optimal-transport (W2) misfit (fwi_misfit_transport) of (nt, ntr) trace gathers, time the slow axis, the
 // trace index the fast one: the traces as densities along time, their normalised CDFs, the sorted searches that give the
 // integer Kantorovich potentials, the squared distance of every trace pair and the adjoint source.  Internal launch
-// interface between fwi_api.hip and fwi_ot.hip.
+// interface between fwi_api_misfit.hip and fwi_ot.hip.
 //
 //   sh = M . s,  dh = M . d                        (s, d: the gathers after the filter B, where there is one)
 //   p_n = P(sh[n, j]),  q_n = P(dh[n, j]);   P(x) = x + c (linear) or log(1 + exp(b x)) / b (softplus)

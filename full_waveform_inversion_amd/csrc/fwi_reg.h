@@ -1,5 +1,5 @@
 // First-order Tikhonov and smoothed isotropic total-variation regularisation of a compact model-sized vector
-// (fwi_vec_regularizer).  Internal launch interface between fwi_api.hip and fwi_reg.hip.
+// (fwi_vec_regularizer).  Internal launch interface between fwi_api_vec.hip and fwi_reg.hip.
 //
 //   d = x - x0 (or x),  (D_a d)_i = d_{i+e_a} - d_i for i_a < n_a - 1, 0 on the last cell of the axis (nx, not cx),
 //   s_i = sum_a w_a (D_a d)_i^2,

@@ -1,5 +1,5 @@
 // The slant stack over vector slots (include/fwi.h, fwi_vec_shift_sum): one compact volume from up to SLANT_MAX others,
-// each shifted along z by a real number of cells.  Internal launch interface between fwi_api.hip and fwi_slant.hip.
+// each shifted along z by a real number of cells.  Internal launch interface between fwi_api_vec.hip and fwi_slant.hip.
 //
 //   dst := beta dst + sum_{i < nsrc} (c0_i src_i(z + n_i, .) + c1_i src_i(z + n_i + 1, .))
 //

@@ -1,5 +1,5 @@
 // Separable Gaussian smoothing of a compact model-sized vector (fwi_vec_smooth).  Internal launch interface between
-// fwi_api.hip and fwi_smooth.hip.
+// fwi_api_vec.hip and fwi_smooth.hip.
 //
 //   (S_sigma x)_i = sum_{k = -R .. R} w_|k| x_rho(i + k),   R = int(3 sigma + 0.5),
 //   w_k = exp(-k^2 / 2 sigma^2) / sum_j exp(-j^2 / 2 sigma^2),

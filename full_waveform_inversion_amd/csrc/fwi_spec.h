@@ -1,7 +1,7 @@
 // Frequency-domain (spectral) data misfit (fwi_misfit_spectral) of (nt, ntr) trace gathers, time the slow axis, the trace
 // index the fast one: the discrete Fourier coefficients of both gathers at F frequencies of the caller's choice, the
 // misfit and its derivative per (frequency, trace) pair, and the adjoint source.  Internal launch interface between
-// fwi_api.hip and fwi_spec.hip.
+// fwi_api_misfit.hip and fwi_spec.hip.
 //
 //   sh = M . s,  dh = M . d                        (s, d: the gathers after the filter B, where there is one)
 //   theta_kn = 2 pi frac(f_k n dt)                 (the table, formed on the host in fp64)

@@ -1,6 +1,6 @@
 // Cross-correlation traveltime misfit (fwi_misfit_traveltime) of (nt, ntr) trace gathers, time the slow axis, the trace
 // index the fast one: the correlation of every trace pair over a window of lags, the picked lag with its parabolic
-// refinement, the delay of every trace and the adjoint source.  Internal launch interface between fwi_api.hip and
+// refinement, the delay of every trace and the adjoint source.  Internal launch interface between fwi_api_misfit.hip and
 // fwi_ttime.hip.
 //
 //   sh = M . s,  dh = M . d                        (s, d: the gathers after the filter B, where there is one)

@@ -162,7 +162,11 @@ def test_binding_and_header_declare_the_call_under_the_same_abi():
     assert lib.fwi_abi_version() == 14
     assert lib.fwi_vec_shift_sum(None, 0, 1, None, None, None, 0.0) == 1  # null context: refused without a device
     makefile = open(os.path.join(ROOT, "full_waveform_inversion_amd", "csrc", "Makefile")).read()
-    assert " fwi_slant.o " in makefile and " fwi_slant.h " in makefile
+    # the object is built, and rebuilt when fwi_slant.h (or any header it includes) changes: the compiler writes the
+    # dependencies of every object beside it and the Makefile reads them back
+    assert " fwi_slant.o " in makefile
+    assert re.search(r"^%\.o: %\.hip\n\t.* -MMD -MP -c \$< -o \$@$", makefile, re.M)
+    assert re.search(r"^-include \$\(OBJS:\.o=\.d\)$", makefile, re.M)
 
 
 def test_the_engine_and_the_shot_loop_have_the_methods():
