@@ -14,6 +14,7 @@
 #include "fwi_ttime.h"
 #include "fwi_ot.h"
 #include "fwi_spec.h"
+#include "fwi_awi.h"
 
 namespace {
 
@@ -385,6 +386,62 @@ struct Impl {
         return FWI_OK;
     }
 
+    // s' = B d_syn, d' = B d_obs, w_j the Wiener filter with w_j * (M d') ~= M s' per trace (normal equations G_j w_j = c_j
+    // from the lag correlations, solved by Cholesky on the device), W_j its second moment about zero lag over its energy,
+    // J = 1/2 sum_j w_j W_j, r = B g where the adjoint sweep reads its amplitudes (fwi_awi.h)
+    static int misfit_adaptive(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R,
+                               const double *trace_weights, int L, double lam, double *J_out, double *w2_out,
+                               int32_t *counts_out, double *filters_out) {
+        Misfit m(ctx);
+        double J = 0.0;
+        T *g = nullptr;
+        const double *w2 = nullptr, *filters = nullptr;  // W_j and the filters within the work array
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        const size_t nfilt = (size_t)m.ntr * (2 * L + 1);
+        if (m.data) {
+            if ((rc = ensure(ctx, ctx->awi_part, awi_partials(m.nt, m.ntr, L) * sizeof(double))) ||
+                (rc = ensure(ctx, ctx->awi_work, awi_work_doubles(m.ntr, L) * sizeof(double))) ||
+                (rc = ensure(ctx, ctx->awi_counts, (size_t)m.ntr * sizeof(int32_t))))
+                return rc;
+            const double *tw;
+            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
+            double *part = (double *)ctx->awi_part.p, *work = (double *)ctx->awi_work.p;
+            int32_t *counts = (int32_t *)ctx->awi_counts.p;
+            m.sum = work + awi_total_at(m.ntr, L);  // the total of the terms 1/2 w_j W_j: J itself
+            w2 = work + awi_w2_at(m.ntr, L), filters = work + awi_w_at(m.ntr, L);
+            const T *s1, *d1;
+            if ((rc = m.prefilter(&s1, &d1))) return rc;
+            // the events around the three phases (fwi_misfit_adaptive_ms): recorded, never waited for here
+            ctx->have_awi_ms = false;
+            for (hipEvent_t &ev : ctx->awi_ev)
+                if (!ev) HIPCHK(ctx, hipEventCreate(&ev));
+            HIPCHK(ctx, hipEventRecord(ctx->awi_ev[0], ctx->stream));
+            HIPCHK(ctx, launch_awi_correlations<T>(part, s1, d1, m.w, L, m.nt, m.ntr, ctx->stream));
+            HIPCHK(ctx, hipEventRecord(ctx->awi_ev[1], ctx->stream));
+            HIPCHK(ctx, launch_awi_solve(work, counts, part, tw, ctx->cfg.dt, lam, L, m.nt, m.ntr, ctx->stream));
+            HIPCHK(ctx, hipEventRecord(ctx->awi_ev[2], ctx->stream));
+            // g reads d' at shifted rows, and without taps adjoint_source() IS d': g goes to the spare gather buffer, and
+            // finish() filters (with taps) or copies (without) it into place
+            g = (T *)ctx->data_tmp.p;
+            HIPCHK(ctx, launch_awi_source<T>(g, d1, m.w, work, counts, L, m.nt, m.ntr, ctx->stream));
+            HIPCHK(ctx, hipEventRecord(ctx->awi_ev[3], ctx->stream));
+            ctx->have_awi_ms = true;
+        }
+        if ((rc = m.finish(g, &J)) || (rc = m.per_trace(w2_out, w2, counts_out, (const int32_t *)ctx->awi_counts.p)))
+            return rc;
+        if (filters_out) {  // (ntr, 2 L + 1); without receivers or samples no trace counts: zeros
+            if (!m.data) {
+                std::fill(filters_out, filters_out + nfilt, 0.0);
+            } else {
+                HIPCHK(ctx, hipMemcpyAsync(filters_out, filters, nfilt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            }
+        }
+        *J_out = J;
+        return FWI_OK;
+    }
+
     // The twiddles of fwi_misfit_spectral, formed in fp64 as fourier_table forms the store's (from the fractional part of
     // f_k n dt) and kept on the context: block k, row n = (cos theta_kn, sin theta_kn), the rows from nt on zero
     // (spec_table_rows).  Rebuilt only when nt or the frequencies change.
@@ -670,6 +727,37 @@ int fwi_misfit_spectral(fwi_ctx *ctx, const void *d_obs, const void *weights, co
     if (int rc = misfit_synthetics(ctx, who, "or fwi_born ")) return rc;
     return DISPATCH_CALL(ctx, misfit_spectral, typed(d_obs), typed(weights), taps, R, nfreq, freqs_hz, kind, eps,
                          freq_weights, trace_weights, J_out, phase_out, logamp_out, counts_out);
+}
+
+int fwi_misfit_adaptive(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
+                        const double *trace_weights, int32_t L, double lam, double *J_out, double *w2_out,
+                        int32_t *counts_out, double *filters_out) {
+    if (int rc = misfit_callable(ctx, "fwi_misfit_adaptive", d_obs, J_out)) return rc;
+    if (int rc = data_args(ctx, "fwi_misfit_adaptive", taps, R)) return rc;
+    static_assert(FWI_AWI_LMAX == AWI_LMAX, "include/fwi.h and fwi_awi.h disagree");
+    if (L < 1 || L > FWI_AWI_LMAX)
+        return ctx->fail(FWI_EINVAL, "fwi_misfit_adaptive: L=%d outside [1, %d]", (int)L, FWI_AWI_LMAX);
+    if (int rc = nonneg_finite(ctx, "fwi_misfit_adaptive", "lam", lam, true)) return rc;
+    if (int rc = trace_weight_args(ctx, "fwi_misfit_adaptive", trace_weights)) return rc;
+    if (int rc = misfit_synthetics(ctx, "fwi_misfit_adaptive", "or fwi_born ")) return rc;
+    return DISPATCH_CALL(ctx, misfit_adaptive, typed(d_obs), typed(weights), taps, R, trace_weights, L, lam, J_out, w2_out,
+                         counts_out, filters_out);
+}
+
+int fwi_misfit_adaptive_ms(fwi_ctx *ctx, double *ms_out) {
+    if (!ctx) return FWI_EINVAL;
+    if (!ms_out) return ctx->fail(FWI_EINVAL, "fwi_misfit_adaptive_ms: null argument");
+    if (!ctx->have_awi_ms)
+        return ctx->fail(FWI_ESTATE, "fwi_misfit_adaptive_ms: no fwi_misfit_adaptive call with receivers has launched its "
+                                     "kernels");
+    (void)hipSetDevice(ctx->cfg.device);
+    HIPCHK(ctx, hipEventSynchronize(ctx->awi_ev[3]));
+    for (int i = 0; i < 3; ++i) {
+        float ms = 0.f;
+        HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->awi_ev[i], ctx->awi_ev[i + 1]));
+        ms_out[i] = (double)ms;
+    }
+    return FWI_OK;
 }
 
 int fwi_match_solve(const double *G, const double *b, int32_t K, double mu, double *f_out) {

@@ -48,7 +48,8 @@ struct Buf {
     X(corr_part) X(corr_coef)                                                                                  \
     X(tt_part) X(tt_coef) X(tt_lag)                                                                            \
     X(ot_work) X(ot_counts)                                                                                    \
-    X(spec_part) X(spec_coef) X(spec_counts) X(spec_fw) X(spec_table)
+    X(spec_part) X(spec_coef) X(spec_counts) X(spec_fw) X(spec_table)                                          \
+    X(awi_part) X(awi_work) X(awi_counts)
 #define FWI_DECLARE_BUF(name) Buf name;
 #define FWI_DECLARE_PTR(name) void *name = nullptr;
 
@@ -214,6 +215,10 @@ struct fwi_ctx {
     // fwi_misfit_spectral (fwi_spec.hip): the segment sums, G / phi / a and the terms of J, which pairs count, the
     // frequency weights, and the twiddle table with the (nt, frequencies) it was formed for (dt is the context's)
     FWI_MISFIT_BUFS(FWI_DECLARE_BUF)
+    // fwi_misfit_adaptive (fwi_awi.hip): the correlations of both kinds, z / the filters / W / the terms of J, which
+    // traces count; the events around the three phases of the last call (created by the first), fwi_misfit_adaptive_ms
+    hipEvent_t awi_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool have_awi_ms = false;
     int spec_table_nt = 0;
     std::vector<double> spec_table_freqs, spec_table_host;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)

@@ -132,6 +132,40 @@ absolute and must not follow ``s``.  A trace counts iff every ``p_n`` and ``q_n`
 are finite and ``> 0``; otherwise ``W_j = 0``, its term of ``J`` is 0 and its adjoint source is 0 (under ``linear`` a
 trace that goes below ``-c`` drops out).  No linear Gauss-Newton weight either.
 
+Adaptive (per-trace matching-filter) misfit, :class:`AdaptiveMatching` (``Engine.misfit_adaptive``,
+``fwi_misfit_adaptive``, ``csrc/fwi_awi.hip``): adaptive waveform inversion (Warner & Guasch 2016).  The matching filter
+above estimates one filter per shot, which absorbs the source signature and nothing else; this one designs one Wiener
+filter per trace that turns the observed trace into the synthetic one, and penalises the filter's energy away from zero
+lag, normalised by its energy.  It needs no pick and no window, keeps amplitude and phase, grows with the square of a time
+shift up to the filter's half-length, and a gain per trace cancels exactly.  With ``s = d_syn``, ``d = d_obs``, ``B``,
+``M``, the per-trace weights ``tw_j`` and ``dt`` as above, ``L >= 1``, ``K = 2 L + 1`` coefficients ``w_k``,
+``k = -L .. L``, stored at ``w[k + L]``, and ``lam > 0`` a relative ridge, per trace ``j``, every trace zero-extended
+outside ``[0, nt)``:
+
+    s' = B s,  d' = B d            (rounded to the context dtype once, only when taps are given)
+    sh = M . s',  dh = M . d'
+    a_j(m) = sum_n dh[n, j] dh[n + m, j]            m = 0 .. 2 L   (0 once m > nt - 1)
+    c_j(k) = sum_n sh[n + k, j] dh[n, j]            k = -L .. L    (= sum_n dh[n - k, j] sh[n, j])
+    G_j[k, l] = a_j(|k - l|) + lam a_j(0) [k == l]  exactly Toeplitz: the fit runs over the whole convolution output
+    w_j = G_j^-1 c_j                                the filter with  w * dh ~= sh,  linear in s
+    N_j = sum_k w_k^2
+    W_j = sum_k (k dt)^2 w_k^2 / N_j                (s^2)
+    J   = 1/2 sum_j tw_j W_j
+    y_k = tw_j w_k ((k dt)^2 - W_j) / N_j
+    z_j = G_j^-1 y_j
+    g[n, j] = M[n, j] sum_k z_k dh[n - k, j]        (rounded to the dtype once)
+    r = dJ/ds = B g
+
+``G_j`` depends on the data only, so the ridge relative to ``a_j(0)`` adds no term to the gradient and ``r`` is the exact
+gradient of this discrete ``J``.  A trace counts iff ``a_j(0)`` is finite and ``> 0``, every Cholesky pivot of ``G_j`` is
+finite and ``> 0`` and ``N_j`` is finite and ``> 0`` (a dead synthetic trace gives ``w = 0``); otherwise ``W_j = 0``, its
+term of ``J``, its filter and its adjoint source are 0.  ``W_j <= (L dt)^2``; ``L`` may exceed ``nt - 1``.
+``d_obs == d_syn`` does NOT give ``J = 0``: it gives the second moment of ``G^-1 a``, a band-limited delta, and a
+non-zero ``r``; ``sqrt(W)`` is then the width the ridge and the bandwidth leave (4.1 samples for a 25 Hz Ricker at
+2 ms, ``L = 64``, ``lam = 1e-2``), the floor below which a shift cannot be read.  ``J`` is not differentiable where a
+trace starts or stops counting.  The condition number of ``G_j`` is at most ``1 + K / lam``.  No linear Gauss-Newton
+weight either.
+
 Frequency-domain (spectral) misfit, :class:`SpectralMisfit` (``Engine.misfit_spectral``, ``fwi_misfit_spectral``,
 ``csrc/fwi_spec.hip``): every misfit above compares traces in the time domain.  This one compares the discrete Fourier
 coefficients of the weighted, filtered gathers at up to 64 frequencies of the caller's choice -- their difference, their
@@ -849,6 +883,132 @@ class TransportW2(_PerTrace):
         self.distances, self.counts = W, counts
         src = np.where(counts, 0.5 * w * dt2 / Ss, 0.0) * (phi - phibar) * dP
         return float(np.sum(0.5 * w * W)), self._residual(src, M)
+
+
+class AdaptiveMatching(_PerTrace):
+    """The adaptive (per-trace matching-filter) misfit of the module's definition in fp64 NumPy,
+    ``objective(d_syn, d_obs, weights=None, trace_weights=None) -> (J, r)``, and the ``objective=`` that
+    ``shots.misfit_and_gradient`` recognises (an engine that has ``misfit_adaptive`` replaces it by the device path; the
+    shot loop hands it ``Shot.weights`` and ``Shot.trace_weights``).
+
+    ``dt``: the sampling interval in seconds.  ``L``: the half-length of the filters in samples, ``1 .. L_MAX``.
+    ``lam``: the ridge ``> 0``, relative to each trace's ``a_j(0)``.  ``taps``: the one-sided ``b_0 .. b_R`` of ``B``, or
+    None.  ``dtype``: round ``B s``, ``B d`` (with taps) and ``g`` to it once each, as a device context of that dtype
+    does (None: keep fp64).
+
+    ``moments`` holds the ``W_j`` of the last call in s^2, ``filters`` its ``w_j`` as ``(ntr, 2 L + 1)`` (both 0 where a
+    trace does not count) and ``counts`` which traces count.  ``d_obs == d_syn`` does not give ``J = 0`` (the module's
+    docstring).  The systems are solved by this class's own dense Cholesky factorisation, batched over the traces.  Not a
+    :class:`WeightedL2`: there is no linear Gauss-Newton weight, and ``gauss_newton_hvp`` refuses it."""
+
+    L_MAX = 64  # the largest half-length the device path accepts (fwi_misfit_adaptive)
+
+    def __init__(self, dt, L, lam=1e-2, taps=None, dtype=None):
+        if not (float(dt) > 0.0 and np.isfinite(dt)):
+            raise ValueError("dt must be > 0")
+        if int(L) != L or not 1 <= int(L) <= self.L_MAX:
+            raise ValueError("L must be an integer number of samples in [1, %d]" % self.L_MAX)
+        if not (float(lam) > 0.0 and np.isfinite(lam)):
+            raise ValueError("lam must be finite and > 0")
+        self.dt = float(dt)
+        self.L = int(L)
+        self.lam = float(lam)
+        self._band(taps, dtype)
+        self.moments = self.filters = self.counts = None
+
+    engine_method = "misfit_adaptive"
+
+    def device(self, engine, shot, i):
+        return engine.misfit_adaptive(shot.d_obs, self.L, self.lam, shot.weights, self.taps, shot.trace_weights)
+
+    def correlations(self, d_syn, d_obs, weights=None, majorants=True):
+        """``(a, c, (Aa, Ac), sh, dh)``: ``a[m, j] = a_j(m)`` for ``m = 0 .. 2 L``, ``c[k + L, j] = c_j(k)`` for
+        ``k = -L .. L``, their majorants, the same sums of absolute products (None without ``majorants``), and the
+        weighted, filtered gathers"""
+        sh, dh, _ = self._weighted(d_syn, d_obs, weights)
+        nt, ntr = sh.shape
+        L = self.L
+        a, c = np.zeros((2 * L + 1, ntr)), np.zeros((2 * L + 1, ntr))
+        Aa, Ac = (np.zeros_like(a), np.zeros_like(c)) if majorants else (None, None)
+        ash, adh = (np.abs(sh), np.abs(dh)) if majorants else (None, None)
+        for m in range(min(2 * L, nt - 1) + 1):
+            a[m] = np.sum(dh[:nt - m] * dh[m:], axis=0)
+            if majorants:
+                Aa[m] = np.sum(adh[:nt - m] * adh[m:], axis=0)
+        for k in range(-min(L, nt - 1), min(L, nt - 1) + 1):
+            p, q = (slice(k, nt), slice(0, nt - k)) if k >= 0 else (slice(0, nt + k), slice(-k, nt))
+            c[k + L] = np.sum(sh[p] * dh[q], axis=0)
+            if majorants:
+                Ac[k + L] = np.sum(ash[p] * adh[q], axis=0)
+        return a, c, ((Aa, Ac) if majorants else None), sh, dh
+
+    def normal(self, a):
+        """``(G, alive)``: the ``(ntr, K, K)`` Toeplitz matrices ``a_j(|k - l|) + lam a_j(0) [k == l]`` and which traces
+        have a finite ``a_j(0) > 0`` (the others are given the identity, so that everything downstream stays finite)"""
+        K = 2 * self.L + 1
+        a0 = a[0]
+        alive = np.isfinite(a0) & (a0 > 0.0)
+        k = np.arange(K)
+        G = np.transpose(a[np.abs(k[:, None] - k[None, :])], (2, 0, 1)).copy()
+        G[:, k, k] = a0[:, None] + self.lam * a0[:, None]
+        G[~alive] = np.eye(K)
+        return G, alive
+
+    @staticmethod
+    def cholesky(G):
+        """``(F, ok)``: the lower Cholesky factors ``(ntr, K, K)`` of the batch, column by column, and which matrices had
+        every pivot finite and ``> 0`` (a failed pivot is replaced by 1)"""
+        n, K, _ = G.shape
+        F, ok = np.zeros_like(G), np.ones(n, bool)
+        for j in range(K):
+            with np.errstate(invalid="ignore", over="ignore"):
+                s = G[:, j:, j] - np.einsum("nik,nk->ni", F[:, j:, :j], F[:, j, :j])
+                good = np.isfinite(s[:, 0]) & (s[:, 0] > 0.0)
+            ok &= good
+            p = np.sqrt(np.where(good, s[:, 0], 1.0))
+            F[:, j, j] = p
+            F[:, j + 1:, j] = s[:, 1:] / p[:, None]
+        return F, ok
+
+    @staticmethod
+    def solve(F, b):
+        """``(F F^T)^-1 b`` for the batch: ``b`` is ``(ntr, K)``"""
+        K = F.shape[1]
+        x = np.array(b, np.float64)
+        for k in range(K):
+            x[:, k] /= F[:, k, k]
+            x[:, k + 1:] -= F[:, k + 1:, k] * x[:, k:k + 1]
+        for k in range(K - 1, -1, -1):
+            x[:, k] /= F[:, k, k]
+            x[:, :k] -= F[:, k, :k] * x[:, k:k + 1]
+        return x
+
+    def __call__(self, d_syn, d_obs, weights=None, trace_weights=None):
+        a, c, _, _, dh = self.correlations(d_syn, d_obs, weights, majorants=False)
+        nt, ntr = dh.shape
+        L, K = self.L, 2 * self.L + 1
+        tw = self._trace_weights(trace_weights, ntr)
+        G, alive = self.normal(a)
+        F, ok = self.cholesky(G)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            w = self.solve(F, c.T)
+            t2 = (np.arange(-L, L + 1, dtype=np.float64) * self.dt) ** 2
+            N, S = np.sum(w * w, axis=1), np.sum(t2 * (w * w), axis=1)
+            counts = alive & ok & np.isfinite(N) & (N > 0.0) & np.isfinite(S)
+        Ns = np.where(counts, N, 1.0)
+        w = np.where(counts[:, None], w, 0.0)
+        W = np.where(counts, S / Ns, 0.0)
+        y = np.where(counts[:, None], tw[:, None] * w * (t2[None, :] - W[:, None]) / Ns[:, None], 0.0)
+        z = np.where(counts[:, None], self.solve(np.where(counts[:, None, None], F, np.eye(K)), y), 0.0)
+        self.moments, self.filters, self.counts = W, w, counts
+        g = np.zeros((nt, ntr))
+        for k in range(-min(L, nt - 1), min(L, nt - 1) + 1):  # g[n] += z_k dh[n - k]
+            if k >= 0:
+                g[k:] += z[:, k + L] * dh[:nt - k]
+            else:
+                g[:nt + k] += z[:, k + L] * dh[-k:]
+        g = np.where(counts[None, :], g, 0.0)
+        return float(np.sum(0.5 * tw * W)), self._residual(g, weights)
 
 
 SPECTRAL_KINDS = ("l2", "phase", "logamp", "log")

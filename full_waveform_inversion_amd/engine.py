@@ -387,6 +387,41 @@ class Engine:
                          (twp, _lib.OT_TRANSFORMS[transform], float(param)), outp)
         return (J,) + out if per_trace else J
 
+    def misfit_adaptive(self, d_obs, L, lam=1e-2, weights=None, taps=None, trace_weights=None, per_trace=False):
+        """Adaptive (per-trace matching-filter) misfit of the last forward's seismograms (adaptive waveform inversion,
+        Warner & Guasch 2016), which keeps amplitude and phase, needs no pick and no window and grows with the square of
+        a time shift up to the filter's half-length: with ``sh = M . B d_syn``, ``dh = M . B d_obs``, ``w_j`` the Wiener
+        filter of ``2 L + 1`` coefficients with ``w_j * dh_j ~= sh_j`` (normal equations ``(A_j + lam a_j(0) I) w_j =
+        c_j`` from the lag correlations, solved per trace on the device), ``W_j = sum_k (k dt)^2 w_k^2 / sum_k w_k^2``
+        (s^2) and ``J = 1/2 sum_j tw_j W_j``.  ``L`` is in samples, ``1 .. 64``; ``lam > 0`` is a ridge relative to the
+        trace's energy.  A gain per trace cancels.  ``d_obs == d_syn`` does NOT give ``J = 0``: ``sqrt(W)`` is then the
+        width of the band-limited delta the ridge leaves, the floor below which a shift cannot be read.  A trace counts
+        only if its data are alive, its system is positive definite and its filter has energy; otherwise its ``W``, its
+        term of J and its adjoint source are 0.  ``weights`` and ``taps`` as in :meth:`misfit_weighted`,
+        ``trace_weights`` as in :meth:`misfit_correlation`.  The adjoint source ``dJ/dd_syn`` is formed on the device and
+        kept there for ``adjoint(None)``.  Returns J, with ``per_trace=True`` ``(J, W, counts, filters)``: the ``ntr``
+        moments ``W_j``, 1 / 0 per trace and the filters ``(ntr, 2 L + 1)`` (``fwi_misfit_adaptive``; the NumPy twin is
+        :class:`datafit.AdaptiveMatching`)."""
+        if int(L) != L:
+            raise ValueError("L must be an integer number of samples")
+        L = int(L)
+        twp, _keep = self._trace_weights(trace_weights)
+        out, outp = self._per_trace(per_trace, np.float64, np.int32)
+        if per_trace:
+            filters = np.zeros((self._nrec, 2 * max(L, 0) + 1))
+            out, outp = out + (filters,), outp + (filters.ctypes.data_as(C.c_void_p),)
+        else:
+            outp = outp + (None,)
+        J = self._misfit(self._lib.fwi_misfit_adaptive, d_obs, weights, taps, (twp, L, float(lam)), outp)
+        return (J,) + out if per_trace else J
+
+    def misfit_adaptive_ms(self):
+        """``(correlations, solve, source)``: the device times in ms of the three phases of the last
+        :meth:`misfit_adaptive` call, from HIP events on the context's stream (``fwi_misfit_adaptive_ms``)."""
+        ms = np.zeros(3)
+        self._chk(self._lib.fwi_misfit_adaptive_ms(self._c, ms.ctypes.data_as(C.c_void_p)))
+        return tuple(float(v) for v in ms)
+
     def misfit_spectral(self, d_obs, freqs, kind="l2", eps=0.0, weights=None, taps=None, freq_weights=None,
                         trace_weights=None, per_pair=False):
         """Frequency-domain (spectral) misfit of the last forward's seismograms: with ``sh = M . B d_syn``,

@@ -353,7 +353,8 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     (see objectives.py for the reference's similarity measures as misfits).
 
     An objective of :mod:`datafit` -- ``WeightedL2``, ``MatchedL2``, ``EnvelopeL2``, ``NormalizedCorrelation``,
-    ``TraveltimeL2``, ``TransportW2``, ``SpectralMisfit`` or a subclass of one -- names its own two calls.
+    ``TraveltimeL2``, ``TransportW2``, ``AdaptiveMatching``, ``SpectralMisfit`` or a subclass of one -- names its own two
+    calls.
     ``objective.host(d_syn, shot, i)`` is the NumPy twin with what its class takes from the shot: ``Shot.weights``, for
     the sums over traces and the spectral misfit ``Shot.trace_weights`` as well, for the matching filter ``shot=i``.
     Under ``device_l2``, an engine that has the
@@ -363,8 +364,8 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
 
     Either branch uses the same per-shot numbers, which depend on the data only: ``objective.mu_of(i)`` (one damping for
     every shot, or a sequence indexed like ``shots``), ``objective.eps_of(d_obs)``, ``objective.param_of(d_obs)``; either
-    leaves shot ``i``'s matching filter in ``objective.filters[i]``.  ``objective.dt`` of a traveltime or transport
-    objective must be the engine's time step.
+    leaves shot ``i``'s matching filter in ``objective.filters[i]``.  ``objective.dt`` of a traveltime, transport or
+    adaptive objective must be the engine's time step.
 
     ``device_l2`` (least squares only): form the residual and J on the device (``fwi_misfit_l2``) -- in the
     engine's dtype, i.e. with an fp32 engine ``d_obs`` is rounded to fp32 before the subtraction, which puts

@@ -387,6 +387,60 @@ int fwi_misfit_transport(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const 
                          const double *trace_weights /* ntr, or NULL */, int32_t transform, double param, double *J_out,
                          double *w2_out /* ntr, or NULL: W_j in s^2 */, int32_t *counts_out /* ntr, or NULL: 1 / 0 */);
 
+/* Adaptive (per-trace matching-filter) misfit on the device (adaptive waveform inversion; Warner & Guasch 2016): the
+ * envelope drops the phase, the correlation the amplitude, the traveltime misfit reduces a trace to one pick, W2 needs a
+ * positivisation and fwi_misfit_matched estimates one filter per shot.  This one designs one Wiener filter per TRACE that
+ * turns the observed trace into the synthetic one and penalises the filter's energy away from zero lag, normalised by
+ * its energy: no pick and no window, amplitude and phase are kept, it grows with the square of a time shift up to the
+ * filter's half-length, and a gain per trace cancels exactly.  With s = d_syn of the last forward and d = d_obs, both
+ * (nt, ntr) as above, B, M and the per-trace weights tw_j exactly as in fwi_misfit_traveltime, L >= 1 the half-length in
+ * samples, K = 2 L + 1 coefficients w_k, k = -L .. L, stored at w[k + L], dt the context's time step and lam > 0 a
+ * relative ridge, per trace j, every trace zero-extended outside [0, nt):
+ *     s' = B s,  d' = B d            (rounded to the context's dtype once, only when taps are given)
+ *     sh = M . s',  dh = M . d'
+ *     a_j(m) = sum_n dh[n, j] dh[n + m, j]            m = 0 .. 2 L   (0 once m > nt - 1)
+ *     c_j(k) = sum_n sh[n + k, j] dh[n, j]            k = -L .. L    (= sum_n dh[n - k, j] sh[n, j])
+ *     G_j[k, l] = a_j(|k - l|) + lam a_j(0) [k == l]  exactly Toeplitz: the fit runs over the whole convolution output
+ *     w_j = G_j^-1 c_j                                the filter with  w * dh ~= sh,  linear in s
+ *     N_j = sum_k w_k^2
+ *     W_j = sum_k (k dt)^2 w_k^2 / N_j                (s^2)
+ *     J   = 1/2 sum_j tw_j W_j
+ *     y_k = tw_j w_k ((k dt)^2 - W_j) / N_j
+ *     z_j = G_j^-1 y_j
+ *     g[n, j] = M[n, j] sum_k z_k dh[n - k, j]        (rounded to the dtype once)
+ *     r = dJ/ds = B g
+ * G_j depends on the data only: a ridge relative to a_j(0) adds no term to the gradient, and r is the exact gradient of
+ * this discrete J.  A trace counts iff a_j(0) is finite and > 0, every Cholesky pivot of G_j is finite and > 0 and N_j is
+ * finite and > 0 (a dead synthetic trace gives w = 0 and does not count); for a trace that does not count W_j = 0, its
+ * term of J, its filter and its adjoint source are 0.  W_j <= (L dt)^2.  A gain on a synthetic trace cancels.  L may
+ * exceed nt - 1 (the lags beyond nt - 1 are 0).  d_obs == d_syn does NOT give J = 0: it gives the second moment of
+ * G^-1 a, a band-limited delta whose width the ridge and the bandwidth of the data set, and a non-zero r; sqrt(W) is
+ * that width, the floor below which a shift cannot be read.  J is NOT differentiable where a trace starts or stops
+ * counting.  *J_out = J; w2_out, if not NULL, receives the ntr values W_j in s^2, counts_out, if not NULL, 1 for a trace
+ * that counts and 0 otherwise, filters_out, if not NULL, the filters w_j as (ntr, 2 L + 1); r stays on the device as the
+ * residual of the next fwi_adjoint(ctx, NULL, ...).  The synthetics are left alone: the call can be repeated.
+ * Everything between the loads and the roundings named above is fp64.  a_j and c_j are added by fma over ascending time
+ * within a time slice and over the slices in ascending order, the number of slices a function of (nt, ntr, L) only; the
+ * systems are solved by Cholesky, one workgroup per trace: every entry of the factor takes its terms by fma over
+ * ascending index, the forward substitutions take theirs over ascending, the back substitutions over descending index,
+ * N_j and the moment are added over ascending k, g by fma over ascending k, and J adds its traces in a fixed order,
+ * without atomics: equal inputs give equal bits.  State rules, off-grid receivers (ntr is then the number of points) and
+ * work buffers as fwi_misfit_weighted.  FWI_EINVAL: a null J_out, a null d_obs with nrec > 0, the tap errors of
+ * fwi_misfit_weighted, L < 1 or > FWI_AWI_LMAX, lam <= 0 or not finite, a trace weight that is negative or not finite.
+ * No receivers: J = 0 and nothing is launched. */
+#define FWI_AWI_LMAX 64
+int fwi_misfit_adaptive(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                        const double *taps /* R + 1, or NULL */, int32_t R,
+                        const double *trace_weights /* ntr, or NULL */, int32_t L, double lam, double *J_out,
+                        double *w2_out /* ntr, or NULL: W_j in s^2 */, int32_t *counts_out /* ntr, or NULL: 1 / 0 */,
+                        double *filters_out /* (ntr, 2 L + 1), or NULL: w_j */);
+
+/* The device times in milliseconds of the three phases of the last fwi_misfit_adaptive call on this context, from HIP
+ * events on its stream: ms_out[0] the lag correlations a_j and c_j, ms_out[1] the per-trace solves with the sum of J,
+ * ms_out[2] the adjoint source g (B g and the scatter onto the nodes are not included).  Waits for that call's kernels.
+ * FWI_ESTATE before the first such call with receivers; FWI_EINVAL: a null ms_out. */
+int fwi_misfit_adaptive_ms(fwi_ctx *ctx, double *ms_out /* 3 */);
+
 /* Frequency-domain (spectral) data misfit on the device: every misfit above compares traces in the time domain; this
  * one compares their discrete Fourier coefficients at F frequencies of the caller's choice, amplitude and phase together
  * or apart (the logarithmic and phase-only misfits of Shin & Min 2006 and Bednar, Shin & Pyun 2007), with a weight per

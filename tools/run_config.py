@@ -130,6 +130,15 @@ def main():
     ap.add_argument("--transport-param", type=float, default=None, metavar="X",
                     help="the absolute parameter of --transport: b of softplus, c of linear (default: per shot from its "
                          "observed data, datafit.TransportW2.param_of, computed once and held through the run)")
+    ap.add_argument("--adaptive", type=int, default=None, metavar="L",
+                    help="adaptive (per-trace matching-filter) misfit, 1/2 the sum over traces of the second moment about "
+                         "zero lag of the Wiener filter of 2 L + 1 samples that turns the observed trace into the synthetic "
+                         "one, over the filter's energy: keeps amplitude and phase, needs no pick, grows with the square of "
+                         "the time shift up to L samples, blind to the gain of a trace; not zero at equal data "
+                         "(datafit.AdaptiveMatching, on the device); composes with --bands and --mute-direct, not with the "
+                         "other misfits")
+    ap.add_argument("--adaptive-ridge", type=float, default=None, metavar="LAM",
+                    help="the ridge of --adaptive, relative to the energy of each observed trace (default 1e-2)")
     ap.add_argument("--spectral", choices=datafit.SPECTRAL_KINDS, default=None,
                     help="frequency-domain misfit on the bins of --spectral-band: 1/2 the sum over frequencies and traces "
                          "of the squared difference of the Fourier coefficients (l2), of their phases (phase), of their "
@@ -227,7 +236,7 @@ def main():
         ap.error("--match-source L must lie in [0, %d]" % datafit.L_MAX)
     if not (a.match_mu_percent >= 0.0 and np.isfinite(a.match_mu_percent)):
         ap.error("--match-mu-percent P must be finite and >= 0")
-    misfits = [flag for flag in ("--spectral", "--transport", "--traveltime", "--correlation", "--envelope", "--match-source")
+    misfits = [flag for flag in ("--adaptive", "--spectral", "--transport", "--traveltime", "--correlation", "--envelope", "--match-source")
                if getattr(a, flag[2:].replace("-", "_")) is not None]
     if len(misfits) > 1:
         ap.error("%s are different misfits: choose one" % " and ".join(misfits))
@@ -235,6 +244,12 @@ def main():
         ap.error("--transport-param needs --transport")
     if a.transport_param is not None and not (a.transport_param > 0.0 and np.isfinite(a.transport_param)):
         ap.error("--transport-param X must be finite and > 0")
+    if a.adaptive_ridge is not None and a.adaptive is None:
+        ap.error("--adaptive-ridge needs --adaptive")
+    if a.adaptive_ridge is not None and not (a.adaptive_ridge > 0.0 and np.isfinite(a.adaptive_ridge)):
+        ap.error("--adaptive-ridge LAM must be finite and > 0")
+    if a.adaptive is not None and not 1 <= a.adaptive <= datafit.AdaptiveMatching.L_MAX:
+        ap.error("--adaptive L must lie in [1, %d] samples" % datafit.AdaptiveMatching.L_MAX)
     if a.traveltime is not None and not 1 <= a.traveltime <= datafit.K_MAX:
         ap.error("--traveltime MAX_LAG must lie in [1, %d] samples" % datafit.K_MAX)
     if a.correlation is not None and not (a.correlation >= 0.0 and np.isfinite(a.correlation)):
@@ -350,6 +365,8 @@ def main():
             return datafit.TraveltimeL2(w.dt, a.traveltime, taps)
         if a.transport is not None:  # (the parameter: given, or a data-only number per shot, param_of of its d_obs)
             return datafit.TransportW2(w.dt, a.transport, a.transport_param, taps)
+        if a.adaptive is not None:
+            return datafit.AdaptiveMatching(w.dt, a.adaptive, 1e-2 if a.adaptive_ridge is None else a.adaptive_ridge, taps)
         return datafit.WeightedL2(taps) if (taps is not None or a.mute_direct is not None) else None
 
     def filters_line(o, band=None):
@@ -493,6 +510,7 @@ def main():
                           "spectral_floor_percent": a.spectral_floor_percent if a.spectral is not None else None,
                           "spectral_whiten": a.spectral_whiten, "fourier_imaging": a.fourier_imaging,
                           "transport": a.transport, "transport_param": a.transport_param,
+                          "adaptive_L": a.adaptive, "adaptive_ridge": a.adaptive_ridge,
                           "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
                           "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
                           "envelope_floor_percent": a.envelope_floor_percent if a.envelope is not None else None,
