@@ -30,6 +30,7 @@ MATCH_LMAX = 64  # FWI_MATCH_LMAX
 TT_KMAX = 1024  # FWI_TT_KMAX
 OT_TRANSFORMS = {"linear": 0, "softplus": 1}  # FWI_OT_LINEAR, FWI_OT_SOFTPLUS
 AWI_LMAX = 64  # FWI_AWI_LMAX
+ROBUST_KINDS = {"huber": 0, "hybrid": 1, "cauchy": 2}  # FWI_ROBUST_HUBER, FWI_ROBUST_HYBRID, FWI_ROBUST_CAUCHY
 FOURIER_FMAX, FOURIER_BMAX = 64, 8  # FWI_FOURIER_FMAX, FWI_FOURIER_BMAX
 SPLIT_SAME, SPLIT_OPPOSITE, SPLIT_HILBERT, SPLIT_RMAX = 0, 1, 2, 64  # FWI_SPLIT_*, FWI_SPLIT_RMAX
 SHIFT_SUM_MAX = 64  # FWI_SHIFT_SUM_MAX
@@ -79,6 +80,9 @@ SIGNATURES = {
     "fwi_misfit_transport": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _D, C.POINTER(_D), _P, _P]),
     "fwi_misfit_adaptive": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _D, C.POINTER(_D), _P, _P, _P]),
     "fwi_misfit_adaptive_ms": (C.c_int, [_P, _P]),
+    "fwi_misfit_robust": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _P, C.POINTER(_D)]),
+    "fwi_residual_weight_robust": (C.c_int, [_P, _P, _I32]),
+    "fwi_residual_median": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P]),
     "fwi_misfit_spectral": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _I32, _D, _P, _P, C.POINTER(_D), _P, _P, _P]),
     "fwi_gradient": (C.c_int, [_P, _I32, _P]),
     "fwi_gradient_reset": (C.c_int, [_P]),

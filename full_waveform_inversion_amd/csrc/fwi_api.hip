@@ -2126,7 +2126,7 @@ int fwi_set_model(fwi_ctx *ctx, const void *c_host) {
 // the source set has been replaced, an allocation that does not fit -- leaves flags that describe the old shot beside
 // point sets, sizes or buffers of the new one.
 static void drop_forward(fwi_ctx *ctx) {
-    ctx->have_forward = ctx->have_q = ctx->have_m = ctx->have_syn = ctx->have_dev_residual = false;
+    ctx->have_forward = ctx->have_q = ctx->have_m = ctx->have_syn = ctx->have_dev_residual = ctx->have_irls = false;
     ctx->resid_pts_in = fwi_ctx::RESID_PTS_NONE;
 }
 

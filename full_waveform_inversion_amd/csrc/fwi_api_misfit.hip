@@ -1,4 +1,4 @@
-// C-ABI of the engine, the data misfits (include/fwi.h: fwi_misfit_*, fwi_match_solve, fwi_residual_weight): the
+// C-ABI of the engine, the data misfits (include/fwi.h: fwi_misfit_*, fwi_match_solve, fwi_residual_*): the
 // synthetics of the last forward against the data, the adjoint source left on the device.  Host side, no time loop.
 #include <algorithm>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include "fwi_ot.h"
 #include "fwi_spec.h"
 #include "fwi_awi.h"
+#include "fwi_robust.h"
 
 namespace {
 
@@ -556,6 +557,110 @@ struct Impl {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return FWI_OK;
     }
+
+    // e = M . B (d_syn - d_obs) as fwi_misfit_weighted's, J = sum_j tw_j sum_n rho(e; a_j), g = tw_j psi e in place of e,
+    // r = B (M . g) where the adjoint sweep reads its amplitudes (fwi_robust.h).  keep: W = tw_j M^2 psi stays in
+    // ctx->robust_w for fwi_residual_weight_robust; whatever W was held goes with the call.
+    static int misfit_robust(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, int kind,
+                             const double *thresh, const double *trace_weights, int keep, double *jtrace_out,
+                             int32_t *nout_out, double *J_out) {
+        Misfit m(ctx);
+        double J = 0.0;
+        ctx->have_irls = false;
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        const size_t tiles_ntr = (size_t)robust_tiles(m.nt) * m.ntr;
+        if (m.data) {
+            if ((rc = ensure(ctx, ctx->robust_part, robust_partials(m.nt, m.ntr) * sizeof(double))) ||
+                (rc = ensure(ctx, ctx->robust_cnt, robust_counts(m.nt, m.ntr) * sizeof(int32_t))) ||
+                (rc = ensure(ctx, ctx->robust_thresh, (size_t)m.ntr * sizeof(double))) ||
+                (keep && (rc = ensure(ctx, ctx->robust_w, m.n * sizeof(T)))))
+                return rc;
+            const double *tw;
+            if ((rc = m.trace_weights(trace_weights, &tw))) return rc;
+            // (the caller's pageable memory: the copy is complete before anything that can fail and return follows it)
+            HIPCHK(ctx, hipMemcpyAsync(ctx->robust_thresh.p, thresh, (size_t)m.ntr * sizeof(double), hipMemcpyHostToDevice,
+                                       ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            T *e = (T *)ctx->data_tmp.p;
+            HIPCHK(ctx, launch_fir_time<T>(e, m.syn, m.resid, nullptr, m.w, m.b, m.Re, m.nt, m.ntr, nullptr, false,
+                                           ctx->stream));
+            // the block sums and their total go where fwi_misfit_weighted's go: m.sum is J itself
+            HIPCHK(ctx, launch_robust_source<T>(e, keep ? (T *)ctx->robust_w.p : nullptr, e, m.w,
+                                                (const double *)ctx->robust_thresh.p, tw, kind,
+                                                (double *)ctx->robust_part.p, (int32_t *)ctx->robust_cnt.p, m.part, m.nt,
+                                                m.ntr, ctx->stream));
+            HIPCHK(ctx, launch_robust_terms((double *)ctx->robust_part.p, (int32_t *)ctx->robust_cnt.p, tw, m.nt, m.ntr,
+                                            ctx->stream));
+            HIPCHK(ctx, launch_fir_time<T>(m.resid, e, nullptr, m.w, nullptr, m.b, m.Re, m.nt, m.ntr, nullptr, false,
+                                           ctx->stream));
+        }
+        if ((rc = m.finish(m.resid, &J)) ||
+            (rc = m.per_trace(jtrace_out, (const double *)ctx->robust_part.p + tiles_ntr, nout_out,
+                              (const int32_t *)ctx->robust_cnt.p + tiles_ntr)))
+            return rc;
+        ctx->have_irls = keep != 0;
+        *J_out = J;
+        return FWI_OK;
+    }
+
+    // the lower median of |e|, e as above, per trace or of the whole gather; no residual is left on the device
+    static int residual_median(fwi_ctx *ctx, const T *d_obs, const T *weights, const double *taps, int R, int segment,
+                               double *med_out, int64_t *count_out) {
+        Misfit m(ctx);
+        int rc = m.begin(d_obs, weights, taps, R);
+        if (rc) return rc;
+        const size_t nseg = segment ? 1 : (size_t)m.ntr;
+        if (!m.data) {
+            std::fill(med_out, med_out + nseg, 0.0);
+            std::fill(count_out, count_out + nseg, (int64_t)0);
+            return FWI_OK;
+        }
+        if ((rc = ensure(ctx, ctx->robust_med, nseg * (sizeof(double) + sizeof(int64_t)) + median_all_work()))) return rc;
+        double *med = (double *)ctx->robust_med.p;
+        int64_t *count = (int64_t *)(med + nseg);
+        T *e = (T *)ctx->data_tmp.p;
+        HIPCHK(ctx, launch_fir_time<T>(e, m.syn, m.resid, nullptr, m.w, m.b, m.Re, m.nt, m.ntr, nullptr, false, ctx->stream));
+        if (segment)
+            HIPCHK(ctx, launch_median_all<T>(med, count, count + nseg, e, m.w, (int64_t)m.n, ctx->stream));
+        else
+            HIPCHK(ctx, launch_median_traces<T>(med, count, e, m.w, m.nt, m.ntr, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(med_out, med, nseg * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(count_out, count, nseg * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return FWI_OK;
+    }
+
+    // where the residual on the device lies: per node, or per off-grid point (nullptr: those series were not kept)
+    static void *device_residual(fwi_ctx *ctx) {
+        if (!ctx->rec_sp.npts) return ctx->amp.p;
+        if (ctx->resid_pts_in == fwi_ctx::RESID_PTS_NONE) return nullptr;
+        return ctx->resid_pts_in == fwi_ctx::RESID_PTS_A ? ctx->pts_a.p : ctx->pts_d.p;
+    }
+
+    // device residual := B (W . (B residual)), W the kept IRLS weight: per node, or per off-grid point and scattered
+    static int residual_weight_robust(fwi_ctx *ctx, const double *taps, int R) {
+        const fwi_ctx::SpreadSet &sp = ctx->rec_sp;
+        const int nt = ctx->nt, ntr = sp.npts ? sp.npts : ctx->nrec;
+        if (!ctx->nrec || !nt || !ntr) return FWI_OK;
+        void *resid = device_residual(ctx);
+        if (!resid)
+            return ctx->fail(FWI_ESTATE, "fwi_residual_weight_robust: the residual's per-point series were not kept "
+                                         "(off-grid receivers): weight it on the host");
+        int rc, Re;
+        const T *w;
+        const double *b;
+        if ((rc = data_prepare(ctx, nullptr, taps, R, nt, ntr, &w, &b, &Re))) return rc;
+        HIPCHK(ctx, launch_fir_time<T>((T *)ctx->data_tmp.p, (const T *)resid, nullptr, nullptr, (const T *)ctx->robust_w.p,
+                                       b, Re, nt, ntr, nullptr, false, ctx->stream));
+        HIPCHK(ctx, launch_fir_time<T>((T *)resid, (const T *)ctx->data_tmp.p, nullptr, nullptr, nullptr, b, Re, nt, ntr,
+                                       nullptr, false, ctx->stream));
+        if (sp.npts)
+            HIPCHK(ctx, launch_scatter_series<T>((const T *)resid, (T *)ctx->amp.p, (const int *)sp.owner,
+                                                 (const T *)sp.weight, nt, sp.npts, ctx->nrec, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return FWI_OK;
+    }
 };
 
 }  // namespace
@@ -772,6 +877,56 @@ int fwi_residual_weight(fwi_ctx *ctx, const void *weights, const double *taps, i
                                      "fwi_misfit_weighted leave one; fwi_adjoint uses it up)");
     (void)hipSetDevice(ctx->cfg.device);
     return DISPATCH_CALL(ctx, residual_weight, typed(weights), taps, R);
+}
+
+int fwi_misfit_robust(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R, int32_t kind,
+                      const double *thresh, const double *trace_weights, int32_t keep_irls, double *J_trace_out,
+                      int32_t *nout_out, double *J_out) {
+    const char *who = "fwi_misfit_robust";
+    if (int rc = misfit_callable(ctx, who, d_obs, J_out)) return rc;
+    if (int rc = data_args(ctx, who, taps, R)) return rc;
+    static_assert(FWI_ROBUST_HUBER == ROBUST_HUBER && FWI_ROBUST_HYBRID == ROBUST_HYBRID &&
+                  FWI_ROBUST_CAUCHY == ROBUST_CAUCHY, "include/fwi.h and fwi_robust.h disagree");
+    if (kind != FWI_ROBUST_HUBER && kind != FWI_ROBUST_HYBRID && kind != FWI_ROBUST_CAUCHY)
+        return ctx->fail(FWI_EINVAL, "%s: kind=%d is none of FWI_ROBUST_HUBER, FWI_ROBUST_HYBRID, FWI_ROBUST_CAUCHY", who,
+                         (int)kind);
+    if (ctx->nrec) {
+        if (!thresh) return ctx->fail(FWI_EINVAL, "%s: null thresholds", who);
+        const int ntr = ctx->rec_sp.npts ? ctx->rec_sp.npts : ctx->nrec;
+        for (int j = 0; j < ntr; ++j) {
+            if (!(thresh[j] > 0.0)) return ctx->fail(FWI_EINVAL, "%s: thresh[%d]=%g must be > 0", who, j, thresh[j]);
+            if (std::isinf(thresh[j]) && kind != FWI_ROBUST_HUBER)
+                return ctx->fail(FWI_EINVAL, "%s: thresh[%d] is infinite, which only FWI_ROBUST_HUBER takes", who, j);
+        }
+    }
+    if (int rc = trace_weight_args(ctx, who, trace_weights)) return rc;
+    if (int rc = misfit_synthetics(ctx, who, "or fwi_born ")) return rc;
+    return DISPATCH_CALL(ctx, misfit_robust, typed(d_obs), typed(weights), taps, R, kind, thresh, trace_weights, keep_irls,
+                         J_trace_out, nout_out, J_out);
+}
+
+int fwi_residual_median(fwi_ctx *ctx, const void *d_obs, const void *weights, const double *taps, int32_t R,
+                        int32_t segment, double *med_out, int64_t *count_out) {
+    const char *who = "fwi_residual_median";
+    if (int rc = misfit_callable(ctx, who, d_obs, count_out ? (const void *)med_out : nullptr)) return rc;
+    if (int rc = data_args(ctx, who, taps, R)) return rc;
+    if (segment != 0 && segment != 1)
+        return ctx->fail(FWI_EINVAL, "%s: segment=%d is neither 0 (per trace) nor 1 (the whole gather)", who, (int)segment);
+    if (int rc = misfit_synthetics(ctx, who, "or fwi_born ")) return rc;
+    return DISPATCH_CALL(ctx, residual_median, typed(d_obs), typed(weights), taps, R, segment, med_out, count_out);
+}
+
+int fwi_residual_weight_robust(fwi_ctx *ctx, const double *taps, int32_t R) {
+    if (!ctx) return FWI_EINVAL;
+    if (int rc = data_args(ctx, "fwi_residual_weight_robust", taps, R)) return rc;
+    if (!ctx->have_irls)
+        return ctx->fail(FWI_ESTATE, "fwi_residual_weight_robust: no IRLS weight is held (fwi_misfit_robust with keep_irls "
+                                     "leaves one; the next forward drops it)");
+    if (!ctx->have_dev_residual)
+        return ctx->fail(FWI_ESTATE, "fwi_residual_weight_robust: no residual on the device (fwi_born or a misfit call "
+                                     "leaves one; fwi_adjoint uses it up)");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH_CALL(ctx, residual_weight_robust, taps, R);
 }
 
 }  // extern "C"

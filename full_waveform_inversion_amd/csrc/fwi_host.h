@@ -49,7 +49,8 @@ struct Buf {
     X(tt_part) X(tt_coef) X(tt_lag)                                                                            \
     X(ot_work) X(ot_counts)                                                                                    \
     X(spec_part) X(spec_coef) X(spec_counts) X(spec_fw) X(spec_table)                                          \
-    X(awi_part) X(awi_work) X(awi_counts)
+    X(awi_part) X(awi_work) X(awi_counts)                                                                      \
+    X(robust_part) X(robust_cnt) X(robust_thresh) X(robust_w) X(robust_med)
 #define FWI_DECLARE_BUF(name) Buf name;
 #define FWI_DECLARE_PTR(name) void *name = nullptr;
 
@@ -219,6 +220,11 @@ struct fwi_ctx {
     // traces count; the events around the three phases of the last call (created by the first), fwi_misfit_adaptive_ms
     hipEvent_t awi_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool have_awi_ms = false;
+    // fwi_misfit_robust, fwi_residual_median (fwi_robust.hip): the per-tile sums of rho and the terms per trace, the
+    // counts beyond the threshold likewise, the thresholds, the IRLS weight W = tw M^2 psi(e) of the last call that
+    // kept one (have_irls: it belongs to the forward the context holds; fwi_residual_weight_robust), the medians with
+    // their counts and the whole-gather select's bins
+    bool have_irls = false;
     int spec_table_nt = 0;
     std::vector<double> spec_table_freqs, spec_table_host;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)

@@ -1011,6 +1011,174 @@ class AdaptiveMatching(_PerTrace):
         return float(np.sum(0.5 * tw * W)), self._residual(g, weights)
 
 
+ROBUST_KINDS = ("huber", "hybrid", "cauchy")  # FWI_ROBUST_HUBER, FWI_ROBUST_HYBRID, FWI_ROBUST_CAUCHY
+# the threshold in units of the scale at which each norm keeps 95 % of least squares' efficiency on Gaussian residuals
+# (Huber 1964; Holland & Welsch 1977); the hybrid norm's is the conventional 1
+ROBUST_C = {"huber": 1.345, "hybrid": 1.0, "cauchy": 2.385}
+MAD_TO_SIGMA = 1.4826  # 1 / Phi^-1(3/4): the median of |x| of a Gaussian sample, times this, estimates its sigma
+
+
+def median_abs(e, weights=None, per_trace=True):
+    """``(med, count)``: the lower median of ``|e|`` over the samples that count -- all of them, or with ``weights`` those
+    whose weight is ``> 0`` -- and their number, per trace of the ``(nt, ntr)`` gather (two ``(ntr,)`` arrays) or with
+    ``per_trace=False`` of the whole gather (two numbers).  The lower median is the order statistic ``(count - 1) // 2``,
+    0-based, of ``np.sort``, which puts ``+inf`` and NaN last; ``count == 0`` gives 0.  The twin of
+    ``Engine.residual_median``, which is handed ``d_obs`` and forms ``e = M . B (d_syn - d_obs)`` itself."""
+    a = np.abs(np.asarray(e))
+    if a.ndim != 2:
+        raise ValueError("e must be (nt, ntr)")
+    if not np.issubdtype(a.dtype, np.floating):
+        a = a.astype(np.float64)
+    keep = np.ones(a.shape, bool) if weights is None else np.asarray(weights) > 0
+    if keep.shape != a.shape:
+        raise ValueError("weights have shape %r, the data %r" % (keep.shape, a.shape))
+    if not per_trace:
+        a, keep = a.reshape(-1, 1), keep.reshape(-1, 1)
+    count = np.sum(keep, axis=0).astype(np.int64)
+    # the samples that do not count go behind everything, a NaN that counts included (which NaN is then all the same)
+    s = np.sort(np.where(keep, a, np.nan), axis=0) if a.size else np.zeros((1, a.shape[1]))
+    med = np.where(count > 0, s[np.maximum(count - 1, 0) // 2, np.arange(a.shape[1])], 0.0).astype(np.float64)
+    return (med, count) if per_trace else (float(med[0]), int(count[0]))
+
+
+def mad_scale(e, weights=None, per_trace=True):
+    """``1.4826 *`` the lower median of ``|e|`` (:func:`median_abs`): the scale ``sigma`` of the residuals that a few
+    outliers do not move, per trace or of the whole gather."""
+    return MAD_TO_SIGMA * median_abs(e, weights, per_trace)[0]
+
+
+class RobustMisfit(_PerTrace):
+    """The robust (M-estimator) misfits in fp64 NumPy, ``objective(d_syn, d_obs, weights=None, trace_weights=None) ->
+    (J, r)``, and the ``objective=`` that ``shots.misfit_and_gradient`` and ``shots.gauss_newton_hvp`` recognise (an
+    engine that has ``misfit_robust`` replaces it by the device path; the shot loop hands it ``Shot.weights`` and
+    ``Shot.trace_weights``).  With ``a_j = c sigma_j`` the threshold of trace j::
+
+        e = M . B (s - d)                    (rounded to ``dtype`` once)
+        v = (e / a_j)^2
+        huber :  rho = e^2 / 2 if |e| <= a_j, a_j |e| - a_j^2 / 2 otherwise        psi = min(1, a_j / |e|)
+        hybrid:  rho = e^2 / (1 + sqrt(1 + v))  = a^2 (sqrt(1 + v) - 1)            psi = 1 / sqrt(1 + v)
+        cauchy:  rho = (a_j^2 / 2) log1p(v)                                        psi = 1 / (1 + v)
+        J = sum_j tw_j sum_n rho[n, j]     g = tw_j psi e     r = dJ/ds = B (M . g)
+
+    ``d_obs == d_syn`` gives ``J = 0`` and ``r = 0`` exactly.  ``|d(psi e)/de| <= 1``; huber is C^1 and the other two are
+    smooth (no non-differentiable set); cauchy is NOT convex (``d(psi e)/de = -1/8`` at ``v = 3``).  huber with an
+    infinite threshold is :class:`WeightedL2`, bit for bit.
+
+    ``kind``: one of ``ROBUST_KINDS``.  ``c``: the threshold in units of the scale (None: ``ROBUST_C[kind]``).  ``scale``:
+    the ``sigma`` of the residuals, which MUST NOT depend on the synthetics of the call it is used in (a threshold that
+    did would add a term to the gradient): a float; a sequence indexed like ``shots`` of floats or ``(ntr,)`` arrays
+    (``shots.residual_scales`` measures one at a given model: hold it through a stage); or None, a data-only default,
+    ``1.4826 *`` the lower median of ``|M . B d_obs|`` per trace, which is CRUDE: it is the scale of the data, not of the
+    residuals, and far too large near convergence.  A trace whose scale is 0 (dead, or more than half its samples zero)
+    takes the largest threshold of its gather.  ``taps``, ``dtype`` as in the siblings.
+
+    ``J_trace``, ``nout`` and ``psi`` hold the terms of J per trace, the number of samples beyond the threshold per trace
+    and ``psi(e)`` of the last call; :meth:`normal` is the IRLS Gauss-Newton weight ``B (tw M^2 psi . B x)``
+    (``Engine.residual_weight_robust``'s twin), positive semi-definite for every kind."""
+
+    def __init__(self, kind="huber", c=None, scale=None, taps=None, dtype=None):
+        if kind not in ROBUST_KINDS:
+            raise ValueError("kind must be one of %s" % (ROBUST_KINDS,))
+        c = ROBUST_C[kind] if c is None else float(c)
+        if not (c > 0.0) or (np.isinf(c) and kind != "huber"):
+            raise ValueError("c must be > 0, and finite unless kind is 'huber'")
+        if self._one_number(scale) and not float(scale) > 0.0:
+            raise ValueError("scale must be > 0")
+        self.kind, self.c, self.scale = kind, c, scale
+        self._band(taps, dtype)
+        self.J_trace = self.nout = self.psi = None
+
+    @staticmethod
+    def _one_number(scale):
+        """one scale for every shot (not None, not a sequence indexed like the shots, whose entries may differ in shape)"""
+        return isinstance(scale, (int, float, np.integer, np.floating)) or (isinstance(scale, np.ndarray) and scale.ndim == 0)
+
+    def residuals(self, d_syn, d_obs, weights=None):
+        """``(e, M)``: ``e = M . B (d_syn - d_obs)`` rounded to ``dtype`` once, and the checked weights"""
+        s, d = np.asarray(d_syn, np.float64), np.asarray(d_obs, np.float64)
+        if s.ndim != 2 or s.shape != d.shape:
+            raise ValueError("d_syn %r and d_obs %r must be (nt, ntr) alike" % (s.shape, d.shape))
+        M = WeightedL2._weights(weights, s.shape)
+        e = fir_time(s - d, self.taps)
+        return self._round(e if M is None else M * e), M
+
+    def scale_of(self, i, d_obs=None, weights=None):
+        """the scale of shot ``i``: ``scale``, its entry ``i``, or the data-only default of the class's docstring"""
+        if self.scale is None:
+            if d_obs is None:
+                raise ValueError("the default scale is formed from the observed data")
+            d = np.asarray(d_obs, np.float64)
+            return mad_scale(self.residuals(np.zeros_like(d), d, weights)[0], weights)
+        if self._one_number(self.scale):
+            return float(self.scale)
+        if i is None:
+            raise ValueError("a scale per shot needs the shot's index")
+        return self.scale[i]
+
+    def thresh_of(self, i, d_obs, weights=None):
+        """the ``(ntr,)`` thresholds ``a_j = c sigma_j`` of shot ``i``"""
+        ntr = np.shape(d_obs)[1]
+        with np.errstate(invalid="ignore"):
+            a = self.c * np.broadcast_to(np.asarray(self.scale_of(i, d_obs, weights), np.float64), (ntr,)).copy()
+        if np.any(np.isnan(a)) or np.any(a < 0.0) or (np.any(np.isinf(a)) and self.kind != "huber"):
+            raise ValueError("the scales must be >= 0, and finite unless kind is 'huber'")
+        if np.any(a == 0.0):
+            a[a == 0.0] = np.max(a) if np.any(a > 0.0) else 1.0
+        return a
+
+    engine_method = "misfit_robust"
+
+    def device(self, engine, shot, i, keep_irls=False):
+        return engine.misfit_robust(shot.d_obs, self.kind, self.thresh_of(i, shot.d_obs, shot.weights), shot.weights,
+                                    self.taps, shot.trace_weights, keep_irls=keep_irls)
+
+    def host(self, d_syn, shot, i):
+        return self(d_syn, shot.d_obs, shot.weights, shot.trace_weights, shot=i)
+
+    def irls(self, d_syn, shot, i):
+        """``psi(e)`` of shot ``i`` at these synthetics, for :meth:`normal` (nothing is kept on the objective)"""
+        e, _ = self.residuals(d_syn, shot.d_obs, shot.weights)
+        return self.psi_rho(e, self.thresh_of(i, shot.d_obs, shot.weights))[0]
+
+    def psi_rho(self, e, a):
+        """``(psi, rho)`` of the kind, elementwise; ``a``: the ``(ntr,)`` thresholds"""
+        ae = np.abs(e)
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            if self.kind == "huber":
+                inside = ae <= a
+                psi = np.where(inside, 1.0, a / np.where(inside, 1.0, ae))
+                return psi, np.where(inside, 0.5 * e * e, a * ae - 0.5 * a * a)
+            v = (e / a) ** 2
+            if self.kind == "hybrid":
+                s = np.sqrt(1.0 + v)
+                return 1.0 / s, e * e / (1.0 + s)
+            return 1.0 / (1.0 + v), 0.5 * a * a * np.log1p(v)
+
+    def __call__(self, d_syn, d_obs, weights=None, trace_weights=None, shot=None, thresh=None):
+        e, M = self.residuals(d_syn, d_obs, weights)
+        ntr = e.shape[1]
+        tw = self._trace_weights(trace_weights, ntr)
+        a = self.thresh_of(shot, d_obs, weights) if thresh is None else np.broadcast_to(
+            np.asarray(thresh, np.float64), (ntr,))
+        if not np.all(a > 0.0) or (np.any(np.isinf(a)) and self.kind != "huber"):
+            raise ValueError("thresholds must be > 0, and finite unless kind is 'huber'")
+        psi, rho = self.psi_rho(e, a)
+        g = self._round(tw * (psi * e))
+        self.psi, self.J_trace, self.nout = psi, tw * np.sum(rho, axis=0), np.sum(np.abs(e) > a, axis=0).astype(np.int32)
+        return float(np.sum(tw * rho)), fir_time(g if M is None else M * g, self.taps)
+
+    def normal(self, x, weights=None, trace_weights=None, W=None):
+        """``B (tw M^2 W . B x)`` with ``W = psi(e)`` (None: that of the last call): the IRLS (majoriser) Gauss-Newton
+        weight, symmetric positive semi-definite since ``psi >= 0``"""
+        x = np.asarray(x, np.float64)
+        W = self.psi if W is None else np.asarray(W, np.float64)
+        if W is None or W.shape != x.shape:
+            raise ValueError("no psi(e) of the shape of x: call the objective on this shot first")
+        M = WeightedL2._weights(weights, x.shape)
+        full = self._round(self._trace_weights(trace_weights, x.shape[1]) * (W if M is None else M * M * W))
+        return fir_time(self._round(full * fir_time(x, self.taps)), self.taps)
+
+
 SPECTRAL_KINDS = ("l2", "phase", "logamp", "log")
 
 

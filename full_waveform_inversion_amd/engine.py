@@ -422,6 +422,57 @@ class Engine:
         self._chk(self._lib.fwi_misfit_adaptive_ms(self._c, ms.ctypes.data_as(C.c_void_p)))
         return tuple(float(v) for v in ms)
 
+    def misfit_robust(self, d_obs, kind, thresh, weights=None, taps=None, trace_weights=None, keep_irls=False,
+                      per_trace=False):
+        """Robust (M-estimator) misfit of the last forward's seismograms, which a few spiky traces or a noise burst do
+        not dominate: with ``e = M . B (d_syn - d_obs)`` as in :meth:`misfit_weighted` and ``a_j > 0`` a threshold per
+        trace in the units of the data, ``J = sum_j tw_j sum_n rho(e[n,j]; a_j)`` with ``kind`` ``"huber"``
+        (``e^2 / 2`` up to ``|e| = a``, ``a |e| - a^2 / 2`` beyond), ``"hybrid"`` (``a^2 (sqrt(1 + (e/a)^2) - 1)``) or
+        ``"cauchy"`` (``a^2 / 2 log(1 + (e/a)^2)``, NOT convex).  ``thresh``: the ``ntr`` thresholds, or one number for
+        all; it is ``c`` times a scale of the residuals (``datafit.mad_scale``, :meth:`residual_median`) and must not
+        depend on the synthetics; ``inf`` is huber's alone and makes it :meth:`misfit_weighted`.  ``weights`` and
+        ``taps`` as there, ``trace_weights`` as in :meth:`misfit_correlation`.  The adjoint source ``B (M . tw psi e)``
+        is formed on the device and kept there for ``adjoint(None)``; ``keep_irls=True`` also keeps
+        ``W = tw M^2 psi(e)`` for :meth:`residual_weight_robust`.  Returns J, with ``per_trace=True``
+        ``(J, J_trace, nout)``: the ``ntr`` terms of J and the number of samples of every trace beyond its threshold
+        (``fwi_misfit_robust``; the NumPy twin is :class:`datafit.RobustMisfit`)."""
+        if kind not in _lib.ROBUST_KINDS:
+            raise ValueError("kind must be one of %s" % sorted(_lib.ROBUST_KINDS))
+        a = np.asarray(thresh, dtype=np.float64)
+        a = np.ascontiguousarray(np.broadcast_to(a, (self._nrec,)) if a.ndim == 0 else a)
+        if a.shape != (self._nrec,):
+            raise ValueError("thresh must be one number or one per trace, shape (%d,)" % self._nrec)
+        twp, _keep = self._trace_weights(trace_weights)
+        out, outp = self._per_trace(per_trace, np.float64, np.int32)
+        J = self._misfit(self._lib.fwi_misfit_robust, d_obs, weights, taps,
+                         (_lib.ROBUST_KINDS[kind], a.ctypes.data_as(C.c_void_p), twp, int(bool(keep_irls))) + outp)
+        return (J,) + out if per_trace else J
+
+    def residual_weight_robust(self, taps=None):
+        """The residual on the device (what ``born`` left for ``adjoint(None)``) := ``B (W . (B residual))`` with the
+        ``W = tw M^2 psi(e)`` that ``misfit_robust(keep_irls=True)`` kept on this forward: the IRLS (majoriser)
+        Gauss-Newton weight of :meth:`misfit_robust`, positive semi-definite for every kind
+        (``fwi_residual_weight_robust``; ``FWI_ESTATE`` without a kept ``W``, which the next forward drops)."""
+        _wp, tp, R, _keep = self._data_args(None, taps)
+        self._chk(self._lib.fwi_residual_weight_robust(self._c, tp, R))
+
+    def residual_median(self, d_obs, weights=None, taps=None, per_trace=True):
+        """``(med, count)``: the lower median of ``|e|``, ``e = M . B (d_syn - d_obs)`` of the last forward's
+        seismograms, and the number of samples it is taken over (all, or with ``weights`` those whose weight is
+        ``> 0``), per trace (``ntr`` values) or with ``per_trace=False`` of the whole gather (two numbers).  An exact
+        order statistic, number ``(count - 1) // 2`` in ascending order, found on the device by a radix select; 0 where
+        nothing counts.  ``1.4826 * med`` is the scale of :func:`datafit.mad_scale`.  Leaves no residual on the device;
+        a misfit call can follow on the same forward (``fwi_residual_median``; the NumPy twin is
+        :func:`datafit.median_abs`)."""
+        d_obs = self._host(d_obs, (self._nt, self._nrec))
+        wp, tp, R, _keep = self._data_args(weights, taps)
+        n = self._nrec if per_trace else 1
+        med, count = np.zeros(n), np.zeros(n, np.int64)
+        self._chk(self._lib.fwi_residual_median(self._c, d_obs.ctypes.data_as(C.c_void_p), wp, tp, R,
+                                                0 if per_trace else 1, med.ctypes.data_as(C.c_void_p),
+                                                count.ctypes.data_as(C.c_void_p)))
+        return (med, count) if per_trace else (float(med[0]), int(count[0]))
+
     def misfit_spectral(self, d_obs, freqs, kind="l2", eps=0.0, weights=None, taps=None, freq_weights=None,
                         trace_weights=None, per_pair=False):
         """Frequency-domain (spectral) misfit of the last forward's seismograms: with ``sh = M . B d_syn``,

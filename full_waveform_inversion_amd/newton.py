@@ -73,7 +73,9 @@ def gauss_newton_step(engine, model, shots, g, exchange=None, wrt="velocity", pr
     (``regularizers.regularized_fg``).  None: no such term.
 
     ``objective``: the ``datafit.WeightedL2`` that ``g`` was computed with; every product then carries its weight,
-    ``H_GN = sum_s J_s^T B M_s^2 B J_s`` (``shots.gauss_newton_hvp``).  None: plain least squares."""
+    ``H_GN = sum_s J_s^T B M_s^2 B J_s`` (``shots.gauss_newton_hvp``), or the ``datafit.RobustMisfit``: the weight is then
+    its IRLS one at ``model``, ``B (tw M_s^2 psi(e_s)) B``, positive semi-definite for every kind (each product forms it
+    anew from the shot's residual: one more misfit call per shot, no further sweep).  None: plain least squares."""
     from .shots import _engines, gauss_newton_hvp
     for e in _engines(engine):
         e.set_model(model)

@@ -295,6 +295,43 @@ def model_data(engine, model, shots, exchange=None):
     return shots
 
 
+def residual_scales(engine, model, shots, objective, per_trace=True, exchange=None):
+    """The scale ``sigma`` of every shot's residuals at ``model`` (None: the model the engines hold) for a
+    ``datafit.RobustMisfit(scale=...)``: ``1.4826 *`` the lower median of ``|e|``, ``e = M_s . B (d_syn - d_obs)`` with
+    the shot's ``weights`` and the objective's ``taps``, per trace (an ``(ntr,)`` array per shot) or with
+    ``per_trace=False`` of the whole gather (a float per shot).  One forward per shot, nothing is imaged; where the
+    engine has ``residual_median`` and the shot's data stay on the device the median is an exact order statistic found
+    there, else ``datafit.mad_scale`` of the downloaded synthetics.  Returns the list indexed like ``shots``, complete on
+    every rank.  The scales are NUMBERS of this model: held fixed while the model moves (a ``--bands`` stage, a line
+    search) they add no term to the gradient."""
+    from .datafit import MAD_TO_SIGMA, RobustMisfit, mad_scale
+    ex = exchange or NoExchange()
+    if model is not None:
+        for e in _engines(engine):
+            e.set_model(model)
+    twin = objective if isinstance(objective, RobustMisfit) else RobustMisfit(taps=getattr(objective, "taps", None))
+
+    def one(e, i):
+        s = shots[i]
+        if s.d_obs is None:
+            raise ValueError("shot %d has no observed data on rank %d" % (i, ex.rank))
+        d = s.forward(e, save=False)
+        if hasattr(e, "residual_median") and (s.rec_spread is None or s._on_device(e)):
+            return MAD_TO_SIGMA * np.asarray(e.residual_median(s.d_obs, s.weights, twin.taps, per_trace)[0], np.float64)
+        return np.asarray(mad_scale(twin.residuals(d, s.d_obs, s.weights)[0], s.weights, per_trace), np.float64)
+
+    mine = partition_shots(len(shots), ex.rank, ex.world)
+    got = engine.map_shots(mine, one) if isinstance(engine, EnginePool) else [one(engine, i) for i in mine]
+    # every rank's shots side by side in one array, zeros for the others' shots: the sum over the ranks completes it
+    sizes = [np.shape(s.d_obs)[1] if per_trace else 1 for s in shots]
+    ends = np.cumsum([0] + sizes)
+    flat = np.zeros(ends[-1])
+    for i, v in zip(mine, got):
+        flat[ends[i]:ends[i + 1]] = v
+    flat = ex.reduce_array(flat)
+    return [flat[ends[i]:ends[i + 1]].copy() if per_trace else float(flat[ends[i]]) for i in range(len(shots))]
+
+
 class _Illuminated:
     """Turns illumination on in every engine for one evaluation, and back off afterwards if it was off."""
 
@@ -353,8 +390,8 @@ def misfit_and_gradient(engine, model, shots, exchange=None, wrt="velocity", obj
     (see objectives.py for the reference's similarity measures as misfits).
 
     An objective of :mod:`datafit` -- ``WeightedL2``, ``MatchedL2``, ``EnvelopeL2``, ``NormalizedCorrelation``,
-    ``TraveltimeL2``, ``TransportW2``, ``AdaptiveMatching``, ``SpectralMisfit`` or a subclass of one -- names its own two
-    calls.
+    ``TraveltimeL2``, ``TransportW2``, ``AdaptiveMatching``, ``RobustMisfit``, ``SpectralMisfit`` or a subclass of one --
+    names its own two calls.
     ``objective.host(d_syn, shot, i)`` is the NumPy twin with what its class takes from the shot: ``Shot.weights``, for
     the sums over traces and the spectral misfit ``Shot.trace_weights`` as well, for the matching filter ``shot=i``.
     Under ``device_l2``, an engine that has the
@@ -701,14 +738,39 @@ def misfit_and_gradient_device(engine, model_slot, grad_slot, shots, exchange=No
 def _hvp_sweep(engine, shots, ex, born_one, objective=None, spectral=None):
     """forward(save) + Born + adjoint(imaging) of this rank's shots; ``born_one(e, s, download)`` applies J_s.  With a
     ``datafit.WeightedL2`` objective its weight ``W_s = B M_s^2 B`` acts on the Born data between the two: on the device
-    where the residual stays there and the engine has ``residual_weight``, else through the host twin.  ``spectral``
-    (:class:`_Spectral`): the adjoint is its spectral one."""
-    from .datafit import WeightedL2
-    if objective is not None and not isinstance(objective, WeightedL2):
+    where the residual stays there and the engine has ``residual_weight``, else through the host twin.  With a
+    ``datafit.RobustMisfit`` the weight is the IRLS one at the current model, ``B (tw M^2 psi(e_s)) B``: the objective is
+    evaluated on the forward's synthetics first (``device(..., keep_irls=True)``, which keeps the weight on the device
+    for ``residual_weight_robust``; else the host twin and its ``normal``), so the shots need observed data.
+    ``spectral`` (:class:`_Spectral`): the adjoint is its spectral one."""
+    from .datafit import RobustMisfit, WeightedL2
+    robust = isinstance(objective, RobustMisfit)
+    if objective is not None and not robust and not isinstance(objective, WeightedL2):
         raise ValueError("objective must be a datafit.WeightedL2 (or None: plain least squares)")
+
+    def one_robust(e, s, i):
+        if s.d_obs is None:
+            raise ValueError("shot %d has no observed data on rank %d" % (i, ex.rank))
+        d = s.forward(e, save=True)
+        if s._residual_stays(e) and hasattr(e, "residual_weight_robust"):
+            objective.device(e, s, i, keep_irls=True)
+            born_one(e, s, False)
+            e.residual_weight_robust(objective.taps)
+            r = None
+        else:
+            psi = objective.irls(d, s, i)
+            r = objective.normal(born_one(e, s, True), s.weights, s.trace_weights, psi)
+        if spectral is not None:
+            spectral.adjoint(e, s, r)
+        elif r is None:
+            e.adjoint(None)
+        else:
+            s.adjoint(e, r)
 
     def one(e, i):
         s = shots[i]
+        if robust:
+            return one_robust(e, s, i)
         s.forward(e, save=True)
         if s._residual_stays(e) and (objective is None or hasattr(e, "residual_weight")):
             born_one(e, s, False)
@@ -763,6 +825,9 @@ def gauss_newton_hvp(engine, model, shots, v, exchange=None, wrt="velocity", obj
     store and checkpointing included -- and is today's product, bit for bit, on a plain one.
     OVERWRITES the gradient accumulator of the engine(s) (``reset_gradient`` first, like :func:`misfit_and_gradient`).
     ``model=None`` keeps the model the engines already hold.  The shots need no observed data.
+    With ``objective`` a ``datafit.RobustMisfit`` the weight is its IRLS (majoriser) one at ``model``,
+    ``W_s = B (tw M_s^2 psi(e_s)) B`` with ``e_s`` the shot's residual there: positive semi-definite for every kind, and
+    the shots then DO need their observed data.
 
     Engines that keep the Fourier store (``fourier_freqs`` is not None): J is ``Engine.fourier_born``, the transpose of
     ``adjoint`` on that store; with ``spectral_imaging=True`` the product is ``J_a^T J_a`` through

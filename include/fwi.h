@@ -441,6 +441,69 @@ int fwi_misfit_adaptive(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const v
  * FWI_ESTATE before the first such call with receivers; FWI_EINVAL: a null ms_out. */
 int fwi_misfit_adaptive_ms(fwi_ctx *ctx, double *ms_out /* 3 */);
 
+/* Robust (M-estimator) data misfits on the device: Huber, the hybrid L1/L2 norm and Cauchy.  Every misfit above is
+ * quadratic in what it compares, or a ratio of quadratic sums, so a few spiky traces or a noise burst dominate J and the
+ * adjoint source; these grow linearly (huber, hybrid) or logarithmically (cauchy) beyond a threshold.  With s = d_syn of
+ * the last forward and d = d_obs, both (nt, ntr), B and M of fwi_misfit_weighted, tw_j >= 0 weights per trace and
+ * a_j > 0 a THRESHOLD per trace in the units of the data, the residual amplitude at which the norm leaves least squares
+ * (a caller forms it as a_j = c sigma_j from a scale estimate sigma_j, e.g. 1.4826 times fwi_residual_median's; only a_j
+ * crosses this boundary):
+ *     e = M . B (s - d)                    (fp64, rounded to the context's dtype once, as fwi_misfit_weighted's e)
+ *     v = (e / a_j)^2
+ *     huber :  rho = e^2 / 2 if |e| <= a_j,  a_j |e| - a_j^2 / 2 otherwise          psi = min(1, a_j / |e|)  (1 at e = 0)
+ *     hybrid:  rho = e^2 / (1 + sqrt(1 + v))   (= a^2 (sqrt(1 + v) - 1), written without cancellation)
+ *                                                                                  psi = 1 / sqrt(1 + v)
+ *     cauchy:  rho = (a_j^2 / 2) log1p(v)                                           psi = 1 / (1 + v)
+ *     J = sum_j tw_j sum_n rho[n, j]        g = tw_j psi e        r = dJ/ds = B (M . g)
+ * d_obs == d_syn gives J = 0 and r = 0 exactly, for every kind.  |d(psi e)/de| <= 1 for the three kinds; huber is C^1
+ * and the other two are smooth, so there is no non-differentiable set.  Cauchy's d(psi e)/de reaches -1/8 at v = 3:
+ * CAUCHY IS NOT CONVEX in e.  Huber alone takes a_j = +inf: then psi = 1, and with tw = 1 r is fwi_misfit_weighted's r
+ * bit for bit and J is its J (the same bits where that J is summed from e as stored: an fp64 context, or neither taps
+ * nor weights; otherwise fwi_misfit_weighted sums the unrounded e and the two differ by the rounding of e).  a_j MUST
+ * NOT DEPEND ON s: a threshold that did would add a term to the gradient (the rule of mu in fwi_misfit_matched).
+ * All arithmetic is fp64; g is rounded to the dtype once.  J is summed from the unrounded terms in a fixed order (a
+ * thread's 8 consecutive times ascending, the block's 256 threads by a halving tree, the blocks in a fixed order: the
+ * order of fwi_misfit_weighted), no floating-point atomics: equal inputs give equal bits.  *J_out = J; J_trace_out, if
+ * not NULL, receives the ntr terms tw_j sum_n rho[n, j] (per trace: tiles of 32 times ascending; their sum is J to
+ * round-off, not to the bit), nout_out, if not NULL, the number of samples of every trace with |e| > a_j.
+ * keep_irls != 0 keeps W = tw_j M^2 psi(e), rounded to the dtype, in a buffer of the context for
+ * fwi_residual_weight_robust.  r stays on the device as the residual of the next fwi_adjoint(ctx, NULL, ...).  State
+ * rules, off-grid receivers (per point, then scattered), work buffers and the taps / weights errors as
+ * fwi_misfit_weighted.  FWI_EINVAL, checked on the host before anything is uploaded: an unknown kind, null thresholds
+ * with nrec > 0, a threshold that is <= 0 or NaN, or +inf for a kind other than huber, a trace weight that is negative or
+ * not finite.  No reference counterpart. */
+#define FWI_ROBUST_HUBER 0
+#define FWI_ROBUST_HYBRID 1
+#define FWI_ROBUST_CAUCHY 2
+int fwi_misfit_robust(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                      const double *taps /* R + 1, or NULL */, int32_t R, int32_t kind,
+                      const double *thresh /* ntr: a_j */, const double *trace_weights /* ntr, or NULL */,
+                      int32_t keep_irls, double *J_trace_out /* ntr, or NULL */,
+                      int32_t *nout_out /* ntr, or NULL: samples with |e| > a_j */, double *J_out);
+/* The IRLS (majoriser) Gauss-Newton weight of fwi_misfit_robust: residual := B (W . (B residual)) with the W the last
+ * fwi_misfit_robust(keep_irls) on this forward kept, in place on the residual fwi_born / fwi_born_imaging left on the
+ * device, so that fwi_forward(save), fwi_misfit_robust(keep_irls), fwi_born_imaging, this call, fwi_adjoint(NULL,
+ * image = 1) is H v = J^T B W B J v.  W >= 0, so H is positive semi-definite for every kind, cauchy included: that is
+ * why psi is used and not rho''.  Two filter passes as fwi_residual_weight.  FWI_ESTATE when no W is held (none kept;
+ * the first thing a forward call does is to drop it with the shot before; fwi_destroy frees it) or when no residual is
+ * on the device; FWI_EINVAL: the tap errors of fwi_misfit_weighted.  Synchronises the stream. */
+int fwi_residual_weight_robust(fwi_ctx *ctx, const double *taps /* R + 1, or NULL */, int32_t R);
+/* The lower median of |e|, e as above, on the device: the scale estimate behind a threshold.  segment 0: per trace
+ * (ntr values), 1: of the whole gather (one value).  The samples that count are all of them with weights == NULL, and
+ * those with M[n, j] > 0 otherwise; count_out receives their number per segment and med_out the order statistic
+ * (count - 1) / 2, 0-based, in ascending order of the bit patterns of |e| in the context's dtype with the sign bit
+ * cleared: +inf and NaN sort last, as np.sort puts them, without a special case (the pass that forms e multiplies the 8
+ * times of an aligned group by zero taps, so one non-finite sample of the data makes the e of its group non-finite).
+ * count == 0 gives med = 0.  An exact
+ * order statistic (a radix select, most significant digit first, integer atomics only): the same on every call, no
+ * tolerance.  It leaves NO residual on the device (whatever was there is gone) and keeps the synthetics, so that a misfit
+ * call can follow on the same forward.  State rules, off-grid receivers and tap errors as fwi_misfit_weighted; FWI_EINVAL
+ * also for a null output or a segment that is neither 0 nor 1; a whole gather of more than 2^32 - 1 samples is refused
+ * (FWI_EHIP). */
+int fwi_residual_median(fwi_ctx *ctx, const void *d_obs /* (nt, ntr) */, const void *weights /* (nt, ntr) or NULL */,
+                        const double *taps /* R + 1, or NULL */, int32_t R, int32_t segment,
+                        double *med_out /* ntr, or 1 */, int64_t *count_out /* ntr, or 1 */);
+
 /* Frequency-domain (spectral) data misfit on the device: every misfit above compares traces in the time domain; this
  * one compares their discrete Fourier coefficients at F frequencies of the caller's choice, amplitude and phase together
  * or apart (the logarithmic and phase-only misfits of Shin & Min 2006 and Bednar, Shin & Pyun 2007), with a weight per

@@ -139,6 +139,19 @@ def main():
                          "other misfits")
     ap.add_argument("--adaptive-ridge", type=float, default=None, metavar="LAM",
                     help="the ridge of --adaptive, relative to the energy of each observed trace (default 1e-2)")
+    ap.add_argument("--robust", choices=datafit.ROBUST_KINDS, default=None,
+                    help="robust (M-estimator) misfit of the filtered, weighted residual: quadratic up to a threshold per "
+                         "trace, linear (huber, hybrid) or logarithmic (cauchy, not convex) beyond it, so that spikes and "
+                         "noise bursts do not dominate the gradient (datafit.RobustMisfit, on the device); the threshold is "
+                         "--robust-c times the scale of --robust-scale; composes with --bands and --mute-direct, not with "
+                         "the other misfits")
+    ap.add_argument("--robust-c", type=float, default=None, metavar="C",
+                    help="the threshold of --robust in units of the scale (default 1.345 huber, 1.0 hybrid, 2.385 cauchy)")
+    ap.add_argument("--robust-scale", default=None, metavar="{trace,gather,VALUE}",
+                    help="the scale of --robust: 1.4826 times the median of the absolute residuals per trace (trace, the "
+                         "default) or per shot gather (gather), taken ONCE per --bands stage at that stage's starting "
+                         "model (shots.residual_scales: one more forward per shot and stage) and held through it, or an "
+                         "absolute VALUE in the units of the data")
     ap.add_argument("--spectral", choices=datafit.SPECTRAL_KINDS, default=None,
                     help="frequency-domain misfit on the bins of --spectral-band: 1/2 the sum over frequencies and traces "
                          "of the squared difference of the Fourier coefficients (l2), of their phases (phase), of their "
@@ -236,7 +249,7 @@ def main():
         ap.error("--match-source L must lie in [0, %d]" % datafit.L_MAX)
     if not (a.match_mu_percent >= 0.0 and np.isfinite(a.match_mu_percent)):
         ap.error("--match-mu-percent P must be finite and >= 0")
-    misfits = [flag for flag in ("--adaptive", "--spectral", "--transport", "--traveltime", "--correlation", "--envelope", "--match-source")
+    misfits = [flag for flag in ("--robust", "--adaptive", "--spectral", "--transport", "--traveltime", "--correlation", "--envelope", "--match-source")
                if getattr(a, flag[2:].replace("-", "_")) is not None]
     if len(misfits) > 1:
         ap.error("%s are different misfits: choose one" % " and ".join(misfits))
@@ -244,6 +257,17 @@ def main():
         ap.error("--transport-param needs --transport")
     if a.transport_param is not None and not (a.transport_param > 0.0 and np.isfinite(a.transport_param)):
         ap.error("--transport-param X must be finite and > 0")
+    if (a.robust_c is not None or a.robust_scale is not None) and a.robust is None:
+        ap.error("--robust-c and --robust-scale need --robust")
+    if a.robust_c is not None and not (a.robust_c > 0.0 and np.isfinite(a.robust_c)):
+        ap.error("--robust-c C must be finite and > 0")
+    robust_scale = a.robust_scale or "trace"
+    if robust_scale not in ("trace", "gather"):
+        try:
+            robust_scale = float(robust_scale)
+            assert robust_scale > 0.0 and np.isfinite(robust_scale)
+        except (ValueError, AssertionError):
+            ap.error("--robust-scale takes trace, gather or a finite VALUE > 0")
     if a.adaptive_ridge is not None and a.adaptive is None:
         ap.error("--adaptive-ridge needs --adaptive")
     if a.adaptive_ridge is not None and not (a.adaptive_ridge > 0.0 and np.isfinite(a.adaptive_ridge)):
@@ -350,8 +374,19 @@ def main():
             fw = 1.0 / (power + 1e-4 * float(power.max()))
             imaging["freq_weights"] = fw / float(fw.mean())
 
-    def objective_of(taps):
-        """the misfit of one stage: a fresh object per band (a MatchedL2 keeps the shots' filters of ITS band)"""
+    m0 = w.c_init.astype(np.float32)
+    robust_stages = []  # per stage of --robust: the band and every shot's scale(s), as measured at its starting model
+
+    def objective_of(taps, model=m0, band=None):
+        """the misfit of one stage: a fresh object per band (a MatchedL2 keeps the shots' filters of ITS band, a
+        RobustMisfit the scales measured at ``model``, the stage's starting model)"""
+        if a.robust is not None:
+            scale = robust_scale
+            if not isinstance(scale, float):
+                scale = sh.residual_scales(pool, np.asarray(model, np.float32), shots,
+                                           datafit.RobustMisfit(a.robust, a.robust_c, 1.0, taps), scale == "trace", ex)
+                robust_stages.append({"band_hz": band, "scales": [np.round(np.atleast_1d(v), 9).tolist() for v in scale]})
+            return datafit.RobustMisfit(a.robust, a.robust_c, scale, taps)
         if a.spectral is not None:  # (the floor: a data-only number per shot, datafit.spectral_floor of its d_obs)
             return datafit.SpectralMisfit(w.dt, spectral_freqs, a.spectral, None, taps, freq_weights=spectral_fw,
                                           floor_percent=a.spectral_floor_percent)
@@ -376,7 +411,7 @@ def main():
         out = {i: float(1.0 - f[o.L] ** 2 / max(float(np.sum(f * f)), 1e-300)) for i, f in sorted(o.filters.items())}
         print(json.dumps({"rank": rank, "band_hz": band, "match_filter_energy_outside_lag0": out}), flush=True)
 
-    obj = [objective_of(None)]
+    obj = [None if (bands and a.robust is not None) else objective_of(None)]  # (--bands measures per stage)
     t0 = time.perf_counter()
     evals = [0]
 
@@ -395,7 +430,6 @@ def main():
         first_H.append(H)
         return J, g
 
-    m0 = w.c_init.astype(np.float32)
     ckpt = a.checkpoint if (a.checkpoint and rank == 0) else None  # every rank holds the same state: one writer
     bounds = (0.5 * float(w.c.min()), 1.5 * float(w.c.max()))
     reg_eps = None
@@ -408,7 +442,7 @@ def main():
     mute = sh.source_mute(w.shape, shots, a.mute_sources) if a.mute_sources is not None else None
     if bands:
         def run_band(x, f_hz):  # the device L-BFGS, started afresh: curvature pairs of another band are invalid
-            obj[0] = objective_of(datafit.lowpass_taps(w.dt, f_hz, a.band_halfwidth))
+            obj[0] = objective_of(datafit.lowpass_taps(w.dt, f_hz, a.band_halfwidth), x, f_hz)
 
             def fg_band(xs, gs):
                 evals[0] += 1
@@ -511,6 +545,10 @@ def main():
                           "spectral_whiten": a.spectral_whiten, "fourier_imaging": a.fourier_imaging,
                           "transport": a.transport, "transport_param": a.transport_param,
                           "adaptive_L": a.adaptive, "adaptive_ridge": a.adaptive_ridge,
+                          "robust": a.robust,
+                          "robust_c": (a.robust_c or datafit.ROBUST_C[a.robust]) if a.robust is not None else None,
+                          "robust_scale": a.robust_scale or "trace" if a.robust is not None else None,
+                          "robust_scales": robust_stages if a.robust is not None else None,
                           "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
                           "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
                           "envelope_floor_percent": a.envelope_floor_percent if a.envelope is not None else None,
