@@ -34,6 +34,7 @@ ROBUST_KINDS = {"huber": 0, "hybrid": 1, "cauchy": 2}  # FWI_ROBUST_HUBER, FWI_R
 FOURIER_FMAX, FOURIER_BMAX = 64, 8  # FWI_FOURIER_FMAX, FWI_FOURIER_BMAX
 SPLIT_SAME, SPLIT_OPPOSITE, SPLIT_HILBERT, SPLIT_RMAX = 0, 1, 2, 64  # FWI_SPLIT_*, FWI_SPLIT_RMAX
 SHIFT_SUM_MAX = 64  # FWI_SHIFT_SUM_MAX
+EIKONAL_K = {2: 8, 3: 4}  # inner sweeps per launch of fwi_eikonal* by ndim (EIK_K2, EIK_K3; FWI_EIKONAL_K overrides)
 SPEC_KINDS = {"l2": 0, "phase": 1, "logamp": 2, "log": 3}  # FWI_SPEC_L2, FWI_SPEC_PHASE, FWI_SPEC_LOGAMP, FWI_SPEC_LOG
 UNIQUE_ID_BYTES = 128
 EINVAL = 1
@@ -138,6 +139,11 @@ SIGNATURES = {
     "fwi_vec_smooth": (C.c_int, [_P, _I32, C.POINTER(_D)]),
     "fwi_vec_regularizer": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _D, _D, C.POINTER(_D), _D, C.POINTER(_D)]),
     "fwi_vec_shift_sum": (C.c_int, [_P, _I32, _I32, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_D), _D]),
+    "fwi_vec_scatter_points": (C.c_int, [_P, _I32, _I32, _P, _P, _D]),
+    "fwi_vec_gather_points": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "fwi_eikonal": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, C.POINTER(_I32)]),
+    "fwi_eikonal_adjoint": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
+    "fwi_eikonal_gradient": (C.c_int, [_P, _I32, _I32, _I32, _I32, _D, _I32, _P, _P, _P]),
     "fwi_born": (C.c_int, [_P, _I32, _P, _I32, _P]),
     "fwi_born_vec": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "fwi_born_imaging": (C.c_int, [_P, _I32, _P, _I32, _P]),

@@ -2086,6 +2086,7 @@ void fwi_destroy(fwi_ctx *ctx) {
     FWI_VEC_PTRS(RELEASE_PTR)
     FWI_FOURIER_PTRS(RELEASE_PTR)
     FWI_MISFIT_BUFS(RELEASE_BUF)
+    FWI_EIKONAL_BUFS(RELEASE_BUF)
 #undef RELEASE_BUF
 #undef RELEASE_PTR
     k = 0;

@@ -1,0 +1,260 @@
+// C-ABI of the engine, first-arrival traveltimes (include/fwi.h: fwi_eikonal*, fwi_vec_scatter_points,
+// fwi_vec_gather_points).  Host side only: argument checks, the launch loops of the two block-Jacobi iterations and
+// their stopping rule.  Works on vector slots and the compact velocity; no sweep state is read or written.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <vector>
+
+#include "fwi_eikonal.h"
+#include "fwi_host.h"
+
+namespace {
+
+constexpr int EIK_BATCH = 4;  // launches between two reads of the change flags
+
+// node coordinates (n, ndim) in grid order -> compact indices; FWI_EINVAL for a node outside the grid (and, with
+// `unique`, for one listed twice)
+int compact_nodes(fwi_ctx *ctx, const char *who, const char *what, int64_t n, const int32_t *idx, bool unique,
+                  std::vector<int64_t> &out) {
+    const GridDesc &g = ctx->gd;
+    const int nd = g.ndim;
+    out.resize((size_t)n);
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t *p = idx + k * nd;
+        const int z = p[0], y = nd == 3 ? p[1] : 0, x = p[nd - 1];
+        if (z < 0 || z >= g.nz || y < 0 || y >= g.ny || x < 0 || x >= g.nx)
+            return ctx->fail(FWI_EINVAL, "%s: %s[%lld] lies outside the grid", who, what, (long long)k);
+        out[(size_t)k] = ((int64_t)z * g.ny + y) * g.cx + x;
+    }
+    if (unique && n > 1) {
+        std::vector<int64_t> s(out);
+        std::sort(s.begin(), s.end());
+        if (std::adjacent_find(s.begin(), s.end()) != s.end())
+            return ctx->fail(FWI_EINVAL, "%s: %s names a node twice", who, what);
+    }
+    return FWI_OK;
+}
+
+int inner_sweeps(const fwi_ctx *ctx) {
+    // FWI_EIKONAL_K: inner sweeps per launch (tuning / tests), read at every call
+    const char *e = getenv("FWI_EIKONAL_K");
+    const int k = e ? atoi(e) : 0;
+    return (k >= 1 && k <= EIK_KMAX) ? k : eik_default_k(ctx->gd);
+}
+
+template <typename T>
+struct Impl {
+    // idx -> ctx->eik_idx, values (as T) -> ctx->eik_val
+    static int upload_points(fwi_ctx *ctx, const std::vector<int64_t> &idx, const double *val) {
+        const size_t n = idx.size();
+        int rc = ensure(ctx, ctx->eik_idx, n * sizeof(int64_t));
+        if (rc || (rc = upload_series(ctx, ctx->eik_idx.p, idx.data(), n * sizeof(int64_t)))) return rc;
+        if (!val) return FWI_OK;
+        std::vector<T> v(n);
+        for (size_t k = 0; k < n; ++k) v[k] = (T)val[k];
+        if ((rc = ensure(ctx, ctx->eik_val, n * sizeof(T))) || (rc = upload_series(ctx, ctx->eik_val.p, v.data(), n * sizeof(T))))
+            return rc;
+        return FWI_OK;  // (upload_series has copied v into the context's staging buffer)
+    }
+
+    // Launches `step(in, out, flag)` from `a` into `b` and back until one changes nothing (then a == b on the grid) or
+    // the cap is reached (FWI_ESTATE; the newest iterate is left in a).  The flags are read every EIK_BATCH launches;
+    // the count reported is that of the first launch that changed nothing, whatever the batch.
+    template <typename Step>
+    static int iterate(fwi_ctx *ctx, const char *who, T *a, T *b, int32_t max_sweeps, int32_t *launches_out, Step step) {
+        const GridDesc &g = ctx->gd;
+        const int K = inner_sweeps(ctx);
+        const int64_t cap = max_sweeps > 0 ? max_sweeps : 4 * ((int64_t)g.nz + (g.ndim == 3 ? g.ny : 0) + g.nx);
+        const int64_t max_launches = (cap + K - 1) / K;
+        int rc = ensure(ctx, ctx->eik_flags, EIK_BATCH * sizeof(int));
+        if (rc) return rc;
+        int *flags = (int *)ctx->eik_flags.p;
+        T *in = a, *out = b;
+        int64_t done = 0;
+        while (done < max_launches) {
+            const int nb = (int)std::min<int64_t>(EIK_BATCH, max_launches - done);
+            int host[EIK_BATCH];
+            HIPCHK(ctx, hipMemsetAsync(flags, 0, nb * sizeof(int), ctx->stream));
+            for (int i = 0; i < nb; ++i) {
+                HIPCHK(ctx, step(in, out, K, flags + i));
+                std::swap(in, out);
+            }
+            HIPCHK(ctx, hipMemcpyAsync(host, flags, nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            for (int i = 0; i < nb; ++i)
+                if (!host[i]) {
+                    if (launches_out) *launches_out = (int32_t)(done + i + 1);
+                    return FWI_OK;
+                }
+            done += nb;
+        }
+        if (in != a) HIPCHK(ctx, hipMemcpyAsync(a, in, (size_t)g.npts * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (launches_out) *launches_out = (int32_t)done;
+        return ctx->fail(FWI_ESTATE, "%s: still changing after %lld launches of %d sweeps (max_sweeps = %lld)", who,
+                         (long long)done, K, (long long)cap);
+    }
+
+    static int eikonal(fwi_ctx *ctx, void *vt, void *vs, const std::vector<int64_t> &idx, const double *dist, int64_t ref,
+                       int32_t max_sweeps, int32_t *launches_out) {
+        const GridDesc &g = ctx->gd;
+        T *t = (T *)vt, *sc = (T *)vs;
+        const T *c = (const T *)ctx->c_dev;
+        int rc = upload_points(ctx, idx, dist);
+        if (rc) return rc;
+        HIPCHK(ctx, launch_eikonal_fill<T>(g, t, ctx->stream));
+        HIPCHK(ctx, launch_eikonal_fill<T>(g, sc, ctx->stream));
+        HIPCHK(ctx, launch_eikonal_init<T>(t, sc, c, (const int64_t *)ctx->eik_idx.p, (const T *)ctx->eik_val.p, ref,
+                                           (int)idx.size(), ctx->stream));
+        const double h = ctx->cfg.h;
+        hipStream_t s = ctx->stream;
+        return iterate(ctx, "fwi_eikonal", t, sc, max_sweeps, launches_out, [&](T *in, T *out, int K, int *flag) {
+            return launch_eikonal_sweep<T>(g, in, out, c, h, K, flag, s);
+        });
+    }
+
+    static int adjoint(fwi_ctx *ctx, const void *vt, const void *vb, void *vl, void *vs, int32_t max_sweeps,
+                       int32_t *launches_out) {
+        const GridDesc &g = ctx->gd;
+        const T *t = (const T *)vt, *b = (const T *)vb, *c = (const T *)ctx->c_dev;
+        HIPCHK(ctx, hipMemcpyAsync(vl, vb, (size_t)g.npts * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        const double h = ctx->cfg.h;
+        hipStream_t s = ctx->stream;
+        return iterate(ctx, "fwi_eikonal_adjoint", (T *)vl, (T *)vs, max_sweeps, launches_out,
+                       [&](T *in, T *out, int K, int *flag) {
+                           return launch_eikonal_adjoint_sweep<T>(g, t, b, in, out, c, h, K, flag, s);
+                       });
+    }
+
+    static int gradient(fwi_ctx *ctx, int32_t wrt, const void *vt, const void *vl, void *vo, double beta,
+                        const std::vector<int64_t> &idx, const double *dist, int64_t ref) {
+        int rc = upload_points(ctx, idx, dist);
+        if (rc) return rc;
+        HIPCHK(ctx, launch_eikonal_gradient<T>(ctx->gd, (const T *)vt, (const T *)vl, (const T *)ctx->c_dev, (T *)vo,
+                                               ctx->cfg.h, beta, wrt == FWI_WRT_VELOCITY, (const int64_t *)ctx->eik_idx.p,
+                                               (const T *)ctx->eik_val.p, ref, (int)idx.size(), ctx->stream));
+        return FWI_OK;
+    }
+
+    static int scatter(fwi_ctx *ctx, void *vx, const std::vector<int64_t> &idx, const double *val, double beta) {
+        int rc = idx.empty() ? FWI_OK : upload_points(ctx, idx, val);
+        if (rc) return rc;
+        HIPCHK(ctx, launch_scatter_points<T>((T *)vx, ctx->gd.npts, beta, (const int64_t *)ctx->eik_idx.p,
+                                             (const T *)ctx->eik_val.p, (int)idx.size(), ctx->stream));
+        return FWI_OK;
+    }
+
+    static int gather(fwi_ctx *ctx, const void *vx, const std::vector<int64_t> &idx, double *out) {
+        const size_t n = idx.size();
+        int rc = upload_points(ctx, idx, nullptr);
+        if (rc || (rc = ensure(ctx, ctx->eik_out, n * sizeof(double)))) return rc;
+        HIPCHK(ctx, launch_gather_points<T>((const T *)vx, (const int64_t *)ctx->eik_idx.p, (double *)ctx->eik_out.p,
+                                            (int)n, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(out, ctx->eik_out.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return FWI_OK;
+    }
+};
+
+// the init list of fwi_eikonal / fwi_eikonal_gradient: FWI_EINVAL unless it is non-empty, inside the grid, listed once
+// per node and its distances are finite and >= 0
+int init_list(fwi_ctx *ctx, const char *who, int32_t n, const int32_t *idx, const double *dist, const int32_t *ref,
+              std::vector<int64_t> &nodes, int64_t *ref_out) {
+    if (n < 1) return ctx->fail(FWI_EINVAL, "%s: the init list is empty (n_init = %d)", who, (int)n);
+    if (!idx || !dist || !ref) return ctx->fail(FWI_EINVAL, "%s: null %s", who, !idx ? "init_idx" : !dist ? "init_dist" : "ref_idx");
+    for (int32_t k = 0; k < n; ++k)
+        if (!std::isfinite(dist[k]) || dist[k] < 0.0)
+            return ctx->fail(FWI_EINVAL, "%s: init_dist[%d] = %g must be finite and >= 0", who, (int)k, dist[k]);
+    std::vector<int64_t> r;
+    int rc = compact_nodes(ctx, who, "ref_idx", 1, ref, false, r);
+    if (rc || (rc = compact_nodes(ctx, who, "init_idx", n, idx, true, nodes))) return rc;
+    *ref_out = r[0];
+    return FWI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fwi_vec_scatter_points(fwi_ctx *ctx, int32_t slot, int32_t n, const int32_t *idx, const double *values, double beta) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vx, slot);
+    if (n < 0) return ctx->fail(FWI_EINVAL, "fwi_vec_scatter_points: n = %d must be >= 0", (int)n);
+    if (n > 0 && (!idx || !values)) return ctx->fail(FWI_EINVAL, "fwi_vec_scatter_points: null %s", !idx ? "idx" : "values");
+    if (!std::isfinite(beta)) return ctx->fail(FWI_EINVAL, "fwi_vec_scatter_points: beta = %g must be finite", beta);
+    for (int32_t k = 0; k < n; ++k)
+        if (!std::isfinite(values[k]))
+            return ctx->fail(FWI_EINVAL, "fwi_vec_scatter_points: values[%d] = %g must be finite", (int)k, values[k]);
+    std::vector<int64_t> nodes;
+    int rc = compact_nodes(ctx, "fwi_vec_scatter_points", "idx", n, idx, true, nodes);
+    if (rc) return rc;
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH_CALL(ctx, scatter, vx, nodes, values, beta);
+}
+
+int fwi_vec_gather_points(fwi_ctx *ctx, int32_t slot, int32_t n, const int32_t *idx, double *out) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vx, slot);
+    if (n < 0) return ctx->fail(FWI_EINVAL, "fwi_vec_gather_points: n = %d must be >= 0", (int)n);
+    if (n == 0) return FWI_OK;
+    if (!idx || !out) return ctx->fail(FWI_EINVAL, "fwi_vec_gather_points: null %s", !idx ? "idx" : "out");
+    std::vector<int64_t> nodes;
+    int rc = compact_nodes(ctx, "fwi_vec_gather_points", "idx", n, idx, false, nodes);
+    if (rc) return rc;
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH_CALL(ctx, gather, vx, nodes, out);
+}
+
+int fwi_eikonal(fwi_ctx *ctx, int32_t t_slot, int32_t scratch_slot, int32_t n_init, const int32_t *init_idx,
+                const double *init_dist, const int32_t *ref_idx, int32_t max_sweeps, int32_t *launches_out) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vt, t_slot);
+    VEC_OR_FAIL(ctx, vs, scratch_slot);
+    if (vt == vs) return ctx->fail(FWI_EINVAL, "fwi_eikonal: scratch_slot is t_slot (slot %d)", (int)t_slot);
+    std::vector<int64_t> nodes;
+    int64_t ref = 0;
+    int rc = init_list(ctx, "fwi_eikonal", n_init, init_idx, init_dist, ref_idx, nodes, &ref);
+    if (rc) return rc;
+    if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_eikonal: no model set");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH_CALL(ctx, eikonal, vt, vs, nodes, init_dist, ref, max_sweeps, launches_out);
+}
+
+int fwi_eikonal_adjoint(fwi_ctx *ctx, int32_t t_slot, int32_t rhs_slot, int32_t lam_slot, int32_t scratch_slot,
+                        int32_t max_sweeps, int32_t *launches_out) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vt, t_slot);
+    VEC_OR_FAIL(ctx, vb, rhs_slot);
+    VEC_OR_FAIL(ctx, vl, lam_slot);
+    VEC_OR_FAIL(ctx, vs, scratch_slot);
+    if (vt == vb || vt == vl || vt == vs || vb == vl || vb == vs || vl == vs)
+        return ctx->fail(FWI_EINVAL, "fwi_eikonal_adjoint: t, rhs, lam and scratch must be four different slots "
+                         "(got %d, %d, %d, %d)", (int)t_slot, (int)rhs_slot, (int)lam_slot, (int)scratch_slot);
+    if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_eikonal_adjoint: no model set");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH_CALL(ctx, adjoint, vt, vb, vl, vs, max_sweeps, launches_out);
+}
+
+int fwi_eikonal_gradient(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t lam_slot, int32_t out_slot, double beta,
+                         int32_t n_init, const int32_t *init_idx, const double *init_dist, const int32_t *ref_idx) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vt, t_slot);
+    VEC_OR_FAIL(ctx, vl, lam_slot);
+    VEC_OR_FAIL(ctx, vo, out_slot);
+    if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
+        return ctx->fail(FWI_EINVAL, "fwi_eikonal_gradient: unknown parametrisation %d", (int)wrt);
+    if (vo == vt || vo == vl)
+        return ctx->fail(FWI_EINVAL, "fwi_eikonal_gradient: out (slot %d) must not alias %s", (int)out_slot,
+                         vo == vt ? "t" : "lam");
+    if (!std::isfinite(beta)) return ctx->fail(FWI_EINVAL, "fwi_eikonal_gradient: beta = %g must be finite", beta);
+    std::vector<int64_t> nodes;
+    int64_t ref = 0;
+    int rc = init_list(ctx, "fwi_eikonal_gradient", n_init, init_idx, init_dist, ref_idx, nodes, &ref);
+    if (rc) return rc;
+    if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_eikonal_gradient: no model set");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH_CALL(ctx, gradient, wrt, vt, vl, vo, beta, nodes, init_dist, ref);
+}
+
+}  // extern "C"

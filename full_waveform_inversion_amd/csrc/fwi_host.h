@@ -1,4 +1,4 @@
-// What the host units of the C ABI share (fwi_api.hip and fwi_api_{misfit,fourier,vec,comm}.hip): the context, the
+// What the host units of the C ABI share (fwi_api.hip and fwi_api_{misfit,fourier,vec,eikonal,comm}.hip): the context, the
 // error and dispatch macros, and the few helpers that cross from one unit into another.  Private, like the launch
 // headers; whatever a single unit uses stays in that unit.
 #pragma once
@@ -51,6 +51,7 @@ struct Buf {
     X(spec_part) X(spec_coef) X(spec_counts) X(spec_fw) X(spec_table)                                          \
     X(awi_part) X(awi_work) X(awi_counts)                                                                      \
     X(robust_part) X(robust_cnt) X(robust_thresh) X(robust_w) X(robust_med)
+#define FWI_EIKONAL_BUFS(X) X(eik_idx) X(eik_val) X(eik_out) X(eik_flags)
 #define FWI_DECLARE_BUF(name) Buf name;
 #define FWI_DECLARE_PTR(name) void *name = nullptr;
 
@@ -225,6 +226,9 @@ struct fwi_ctx {
     // kept one (have_irls: it belongs to the forward the context holds; fwi_residual_weight_robust), the medians with
     // their counts and the whole-gather select's bins
     bool have_irls = false;
+    // fwi_eikonal*, fwi_vec_scatter_points, fwi_vec_gather_points (fwi_eikonal.hip): the compact indices and the values
+    // of the point list of the running call, the gathered values, the change flags of a batch of launches
+    FWI_EIKONAL_BUFS(FWI_DECLARE_BUF)
     int spec_table_nt = 0;
     std::vector<double> spec_table_freqs, spec_table_host;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)

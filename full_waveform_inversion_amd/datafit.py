@@ -1376,11 +1376,41 @@ def offset_time_mute(shot, h, dt, v_fast, t_pad=0.0, taper=0):
     src, rec = np.atleast_2d(src), np.atleast_2d(rec)
     nt = np.asarray(shot.wavelet if shot.point_wavelet is None else shot.point_wavelet).shape[0]
     off = float(h) * np.sqrt(np.sum((rec - src[0]) ** 2, axis=1))
-    s = np.arange(nt, dtype=np.float64)[:, None] - (off / float(v_fast) + float(t_pad))[None, :] / float(dt)
+    return first_arrival_mute(off / float(v_fast), nt, dt, t_pad, taper)
+
+
+def first_arrival_mute(times, nt, dt, t_pad=0.0, taper=0):
+    """:func:`offset_time_mute` with a first-arrival time per trace in place of ``offset / v_fast`` -- picks
+    (:func:`first_breaks`) or eikonal times (``Engine.eikonal_times``): weights ``(nt, ntr)`` that are 0 for
+    ``t < times + t_pad``, then a raised cosine over ``taper`` samples, 1 after it.  A NaN time mutes its whole trace."""
+    times = np.asarray(times, np.float64).reshape(-1)
+    if not float(dt) > 0.0 or int(taper) < 0 or int(nt) < 1:
+        raise ValueError("dt must be > 0, nt >= 1 and taper >= 0")
+    s = np.arange(int(nt), dtype=np.float64)[:, None] - (times + float(t_pad))[None, :] / float(dt)
     if int(taper) == 0:
         return (s >= 0.0).astype(np.float64)
     w = 0.5 * (1.0 - np.cos(np.pi * np.clip(s / int(taper), 0.0, 1.0)))
-    return np.where(s >= int(taper), 1.0, w)
+    return np.where(np.isnan(s), 0.0, np.where(s >= int(taper), 1.0, w))
+
+
+def first_breaks(d, dt, fraction=0.1):
+    """First-break picks of the traces ``d`` ``(nt, ntr)``: per trace the time at which ``|d|`` first reaches ``fraction``
+    (in (0, 1]) of the trace's maximum of ``|d|``, interpolated linearly between the last sample below the threshold and
+    the first one at or above it.  NaN for a dead trace (all zeros, or anything not finite)."""
+    d = np.abs(np.asarray(d, np.float64))
+    if d.ndim == 1:
+        d = d[:, None]
+    if d.ndim != 2 or not 0.0 < float(fraction) <= 1.0 or not float(dt) > 0.0:
+        raise ValueError("d must be (nt, ntr), 0 < fraction <= 1 and dt > 0")
+    peak = d.max(axis=0)
+    live = np.isfinite(peak) & (peak > 0.0)
+    thr = np.where(live, float(fraction) * peak, np.inf)
+    k = np.argmax(d >= thr[None, :], axis=0)  # the first sample at or above the threshold (0 for dead traces)
+    cols = np.arange(d.shape[1])
+    hi, lo = d[k, cols], d[np.maximum(k - 1, 0), cols]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        frac = np.where((k > 0) & (hi > lo), (thr - lo) / (hi - lo), 1.0)  # position between sample k - 1 and k
+    return np.where(live, (k - 1 + frac) * float(dt), np.nan)
 
 
 def frequency_continuation(run_band, x0, bands, taps_of=None):

@@ -1,0 +1,340 @@
+"""First-arrival traveltimes on the engine's grid and their discrete adjoint: the NumPy twin of ``fwi_eikonal*`` and the
+DEFINITION of what those calls compute.
+
+``|grad T| = s``, ``s = 1 / c``, by the first-order Godunov upwind scheme.  For cell ``i`` and axis ``d``,
+``t_d = min(T[i - e_d], T[i + e_d])`` (a neighbour outside the grid counts as ``+inf``; on a tie the lower-index one is
+"the" upwind neighbour).  With the ``t_d`` sorted ``a <= b <= c`` and ``f = s_i h``, the local solution ``G_i`` is
+
+    a + f                                               if that is <= b,
+    a + (b' + sqrt(2 f^2 - b'^2)) / 2                   else, if that is <= c   (b' = b - a; the last case in 2-D),
+    a + (S + sqrt(S^2 - 3 (Q - f^2))) / 3               else                    (S = b' + c', Q = b'^2 + c'^2, c' = c - a),
+
+the usual roots ``(a + b + sqrt(2 f^2 - (a - b)^2)) / 2`` and ``(S + sqrt(S^2 - 3 (Q - f^2))) / 3`` written with the
+smallest time taken out, so that the square root's argument is formed from differences of the order of ``f`` and not
+from squares of whole traveltimes.  The source is an init list (nodes, their distances ``d_i`` in metres and one
+reference node): ``T_init = s_ref d_i`` on the listed nodes, ``+inf`` elsewhere, and the solution is the limit of
+``T <- min(T, T_init, G(T))`` from ``+inf``.  There is no mask: a listed node is *source-determined* exactly when its
+final ``T_i < G_i``.
+
+The adjoint differentiates that fixed point.  With the active axes ``D = {d : t_d < T_i}``,
+
+    dG_i/dt_d = (T_i - t_d) / sum_{e in D} (T_i - t_e),      dG_i/ds_i = s_i h^2 / sum_{e in D} (T_i - t_e),
+
+both zero where ``T_i < G_i``; ``lambda = b + A^T lambda`` with ``A_ij = dG_i/dT_j`` (strictly causal, so the Jacobi
+iteration stops bit-exactly), ``g_s = (dG/ds) lambda`` plus ``sum_i d_i lambda_i`` over the source-determined listed
+nodes at ``ref``.
+
+Out of scope: the factored eikonal equation, second-order stencils, anisotropy and later arrivals.  The scheme is first
+order: 0.3 - 1.2 % of ``max T`` on 101^2 - 401^2 grids (the table in DESIGN.md), most of it from the source's
+neighbourhood, which a ball of a few cells (``radius``) reduces.
+
+No reference counterpart.
+"""
+from __future__ import annotations
+
+import itertools
+
+import numpy as np
+
+WRT = ("velocity", "slowness2")
+
+
+def ball(coords, shape, h, radius=0.0):
+    """The init list of a source at fractional grid coordinates ``coords`` (cells): ``(idx (n, ndim) int32, dist (n,)
+    float64 metres, ref (ndim,) int32)``.  Every node within ``radius`` cells is listed, in ascending flat order; at
+    ``radius`` 0 the nearest node alone.  ``ref`` is the nearest node, the lowest index on a tie."""
+    shape = tuple(int(n) for n in shape)
+    x = np.asarray(coords, np.float64).reshape(-1)
+    if x.size != len(shape):
+        raise ValueError("coords must hold %d coordinates, got %r" % (len(shape), np.shape(coords)))
+    if np.any(x < 0.0) or np.any(x > np.array(shape) - 1.0):
+        raise ValueError("the source must lie inside the grid [0, n - 1] on every axis")
+    if not (np.isfinite(radius) and radius >= 0.0):
+        raise ValueError("radius = %r must be finite and >= 0" % (radius,))
+    R = float(radius) + 1.0  # the nearest node is at most sqrt(ndim) / 2 < 1 away
+    rng = [np.arange(max(0, int(np.floor(x[d] - R))), min(shape[d] - 1, int(np.ceil(x[d] + R))) + 1)
+           for d in range(len(shape))]
+    nodes = np.array(list(itertools.product(*rng)), dtype=np.int64).reshape(-1, len(shape))  # ascending flat order
+    r = np.sqrt(((nodes - x) ** 2).sum(axis=1))
+    ref = int(np.argmin(r))  # the first of equal minima: the lowest index
+    keep = r <= float(radius)
+    keep[ref] = True
+    return (np.ascontiguousarray(nodes[keep], dtype=np.int32), np.ascontiguousarray(r[keep] * float(h)),
+            np.ascontiguousarray(nodes[ref], dtype=np.int32))
+
+
+def _source(src, shape, h, radius):
+    """``src`` as an init list: already one (a 3-tuple), or coordinates for :func:`ball`"""
+    if isinstance(src, tuple) and len(src) == 3 and np.ndim(src[0]) == 2:
+        idx, dist, ref = src
+        return (np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(dist, dtype=np.float64),
+                np.ascontiguousarray(np.reshape(ref, -1), dtype=np.int32))
+    return ball(src, shape, h, radius)
+
+
+def _shift(T, d, k, fill):
+    """``T[i + k e_d]``, ``fill`` outside the grid"""
+    out = np.full_like(T, fill)
+    n = T.shape[d]
+    src = [slice(None)] * T.ndim
+    dst = [slice(None)] * T.ndim
+    if k > 0:
+        src[d], dst[d] = slice(k, n), slice(0, n - k)
+    else:
+        src[d], dst[d] = slice(0, n + k), slice(-k, n)
+    out[tuple(dst)] = T[tuple(src)]
+    return out
+
+
+def upwind(T):
+    """Per axis ``(t_d, lower)``: the smaller neighbour's time and whether it is the lower-index one (ties: yes)"""
+    out = []
+    for d in range(T.ndim):
+        lo, hi = _shift(T, d, -1, np.inf), _shift(T, d, +1, np.inf)
+        out.append((np.minimum(lo, hi), lo <= hi))
+    return out
+
+
+def local_solution(t, f):
+    """``G`` from the per-axis upwind times ``t`` (a list of ndim arrays) and ``f = s h``, in their dtype"""
+    two, three = f.dtype.type(2), f.dtype.type(3)
+    srt = np.sort(np.stack(t), axis=0)
+    a, b = srt[0], srt[1]
+    c = srt[2] if len(t) == 3 else np.full_like(a, np.inf)
+    with np.errstate(invalid="ignore", over="ignore"):
+        x1 = a + f
+        bp = b - a
+        x2 = a + (bp + np.sqrt(two * f * f - bp * bp)) / two
+        cp = c - a
+        S, Q = bp + cp, bp * bp + cp * cp
+        x3 = a + (S + np.sqrt(S * S - three * (Q - f * f))) / three
+    return np.where(x1 <= b, x1, np.where(x2 <= c, x2, x3))
+
+
+def _slowness(c, dtype):
+    c = np.asarray(c, dtype=dtype)
+    return dtype.type(1) / c
+
+
+def init_times(c, h, init, dtype=np.float64):
+    """``T_init``: ``s_ref d_i`` on the listed nodes, ``+inf`` elsewhere"""
+    dtype = np.dtype(dtype)
+    idx, dist, ref = init
+    s = _slowness(c, dtype)
+    T0 = np.full(s.shape, np.inf, dtype)
+    T0[tuple(idx.T)] = s[tuple(ref)] * dist.astype(dtype)
+    return T0
+
+
+def sweep(T, s, h):
+    """One Jacobi sweep ``min(T, G(T))`` (``T_init`` is in ``T`` from the start and ``min`` keeps it)"""
+    f = s * s.dtype.type(h)
+    return np.minimum(T, local_solution([t for t, _ in upwind(T)], f))
+
+
+def solve(c, h, src, radius=0.0, dtype=np.float64, max_sweeps=None, return_sweeps=False):
+    """First-arrival times of the model ``c`` (m/s) for the source ``src`` (coordinates in cells, or an init list):
+    plain Jacobi from ``+inf`` until a sweep changes no bit."""
+    dtype = np.dtype(dtype)
+    c = np.asarray(c)
+    init = _source(src, c.shape, h, radius)
+    s = _slowness(c, dtype)
+    T = init_times(c, h, init, dtype)
+    cap = 4 * sum(c.shape) if max_sweeps is None else int(max_sweeps)
+    for n in range(1, cap + 1):
+        Tn = sweep(T, s, h)
+        if np.array_equal(Tn, T):
+            return (T, n) if return_sweeps else T
+        T = Tn
+    raise RuntimeError("eikonal.solve: no fixed point after %d sweeps" % cap)
+
+
+def solve_blocks(c, h, src, radius=0.0, tile=8, inner=4, dtype=np.float64):
+    """The same fixed point by block Jacobi, as the device runs it: per outer step every ``tile``-cell block takes
+    ``inner`` sweeps with the cells around it frozen, all blocks reading the same input.  Returns ``(T, outer steps)``."""
+    dtype = np.dtype(dtype)
+    c = np.asarray(c)
+    init = _source(src, c.shape, h, radius)
+    s = _slowness(c, dtype)
+    T = init_times(c, h, init, dtype)
+    f = s * dtype.type(h)
+    nd = c.ndim
+    for n in range(1, 4 * sum(c.shape) + 1):
+        Tn = T.copy()
+        for org in itertools.product(*[range(0, m, tile) for m in c.shape]):
+            lo = [max(0, o - 1) for o in org]
+            hi = [min(m, o + tile + 1) for o, m in zip(org, c.shape)]
+            box = tuple(slice(a, b) for a, b in zip(lo, hi))
+            own = tuple(slice(o - a, min(o + tile, m) - a) for o, a, m in zip(org, lo, c.shape))
+            P = np.full([b - a + 2 for a, b in zip(lo, hi)], np.inf, dtype)  # the box with +inf around it
+            ins = tuple(slice(1, -1) for _ in range(nd))
+            P[ins] = T[box]
+            F = np.ones(P.shape, dtype)
+            F[ins] = f[box]
+            keep = np.ones(P.shape, bool)  # everything but the block's own cells is frozen
+            keep[tuple(slice(o.start + 1, o.stop + 1) for o in own)] = False
+            for _ in range(inner):
+                Pn = np.minimum(P, local_solution([t for t, _ in upwind(P)], F))
+                P = np.where(keep, P, Pn)
+            Tn[tuple(slice(o, min(o + tile, m)) for o, m in zip(org, c.shape))] = P[ins][own]
+        if np.array_equal(Tn, T):
+            return T, n
+        T = Tn
+    raise RuntimeError("eikonal.solve_blocks: no fixed point")
+
+
+def derivatives(T, c, h):
+    """At the fixed point ``T``: ``(W, lower, dGds)`` with ``W[d] = dG_i/dt_d`` (0 on inactive axes and where
+    ``T_i < G_i``), ``lower[d]`` whether the upwind neighbour on axis ``d`` is the lower-index one, and ``dG_i/ds_i``."""
+    dtype = T.dtype
+    s = _slowness(c, dtype)
+    hh = dtype.type(h)
+    up = upwind(T)
+    G = local_solution([t for t, _ in up], s * hh)
+    live = np.isfinite(T) & ~(T < G)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        diff = [np.where(live & (t < T), T - t, dtype.type(0)) for t, _ in up]
+        den = diff[0]
+        for x in diff[1:]:
+            den = den + x
+        ok = den > 0
+        W = [np.where(ok, x / den, dtype.type(0)) for x in diff]
+        dGds = np.where(ok, s * hh * hh / den, dtype.type(0))
+    return W, [lo for _, lo in up], dGds
+
+
+def adjoint_sweep(lam, b, W, lower):
+    """``b + A^T lam`` in gather form, the terms of a cell added axis by axis, lower neighbour first"""
+    zero = lam.dtype.type(0)
+    out = b.copy()
+    for d in range(lam.ndim):
+        # cell i = j - e_d hands lam_i to j when its upwind neighbour on d is the upper one; i = j + e_d when the lower
+        out = out + _shift(np.where(lower[d], zero, W[d] * lam), d, -1, zero)
+        out = out + _shift(np.where(lower[d], W[d] * lam, zero), d, +1, zero)
+    return out
+
+
+def adjoint(T, c, h, b, return_sweeps=False):
+    """``lambda = b + A^T lambda`` by Jacobi from ``lambda = b``, recomputed in full until a sweep changes no bit"""
+    W, lower, _ = derivatives(T, c, h)
+    b = np.asarray(b, dtype=T.dtype)
+    lam = b.copy()
+    for n in range(1, 4 * sum(T.shape) + 1):
+        ln = adjoint_sweep(lam, b, W, lower)
+        if np.array_equal(ln, lam):
+            return (lam, n) if return_sweeps else lam
+        lam = ln
+    raise RuntimeError("eikonal.adjoint: no fixed point")
+
+
+def adjoint_matrix(T, c, h):
+    """The dense ``A`` (``A[i, j] = dG_i/dT_j``, flat indices) of a SMALL grid, for tests"""
+    W, lower, _ = derivatives(T, c, h)
+    n = T.size
+    A = np.zeros((n, n))
+    flat = np.arange(n).reshape(T.shape)
+    for d in range(T.ndim):
+        for i in np.ndindex(*T.shape):
+            if W[d][i] != 0:
+                j = list(i)
+                j[d] += -1 if lower[d][i] else 1
+                A[flat[i], flat[tuple(j)]] = W[d][i]
+    return A
+
+
+def gradient(T, lam, c, h, init, wrt="velocity", ball_term=True):
+    """The gradient of ``sum_i b_i T_i`` with respect to the model: ``g_s = (dG/ds) lambda`` plus the source term at
+    ``ref``, then ``g_c = -g_s / c^2`` (``wrt="velocity"``) or ``g_m = g_s c / 2`` (``"slowness2"``, ``m = 1 / c^2``)"""
+    if wrt not in WRT:
+        raise ValueError("wrt must be one of %r" % (WRT,))
+    dtype = T.dtype
+    c = np.asarray(c, dtype=dtype)
+    _, _, dGds = derivatives(T, c, h)
+    gs = dGds * lam
+    if ball_term:
+        idx, dist, ref = init
+        s = _slowness(c, dtype)
+        G = local_solution([t for t, _ in upwind(T)], s * dtype.type(h))
+        acc = dtype.type(0)
+        for k in range(len(dist)):  # in list order, as the device's one thread
+            i = tuple(idx[k])
+            if T[i] < G[i]:
+                acc = acc + dtype.type(dist[k]) * lam[i]
+        gs[tuple(ref)] += acc
+    return -gs / (c * c) if wrt == "velocity" else gs * c / dtype.type(2)
+
+
+def times_at(T, rec):
+    """Times at receivers: node indices ``(n, ndim)`` or a ``points.Spread`` (multilinear weights)"""
+    if hasattr(rec, "pt_start"):
+        v = T[tuple(np.asarray(rec.idx).T)].astype(np.float64) * rec.weights
+        return np.add.reduceat(v, rec.pt_start[:-1]) if len(v) else np.zeros(0)
+    return T[tuple(np.asarray(rec, dtype=np.int64).reshape(-1, T.ndim).T)].astype(np.float64)
+
+
+def exact_constant(shape, h, c0, coords):
+    """``s r`` of a constant medium"""
+    ax = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij")
+    r = np.sqrt(sum((a - x) ** 2 for a, x in zip(ax, np.asarray(coords, np.float64)))) * h
+    return r / c0
+
+
+def exact_gradient(shape, h, c0, g, coords):
+    """``acosh(1 + g^2 r^2 / (2 c c0)) / g`` of ``c = c0 + g (z - z_src)``, depth the first axis; ``c0`` the velocity at
+    the source"""
+    x = np.asarray(coords, np.float64)
+    ax = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij")
+    r2 = sum((a - xs) ** 2 for a, xs in zip(ax, x)) * h * h
+    c = c0 + g * (ax[0] - x[0]) * h
+    return np.arccosh(1.0 + g * g * r2 / (2.0 * c * c0)) / g
+
+
+class TwinEngine:
+    """The five engine calls ``shots.traveltime_fg`` needs, backed by this module on the CPU (tests, prototypes): model
+    and slots are host arrays."""
+
+    def __init__(self, shape, h, dtype=np.float64):
+        self.shape, self.h, self.dtype = tuple(shape), float(h), np.dtype(dtype)
+        self.ndim = len(self.shape)
+        self.c = None
+        self.vecs = []
+        self.last_eikonal_launches = 0
+        self._init = {}
+
+    def set_model(self, model):
+        self.c = np.array(model, dtype=self.dtype).reshape(self.shape)
+
+    def vec_create(self, count):
+        self.vecs = [np.zeros(self.shape, self.dtype) for _ in range(count)]
+
+    def vec_download(self, slot):
+        return self.vecs[slot].copy()
+
+    def vec_upload(self, slot, a):
+        self.vecs[slot] = np.array(a, dtype=self.dtype).reshape(self.shape)
+
+    def eikonal(self, src, t_slot, scratch_slot, radius=0.0, max_sweeps=None):
+        init = _source(src, self.shape, self.h, radius)
+        self.vecs[t_slot], self.last_eikonal_launches = solve(self.c, self.h, init, dtype=self.dtype,
+                                                              max_sweeps=max_sweeps, return_sweeps=True)
+        self._init[t_slot] = init
+        return init
+
+    def eikonal_times(self, t_slot, rec):
+        return times_at(self.vecs[t_slot], rec)
+
+    def vec_scatter_points(self, slot, idx, values, beta=0.0):
+        a = self.dtype.type(beta) * self.vecs[slot] if beta != 0.0 else np.zeros(self.shape, self.dtype)
+        a[tuple(np.asarray(idx).reshape(-1, self.ndim).T)] += np.asarray(values, dtype=self.dtype)
+        self.vecs[slot] = a
+
+    def vec_gather_points(self, slot, idx):
+        return self.vecs[slot][tuple(np.asarray(idx).reshape(-1, self.ndim).T)].astype(np.float64)
+
+    def eikonal_adjoint(self, t_slot, rhs_slot, lam_slot, scratch_slot, max_sweeps=None):
+        self.vecs[lam_slot], self.last_eikonal_launches = adjoint(self.vecs[t_slot], self.c, self.h, self.vecs[rhs_slot],
+                                                                  return_sweeps=True)
+
+    def eikonal_gradient(self, t_slot, lam_slot, out_slot, init, beta=0.0, wrt="velocity"):
+        g = gradient(self.vecs[t_slot], self.vecs[lam_slot], self.c, self.h, init, wrt)
+        self.vecs[out_slot] = g if beta == 0.0 else self.dtype.type(beta) * self.vecs[out_slot] + g

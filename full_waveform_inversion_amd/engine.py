@@ -1106,6 +1106,84 @@ class Engine:
         e = np.array([self.vec_dot(s, s) for s in slots])
         return float(np.sum(np.abs(lags) ** power * e)), float(np.sum(e))
 
+    # -- values at nodes, first-arrival traveltimes (fwi_eikonal*; the twin and definition is eikonal.py) -----------
+    def _nodes(self, idx):
+        idx = self._idx(idx)
+        return idx, idx.ctypes.data_as(C.c_void_p)
+
+    def vec_scatter_points(self, slot, idx, values, beta=0.0):
+        """Slot ``:= beta slot``, then ``slot[idx_k] += values[k]`` for the unique nodes ``idx`` ``(n, ndim)``, on the
+        device: NumPy's ``a = beta * a; a[idx] += values`` in the engine's dtype, bit for bit."""
+        idx, pidx = self._nodes(idx)
+        v = np.ascontiguousarray(np.atleast_1d(values), dtype=np.float64)
+        if v.shape != (len(idx),):
+            raise _lib.FwiError(_lib.EINVAL, "vec_scatter_points: one value per node, got %r for %d nodes"
+                                % (v.shape, len(idx)))
+        self._chk(self._lib.fwi_vec_scatter_points(self._c, int(slot), len(idx), pidx, v.ctypes.data_as(C.c_void_p),
+                                                   float(beta)))
+
+    def vec_gather_points(self, slot, idx):
+        """``slot[idx_k]`` as float64, gathered on the device (nothing model-sized crosses)."""
+        idx, pidx = self._nodes(idx)
+        out = np.empty(len(idx), np.float64)
+        self._chk(self._lib.fwi_vec_gather_points(self._c, int(slot), len(idx), pidx, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    last_eikonal_launches = 0  # launches of the latest eikonal / eikonal_adjoint call (also when it hit the cap)
+
+    def _init_args(self, init):
+        idx, dist, ref = init
+        idx = self._idx(idx)
+        dist = np.ascontiguousarray(np.atleast_1d(dist), dtype=np.float64)
+        ref = np.ascontiguousarray(np.reshape(ref, -1), dtype=np.int32)
+        if dist.shape != (len(idx),) or ref.shape != (self.ndim,):
+            raise _lib.FwiError(_lib.EINVAL, "init list: one distance per node and one reference node, got %d nodes, "
+                                "distances %r, reference %r" % (len(idx), dist.shape, ref.shape))
+        return (idx, dist, ref), (len(idx), idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
+                                  ref.ctypes.data_as(C.c_void_p))
+
+    def eikonal(self, src, t_slot, scratch_slot, radius=0.0, max_sweeps=None):
+        """First-arrival times of the engine's model into slot ``t_slot`` (``scratch_slot``: the other half of the
+        ping-pong pair, its contents are lost).  ``src``: the source's grid coordinates, whole or fractional, turned
+        into an init list by ``eikonal.ball(src, shape, h, radius)`` -- every node within ``radius`` cells starts at
+        its straight-ray time in the velocity of the nearest node -- or such a list ``(idx, dist, ref)`` itself.
+        Returns the init list, which :meth:`eikonal_gradient` takes.  ``max_sweeps=None``: ``4 * sum(shape)``;
+        a cap that is reached raises ``FwiError`` (FWI_ESTATE) and leaves an upper bound in the slot."""
+        from . import eikonal as ek
+        init, args = self._init_args(ek._source(src, self.shape, self.h, radius))
+        n = C.c_int32(0)
+        try:
+            self._chk(self._lib.fwi_eikonal(self._c, int(t_slot), int(scratch_slot), *args,
+                                            0 if max_sweeps is None else int(max_sweeps), C.byref(n)))
+        finally:
+            self.last_eikonal_launches = int(n.value)
+        return init
+
+    def eikonal_times(self, t_slot, rec):
+        """The times of slot ``t_slot`` at receivers: node indices ``(n, ndim)``, or a ``points.Spread`` whose nodes
+        are gathered on the device and combined with its multilinear weights here.  float64."""
+        if hasattr(rec, "pt_start"):
+            v = self.vec_gather_points(t_slot, rec.idx) * rec.weights
+            return np.add.reduceat(v, rec.pt_start[:-1]) if len(v) else np.zeros(0)
+        return self.vec_gather_points(t_slot, rec)
+
+    def eikonal_adjoint(self, t_slot, rhs_slot, lam_slot, scratch_slot, max_sweeps=None):
+        """Slot ``lam_slot`` := the solution of ``lambda = rhs + A^T lambda`` at the fixed point in ``t_slot``
+        (``fwi_eikonal_adjoint``); four different slots."""
+        n = C.c_int32(0)
+        try:
+            self._chk(self._lib.fwi_eikonal_adjoint(self._c, int(t_slot), int(rhs_slot), int(lam_slot), int(scratch_slot),
+                                                    0 if max_sweeps is None else int(max_sweeps), C.byref(n)))
+        finally:
+            self.last_eikonal_launches = int(n.value)
+
+    def eikonal_gradient(self, t_slot, lam_slot, out_slot, init, beta=0.0, wrt="velocity"):
+        """Slot ``out_slot := beta out_slot +`` the gradient of ``sum_i rhs_i T_i`` with respect to the model, from the
+        times, the adjoint variable and the init list :meth:`eikonal` returned."""
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        _, args = self._init_args(init)
+        self._chk(self._lib.fwi_eikonal_gradient(self._c, w, int(t_slot), int(lam_slot), int(out_slot), float(beta), *args))
+
     def vec_clip(self, x, lo, hi):
         self._chk(self._lib.fwi_vec_clip(self._c, x, float(lo), float(hi)))
 

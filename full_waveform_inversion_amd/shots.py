@@ -1067,3 +1067,102 @@ def source_mute(shape, shots, radius):
             t = t + ((a - float(c)) ** 2).reshape(sh_)
         np.minimum(d2, t, out=d2)
     return 1.0 - np.exp(-d2 / float(radius) ** 2)
+
+
+TRAVELTIME_SLOTS = 5  # vector slots traveltime_fg uses from slot0 on: times, scratch, right-hand side, lambda, gradient
+
+
+def _traveltime_points(shot):
+    """(source coordinates, receivers) of a shot for the eikonal calls: its first source, the point itself when it is
+    off-grid, and the receiver points (a ``points.Spread``) or nodes"""
+    src = shot.src_spread.coords[0] if shot.src_spread is not None else np.asarray(shot.src_idx).reshape(-1, np.shape(shot.src_idx)[-1])[0]
+    return np.asarray(src, np.float64), (shot.rec_spread if shot.rec_spread is not None else np.asarray(shot.rec_idx))
+
+
+def traveltime_times(engine, model, shots, radius=0.0, slot0=0, exchange=None):
+    """First-arrival times of every shot at its receivers in ``model`` (None: the model the engines hold): a list
+    indexed like ``shots``, complete on every rank.  The picks of a synthetic test, or the times of a
+    ``datafit.first_arrival_mute``."""
+    ex = exchange or NoExchange()
+    if model is not None:
+        for e in _engines(engine):
+            e.set_model(model)
+
+    def one(e, i):
+        src, rec = _traveltime_points(shots[i])
+        e.eikonal(src, slot0, slot0 + 1, radius=radius)
+        return e.eikonal_times(slot0, rec)
+
+    mine = partition_shots(len(shots), ex.rank, ex.world)
+    got = engine.map_shots(mine, one) if isinstance(engine, EnginePool) else [one(engine, i) for i in mine]
+    sizes = [s.rec_spread.n if s.rec_spread is not None else len(np.asarray(s.rec_idx).reshape(-1, np.shape(s.rec_idx)[-1]))
+             for s in shots]
+    ends = np.cumsum([0] + sizes)
+    flat = np.zeros(ends[-1])
+    for i, v in zip(mine, got):
+        flat[ends[i]:ends[i + 1]] = v
+    flat = np.asarray(ex.reduce_array(flat))
+    return [flat[ends[i]:ends[i + 1]].copy() for i in range(len(shots))]
+
+
+def traveltime_fg(engine, model, shots, picks, pick_weights=None, radius=0.0, slot0=0, exchange=None, wrt="velocity"):
+    """First-arrival traveltime tomography: ``(J, g)`` with
+
+        ``J = 1/2 sum_s sum_r w_sr (T_s(x_r) - t_sr)^2``
+
+    and ``g = dJ/dmodel`` (``wrt`` as in :func:`misfit_and_gradient`; ``model`` is a velocity), summed over shots, the
+    engines of a pool and the ranks -- what ``lbfgs`` takes as ``lambda m: traveltime_fg(engine, m, ...)``.
+    ``picks[i]``: the picked times of shot ``i`` at its receivers (NaN: no pick, the receiver does not count);
+    ``pick_weights[i]``: weights >= 0 likewise (None: 1).  Per shot one eikonal solve from the shot's FIRST source
+    (``src_spread.coords`` when it is off-grid, with every node within ``radius`` cells initialised, ``eikonal.ball``),
+    the residuals scattered at the receivers' nodes (``rec_spread``: with the multilinear weights), one adjoint solve,
+    and the gradient added into a slot (``beta = 1``) that is downloaded once per engine.  Uses the
+    ``TRAVELTIME_SLOTS`` vector slots from ``slot0`` on, which must exist (``vec_create``).  The engine may be anything
+    with ``set_model``, ``eikonal``, ``eikonal_times``, ``vec_scatter_points``, ``eikonal_adjoint``,
+    ``eikonal_gradient`` and ``vec_download``: ``eikonal.TwinEngine`` runs it on the CPU."""
+    ex = exchange or NoExchange()
+    T, SC, B, L, G = (slot0 + k for k in range(TRAVELTIME_SLOTS))
+    engines = _engines(engine)
+    for e in engines:
+        e.set_model(model)
+    first = {id(e): True for e in engines}
+
+    def one(e, i):
+        s = shots[i]
+        src, rec = _traveltime_points(s)
+        t = np.asarray(picks[i], np.float64).reshape(-1)
+        w = np.ones(t.shape) if pick_weights is None or pick_weights[i] is None else \
+            np.asarray(pick_weights[i], np.float64).reshape(-1)
+        init = e.eikonal(src, T, SC, radius=radius)
+        tau = e.eikonal_times(T, rec)
+        if t.shape != tau.shape or w.shape != tau.shape:
+            raise ValueError("shot %d: %d receivers, %d picks, %d weights" % (i, tau.size, t.size, w.size))
+        ok = ~np.isnan(t)
+        r = np.where(ok, w * (tau - np.where(ok, t, 0.0)), 0.0)  # dJ/dT(x_r)
+        if hasattr(rec, "pt_start"):  # off-grid receivers: onto their nodes, a node shared by two receivers once
+            nodes, inv = np.unique(np.asarray(rec.idx), axis=0, return_inverse=True)
+            vals = np.zeros(len(nodes))
+            np.add.at(vals, np.reshape(inv, -1), r[rec.owner] * rec.weights)
+        else:
+            nodes, inv = np.unique(np.asarray(rec).reshape(-1, np.shape(rec)[-1]), axis=0, return_inverse=True)
+            vals = np.zeros(len(nodes))
+            np.add.at(vals, np.reshape(inv, -1), r)
+        e.vec_scatter_points(B, nodes, vals, beta=0.0)
+        e.eikonal_adjoint(T, B, L, SC)
+        e.eikonal_gradient(T, L, G, init, beta=0.0 if first[id(e)] else 1.0, wrt=wrt)
+        first[id(e)] = False
+        return 0.5 * float(np.sum(np.where(ok, w * (tau - np.where(ok, t, 0.0)) ** 2, 0.0)))
+
+    mine = partition_shots(len(shots), ex.rank, ex.world)
+    if isinstance(engine, EnginePool):
+        J = float(sum(engine.map_shots(mine, one)))
+    else:
+        J = float(sum(one(engine, i) for i in mine))
+    shape = np.shape(model)
+    g = np.zeros(shape, np.float64)
+    for e in engines:
+        if not first[id(e)]:
+            g += np.asarray(e.vec_download(G), np.float64)
+    g = np.asarray(ex.reduce_array(g)).reshape(shape)
+    J = float(np.asarray(ex.reduce_array(np.array([J]))).ravel()[0])
+    return J, g

@@ -167,7 +167,17 @@ def main():
     ap.add_argument("--spectral-whiten", action="store_true",
                     help="frequency weights 1 / (mean power of the observed data at the frequency + 1e-4 of the largest): "
                          "the weak frequencies count like the strong ones (datafit.whitening_weights; one rank)")
+    ap.add_argument("--tomography", type=int, default=0, metavar="ITERS",
+                    help="before the waveform stages: ITERS L-BFGS iterations of first-arrival traveltime tomography "
+                         "(shots.traveltime_fg: eikonal times and their adjoint on the device) from the starting model, "
+                         "on picks taken from the eikonal times of the true model; its result starts the waveform "
+                         "stages.  Takes the bounds, --smooth and --regularize / --reg-weight / --reg-eps / --reg-prior "
+                         "of the run")
+    ap.add_argument("--tomography-radius", type=float, default=3.0, metavar="R",
+                    help="cells around each source that start at their straight-ray time (eikonal.ball)")
     a = ap.parse_args()
+    if a.tomography < 0 or not (a.tomography_radius >= 0.0 and np.isfinite(a.tomography_radius)):
+        ap.error("--tomography ITERS must be >= 0 and --tomography-radius R finite and >= 0")
     bands = [float(f) for f in a.bands.split(",")] if a.bands else None
     if a.spectral is None and (a.spectral_band is not None or a.spectral_whiten):
         ap.error("--spectral-band / --spectral-whiten need --spectral")
@@ -375,6 +385,30 @@ def main():
             imaging["freq_weights"] = fw / float(fw.mean())
 
     m0 = w.c_init.astype(np.float32)
+    tomo = None
+    if a.tomography > 0:  # traveltime tomography first: the model it ends at starts the waveform stages
+        for eng in pool.engines:
+            eng.vec_create(sh.TRAVELTIME_SLOTS)
+        picks = sh.traveltime_times(pool, w.c.astype(np.float32), shots, a.tomography_radius, 0, ex)
+        tomo_J = []
+
+        def fg_tomo(m):
+            J, g = sh.traveltime_fg(pool, np.asarray(m, np.float32), shots, picks, None, a.tomography_radius, 0, ex)
+            tomo_J.append(J)
+            return J, g
+        if a.regularize is not None:
+            fg_tomo = rg.regularized_fg(fg_tomo, a.reg_weight, a.regularize, 1.0,
+                                        (a.reg_eps if a.reg_eps is not None else 1e-3 * float(m0.max()))
+                                        if a.regularize == "tv" else None, m0 if a.reg_prior == "start" else None)
+        m_tomo, _, tomo_log = lbfgs(fg_tomo, m0.astype(np.float64), maxiter=a.tomography, history=5,
+                                    first_step=0.02 * float(m0.max()),
+                                    bounds=(0.5 * float(w.c.min()), 1.5 * float(w.c.max())),
+                                    h0=sh.smoothing_h0(a.smooth) if a.smooth is not None else None)
+        tomo = {"iters": a.tomography, "radius": a.tomography_radius, "evaluations": len(tomo_J),
+                "J": [float(l["f"]) for l in tomo_log]}
+        m0 = np.asarray(m_tomo, np.float32)
+        for eng in pool.engines:
+            eng.vec_create(0)
     robust_stages = []  # per stage of --robust: the band and every shot's scale(s), as measured at its starting model
 
     def objective_of(taps, model=m0, band=None):
@@ -552,7 +586,8 @@ def main():
                           "envelope": a.envelope, "hilbert_fmin": a.hilbert_fmin,
                           "hilbert_halfwidth": len(hilbert) if hilbert is not None else None,
                           "envelope_floor_percent": a.envelope_floor_percent if a.envelope is not None else None,
-                          "match_mu_percent": a.match_mu_percent if a.match_source is not None else None, "log": log}))
+                          "match_mu_percent": a.match_mu_percent if a.match_source is not None else None,
+                          "tomography": tomo, "log": log}))
     pool.close()
     if rdzv is not None:
         rdzv.barrier()
