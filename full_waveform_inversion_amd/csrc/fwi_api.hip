@@ -83,18 +83,18 @@ int upload_series(fwi_ctx *ctx, void *dst, const void *src, size_t bytes) {
 
 int ensure(fwi_ctx *ctx, Buf &b, size_t bytes) {
     if (b.cap >= bytes && b.p) return FWI_OK;
-    if (b.p) HIPCHK(ctx, hipFree(b.p));
-    b.p = nullptr;
-    HIPCHK(ctx, hipMalloc(&b.p, bytes ? bytes : 16));
+    int rc;
+    if ((rc = dev_release(ctx, &b.p, b.member)) || (rc = dev_acquire(ctx, &b.p, bytes ? bytes : 16, b.member, b.index)))
+        return rc;
     b.cap = bytes;
     return FWI_OK;
 }
 
 // the block partials (and their total) of the fixed-order sums (launch_dot, launch_residual_l2): allocated on first use
 int sum_partials(fwi_ctx *ctx, double **part) {
-    if (!ctx->sum_part) HIPCHK(ctx, hipMalloc(&ctx->sum_part, (size_t)(SUM_MAX_BLOCKS + 1) * sizeof(double)));
+    const int rc = dev_first_use(ctx, &ctx->sum_part, (size_t)(SUM_MAX_BLOCKS + 1) * sizeof(double), "sum_part");
     *part = (double *)ctx->sum_part;
-    return FWI_OK;
+    return rc;
 }
 
 // Host arrays are model-shaped (row stride nx); compact device arrays have row stride cx (nx
@@ -108,7 +108,7 @@ int upload_compact(fwi_ctx *ctx, void *dst, const void *host) {
         return FWI_OK;
     }
     const size_t nlog = (size_t)g.nz * g.ny * g.nx;
-    if (!ctx->logical) HIPCHK(ctx, hipMalloc(&ctx->logical, nlog * sizeof(T)));
+    if (int rc = dev_first_use(ctx, &ctx->logical, nlog * sizeof(T), "logical")) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->logical, host, nlog * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, launch_repack<T>(g, (T *)dst, (const T *)ctx->logical, 1, ctx->stream));
     return FWI_OK;
@@ -122,7 +122,7 @@ int download_compact(fwi_ctx *ctx, void *host, const void *src) {
         return FWI_OK;
     }
     const size_t nlog = (size_t)g.nz * g.ny * g.nx;
-    if (!ctx->logical) HIPCHK(ctx, hipMalloc(&ctx->logical, nlog * sizeof(T)));
+    if (int rc = dev_first_use(ctx, &ctx->logical, nlog * sizeof(T), "logical")) return rc;
     HIPCHK(ctx, launch_repack<T>(g, (T *)ctx->logical, (const T *)src, 0, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(host, ctx->logical, nlog * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
     return FWI_OK;
@@ -149,14 +149,14 @@ int download_series(fwi_ctx *ctx, void *dst, const void *src, size_t bytes) {
     return FWI_OK;
 }
 
-// ensure for a group of plain pointers of `bytes` each that share one capacity
-int ensure_all(fwi_ctx *ctx, std::initializer_list<void **> group, size_t *cap, size_t bytes) {
+// ensure for a group of plain pointers of `bytes` each that share one capacity: `member`[index0], [index0 + 1], ...
+int ensure_all(fwi_ctx *ctx, const char *member, int index0, std::initializer_list<void **> group, size_t *cap,
+               size_t bytes) {
     if (*cap >= bytes && std::all_of(group.begin(), group.end(), [](void **p) { return *p != nullptr; })) return FWI_OK;
-    for (void **p : group) {
-        if (*p) HIPCHK(ctx, hipFree(*p));
-        *p = nullptr;
-        HIPCHK(ctx, hipMalloc(p, bytes ? bytes : 16));
-    }
+    int rc;
+    for (void **p : group)
+        if ((rc = dev_release(ctx, p, member)) || (rc = dev_acquire(ctx, p, bytes ? bytes : 16, member, index0++)))
+            return rc;
     *cap = bytes;
     return FWI_OK;
 }
@@ -167,27 +167,26 @@ int ensure_all(fwi_ctx *ctx, std::initializer_list<void **> group, size_t *cap, 
 // against *free_bytes in its own words.
 struct Want {
     void **p;
+    const char *member;
     size_t bytes;
     bool zero;
+    int index = 0;
 };
 int alloc_all(fwi_ctx *ctx, std::initializer_list<Want> want, size_t *total, size_t *free_bytes) {
     size_t device_bytes = 0;
     *total = 0;
     for (const Want &w : want) *total += w.bytes;
     HIPCHK(ctx, hipMemGetInfo(free_bytes, &device_bytes));
-    hipError_t e = hipSuccess;
+    int e = hipSuccess;
     if (*total <= *free_bytes)
         for (const Want &w : want) {
             if (!w.bytes) continue;
-            if ((e = hipMalloc(w.p, w.bytes)) != hipSuccess) break;
+            if ((e = ctx->mem.acquire(w.p, w.bytes, w.member, w.index)) != hipSuccess) break;
             if (w.zero && (e = hipMemsetAsync(*w.p, 0, w.bytes, ctx->stream)) != hipSuccess) break;
         }
     if (*total <= *free_bytes && e == hipSuccess) return FWI_OK;
     (void)hipGetLastError();
-    for (const Want &w : want) {
-        if (*w.p) (void)hipFree(*w.p);
-        *w.p = nullptr;
-    }
+    for (const Want &w : want) (void)ctx->mem.release(w.p);
     return FWI_ENOMEM;
 }
 
@@ -462,8 +461,8 @@ struct Impl {
         int rcode;
         if ((rcode = flatten(ctx, idx, n, p, c))) return rcode;
         const size_t need = (size_t)n * 8 + 16;
-        if ((rcode = ensure_all(ctx, {&ps.pidx, &ps.cidx, &ps.cu, &ps.cq, &ps.s_pidx, &ps.s_cidx, &ps.s_cu, &ps.s_cq,
-                                      &ps.s_col, &ps.s_run}, &ps.cap, need)))
+        if ((rcode = ensure_all(ctx, ps.member, 0, {&ps.pidx, &ps.cidx, &ps.cu, &ps.cq, &ps.s_pidx, &ps.s_cidx, &ps.s_cu,
+                                                    &ps.s_cq, &ps.s_col, &ps.s_run}, &ps.cap, need)))
             return rcode;
         auto up = [&](void *d, const void *h, size_t b) {
             return b ? hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
@@ -590,9 +589,10 @@ struct Impl {
                 fint[k] = e.interior; fcidx[k] = c[e.col]; fcu[k] = cu[e.col]; fcq[k] = cq[e.col];
             }
             const size_t fneed = ne * 8 + 16, sneed = (size_t)(ntile + 1) * sizeof(int);
-            if ((rcode = ensure_all(ctx, {&ps.fi_lz, &ps.fi_lx, &ps.fi_col, &ps.fi_int, &ps.fi_cidx, &ps.fi_cu, &ps.fi_cq,
-                                          &ps.fi_run, &ps.fr_lz, &ps.fr_lx, &ps.fr_col}, &ps.fcap, fneed)) ||
-                (rcode = ensure_all(ctx, {&ps.fi_start, &ps.fr_start}, &ps.fcap_start, sneed)))
+            if ((rcode = ensure_all(ctx, ps.member, 11, {&ps.fi_lz, &ps.fi_lx, &ps.fi_col, &ps.fi_int, &ps.fi_cidx, &ps.fi_cu,
+                                                         &ps.fi_cq, &ps.fi_run, &ps.fr_lz, &ps.fr_lx, &ps.fr_col},
+                                    &ps.fcap, fneed)) ||
+                (rcode = ensure_all(ctx, ps.member, 22, {&ps.fi_start, &ps.fr_start}, &ps.fcap_start, sneed)))
                 return rcode;
             HIPCHK(ctx, up(ps.fi_start, fst.data(), sneed));
             HIPCHK(ctx, up(ps.fr_start, rst.data(), sneed));
@@ -1132,8 +1132,8 @@ struct Impl {
         const size_t acc = 2 * F * vol, ring = (size_t)(ctx->four_batch + 1) * vol;
         size_t total, fr;
         // (zeroed: the pad columns of a ring slot are the step kernels' to write or to leave)
-        if (int rc = alloc_all(ctx, {{&ctx->four_acc, acc, true}, {&ctx->four_ring, ring, true},
-                                     {&ctx->four_tw, F * rows * 2 * sizeof(double), true}}, &total, &fr))
+        if (int rc = alloc_all(ctx, {{&ctx->four_acc, "four_acc", acc, true}, {&ctx->four_ring, "four_ring", ring, true},
+                                     {&ctx->four_tw, "four_tw", F * rows * 2 * sizeof(double), true}}, &total, &fr))
             return rc != FWI_ENOMEM ? rc : ctx->fail(FWI_ENOMEM,
                              "Fourier forward-term store needs %.1f GiB (%d frequencies, batch %d) but only %.1f GiB are "
                              "free; fewer frequencies or a smaller batch need less",
@@ -1180,7 +1180,7 @@ struct Impl {
         if (four && (rc = fourier_alloc(ctx))) return rc;
         size_t total, fr;
         if (save && K == 0 && !four && !ctx->q_store) {
-            if ((rc = alloc_all(ctx, {{&ctx->q_store, Store(ctx).bytes(ctx->cfg.nt_max), false}}, &total, &fr)))
+            if ((rc = alloc_all(ctx, {{&ctx->q_store, "q_store", Store(ctx).bytes(ctx->cfg.nt_max), false}}, &total, &fr)))
                 return rc != FWI_ENOMEM ? rc : ctx->fail(FWI_ENOMEM,
                                  "forward-term store needs %.1f GiB (nt_max=%d) but only %.1f GiB are free; "
                                  "set ckpt_interval (recomputation) or image_stride (decimated imaging)",
@@ -1195,18 +1195,18 @@ struct Impl {
             const size_t *pb = ctx->pml_bytes;
             ctx->pml_snap_stride = 2 * (pb[0] + pb[1] + pb[2]);
             if ((rc = alloc_all(ctx, {
-                     {&ctx->snap, (size_t)nseg * 2 * fb, false},
-                     {&ctx->q_store, (size_t)(K + 1) * g.npts * sizeof(T), false},  // K slots + carry
+                     {&ctx->snap, "snap", (size_t)nseg * 2 * fb, false},
+                     {&ctx->q_store, "q_store", (size_t)(K + 1) * g.npts * sizeof(T), false},  // K slots + carry
                      // (padded fields are zeroed at allocation: in increment form fwd[1] only ever receives interior points and
                      // its halo must read 0 -- found by the option fuzz reusing device memory of earlier contexts; the others
                      // are overwritten whole before use, but fwi_check_padding looks at every padded field of the context)
-                     {&ctx->fwd[0], fb, true},
-                     {&ctx->fwd[1], fb, true}, {&ctx->fwv, ctx->inc ? fb : 0, true},
-                     {&ctx->fwx[0], ctx->fused2d ? fb : 0, true}, {&ctx->fwx[1], ctx->fused2d ? fb : 0, true},
-                     {&ctx->pml_psi_fw[0], pb[0], false}, {&ctx->pml_zeta_fw[0], pb[0], false},
-                     {&ctx->pml_psi_fw[1], pb[1], false}, {&ctx->pml_zeta_fw[1], pb[1], false},
-                     {&ctx->pml_psi_fw[2], pb[2], false}, {&ctx->pml_zeta_fw[2], pb[2], false},
-                     {&ctx->pml_snap, (size_t)nseg * ctx->pml_snap_stride, false}}, &total, &fr)))
+                     {&ctx->fwd[0], "fwd", fb, true},
+                     {&ctx->fwd[1], "fwd", fb, true, 1}, {&ctx->fwv, "fwv", ctx->inc ? fb : 0, true},
+                     {&ctx->fwx[0], "fwx", ctx->fused2d ? fb : 0, true}, {&ctx->fwx[1], "fwx", ctx->fused2d ? fb : 0, true, 1},
+                     {&ctx->pml_psi_fw[0], "pml_psi_fw", pb[0], false}, {&ctx->pml_zeta_fw[0], "pml_zeta_fw", pb[0], false},
+                     {&ctx->pml_psi_fw[1], "pml_psi_fw", pb[1], false, 1}, {&ctx->pml_zeta_fw[1], "pml_zeta_fw", pb[1], false, 1},
+                     {&ctx->pml_psi_fw[2], "pml_psi_fw", pb[2], false, 2}, {&ctx->pml_zeta_fw[2], "pml_zeta_fw", pb[2], false, 2},
+                     {&ctx->pml_snap, "pml_snap", (size_t)nseg * ctx->pml_snap_stride, false}}, &total, &fr)))
                 return rc != FWI_ENOMEM ? rc : ctx->fail(FWI_ENOMEM,
                                  "checkpoint buffers need %.1f GiB (nt_max=%d, ckpt_interval=%d) but only %.1f GiB "
                                  "are free; a ckpt_interval near sqrt(2 nt_max) needs the least memory",
@@ -1306,7 +1306,7 @@ struct Impl {
         if (ctx->four_adj) return FWI_OK;
         const size_t F = ctx->four_freqs.size(), bytes = 2 * F * (size_t)ctx->gd.npts * sizeof(T);
         size_t total, fr;
-        if (int rc = alloc_all(ctx, {{&ctx->four_adj, bytes, true}}, &total, &fr))
+        if (int rc = alloc_all(ctx, {{&ctx->four_adj, "four_adj", bytes, true}}, &total, &fr))
             return rc != FWI_ENOMEM ? rc : ctx->fail(FWI_ENOMEM,
                              "fwi_adjoint_spectral: the adjoint accumulators need %.1f GiB (%d frequencies) but only "
                              "%.1f GiB are free; fewer frequencies need less",
@@ -1530,7 +1530,7 @@ struct Impl {
         const int nt = ctx->nt, nrec = ctx->nrec, S = ctx->istride, K = ctx->ckpt;
         hipStream_t s = ctx->stream;
         int rc;
-        if (!ctx->born_w) HIPCHK(ctx, hipMalloc(&ctx->born_w, (size_t)g.npts * sizeof(T)));
+        if ((rc = dev_first_use(ctx, &ctx->born_w, (size_t)g.npts * sizeof(T), "born_w"))) return rc;
         if (dm_host && (rc = upload_compact<T>(ctx, ctx->born_w, dm_host))) return rc;
         if (!dm_host && !dm_dev) {  // ones, pad columns zero: 1 / (0 + 1)
             HIPCHK(ctx, hipMemsetAsync(ctx->born_w, 0, (size_t)g.npts * sizeof(T), s));
@@ -1668,7 +1668,7 @@ struct Impl {
         int rc = fourier_adjoint_alloc(ctx);
         if (rc) return rc;
         ctx->have_m = false;
-        if (!ctx->born_w) HIPCHK(ctx, hipMalloc(&ctx->born_w, (size_t)g.npts * sizeof(T)));
+        if ((rc = dev_first_use(ctx, &ctx->born_w, (size_t)g.npts * sizeof(T), "born_w"))) return rc;
         const size_t nlog = (size_t)g.nz * g.ny * g.nx;
         for (int l = 0; l < nlag; ++l) {
             const T *img = images_dev ? (const T *)images_dev[l] : (const T *)ctx->born_w;
@@ -1698,6 +1698,10 @@ int create_impl(fwi_ctx *ctx) {
     const fwi_config &c = ctx->cfg;
     const GridDesc &g = ctx->gd;
     const size_t es = ctx->esize;
+    int rc;
+    auto alloc = [ctx](auto **slot, const char *member, size_t bytes, int index = 0) {
+        return dev_acquire(ctx, (void **)slot, bytes, member, index);
+    };
     HIPCHK(ctx, hipSetDevice(c.device));
     HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIPCHK(ctx, hipEventCreate(&ctx->ev0));
@@ -1705,24 +1709,24 @@ int create_impl(fwi_ctx *ctx) {
     const size_t fslack = ctx->place_kind == 2 ? ctx->place_pad : 0;  // (tune_placement may move C; the u buffers
                                                                        // change roles with others and stay where they are)
     for (int i = 0; i < 2; ++i) {
-        HIPCHK(ctx, hipMalloc(&ctx->u[i], (size_t)g.ptot * es));
+        if ((rc = alloc(&ctx->u[i], "u", (size_t)g.ptot * es, i))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->u[i], 0, (size_t)g.ptot * es, ctx->stream));
     }
-    HIPCHK(ctx, hipMalloc(&ctx->C, (size_t)g.ptot * es + fslack));
+    if ((rc = alloc(&ctx->C, "C", (size_t)g.ptot * es + fslack))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->C, 0, (size_t)g.ptot * es + fslack, ctx->stream));
-    HIPCHK(ctx, hipMalloc(&ctx->c_dev, (size_t)g.npts * es));
-    HIPCHK(ctx, hipMalloc(&ctx->g_acc, (size_t)g.npts * es));
+    if ((rc = alloc(&ctx->c_dev, "c_dev", (size_t)g.npts * es))) return rc;
+    if ((rc = alloc(&ctx->g_acc, "g_acc", (size_t)g.npts * es))) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->g_acc, 0, (size_t)g.npts * es, ctx->stream));
-    HIPCHK(ctx, hipMalloc(&ctx->g_out, (size_t)g.npts * es));
-    HIPCHK(ctx, hipMalloc(&ctx->dz, (size_t)g.nz * es));
-    HIPCHK(ctx, hipMalloc(&ctx->dy, (size_t)g.ny * es));
-    HIPCHK(ctx, hipMalloc(&ctx->dx, (size_t)g.nx * es));
-    HIPCHK(ctx, hipMalloc((void **)&ctx->red, 64));
+    if ((rc = alloc(&ctx->g_out, "g_out", (size_t)g.npts * es))) return rc;
+    if ((rc = alloc(&ctx->dz, "dz", (size_t)g.nz * es))) return rc;
+    if ((rc = alloc(&ctx->dy, "dy", (size_t)g.ny * es))) return rc;
+    if ((rc = alloc(&ctx->dx, "dx", (size_t)g.nx * es))) return rc;
+    if ((rc = alloc(&ctx->red, "red", 64))) return rc;
     if (ctx->fused2d) {  // tile order of the fused 2-D kernel on grids of more than one round of tiles (on THIS device)
         std::vector<int> order;
         fused2d_tile_order(g, ctx->fused_ft, c.npml, order, ctx->cpml ? 1 : 0);
         if (!order.empty()) {
-            HIPCHK(ctx, hipMalloc((void **)&ctx->fused_order, order.size() * sizeof(int)));
+            if ((rc = alloc(&ctx->fused_order, "fused_order", order.size() * sizeof(int)))) return rc;
             HIPCHK(ctx, hipMemcpy(ctx->fused_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
         }
     }
@@ -1741,16 +1745,16 @@ int create_impl(fwi_ctx *ctx) {
                 if (o != d) cnt *= (size_t)(o == 2 ? g.cx : nd[o]);
             ctx->pml_bytes[d] = cnt * es;
             const size_t slack = (d == 2 && ctx->place_kind == 1) ? ctx->place_pad : 0;  // (the x border's arrays can be moved: tune_placement)
-            HIPCHK(ctx, hipMalloc(&ctx->pml_psi[d], ctx->pml_bytes[d] + slack));
-            HIPCHK(ctx, hipMalloc(&ctx->pml_zeta[d], ctx->pml_bytes[d] + slack));
+            if ((rc = alloc(&ctx->pml_psi[d], "pml_psi", ctx->pml_bytes[d] + slack, d))) return rc;
+            if ((rc = alloc(&ctx->pml_zeta[d], "pml_zeta", ctx->pml_bytes[d] + slack, d))) return rc;
             if (ctx->fused2d) {  // the set the fused launch writes (see fwi_ctx::pml_spare_psi)
-                HIPCHK(ctx, hipMalloc(&ctx->pml_spare_psi[d], ctx->pml_bytes[d]));
-                HIPCHK(ctx, hipMalloc(&ctx->pml_spare_zeta[d], ctx->pml_bytes[d]));
+                if ((rc = alloc(&ctx->pml_spare_psi[d], "pml_spare_psi", ctx->pml_bytes[d], d))) return rc;
+                if ((rc = alloc(&ctx->pml_spare_zeta[d], "pml_spare_zeta", ctx->pml_bytes[d], d))) return rc;
                 HIPCHK(ctx, hipMemsetAsync(ctx->pml_spare_psi[d], 0, ctx->pml_bytes[d], ctx->stream));
                 HIPCHK(ctx, hipMemsetAsync(ctx->pml_spare_zeta[d], 0, ctx->pml_bytes[d], ctx->stream));
             }
-            HIPCHK(ctx, hipMalloc(&ctx->pml_a[d], (size_t)n * es));
-            HIPCHK(ctx, hipMalloc(&ctx->pml_b[d], (size_t)n * es));
+            if ((rc = alloc(&ctx->pml_a[d], "pml_a", (size_t)n * es, d))) return rc;
+            if ((rc = alloc(&ctx->pml_b[d], "pml_b", (size_t)n * es, d))) return rc;
             std::vector<double> pa(n), pb(n);  // cpml_profiles() of the oracle
             for (int i = 0; i < n; ++i) {
                 const double dist = std::max(0.0, std::max((double)c.npml - i, (double)i - (n - 1 - c.npml)));
@@ -1775,8 +1779,8 @@ int create_impl(fwi_ctx *ctx) {
         const size_t bz = (size_t)pml_shell_rows(g.nz, c.npml, g.r) * g.ny * g.cx * es;
         const size_t by = (size_t)(g.nz + 1) * pml_shell_rows(g.ny, c.npml, g.r) * g.cx * es;
         const size_t slack = ctx->place_kind == 1 ? ctx->place_pad : 0;
-        HIPCHK(ctx, hipMalloc(&ctx->pml_tz, bz + slack));
-        HIPCHK(ctx, hipMalloc(&ctx->pml_ty, by + slack));
+        if ((rc = alloc(&ctx->pml_tz, "pml_tz", bz + slack))) return rc;
+        if ((rc = alloc(&ctx->pml_ty, "pml_ty", by + slack))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->pml_tz, 0, bz + slack, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(ctx->pml_ty, 0, by + slack, ctx->stream));
         if (ctx->place_kind == 1) {  // search order: the positions that decided the slab experiments first
@@ -1786,7 +1790,6 @@ int create_impl(fwi_ctx *ctx) {
             ctx->movable(&ctx->pml_psi[2], ctx->pml_bytes[2]);
         }
     }
-    int rc;
     if (c.dtype == FWI_F32) {
         if ((rc = upload_vec<float>(ctx, ctx->dz, ctx->pz))) return rc;
         if ((rc = upload_vec<float>(ctx, ctx->dy, ctx->py))) return rc;
@@ -1883,15 +1886,30 @@ int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
     }
     if (cfg->device < 0 || cfg->device >= ndev) return bad("device ordinal out of range");
 
+    // Whatever else can refuse the configuration is looked at before the context exists: every failure behind `new`
+    // leaves through fwi_destroy at the end.
+    // (FWI_XPITCH_EXTRA: the layout A/B hook of DESIGN.md's pitch sweep, read ONCE per process -- not on any hot path)
+    static const int xpitch_extra = getenv("FWI_XPITCH_EXTRA") ? atoi(getenv("FWI_XPITCH_EXTRA")) : 0;
+    const GridDesc gd = make_grid(cfg->ndim, cfg->nz, cfg->ny, cfg->nx, cfg->order, xpitch_extra);
+    const bool can_stream = stream_supported(gd, cfg->dtype == FWI_F32);
+    if (cfg->kernel == FWI_KERNEL_STREAM && !can_stream) return bad("STREAM kernel: fp64 is 3-D only");
+    // the increment form exists in the 3-D fp32 stream kernel and in the point kernel
+    const bool inc_point = cfg->update_form == FWI_UPDATE_INCREMENT && !(cfg->ndim == 3 && cfg->dtype == FWI_F32);
+    if (inc_point && cfg->kernel == FWI_KERNEL_STREAM)
+        return bad("update_form increment: the STREAM kernel takes it for 3-D fp32 only");
+    // (the syntax of "fixed:" only; whether it applies depends on what the context turns out to place, below)
+    const char *pt = getenv("FWI_PLACEMENT_TUNE");
+    const bool place_fixed = pt && !strncmp(pt, "fixed:", 6);
+    int fixed_k[8] = {};
+    const bool fixed_ok = !place_fixed || parse_fixed_placement(pt + 6, fixed_k);
+
     fwi_ctx *ctx = new (std::nothrow) fwi_ctx;
     if (!ctx) {
         g_create_error = "fwi_create: out of host memory";
         return FWI_ENOMEM;
     }
     ctx->cfg = *cfg;
-    // (FWI_XPITCH_EXTRA: the layout A/B hook of DESIGN.md's pitch sweep, read ONCE per process -- not on any hot path)
-    static const int xpitch_extra = getenv("FWI_XPITCH_EXTRA") ? atoi(getenv("FWI_XPITCH_EXTRA")) : 0;
-    ctx->gd = make_grid(cfg->ndim, cfg->nz, cfg->ny, cfg->nx, cfg->order, xpitch_extra);
+    ctx->gd = gd;
     ctx->esize = cfg->dtype == FWI_F32 ? 4 : 8;
     ctx->ckpt = cfg->ckpt_interval;
     ctx->istride = cfg->image_stride > 1 ? cfg->image_stride : 1;
@@ -1900,20 +1918,7 @@ int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
     ctx->qbf16 = cfg->store_dtype == FWI_STORE_BF16;
     ctx->graph_mode = cfg->launch_mode == FWI_LAUNCH_GRAPH;  // (AUTO = stream: the measurement is with the comment below)
     ctx->qes = ctx->qbf16 ? 2 : (cfg->dtype == FWI_F32 ? 4 : 8);
-    const bool can_stream = stream_supported(ctx->gd, cfg->dtype == FWI_F32);
-    if (cfg->kernel == FWI_KERNEL_STREAM && !can_stream) {
-        delete ctx;
-        return bad("STREAM kernel: fp64 is 3-D only");
-    }
-    ctx->kernel = (cfg->kernel == FWI_KERNEL_POINT || !can_stream) ? K_POINT : K_STREAM;
-    if (ctx->inc && !(cfg->ndim == 3 && cfg->dtype == FWI_F32)) {
-        // the increment form exists in the 3-D fp32 stream kernel and in the point kernel
-        if (cfg->kernel == FWI_KERNEL_STREAM) {
-            delete ctx;
-            return bad("update_form increment: the STREAM kernel takes it for 3-D fp32 only");
-        }
-        ctx->kernel = K_POINT;
-    }
+    ctx->kernel = (cfg->kernel == FWI_KERNEL_POINT || !can_stream || inc_point) ? K_POINT : K_STREAM;
     if (ctx->kernel == K_STREAM) {
         // what a time step touches beside the three fields: the increment field; the CPML's memory variables (psi, zeta
         // over 2 npml planes per axis) and the handed-over border terms (two shells of npml + r)
@@ -1981,30 +1986,26 @@ int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
     // search: movable array i (in the search order) sits k_i * 2 MiB into its allocation, the last value repeats (tests:
     // a layout that is asked for instead of timed; 0 <= k <= 7, anything else is FWI_EINVAL).  A context that places
     // nothing ignores "fixed:" as it ignores "force".
-    const char *pt = getenv("FWI_PLACEMENT_TUNE");
-    const bool place_fixed = pt && !strncmp(pt, "fixed:", 6);
     const bool place_on = cfg->dtype == FWI_F32 && cfg->ndim == 3 && ctx->kernel == K_STREAM && !(pt && !strcmp(pt, "0")) &&
                           ((double)ctx->gd.ptot * ctx->esize >= 48e6 || (pt && !strcmp(pt, "force")) || place_fixed);
     if (place_on && ctx->xpml) ctx->place_kind = 1;
     else if (place_on && ctx->inc && !ctx->cpml) ctx->place_kind = 2;
     const bool place = ctx->place_kind != 0;
     if (place) ctx->place_pad = (size_t)14 << 20;
-    int fixed_k[8] = {};
-    if (place && place_fixed && !parse_fixed_placement(pt + 6, fixed_k)) {
-        delete ctx;  // (nothing on the device yet)
-        return bad("FWI_PLACEMENT_TUNE=fixed:<k0>,<k1>,...: one to eight offsets, each 0 ... 7 (units of 2 MiB)");
-    }
-    int rc = create_impl(ctx);
+    int rc = place && place_fixed && !fixed_ok
+                 ? ctx->fail(FWI_EINVAL, "FWI_PLACEMENT_TUNE=fixed:<k0>,<k1>,...: one to eight offsets, each 0 ... 7 "
+                                         "(units of 2 MiB)")
+                 : create_impl(ctx);
     const size_t vslack = ctx->place_kind ? ctx->place_pad : 0;
     if (rc == FWI_OK && ctx->inc &&
-        (hipMalloc(&ctx->vf, (size_t)ctx->gd.ptot * ctx->esize + vslack) != hipSuccess ||
+        (ctx->mem.acquire(&ctx->vf, (size_t)ctx->gd.ptot * ctx->esize + vslack, "vf") != hipSuccess ||
          hipMemset(ctx->vf, 0, (size_t)ctx->gd.ptot * ctx->esize + vslack) != hipSuccess))
         rc = ctx->fail(FWI_ENOMEM, "allocating the increment field failed");
     if (rc == FWI_OK && ctx->place_kind && ctx->inc) ctx->movable(&ctx->vf, (size_t)ctx->gd.ptot * ctx->esize);
     if (rc == FWI_OK && ctx->place_kind == 2) ctx->movable(&ctx->C, (size_t)ctx->gd.ptot * ctx->esize);
     if (rc == FWI_OK && (ctx->fused2d || ctx->pair3d)) {
         for (int i = 0; i < 2 && rc == FWI_OK; ++i) {
-            if (hipMalloc(&ctx->fx[i], (size_t)ctx->gd.ptot * ctx->esize) != hipSuccess ||
+            if (ctx->mem.acquire(&ctx->fx[i], (size_t)ctx->gd.ptot * ctx->esize, "fx", i) != hipSuccess ||
                 hipMemset(ctx->fx[i], 0, (size_t)ctx->gd.ptot * ctx->esize) != hipSuccess)
                 rc = ctx->fail(FWI_ENOMEM, "allocating the fused 2-D buffer pair failed");
         }
@@ -2037,74 +2038,16 @@ void fwi_destroy(fwi_ctx *ctx) {
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
-    // the movable arrays (fwi_create, Impl::tune_placement) go back to the start of their allocations BEFORE any pointer
-    // is read for freeing: hipFree takes what hipMalloc returned, not an address inside it
-    for (int i = 0; i < ctx->nmov; ++i)
-        if (*ctx->mov_slot[i]) *ctx->mov_slot[i] = (char *)*ctx->mov_slot[i] - ctx->mov_shift[i];
-    // The function returns nothing, so the FIRST free the runtime refuses is reported through the thread's creation
-    // error (fwi_last_error(NULL)): "fwi_destroy: hipFree(<member>[<index>]): <HIP error>".  The rest is still freed.
-    bool failed = false;
-    auto release = [&](const char *member, int idx, void *p) {
-        if (!p) return;
-        const hipError_t e = hipFree(p);
-        if (e == hipSuccess || failed) return;
-        failed = true;
+    // Every device allocation, from the context's record: each base once, wherever the members point by now -- into a
+    // padded allocation (fwi_create, Impl::tune_placement) or at each other's (adopt).  The function returns nothing, so
+    // the FIRST free the runtime refuses is reported through the thread's creation error (fwi_last_error(NULL)):
+    // "fwi_destroy: hipFree(<member>[<index>]): <HIP error>", <member> being the one the allocation was MADE for (after a
+    // sweep that swapped buffers, not necessarily the one that holds it).  The rest is still freed.
+    ctx->mem.release_all([](const char *member, int index, int code) {
         char msg[256];
-        snprintf(msg, sizeof msg, "fwi_destroy: hipFree(%s[%d]): %s", member, idx, hipGetErrorString(e));
+        snprintf(msg, sizeof msg, "fwi_destroy: hipFree(%s[%d]): %s", member, index, hipGetErrorString((hipError_t)code));
         g_create_error = msg;
-    };
-    int k = 0;
-    for (fwi_ctx::PointSet *ps : {&ctx->src, &ctx->rec}) {
-        int j = 0;
-        for (void *p : {ps->pidx, ps->cidx, ps->cu, ps->cq, ps->s_start.p, ps->s_pidx, ps->s_cidx, ps->s_cu,
-                        ps->s_cq, ps->s_col, ps->s_run, ps->fi_run, ps->fi_start, ps->fi_lz, ps->fi_lx, ps->fi_col, ps->fi_int,
-                        ps->fi_cidx, ps->fi_cu, ps->fi_cq, ps->fr_start, ps->fr_lz, ps->fr_lx, ps->fr_col, ps->pr_start.p,
-                        ps->pr_ent.p})
-            release(ps == &ctx->src ? "src" : "rec", j++, p);
-    }
-    // the fields of fwi_create and of the sweeps; the on-demand buffers of the families follow from their lists (fwi_host.h)
-    const struct {
-        const char *member;
-        void *p;
-    } fields[] = {{"u", ctx->u[0]}, {"u", ctx->u[1]}, {"C", ctx->C}, {"c_dev", ctx->c_dev}, {"dz", ctx->dz}, {"dy", ctx->dy},
-                  {"dx", ctx->dx}, {"q_store", ctx->q_store},
-                  {"g_acc", ctx->g_acc}, {"h_acc", ctx->h_acc}, {"born_w", ctx->born_w},
-                  {"g_out", ctx->g_out}, {"red", ctx->red},
-                  {"snap", ctx->snap}, {"fwd", ctx->fwd[0]}, {"fwd", ctx->fwd[1]}, {"fx", ctx->fx[0]}, {"fx", ctx->fx[1]},
-                  {"fwx", ctx->fwx[0]}, {"fwx", ctx->fwx[1]}, {"logical", ctx->logical}, {"vf", ctx->vf}, {"fwv", ctx->fwv},
-                  {"pml_snap", ctx->pml_snap}, {"pml_tz", ctx->pml_tz}, {"pml_ty", ctx->pml_ty},
-                  {"fused_order", ctx->fused_order}};
-    const char *prev = "";
-    for (const auto &f : fields) {  // (the index counts within a member: u[0], u[1], C[0], ...)
-        k = strcmp(prev, f.member) ? 0 : k + 1;
-        prev = f.member;
-        release(f.member, k, f.p);
-    }
-#define RELEASE_BUF(name) release(#name, 0, ctx->name.p);
-#define RELEASE_PTR(name) release(#name, 0, ctx->name);
-    FWI_SHOT_BUFS(RELEASE_BUF)
-    FWI_VEC_PTRS(RELEASE_PTR)
-    FWI_FOURIER_PTRS(RELEASE_PTR)
-    FWI_MISFIT_BUFS(RELEASE_BUF)
-    FWI_EIKONAL_BUFS(RELEASE_BUF)
-#undef RELEASE_BUF
-#undef RELEASE_PTR
-    k = 0;
-    for (void *v : ctx->vecs) release("vecs", k++, v);
-    for (int d = 0; d < 3; ++d) {
-        release("pml_psi", d, ctx->pml_psi[d]);
-        release("pml_zeta", d, ctx->pml_zeta[d]);
-        release("pml_a", d, ctx->pml_a[d]);
-        release("pml_b", d, ctx->pml_b[d]);
-        release("pml_psi_fw", d, ctx->pml_psi_fw[d]);
-        release("pml_zeta_fw", d, ctx->pml_zeta_fw[d]);
-        release("pml_spare_psi", d, ctx->pml_spare_psi[d]);
-        release("pml_spare_zeta", d, ctx->pml_spare_zeta[d]);
-    }
-    for (fwi_ctx::SpreadSet *sp : {&ctx->src_sp, &ctx->rec_sp}) {
-        k = 0;
-        for (void *q : {sp->pt_start, sp->owner, sp->weight}) release(sp == &ctx->src_sp ? "src_sp" : "rec_sp", k++, q);
-    }
+    });
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -2170,7 +2113,7 @@ static int set_spread(fwi_ctx *ctx, fwi_ctx::SpreadSet &sp, int32_t npts, int32_
         for (int m = a; m < b; ++m) owner[m] = p;
     }
     const size_t need = (size_t)std::max(nnodes, npts + 1) * 8 + 16;
-    if (int rc = ensure_all(ctx, {&sp.pt_start, &sp.owner, &sp.weight}, &sp.cap, need)) return rc;
+    if (int rc = ensure_all(ctx, sp.member, 0, {&sp.pt_start, &sp.owner, &sp.weight}, &sp.cap, need)) return rc;
     HIPCHK(ctx, hipMemcpyAsync(sp.pt_start, pt_start, (size_t)(npts + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(sp.owner, owner.data(), (size_t)nnodes * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(sp.weight, weight, (size_t)nnodes * ctx->esize, hipMemcpyHostToDevice, ctx->stream));
@@ -2409,19 +2352,16 @@ int fwi_set_illumination(fwi_ctx *ctx, int32_t on) {
     const size_t bytes = (size_t)ctx->gd.npts * ctx->esize;
     if (on && !ctx->h_acc) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIPCHK(ctx, hipMalloc(&ctx->h_acc, bytes));
+        if (int rc = dev_acquire(ctx, &ctx->h_acc, bytes, "h_acc")) return rc;
         hipError_t e = hipMemsetAsync(ctx->h_acc, 0, bytes, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) {
-            (void)hipFree(ctx->h_acc);
-            ctx->h_acc = nullptr;
+            (void)ctx->mem.release(&ctx->h_acc);
             return ctx->fail(FWI_EHIP, "fwi_set_illumination: %s", hipGetErrorString(e));
         }
     } else if (!on && ctx->h_acc) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // no sweep in flight still adds into it
-        void *p = ctx->h_acc;
-        ctx->h_acc = nullptr;
-        HIPCHK(ctx, hipFree(p));
+        return dev_release(ctx, &ctx->h_acc, "h_acc");
     }
     return FWI_OK;
 }
@@ -2438,16 +2378,15 @@ static int fourier_release(fwi_ctx *ctx) {
     ctx->four_batch = ctx->four_rows = 0;
     ctx->four_sweep = false;
     ctx->have_m = false;
-#define ADDRESS_OF(name) &ctx->name,
-    void **const arrays[] = {FWI_FOURIER_PTRS(ADDRESS_OF)};
-#undef ADDRESS_OF
-    if (std::any_of(std::begin(arrays), std::end(arrays), [](void **p) { return *p != nullptr; }))
+    const struct {
+        void **slot;
+        const char *member;
+    } arrays[] = {{&ctx->four_acc, "four_acc"}, {&ctx->four_ring, "four_ring"}, {&ctx->four_tw, "four_tw"},
+                  {&ctx->four_adj, "four_adj"}, {&ctx->four_w, "four_w"}};
+    if (std::any_of(std::begin(arrays), std::end(arrays), [](const auto &a) { return *a.slot != nullptr; }))
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // no sweep still uses them
-    for (void **p : arrays) {
-        void *q = *p;
-        *p = nullptr;
-        if (q) HIPCHK(ctx, hipFree(q));
-    }
+    for (const auto &a : arrays)
+        if (int rc = dev_release(ctx, a.slot, a.member)) return rc;  // (the pointer is null by then: dev_release)
     return FWI_OK;
 }
 
@@ -2487,9 +2426,7 @@ int fwi_set_fourier_store(fwi_ctx *ctx, int32_t nfreq, const double *freqs_hz, i
     ctx->have_q = false;  // (before the free below can fail: the store it speaks of is about to go)
     if (ctx->q_store) {  // the native store of an earlier forward: its memory is what this store is there to save
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        void *q = ctx->q_store;
-        ctx->q_store = nullptr;
-        HIPCHK(ctx, hipFree(q));
+        if (int rc = dev_release(ctx, &ctx->q_store, "q_store")) return rc;
     }
     ctx->four_freqs.assign(freqs_hz, freqs_hz + nfreq);
     ctx->four_batch = batch;

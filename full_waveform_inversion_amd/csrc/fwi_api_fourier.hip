@@ -23,7 +23,7 @@ template <typename T>
 int fourier_weights(fwi_ctx *ctx, const double *fw, const double *tau, bool unit, const double *taps, int ntaps) {
     const int S = ctx->istride, N = (ctx->nt + S - 1) / S, F = (int)ctx->four_freqs.size();
     const double sdt = (double)S * ctx->cfg.dt;
-    if (!ctx->four_w) HIPCHK(ctx, hipMalloc(&ctx->four_w, 2 * FWI_FOURIER_FMAX * sizeof(double)));
+    if (int rc = dev_first_use(ctx, &ctx->four_w, 2 * FWI_FOURIER_FMAX * sizeof(double), "four_w")) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the upload of the pass before may still read the host copy
     std::vector<double> &a = ctx->four_w_host;
     a.assign(tau ? 2 * F : F, 0.0);

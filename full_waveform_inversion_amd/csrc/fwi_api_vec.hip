@@ -124,7 +124,7 @@ template <typename T>
 static int vec_regularizer(fwi_ctx *ctx, int32_t kind, const void *x, const void *x0, const void *v, void *out,
                            double alpha, double beta, const double w[3], double eps, double *value_out) {
     const int64_t nb = reg_blocks<T>(ctx->gd);
-    if (!ctx->reg_part) HIPCHK(ctx, hipMalloc(&ctx->reg_part, (size_t)(nb + 1) * sizeof(double)));
+    if (int rc = dev_first_use(ctx, &ctx->reg_part, (size_t)(nb + 1) * sizeof(double), "reg_part")) return rc;
     double *part = (double *)ctx->reg_part;
     HIPCHK(ctx, launch_regularizer<T>(ctx->gd, kind, (T *)out, (const T *)x, (const T *)x0, (const T *)v, alpha, beta, w,
                                       eps, part, ctx->stream));
@@ -193,12 +193,11 @@ int fwi_vec_create(fwi_ctx *ctx, int32_t count) {
     if (!ctx) return FWI_EINVAL;
     if (count < 0 || count > 256) return ctx->fail(FWI_EINVAL, "fwi_vec_create: count must be in [0, 256]");
     (void)hipSetDevice(ctx->cfg.device);
-    for (void *v : ctx->vecs)
-        if (v) (void)hipFree(v);
+    for (void *&v : ctx->vecs) (void)ctx->mem.release(&v);
     ctx->vecs.assign(count, nullptr);
     const size_t bytes = (size_t)ctx->gd.npts * ctx->esize;
     for (int i = 0; i < count; ++i) {
-        HIPCHK(ctx, hipMalloc(&ctx->vecs[i], bytes));
+        if (int rc = dev_acquire(ctx, &ctx->vecs[i], bytes, "vecs", i)) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->vecs[i], 0, bytes, ctx->stream));
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -354,7 +353,7 @@ int fwi_vec_smooth(fwi_ctx *ctx, int32_t y, const double *sigma) {
     }
     if (npass == 0) return FWI_OK;
     (void)hipSetDevice(ctx->cfg.device);
-    if (!ctx->smooth_tmp) HIPCHK(ctx, hipMalloc(&ctx->smooth_tmp, (size_t)g.npts * ctx->esize));
+    if (int rc = dev_first_use(ctx, &ctx->smooth_tmp, (size_t)g.npts * ctx->esize, "smooth_tmp")) return rc;
     return DISPATCH(ctx, vec_smooth_passes<float>(ctx, vy, axis, R, w, npass),
                     vec_smooth_passes<double>(ctx, vy, axis, R, w, npass));
 }

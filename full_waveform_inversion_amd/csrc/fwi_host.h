@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/fwi.h"
+#include "fwi_devmem.h"
 #include "fwi_kernels.h"
 
 using namespace fwi;
@@ -28,32 +29,19 @@ inline std::string vformat(const char *fmt, va_list ap) {
     return buf;
 }
 
-// A device buffer the context owns and grows on demand (ensure)
+// A device buffer the context owns and grows on demand (ensure); `member`[`index`] is what fwi_ctx::mem records it as
 struct Buf {
+    const char *member;
+    int index;
     void *p = nullptr;
     size_t cap = 0;
+    explicit Buf(const char *m, int i = 0) : member(m), index(i) {}
 };
 
-}  // namespace fwi
+inline int hip_malloc_code(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+inline int hip_free_code(void *p) { return (int)hipFree(p); }
 
-// The on-demand device buffers of a family are named ONCE, in the family's list: fwi_ctx declares its members from the
-// list and fwi_destroy frees them from it, so that none can be declared and leak.
-#define FWI_SHOT_BUFS(X) X(pts_a) X(pts_d) X(wav) X(amp) X(series) X(born_src)
-#define FWI_VEC_PTRS(X) X(smooth_tmp) X(reg_part) X(sum_part)
-#define FWI_FOURIER_PTRS(X) X(four_acc) X(four_ring) X(four_tw) X(four_adj) X(four_w)
-#define FWI_MISFIT_BUFS(X)                                                                                     \
-    X(data_tmp) X(data_w) X(data_taps) X(data_part) X(data_s) X(data_d) X(data_tw)                             \
-    X(match_part) X(match_norm) X(match_f)                                                                     \
-    X(env_g2) X(env_h)                                                                                         \
-    X(corr_part) X(corr_coef)                                                                                  \
-    X(tt_part) X(tt_coef) X(tt_lag)                                                                            \
-    X(ot_work) X(ot_counts)                                                                                    \
-    X(spec_part) X(spec_coef) X(spec_counts) X(spec_fw) X(spec_table)                                          \
-    X(awi_part) X(awi_work) X(awi_counts)                                                                      \
-    X(robust_part) X(robust_cnt) X(robust_thresh) X(robust_w) X(robust_med)
-#define FWI_EIKONAL_BUFS(X) X(eik_idx) X(eik_val) X(eik_out) X(eik_flags)
-#define FWI_DECLARE_BUF(name) Buf name;
-#define FWI_DECLARE_PTR(name) void *name = nullptr;
+}  // namespace fwi
 
 struct fwi_ctx {
     fwi_config cfg;
@@ -71,6 +59,10 @@ struct fwi_ctx {
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     double host_submit_ms = 0.0, host_graph_ms = 0.0;
+
+    // Every device allocation of the context is made through `mem` (dev_acquire, ensure, alloc_all) and recorded there
+    // under the member it is made for; fwi_destroy frees from that record, whatever the members point at by then.
+    DeviceMemory mem{hip_malloc_code, hip_free_code};
 
     // device fields
     void *u[2] = {nullptr, nullptr};  // padded wavefields (ping-pong)
@@ -145,7 +137,7 @@ struct fwi_ctx {
     // latest forward(save).  four_w: the F weights a_k w_k of the running image / illumination pass on the device (the
     // 2 F of a time-lag image, fwi_feximage.hip; the F of a split image with its taps behind them at FWI_FOURIER_FMAX,
     // fwi_fsplit.hip; room for 2 FWI_FOURIER_FMAX doubles).
-    FWI_FOURIER_PTRS(FWI_DECLARE_PTR)
+    void *four_acc = nullptr, *four_ring = nullptr, *four_tw = nullptr, *four_adj = nullptr, *four_w = nullptr;
     bool have_m = false;
     std::vector<double> four_w_host;
     size_t store_held = 0;    // device bytes held for the forward store of whichever kind (fwi_store_bytes)
@@ -167,6 +159,8 @@ struct fwi_ctx {
     // A point set on the device: original order (sampling, POINT-kernel injection) and the
     // copy sorted by stream-kernel tile with its CSR offsets (fused injection).
     struct PointSet {
+        const char *member;  // "src" / "rec": what the set's arrays are recorded as (indices 0 ... 25, in upload_set's order)
+        explicit PointSet(const char *m = "") : member(m), s_start(m, 10), pr_start(m, 24), pr_ent(m, 25) {}
         int n = 0;
         void *pidx = nullptr, *cidx = nullptr, *cu = nullptr, *cq = nullptr;
         void *s_pidx = nullptr, *s_cidx = nullptr, *s_cu = nullptr, *s_cq = nullptr,
@@ -181,15 +175,16 @@ struct fwi_ctx {
         size_t fcap = 0, fcap_start = 0;
         // entries of the 3-D two-step kernel, CSR over its workgroups
         Buf pr_start, pr_ent;
-    } src, rec;
+    } src{"src"}, rec{"rec"};
     // Off-grid points of the last forward (fwi_forward_spread): per point set the CSR over points, the owner of
     // every node entry and its interpolation weight; time series cross the boundary per POINT and are scattered /
     // gathered on the device.  npts = 0: node-based call.
     struct SpreadSet {
+        const char *member;
         int npts = 0;
         void *pt_start = nullptr, *owner = nullptr, *weight = nullptr;
         size_t cap = 0;
-    } src_sp, rec_sp;
+    } src_sp{"src_sp"}, rec_sp{"rec_sp"};
     // pts_a: (nt, npts) per-point series being uploaded / downloaded
     // pts_d: (nt, nrec points) gathered synthetics of the last forward (fwi_misfit_l2)
     // wav: (nt, nsrc) source wavelets of the last forward (kept for recomputation)
@@ -197,13 +192,13 @@ struct fwi_ctx {
     // series: (nt, n) sampled series of the running sweep
     // born_src: Born modelling on a bf16 store: (nt, nsrc) amplitudes w(x_s) wav^n_s of the source's exact share
     // (launch_born_source_share)
-    FWI_SHOT_BUFS(FWI_DECLARE_BUF)
+    Buf pts_a{"pts_a"}, pts_d{"pts_d"}, wav{"wav"}, amp{"amp"}, series{"series"}, born_src{"born_src"};
     std::vector<void *> vecs;  // optimiser vectors (compact, model-sized)
     // smooth_tmp: compact ping-pong vector of fwi_vec_smooth; allocated by its first call
     // reg_part: block partial sums (and their total) of fwi_vec_regularizer; allocated by its first call
     // sum_part: the same of fwi_vec_dot, fwi_dot and fwi_misfit_l2 (SUM_MAX_BLOCKS + 1 doubles); allocated by the first
     // of those calls
-    FWI_VEC_PTRS(FWI_DECLARE_PTR)
+    void *smooth_tmp = nullptr, *reg_part = nullptr, *sum_part = nullptr;
     // the data misfits and fwi_residual_weight (Impl<T>::Misfit), each allocated by the first call that needs it: the
     // series between two passes (e; g1 of the envelope), the weights, the taps of B, the block partial sums of J (and
     // their total), the filtered synthetics s' and data d' of the misfits that filter first (with taps; s' later holds
@@ -216,19 +211,30 @@ struct fwi_ctx {
     // fwi_misfit_transport (fwi_ot.hip): densities, CDFs, potentials and every sum (ot_work_doubles), which traces count
     // fwi_misfit_spectral (fwi_spec.hip): the segment sums, G / phi / a and the terms of J, which pairs count, the
     // frequency weights, and the twiddle table with the (nt, frequencies) it was formed for (dt is the context's)
-    FWI_MISFIT_BUFS(FWI_DECLARE_BUF)
+    Buf data_tmp{"data_tmp"}, data_w{"data_w"}, data_taps{"data_taps"}, data_part{"data_part"}, data_s{"data_s"},
+        data_d{"data_d"}, data_tw{"data_tw"};
+    Buf match_part{"match_part"}, match_norm{"match_norm"}, match_f{"match_f"};
+    Buf env_g2{"env_g2"}, env_h{"env_h"};
+    Buf corr_part{"corr_part"}, corr_coef{"corr_coef"};
+    Buf tt_part{"tt_part"}, tt_coef{"tt_coef"}, tt_lag{"tt_lag"};
+    Buf ot_work{"ot_work"}, ot_counts{"ot_counts"};
+    Buf spec_part{"spec_part"}, spec_coef{"spec_coef"}, spec_counts{"spec_counts"}, spec_fw{"spec_fw"},
+        spec_table{"spec_table"};
     // fwi_misfit_adaptive (fwi_awi.hip): the correlations of both kinds, z / the filters / W / the terms of J, which
     // traces count; the events around the three phases of the last call (created by the first), fwi_misfit_adaptive_ms
+    Buf awi_part{"awi_part"}, awi_work{"awi_work"}, awi_counts{"awi_counts"};
     hipEvent_t awi_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool have_awi_ms = false;
     // fwi_misfit_robust, fwi_residual_median (fwi_robust.hip): the per-tile sums of rho and the terms per trace, the
     // counts beyond the threshold likewise, the thresholds, the IRLS weight W = tw M^2 psi(e) of the last call that
     // kept one (have_irls: it belongs to the forward the context holds; fwi_residual_weight_robust), the medians with
     // their counts and the whole-gather select's bins
+    Buf robust_part{"robust_part"}, robust_cnt{"robust_cnt"}, robust_thresh{"robust_thresh"}, robust_w{"robust_w"},
+        robust_med{"robust_med"};
     bool have_irls = false;
     // fwi_eikonal*, fwi_vec_scatter_points, fwi_vec_gather_points (fwi_eikonal.hip): the compact indices and the values
     // of the point list of the running call, the gathered values, the change flags of a batch of launches
-    FWI_EIKONAL_BUFS(FWI_DECLARE_BUF)
+    Buf eik_idx{"eik_idx"}, eik_val{"eik_val"}, eik_out{"eik_out"}, eik_flags{"eik_flags"};
     int spec_table_nt = 0;
     std::vector<double> spec_table_freqs, spec_table_host;
     // off-grid receivers: where the per-POINT series of the device residual lie (the nodes' are in ctx->amp)
@@ -281,6 +287,28 @@ inline void *vec_slot(fwi_ctx *ctx, int32_t slot) {
     if (!name) return (ctx)->fail(FWI_EINVAL, "%s: vector slot %d does not exist", __func__, (int)(slot))
 
 namespace fwi {
+
+// What HIPCHK makes of a failed hipMalloc / hipFree, from the code fwi_ctx::mem returns for `member`
+inline int dev_fail(fwi_ctx *ctx, const char *call, const char *member, int code) {
+    if (code == DeviceMemory::UNKNOWN) return ctx->fail(FWI_EHIP, "%s(%s): not an allocation of this context", call, member);
+    return ctx->fail(code == hipErrorOutOfMemory ? FWI_ENOMEM : FWI_EHIP, "%s(%s): %s", call, member,
+                     hipGetErrorString((hipError_t)code));
+}
+// *slot := `bytes` of device memory, recorded as `member`[`index`]; *slot is null where it fails
+inline int dev_acquire(fwi_ctx *ctx, void **slot, size_t bytes, const char *member, int index = 0) {
+    const int code = ctx->mem.acquire(slot, bytes, member, index);
+    return code ? dev_fail(ctx, "hipMalloc", member, code) : FWI_OK;
+}
+// ... and given back.  *slot is null BEFORE the runtime is asked, so a free it refuses leaves no pointer to memory that
+// may be gone; a null *slot is a no-op
+inline int dev_release(fwi_ctx *ctx, void **slot, const char *member) {
+    const int code = ctx->mem.release(slot);
+    return code ? dev_fail(ctx, "hipFree", member, code) : FWI_OK;
+}
+// a buffer of a fixed size that the first call which needs it allocates
+inline int dev_first_use(fwi_ctx *ctx, void **slot, size_t bytes, const char *member) {
+    return *slot ? FWI_OK : dev_acquire(ctx, slot, bytes, member);
+}
 
 // Defined in fwi_api.hip.  ensure: `b` holds at least `bytes` (its content is not kept when it grows)
 int ensure(fwi_ctx *ctx, Buf &b, size_t bytes);
