@@ -1802,24 +1802,6 @@ int create_impl(fwi_ctx *ctx) {
     return FWI_OK;
 }
 
-// FWI_PLACEMENT_TUNE=fixed:<k0>,<k1>,... (fwi_create): one to eight offsets in units of 2 MiB, each within the
-// 14 MiB of slack (0 ... 7); the last one repeats for the arrays that are not listed
-bool parse_fixed_placement(const char *s, int k[8]) {
-    int n = 0;
-    for (;;) {
-        char *end = nullptr;
-        if (*s < '0' || *s > '9') return false;  // (no sign, no blank: strtol would take them)
-        const long v = strtol(s, &end, 10);
-        if (v > 7 || n == 8) return false;
-        k[n++] = (int)v;
-        if (*end == '\0') break;
-        if (*end != ',') return false;
-        s = end + 1;
-    }
-    for (; n < 8; ++n) k[n] = k[n - 1];
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1835,13 +1817,7 @@ int fwi_device_count(int32_t *n_out) {
 
 const char *fwi_last_error(const fwi_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-const char *fwi_kernel_name(const fwi_ctx *ctx) {
-    if (!ctx) return "";
-    if (ctx->fused2d) return "step2d_fused";
-    if (ctx->kernel == K_STREAM && ctx->gd.ndim == 2) return "step2d_tile";
-    if (ctx->kernel == K_STREAM) return "step3d_stream";
-    return "step_point";
-}
+const char *fwi_kernel_name(const fwi_ctx *ctx) { return ctx ? plan_kernel_name(*ctx) : ""; }
 
 int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
     if (!cfg || !out) {
@@ -1886,116 +1862,36 @@ int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
     }
     if (cfg->device < 0 || cfg->device >= ndev) return bad("device ordinal out of range");
 
-    // Whatever else can refuse the configuration is looked at before the context exists: every failure behind `new`
-    // leaves through fwi_destroy at the end.
-    // (FWI_XPITCH_EXTRA: the layout A/B hook of DESIGN.md's pitch sweep, read ONCE per process -- not on any hot path)
-    static const int xpitch_extra = getenv("FWI_XPITCH_EXTRA") ? atoi(getenv("FWI_XPITCH_EXTRA")) : 0;
-    const GridDesc gd = make_grid(cfg->ndim, cfg->nz, cfg->ny, cfg->nx, cfg->order, xpitch_extra);
-    const bool can_stream = stream_supported(gd, cfg->dtype == FWI_F32);
-    if (cfg->kernel == FWI_KERNEL_STREAM && !can_stream) return bad("STREAM kernel: fp64 is 3-D only");
-    // the increment form exists in the 3-D fp32 stream kernel and in the point kernel
-    const bool inc_point = cfg->update_form == FWI_UPDATE_INCREMENT && !(cfg->ndim == 3 && cfg->dtype == FWI_F32);
-    if (inc_point && cfg->kernel == FWI_KERNEL_STREAM)
-        return bad("update_form increment: the STREAM kernel takes it for 3-D fp32 only");
-    // (the syntax of "fixed:" only; whether it applies depends on what the context turns out to place, below)
-    const char *pt = getenv("FWI_PLACEMENT_TUNE");
-    const bool place_fixed = pt && !strncmp(pt, "fixed:", 6);
-    int fixed_k[8] = {};
-    const bool fixed_ok = !place_fixed || parse_fixed_placement(pt + 6, fixed_k);
+    // Whatever else can refuse the configuration is looked at before the context exists (plan_context: which path the
+    // context takes, from the configuration and the creation-time hooks alone): every failure behind `new` leaves through
+    // fwi_destroy at the end.
+    const Hooks hooks = Hooks::from_env();
+    Plan plan;
+    std::string why;
+    const int planned = plan_context(*cfg, hooks, &plan, &why);
+    // (a refused "fixed:" is found after the path is decided, plan_context: the line is still written)
+    if (hooks.debug_pml && (planned == FWI_OK || plan.place_kind)) {
+        char line[160];
+        plan_report(plan, line, sizeof line);
+        fprintf(stderr, "%s\n", line);
+    }
+    if (planned) return bad(why.c_str());
 
     fwi_ctx *ctx = new (std::nothrow) fwi_ctx;
     if (!ctx) {
         g_create_error = "fwi_create: out of host memory";
         return FWI_ENOMEM;
     }
+    static_cast<Plan &>(*ctx) = plan;
     ctx->cfg = *cfg;
-    ctx->gd = gd;
-    ctx->esize = cfg->dtype == FWI_F32 ? 4 : 8;
-    ctx->ckpt = cfg->ckpt_interval;
-    ctx->istride = cfg->image_stride > 1 ? cfg->image_stride : 1;
-    ctx->inc = cfg->update_form == FWI_UPDATE_INCREMENT;
-    ctx->cpml = cfg->abc == FWI_ABC_CPML && cfg->npml > 0;
-    ctx->qbf16 = cfg->store_dtype == FWI_STORE_BF16;
-    ctx->graph_mode = cfg->launch_mode == FWI_LAUNCH_GRAPH;  // (AUTO = stream: the measurement is with the comment below)
-    ctx->qes = ctx->qbf16 ? 2 : (cfg->dtype == FWI_F32 ? 4 : 8);
-    ctx->kernel = (cfg->kernel == FWI_KERNEL_POINT || !can_stream || inc_point) ? K_POINT : K_STREAM;
-    if (ctx->kernel == K_STREAM) {
-        // what a time step touches beside the three fields: the increment field; the CPML's memory variables (psi, zeta
-        // over 2 npml planes per axis) and the handed-over border terms (two shells of npml + r)
-        double extra = ctx->inc ? (double)ctx->gd.ptot * ctx->esize : 0.0;
-        if (ctx->cpml && cfg->ndim == 3) {
-            const double face[3] = {(double)ctx->gd.ny * ctx->gd.cx, (double)ctx->gd.nz * ctx->gd.cx, (double)ctx->gd.nz * ctx->gd.ny};
-            for (int d = 0; d < 3; ++d) extra += 2.0 * std::min(2 * cfg->npml, d == 0 ? cfg->nz : d == 1 ? cfg->ny : cfg->nx) * face[d] * ctx->esize;
-            for (int d = 0; d < 2; ++d) extra += 2.0 * (cfg->npml + ctx->gd.r) * face[d] * ctx->esize;
-        }
-        ctx->tune = stream_default_tuning(ctx->gd, cfg->dtype == FWI_F32, extra);
-        if (cfg->zchunk > 0) ctx->tune.zchunk = cfg->zchunk;
-        if (const char *pf = getenv("FWI_STREAM_PF")) {  // tuning hook: prefetch depth in planes
-            const int v = atoi(pf);
-            if (v >= 1 && v <= 3) ctx->tune.pf = v;
-        }
-        if (const char *ty = getenv("FWI_STREAM_TY")) {  // tuning hook: rows per workgroup
-            const int v = atoi(ty);
-            if (v == 4 || v == 8 || (v == 16 && cfg->ndim == 2)) ctx->tune.ty = v;
-        }
-    }
-    // 2-D fp32 grids: advance FUSED2D_STEPS time steps per launch (fwi_fused2d.hip) whenever the step
-    // count allows it (FWI_NO_FUSED2D is the tuning / comparison hook)
-    // (CPML: the fused kernel carries the border recursion itself where the tiling admits it, fused2d_cpml_supported;
-    // otherwise the slab kernels run between time steps: one step per launch, the tile kernel.  FWI_NO_FUSED2D_CPML is
-    // the comparison hook)
-    // Increment form in 2-D: the fused kernel carries it (same traffic as the standard form); the steps it cannot take
-    // (step counts off the multiple of 4) go through the point kernel, which ctx->kernel names in that case.
-    if (const char *sk = getenv("FWI_FUSED2D_SKIPD")) ctx->fused_skipd = atoi(sk) != 0;  // tuning / test hook
-    const bool cpml_in_launch = ctx->cpml && !ctx->inc && ctx->kernel == K_STREAM &&
-                                fused2d_cpml_supported(ctx->gd, cfg->npml) && !getenv("FWI_NO_FUSED2D_CPML");
-    ctx->fused2d = cfg->ndim == 2 && cfg->dtype == FWI_F32 && (!ctx->cpml || cpml_in_launch) && !getenv("FWI_NO_FUSED2D") &&
-                   (ctx->inc ? cfg->kernel == FWI_KERNEL_AUTO : ctx->kernel == K_STREAM);
-    if (ctx->fused2d && !ctx->cpml && !ctx->inc) ctx->fused_ft = fused2d_pick_tile(ctx->gd);
-    // 3-D fp32 stream contexts: two time steps per pass for forward sweeps without imaging (FWI_STREAM_PAIR=0 /
-    // =1 is the tuning / comparison hook)
-    if (cfg->ndim == 3 && cfg->dtype == FWI_F32 && ctx->kernel == K_STREAM && !ctx->inc && !ctx->cpml) {
-        const char *pe = getenv("FWI_STREAM_PAIR");
-        ctx->pair3d = (pe ? atoi(pe) != 0 : false) && cfg->npml == 0;  // (the two-step kernel exists undamped only)
-        if (ctx->pair3d) {
-            pair3d_default_tuning(ctx->gd, &ctx->pair_zc, &ctx->pair_tw);
-            if (const char *zc = getenv("FWI_PAIR_ZCHUNK")) {
-                const int v = atoi(zc);
-                if (v >= 1) ctx->pair_zc = v;
-            }
-        }
-    }
-    // CPML in 3-D: the z / y borders run as ONE line launch before every step, which hands their term to the step kernel
-    // (both axes or none); with it the 3-D fp32 O(8) stream kernel carries the x border's recursion in its own lanes.
-    // Whatever is left runs as slab phases around the step kernel.
-    if (ctx->cpml && cfg->ndim == 3) ctx->pml_lines = pml_line_axes(ctx->gd, cfg->npml);
-    ctx->xpml = ctx->cpml && ctx->kernel == K_STREAM && ctx->pml_lines == 3 && !getenv("FWI_NO_STREAM_XPML") &&
-                stream_xpml_supported(ctx->gd, ctx->tune, cfg->npml, cfg->dtype == FWI_F32);
     // launch_mode AUTO = stream launches.  hipGraph capture of the time loop was built and measured in round 4 (VERDICT r03
     // item 3) with the mode switched between sweeps of ONE context: -0.6 % (3-D CPML, two kernels per step) ... +1.4 %
     // (2-D 256^2) of the loop time, nothing near the 3 % that would justify a second launch path by default; the host is
     // far ahead of the GPU either way (1.3 ms to submit 500 launches that run 3.1 ms at 256^2).  A first probe that ran the
     // two modes on two contexts side by side had shown the graph 6 - 13 % ahead on the 3-D CPML: an artefact of that set-up
     // (the stream-mode context ran 6 % slower than it does alone), which is why the A/B is done on one context now.
-    if (getenv("FWI_DEBUG_PML"))
-        fprintf(stderr, "fwi: cpml=%d fused2d=%d pair3d=%d x-in-kernel=%d line-axes=%d (ty %d zchunk %d)\n", (int)ctx->cpml,
-                (int)ctx->fused2d, (int)ctx->pair3d, (int)ctx->xpml, ctx->pml_lines, ctx->tune.ty, ctx->tune.zchunk);
-    // 3-D CPML contexts past the cache-resident sizes place their small arrays by measurement (Impl::tune_placement).
-    // FWI_PLACEMENT_TUNE: "0" = off, "pad" = padded allocations without the search (A/B hooks), "force" = also on grids
-    // below the size threshold (tests: the oracle comparisons run small grids), "fixed:<k0>,<k1>,..." = on any grid, NO
-    // search: movable array i (in the search order) sits k_i * 2 MiB into its allocation, the last value repeats (tests:
-    // a layout that is asked for instead of timed; 0 <= k <= 7, anything else is FWI_EINVAL).  A context that places
-    // nothing ignores "fixed:" as it ignores "force".
-    const bool place_on = cfg->dtype == FWI_F32 && cfg->ndim == 3 && ctx->kernel == K_STREAM && !(pt && !strcmp(pt, "0")) &&
-                          ((double)ctx->gd.ptot * ctx->esize >= 48e6 || (pt && !strcmp(pt, "force")) || place_fixed);
-    if (place_on && ctx->xpml) ctx->place_kind = 1;
-    else if (place_on && ctx->inc && !ctx->cpml) ctx->place_kind = 2;
-    const bool place = ctx->place_kind != 0;
-    if (place) ctx->place_pad = (size_t)14 << 20;
-    int rc = place && place_fixed && !fixed_ok
-                 ? ctx->fail(FWI_EINVAL, "FWI_PLACEMENT_TUNE=fixed:<k0>,<k1>,...: one to eight offsets, each 0 ... 7 "
-                                         "(units of 2 MiB)")
-                 : create_impl(ctx);
+    ctx->graph_mode = cfg->launch_mode == FWI_LAUNCH_GRAPH;
+    int rc = create_impl(ctx);
     const size_t vslack = ctx->place_kind ? ctx->place_pad : 0;
     if (rc == FWI_OK && ctx->inc &&
         (ctx->mem.acquire(&ctx->vf, (size_t)ctx->gd.ptot * ctx->esize + vslack, "vf") != hipSuccess ||
@@ -2010,14 +1906,14 @@ int fwi_create(const fwi_config *cfg, fwi_ctx **out) {
                 rc = ctx->fail(FWI_ENOMEM, "allocating the fused 2-D buffer pair failed");
         }
     }
-    if (rc == FWI_OK && place && place_fixed) {
+    if (rc == FWI_OK && ctx->place_mode == PLACE_FIXED) {
         // every allocation was zeroed over its whole padded length where its content matters before the first write
         // (tz, ty, v, C; the x border's psi / zeta are zeroed where they lie at the start of every sweep)
         for (int i = 0; i < ctx->nmov; ++i) {
-            ctx->mov_shift[i] = (size_t)fixed_k[i] * ((size_t)2 << 20);
+            ctx->mov_shift[i] = (size_t)ctx->fixed_k[i] * ((size_t)2 << 20);
             *ctx->mov_slot[i] = (char *)*ctx->mov_slot[i] + ctx->mov_shift[i];
         }
-    } else if (rc == FWI_OK && place && !(pt && !strcmp(pt, "pad"))) {
+    } else if (rc == FWI_OK && ctx->place_mode == PLACE_SEARCH) {
         rc = Impl<float>::tune_placement(ctx);
     }
     if (rc) {

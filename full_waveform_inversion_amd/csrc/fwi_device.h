@@ -12,8 +12,6 @@
 
 namespace fwi {
 
-static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-
 // Source / residual injection into the points a workgroup has just written.  The host sorts a tile's entries by
 // node, so the entries of one node are consecutive: the thread of a run's FIRST entry adds the whole run, in entry
 // order, and issues ONE add per node -- duplicate nodes (two sources on one node) sum in a fixed order:
@@ -153,8 +151,5 @@ __device__ __forceinline__ float rcp_nr(float a) {
     return r * fmaf(-a, r, 2.f);
 }
 __device__ __forceinline__ double rcp_nr(double a) { return 1.0 / a; }
-
-// x tiles of `tile_x` elements: 64 lanes x one 16-byte vector (256 floats / 128 doubles)
-static inline int stream_nxt(const GridDesc &g, int tile_x) { return (int)(round_up(g.nx, tile_x) / tile_x); }
 
 }  // namespace fwi

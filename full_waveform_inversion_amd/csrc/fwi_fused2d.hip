@@ -367,10 +367,6 @@ extern "C" int fwi_debug_fused2d_stamps(unsigned long long *out, int n) {
 }
 #endif
 
-int fused2d_num_tiles(const GridDesc &g, int ft) {
-    return ((g.nx + ft - 1) / ft) * ((g.nz + ft - 1) / ft);
-}
-
 void fused2d_tile_order(const GridDesc &g, int ft, int npml, std::vector<int> &order, int seam) {
     order.clear();
     static const bool off = getenv("FWI_FUSED2D_NO_TILE_ORDER") != nullptr;  // tuning / A-B hook
@@ -401,27 +397,6 @@ void fused2d_tile_order(const GridDesc &g, int ft, int npml, std::vector<int> &o
         acc += cnt[x];
     }
     for (int i = nh; i < nt; ++i) order[i] = rest[start[i & 7] + pos[i & 7]++];
-}
-
-int fused2d_pick_tile(const GridDesc &g) {
-    if (const char *e = getenv("FWI_FUSED2D_TILE")) {
-        const int v = atoi(e);
-        if (v == 64 || v == 32 || v == 16) return v;
-    }
-    // cost of a launch ~ rounds of 256 workgroups x extended tile area (the halo is 4 r = 16 cells whatever the tile:
-    // a 32-point tile computes 4x its own area, a 16-point tile 9x -- worth it only while CUs would idle otherwise)
-    const int HL = (FUSED2D_STEPS * g.r + 3) / 4 * 4;
-    int best = FUSED2D_TILE;
-    int64_t best_cost = -1;
-    for (int ft : {64, 32, 16}) {
-        const int64_t tiles = fused2d_num_tiles(g, ft), e = ft + 2 * HL;
-        const int64_t cost = ((tiles + 255) / 256) * e * e;
-        if (best_cost < 0 || cost < best_cost) {
-            best_cost = cost;
-            best = ft;
-        }
-    }
-    return best;
 }
 
 template <int R, int FT, bool DAMP, bool SKIPD>

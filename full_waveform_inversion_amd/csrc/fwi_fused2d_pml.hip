@@ -42,29 +42,7 @@ struct alignas(16) q4 {
 };
 typedef float nt4 __attribute__((ext_vector_type(4)));
 
-constexpr int cpml_halo(int r) { return (FUSED2D_STEPS * r + 3) / 4 * 4; }
-
 }  // namespace
-
-bool fused2d_cpml_supported(const GridDesc &g, int npml) {
-    if (g.ndim != 2 || g.r != 4 || npml < 1) return false;  // (O(8) is what is instantiated)
-    const int HL = cpml_halo(g.r), FT = FUSED2D_TILE;
-    if (npml > FT - HL) return false;  // the memory-variable images hold 48 border cells
-    // Every tile (whole tiles, one overlap seam per axis: fused2d_origin) must see each border either not at all or
-    // from a side where nothing but the outside of the grid lies beyond it, and never both borders of an axis
-    for (int n : {g.nz, g.nx}) {
-        if (n <= FT) return false;
-        const int nt = (n + FT - 1) / FT;
-        for (int t = 0; t < nt; ++t) {
-            const int lo = fused2d_origin(t, n, FT, 1) - HL, hi = lo + FT + 2 * HL;
-            const bool low = lo < npml, high = hi > n - npml;  // border cells in the extended region
-            if (low && high) return false;
-            if (low && lo > 0) return false;     // the low border would begin inside this tile's halo
-            if (high && hi < n) return false;    // ... the high border end in it
-        }
-    }
-    return true;
-}
 
 // NPB: border width the memory-variable images are sized for (npml <= NPB).  REV: the adjoint recursion.
 // Diagnostic builds only (-DFWI_CPML_ABLATE=bits, timing A/B; results are wrong): 1 = no neighbour pass, 2 = no border

@@ -43,12 +43,10 @@ inline int hip_free_code(void *p) { return (int)hipFree(p); }
 
 }  // namespace fwi
 
-struct fwi_ctx {
+// The context: what was decided for it before anything was allocated (fwi::Plan: gd, kernel, tune, inc, cpml, fused2d, ...;
+// fwi_plan.h), and everything it owns and remembers since.
+struct fwi_ctx : fwi::Plan {
     fwi_config cfg;
-    GridDesc gd;
-    int kernel = K_POINT;
-    StreamTuning tune{8, 0, 1, 256};
-    size_t esize = 4;  // bytes per element
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_loop_time = false;
@@ -66,31 +64,15 @@ struct fwi_ctx {
 
     // device fields
     void *u[2] = {nullptr, nullptr};  // padded wavefields (ping-pong)
-    bool inc = false;                 // increment form: state (u, v = u - u_prev); u[] ping-pongs u, v lives in vf
-    void *vf = nullptr, *fwv = nullptr;  // v of the running sweep / of the checkpointed forward recomputation
-    // 3-D temporal blocking (fwi_pair3d.hip): forward sweeps without imaging advance two steps per pass
-    bool qbf16 = false;  // forward-term store in bf16 (fp32 3-D stream contexts)
-    size_t qes = 4;      // bytes per stored forward-term element
-    bool pair3d = false;
-    int pair_zc = 0, pair_tw = 256;
-    int fused_skipd = -1;  // Fused2dArgs::skipd (FWI_FUSED2D_SKIPD, read at create)
+    void *vf = nullptr, *fwv = nullptr;  // increment form: v of the running sweep / of the checkpointed forward recomputation
     int *fused_order = nullptr;  // Fused2dArgs::tile_order (device; grids of more than one round of tiles with a border)
-    int fused_ft = FUSED2D_TILE;  // interior tile edge of the fused 2-D kernel (fused2d_pick_tile; 64 with CPML / increment)
-    // convolutional PML: memory variables per axis (z, y, x), compact over that axis' border, and 1-D coefficients
-    bool cpml = false;
-    bool xpml = false;  // 3-D fp32 stream contexts: the x border's recursion runs inside the step kernel
-    int pml_lines = 0;  // axes (z = 1, y = 2) whose border runs as one line launch per step (pml_line_axes)
-    // ... whose term T_d the line launch hands to the step kernel: arrays compact over the axis' shell (StepArgs::pml_tz /
-    // pml_ty; scratch within one time step, so one pair serves every sweep of the context)
+    // convolutional PML: memory variables per axis (z, y, x), compact over that axis' border, and 1-D coefficients;
+    // pml_tz / pml_ty: the term T_d that the line launch of an axis in pml_lines hands to the step kernel, arrays compact
+    // over the axis' shell (StepArgs::pml_tz / pml_ty; scratch within one time step: one pair serves every sweep)
     void *pml_tz = nullptr, *pml_ty = nullptr;
     void *pml_psi[3] = {nullptr, nullptr, nullptr}, *pml_zeta[3] = {nullptr, nullptr, nullptr};
-    // Placement of the four small arrays the 3-D CPML step kernel streams beside the fields (the x border's psi and zeta,
-    // the handed-over terms tz and ty): each sits `place_shift` bytes into an allocation `place_pad` bytes longer than
-    // the array, at the position Impl::tune_placement measured as the fastest (0 = untuned; see there)
-    // (place_kind 2, increment-form contexts without CPML: the fields v and C instead -- worth 1.5 - 3 % there, the
-    // per-process spread of that form is not theirs to fix; the u buffers change roles with others and stay put)
-    int place_kind = 0;
-    size_t place_pad = 0;
+    // Placement (Plan::place_kind): each movable array sits mov_shift bytes into an allocation place_pad bytes longer than
+    // the array -- at the position Impl::tune_placement measured as the fastest, or where "fixed:" asked (0 = not moved)
     int nmov = 0;                 // the movable arrays in search order: the member that points at them, their size,
     void **mov_slot[8] = {};      // how far into their allocation they currently sit
     size_t mov_bytes[8] = {}, mov_shift[8] = {};
@@ -115,8 +97,7 @@ struct fwi_ctx {
     void *C = nullptr;                // padded dt^2 c^2
     void *c_dev = nullptr;            // compact velocity
     void *dz = nullptr, *dy = nullptr, *dx = nullptr;
-    void *q_store = nullptr;  // nt_max x npts forward terms
-    int istride = 1;          // imaging stride: the forward term is stored / correlated every istride-th step
+    void *q_store = nullptr;  // nt_max x npts forward terms (every istride-th step)
     void *logical = nullptr;  // nz x ny x nx staging array for host <-> compact copies when cx != nx
     void *g_acc = nullptr;    // compact gradient accumulator
     void *g_out = nullptr;    // compact scratch for fwi_gradient (and fwi_illumination)
@@ -242,13 +223,10 @@ struct fwi_ctx {
     int resid_pts_in = RESID_PTS_NONE;
     void *pin = nullptr;     // pinned host staging for the time series
     size_t cap_pin = 0;
-    // checkpointing (SURVEY s.8f-3): snapshot of (u^n, u^{n-1}) every `ckpt` steps instead of the
-    // imaging term of every step; q_store then holds ckpt + 1 slots and fwd[] the recomputed fields
-    int ckpt = 0;
+    // checkpointing (Plan::ckpt): q_store holds ckpt + 1 slots and fwd[] the recomputed fields
     bool ckpt_ready = false;  // every checkpoint buffer below is allocated
     void *snap = nullptr, *fwd[2] = {nullptr, nullptr};
-    // 2-D temporal blocking: second buffer pair the fused kernel writes into, and whether it is used
-    bool fused2d = false;
+    // temporal blocking (fused2d, pair3d): second buffer pair the kernel writes into
     void *fx[2] = {nullptr, nullptr};   // second pair for the time sweep in flight
     void *fwx[2] = {nullptr, nullptr};  // second pair for the checkpointed forward recomputation
 

@@ -6,38 +6,9 @@
 
 #include <vector>
 
+#include "fwi_plan.h"  // GridDesc, StreamTuning, the layout constants, the host predicates
+
 namespace fwi {
-
-// Layout halo of every padded field: 4 cells on each side of every stencil
-// axis, whatever the order (4 floats = 16 B keeps interior rows float4-aligned).
-constexpr int HALO = 4;
-// Padded extents: x to XALIGN cells plus one shared halo (tight rows: slack between rows costs HBM efficiency, make_grid),
-// y to YALIGN rows.
-constexpr int XALIGN = 4;
-constexpr int YALIGN = 16;
-// Zero planes appended behind the far z halo of 3-D fields: the stream kernel reads up to
-// r + PF (<= 4 + 3) planes past the last interior plane without clamping.
-constexpr int LOOKAHEAD = 4;
-
-// Padded field geometry.  Element (z, y, x) of the interior lives at
-// off0 + z*sz + y*sy + x.  2-D grids are ny = 1 with no y halo (sz == sy).
-struct GridDesc {
-    int ndim, nz, ny, nx;
-    int cx;          // row stride of COMPACT arrays: nx rounded up to 4, so that rows stay 16-byte
-                     // aligned for any nx; the cx - nx pad columns hold zeros
-    int r;           // stencil radius (order / 2)
-    int64_t sy, sz;  // padded strides in elements (x stride is 1)
-    int64_t off0;    // padded offset of interior point (0, 0, 0)
-    int64_t ptot;    // elements of one padded field
-    int64_t npts;    // nz * ny * cx: elements of one compact array (pad columns included)
-};
-
-// `xpitch_extra`: floats of slack added to the (tight) x pitch -- the A/B hook behind DESIGN.md's pitch sweep; fwi_create
-// reads FWI_XPITCH_EXTRA once per process and passes it here (it is not consulted on any other path).
-GridDesc make_grid(int ndim, int nz, int ny, int nx, int order, int xpitch_extra = 0);
-// Widest x tile of any step kernel in elements (64 lanes x one float4): the tail behind the last row of a padded field
-// covers the edge loads of such a tile whose row ends early (values never used).
-constexpr int MAX_TILE_X = 256;
 
 template <typename T>
 struct StepArgs {
@@ -93,16 +64,6 @@ struct StepArgs {
     int nrec;
 };
 
-enum StencilKernel { K_POINT = 1, K_STREAM = 2 };
-
-struct StreamTuning {
-    int ty;      // rows per workgroup (4 or 8)
-    int zchunk;  // planes marched per workgroup
-    int pf;      // planes fetched ahead of use (1..3)
-    int tile_x;  // x extent of a tile in elements: at most 64 lanes x one 16-byte vector (256 fp32 /
-                 // 128 fp64); the 3-D kernel takes narrower, equal tiles when nx is not a multiple of that
-};
-
 // Workgroup tile of the stream kernel that owns grid point (z, y, x): the index
 // into StepArgs::inj_start.  Must match the kernel's block decode.
 int stream_tile_of(const GridDesc &g, const StreamTuning &t, int z, int y, int x);
@@ -111,13 +72,6 @@ int stream_num_tiles(const GridDesc &g, const StreamTuning &t);
 // Same for the point kernel (64 x 4 point workgroups).
 int point_tile_of(const GridDesc &g, int z, int y, int x);
 int point_num_tiles(const GridDesc &g);
-
-// True when the stream kernel supports this grid / dtype.
-bool stream_supported(const GridDesc &g, bool is_f32);
-// `extra_bytes`: what a time step touches beside the three padded fields (the increment form's fourth field, the CPML's
-// memory variables and handed-over terms): it decides whether the step is Infinity-Cache resident, i.e. which regime the
-// launch shape is chosen for.
-StreamTuning stream_default_tuning(const GridDesc &g, bool is_f32, double extra_bytes = 0.0);
 
 template <typename T>
 hipError_t launch_step(int kernel, const GridDesc &g, const StepArgs<T> &a, const StreamTuning &t,
@@ -183,10 +137,7 @@ template <typename T>
 hipError_t launch_residual_l2(const T *syn, T *obs_inout, int64_t n, double *part, hipStream_t s);
 
 // ---- convolutional PML (fwi_pml.hip): slab kernels around the undamped step kernels ------------------------
-// The SHELL of an axis of n cells: its two borders and the r cells inward that their term reaches (the rows whose
-// update takes a CPML term of that axis).  When the two shells meet (n < 2 npml + 3 r, the line kernel's one-segment
-// case) the shell is the whole axis.  Rows are numbered low border first.
-__host__ __device__ inline int pml_shell_rows(int n, int npml, int r) { return n < 2 * npml + 3 * r ? n : 2 * (npml + r); }
+// (the shell of an axis: pml_shell_rows, fwi_plan.h)
 __host__ __device__ inline bool pml_in_shell(int j, int n, int npml, int r) {
     return n < 2 * npml + 3 * r || j < npml + r || j >= n - npml - r;
 }
@@ -216,18 +167,11 @@ hipError_t launch_pml(const GridDesc &g, const PmlArgs<T> &p, int phase, int rev
 // Line form of the z / y border (3-D): ONE launch for both axes BEFORE the step kernel advances the memory variables
 // and writes the border's term into PmlArgs::tz / ty (a thread marches its line through the border with the field and
 // the new memory variables in register windows); the step kernel adds the term inside q (StepArgs::pml_tz / pml_ty).
-// pml_line_axes: the axes (z = 1, y = 2) it takes for this grid -- the slab phases are then run without them.
-int pml_line_axes(const GridDesc &g, int npml);
+// (pml_line_axes, fwi_plan.h: the axes (z = 1, y = 2) it takes for this grid -- the slab phases are then run without them)
 template <typename T>
 hipError_t launch_pml_lines(const GridDesc &g, const PmlArgs<T> &p, int reverse, hipStream_t s, int axes);
-// True when the 3-D stream kernel can carry the x border's recursion in its lanes (see step3d_stream, XP)
-bool stream_xpml_supported(const GridDesc &g, const StreamTuning &t, int npml, bool is_f32);
 
-// ---- 2-D temporal blocking (fwi_fused2d.hip): FUSED2D_STEPS time steps per launch ----------------
-constexpr int FUSED2D_STEPS = 4;   // time steps advanced per launch
-constexpr int FUSED2D_TILE = 64;   // interior tile edge (points) of a grid that fills the chip with such tiles; extended
-                                   // edge = TILE + 2 STEPS r.  Smaller grids take 32- or 16-point tiles (Fused2dArgs::ft)
-
+// ---- 2-D temporal blocking (fwi_fused2d.hip): FUSED2D_STEPS time steps per launch (fwi_plan.h) ----
 struct Fused2dArgs {
     const float *u_cur, *u_prev, *C;   // padded inputs: u^n, u^{n-1}, dt^2 c^2
     float *out_cur, *out_prev;         // padded outputs: u^{n+K}, u^{n+K-1} (a different buffer pair)
@@ -271,23 +215,6 @@ struct Fused2dArgs {
     float pml_dk[5], pml_dk1[5];
 };
 
-// Tiling of an axis of n cells by WHOLE tiles of ft cells with one overlap seam in the middle -- the fused 2-D kernel
-// with the CPML inside, whose border tiles must be whole (the recursion reaches 2 r cells per sub-step, so a border cell
-// may not sit in a tile's halo): the lower half of the tiles starts at t * ft, the upper half is anchored at the high
-// end (origins rounded up to a 16-byte group; the last tile may overhang n by <= 3 cells like any partial tile), and the
-// two tiles either side of the seam overlap by nt * ft - n cells in the interior of the grid, which both compute and
-// the lower one stores.  `seam` = 0: the plain tiling t * ft.  fused2d_own: the first cell of tile t that t owns.
-__host__ __device__ inline int fused2d_origin(int t, int n, int ft, int seam) {
-    const int nt = (n + ft - 1) / ft;
-    return (!seam || nt < 2 || t < nt / 2) ? t * ft : ((n - (nt - t) * ft + 3) & ~3);
-}
-__host__ __device__ inline int fused2d_own(int t, int n, int ft, int seam) {
-    return t == 0 ? 0 : fused2d_origin(t - 1, n, ft, seam) + ft;  // (= the tile's origin except just above the seam)
-}
-int fused2d_num_tiles(const GridDesc &g, int ft = FUSED2D_TILE);
-// Tile edge that minimises rounds of workgroups x extended tile area (a 512^2 grid makes 64 tiles of 64^2 -- a
-// quarter of the chip -- but 256 of 32^2); FWI_FUSED2D_TILE overrides (tuning / tests).
-int fused2d_pick_tile(const GridDesc &g);
 // Grids of more than one round of tiles: the order in which the workgroups take the tiles.  Tiles whose extended
 // region reaches into the absorbing border do more work per sub-step (the damped update; with the CPML the border
 // recursion, ~2x an interior tile): they go FIRST, dealt evenly over the XCDs, corners before edges, so that the launch
@@ -295,13 +222,9 @@ int fused2d_pick_tile(const GridDesc &g);
 // or less (the kernel's own numbering is kept).
 void fused2d_tile_order(const GridDesc &g, int ft, int npml, std::vector<int> &order, int seam = 0);
 hipError_t launch_fused2d(const GridDesc &g, const Fused2dArgs &a, hipStream_t s);
-// True when the fused kernel can carry the CPML of this grid: every border cell a tile sees lies deep inside that
-// tile's extended region or against the outside of the grid (conditions at fused2d_cpml_supported).
-bool fused2d_cpml_supported(const GridDesc &g, int npml);
 hipError_t launch_fused2d_cpml(const GridDesc &g, const Fused2dArgs &a, hipStream_t s);
 
 // ---- 3-D temporal blocking (fwi_pair3d.hip): two time steps per pass, fp32, forward sweeps without imaging ----
-constexpr int PAIR3D_TY = 8;   // interior rows (= waves) per workgroup
 struct Pair3dInj {             // one source term as seen by one workgroup
     int z, yoff, xoff;         // plane; row relative to the tile's first interior row; column relative to lane 0's
     int col;                   // column of the amplitude rows
@@ -323,7 +246,6 @@ struct Pair3dArgs {
     float rec_scale;
     int nrec;
 };
-void pair3d_default_tuning(const GridDesc &g, int *zchunk, int *tw);
 int pair3d_num_tiles(const GridDesc &g, int zchunk, int tw);
 int pair3d_tile_of(const GridDesc &g, int zchunk, int tw, int z, int y, int x);
 hipError_t launch_pair3d(const GridDesc &g, const Pair3dArgs &a, int zchunk, int tw, hipStream_t s);

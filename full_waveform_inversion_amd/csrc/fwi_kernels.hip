@@ -16,39 +16,6 @@
 
 namespace fwi {
 
-GridDesc make_grid(int ndim, int nz, int ny, int nx, int order, int xpitch_extra) {
-    GridDesc g;
-    g.ndim = ndim;
-    g.nz = nz;
-    g.ny = (ndim == 3) ? ny : 1;
-    g.nx = nx;
-    g.r = order / 2;
-    const int hy = (ndim == 3) ? HALO : 0;
-    // x pitch: TIGHT -- nx rounded to XALIGN (4: one 16-byte lane) plus ONE halo: the HALO zero cells right of a row are the HALO cells left
-    // of the next (nothing writes them).  Every kernel clamps its lanes' addresses into [0, nx] + the halo, so no tile needs
-    // slack, and the unused bytes between rows are expensive: until round 3 rows were 4 + roundup(nx, 256) + 4 floats, which
-    // cost the 3-D sizes that are not multiples of 256 up to a quarter of their HBM-regime rate (512 x 512 x 384 280 -> 354
-    // Gpts/s, 448^3 299 -> 351, 640^3 293 -> 333, 320^3 266 -> 325, 272^3 277 -> 339, 384^3 289 -> 323).  Pitch sweep at 512^3,
-    // nx + 8 / 16 / 24 / 32 / 64 / 128 / 256 floats: 350 / 340 / 317 / 305 / 292 / 287 / 276 Gpts/s; nx + 4 against nx + 8: 256^3
-    // 424 -> 434, 384^3 301 -> 305.  2-D (cache-resident up to ~4096^2): +1..2 % at every size from 1000^2 to 8192^2.
-    // `xpitch_extra` (FWI_XPITCH_EXTRA floats, read once by fwi_create) is the A/B hook.
-    g.sy = HALO + round_up(nx, XALIGN) + std::max(0, xpitch_extra / 4 * 4);
-    // (rows whose interior starts on a 128-byte line -- pitch nx + 32 with the gap shared as right / left halo -- were
-    // measured as well: 256^3 +2 %, 512^3 +1 %, 640^3 -8 %: not adopted)
-    // (sharing the y-halo rows between consecutive planes the same way was measured: within noise, 512^3 349 vs 352)
-    const int64_t py = (ndim == 3) ? HALO + round_up(g.ny, YALIGN) + HALO : 1;
-    g.sz = g.sy * py;
-    g.off0 = (int64_t)HALO * g.sz + (int64_t)hy * g.sy + HALO;
-    // 2-D: rows are the tiled axis of step2d_tile, so they are rounded like y is in 3-D.
-    // 3-D: LOOKAHEAD extra zero planes behind the far z halo, so the stream kernel's prefetches of
-    // planes z + r + 1 ... need no clamping (affine addresses: the plane offsets strength-reduce).
-    g.ptot = g.sz * (int64_t)(((ndim == 2) ? round_up(nz, YALIGN) : nz + LOOKAHEAD) + 2 * HALO) + HALO + 2 * MAX_TILE_X;  // (+ the last row's right halo, and
-                                        // the edge loads of a 256-column tile whose row ends early: values never used)
-    g.cx = (int)round_up(nx, 4);
-    g.npts = (int64_t)nz * g.ny * g.cx;
-    return g;
-}
-
 // ---------------------------------------------------------------------------
 // POINT kernel: one thread per grid point, all 4r+... neighbours straight from
 // global memory (L1/L2 absorb the re-reads).  Generic in dtype, order and
@@ -265,102 +232,6 @@ int stream_num_tiles(const GridDesc &g, const StreamTuning &t) {
     const int nxt = stream_nxt(g, t.tile_x);
     if (g.ndim == 2) return nxt * ((g.nz + t.ty - 1) / t.ty);
     return nxt * ((g.ny + t.ty - 1) / t.ty) * ((g.nz + t.zchunk - 1) / t.zchunk);
-}
-
-bool stream_supported(const GridDesc &g, bool is_f32) {
-    if (g.nz < 1) return false;
-    // any nx: the padded fields and the compact arrays (row stride cx = nx rounded up to 4) keep every
-    // lane's 16-byte vector aligned; lanes straddling x = nx compute zeros there (C = 0 in the pad)
-    if (is_f32) return true;                  // float4 lanes (3-D stream kernel, 2-D tile kernel)
-    return g.ndim == 3;                       // double2 lanes: 3-D stream kernel only
-}
-
-bool stream_xpml_supported(const GridDesc &g, const StreamTuning &t, int npml, bool is_f32) {
-    if (g.ndim != 3 || !is_f32 || g.r != 4 || npml < 4) return false;
-    // (a lane's four cells lie wholly inside or outside the border when npml % 4 == 0; an even npml leaves one lane per
-    // side astride the inner edge, whose stores are masked (stream_xpml_partial); the high side's lanes stay 16-byte
-    // aligned in the slab row because nx - 2 npml is a multiple of 4)
-    if (npml % 2 || g.nx % 4) return false;
-    if (g.nx < 2 * (npml + g.r)) return false;         // the two borders (and their reach) do not meet
-    const int tw = t.tile_x, nxt = stream_nxt(g, tw);
-    // each border and the r cells it reaches into lie inside ONE tile row, i.e. inside one wave
-    return tw >= npml + g.r && g.nx - (nxt - 1) * tw >= npml + g.r;
-}
-
-StreamTuning stream_default_tuning(const GridDesc &g, bool is_f32, double extra_bytes) {
-    const int full_x = is_f32 ? 256 : 128, vl = is_f32 ? 4 : 2;
-    // 3-D: split nx into equal x tiles (multiples of the lane vector) rather than full ones plus a remainder
-    const int nxt0 = (g.nx + full_x - 1) / full_x;
-    const int tile_x = (g.ndim == 2) ? full_x : (int)round_up((g.nx + nxt0 - 1) / nxt0, vl);
-    // 2-D: rows per workgroup.  16 is 7 % faster for a lone shot (6.98 vs 7.46 us/step at 1024^2) but
-    // 8 co-schedules better when several shots share the GPU (4 concurrent: 3.5 vs 4.4 us/step/shot).
-    if (g.ndim == 2) return StreamTuning{8, 1, 1, tile_x};
-    // Measured on MI355X (tools/tune_stream.py, tools/size_sweep.py; profiles/r02_stream_tuning_sweep.txt).  Two
-    // things decide: every z chunk re-reads 2r halo planes and pays a prologue (~10 planes' worth), so chunks should
-    // be long; and workgroups run in rounds of one per CU (256), so the last round should not be a sliver -- a grid
-    // whose tiles make 288 columns (768^3 with 8-row tiles) spends its second round on 32 workgroups (235 Gpts/s;
-    // 305 with 96-plane chunks = 9 full rounds).  Cost of a candidate (rows per tile, chunks), relative to ideal,
-    // with W = the workgroups that saturate the memory system:
-    //   (1 + 10 / zchunk) x sum over rounds of max(1, workgroups in the round / W), over (workgroups / W)
-    // Two regimes: while the three fields fit the Infinity Cache every CU counts (W = 256) and 4-row tiles cost
-    // nothing extra -- their third read of a y row hits in L2; from HBM ~200 workgroups already saturate (W = 200;
-    // 384^3 is fastest with 192 workgroups of 192 planes, not with 768 of 48) and the 4-row tile's extra row reads
-    // show (200 x 400 x 400: TY 8 x 100 planes 283 Gpts/s, TY 4 x 200 planes 240).  The model reproduces the
-    // hand-tuned choices of round 1 (256^3: TY 4 x 64 planes, 407 Gpts/s vs TY 8 x 32 347; 512^3: TY 8 x 256, 328 vs
-    // TY 4 x 256 302) and the measured ranking of the chunk lengths at 300^3, 384^3 and 768^3; against the round-1
-    // rule (one round, then stop; FWI_STREAM_TUNING=legacy) it changes 700^3 (+39 %) and 768^3 (+24 %) and nothing
-    // else from 96^3 to 1024^3.  What it cannot fix: a grid whose columns make 192 - 240 workgroups runs at about
-    // that share of the 512^3 rate (384^3: 280 vs 352 Gpts/s) -- per-CU throughput is bounded (neither a deeper
-    // prefetch, PF = 2, nor fuller waves, 32-lane rows for 100 % lane use at 384^3, moved it: both measured, both
-    // dropped), and shorter chunks to fill more rounds cost more in halo planes than the idle CUs do.
-    static const bool legacy = getenv("FWI_STREAM_TUNING") && !strcmp(getenv("FWI_STREAM_TUNING"), "legacy");
-    if (legacy) {
-        StreamTuning best{4, g.nz, 1, tile_x};
-        for (int ty : {8, 4}) {
-            const int64_t tiles_xy = stream_nxt(g, tile_x) * (round_up(g.ny, ty) / ty);
-            const int nzc = (int)std::max<int64_t>(1, std::min<int64_t>(g.nz, 256 / std::max<int64_t>(1, tiles_xy)));
-            const int zc = std::max((g.nz + nzc - 1) / nzc, std::min(g.nz, 16));
-            best = StreamTuning{ty, zc, 1, tile_x};
-            if (zc >= 64 || zc >= g.nz) break;  // long enough chunks with 8-row tiles: keep them
-        }
-        return best;
-    }
-    constexpr double CUS = 256.0, PROLOGUE = 10.0;
-    // (200 MiB: 256^3 = 192 MiB is resident, 272^3 = 230 MiB measurably is not -- it runs 12 % faster tuned as HBM)
-    // Round 4: everything the step touches counts, not the three fields alone -- 256^3 with a 16-cell CPML (fields + 50 MB of
-    // memory variables + 21 MB of handed-over terms) or in increment form (a fourth field) is an HBM-regime problem and
-    // wants the HBM-regime shape: 8-row tiles x 32 planes instead of 4 x 64 (CPML forward 83.3 -> 71.1, adjoint 102.7 -> 93.6
-    // us/step on one box; increment form 67.8 / 81.3 / 77.3 -> 63.7 / 76.7 / 75.4) -- once the 8-row x-border variants
-    // stopped spilling, that is: in round 3 the same choice measured 116 against 100.
-    const bool cache_resident = 3.0 * (double)g.npts * (is_f32 ? 4 : 8) + extra_bytes <= 200.0 * 1024 * 1024;
-    // (the kernels that carry extras -- the x border's recursion, the handed-over terms, the increment field -- have a
-    // longer dependency chain per plane: every CU counts for them even from HBM.  Measured at 256^3 with the CPML: 8 rows
-    // x 32 planes = 256 workgroups 71.6 / 79.8 / 93.7 us/step forward / store / adjoint, x 37 planes = 224 workgroups -- what
-    // W = 200 picks -- 81.6 / 97.1 / 100.4, round 3's 4 rows x 64 planes 84.1 / 95.6 / 103.3; at 320^3 one round of 240
-    // workgroups 188 against 248 for 320 or 160 of them)
-    const double WSAT = (cache_resident || extra_bytes > 0.0) ? 256.0 : 200.0, TY4_PENALTY = cache_resident ? 1.0 : 1.15;
-    StreamTuning best{8, g.nz, 1, tile_x};
-    double best_cost = 1e30;
-    const int zc_min = std::min(g.nz, 16);
-    for (int ty : {8, 4}) {
-        const int64_t tiles_xy = stream_nxt(g, tile_x) * (round_up(g.ny, ty) / ty);
-        int last_zc = 0;
-        for (int nzc = 1; nzc <= g.nz; ++nzc) {
-            const int zc = (g.nz + nzc - 1) / nzc;
-            if (zc < zc_min) break;
-            if (zc == last_zc) continue;
-            last_zc = zc;
-            const double nblk = (double)tiles_xy * ((g.nz + zc - 1) / zc);
-            const double full = std::floor(nblk / CUS), rem = nblk - full * CUS;
-            const double rounds = full * (CUS / WSAT) + (rem > 0 ? std::max(1.0, rem / WSAT) : 0.0);
-            const double cost = (1.0 + PROLOGUE / zc) * rounds / (nblk / WSAT) * (ty == 4 ? TY4_PENALTY : 1.0);
-            if (cost < best_cost - 1e-9) {
-                best_cost = cost;
-                best = StreamTuning{ty, zc, 1, tile_x};
-            }
-        }
-    }
-    return best;
 }
 
 template <typename T>

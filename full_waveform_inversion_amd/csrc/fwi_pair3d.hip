@@ -278,21 +278,6 @@ int pair3d_num_tiles(const GridDesc &g, int zchunk, int tw) {
     return nxt * ((g.ny + PAIR3D_TY - 1) / PAIR3D_TY) * ((g.nz + zchunk - 1) / zchunk);
 }
 
-void pair3d_default_tuning(const GridDesc &g, int *zchunk, int *tw) {
-    // x: one tile for rows of <= 256 columns, else equal tiles of <= 240 interior columns (multiples of 4)
-    int t = 256;
-    if (g.nx > 256) {
-        const int n = (g.nx + 239) / 240;
-        t = ((g.nx + n - 1) / n + 3) & ~3;
-    }
-    *tw = t;
-    const int nxt = g.nx <= 256 ? 1 : (g.nx + t - 1) / t;
-    const int64_t cols = (int64_t)nxt * ((g.ny + PAIR3D_TY - 1) / PAIR3D_TY);
-    // one resident round of workgroups (256 CUs): as few z chunks as that allows (each re-computes 2r planes)
-    const int nzc = (int)std::max<int64_t>(1, std::min<int64_t>(g.nz, 256 / std::max<int64_t>(1, cols)));
-    *zchunk = std::max((g.nz + nzc - 1) / nzc, std::min(g.nz, 16));
-}
-
 // workgroup (in the kernel's renumbered order) that owns interior point (z, y, x)
 int pair3d_tile_of(const GridDesc &g, int zchunk, int tw, int z, int y, int x) {
     const int nxt = g.nx <= 256 ? 1 : (g.nx + tw - 1) / tw;

@@ -418,7 +418,6 @@ __global__ __launch_bounds__(256) void pml_kernel_x4(PmlArgs<float> p, GridDesc 
 // 4 B (C) + 8 B (u') [+ 8 B (v') + 8 B (q)], the kernel has no optional operands left, and the z and the y lines share
 // ONE launch (block ranges): 2 launches per time step instead of 3.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int PML_LINE_MAXC = 192;  // rows of the coefficient tables (pml_line_axes checks)
 
 template <typename T, int R, int D, bool REV, int VL>
 __device__ __forceinline__ void pml_line_body(const PmlArgs<T> &p, const GridDesc &g, int bxi, int boi, int seg, T *ca,
@@ -673,22 +672,6 @@ __global__ __launch_bounds__(256) void pml_line_t(PmlArgs<T> p, GridDesc g, int 
         const int bxi = b % gx, t = b / gx;
         pml_line_body<T, R, 1, REV, VL>(p, g, bxi, t % goy, t / goy, ca, cb, cin);
     }
-}
-
-// Axes (bit mask: z = 1, y = 2) the line form takes for this grid: both or none (the step kernels take the handed-over
-// term of both axes together); the slab phases keep the rest.
-int pml_line_axes(const GridDesc &g, int npml) {
-    const bool off = getenv("FWI_NO_PML_LINES") != nullptr;  // (read per context: the tests switch it)
-    if (off || g.ndim != 3 || npml < 1) return 0;
-    const int nd[2] = {g.nz, g.ny};
-    for (int d = 0; d < 2; ++d) {
-        constexpr int B = 4;
-        const int n = nd[d], r = g.r, W = (2 * r + B - 1) / B * B;
-        const int len = n < 2 * npml + 3 * r ? n : npml + r;            // cells of a segment
-        const int rows = (len + W + B - 1) / B * B + 3 * r + B;         // table rows the kernel fills
-        if (rows > PML_LINE_MAXC || n < 1) return 0;
-    }
-    return 3;
 }
 
 // 16-byte lanes for fp64 and (round 4) fp32 O(8), 8-byte for fp32 O(2) / O(4).
