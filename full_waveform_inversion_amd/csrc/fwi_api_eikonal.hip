@@ -1,5 +1,5 @@
 // C-ABI of the engine, first-arrival traveltimes (include/fwi.h: fwi_eikonal*, fwi_vec_scatter_points,
-// fwi_vec_gather_points).  Host side only: argument checks, the launch loops of the two block-Jacobi iterations and
+// fwi_vec_gather_points).  Host side only: argument checks, the launch loops of the three block-Jacobi iterations and
 // their stopping rule.  Works on vector slots and the compact velocity; no sweep state is read or written.
 #include <algorithm>
 #include <cmath>
@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "fwi_eikonal.h"
+#include "fwi_eikonal_tangent.h"
 #include "fwi_host.h"
 
 namespace {
@@ -124,6 +125,24 @@ struct Impl {
         return iterate(ctx, "fwi_eikonal_adjoint", (T *)vl, (T *)vs, max_sweeps, launches_out,
                        [&](T *in, T *out, int K, int *flag) {
                            return launch_eikonal_adjoint_sweep<T>(g, t, b, in, out, c, h, K, flag, s);
+                       });
+    }
+
+    static int tangent(fwi_ctx *ctx, int32_t wrt, const void *vt, const void *vd, void *vo, void *vs,
+                       const std::vector<int64_t> &idx, const double *dist, int64_t ref, int32_t max_sweeps,
+                       int32_t *launches_out) {
+        const GridDesc &g = ctx->gd;
+        const T *t = (const T *)vt, *dm = (const T *)vd, *c = (const T *)ctx->c_dev;
+        int rc = upload_points(ctx, idx, dist);
+        if (rc) return rc;
+        const double h = ctx->cfg.h;
+        const int wv = wrt == FWI_WRT_VELOCITY;
+        hipStream_t s = ctx->stream;
+        HIPCHK(ctx, launch_eikonal_tangent_init<T>(g, t, dm, c, (T *)vo, (T *)vs, h, wv, (const int64_t *)ctx->eik_idx.p,
+                                                   (const T *)ctx->eik_val.p, ref, (int)idx.size(), s));
+        return iterate(ctx, "fwi_eikonal_tangent", (T *)vo, (T *)vs, max_sweeps, launches_out,
+                       [&](T *in, T *out, int K, int *flag) {
+                           return launch_eikonal_tangent_sweep<T>(g, t, dm, in, out, c, h, wv, K, flag, s);
                        });
     }
 
@@ -255,6 +274,28 @@ int fwi_eikonal_gradient(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t lam_
     if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_eikonal_gradient: no model set");
     (void)hipSetDevice(ctx->cfg.device);
     return DISPATCH_CALL(ctx, gradient, wrt, vt, vl, vo, beta, nodes, init_dist, ref);
+}
+
+int fwi_eikonal_tangent(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t dm_slot, int32_t out_slot,
+                        int32_t scratch_slot, int32_t n_init, const int32_t *init_idx, const double *init_dist,
+                        const int32_t *ref_idx, int32_t max_sweeps, int32_t *launches_out) {
+    if (!ctx) return FWI_EINVAL;
+    VEC_OR_FAIL(ctx, vt, t_slot);
+    VEC_OR_FAIL(ctx, vd, dm_slot);
+    VEC_OR_FAIL(ctx, vo, out_slot);
+    VEC_OR_FAIL(ctx, vs, scratch_slot);
+    if (wrt != FWI_WRT_VELOCITY && wrt != FWI_WRT_SLOWNESS2)
+        return ctx->fail(FWI_EINVAL, "fwi_eikonal_tangent: unknown parametrisation wrt = %d", (int)wrt);
+    if (vt == vd || vt == vo || vt == vs || vd == vo || vd == vs || vo == vs)
+        return ctx->fail(FWI_EINVAL, "fwi_eikonal_tangent: t_slot, dm_slot, out_slot and scratch_slot must be four "
+                         "different slots (got %d, %d, %d, %d)", (int)t_slot, (int)dm_slot, (int)out_slot, (int)scratch_slot);
+    std::vector<int64_t> nodes;
+    int64_t ref = 0;
+    int rc = init_list(ctx, "fwi_eikonal_tangent", n_init, init_idx, init_dist, ref_idx, nodes, &ref);
+    if (rc) return rc;
+    if (!ctx->have_model) return ctx->fail(FWI_ESTATE, "fwi_eikonal_tangent: no model set");
+    (void)hipSetDevice(ctx->cfg.device);
+    return DISPATCH_CALL(ctx, tangent, wrt, vt, vd, vo, vs, nodes, init_dist, ref, max_sweeps, launches_out);
 }
 
 }  // extern "C"

@@ -24,6 +24,11 @@ both zero where ``T_i < G_i``; ``lambda = b + A^T lambda`` with ``A_ij = dG_i/dT
 iteration stops bit-exactly), ``g_s = (dG/ds) lambda`` plus ``sum_i d_i lambda_i`` over the source-determined listed
 nodes at ``ref``.
 
+The tangent (``fwi_eikonal_tangent``) differentiates the same fixed point forwards: with
+``ds = -dm / c^2`` (or ``dm c / 2`` for ``m = 1 / c^2``), ``b = (dG/ds) ds`` and ``b_i = d_i ds[ref]`` on the
+source-determined listed nodes, ``x = b + A x`` in gather form, by the same Jacobi iteration.  It is the exact transpose
+of the adjoint followed by the gradient.
+
 Out of scope: the factored eikonal equation, second-order stencils, anisotropy and later arrivals.  The scheme is first
 order: 0.3 - 1.2 % of ``max T`` on 101^2 - 401^2 grids (the table in DESIGN.md), most of it from the source's
 neighbourhood, which a ball of a few cells (``radius``) reduces.
@@ -264,6 +269,58 @@ def gradient(T, lam, c, h, init, wrt="velocity", ball_term=True):
     return -gs / (c * c) if wrt == "velocity" else gs * c / dtype.type(2)
 
 
+def tangent_sweep(x, b, W, lower):
+    """``b + A x`` in gather form: cell ``i`` reads its own upwind neighbour on every axis (the lower-index one where
+    ``lower[d]``), the terms added axis by axis in ascending order after ``b``"""
+    zero = x.dtype.type(0)
+    out = b.copy()
+    for d in range(x.ndim):
+        out = out + W[d] * np.where(lower[d], _shift(x, d, -1, zero), _shift(x, d, +1, zero))
+    return out
+
+
+def tangent_rhs(T, c, h, dm, init, wrt="velocity", ball_term=True):
+    """``(b, W, lower)`` of :func:`tangent`: ``b = (dG/ds) ds`` with ``ds = -dm / c^2`` (``wrt="velocity"``) or
+    ``dm c / 2`` (``"slowness2"``), the transposes of the two conversions of :func:`gradient`, and
+    ``b_i = dist_k ds[ref]`` on the listed nodes that are source-determined (``T_i < G_i``)"""
+    if wrt not in WRT:
+        raise ValueError("wrt must be one of %r" % (WRT,))
+    dtype = T.dtype
+    c = np.asarray(c, dtype=dtype)
+    dm = np.asarray(dm, dtype=dtype)
+    if dm.shape != T.shape:
+        raise ValueError("dm must have the grid's shape %r, got %r" % (T.shape, dm.shape))
+    W, lower, dGds = derivatives(T, c, h)
+    ds = -dm / (c * c) if wrt == "velocity" else dm * c / dtype.type(2)
+    b = dGds * ds
+    if ball_term:
+        idx, dist, ref = init
+        G = local_solution([t for t, _ in upwind(T)], _slowness(c, dtype) * dtype.type(h))
+        for k in range(len(dist)):
+            i = tuple(idx[k])
+            if T[i] < G[i]:
+                b[i] = dtype.type(dist[k]) * ds[tuple(ref)]
+    return b, W, lower
+
+
+def tangent(T, c, h, dm, init, wrt="velocity", return_sweeps=False, ball_term=True, max_sweeps=None):
+    """The derivative of the fixed point ``T`` along the model perturbation ``dm``, in ``T``'s dtype:
+    ``x = b + A x`` (``A`` and ``b`` of :func:`tangent_rhs`) by Jacobi from ``x = b``, recomputed in full until a sweep
+    changes no bit (``A`` is strictly causal: it stops after the longest dependency chain).  Where ``T_i = +inf`` or
+    the cell is not live, ``x_i = b_i``.  ``max_sweeps=None``: ``4 * sum(shape)``; ``RuntimeError`` beyond the cap.  The
+    exact transpose of :func:`adjoint` followed by :func:`gradient`; on the
+    non-differentiable set the same one-sided choice."""
+    b, W, lower = tangent_rhs(T, c, h, dm, init, wrt, ball_term)
+    x = b.copy()
+    cap = 4 * sum(T.shape) if max_sweeps is None else int(max_sweeps)
+    for n in range(1, cap + 1):
+        xn = tangent_sweep(x, b, W, lower)
+        if np.array_equal(xn, x):
+            return (x, n) if return_sweeps else x
+        x = xn
+    raise RuntimeError("eikonal.tangent: no fixed point after %d sweeps" % cap)
+
+
 def times_at(T, rec):
     """Times at receivers: node indices ``(n, ndim)`` or a ``points.Spread`` (multilinear weights)"""
     if hasattr(rec, "pt_start"):
@@ -290,8 +347,8 @@ def exact_gradient(shape, h, c0, g, coords):
 
 
 class TwinEngine:
-    """The five engine calls ``shots.traveltime_fg`` needs, backed by this module on the CPU (tests, prototypes): model
-    and slots are host arrays."""
+    """The engine calls ``shots.traveltime_fg`` and ``shots.TraveltimeOperator`` need, backed by this module on the CPU
+    (tests, prototypes): model and slots are host arrays."""
 
     def __init__(self, shape, h, dtype=np.float64):
         self.shape, self.h, self.dtype = tuple(shape), float(h), np.dtype(dtype)
@@ -338,3 +395,31 @@ class TwinEngine:
     def eikonal_gradient(self, t_slot, lam_slot, out_slot, init, beta=0.0, wrt="velocity"):
         g = gradient(self.vecs[t_slot], self.vecs[lam_slot], self.c, self.h, init, wrt)
         self.vecs[out_slot] = g if beta == 0.0 else self.dtype.type(beta) * self.vecs[out_slot] + g
+
+    def eikonal_tangent(self, t_slot, dm_slot, out_slot, scratch_slot, init, wrt="velocity", max_sweeps=None):
+        """As ``Engine.eikonal_tangent``; what ``fwi_eikonal_tangent`` refuses is a ``ValueError`` here"""
+        slots = (t_slot, dm_slot, out_slot, scratch_slot)
+        for name, s in zip(("t_slot", "dm_slot", "out_slot", "scratch_slot"), slots):
+            if not 0 <= int(s) < len(self.vecs):
+                raise ValueError("eikonal_tangent: %s = %d does not exist" % (name, s))
+        if len(set(int(s) for s in slots)) != 4:
+            raise ValueError("eikonal_tangent: t_slot, dm_slot, out_slot and scratch_slot must be four different slots, "
+                             "got %r" % (slots,))
+        if wrt not in WRT:
+            raise ValueError("eikonal_tangent: wrt must be one of %r, got %r" % (WRT, wrt))
+        idx, dist, ref = _source(init, self.shape, self.h, 0.0)
+        if len(idx) < 1 or dist.shape != (len(idx),) or ref.shape != (self.ndim,):
+            raise ValueError("eikonal_tangent: the init list is empty or ill-shaped (%d nodes, distances %r, reference %r)"
+                             % (len(idx), dist.shape, ref.shape))
+        n = np.array(self.shape)
+        if np.any(idx < 0) or np.any(idx >= n) or np.any(ref < 0) or np.any(ref >= n):
+            raise ValueError("eikonal_tangent: init_idx or ref_idx lies outside the grid")
+        if len(np.unique(idx, axis=0)) != len(idx):
+            raise ValueError("eikonal_tangent: init_idx names a node twice")
+        if not np.all(np.isfinite(dist) & (dist >= 0.0)):
+            raise ValueError("eikonal_tangent: init_dist must be finite and >= 0")
+        if self.c is None:
+            raise ValueError("eikonal_tangent: no model set")
+        self.vecs[out_slot], self.last_eikonal_launches = tangent(self.vecs[t_slot], self.c, self.h, self.vecs[dm_slot],
+                                                                  (idx, dist, ref), wrt, return_sweeps=True,
+                                                                  max_sweeps=max_sweeps)

@@ -1184,6 +1184,23 @@ class Engine:
         _, args = self._init_args(init)
         self._chk(self._lib.fwi_eikonal_gradient(self._c, w, int(t_slot), int(lam_slot), int(out_slot), float(beta), *args))
 
+    def eikonal_tangent(self, t_slot, dm_slot, out_slot, scratch_slot, init, wrt="velocity", max_sweeps=None):
+        """Slot ``out_slot`` := ``dT``, the derivative of the times in ``t_slot`` along the model perturbation in
+        ``dm_slot`` (``fwi_eikonal_tangent``; ``eikonal.tangent`` is the definition): the exact transpose of
+        :meth:`eikonal_adjoint` followed by :meth:`eikonal_gradient`.  ``init``: the list :meth:`eikonal` returned;
+        four different slots, ``scratch_slot``'s contents are lost."""
+        if wrt not in ("velocity", "slowness2"):
+            raise ValueError("wrt must be 'velocity' or 'slowness2', got %r" % (wrt,))
+        w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        _, args = self._init_args(init)
+        n = C.c_int32(0)
+        try:
+            self._chk(self._lib.fwi_eikonal_tangent(self._c, w, int(t_slot), int(dm_slot), int(out_slot),
+                                                    int(scratch_slot), *args,
+                                                    0 if max_sweeps is None else int(max_sweeps), C.byref(n)))
+        finally:
+            self.last_eikonal_launches = int(n.value)
+
     def vec_clip(self, x, lo, hi):
         self._chk(self._lib.fwi_vec_clip(self._c, x, float(lo), float(hi)))
 

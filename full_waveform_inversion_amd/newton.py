@@ -3,6 +3,9 @@
 ``H_GN = sum_s J_s^T J_s`` is applied matrix-free (``shots.gauss_newton_hvp``: three sweeps per shot and product), so an
 inner iteration costs about one and a half gradient evaluations.  Host arrays are enough at this size of problem; the
 products themselves run on the device.  No reference counterpart.
+
+Traveltime tomography has the same two layers on ``shots.TraveltimeOperator`` (one tangent and one adjoint eikonal solve
+per shot and product): :func:`traveltime_newton_step` and :func:`traveltime_gauss_newton`.
 """
 from __future__ import annotations
 
@@ -89,3 +92,100 @@ def gauss_newton_step(engine, model, shots, g, exchange=None, wrt="velocity", pr
         return Hv if regularizer is None else Hv + regularizer.hvp(model, v)
 
     return cg(hvp, -g, precond=precond, maxiter=maxiter, rtol=rtol, callback=callback)
+
+
+def traveltime_newton_step(op, g, damping=0.0, maxiter=10, rtol=1e-2, precond=None, regularizer=None, callback=None):
+    """The (truncated) Gauss-Newton step of traveltime tomography: ``(H + damping I [+ lam L]) p = -g`` by :func:`cg`,
+    ``H = sum_s J_s^T W_s J_s`` applied by ``op`` (a ``shots.TraveltimeOperator`` at the model where
+    ``shots.traveltime_fg`` returned ``g``, same ``wrt`` and weights): per inner iteration one tangent and one adjoint
+    solve per shot.  ``precond`` as in :func:`cg`; ``regularizer`` as in :func:`gauss_newton_step` (the operator must
+    have been given its model).
+    Returns ``(p, log)`` (``log`` as :func:`cg`)."""
+    g = np.asarray(g, np.float64)
+    if regularizer is not None and op.model is None:
+        raise ValueError("traveltime_newton_step: a regularizer needs the operator's model (TraveltimeOperator(model=...))")
+    if regularizer is not None and op.wrt != "velocity":
+        raise ValueError("traveltime_newton_step: a regularizer acts on the velocity model; use wrt='velocity' with it")
+
+    def hvp(v):
+        Hv = np.asarray(op.hvp(v), np.float64)
+        Hv = Hv + damping * v if damping else Hv
+        return Hv if regularizer is None else Hv + regularizer.hvp(op.model, v)
+
+    return cg(hvp, -g, precond=precond, maxiter=maxiter, rtol=rtol, callback=callback)
+
+
+def traveltime_gauss_newton(engine, model0, shots, picks, pick_weights=None, iters=3, cg_iters=6, rtol=1e-2,
+                            rel_damping=1e-2, bounds=None, radius=0.0, slot0=0, exchange=None, wrt="velocity",
+                            regularizer=None, precond=None):
+    """Damped Gauss-Newton traveltime tomography from the velocity ``model0``: ``(model, log)``.  Per iteration: the
+    operator at the model (``shots.TraveltimeOperator``, times kept); ``mu = rel_damping (g.Hg) / (g.g)`` (one
+    product); ``p`` from :func:`traveltime_newton_step` with ``damping = mu`` (``cg_iters`` products at most); then
+    ``t = 1``, halved while ``J`` (``shots.traveltime_fg`` at ``model + t p`` clipped to ``bounds``, with the
+    regulariser's value) does not fall -- after 10 halvings the iterations stop at the model reached.  The ``(J, g)``
+    of the accepted trial start the next iteration.  With ``wrt="slowness2"`` the step is taken in ``1 / c^2`` and
+    turned back into a velocity.  ``log[0]`` holds the starting ``J``; ``log[k]`` the ``J`` after iteration k, its
+    ``t``, ``mu``, the :func:`cg` log and the eikonal / tangent / adjoint solves of the iteration on this rank (those of
+    ``log[0]``: the first evaluation).  ``regularizer`` and ``precond`` as in :func:`traveltime_newton_step` (the
+    regulariser's value and gradient are added to ``J`` and ``g``; it acts on the velocity model, so it is refused
+    with ``wrt="slowness2"``).  The engines need ``max(shots.TRAVELTIME_SLOTS, op.slots_needed(n_local))``
+    vector slots from ``slot0`` on."""
+    from .shots import NoExchange, TraveltimeOperator, partition_shots, traveltime_fg
+    if regularizer is not None and wrt != "velocity":
+        raise ValueError("traveltime_gauss_newton: a regularizer acts on the velocity model; use wrt='velocity' with it")
+    ex = exchange or NoExchange()
+    n_local = len(partition_shots(len(shots), ex.rank, ex.world))
+    count = {"eikonal": 0, "tangent": 0, "adjoint": 0}
+
+    def fg(m):
+        J, g = traveltime_fg(engine, m, shots, picks, pick_weights, radius=radius, slot0=slot0, exchange=exchange,
+                             wrt=wrt)
+        count["eikonal"] += n_local
+        count["adjoint"] += n_local
+        if regularizer is not None:
+            r, gr = regularizer.value_and_gradient(m)
+            J, g = J + r, g + gr
+        return J, np.asarray(g, np.float64)
+
+    def moved(m, step):
+        if wrt == "slowness2":
+            m = np.maximum(1.0 / m ** 2 + step, np.finfo(np.float64).tiny) ** -0.5
+        else:
+            m = m + step
+        return m if bounds is None else np.clip(m, bounds[0], bounds[1])
+
+    def taken():
+        out = dict(count)
+        for k in count:
+            count[k] = 0
+        return out
+
+    m = np.array(model0, np.float64)
+    J, g = fg(m)
+    log = [{"iter": 0, "J": J, "solves": taken()}]
+    for it in range(1, int(iters) + 1):
+        op = TraveltimeOperator(engine, m, shots, radius=radius, slot0=slot0, exchange=exchange, wrt=wrt,
+                                pick_weights=pick_weights, picks=picks, keep_times=True)
+        gg = float(np.vdot(g, g))
+        if gg == 0.0:
+            log[-1]["stop"] = "zero_gradient"
+            break
+        mu = float(rel_damping) * float(np.vdot(g, op.hvp(g))) / gg
+        p, cglog = traveltime_newton_step(op, g, damping=mu, maxiter=cg_iters, rtol=rtol, precond=precond,
+                                          regularizer=regularizer)
+        for k in ("eikonal", "tangent", "adjoint"):
+            count[k] += op.solves[k]
+        t = 1.0
+        for _ in range(11):
+            mt = moved(m, t * p)
+            Jt, gt = fg(mt)
+            if Jt < J:
+                break
+            t *= 0.5
+        else:
+            log[-1]["stop"] = "line_search"
+            log[-1]["solves_after"] = taken()
+            break
+        m, J, g = mt, Jt, gt
+        log.append({"iter": it, "J": J, "t": t, "mu": mu, "cg": cglog, "solves": taken()})
+    return m, log

@@ -1139,14 +1139,7 @@ def traveltime_fg(engine, model, shots, picks, pick_weights=None, radius=0.0, sl
             raise ValueError("shot %d: %d receivers, %d picks, %d weights" % (i, tau.size, t.size, w.size))
         ok = ~np.isnan(t)
         r = np.where(ok, w * (tau - np.where(ok, t, 0.0)), 0.0)  # dJ/dT(x_r)
-        if hasattr(rec, "pt_start"):  # off-grid receivers: onto their nodes, a node shared by two receivers once
-            nodes, inv = np.unique(np.asarray(rec.idx), axis=0, return_inverse=True)
-            vals = np.zeros(len(nodes))
-            np.add.at(vals, np.reshape(inv, -1), r[rec.owner] * rec.weights)
-        else:
-            nodes, inv = np.unique(np.asarray(rec).reshape(-1, np.shape(rec)[-1]), axis=0, return_inverse=True)
-            vals = np.zeros(len(nodes))
-            np.add.at(vals, np.reshape(inv, -1), r)
+        nodes, vals = _receiver_nodes(rec, r)  # off-grid receivers: onto their nodes
         e.vec_scatter_points(B, nodes, vals, beta=0.0)
         e.eikonal_adjoint(T, B, L, SC)
         e.eikonal_gradient(T, L, G, init, beta=0.0 if first[id(e)] else 1.0, wrt=wrt)
@@ -1166,3 +1159,175 @@ def traveltime_fg(engine, model, shots, picks, pick_weights=None, radius=0.0, sl
     g = np.asarray(ex.reduce_array(g)).reshape(shape)
     J = float(np.asarray(ex.reduce_array(np.array([J]))).ravel()[0])
     return J, g
+
+
+def _receiver_nodes(rec, r):
+    """Receiver values ``r`` onto the grid's nodes: ``(nodes, values)``, a node shared by two receivers once (a
+    ``points.Spread``: with its multilinear weights)"""
+    if hasattr(rec, "pt_start"):
+        nodes, inv = np.unique(np.asarray(rec.idx), axis=0, return_inverse=True)
+        vals = np.zeros(len(nodes))
+        np.add.at(vals, np.reshape(inv, -1), r[rec.owner] * rec.weights)
+    else:
+        nodes, inv = np.unique(np.asarray(rec).reshape(-1, np.shape(rec)[-1]), axis=0, return_inverse=True)
+        vals = np.zeros(len(nodes))
+        np.add.at(vals, np.reshape(inv, -1), r)
+    return nodes, vals
+
+
+class TraveltimeOperator:
+    """The linearisation of the first-arrival times at one model: ``J_s = dT_s(x_r)/dmodel`` of every shot, its
+    transpose and the Gauss-Newton Hessian ``sum_s J_s^T W_s J_s`` of :func:`traveltime_fg`'s functional, over shots,
+    the engines of a pool and the ranks.  ``J_s v`` is one ``eikonal_tangent`` solve, ``J_s^T r`` one ``eikonal_adjoint``
+    solve and an ``eikonal_gradient`` pass; the two are exact transposes of each other.
+
+    ``model``: a velocity (None: the model the engines hold).  ``pick_weights[i]``: the weights ``W_s`` (None: 1);
+    ``picks[i]``: only its NaNs count, a receiver without a pick gets weight zero as in :func:`traveltime_fg`.  With
+    ``keep_times`` each local shot's ``T`` is solved once, here, into a slot of its own and a product costs two solves;
+    without, ``T`` is solved again in every product (three solves) and one slot holds it.  Uses
+    ``slots_needed(n_local)`` vector slots from ``slot0`` on, on every engine.  The engine may be anything with the
+    engine's calls: ``eikonal.TwinEngine`` runs it on the CPU.  ``solves`` counts this rank's eikonal / tangent /
+    adjoint solves, those of the constructor (``keep_times``) included."""
+
+    WORK_SLOTS = 6  # scratch, v, dT, right-hand side, lambda, gradient; the times follow
+
+    def __init__(self, engine, model, shots, radius=0.0, slot0=0, exchange=None, wrt="velocity", pick_weights=None,
+                 picks=None, keep_times=True):
+        if wrt not in ("velocity", "slowness2"):
+            raise ValueError("wrt must be 'velocity' or 'slowness2', got %r" % (wrt,))
+        self.engine, self.shots, self.radius, self.wrt = engine, shots, float(radius), wrt
+        self.ex = exchange or NoExchange()
+        self.keep_times = bool(keep_times)
+        self.engines = _engines(engine)
+        self.SC, self.V, self.X, self.B, self.L, self.G = (int(slot0) + k for k in range(self.WORK_SLOTS))
+        self.T0 = int(slot0) + self.WORK_SLOTS
+        self.mine = partition_shots(len(shots), self.ex.rank, self.ex.world)
+        self.solves = {"eikonal": 0, "tangent": 0, "adjoint": 0}
+        self.model = None if model is None else np.array(model, np.float64)
+        if model is not None:
+            for e in self.engines:
+                e.set_model(model)
+        self.shape = tuple(self.engines[0].shape)
+        self.points = [_traveltime_points(s) for s in shots]
+        self.sizes = [rec.n if hasattr(rec, "pt_start") else len(np.asarray(rec).reshape(-1, np.shape(rec)[-1]))
+                      for _, rec in self.points]
+        self.weights = []
+        for i, n in enumerate(self.sizes):
+            w = np.ones(n) if pick_weights is None or pick_weights[i] is None else \
+                np.asarray(pick_weights[i], np.float64).reshape(-1)
+            if picks is not None and picks[i] is not None:
+                t = np.asarray(picks[i], np.float64).reshape(-1)
+                if t.shape != w.shape:
+                    raise ValueError("shot %d: %d weights, %d picks" % (i, w.size, t.size))
+                w = np.where(np.isnan(t), 0.0, w)
+            if w.shape != (n,):
+                raise ValueError("shot %d: %d receivers, %d weights" % (i, n, w.size))
+            self.weights.append(w)
+        self.inits = {}
+        if self.keep_times:
+            self._map(lambda e, pos, i: self._solve(e, pos, i))
+            self.solves["eikonal"] += len(self.mine)
+
+    def slots_needed(self, n_local):
+        """vector slots used from ``slot0`` on by a rank with ``n_local`` shots (on each of its engines)"""
+        per_engine = -(-int(n_local) // len(self.engines))
+        return self.WORK_SLOTS + (max(1, per_engine) if self.keep_times else 1)
+
+    # position pos of this rank's shots runs on engine pos % n, as EnginePool.map_shots deals them out
+    def _t_slot(self, pos):
+        return self.T0 + (pos // len(self.engines) if self.keep_times else 0)
+
+    def _map(self, fn):
+        pos_of = {i: pos for pos, i in enumerate(self.mine)}
+        if isinstance(self.engine, EnginePool):
+            return self.engine.map_shots(self.mine, lambda e, i: fn(e, pos_of[i], i))
+        return [fn(self.engine, pos_of[i], i) for i in self.mine]
+
+    def _solve(self, e, pos, i):
+        self.inits[i] = e.eikonal(self.points[i][0], self._t_slot(pos), self.SC, radius=self.radius)
+
+    def _times_slot(self, e, pos, i):
+        if not self.keep_times:
+            self._solve(e, pos, i)
+        return self._t_slot(pos)
+
+    def _complete(self, got):
+        """this rank's per-shot receiver arrays -> the list over all shots, complete on every rank"""
+        ends = np.cumsum([0] + self.sizes)
+        flat = np.zeros(ends[-1])
+        for i, v in zip(self.mine, got):
+            flat[ends[i]:ends[i + 1]] = v
+        flat = np.asarray(self.ex.reduce_array(flat))
+        return [flat[ends[i]:ends[i + 1]].copy() for i in range(len(self.shots))]
+
+    def _count(self, tangent=0, adjoint=0):
+        n = len(self.mine)
+        self.solves["tangent"] += tangent * n
+        self.solves["adjoint"] += adjoint * n
+        self.solves["eikonal"] += 0 if self.keep_times else n
+
+    def _upload(self, v):
+        v = np.asarray(v, np.float64).reshape(self.shape)
+        for e in self.engines:
+            e.vec_upload(self.V, v.astype(getattr(e, "dtype", np.float64)))
+
+    def _jvp_one(self, e, pos, i):
+        """dT_s at the receivers of shot i, from the perturbation in slot V"""
+        T = self._times_slot(e, pos, i)
+        e.eikonal_tangent(T, self.V, self.X, self.SC, self.inits[i], wrt=self.wrt)
+        rec = self.points[i][1]
+        if hasattr(rec, "pt_start"):
+            x = e.vec_gather_points(self.X, rec.idx) * rec.weights
+            return np.add.reduceat(x, rec.pt_start[:-1]) if len(x) else np.zeros(0)
+        return e.vec_gather_points(self.X, rec)
+
+    def _vjp_one(self, e, pos, i, r, first, solve=True):
+        """G (+)= J_s^T r"""
+        T = self._times_slot(e, pos, i) if solve else self._t_slot(pos)
+        nodes, vals = _receiver_nodes(self.points[i][1], np.asarray(r, np.float64).reshape(-1))
+        e.vec_scatter_points(self.B, nodes, vals, beta=0.0)
+        e.eikonal_adjoint(T, self.B, self.L, self.SC)
+        e.eikonal_gradient(T, self.L, self.G, self.inits[i], beta=0.0 if first[id(e)] else 1.0, wrt=self.wrt)
+        first[id(e)] = False
+
+    def _gather_gradient(self, first):
+        g = np.zeros(self.shape, np.float64)
+        for e in self.engines:
+            if not first[id(e)]:
+                g += np.asarray(e.vec_download(self.G), np.float64)
+        return np.asarray(self.ex.reduce_array(g)).reshape(self.shape)
+
+    def times(self):
+        """The times of every shot at its receivers, as :func:`traveltime_times`"""
+        if not self.keep_times:
+            self.solves["eikonal"] += len(self.mine)
+        return self._complete(self._map(lambda e, pos, i: e.eikonal_times(self._times_slot(e, pos, i), self.points[i][1])))
+
+    def jvp(self, v):
+        """``[J_s v]``: the change of every shot's times at its receivers for the model change ``v``, complete on
+        every rank"""
+        self._upload(v)
+        self._count(tangent=1)
+        return self._complete(self._map(self._jvp_one))
+
+    def vjp(self, r_list):
+        """``sum_s J_s^T r_s``, model-shaped fp64, summed over engines and ranks; ``r_list[i]``: one value per receiver"""
+        first = {id(e): True for e in self.engines}
+        for i in self.mine:
+            if np.size(r_list[i]) != self.sizes[i]:
+                raise ValueError("shot %d: %d receivers, %d values" % (i, self.sizes[i], np.size(r_list[i])))
+        self._count(adjoint=1)
+        self._map(lambda e, pos, i: self._vjp_one(e, pos, i, r_list[i], first))
+        return self._gather_gradient(first)
+
+    def hvp(self, v):
+        """``sum_s J_s^T W_s J_s v``, model-shaped fp64, summed over engines and ranks"""
+        first = {id(e): True for e in self.engines}
+        self._upload(v)
+        self._count(tangent=1, adjoint=1)
+
+        def one(e, pos, i):
+            self._vjp_one(e, pos, i, self.weights[i] * self._jvp_one(e, pos, i), first, solve=False)
+
+        self._map(one)
+        return self._gather_gradient(first)

@@ -43,6 +43,7 @@ extern "C" {
 /* ... and with spectral imaging on it (fwi_adjoint_spectral, fwi_fourier_image, fwi_fourier_gradient[_vec],
  * fwi_fourier_adjoint_spectrum, fwi_fourier_illumination[_vec]). */
 /* ... and with the extended images (fwi_fourier_offset_image[_vec], fwi_fourier_lag_image[_vec]). */
+/* ... and with the tangent of the first-arrival traveltimes (fwi_eikonal_tangent). */
 #define FWI_ABI_VERSION 14
 
 enum { FWI_F32 = 0, FWI_F64 = 1 };
@@ -839,6 +840,30 @@ int fwi_eikonal_adjoint(fwi_ctx *ctx, int32_t t_slot, int32_t rhs_slot, int32_t 
                         int32_t max_sweeps, int32_t *launches_out);
 int fwi_eikonal_gradient(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t lam_slot, int32_t out_slot, double beta,
                          int32_t n_init, const int32_t *init_idx, const double *init_dist, const int32_t *ref_idx);
+
+/* fwi_eikonal_tangent: out_slot := dT, the derivative of the fixed point T in t_slot along the model perturbation in
+ * dm_slot (the definition is `tangent` of full_waveform_inversion_amd/eikonal.py).  With the weights,
+ * the active axes D and the init list of the three calls above:
+ *   ds_i = -dm_i / c_i^2 for FWI_WRT_VELOCITY, dm_i c_i / 2 for FWI_WRT_SLOWNESS2 (the transposes of the gradient's
+ *          g = -g_s / c^2 and g = g_s c / 2),
+ *   b_i  = ds_i h^2 / (c_i sum_{e in D} (T_i - t_e)); on a listed node that is source-determined (T_i < G_i, the same
+ *          decision as in fwi_eikonal_gradient) b_i = init_dist[k] ds[ref]; 0 where T_i = +inf,
+ *   x    = b + A x,  (A x)_i = sum_d dG_i/dt_d x[upwind neighbour of i on axis d]: gather form, the terms of a cell
+ *          added axis by axis in ascending order after b_i, the upwind neighbour being the lower-index one on a tie.
+ * It is the exact transpose of fwi_eikonal_adjoint followed by fwi_eikonal_gradient: <w, dT> equals <g(w), dm> to
+ * round-off for every w and dm.  A is strictly causal, so the block-Jacobi iteration between out_slot and scratch_slot
+ * stops bit-exactly; launches, max_sweeps, the cap (FWI_ESTATE if the last allowed launch still changed something) and
+ * *launches_out behave as for fwi_eikonal_adjoint.  b is never stored and no model-sized memory is allocated: both
+ * slots start as zeros with the source-determined listed nodes set, and a launch forms b_i of a live cell from dm_i
+ * and c_i.  No atomics on x.  t_slot and dm_slot are read only; scratch_slot's contents are lost; pad columns stay
+ * zero.  The non-differentiable set gets the same one-sided choice as the adjoint.  Refused before anything is written
+ * -- FWI_EINVAL, naming the argument: a slot that does not exist; any two of the four slots equal; an empty init list;
+ * a listed or reference node outside the grid or listed twice; a negative or non-finite distance; an unknown wrt; a
+ * null pointer.  FWI_ESTATE: no model set.  The values of dm are not validated.  No sweep state of the context is
+ * touched.  No reference counterpart. */
+int fwi_eikonal_tangent(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t dm_slot, int32_t out_slot,
+                        int32_t scratch_slot, int32_t n_init, const int32_t *init_idx, const double *init_dist,
+                        const int32_t *ref_idx, int32_t max_sweeps, int32_t *launches_out);
 
 /* Born (linearised) modelling dd = J dm: the exact derivative of the discrete fwi_forward along a model perturbation,
  * whose exact transpose is fwi_adjoint(image) + fwi_gradient.  With C = dt^2 c^2 and q^n the forward term the store of

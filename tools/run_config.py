@@ -15,7 +15,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
-from full_waveform_inversion_amd import Engine, datafit, regularizers as rg, shots as sh, workloads  # noqa: E402
+from full_waveform_inversion_amd import Engine, datafit, newton as nw, regularizers as rg, shots as sh, workloads  # noqa: E402
 from full_waveform_inversion_amd.lbfgs import lbfgs, lbfgs_device, lbfgs_device_slots  # noqa: E402
 
 
@@ -175,7 +175,13 @@ def main():
                          "of the run")
     ap.add_argument("--tomography-radius", type=float, default=3.0, metavar="R",
                     help="cells around each source that start at their straight-ray time (eikonal.ball)")
+    ap.add_argument("--tomography-newton", type=int, default=None, metavar="CG_ITERS",
+                    help="the --tomography ITERS iterations are damped Gauss-Newton ones (newton.traveltime_gauss_newton: "
+                         "at most CG_ITERS conjugate-gradient products per iteration, each a tangent and an adjoint "
+                         "eikonal solve per shot) instead of L-BFGS; --smooth preconditions the inner iteration")
     a = ap.parse_args()
+    if a.tomography_newton is not None and (a.tomography_newton < 1 or a.tomography < 1):
+        ap.error("--tomography-newton CG_ITERS must be >= 1 and needs --tomography ITERS")
     if a.tomography < 0 or not (a.tomography_radius >= 0.0 and np.isfinite(a.tomography_radius)):
         ap.error("--tomography ITERS must be >= 0 and --tomography-radius R finite and >= 0")
     bands = [float(f) for f in a.bands.split(",")] if a.bands else None
@@ -387,8 +393,11 @@ def main():
     m0 = w.c_init.astype(np.float32)
     tomo = None
     if a.tomography > 0:  # traveltime tomography first: the model it ends at starts the waveform stages
-        for eng in pool.engines:
-            eng.vec_create(sh.TRAVELTIME_SLOTS)
+        n_local = len(sh.partition_shots(len(shots), ex.rank, ex.world))  # "solves" below counts this rank's
+        per_engine = -(-n_local // len(pool.engines))
+        for eng in pool.engines:  # the Gauss-Newton operator keeps every local shot's times in a slot of its own
+            eng.vec_create(sh.TRAVELTIME_SLOTS if a.tomography_newton is None else
+                           max(sh.TRAVELTIME_SLOTS, sh.TraveltimeOperator.WORK_SLOTS + max(1, per_engine)))
         picks = sh.traveltime_times(pool, w.c.astype(np.float32), shots, a.tomography_radius, 0, ex)
         tomo_J = []
 
@@ -400,12 +409,26 @@ def main():
             fg_tomo = rg.regularized_fg(fg_tomo, a.reg_weight, a.regularize, 1.0,
                                         (a.reg_eps if a.reg_eps is not None else 1e-3 * float(m0.max()))
                                         if a.regularize == "tv" else None, m0 if a.reg_prior == "start" else None)
-        m_tomo, _, tomo_log = lbfgs(fg_tomo, m0.astype(np.float64), maxiter=a.tomography, history=5,
-                                    first_step=0.02 * float(m0.max()),
-                                    bounds=(0.5 * float(w.c.min()), 1.5 * float(w.c.max())),
-                                    h0=sh.smoothing_h0(a.smooth) if a.smooth is not None else None)
-        tomo = {"iters": a.tomography, "radius": a.tomography_radius, "evaluations": len(tomo_J),
-                "J": [float(l["f"]) for l in tomo_log]}
+        tomo_bounds = (0.5 * float(w.c.min()), 1.5 * float(w.c.max()))
+        tomo_h0 = sh.smoothing_h0(a.smooth) if a.smooth is not None else None
+        if a.tomography_newton is None:
+            m_tomo, _, tomo_log = lbfgs(fg_tomo, m0.astype(np.float64), maxiter=a.tomography, history=5,
+                                        first_step=0.02 * float(m0.max()), bounds=tomo_bounds, h0=tomo_h0)
+            tomo = {"solver": "lbfgs", "iters": a.tomography, "radius": a.tomography_radius,
+                    "evaluations": len(tomo_J), "J": [float(l["f"]) for l in tomo_log],
+                    "solves": {"eikonal": len(tomo_J) * n_local, "tangent": 0, "adjoint": len(tomo_J) * n_local}}
+        else:
+            reg = None if a.regularize is None else rg.Regularizer(
+                a.reg_weight, a.regularize, 1.0,
+                (a.reg_eps if a.reg_eps is not None else 1e-3 * float(m0.max())) if a.regularize == "tv" else None,
+                m0 if a.reg_prior == "start" else None)
+            m_tomo, tomo_log = nw.traveltime_gauss_newton(pool, m0.astype(np.float64), shots, picks, None, a.tomography,
+                                                          a.tomography_newton, bounds=tomo_bounds,
+                                                          radius=a.tomography_radius, exchange=ex, regularizer=reg,
+                                                          precond=tomo_h0)
+            tomo = {"solver": "gauss-newton", "iters": a.tomography, "cg_iters": a.tomography_newton,
+                    "radius": a.tomography_radius, "J": [float(l["J"]) for l in tomo_log],
+                    "solves": {k: int(sum(l["solves"][k] for l in tomo_log)) for k in ("eikonal", "tangent", "adjoint")}}
         m0 = np.asarray(m_tomo, np.float32)
         for eng in pool.engines:
             eng.vec_create(0)
