@@ -145,6 +145,11 @@ SIGNATURES = {
     "fwi_eikonal_adjoint": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
     "fwi_eikonal_gradient": (C.c_int, [_P, _I32, _I32, _I32, _I32, _D, _I32, _P, _P, _P]),
     "fwi_eikonal_tangent": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, C.POINTER(_I32)]),
+    "fwi_eikonal_stage": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, C.POINTER(_I32)]),
+    "fwi_eikonal_handover": (C.c_int, [_P, _I32, _I32, _I32, _D]),
+    "fwi_eikonal_gradient_field": (C.c_int, [_P, _I32, _I32, _I32, _I32, _D]),
+    "fwi_eikonal_tangent_stage": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _I32,
+                                            C.POINTER(_I32)]),
     "fwi_born": (C.c_int, [_P, _I32, _P, _I32, _P]),
     "fwi_born_vec": (C.c_int, [_P, _I32, _I32, _I32, _P]),
     "fwi_born_imaging": (C.c_int, [_P, _I32, _P, _I32, _P]),

@@ -31,45 +31,7 @@ __global__ __launch_bounds__(256) void eikonal_init(T *t0, T *t1, const T *c, co
 template <typename T, int ND>
 __global__ __launch_bounds__(Eik<ND>::NT) void eikonal_sweep(GridDesc g, const T *__restrict__ in, T *__restrict__ out,
                                                              const T *__restrict__ c, T h, int K, int *flag) {
-#pragma clang fp contract(off)
-    constexpr int TL = Eik<ND>::TL, NT = Eik<ND>::NT, P = TL + 2;
-    constexpr int NP = ND == 2 ? P * P : P * P * P;
-    __shared__ T sT[NP];
-    int n[ND], o[ND], l[ND];
-    int64_t st[ND], gi;
-    eik_dims<ND>(g, n, st);
-    eik_origin<ND>(o);
-    for (int i = threadIdx.x; i < NP; i += NT) {  // the tile and one frozen cell around it; +inf outside the grid
-        eik_decode<ND>(i, P, l);
-        sT[i] = eik_cell<ND>(n, st, o, l, 1, gi) ? in[gi] : eik_inf<T>();
-    }
-    eik_decode<ND>(threadIdx.x, TL, l);
-    const bool valid = eik_cell<ND>(n, st, o, l, 0, gi);
-    int li = 0, ls[ND];  // this thread's cell in the LDS box, and the box's strides
-    {
-        int s = 1;
-        for (int d = ND - 1; d >= 0; --d) {
-            ls[d] = s;
-            li += (l[d] + 1) * s;
-            s *= P;
-        }
-    }
-    const T f = valid ? ((T)1 / c[gi]) * h : (T)1;
-    __syncthreads();
-    const T orig = sT[li];
-    T cur = orig;
-    for (int k = 0; k < K; ++k) {
-        T t[ND];
-#pragma unroll
-        for (int d = 0; d < ND; ++d) t[d] = eik_min(sT[li - ls[d]], sT[li + ls[d]]);
-        const T nw = valid ? eik_min(cur, eik_local<T, ND>(t, f)) : cur;
-        __syncthreads();
-        sT[li] = nw;
-        cur = nw;
-        __syncthreads();
-    }
-    if (valid) out[gi] = cur;
-    if (__syncthreads_or(valid && cur != orig) && threadIdx.x == 0) atomicMax(flag, 1);
+    eik_sweep_tile<T, ND, false>(g, in, out, c, nullptr, h, K, flag);
 }
 
 template <typename T, int ND>

@@ -54,64 +54,7 @@ __global__ __launch_bounds__(Eik<ND>::NT) void eikonal_tangent_sweep(GridDesc g,
                                                                      const T *__restrict__ in, T *__restrict__ out,
                                                                      const T *__restrict__ c, T h, int wrt_velocity,
                                                                      int K, int *flag) {
-#pragma clang fp contract(off)
-    constexpr int TL = Eik<ND>::TL, NT = Eik<ND>::NT, P = TL + 2;
-    constexpr int NP = ND == 2 ? P * P : P * P * P;
-    __shared__ T sT[NP];  // times, one cell around the tile (+inf outside the grid)
-    __shared__ T sX[NP];  // the iterate, one frozen cell around the tile (0 outside the grid)
-    int n[ND], o[ND], l[ND];
-    int64_t st[ND], gi;
-    eik_dims<ND>(g, n, st);
-    eik_origin<ND>(o);
-    for (int i = threadIdx.x; i < NP; i += NT) {
-        eik_decode<ND>(i, P, l);
-        const bool ok = eik_cell<ND>(n, st, o, l, 1, gi);
-        sT[i] = ok ? tim[gi] : eik_inf<T>();
-        sX[i] = ok ? in[gi] : (T)0;
-    }
-    eik_decode<ND>(threadIdx.x, TL, l);
-    const bool valid = eik_cell<ND>(n, st, o, l, 0, gi);
-    int li = 0, ls[ND];  // this thread's cell in the LDS boxes, and their strides
-    {
-        int s = 1;
-        for (int d = ND - 1; d >= 0; --d) {
-            ls[d] = s;
-            li += (l[d] + 1) * s;
-            s *= P;
-        }
-    }
-    __syncthreads();
-    // the local solver once per tile cell: the weights of this cell's own upwind neighbours and its right-hand side
-    T w[ND], b = (T)0;
-    int nb[ND];
-    bool live = false;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) w[d] = (T)0, nb[d] = li;
-    if (valid) {
-        T t[ND], den;
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            const T lo = sT[li - ls[d]], hi = sT[li + ls[d]];
-            t[d] = eik_min(lo, hi);
-            nb[d] = lo <= hi ? li - ls[d] : li + ls[d];
-        }
-        const T cv = c[gi], s = (T)1 / cv;
-        eik_weights<T, ND>(sT[li], t, s * h, w, den, live);
-        const T dGds = den > (T)0 ? s * h * h / den : (T)0;
-        b = dGds * eik_dslowness<T>(dm[gi], cv, wrt_velocity);
-    }
-    const T orig = sX[li];
-    T cur = orig;
-    for (int k = 0; k < K; ++k) {
-        T acc = b;  // gather form: this cell's own upwind neighbours, axis by axis after b
-#pragma unroll
-        for (int d = 0; d < ND; ++d) acc = acc + w[d] * sX[nb[d]];
-        __syncthreads();
-        if (live) sX[li] = acc, cur = acc;  // a cell that is not live stays as the init launches left it
-        __syncthreads();
-    }
-    if (valid) out[gi] = cur;
-    if (__syncthreads_or(valid && cur != orig) && threadIdx.x == 0) atomicMax(flag, 1);
+    eik_tangent_tile<T, ND, false>(g, tim, dm, nullptr, in, out, c, h, wrt_velocity, K, flag);
 }
 
 }  // namespace

@@ -29,7 +29,20 @@ The tangent (``fwi_eikonal_tangent``) differentiates the same fi
 source-determined listed nodes, ``x = b + A x`` in gather form, by the same Jacobi iteration.  It is the exact transpose
 of the adjoint followed by the gradient.
 
-Out of scope: the factored eikonal equation, second-order stencils, anisotropy and later arrivals.  The scheme is first
+Reflections off a FIXED interface are two such solves in a row.  A *wall* is a boolean array of the
+grid's shape: a walled cell holds ``+inf`` from start to end and is, to every other cell, a neighbour outside the grid
+(``f = +inf`` in the local solver: ``G = +inf``).  :func:`solve_from` is the limit of ``T <- min(T, G(T))`` from any
+``T_init`` (finite and ``>= 0`` on the secondary sources, ``+inf`` elsewhere); a node is *source-determined* when its
+final ``T_i`` is finite and ``< G_i``, and then ``T_i = T_init,i``.  Stage 1 runs from the source inside the wall, stage
+2 restarts from the interface nodes with the times they just got; :func:`handover` carries a field across on the
+source-determined nodes, which is all the adjoint and the tangent of the chain need beside the pieces above
+(:func:`reflection_gradient`, :func:`reflection_tangent`: exact transposes).  The adjoint needs no wall: a walled
+cell is not live and never anybody's upwind neighbour.
+
+Out of scope: the factored eikonal equation, second-order stencils, anisotropy; of the later arrivals everything but
+reflections off a fixed, node-rounded interface -- the reflector's depth is not an unknown and has no sub-cell position
+(its staircase is part of the first-order error), head waves, multiples and transmitted conversions are not separate
+arrivals.  The scheme is first
 order: 0.3 - 1.2 % of ``max T`` on 101^2 - 401^2 grids (the table in DESIGN.md), most of it from the source's
 neighbourhood, which a ball of a few cells (``radius``) reduces.
 
@@ -131,37 +144,81 @@ def init_times(c, h, init, dtype=np.float64):
     return T0
 
 
-def sweep(T, s, h):
-    """One Jacobi sweep ``min(T, G(T))`` (``T_init`` is in ``T`` from the start and ``min`` keeps it)"""
+def _wall(wall, shape):
+    if wall is None:
+        return None
+    wall = np.asarray(wall)
+    if wall.shape != tuple(shape):
+        raise ValueError("wall must have the grid's shape %r, got %r" % (tuple(shape), wall.shape))
+    return wall != 0
+
+
+def sweep(T, s, h, wall=None):
+    """One Jacobi sweep ``min(T, G(T))`` (``T_init`` is in ``T`` from the start and ``min`` keeps it); a walled cell
+    (``wall``: booleans of the grid's shape) is never updated"""
     f = s * s.dtype.type(h)
-    return np.minimum(T, local_solution([t for t, _ in upwind(T)], f))
+    Tn = np.minimum(T, local_solution([t for t, _ in upwind(T)], f))
+    return Tn if wall is None else np.where(wall, T, Tn)
 
 
-def solve(c, h, src, radius=0.0, dtype=np.float64, max_sweeps=None, return_sweeps=False):
-    """First-arrival times of the model ``c`` (m/s) for the source ``src`` (coordinates in cells, or an init list):
-    plain Jacobi from ``+inf`` until a sweep changes no bit."""
-    dtype = np.dtype(dtype)
-    c = np.asarray(c)
-    init = _source(src, c.shape, h, radius)
-    s = _slowness(c, dtype)
-    T = init_times(c, h, init, dtype)
-    cap = 4 * sum(c.shape) if max_sweeps is None else int(max_sweeps)
+def _fixed_point(T, s, h, wall, max_sweeps, return_sweeps, who):
+    if wall is not None:
+        T = np.where(wall, T.dtype.type(np.inf), T)
+    cap = 4 * sum(T.shape) if max_sweeps is None else int(max_sweeps)
     for n in range(1, cap + 1):
-        Tn = sweep(T, s, h)
+        Tn = sweep(T, s, h, wall)
         if np.array_equal(Tn, T):
             return (T, n) if return_sweeps else T
         T = Tn
-    raise RuntimeError("eikonal.solve: no fixed point after %d sweeps" % cap)
+    raise RuntimeError("eikonal.%s: no fixed point after %d sweeps" % (who, cap))
 
 
-def solve_blocks(c, h, src, radius=0.0, tile=8, inner=4, dtype=np.float64):
-    """The same fixed point by block Jacobi, as the device runs it: per outer step every ``tile``-cell block takes
-    ``inner`` sweeps with the cells around it frozen, all blocks reading the same input.  Returns ``(T, outer steps)``."""
+def solve(c, h, src, radius=0.0, dtype=np.float64, max_sweeps=None, return_sweeps=False, wall=None):
+    """First-arrival times of the model ``c`` (m/s) for the source ``src`` (coordinates in cells, or an init list):
+    plain Jacobi from ``+inf`` until a sweep changes no bit.  ``wall``: cells the front may not enter (``+inf``)."""
     dtype = np.dtype(dtype)
     c = np.asarray(c)
     init = _source(src, c.shape, h, radius)
+    return _fixed_point(init_times(c, h, init, dtype), _slowness(c, dtype), h, _wall(wall, c.shape), max_sweeps,
+                        return_sweeps, "solve")
+
+
+def check_start(T_init, wall=None):
+    """What a slot-started solve refuses: ``ValueError`` unless ``T_init`` is free of NaNs and of negative entries and
+    holds a finite one, on the cells that are not walled"""
+    T_init = np.asarray(T_init)
+    free = T_init if wall is None else T_init[~wall]
+    if np.any(np.isnan(free)) or np.any(free < 0):
+        raise ValueError("T_init holds a NaN or a negative entry")
+    if not np.any(np.isfinite(free)):
+        raise ValueError("T_init holds no finite entry: there is no source")
+
+
+def solve_from(c, h, T_init, wall=None, dtype=np.float64, max_sweeps=None, return_sweeps=False):
+    """The limit of ``T <- min(T, G(T))`` from ``T = T_init`` (finite and ``>= 0`` on the secondary sources, ``+inf``
+    elsewhere; walled cells ``+inf`` whatever it says there).  With ``T_init = init_times(c, h, init)`` and no wall it
+    is :func:`solve`, bit for bit."""
+    dtype = np.dtype(dtype)
+    c = np.asarray(c)
+    T0 = np.array(T_init, dtype=dtype)
+    if T0.shape != c.shape:
+        raise ValueError("T_init must have the grid's shape %r, got %r" % (c.shape, T0.shape))
+    wall = _wall(wall, c.shape)
+    check_start(T0, wall)
+    return _fixed_point(T0, _slowness(c, dtype), h, wall, max_sweeps, return_sweeps, "solve_from")
+
+
+def solve_blocks(c, h, src, radius=0.0, tile=8, inner=4, dtype=np.float64, wall=None, T_init=None):
+    """The same fixed point by block Jacobi, as the device runs it: per outer step every ``tile``-cell block takes
+    ``inner`` sweeps with the cells around it frozen, all blocks reading the same input.  Returns ``(T, outer steps)``.
+    ``wall``: cells that are never updated; ``T_init``: the start of :func:`solve_from` instead of ``src``."""
+    dtype = np.dtype(dtype)
+    c = np.asarray(c)
     s = _slowness(c, dtype)
-    T = init_times(c, h, init, dtype)
+    T = init_times(c, h, _source(src, c.shape, h, radius), dtype) if T_init is None else np.array(T_init, dtype=dtype)
+    wall = _wall(wall, c.shape)
+    if wall is not None:
+        T = np.where(wall, dtype.type(np.inf), T)
     f = s * dtype.type(h)
     nd = c.ndim
     for n in range(1, 4 * sum(c.shape) + 1):
@@ -178,6 +235,8 @@ def solve_blocks(c, h, src, radius=0.0, tile=8, inner=4, dtype=np.float64):
             F[ins] = f[box]
             keep = np.ones(P.shape, bool)  # everything but the block's own cells is frozen
             keep[tuple(slice(o.start + 1, o.stop + 1) for o in own)] = False
+            if wall is not None:
+                keep[ins] |= wall[box]
             for _ in range(inner):
                 Pn = np.minimum(P, local_solution([t for t, _ in upwind(P)], F))
                 P = np.where(keep, P, Pn)
@@ -256,7 +315,7 @@ def gradient(T, lam, c, h, init, wrt="velocity", ball_term=True):
     c = np.asarray(c, dtype=dtype)
     _, _, dGds = derivatives(T, c, h)
     gs = dGds * lam
-    if ball_term:
+    if ball_term and init is not None:
         idx, dist, ref = init
         s = _slowness(c, dtype)
         G = local_solution([t for t, _ in upwind(T)], s * dtype.type(h))
@@ -293,7 +352,7 @@ def tangent_rhs(T, c, h, dm, init, wrt="velocity", ball_term=True):
     W, lower, dGds = derivatives(T, c, h)
     ds = -dm / (c * c) if wrt == "velocity" else dm * c / dtype.type(2)
     b = dGds * ds
-    if ball_term:
+    if ball_term and init is not None:
         idx, dist, ref = init
         G = local_solution([t for t, _ in upwind(T)], _slowness(c, dtype) * dtype.type(h))
         for k in range(len(dist)):
@@ -303,14 +362,34 @@ def tangent_rhs(T, c, h, dm, init, wrt="velocity", ball_term=True):
     return b, W, lower
 
 
-def tangent(T, c, h, dm, init, wrt="velocity", return_sweeps=False, ball_term=True, max_sweeps=None):
+def source_determined(T, c, h):
+    """Where ``T_i`` is finite and ``T_i < G_i``: the nodes whose time is their start's, not their neighbours'"""
+    G = local_solution([t for t, _ in upwind(T)], _slowness(c, T.dtype) * T.dtype.type(h))
+    return np.isfinite(T) & (T < G)
+
+
+def handover(T, c, h, x):
+    """``x`` on the source-determined nodes of the fixed point ``T`` and 0 elsewhere: what one stage of a multi-stage
+    solve hands to the stage before it (the adjoint variable) or receives from it (the tangent)"""
+    x = np.asarray(x, dtype=T.dtype)
+    return np.where(source_determined(T, c, h), x, T.dtype.type(0))
+
+
+def tangent(T, c, h, dm, init, wrt="velocity", return_sweeps=False, ball_term=True, max_sweeps=None, b0=None):
     """The derivative of the fixed point ``T`` along the model perturbation ``dm``, in ``T``'s dtype:
     ``x = b + A x`` (``A`` and ``b`` of :func:`tangent_rhs`) by Jacobi from ``x = b``, recomputed in full until a sweep
     changes no bit (``A`` is strictly causal: it stops after the longest dependency chain).  Where ``T_i = +inf`` or
     the cell is not live, ``x_i = b_i``.  ``max_sweeps=None``: ``4 * sum(shape)``; ``RuntimeError`` beyond the cap.  The
     exact transpose of :func:`adjoint` followed by :func:`gradient`; on the
-    non-differentiable set the same one-sided choice."""
+    non-differentiable set the same one-sided choice.  ``init=None``: no source term.  ``b0``: any array of the grid's
+    shape, added to ``b`` (after ``b_i``, before the axis terms): ``x = b(dm) + b0 + A x``, the tangent of a solve
+    whose start moves by ``b0`` with the model."""
     b, W, lower = tangent_rhs(T, c, h, dm, init, wrt, ball_term)
+    if b0 is not None:
+        b0 = np.asarray(b0, dtype=T.dtype)
+        if b0.shape != T.shape:
+            raise ValueError("b0 must have the grid's shape %r, got %r" % (T.shape, b0.shape))
+        b = b + b0
     x = b.copy()
     cap = 4 * sum(T.shape) if max_sweeps is None else int(max_sweeps)
     for n in range(1, cap + 1):
@@ -346,6 +425,55 @@ def exact_gradient(shape, h, c0, g, coords):
     return np.arccosh(1.0 + g * g * r2 / (2.0 * c * c0)) / g
 
 
+def interface(shape, depth):
+    """``(gamma, wall)`` of a reflector at ``depth`` cells along the first axis, one value per column (an array of
+    ``shape[1:]``, or a scalar): ``gamma`` marks the node nearest to it in every column (the lower index on a tie),
+    ``wall`` everything below that node.  Both boolean, of the grid's shape."""
+    shape = tuple(int(n) for n in shape)
+    d = np.broadcast_to(np.asarray(depth, np.float64), shape[1:])
+    if not np.all(np.isfinite(d)) or np.any(d < 0.0) or np.any(d > shape[0] - 1.0):
+        raise ValueError("the reflector must lie inside the grid [0, %d] on the first axis" % (shape[0] - 1))
+    node = np.ceil(d - 0.5).astype(np.int64)  # nearest, the lower index on a tie
+    z = np.arange(shape[0]).reshape((-1,) + (1,) * (len(shape) - 1))
+    return z == node[None], z > node[None]
+
+
+def exact_reflection_constant(shape, h, c0, src, rec, Z):
+    """The reflection time off a flat reflector at depth ``Z`` (cells, first axis) in a constant medium, by the image
+    source: ``|x_r - x_s'| / c0`` with ``x_s'`` the source mirrored at ``Z``; ``rec``: ``(n, ndim)`` coordinates"""
+    xs = np.asarray(src, np.float64).reshape(-1).copy()
+    xs[0] = 2.0 * float(Z) - xs[0]
+    r = np.asarray(rec, np.float64).reshape(-1, len(shape))
+    return np.sqrt(((r - xs) ** 2).sum(axis=1)) * float(h) / float(c0)
+
+
+def reflection_solve(c, h, src, gamma, wall, radius=0.0, dtype=np.float64):
+    """Both stages of the reflection off the nodes ``gamma`` inside ``wall``: ``(T1, T2, init)`` with ``T1`` the first
+    arrivals from ``src`` and ``T2`` the solve restarted from ``gamma`` with ``T1``'s times there"""
+    dtype = np.dtype(dtype)
+    init = _source(src, np.shape(c), h, radius)
+    T1 = solve(c, h, init, dtype=dtype, wall=wall)
+    T2 = solve_from(c, h, np.where(gamma, T1, dtype.type(np.inf)), wall, dtype=dtype)
+    return T1, T2, init
+
+
+def reflection_gradient(T1, T2, c, h, init, b2, wrt="velocity", with_handover=True):
+    """The gradient of ``sum_i b2_i T2_i`` with respect to the model, through both stages.  ``with_handover=False``
+    drops stage 1 (tests: the check against differences must then fail)."""
+    lam2 = adjoint(T2, c, h, b2)
+    g = gradient(T2, lam2, c, h, None, wrt)
+    if with_handover:
+        lam1 = adjoint(T1, c, h, handover(T2, c, h, lam2))
+        g = g + gradient(T1, lam1, c, h, init, wrt)
+    return g
+
+
+def reflection_tangent(T1, T2, c, h, init, dm, wrt="velocity"):
+    """``dT2`` along the model perturbation ``dm``: the exact transpose of :func:`reflection_gradient`"""
+    x1 = tangent(T1, c, h, dm, init, wrt)
+    return tangent(T2, c, h, dm, None, wrt, b0=handover(T2, c, h, x1))
+
+
 class TwinEngine:
     """The engine calls ``shots.traveltime_fg`` and ``shots.TraveltimeOperator`` need, backed by this module on the CPU
     (tests, prototypes): model and slots are host arrays."""
@@ -370,12 +498,55 @@ class TwinEngine:
     def vec_upload(self, slot, a):
         self.vecs[slot] = np.array(a, dtype=self.dtype).reshape(self.shape)
 
-    def eikonal(self, src, t_slot, scratch_slot, radius=0.0, max_sweeps=None):
+    def vec_copy(self, dst, src):
+        self.vecs[dst] = self.vecs[src].copy()
+
+    def _slots(self, who, **slots):
+        """what the C ABI refuses with FWI_EINVAL: a slot that does not exist, two arguments naming one slot"""
+        for name, s in slots.items():
+            if not 0 <= int(s) < len(self.vecs):
+                raise ValueError("%s: %s = %d does not exist" % (who, name, s))
+        if len(set(int(s) for s in slots.values())) != len(slots):
+            raise ValueError("%s: %s must be %d different slots, got %r"
+                             % (who, ", ".join(slots), len(slots), tuple(slots.values())))
+
+    def _wall_of(self, wall_slot):
+        return None if wall_slot is None else self.vecs[wall_slot] != 0
+
+    def eikonal(self, src, t_slot, scratch_slot, radius=0.0, max_sweeps=None, wall_slot=None):
         init = _source(src, self.shape, self.h, radius)
+        if wall_slot is not None:
+            self._slots("eikonal", t_slot=t_slot, scratch_slot=scratch_slot, wall_slot=wall_slot)
         self.vecs[t_slot], self.last_eikonal_launches = solve(self.c, self.h, init, dtype=self.dtype,
-                                                              max_sweeps=max_sweeps, return_sweeps=True)
+                                                              max_sweeps=max_sweeps, return_sweeps=True,
+                                                              wall=self._wall_of(wall_slot))
         self._init[t_slot] = init
         return init
+
+    def eikonal_restart(self, t_slot, scratch_slot, wall_slot=None, max_sweeps=None):
+        """As ``Engine.eikonal_restart``: the slot holds ``T_init``; what ``fwi_eikonal_stage`` refuses is a
+        ``ValueError`` here"""
+        slots = dict(t_slot=t_slot, scratch_slot=scratch_slot)
+        if wall_slot is not None:
+            slots["wall_slot"] = wall_slot
+        self._slots("eikonal_restart", **slots)
+        wall = self._wall_of(wall_slot)
+        try:
+            check_start(self.vecs[t_slot], wall)
+        except ValueError as err:
+            raise ValueError("eikonal_restart: t_slot: %s" % err)
+        if self.c is None:
+            raise ValueError("eikonal_restart: no model set")
+        self.vecs[t_slot], self.last_eikonal_launches = solve_from(self.c, self.h, self.vecs[t_slot], wall,
+                                                                   dtype=self.dtype, max_sweeps=max_sweeps,
+                                                                   return_sweeps=True)
+
+    def eikonal_handover(self, t_slot, in_slot, out_slot, beta=0.0):
+        self._slots("eikonal_handover", t_slot=t_slot, in_slot=in_slot, out_slot=out_slot)
+        if self.c is None:
+            raise ValueError("eikonal_handover: no model set")
+        v = handover(self.vecs[t_slot], self.c, self.h, self.vecs[in_slot])
+        self.vecs[out_slot] = v if beta == 0.0 else self.dtype.type(beta) * self.vecs[out_slot] + v
 
     def eikonal_times(self, t_slot, rec):
         return times_at(self.vecs[t_slot], rec)
@@ -392,12 +563,16 @@ class TwinEngine:
         self.vecs[lam_slot], self.last_eikonal_launches = adjoint(self.vecs[t_slot], self.c, self.h, self.vecs[rhs_slot],
                                                                   return_sweeps=True)
 
-    def eikonal_gradient(self, t_slot, lam_slot, out_slot, init, beta=0.0, wrt="velocity"):
+    def eikonal_gradient(self, t_slot, lam_slot, out_slot, init=None, beta=0.0, wrt="velocity"):
         g = gradient(self.vecs[t_slot], self.vecs[lam_slot], self.c, self.h, init, wrt)
         self.vecs[out_slot] = g if beta == 0.0 else self.dtype.type(beta) * self.vecs[out_slot] + g
 
-    def eikonal_tangent(self, t_slot, dm_slot, out_slot, scratch_slot, init, wrt="velocity", max_sweeps=None):
-        """As ``Engine.eikonal_tangent``; what ``fwi_eikonal_tangent`` refuses is a ``ValueError`` here"""
+    def eikonal_tangent(self, t_slot, dm_slot, out_slot, scratch_slot, init=None, wrt="velocity", max_sweeps=None,
+                        b0_slot=None):
+        """As ``Engine.eikonal_tangent``; what ``fwi_eikonal_tangent`` (``fwi_eikonal_tangent_stage`` with
+        ``init=None`` or a ``b0_slot``) refuses is a ``ValueError`` here"""
+        if init is None or b0_slot is not None:
+            return self._tangent_stage(t_slot, dm_slot, out_slot, scratch_slot, init, wrt, max_sweeps, b0_slot)
         slots = (t_slot, dm_slot, out_slot, scratch_slot)
         for name, s in zip(("t_slot", "dm_slot", "out_slot", "scratch_slot"), slots):
             if not 0 <= int(s) < len(self.vecs):
@@ -423,3 +598,18 @@ class TwinEngine:
         self.vecs[out_slot], self.last_eikonal_launches = tangent(self.vecs[t_slot], self.c, self.h, self.vecs[dm_slot],
                                                                   (idx, dist, ref), wrt, return_sweeps=True,
                                                                   max_sweeps=max_sweeps)
+
+    def _tangent_stage(self, t_slot, dm_slot, out_slot, scratch_slot, init, wrt, max_sweeps, b0_slot):
+        slots = dict(t_slot=t_slot, dm_slot=dm_slot, out_slot=out_slot, scratch_slot=scratch_slot)
+        if b0_slot is not None:
+            slots["b0_slot"] = b0_slot
+        self._slots("eikonal_tangent", **slots)
+        if wrt not in WRT:
+            raise ValueError("eikonal_tangent: wrt must be one of %r, got %r" % (WRT, wrt))
+        if init is not None:
+            init = _source(init, self.shape, self.h, 0.0)
+        if self.c is None:
+            raise ValueError("eikonal_tangent: no model set")
+        self.vecs[out_slot], self.last_eikonal_launches = tangent(
+            self.vecs[t_slot], self.c, self.h, self.vecs[dm_slot], init, wrt, return_sweeps=True, max_sweeps=max_sweeps,
+            b0=None if b0_slot is None else self.vecs[b0_slot])

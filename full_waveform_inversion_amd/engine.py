@@ -1142,22 +1142,46 @@ class Engine:
         return (idx, dist, ref), (len(idx), idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
                                   ref.ctypes.data_as(C.c_void_p))
 
-    def eikonal(self, src, t_slot, scratch_slot, radius=0.0, max_sweeps=None):
+    def eikonal(self, src, t_slot, scratch_slot, radius=0.0, max_sweeps=None, wall_slot=None):
         """First-arrival times of the engine's model into slot ``t_slot`` (``scratch_slot``: the other half of the
         ping-pong pair, its contents are lost).  ``src``: the source's grid coordinates, whole or fractional, turned
         into an init list by ``eikonal.ball(src, shape, h, radius)`` -- every node within ``radius`` cells starts at
         its straight-ray time in the velocity of the nearest node -- or such a list ``(idx, dist, ref)`` itself.
         Returns the init list, which :meth:`eikonal_gradient` takes.  ``max_sweeps=None``: ``4 * sum(shape)``;
-        a cap that is reached raises ``FwiError`` (FWI_ESTATE) and leaves an upper bound in the slot."""
+        a cap that is reached raises ``FwiError`` (FWI_ESTATE) and leaves an upper bound in the slot.  ``wall_slot``:
+        a slot whose cells ``!= 0`` the front may not enter (``+inf``; ``fwi_eikonal_stage``); None: ``fwi_eikonal``."""
         from . import eikonal as ek
         init, args = self._init_args(ek._source(src, self.shape, self.h, radius))
         n = C.c_int32(0)
+        cap = 0 if max_sweeps is None else int(max_sweeps)
         try:
-            self._chk(self._lib.fwi_eikonal(self._c, int(t_slot), int(scratch_slot), *args,
-                                            0 if max_sweeps is None else int(max_sweeps), C.byref(n)))
+            if wall_slot is None:
+                self._chk(self._lib.fwi_eikonal(self._c, int(t_slot), int(scratch_slot), *args, cap, C.byref(n)))
+            else:
+                self._chk(self._lib.fwi_eikonal_stage(self._c, int(t_slot), int(scratch_slot), int(wall_slot), *args,
+                                                      cap, C.byref(n)))
         finally:
             self.last_eikonal_launches = int(n.value)
         return init
+
+    def eikonal_restart(self, t_slot, scratch_slot, wall_slot=None, max_sweeps=None):
+        """Slot ``t_slot`` := the first-arrival times started from what the slot holds (``fwi_eikonal_stage`` without a
+        list; ``eikonal.solve_from`` is the definition): finite times ``>= 0`` on the secondary sources, ``+inf``
+        elsewhere -- the second stage of a reflection, a plane wave, an exploding reflector, many sources at once.
+        ``wall_slot``, ``max_sweeps`` and the cap as in :meth:`eikonal`."""
+        n = C.c_int32(0)
+        try:
+            self._chk(self._lib.fwi_eikonal_stage(self._c, int(t_slot), int(scratch_slot),
+                                                  -1 if wall_slot is None else int(wall_slot), 0, None, None, None,
+                                                  0 if max_sweeps is None else int(max_sweeps), C.byref(n)))
+        finally:
+            self.last_eikonal_launches = int(n.value)
+
+    def eikonal_handover(self, t_slot, in_slot, out_slot, beta=0.0):
+        """Slot ``out_slot := beta out_slot +`` ``in_slot`` on the source-determined nodes of the times in ``t_slot``
+        (finite and ``T_i < G_i``), 0 elsewhere (``fwi_eikonal_handover``): what a restarted solve hands to the stage
+        before it (its adjoint variable) or takes from it (the tangent)."""
+        self._chk(self._lib.fwi_eikonal_handover(self._c, int(t_slot), int(in_slot), int(out_slot), float(beta)))
 
     def eikonal_times(self, t_slot, rec):
         """The times of slot ``t_slot`` at receivers: node indices ``(n, ndim)``, or a ``points.Spread`` whose nodes
@@ -1177,27 +1201,40 @@ class Engine:
         finally:
             self.last_eikonal_launches = int(n.value)
 
-    def eikonal_gradient(self, t_slot, lam_slot, out_slot, init, beta=0.0, wrt="velocity"):
+    def eikonal_gradient(self, t_slot, lam_slot, out_slot, init=None, beta=0.0, wrt="velocity"):
         """Slot ``out_slot := beta out_slot +`` the gradient of ``sum_i rhs_i T_i`` with respect to the model, from the
-        times, the adjoint variable and the init list :meth:`eikonal` returned."""
+        times, the adjoint variable and the init list :meth:`eikonal` returned.  ``init=None``: no source term
+        (``fwi_eikonal_gradient_field``), the gradient of a restarted solve."""
         w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
+        if init is None:
+            self._chk(self._lib.fwi_eikonal_gradient_field(self._c, w, int(t_slot), int(lam_slot), int(out_slot),
+                                                           float(beta)))
+            return
         _, args = self._init_args(init)
         self._chk(self._lib.fwi_eikonal_gradient(self._c, w, int(t_slot), int(lam_slot), int(out_slot), float(beta), *args))
 
-    def eikonal_tangent(self, t_slot, dm_slot, out_slot, scratch_slot, init, wrt="velocity", max_sweeps=None):
+    def eikonal_tangent(self, t_slot, dm_slot, out_slot, scratch_slot, init=None, wrt="velocity", max_sweeps=None,
+                        b0_slot=None):
         """Slot ``out_slot`` := ``dT``, the derivative of the times in ``t_slot`` along the model perturbation in
         ``dm_slot`` (``fwi_eikonal_tangent``; ``eikonal.tangent`` is the definition): the exact transpose of
         :meth:`eikonal_adjoint` followed by :meth:`eikonal_gradient`.  ``init``: the list :meth:`eikonal` returned;
-        four different slots, ``scratch_slot``'s contents are lost."""
+        four different slots, ``scratch_slot``'s contents are lost.  ``init=None``: no source term, and ``b0_slot``: a
+        slot added to the right-hand side, ``x = b(dm) + b0 + A x`` (either: ``fwi_eikonal_tangent_stage``) -- the
+        tangent of a restarted solve, ``b0`` the :meth:`eikonal_handover` of the stage before."""
         if wrt not in ("velocity", "slowness2"):
             raise ValueError("wrt must be 'velocity' or 'slowness2', got %r" % (wrt,))
         w = {"velocity": _lib.WRT_VELOCITY, "slowness2": _lib.WRT_SLOWNESS2}[wrt]
-        _, args = self._init_args(init)
+        args = (0, None, None, None) if init is None else self._init_args(init)[1]
         n = C.c_int32(0)
+        cap = 0 if max_sweeps is None else int(max_sweeps)
         try:
-            self._chk(self._lib.fwi_eikonal_tangent(self._c, w, int(t_slot), int(dm_slot), int(out_slot),
-                                                    int(scratch_slot), *args,
-                                                    0 if max_sweeps is None else int(max_sweeps), C.byref(n)))
+            if init is not None and b0_slot is None:
+                self._chk(self._lib.fwi_eikonal_tangent(self._c, w, int(t_slot), int(dm_slot), int(out_slot),
+                                                        int(scratch_slot), *args, cap, C.byref(n)))
+            else:
+                self._chk(self._lib.fwi_eikonal_tangent_stage(self._c, w, int(t_slot), int(dm_slot),
+                                                              -1 if b0_slot is None else int(b0_slot), int(out_slot),
+                                                              int(scratch_slot), *args, cap, C.byref(n)))
         finally:
             self.last_eikonal_launches = int(n.value)
 

@@ -1079,6 +1079,21 @@ def _traveltime_points(shot):
     return np.asarray(src, np.float64), (shot.rec_spread if shot.rec_spread is not None else np.asarray(shot.rec_idx))
 
 
+def _times_of_all_shots(engine, shots, ex, one):
+    """``one(engine, i)``, the receiver times of shot ``i``, for this rank's shots: the list over all shots, complete on
+    every rank"""
+    mine = partition_shots(len(shots), ex.rank, ex.world)
+    got = engine.map_shots(mine, one) if isinstance(engine, EnginePool) else [one(engine, i) for i in mine]
+    sizes = [s.rec_spread.n if s.rec_spread is not None else len(np.asarray(s.rec_idx).reshape(-1, np.shape(s.rec_idx)[-1]))
+             for s in shots]
+    ends = np.cumsum([0] + sizes)
+    flat = np.zeros(ends[-1])
+    for i, v in zip(mine, got):
+        flat[ends[i]:ends[i + 1]] = v
+    flat = np.asarray(ex.reduce_array(flat))
+    return [flat[ends[i]:ends[i + 1]].copy() for i in range(len(shots))]
+
+
 def traveltime_times(engine, model, shots, radius=0.0, slot0=0, exchange=None):
     """First-arrival times of every shot at its receivers in ``model`` (None: the model the engines hold): a list
     indexed like ``shots``, complete on every rank.  The picks of a synthetic test, or the times of a
@@ -1093,16 +1108,7 @@ def traveltime_times(engine, model, shots, radius=0.0, slot0=0, exchange=None):
         e.eikonal(src, slot0, slot0 + 1, radius=radius)
         return e.eikonal_times(slot0, rec)
 
-    mine = partition_shots(len(shots), ex.rank, ex.world)
-    got = engine.map_shots(mine, one) if isinstance(engine, EnginePool) else [one(engine, i) for i in mine]
-    sizes = [s.rec_spread.n if s.rec_spread is not None else len(np.asarray(s.rec_idx).reshape(-1, np.shape(s.rec_idx)[-1]))
-             for s in shots]
-    ends = np.cumsum([0] + sizes)
-    flat = np.zeros(ends[-1])
-    for i, v in zip(mine, got):
-        flat[ends[i]:ends[i + 1]] = v
-    flat = np.asarray(ex.reduce_array(flat))
-    return [flat[ends[i]:ends[i + 1]].copy() for i in range(len(shots))]
+    return _times_of_all_shots(engine, shots, ex, one)
 
 
 def traveltime_fg(engine, model, shots, picks, pick_weights=None, radius=0.0, slot0=0, exchange=None, wrt="velocity"):
@@ -1199,7 +1205,7 @@ class TraveltimeOperator:
         self.ex = exchange or NoExchange()
         self.keep_times = bool(keep_times)
         self.engines = _engines(engine)
-        self.SC, self.V, self.X, self.B, self.L, self.G = (int(slot0) + k for k in range(self.WORK_SLOTS))
+        self.SC, self.V, self.X, self.B, self.L, self.G = (int(slot0) + k for k in range(6))
         self.T0 = int(slot0) + self.WORK_SLOTS
         self.mine = partition_shots(len(shots), self.ex.rank, self.ex.world)
         self.solves = {"eikonal": 0, "tangent": 0, "adjoint": 0}
@@ -1224,18 +1230,24 @@ class TraveltimeOperator:
                 raise ValueError("shot %d: %d receivers, %d weights" % (i, n, w.size))
             self.weights.append(w)
         self.inits = {}
+        self._prepare()
         if self.keep_times:
             self._map(lambda e, pos, i: self._solve(e, pos, i))
-            self.solves["eikonal"] += len(self.mine)
+            self.solves["eikonal"] += self.STAGES * len(self.mine)
+
+    STAGES = 1       # eikonal solves per shot, and slots that hold a shot's times
+
+    def _prepare(self):
+        """what the engines need before the first solve (nothing here)"""
 
     def slots_needed(self, n_local):
         """vector slots used from ``slot0`` on by a rank with ``n_local`` shots (on each of its engines)"""
         per_engine = -(-int(n_local) // len(self.engines))
-        return self.WORK_SLOTS + (max(1, per_engine) if self.keep_times else 1)
+        return self.WORK_SLOTS + self.STAGES * (max(1, per_engine) if self.keep_times else 1)
 
     # position pos of this rank's shots runs on engine pos % n, as EnginePool.map_shots deals them out
     def _t_slot(self, pos):
-        return self.T0 + (pos // len(self.engines) if self.keep_times else 0)
+        return self.T0 + self.STAGES * (pos // len(self.engines) if self.keep_times else 0) + self.STAGES - 1
 
     def _map(self, fn):
         pos_of = {i: pos for pos, i in enumerate(self.mine)}
@@ -1261,7 +1273,7 @@ class TraveltimeOperator:
         return [flat[ends[i]:ends[i + 1]].copy() for i in range(len(self.shots))]
 
     def _count(self, tangent=0, adjoint=0):
-        n = len(self.mine)
+        n = self.STAGES * len(self.mine)
         self.solves["tangent"] += tangent * n
         self.solves["adjoint"] += adjoint * n
         self.solves["eikonal"] += 0 if self.keep_times else n
@@ -1300,7 +1312,7 @@ class TraveltimeOperator:
     def times(self):
         """The times of every shot at its receivers, as :func:`traveltime_times`"""
         if not self.keep_times:
-            self.solves["eikonal"] += len(self.mine)
+            self.solves["eikonal"] += self.STAGES * len(self.mine)
         return self._complete(self._map(lambda e, pos, i: e.eikonal_times(self._times_slot(e, pos, i), self.points[i][1])))
 
     def jvp(self, v):
@@ -1331,3 +1343,162 @@ class TraveltimeOperator:
 
         self._map(one)
         return self._gather_gradient(first)
+
+
+# Reflection traveltimes off a fixed interface: two first-arrival solves in a row (eikonal.py defines
+# every piece).  Stage 1 runs from the source inside the wall; stage 2 restarts from the interface nodes with the times
+# they just got.  Out of scope: the reflector's depth as an unknown, head waves, multiples, transmitted conversions.
+REFLECTION_SLOTS = 10  # reflection_fg from slot0 on: wall, start, T1, T2, scratch, right-hand side, lambda2, handover,
+#                        lambda1, gradient
+
+
+class Reflector:
+    """A fixed interface: ``gamma`` marks its nodes and ``wall`` the cells beyond it that no front may enter, both
+    boolean arrays of the grid's shape, as ``eikonal.interface(shape, depth)`` returns them."""
+
+    def __init__(self, gamma, wall):
+        self.gamma, self.wall = np.asarray(gamma) != 0, np.asarray(wall) != 0
+        if self.gamma.shape != self.wall.shape:
+            raise ValueError("gamma %r and wall %r must have the grid's shape" % (self.gamma.shape, self.wall.shape))
+        if not self.gamma.any() or (self.gamma & self.wall).any():
+            raise ValueError("the interface needs at least one node, and none of its nodes may be walled")
+        self.gamma_nodes = np.ascontiguousarray(np.argwhere(self.gamma), dtype=np.int32)  # ascending flat order
+
+    @classmethod
+    def at_depth(cls, shape, depth):
+        from . import eikonal as ek
+        return cls(*ek.interface(shape, depth))
+
+    def upload(self, e, wall_slot, start_slot):
+        """the wall (1 in its cells) and the start's template (0 on the interface, +inf elsewhere) into two slots"""
+        dtype = getattr(e, "dtype", np.float64)
+        e.vec_upload(wall_slot, self.wall.astype(dtype))
+        e.vec_upload(start_slot, np.where(self.gamma, 0.0, np.inf).astype(dtype))
+
+    def solve(self, e, src, radius, W, S0, T1, T2, SC):
+        """both stages on engine ``e``: T1, then T2 started on the device from T1's times on the interface (only the
+        interface's values cross).  Returns the init list of stage 1."""
+        init = e.eikonal(src, T1, SC, radius=radius, wall_slot=W)
+        v = e.vec_gather_points(T1, self.gamma_nodes)
+        if not np.all(np.isfinite(v)):
+            raise ValueError("stage 1 does not reach %d of the interface's %d nodes" % (np.count_nonzero(~np.isfinite(v)), v.size))
+        e.vec_copy(T2, S0)
+        e.vec_scatter_points(T2, self.gamma_nodes, v, beta=1.0)  # 0 + T1 on the interface, +inf stays +inf
+        e.eikonal_restart(T2, SC, wall_slot=W)
+        return init
+
+
+def _reflection_vjp(e, T1, T2, B, L2, H, L1, G, SC, init, beta, wrt):
+    """G := beta G + the gradient of <B, T2> through both stages"""
+    e.eikonal_adjoint(T2, B, L2, SC)
+    e.eikonal_handover(T2, L2, H)
+    e.eikonal_adjoint(T1, H, L1, SC)
+    e.eikonal_gradient(T2, L2, G, None, beta=beta, wrt=wrt)
+    e.eikonal_gradient(T1, L1, G, init, beta=1.0, wrt=wrt)
+
+
+def reflection_times(engine, model, shots, reflector, radius=0.0, slot0=0, exchange=None):
+    """Reflection times off ``reflector`` of every shot at its receivers in ``model`` (None: the model the engines
+    hold), as :func:`traveltime_times`.  Uses the first five of the ``REFLECTION_SLOTS``."""
+    ex = exchange or NoExchange()
+    W, S0, T1, T2, SC = (slot0 + k for k in range(5))
+    for e in _engines(engine):
+        if model is not None:
+            e.set_model(model)
+        reflector.upload(e, W, S0)
+
+    def one(e, i):
+        src, rec = _traveltime_points(shots[i])
+        reflector.solve(e, src, radius, W, S0, T1, T2, SC)
+        return e.eikonal_times(T2, rec)
+
+    return _times_of_all_shots(engine, shots, ex, one)
+
+
+def reflection_fg(engine, model, shots, picks, reflector, pick_weights=None, radius=0.0, slot0=0, exchange=None,
+                  wrt="velocity"):
+    """Reflection traveltime tomography off a fixed ``reflector``: ``(J, g)`` of :func:`traveltime_fg`'s functional with
+    the reflection times in place of the first arrivals, for ``lbfgs``.  Per shot two eikonal solves, two adjoint
+    solves with one handover between them and two gradient passes; the wall and the start's template are uploaded once
+    per engine, the stage-2 start is built on the device, and only receiver and interface values cross per shot.
+    Uses the ``REFLECTION_SLOTS`` vector slots from ``slot0`` on.  Runs on ``eikonal.TwinEngine`` too."""
+    ex = exchange or NoExchange()
+    W, S0, T1, T2, SC, B, L2, H, L1, G = (slot0 + k for k in range(REFLECTION_SLOTS))
+    engines = _engines(engine)
+    for e in engines:
+        e.set_model(model)
+        reflector.upload(e, W, S0)
+    first = {id(e): True for e in engines}
+
+    def one(e, i):
+        src, rec = _traveltime_points(shots[i])
+        t = np.asarray(picks[i], np.float64).reshape(-1)
+        w = np.ones(t.shape) if pick_weights is None or pick_weights[i] is None else \
+            np.asarray(pick_weights[i], np.float64).reshape(-1)
+        init = reflector.solve(e, src, radius, W, S0, T1, T2, SC)
+        tau = e.eikonal_times(T2, rec)
+        if t.shape != tau.shape or w.shape != tau.shape:
+            raise ValueError("shot %d: %d receivers, %d picks, %d weights" % (i, tau.size, t.size, w.size))
+        ok = ~np.isnan(t)
+        r = np.where(ok, w * (tau - np.where(ok, t, 0.0)), 0.0)  # dJ/dT2(x_r)
+        nodes, vals = _receiver_nodes(rec, r)
+        e.vec_scatter_points(B, nodes, vals, beta=0.0)
+        _reflection_vjp(e, T1, T2, B, L2, H, L1, G, SC, init, 0.0 if first[id(e)] else 1.0, wrt)
+        first[id(e)] = False
+        return 0.5 * float(np.sum(np.where(ok, w * (tau - np.where(ok, t, 0.0)) ** 2, 0.0)))
+
+    mine = partition_shots(len(shots), ex.rank, ex.world)
+    if isinstance(engine, EnginePool):
+        J = float(sum(engine.map_shots(mine, one)))
+    else:
+        J = float(sum(one(engine, i) for i in mine))
+    shape = np.shape(model)
+    g = np.zeros(shape, np.float64)
+    for e in engines:
+        if not first[id(e)]:
+            g += np.asarray(e.vec_download(G), np.float64)
+    g = np.asarray(ex.reduce_array(g)).reshape(shape)
+    J = float(np.asarray(ex.reduce_array(np.array([J]))).ravel()[0])
+    return J, g
+
+
+class ReflectionOperator(TraveltimeOperator):
+    """:class:`TraveltimeOperator` for the reflection times off a fixed ``reflector``: ``times``, ``jvp``, ``vjp``,
+    ``hvp`` and ``solves`` mean the same, every solve being two (one per stage, with a handover between them), so that
+    ``newton.traveltime_newton_step(op, g, ...)`` runs on it.  With ``keep_times`` every local shot keeps both stages'
+    times: ``slots_needed(n_local)`` is ``WORK_SLOTS + 2 * shots per engine``."""
+
+    WORK_SLOTS = 11  # the parent's six; wall, start, handover, stage 1's dT, stage 1's lambda; the times follow
+    STAGES = 2
+
+    def __init__(self, engine, model, shots, reflector, **kw):
+        self.reflector = reflector
+        super().__init__(engine, model, shots, **kw)
+
+    def _prepare(self):
+        self.W, self.S0, self.H, self.X1, self.L1 = (self.SC + 6 + k for k in range(5))
+        for e in self.engines:
+            self.reflector.upload(e, self.W, self.S0)
+
+    def _solve(self, e, pos, i):
+        T2 = self._t_slot(pos)
+        self.inits[i] = self.reflector.solve(e, self.points[i][0], self.radius, self.W, self.S0, T2 - 1, T2, self.SC)
+
+    def _jvp_one(self, e, pos, i):
+        T2 = self._times_slot(e, pos, i)
+        e.eikonal_tangent(T2 - 1, self.V, self.X1, self.SC, self.inits[i], wrt=self.wrt)
+        e.eikonal_handover(T2, self.X1, self.H)
+        e.eikonal_tangent(T2, self.V, self.X, self.SC, None, wrt=self.wrt, b0_slot=self.H)
+        rec = self.points[i][1]
+        if hasattr(rec, "pt_start"):
+            x = e.vec_gather_points(self.X, rec.idx) * rec.weights
+            return np.add.reduceat(x, rec.pt_start[:-1]) if len(x) else np.zeros(0)
+        return e.vec_gather_points(self.X, rec)
+
+    def _vjp_one(self, e, pos, i, r, first, solve=True):
+        T2 = self._times_slot(e, pos, i) if solve else self._t_slot(pos)
+        nodes, vals = _receiver_nodes(self.points[i][1], np.asarray(r, np.float64).reshape(-1))
+        e.vec_scatter_points(self.B, nodes, vals, beta=0.0)
+        _reflection_vjp(e, T2 - 1, T2, self.B, self.L, self.H, self.L1, self.G, self.SC, self.inits[i],
+                        0.0 if first[id(e)] else 1.0, self.wrt)
+        first[id(e)] = False

@@ -833,7 +833,8 @@ int fwi_vec_gather_points(fwi_ctx *ctx, int32_t slot, int32_t n, const int32_t *
  * slot that does not exist; two arguments naming the same slot (out_slot may not be t_slot or lam_slot); an empty init
  * list; a listed or reference node outside the grid or listed twice; a negative or non-finite distance or beta; an
  * unknown wrt; a null pointer.  FWI_ESTATE: no model set.  No sweep state of the context is touched.  Out of scope:
- * the factored equation, second-order stencils, anisotropy, later arrivals.  No reference counterpart. */
+ * the factored equation, second-order stencils, anisotropy; of the later arrivals all but reflections off a fixed
+ * interface (fwi_eikonal_stage below).  No reference counterpart. */
 int fwi_eikonal(fwi_ctx *ctx, int32_t t_slot, int32_t scratch_slot, int32_t n_init, const int32_t *init_idx,
                 const double *init_dist, const int32_t *ref_idx, int32_t max_sweeps, int32_t *launches_out);
 int fwi_eikonal_adjoint(fwi_ctx *ctx, int32_t t_slot, int32_t rhs_slot, int32_t lam_slot, int32_t scratch_slot,
@@ -864,6 +865,51 @@ int fwi_eikonal_gradient(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t lam_
 int fwi_eikonal_tangent(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t dm_slot, int32_t out_slot,
                         int32_t scratch_slot, int32_t n_init, const int32_t *init_idx, const double *init_dist,
                         const int32_t *ref_idx, int32_t max_sweeps, int32_t *launches_out);
+
+/* Walled and slot-started solves, and what chains two of them into the reflection off a FIXED interface (DESIGN.md
+ * s.4y; the definitions are `solve_from`, `handover` and `tangent(..., b0)` of full_waveform_inversion_amd/eikonal.py).
+ * A wall is a vector slot: a cell whose value there is != 0 holds T = +inf from start to end, whatever the start says,
+ * and is never updated, so that to every other cell it is a neighbour outside the grid.  A node is source-determined
+ * when its final T_i is finite and < G_i; then T_i is its start's.  Reflection off the nodes Gamma inside a wall:
+ * stage 1 is fwi_eikonal_stage from the source's list with the wall, stage 2 fwi_eikonal_stage with n_init == 0 from a
+ * slot that holds stage 1's times on Gamma and +inf elsewhere; backwards lambda_2 = adjoint(T_2), fwi_eikonal_handover
+ * (T_2, lambda_2) is the right-hand side of stage 1's adjoint, and the gradient is fwi_eikonal_gradient_field(T_2,
+ * lambda_2) + fwi_eikonal_gradient(T_1, lambda_1); forwards x_1 = fwi_eikonal_tangent(T_1), x_2 =
+ * fwi_eikonal_tangent_stage(T_2, b0 = fwi_eikonal_handover(T_2, x_1), n_init = 0).  The two are exact transposes.
+ * fwi_eikonal_adjoint needs no wall: a walled cell is not live and nobody's upwind neighbour.
+ *
+ * fwi_eikonal_stage: t_slot := the limit of T <- min(T, G(T)) from T_init.  n_init > 0: T_init comes from the list as in
+ *   fwi_eikonal; n_init == 0: t_slot holds T_init (finite and >= 0 on the secondary sources, +inf elsewhere; the list
+ *   pointers are not read).  wall_slot == -1: no wall, and nothing is read for one; with a list the times, both slots
+ *   and *launches_out are then those of fwi_eikonal bit for bit (the same launches).  With a wall every launch reads
+ *   one more value per cell.  Launches, K, max_sweeps, the cap (FWI_ESTATE, an upper bound of T in t_slot) and
+ *   *launches_out as for fwi_eikonal; both slots end equal, walled cells +inf in both.  Synchronises once more than
+ *   fwi_eikonal when n_init == 0 (the check of the start).
+ * fwi_eikonal_handover: out_slot := beta out_slot + [T_i finite and T_i < G_i] in_slot, G from the neighbours' times in
+ *   t_slot as in fwi_eikonal_gradient.  One elementwise pass; with beta == 0 out_slot is not read.  Stream-ordered.
+ * fwi_eikonal_gradient_field: fwi_eikonal_gradient without the source term (no list): the gradient of a stage whose
+ *   start is handed over and not a function of the model at a reference node.
+ * fwi_eikonal_tangent_stage: out_slot := the solution of x = b(dm) + b0 + A x with b and A of fwi_eikonal_tangent and
+ *   b0 the values of b0_slot (-1: none), added after b_i and before the axis terms.  n_init == 0: no list, no source
+ *   term.  Both slots start as 0 + b0_i on the cells that are not live (a listed source-determined node:
+ *   init_dist[k] ds[ref] + b0_i) and 0 on the live ones.  Without b0_slot the launches are fwi_eikonal_tangent's.
+ * No atomics on the fields; pad columns of every slot stay zero; equal inputs give equal bits.  Refused before anything
+ * is written -- FWI_EINVAL, naming the argument: a slot that does not exist (wall_slot and b0_slot: other than -1); two
+ * arguments naming one slot; n_init < 0; with n_init == 0 a start that holds, outside the wall, a NaN, a negative entry
+ * or no finite entry; with n_init > 0 a bad list as in fwi_eikonal; an unknown wrt; a beta that is not finite.
+ * FWI_ESTATE: no model set.  The values of the wall, dm, b0 and in are not validated.  No sweep state of the context is
+ * touched.  Out of scope: the reflector's depth as an unknown, a sub-cell reflector position, head waves, multiples and
+ * transmitted conversions as separate arrivals.  No reference counterpart. */
+int fwi_eikonal_stage(fwi_ctx *ctx, int32_t t_slot, int32_t scratch_slot, int32_t wall_slot /* -1: none */,
+                      int32_t n_init /* 0: t_slot holds T_init */, const int32_t *init_idx, const double *init_dist,
+                      const int32_t *ref_idx, int32_t max_sweeps, int32_t *launches_out);
+int fwi_eikonal_handover(fwi_ctx *ctx, int32_t t_slot, int32_t in_slot, int32_t out_slot, double beta);
+int fwi_eikonal_gradient_field(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t lam_slot, int32_t out_slot,
+                               double beta);
+int fwi_eikonal_tangent_stage(fwi_ctx *ctx, int32_t wrt, int32_t t_slot, int32_t dm_slot,
+                              int32_t b0_slot /* -1: none */, int32_t out_slot, int32_t scratch_slot,
+                              int32_t n_init /* 0: no list */, const int32_t *init_idx, const double *init_dist,
+                              const int32_t *ref_idx, int32_t max_sweeps, int32_t *launches_out);
 
 /* Born (linearised) modelling dd = J dm: the exact derivative of the discrete fwi_forward along a model perturbation,
  * whose exact transpose is fwi_adjoint(image) + fwi_gradient.  With C = dt^2 c^2 and q^n the forward term the store of

@@ -175,11 +175,19 @@ def main():
                          "of the run")
     ap.add_argument("--tomography-radius", type=float, default=3.0, metavar="R",
                     help="cells around each source that start at their straight-ray time (eikonal.ball)")
+    ap.add_argument("--tomography-reflector", type=float, default=None, metavar="DEPTH_CELLS",
+                    help="add the reflection traveltimes off a flat, fixed reflector at that depth (cells along the first "
+                         "axis, rounded to the nearest node; shots.reflection_fg) to the --tomography objective, on picks "
+                         "taken from the true model's reflection times; every source must lie above it")
     ap.add_argument("--tomography-newton", type=int, default=None, metavar="CG_ITERS",
                     help="the --tomography ITERS iterations are damped Gauss-Newton ones (newton.traveltime_gauss_newton: "
                          "at most CG_ITERS conjugate-gradient products per iteration, each a tangent and an adjoint "
                          "eikonal solve per shot) instead of L-BFGS; --smooth preconditions the inner iteration")
     a = ap.parse_args()
+    if a.tomography_reflector is not None and (a.tomography < 1 or a.tomography_newton is not None
+                                               or not a.tomography_reflector >= 0.0):
+        ap.error("--tomography-reflector DEPTH_CELLS must be >= 0, needs --tomography ITERS and runs under L-BFGS only "
+                 "(not with --tomography-newton)")
     if a.tomography_newton is not None and (a.tomography_newton < 1 or a.tomography < 1):
         ap.error("--tomography-newton CG_ITERS must be >= 1 and needs --tomography ITERS")
     if a.tomography < 0 or not (a.tomography_radius >= 0.0 and np.isfinite(a.tomography_radius)):
@@ -396,13 +404,23 @@ def main():
         n_local = len(sh.partition_shots(len(shots), ex.rank, ex.world))  # "solves" below counts this rank's
         per_engine = -(-n_local // len(pool.engines))
         for eng in pool.engines:  # the Gauss-Newton operator keeps every local shot's times in a slot of its own
-            eng.vec_create(sh.TRAVELTIME_SLOTS if a.tomography_newton is None else
+            eng.vec_create(sh.TRAVELTIME_SLOTS + (sh.REFLECTION_SLOTS if a.tomography_reflector is not None else 0)
+                           if a.tomography_newton is None else
                            max(sh.TRAVELTIME_SLOTS, sh.TraveltimeOperator.WORK_SLOTS + max(1, per_engine)))
         picks = sh.traveltime_times(pool, w.c.astype(np.float32), shots, a.tomography_radius, 0, ex)
+        reflector = refl_picks = None
+        if a.tomography_reflector is not None:  # the reflection's slots follow the first arrivals'
+            reflector = sh.Reflector.at_depth(w.shape, a.tomography_reflector)
+            refl_picks = sh.reflection_times(pool, w.c.astype(np.float32), shots, reflector, a.tomography_radius,
+                                             sh.TRAVELTIME_SLOTS, ex)
         tomo_J = []
 
         def fg_tomo(m):
             J, g = sh.traveltime_fg(pool, np.asarray(m, np.float32), shots, picks, None, a.tomography_radius, 0, ex)
+            if reflector is not None:
+                Jr, gr = sh.reflection_fg(pool, np.asarray(m, np.float32), shots, refl_picks, reflector, None,
+                                          a.tomography_radius, sh.TRAVELTIME_SLOTS, ex)
+                J, g = J + Jr, g + gr
             tomo_J.append(J)
             return J, g
         if a.regularize is not None:
@@ -417,6 +435,9 @@ def main():
             tomo = {"solver": "lbfgs", "iters": a.tomography, "radius": a.tomography_radius,
                     "evaluations": len(tomo_J), "J": [float(l["f"]) for l in tomo_log],
                     "solves": {"eikonal": len(tomo_J) * n_local, "tangent": 0, "adjoint": len(tomo_J) * n_local}}
+            if reflector is not None:  # two more solves of either kind per shot and evaluation
+                tomo["reflector"] = {"depth_cells": a.tomography_reflector, "interface_nodes": int(reflector.gamma.sum())}
+                tomo["solves"] = {"eikonal": 3 * len(tomo_J) * n_local, "tangent": 0, "adjoint": 3 * len(tomo_J) * n_local}
         else:
             reg = None if a.regularize is None else rg.Regularizer(
                 a.reg_weight, a.regularize, 1.0,
