@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "fwi_host.h"
+#include "fwi_points.h"
 #include "fwi_born.h"
 #include "fwi_fourier.h"
 #include "fwi_fimage.h"
@@ -244,21 +245,12 @@ struct TimeLoop {
     }
 };
 
-// Translate (n, ndim) int32 grid indices into padded / compact flat indices.
-int flatten(fwi_ctx *ctx, const int32_t *idx, int n, std::vector<int64_t> &pidx,
-            std::vector<int64_t> &cidx) {
-    const GridDesc &g = ctx->gd;
-    pidx.resize(n);
-    cidx.resize(n);
-    for (int i = 0; i < n; ++i) {
-        const int32_t *t = idx + (size_t)i * g.ndim;
-        const int z = t[0], y = (g.ndim == 3) ? t[1] : 0, x = t[g.ndim - 1];
-        if (z < 0 || z >= g.nz || y < 0 || y >= g.ny || x < 0 || x >= g.nx)
-            return ctx->fail(FWI_EINVAL, "grid index %d outside the grid", i);
-        pidx[i] = g.off0 + (int64_t)z * g.sz + (int64_t)y * g.sy + x;
-        cidx[i] = ((int64_t)z * g.ny + y) * g.cx + x;
-    }
-    return FWI_OK;
+// v in a table's order: out[k] = v[col[k]]
+template <typename V>
+std::vector<V> permuted(const std::vector<V> &v, const std::vector<int> &col) {
+    std::vector<V> out(col.size());
+    for (size_t k = 0; k < col.size(); ++k) out[k] = v[col[k]];
+    return out;
 }
 
 template <typename T>
@@ -456,10 +448,10 @@ struct Impl {
 
     static int upload_set(fwi_ctx *ctx, fwi_ctx::PointSet &ps, int32_t n, const int32_t *idx,
                           double scale) {
-        const GridDesc &g = ctx->gd;
-        std::vector<int64_t> p, c;
+        FlatPoints flat;
+        const int outside = flatten(ctx->gd, idx, n, &flat);
+        if (outside >= 0) return ctx->fail(FWI_EINVAL, "grid index %d outside the grid", outside);
         int rcode;
-        if ((rcode = flatten(ctx, idx, n, p, c))) return rcode;
         const size_t need = (size_t)n * 8 + 16;
         if ((rcode = ensure_all(ctx, ps.member, 0, {&ps.pidx, &ps.cidx, &ps.cu, &ps.cq, &ps.s_pidx, &ps.s_cidx, &ps.s_cu,
                                                     &ps.s_cq, &ps.s_col, &ps.s_run}, &ps.cap, need)))
@@ -467,8 +459,8 @@ struct Impl {
         auto up = [&](void *d, const void *h, size_t b) {
             return b ? hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
         };
-        HIPCHK(ctx, up(ps.pidx, p.data(), (size_t)n * 8));
-        HIPCHK(ctx, up(ps.cidx, c.data(), (size_t)n * 8));
+        HIPCHK(ctx, up(ps.pidx, flat.pidx.data(), (size_t)n * 8));
+        HIPCHK(ctx, up(ps.cidx, flat.cidx.data(), (size_t)n * 8));
         // velocities at the points: gathered from the device copy of the model
         std::vector<T> cpt(n), cu, cq;
         if (n) {
@@ -480,185 +472,62 @@ struct Impl {
         point_coefs(ctx, idx, n, scale, cpt, cu, cq);
         HIPCHK(ctx, up(ps.cu, cu.data(), (size_t)n * sizeof(T)));
         HIPCHK(ctx, up(ps.cq, cq.data(), (size_t)n * sizeof(T)));
-        std::vector<int> start, col;
-        std::vector<int64_t> sp, sc;
-        std::vector<T> scu, scq;
-        {  // counting sort of the entries by the step kernel's workgroup tile
-            const bool st = ctx->kernel == K_STREAM;
-            const int ntile = st ? stream_num_tiles(g, ctx->tune) : point_num_tiles(g);
-            start.assign(ntile + 1, 0);
-            std::vector<int> tile(n);
-            for (int i = 0; i < n; ++i) {
-                const int32_t *t = idx + (size_t)i * g.ndim;
-                const int z = t[0], y = (g.ndim == 3) ? t[1] : 0, x = t[g.ndim - 1];
-                tile[i] = st ? stream_tile_of(g, ctx->tune, z, y, x) : point_tile_of(g, z, y, x);
-                ++start[tile[i] + 1];
-            }
-            for (int k = 0; k < ntile; ++k) start[k + 1] += start[k];
-            // within a tile by node, then by entry: the entries of one node are consecutive (the kernels add such a
-            // run from one thread in this order, inject_runs)
-            std::vector<int> ord(n);
-            for (int i = 0; i < n; ++i) ord[i] = i;
-            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) {
-                return tile[x] != tile[y] ? tile[x] < tile[y] : p[x] < p[y];
-            });
-            col.resize(n); sp.resize(n); sc.resize(n); scu.resize(n); scq.resize(n);
-            std::vector<int> run(n, 0);
-            for (int k = 0; k < n; ++k) {
-                const int i = ord[k];
-                col[k] = i; sp[k] = p[i]; sc[k] = c[i]; scu[k] = cu[i]; scq[k] = cq[i];
-            }
-            for (int k = n - 1, len = 0; k >= 0; --k) {  // run length at the first entry of each node's run
-                len = (k + 1 < n && sp[k + 1] == sp[k] && tile[ord[k + 1]] == tile[ord[k]]) ? len + 1 : 1;
-                run[k] = (k == 0 || sp[k - 1] != sp[k] || tile[ord[k - 1]] != tile[ord[k]]) ? len : 0;
-            }
-            const size_t sb = start.size() * sizeof(int);
-            if ((rcode = ensure(ctx, ps.s_start, sb))) return rcode;
-            HIPCHK(ctx, up(ps.s_start.p, start.data(), sb));
-            HIPCHK(ctx, up(ps.s_pidx, sp.data(), (size_t)n * 8));
-            HIPCHK(ctx, up(ps.s_cidx, sc.data(), (size_t)n * 8));
-            HIPCHK(ctx, up(ps.s_cu, scu.data(), (size_t)n * sizeof(T)));
-            HIPCHK(ctx, up(ps.s_cq, scq.data(), (size_t)n * sizeof(T)));
-            HIPCHK(ctx, up(ps.s_col, col.data(), (size_t)n * sizeof(int)));
-            HIPCHK(ctx, up(ps.s_run, run.data(), (size_t)n * sizeof(int)));
-        }
-        std::vector<int> fst, flz, flx, fcol, rst, rlz, rlx, rcol;
-        std::vector<unsigned char> fint;
+
+        // the tables (fwi_points.h) and the coefficients in each table's order; all of it lives until the last copy is done
+        StepTable st;
+        Fused2dTables ft;
+        Pair3dTable pt;
+        step_table(*ctx, idx, n, flat, &st);
+        const std::vector<T> scu = permuted(cu, st.col), scq = permuted(cq, st.col);
         std::vector<int64_t> fcidx;
         std::vector<T> fcu, fcq;
         if (ctx->fused2d) {
-            // entries of the fused 2-D kernel: a point is injected by every tile whose EXTENDED region
-            // holds it (each keeps a private copy of the halo) and sampled by the one tile owning it
-            const int FT = ctx->fused_ft;
-            const int HL = (FUSED2D_STEPS * g.r + 3) / 4 * 4;  // as in step2d_fused
-            const int ntx = (g.nx + FT - 1) / FT, ntz = (g.nz + FT - 1) / FT, ntile = ntx * ntz;
-            struct Ent { int tile, lz, lx, col; unsigned char interior; };
-            std::vector<Ent> ents;
-            // (with the CPML inside the launch the tiles are whole, with one overlap seam per axis: fused2d_origin /
-            // fused2d_own give every tile's first cell and the first cell it owns)
-            const int seam = ctx->cpml ? 1 : 0;
-            struct Ax { int t, l; bool own; };
-            auto tiles_of = [&](int c, int nn, int nt, Ax *out) {  // tiles whose extended region holds coordinate c
-                int m = 0;
-                // HL <= FT and the seam shifts a tile by less than FT: the owning tile's index is within 2 of c / FT
-                for (int t = std::max(0, c / FT - 1); t <= std::min(nt - 1, c / FT + 2); ++t) {
-                    const int o = fused2d_origin(t, nn, FT, seam);
-                    if (c < o - HL || c >= o + FT + HL) continue;
-                    const int lo = fused2d_own(t, nn, FT, seam), hi = t + 1 < nt ? fused2d_own(t + 1, nn, FT, seam) : nn;
-                    out[m++] = Ax{t, c - (o - HL), c >= lo && c < hi};
-                }
-                return m;
-            };
-            for (int i = 0; i < n; ++i) {
-                const int z = idx[(size_t)i * g.ndim], x = idx[(size_t)i * g.ndim + 1];
-                Ax az[4], ax[4];
-                const int mz = tiles_of(z, g.nz, ntz, az), mx = tiles_of(x, g.nx, ntx, ax);
-                for (int p = 0; p < mz; ++p)
-                    for (int q = 0; q < mx; ++q)
-                        ents.push_back({az[p].t * ntx + ax[q].t, az[p].l, ax[q].l, i, (unsigned char)(az[p].own && ax[q].own)});
-            }
-            std::stable_sort(ents.begin(), ents.end(), [](const Ent &x, const Ent &y) {
-                if (x.tile != y.tile) return x.tile < y.tile;
-                return x.lz != y.lz ? x.lz < y.lz : x.lx < y.lx;  // a node's entries consecutive, in entry order
-            });
-            auto build = [&](bool interior_only, std::vector<int> &st, std::vector<int> &lz, std::vector<int> &lx,
-                             std::vector<int> &col, std::vector<int> *order) {
-                st.assign(ntile + 1, 0);
-                for (const Ent &e : ents)
-                    if (!interior_only || e.interior) ++st[e.tile + 1];
-                for (int k = 0; k < ntile; ++k) st[k + 1] += st[k];
-                std::vector<int> fill(st.begin(), st.end() - 1);
-                const int tot = st[ntile];
-                lz.resize(tot); lx.resize(tot); col.resize(tot);
-                if (order) order->resize(tot);
-                for (size_t q = 0; q < ents.size(); ++q) {
-                    const Ent &e = ents[q];
-                    if (interior_only && !e.interior) continue;
-                    const int k = fill[e.tile]++;
-                    lz[k] = e.lz; lx[k] = e.lx; col[k] = e.col;
-                    if (order) (*order)[k] = (int)q;
-                }
-            };
-            std::vector<int> order;
-            build(false, fst, flz, flx, fcol, &order);
-            build(true, rst, rlz, rlx, rcol, nullptr);
-            const size_t ne = order.size();
-            fint.resize(ne); fcidx.resize(ne); fcu.resize(ne); fcq.resize(ne);
-            for (size_t k = 0; k < ne; ++k) {
-                const Ent &e = ents[order[k]];
-                fint[k] = e.interior; fcidx[k] = c[e.col]; fcu[k] = cu[e.col]; fcq[k] = cq[e.col];
-            }
-            const size_t fneed = ne * 8 + 16, sneed = (size_t)(ntile + 1) * sizeof(int);
+            fused2d_tables(*ctx, idx, n, &ft);
+            fcidx = permuted(flat.cidx, ft.col);
+            fcu = permuted(cu, ft.col);
+            fcq = permuted(cq, ft.col);
+        }
+        if (ctx->pair3d) {  // (fp32 contexts only, plan_context)
+            pair3d_table(*ctx, idx, n, &pt);
+            for (Pair3dInj &e : pt.ent) e.cu = (float)cu[e.col];
+        }
+
+        const size_t sb = st.start.size() * sizeof(int);
+        if ((rcode = ensure(ctx, ps.s_start, sb))) return rcode;
+        HIPCHK(ctx, up(ps.s_start.p, st.start.data(), sb));
+        HIPCHK(ctx, up(ps.s_pidx, st.pidx.data(), (size_t)n * 8));
+        HIPCHK(ctx, up(ps.s_cidx, st.cidx.data(), (size_t)n * 8));
+        HIPCHK(ctx, up(ps.s_cu, scu.data(), (size_t)n * sizeof(T)));
+        HIPCHK(ctx, up(ps.s_cq, scq.data(), (size_t)n * sizeof(T)));
+        HIPCHK(ctx, up(ps.s_col, st.col.data(), (size_t)n * sizeof(int)));
+        HIPCHK(ctx, up(ps.s_run, st.run.data(), (size_t)n * sizeof(int)));
+        if (ctx->fused2d) {
+            const size_t ne = ft.col.size(), nr = ft.rcol.size();
+            const size_t fneed = ne * 8 + 16, sneed = ft.start.size() * sizeof(int);
             if ((rcode = ensure_all(ctx, ps.member, 11, {&ps.fi_lz, &ps.fi_lx, &ps.fi_col, &ps.fi_int, &ps.fi_cidx, &ps.fi_cu,
                                                          &ps.fi_cq, &ps.fi_run, &ps.fr_lz, &ps.fr_lx, &ps.fr_col},
                                     &ps.fcap, fneed)) ||
                 (rcode = ensure_all(ctx, ps.member, 22, {&ps.fi_start, &ps.fr_start}, &ps.fcap_start, sneed)))
                 return rcode;
-            HIPCHK(ctx, up(ps.fi_start, fst.data(), sneed));
-            HIPCHK(ctx, up(ps.fr_start, rst.data(), sneed));
-            HIPCHK(ctx, up(ps.fi_lz, flz.data(), ne * sizeof(int)));
-            HIPCHK(ctx, up(ps.fi_lx, flx.data(), ne * sizeof(int)));
-            HIPCHK(ctx, up(ps.fi_col, fcol.data(), ne * sizeof(int)));
-            HIPCHK(ctx, up(ps.fi_int, fint.data(), ne));
+            HIPCHK(ctx, up(ps.fi_start, ft.start.data(), sneed));
+            HIPCHK(ctx, up(ps.fr_start, ft.rstart.data(), sneed));
+            HIPCHK(ctx, up(ps.fi_lz, ft.lz.data(), ne * sizeof(int)));
+            HIPCHK(ctx, up(ps.fi_lx, ft.lx.data(), ne * sizeof(int)));
+            HIPCHK(ctx, up(ps.fi_col, ft.col.data(), ne * sizeof(int)));
+            HIPCHK(ctx, up(ps.fi_int, ft.interior.data(), ne));
             HIPCHK(ctx, up(ps.fi_cidx, fcidx.data(), ne * 8));
             HIPCHK(ctx, up(ps.fi_cu, fcu.data(), ne * sizeof(T)));
             HIPCHK(ctx, up(ps.fi_cq, fcq.data(), ne * sizeof(T)));
-            {
-                std::vector<int> frun(ne, 0);  // run length at the first entry of each (tile, node) run
-                for (int k = (int)ne - 1, len = 0; k >= 0; --k) {
-                    auto same = [&](int x, int y) {
-                        const Ent &ex = ents[order[x]], &ey = ents[order[y]];
-                        return ex.tile == ey.tile && ex.lz == ey.lz && ex.lx == ey.lx;
-                    };
-                    len = (k + 1 < (int)ne && same(k, k + 1)) ? len + 1 : 1;
-                    frun[k] = (k == 0 || !same(k - 1, k)) ? len : 0;
-                }
-                HIPCHK(ctx, up(ps.fi_run, frun.data(), ne * sizeof(int)));
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // frun goes out of scope
-            }
-            HIPCHK(ctx, up(ps.fr_lz, rlz.data(), rlz.size() * sizeof(int)));
-            HIPCHK(ctx, up(ps.fr_lx, rlx.data(), rlx.size() * sizeof(int)));
-            HIPCHK(ctx, up(ps.fr_col, rcol.data(), rcol.size() * sizeof(int)));
+            HIPCHK(ctx, up(ps.fi_run, ft.run.data(), ne * sizeof(int)));
+            HIPCHK(ctx, up(ps.fr_lz, ft.rlz.data(), nr * sizeof(int)));
+            HIPCHK(ctx, up(ps.fr_lx, ft.rlx.data(), nr * sizeof(int)));
+            HIPCHK(ctx, up(ps.fr_col, ft.rcol.data(), nr * sizeof(int)));
         }
-        std::vector<int> pst;
-        std::vector<Pair3dInj> pent;
-        if (ctx->pair3d) {
-            if constexpr (std::is_same<T, float>::value) {
-                // a point is injected by every workgroup whose step-1 region (tile widened by r) holds it
-                const int zc = ctx->pair_zc, tw = ctx->pair_tw, r = g.r, TYI = PAIR3D_TY;
-                const int nxt = g.nx <= 256 ? 1 : (g.nx + tw - 1) / tw;
-                const int nyt = (g.ny + TYI - 1) / TYI, nzc = (g.nz + zc - 1) / zc;
-                const int ntile = nxt * nyt * nzc;
-                std::vector<std::vector<Pair3dInj>> per(ntile);
-                for (int i = 0; i < n; ++i) {
-                    const int z = idx[(size_t)i * 3], y = idx[(size_t)i * 3 + 1], x = idx[(size_t)i * 3 + 2];
-                    for (int bz = std::max(0, (z - r) / zc - 1); bz < nzc; ++bz) {
-                        const int z0 = bz * zc, z1 = std::min(g.nz, z0 + zc);
-                        if (z < z0 - r || z >= z1 + r) continue;
-                        for (int by = std::max(0, (y - r) / TYI - 1); by < nyt; ++by) {
-                            const int y0 = by * TYI;
-                            if (y < y0 - r || y >= y0 + TYI + r) continue;
-                            for (int bx = 0; bx < nxt; ++bx) {
-                                const int xi0 = bx * tw, xbase = nxt == 1 ? 0 : xi0 - 2 * HALO;
-                                if (nxt > 1 && (x < xi0 - r || x >= xi0 + tw + r)) continue;
-                                const bool own = z >= z0 && z < z1 && y >= y0 && y < y0 + TYI &&
-                                                 (nxt == 1 || (x >= xi0 && x < xi0 + tw));
-                                per[(bz * nyt + by) * nxt + bx].push_back(
-                                    Pair3dInj{z, y - y0, x - xbase, i, (float)cu[i], own ? 1 : 0});
-                            }
-                        }
-                    }
-                }
-                pst.assign(ntile + 1, 0);
-                for (int k = 0; k < ntile; ++k) {
-                    pst[k + 1] = pst[k] + (int)per[k].size();
-                    pent.insert(pent.end(), per[k].begin(), per[k].end());
-                }
-                const size_t sb = pst.size() * sizeof(int), eb = pent.size() * sizeof(Pair3dInj) + 16;
-                if ((rcode = ensure(ctx, ps.pr_start, sb)) || (rcode = ensure(ctx, ps.pr_ent, eb))) return rcode;
-                HIPCHK(ctx, up(ps.pr_start.p, pst.data(), sb));
-                HIPCHK(ctx, up(ps.pr_ent.p, pent.data(), pent.size() * sizeof(Pair3dInj)));
-            }
+        if (ctx->pair3d) {  // (fp32 contexts only, plan_context)
+            const size_t pb = pt.start.size() * sizeof(int), eb = pt.ent.size() * sizeof(Pair3dInj);
+            if ((rcode = ensure(ctx, ps.pr_start, pb)) || (rcode = ensure(ctx, ps.pr_ent, eb + 16))) return rcode;
+            HIPCHK(ctx, up(ps.pr_start.p, pt.start.data(), pb));
+            HIPCHK(ctx, up(ps.pr_ent.p, pt.ent.data(), eb));
         }
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // host vectors go out of scope
         ps.n = n;
@@ -1993,25 +1862,22 @@ int fwi_forward(fwi_ctx *ctx, int32_t nt, int32_t nsrc, const int32_t *src_idx, 
 static int set_spread(fwi_ctx *ctx, fwi_ctx::SpreadSet &sp, int32_t npts, int32_t nnodes, const int32_t *pt_start,
                       const void *weight, const char *what) {
     sp.npts = 0;
-    if (npts < 0 || (npts > 0 && (!pt_start || !weight)))
-        return ctx->fail(FWI_EINVAL, "fwi_forward_spread: bad %s point set", what);
-    if (npts == 0) {
-        if (nnodes != 0) return ctx->fail(FWI_EINVAL, "fwi_forward_spread: %s nodes without points", what);
-        return FWI_OK;
+    const SpreadOwners so = spread_owners(npts, nnodes, pt_start, weight != nullptr);
+    switch (so.check) {
+        case SPREAD_OK: break;
+        case SPREAD_BAD_SET: return ctx->fail(FWI_EINVAL, "fwi_forward_spread: bad %s point set", what);
+        case SPREAD_NODES_WITHOUT_POINTS: return ctx->fail(FWI_EINVAL, "fwi_forward_spread: %s nodes without points", what);
+        case SPREAD_BAD_RANGE:
+            return ctx->fail(FWI_EINVAL, "fwi_forward_spread: %s pt_start must run from 0 to the node count", what);
+        case SPREAD_BAD_COUNT:
+            return ctx->fail(FWI_EINVAL, "fwi_forward_spread: %s point %d has %d nodes (0..8 allowed)", what, so.point,
+                             so.count);
     }
-    std::vector<int> owner((size_t)nnodes);
-    if (pt_start[0] != 0 || pt_start[npts] != nnodes)
-        return ctx->fail(FWI_EINVAL, "fwi_forward_spread: %s pt_start must run from 0 to the node count", what);
-    for (int p = 0; p < npts; ++p) {
-        const int a = pt_start[p], b = pt_start[p + 1];
-        if (b < a || b - a > 8)
-            return ctx->fail(FWI_EINVAL, "fwi_forward_spread: %s point %d has %d nodes (0..8 allowed)", what, p, b - a);
-        for (int m = a; m < b; ++m) owner[m] = p;
-    }
+    if (npts == 0) return FWI_OK;
     const size_t need = (size_t)std::max(nnodes, npts + 1) * 8 + 16;
     if (int rc = ensure_all(ctx, sp.member, 0, {&sp.pt_start, &sp.owner, &sp.weight}, &sp.cap, need)) return rc;
     HIPCHK(ctx, hipMemcpyAsync(sp.pt_start, pt_start, (size_t)(npts + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(sp.owner, owner.data(), (size_t)nnodes * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(sp.owner, so.owner.data(), (size_t)nnodes * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(sp.weight, weight, (size_t)nnodes * ctx->esize, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // `owner` goes out of scope
     sp.npts = npts;

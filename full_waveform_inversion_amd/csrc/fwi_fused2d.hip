@@ -111,7 +111,7 @@ __global__ __launch_bounds__(fused2d_threads(FT)) void step2d_fused(Fused2dArgs 
     }
     // (walking 4 x 4 blocks of tiles inside the run, so that an XCD owns a 4 x 8 patch instead of a 2 x 16 strip,
     // was measured and rejected: 2.83 vs 2.69 us/step)
-    const int tz = tile / ntx, tx = tile % ntx;
+    const int tz = tile / ntx, tx = tile % ntx;  // (the host's side of this decode: fused2d_tables, fwi_points.cpp)
     const int z0 = tz * FT - HL, x0 = tx * FT - HL;  // grid coordinates of extended (0, 0)
 
     // ---- load: zero outside the grid.  x0 and the 4-cell pad are multiples of 4, so a group is either left of

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(1024) void step2d_fused_cpml(Fused2dArgs a, GridDes
         const int nblk = gridDim.x, x = tile & 7, q = nblk >> 3, r = nblk & 7;
         tile = x * q + min(x, r) + (tile >> 3);
     }
-    const int tz = tile / ntx, tx = tile % ntx;
+    const int tz = tile / ntx, tx = tile % ntx;  // (the host's side of this decode: fused2d_tables, fwi_points.cpp)
     // whole tiles with one overlap seam per axis (fused2d_origin); a tile stores from its first OWNED cell on
     const int z0 = fused2d_origin(tz, g.nz, FT, 1) - HL, x0 = fused2d_origin(tx, g.nx, FT, 1) - HL;  // extended (0, 0)
     const int own_lz = fused2d_own(tz, g.nz, FT, 1) - z0, own_l4 = (fused2d_own(tx, g.nx, FT, 1) - x0) >> 2;  // (>= HL, HL / 4)

@@ -138,7 +138,9 @@ struct fwi_ctx : fwi::Plan {
                             // source-side series into the same buffer)
     bool have_dev_residual = false;  // ctx->amp holds the residual fwi_misfit_l2 formed on the device
     // A point set on the device: original order (sampling, POINT-kernel injection) and the
-    // copy sorted by stream-kernel tile with its CSR offsets (fused injection).
+    // copy sorted by stream-kernel tile with its CSR offsets (fused injection).  The tables are built on the host by
+    // fwi_points.h (StepTable, Fused2dTables, Pair3dTable), which knows no device; Impl<T>::upload_set permutes the typed
+    // coefficients by each table's `col` and uploads them, on every forward call.
     struct PointSet {
         const char *member;  // "src" / "rec": what the set's arrays are recorded as (indices 0 ... 25, in upload_set's order)
         explicit PointSet(const char *m = "") : member(m), s_start(m, 10), pr_start(m, 24), pr_ent(m, 25) {}
@@ -159,7 +161,8 @@ struct fwi_ctx : fwi::Plan {
     } src{"src"}, rec{"rec"};
     // Off-grid points of the last forward (fwi_forward_spread): per point set the CSR over points, the owner of
     // every node entry and its interpolation weight; time series cross the boundary per POINT and are scattered /
-    // gathered on the device.  npts = 0: node-based call.
+    // gathered on the device.  npts = 0: node-based call.  (set_spread; the set's checks and the owner table: spread_owners,
+    // fwi_points.h)
     struct SpreadSet {
         const char *member;
         int npts = 0;

@@ -1,5 +1,7 @@
 // Internal launch interface between the C-ABI (fwi_api.hip) and the gfx950
 // kernels (fwi_kernels.hip).  Not part of the public boundary (include/fwi.h).
+// The point tables the kernels read (inj_* / rec_* below) are built by fwi_points.h on the host, from the plan alone: which
+// workgroup tile owns a point is decided there, against each kernel's block decode.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,7 +51,8 @@ struct StepArgs {
 
     // Point operations fused into the step kernels (all nullptr / 0 = none).
     // Injection into u_next (and q_out): entries sorted by workgroup tile,
-    // inj_start[tile] .. inj_start[tile + 1] is the tile's slice.
+    // inj_start[tile] .. inj_start[tile + 1] is the tile's slice (step_table, fwi_points.h: the tile of a point is
+    // stream_tile_of / point_tile_of there, which must match the kernel's block decode).
     const int *inj_start;
     const int64_t *inj_pidx, *inj_cidx;  // padded / compact flat index per entry
     const T *inj_cu, *inj_cq;            // coefficient of the amplitude in u / in q
@@ -63,15 +66,6 @@ struct StepArgs {
     T rec_scale;
     int nrec;
 };
-
-// Workgroup tile of the stream kernel that owns grid point (z, y, x): the index
-// into StepArgs::inj_start.  Must match the kernel's block decode.
-int stream_tile_of(const GridDesc &g, const StreamTuning &t, int z, int y, int x);
-int stream_num_tiles(const GridDesc &g, const StreamTuning &t);
-
-// Same for the point kernel (64 x 4 point workgroups).
-int point_tile_of(const GridDesc &g, int z, int y, int x);
-int point_num_tiles(const GridDesc &g);
 
 template <typename T>
 hipError_t launch_step(int kernel, const GridDesc &g, const StepArgs<T> &a, const StreamTuning &t,
@@ -225,12 +219,6 @@ hipError_t launch_fused2d(const GridDesc &g, const Fused2dArgs &a, hipStream_t s
 hipError_t launch_fused2d_cpml(const GridDesc &g, const Fused2dArgs &a, hipStream_t s);
 
 // ---- 3-D temporal blocking (fwi_pair3d.hip): two time steps per pass, fp32, forward sweeps without imaging ----
-struct Pair3dInj {             // one source term as seen by one workgroup
-    int z, yoff, xoff;         // plane; row relative to the tile's first interior row; column relative to lane 0's
-    int col;                   // column of the amplitude rows
-    float cu;                  // coefficient of the amplitude in u
-    int interior;              // the point is one of the workgroup's own (then step 2 injects it too)
-};
 struct Pair3dArgs {
     const float *u_cur, *u_prev, *C;   // u^n, u^{n-1}, dt^2 c^2 (padded)
     float *out1, *out2;                // u^{n+1}, u^{n+2} (another buffer pair)
@@ -239,15 +227,13 @@ struct Pair3dArgs {
     int damp, npml;
     float dz_scale;
     const int *inj_start;              // CSR over workgroups (the kernel's renumbered order) into inj
-    const Pair3dInj *inj;
+    const Pair3dInj *inj;              // (fwi_plan.h)
     const float *inj_amp0, *inj_amp1;  // amplitude rows of step n and n + 1
     const int64_t *rec_pidx;           // sampling of the previous pass' two fields (u_prev -> out0, u_cur -> out1)
     float *rec_out0, *rec_out1;
     float rec_scale;
     int nrec;
 };
-int pair3d_num_tiles(const GridDesc &g, int zchunk, int tw);
-int pair3d_tile_of(const GridDesc &g, int zchunk, int tw, int z, int y, int x);
 hipError_t launch_pair3d(const GridDesc &g, const Pair3dArgs &a, int zchunk, int tw, hipStream_t s);
 
 // optimiser vector algebra: y = a x + b y; clamp (a NaN stays NaN); *out = max(*out, max|x|) (out zeroed by the caller;

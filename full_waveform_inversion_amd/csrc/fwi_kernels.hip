@@ -31,6 +31,7 @@ __global__ __launch_bounds__(256) void step_point(StepArgs<T> a, GridDesc g, int
             a.rec_out[i] = a.u_cur[a.rec_pidx[i]] * a.rec_scale;
         return;
     }
+    // (the host's side of this decode: point_tile_of, fwi_points.cpp)
     const int bx = blockIdx.x % nbx;
     const int t2 = blockIdx.x / nbx;
     const int x = bx * 64 + threadIdx.x;
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(64 * TY) void step2d_tile(StepArgs<float> a, GridDe
             a.rec_out[i] = a.u_cur[a.rec_pidx[i]] * a.rec_scale;
         return;
     }
-    const int bx = bid % nxt, bz = bid / nxt;
+    const int bx = bid % nxt, bz = bid / nxt;  // (the host's side of this decode: stream_tile_of, fwi_points.cpp)
     const int x0 = bx * TILE_X + 4 * lane;
     const int z0 = bz * TY, z = z0 + ty;
     const bool act = (x0 < g.nx) && (z < g.nz);
@@ -221,19 +222,6 @@ __global__ __launch_bounds__(64 * TY) void step2d_tile(StepArgs<float> a, GridDe
     }
 }
 
-int stream_tile_of(const GridDesc &g, const StreamTuning &t, int z, int y, int x) {
-    const int nxt = stream_nxt(g, t.tile_x);
-    if (g.ndim == 2) return (z / t.ty) * nxt + x / t.tile_x;
-    const int nyt = (g.ny + t.ty - 1) / t.ty;
-    return ((z / t.zchunk) * nyt + y / t.ty) * nxt + x / t.tile_x;
-}
-
-int stream_num_tiles(const GridDesc &g, const StreamTuning &t) {
-    const int nxt = stream_nxt(g, t.tile_x);
-    if (g.ndim == 2) return nxt * ((g.nz + t.ty - 1) / t.ty);
-    return nxt * ((g.ny + t.ty - 1) / t.ty) * ((g.nz + t.zchunk - 1) / t.zchunk);
-}
-
 template <typename T>
 static hipError_t launch_stream(const GridDesc &g, const StepArgs<T> &a, const StreamTuning &t, hipStream_t s) {
     switch (g.r) {
@@ -281,18 +269,6 @@ static inline void point_blocks(const GridDesc &g, int &nbx, int &nby, int &nblk
     nbx = (g.nx + 63) / 64;
     nby = (g.ndim == 3) ? (g.ny + 3) / 4 : (g.nz + 3) / 4;
     nblk = nbx * nby * ((g.ndim == 3) ? g.nz : 1);
-}
-
-int point_tile_of(const GridDesc &g, int z, int y, int x) {
-    int nbx, nby, nblk;
-    point_blocks(g, nbx, nby, nblk);
-    return (g.ndim == 3) ? (z * nby + y / 4) * nbx + x / 64 : (z / 4) * nbx + x / 64;
-}
-
-int point_num_tiles(const GridDesc &g) {
-    int nbx, nby, nblk;
-    point_blocks(g, nbx, nby, nblk);
-    return nblk;
 }
 
 template <typename T, int R, int NDIM>
@@ -380,7 +356,7 @@ __device__ __forceinline__ T q_elem(const T *q, int64_t i, int bf16) {
 }
 
 // g[x_s] += sum_n mu^{n+1}(x_s) * cq_s * w^n_s: the part of the imaging term that is the source itself (bf16 store).
-// One thread per NODE, over the copy of the source set sorted by node (upload_set: the entries of a node are consecutive,
+// One thread per NODE, over the copy of the source set sorted by node (step_table, fwi_points.h: the entries of a node are consecutive,
 // `run` holds their number at the first of them and 0 at the others, `col` the entry's column of the series): the shares
 // of the sources that sit on one node are added in that order, as the injection adds them, and by a plain store -- an
 // atomicAdd per source left the order of two such sources, and with it the last bit of the gradient there, to the hardware.

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64 * PAIR3D_TY) void step3d_pair(Pair3dArgs a, Grid
         const int x = bid & 7, q = nblk >> 3, r = nblk & 7;
         bid = x * q + min(x, r) + (bid >> 3);
     }
-    const int bx = bid % nxt;
+    const int bx = bid % nxt;  // (the host's side of this decode: pair3d_table, fwi_points.cpp)
     const int t2 = bid / nxt;
     const int by = t2 % nyt, bz = t2 / nyt;
     const bool fullrow = nxt == 1;          // the row is one tile: its ends are the grid boundary
@@ -271,18 +271,6 @@ __global__ __launch_bounds__(64 * PAIR3D_TY) void step3d_pair(Pair3dArgs a, Grid
             cring[(ph + 1) % NRING] = cnext;  // C(s + 1) takes the slot C(s - R) has just left
         }
     }
-}
-
-int pair3d_num_tiles(const GridDesc &g, int zchunk, int tw) {
-    const int nxt = g.nx <= 256 ? 1 : (g.nx + tw - 1) / tw;
-    return nxt * ((g.ny + PAIR3D_TY - 1) / PAIR3D_TY) * ((g.nz + zchunk - 1) / zchunk);
-}
-
-// workgroup (in the kernel's renumbered order) that owns interior point (z, y, x)
-int pair3d_tile_of(const GridDesc &g, int zchunk, int tw, int z, int y, int x) {
-    const int nxt = g.nx <= 256 ? 1 : (g.nx + tw - 1) / tw;
-    const int nyt = (g.ny + PAIR3D_TY - 1) / PAIR3D_TY;
-    return ((z / zchunk) * nyt + y / PAIR3D_TY) * nxt + (nxt == 1 ? 0 : x / tw);
 }
 
 template <int R>

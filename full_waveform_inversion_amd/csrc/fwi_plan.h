@@ -114,6 +114,12 @@ bool fused2d_cpml_supported(const GridDesc &g, int npml);
 // ---- 3-D temporal blocking (fwi_pair3d.hip): two time steps per pass, fp32, forward sweeps without imaging ----
 constexpr int PAIR3D_TY = 8;   // interior rows (= waves) per workgroup
 void pair3d_default_tuning(const GridDesc &g, int *zchunk, int *tw);
+struct Pair3dInj {             // one source term as seen by one workgroup (built by pair3d_table, fwi_points.h)
+    int z, yoff, xoff;         // plane; row relative to the tile's first interior row; column relative to lane 0's
+    int col;                   // column of the amplitude rows
+    float cu;                  // coefficient of the amplitude in u
+    int interior;              // the point is one of the workgroup's own (then step 2 injects it too)
+};
 
 // FWI_PLACEMENT_TUNE=fixed:<k0>,<k1>,... : one to eight offsets in units of 2 MiB, each within the
 // 14 MiB of slack (0 ... 7); the last one repeats for the arrays that are not listed

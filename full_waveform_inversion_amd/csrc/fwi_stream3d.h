@@ -86,7 +86,7 @@ __global__ __launch_bounds__(64 * TY) void step3d_stream(StepArgs<T> a, GridDesc
         bid = x * q + min(x, r) + (bid >> 3);
     }
     zchunk = abs(zchunk);  // (a negative zchunk is the tuning hook that switches the renumbering off)
-    const int bx = bid % nxt;
+    const int bx = bid % nxt;  // (the host's side of this decode: stream_tile_of, fwi_points.cpp)
     const int t2 = bid / nxt;
     const int by = t2 % nyt, bz = t2 / nyt;
     // x tiles are `tw` columns wide (a multiple of VL, <= TX): the host splits nx into equal tiles, so

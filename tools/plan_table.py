@@ -83,14 +83,20 @@ def record(case, lib):
     return dict(rc=rc, error=error, line=line, kernel=name, offsets=offsets)
 
 
-def build_host_program(out_dir):
-    exe = os.path.join(out_dir, "plan_host")
+def build_host_program(out_dir, name="plan_host", units=("fwi_plan.cpp",)):
+    """tests/<name>.cpp over the host-only ``units`` of csrc/, with the address and undefined-behaviour sanitizers."""
+    exe = os.path.join(out_dir, name)
     csrc = os.path.join(ROOT, "full_waveform_inversion_amd", "csrc")
     # (the sanitizers' runtimes inside the program: it then runs as it is, whatever else the loader brings along)
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-static-libasan",
-                           "-static-libubsan", "-g", "-I", csrc, os.path.join(ROOT, "tests", "plan_host.cpp"),
-                           os.path.join(csrc, "fwi_plan.cpp"), "-o", exe])
+                           "-static-libubsan", "-g", "-I", csrc, os.path.join(ROOT, "tests", name + ".cpp")] +
+                          [os.path.join(csrc, u) for u in units] + ["-o", exe])
     return exe
+
+
+def build_points_program(out_dir):
+    """tests/points_host.cpp: a shot's point tables (csrc/fwi_points.cpp) on the CPU; tests/test_points_host.py runs it."""
+    return build_host_program(out_dir, "points_host", ("fwi_plan.cpp", "fwi_points.cpp"))
 
 
 def run_host_program(exe, cases, env, fixed):
